@@ -27,7 +27,8 @@ import numpy as np  # noqa: E402
 
 RAMP_S = 0.25                  # untimed renders before --warmup (reported as "ramp_s" / "ramp_steps")
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
-DEJAVU = "/usr/local/lib/python3.10/dist-packages/matplotlib/mpl-data/fonts/ttf/DejaVuSerif-Italic.ttf"
+DEJAVU = "DejaVuSerif-Italic.ttf"       # tests/golden/fonts/ (fixtures.load_font)
+DUMP_BYTES = 60_000_000        # --dump-outputs: at most this many bytes of .npy payload in all
 
 WORKLOADS = {
     # BASELINE.json configs[2]: the largest single-GPU configuration (~21k CJK-like glyphs) — the headline
@@ -82,8 +83,8 @@ def build_inputs(wl, rank, lo, hi):
     from font_renderer_amd.synth import stroke_glyphset, synth_glyphset
     cell, cols, gen = wl["cell"], wl["cols"], wl.get("gen", "synth")
     if gen == "font_dims":
-        import font_renderer_amd as fr
-        font = fr.Font.initTTF(wl["font"])
+        import fixtures
+        font = fixtures.load_font(wl["font"])
         gs, kept = font.glyphset()
         upm = font.information.units_per_em
         W = wl["atlas_w"]
@@ -95,8 +96,8 @@ def build_inputs(wl, rank, lo, hi):
             parts.append(jb)
         return gs, np.concatenate(parts), (y, W)
     if gen == "font":
-        import font_renderer_amd as fr
-        font = fr.Font.initTTF(wl["font"])
+        import fixtures
+        font = fixtures.load_font(wl["font"])
         gs, kept = font.glyphset()
         upm = font.information.units_per_em
         sizes = [int(cell * f) for f in wl.get("size_factors", (1.0, 0.9, 0.8, 0.7, 0.6, 0.5))]
@@ -126,6 +127,27 @@ def build_inputs(wl, rank, lo, hi):
     return gs, cell_jobs(gs, cell, cell, 2048, cols), atlas_shape(hi - lo, cell, cols)
 
 
+def dump_outputs(d, out, stream, rank, world):
+    """--dump-outputs: the atlas (band) the last timed step left in `out`, as float32 .npy files under d.  Whole when it
+    fits DUMP_BYTES / world; otherwise a fixed, seeded sample of whole rows (np.random.default_rng(0), sorted) written as
+    atlas_rows.npy with the row numbers beside it in atlas_row_index.npy (float64).  The sample depends only on the
+    atlas shape, so two builds run with the same arguments dump the same pixels."""
+    import torch
+    os.makedirs(d, exist_ok=True)
+    tag = f"_rank{rank}" if world > 1 else ""
+    H, W = out.shape
+    budget = DUMP_BYTES // world
+    with torch.cuda.stream(stream):
+        if H * W * 4 <= budget:
+            np.save(os.path.join(d, f"atlas{tag}.npy"), out.float().cpu().numpy())
+            return
+        k = max(1, min(H, budget // (W * 4 + 8)))
+        rows = np.sort(np.random.default_rng(0).choice(H, k, replace=False))
+        sel = out.index_select(0, torch.from_numpy(rows).to(out.device)).float().cpu().numpy()
+    np.save(os.path.join(d, f"atlas_rows{tag}.npy"), sel)
+    np.save(os.path.join(d, f"atlas_row_index{tag}.npy"), rows.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -141,7 +163,12 @@ def main():
     ap.add_argument("--n", type=int, default=0, help="override samples per axis (experiments)")
     ap.add_argument("--segs", type=int, default=0, help="override segments per glyph (experiments)")
     ap.add_argument("--opt", action="append", default=[], help="library tuning knob key=value (experiments)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the atlas the last timed step rendered to DIR/*.npy (float32; "
+                         "a fixed row sample when the whole atlas exceeds the size cap)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -265,6 +292,8 @@ def main():
         p = torch.tensor([pixels], dtype=torch.int64, device=dev)
         dist.all_reduce(p, op=dist.ReduceOp.SUM)
         tot_pixels = int(p.item())
+    if args.dump_outputs:                                    # before anything else renders into `out`
+        dump_outputs(args.dump_outputs, out, stream, rank, world)
     ms_per_step = dt / args.steps * 1e3
     value = tot_pixels / (dt / args.steps) / 1e6            # Mpixel/s, whole job
 
@@ -394,7 +423,7 @@ def main():
             "metric": "Mpixel/s AA glyph coverage", "value": round(value, 1), "unit": "Mpixel/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
             "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic" if wl.get("gen", "synth") in ("synth", "stroke") else "real font outlines (matplotlib's DejaVuSerif-Italic / the committed ASCII fixture), random-free",
+            "data": "synthetic" if wl.get("gen", "synth") in ("synth", "stroke") else "real font outlines (the committed DejaVuSerif-Italic / ASCII fixture), random-free",
             "ramp_s": RAMP_S, "ramp_steps": ramp_steps,
             "config": {"workload": args.workload, "cells_per_gpu": G, "glyphs_in_set": len(gs),
                        "cell": f"{cell}x{cell}" if cell else f"renderGlyph's own image per glyph (render_glyph.zig:14-19), font sizes {list(wl['sizes'])}",

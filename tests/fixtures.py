@@ -1,4 +1,9 @@
-"""Loads tests/golden/ascii_glyphs.npz (numpy.load, no pickle) into Glyph objects."""
+"""Loads tests/golden/ascii_glyphs.npz (numpy.load, no pickle) into Glyph objects, and the
+TrueType fonts committed under tests/golden/fonts/ (xz-compressed; DejaVu: Bitstream Vera
+licence, STIX: OFL — the licence texts sit beside them)."""
+import functools
+import io
+import lzma
 import os
 
 import numpy as np
@@ -6,6 +11,25 @@ import numpy as np
 from font_renderer_amd.glyph import Box, Contour, Glyph, GlyphSet
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+FONTS = os.path.join(GOLDEN, "fonts")
+
+
+@functools.lru_cache(maxsize=None)
+def font_bytes(name: str) -> bytes:
+    """the file bytes of tests/golden/fonts/<name> (e.g. "DejaVuSerif-Italic.ttf")"""
+    with lzma.open(os.path.join(FONTS, name + ".xz"), "rb") as f:
+        return f.read()
+
+
+def font_file(name: str) -> io.BytesIO:
+    """a file object over font_bytes(name), for parsers that want one (fontTools' TTFont)"""
+    return io.BytesIO(font_bytes(name))
+
+
+def load_font(name: str, allow_hinted: bool = False):
+    """fr.Font over a committed font (Font.initTTF without a path)"""
+    import font_renderer_amd as fr
+    return fr.Font(font_bytes(name), allow_hinted)
 
 
 class AsciiSet:

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Mint the real-outline fixture tests/golden/ascii_glyphs.npz.
 
-Run in the build container only (needs fontTools + matplotlib's bundled fonts);
+Run on the build host only (needs fontTools; reads the fonts committed under tests/golden/fonts/);
 the GPU box and the tests only read the committed .npz (numpy.load, no pickle).
 
 What is stored, per glyph (95 printable ASCII x 2 unhinted fonts the reference
@@ -15,13 +15,14 @@ itself would accept — Glyph.zig:85 panics on glyphs that carry instructions):
 The fonts are data inputs (DejaVu: Bitstream-Vera licence, STIX: OFL); nothing of
 the reference is copied or executed.
 """
+import lzma
 import os
 import sys
 
 import numpy as np
 from fontTools.ttLib import TTFont
 
-FONT_DIR = "/usr/local/lib/python3.10/dist-packages/matplotlib/mpl-data/fonts/ttf"
+FONT_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "fonts")      # <name>.xz
 FONTS = ["STIXGeneral.ttf", "DejaVuSerif-Italic.ttf"]
 
 
@@ -59,7 +60,7 @@ def main(out_path):
     exp_pts, exp_cstart, g_cont_start = [], [0], [0]
     skipped = []
     for fi, fname in enumerate(FONTS):
-        font = TTFont(os.path.join(FONT_DIR, fname))
+        font = TTFont(lzma.open(os.path.join(FONT_DIR, fname + ".xz")))
         upm = font["head"].unitsPerEm
         cmap = font.getBestCmap()
         glyf = font["glyf"]

@@ -2,21 +2,16 @@
 SURVEY §8f-1 — against (1) the committed fixture and (2) an independent assembly: raw outlines
 from fontTools (a third-party parser, tooling only) pushed through the ORACLE's restatements of
 Contour.initTTF (Glyph.zig:43-74) and transform1 (Glyph.zig:178-182)."""
-import os
 
 import numpy as np
 import pytest
 
 import font_renderer_amd as fr
-
-FONT_DIR = "/usr/local/lib/python3.10/dist-packages/matplotlib/mpl-data/fonts/ttf"
+from fixtures import font_file, load_font
 
 
 def _font(name, **kw):
-    path = os.path.join(FONT_DIR, name)
-    if not os.path.exists(path):
-        pytest.skip(f"{path} not present")
-    return fr.Font.initTTF(path, **kw)
+    return load_font(name, **kw)                    # tests/golden/fonts/<name>.xz
 
 
 def test_producer_reproduces_fixture(ascii_set):
@@ -73,7 +68,7 @@ def test_whole_font_simple_and_composite_against_oracle(oracle):
     ft = pytest.importorskip("fontTools.ttLib")
     name = "DejaVuSerif-Italic.ttf"
     f = _font(name)
-    tt = ft.TTFont(os.path.join(FONT_DIR, name))
+    tt = ft.TTFont(font_file(name))
     glyf, order = tt["glyf"], tt.getGlyphOrder()
     raw = tt.reader["glyf"]
     loca = tt["loca"].locations
@@ -142,7 +137,7 @@ def test_cmap_lookup_matches_fonttools():
     ft = pytest.importorskip("fontTools.ttLib")
     for name in ("STIXGeneral.ttf", "DejaVuSerif-Italic.ttf"):
         f = _font(name)
-        tt = ft.TTFont(os.path.join(FONT_DIR, name))
+        tt = ft.TTFont(font_file(name))
         cmap, order = tt.getBestCmap(), tt.getGlyphOrder()
         gid = {n: i for i, n in enumerate(order)}
         for ch in list(range(0x20, 0x250)) + [0x3b1, 0x2202, 0x221e, 0xfb01, 0x1d49c]:
@@ -183,11 +178,8 @@ def test_advance_widths_follow_the_reference_reading_of_hmtx(name):
     which are left-side bearings in the TrueType layout.  fr_font_glyph_advance reproduces exactly that; checked against
     fontTools' independent parse of hhea / hmtx."""
     ft = pytest.importorskip("fontTools.ttLib")
-    path = os.path.join(FONT_DIR, name)
-    if not os.path.exists(path):
-        pytest.skip(f"{name} not in this image")
     f = _font(name, allow_hinted=True)
-    tt = ft.TTFont(path)
+    tt = ft.TTFont(font_file(name))
     order, hmtx, n_long = tt.getGlyphOrder(), tt["hmtx"], tt["hhea"].numberOfHMetrics
     assert f.num_glyphs == len(order)
     for gi, gname in enumerate(order):

@@ -7,6 +7,7 @@ import pytest
 
 import font_renderer_amd as fr
 import oracle_lib as O
+from fixtures import load_font
 from font_renderer_amd import render_glyph as rg
 from font_renderer_amd.atlas import atlas_shape, cell_jobs
 from font_renderer_amd.glyph import Box, Contour, Glyph, GlyphSet
@@ -496,6 +497,7 @@ def test_exact_integer_path(ctx, oracle, ascii_set):
     gg = gs.glyph(0)
     qq = np.stack(np.meshgrid(np.arange(60, 2000, 37), np.arange(60, 2000, 41)), -1).reshape(-1, 2).astype(np.int16)
     assert np.array_equal(fr.windingInGlyph(gg, None, qq, ctx=ctx), oracle.winding_in_glyph(gg, qq))
+    oracle.diag_reset()                   # the counters are process-wide: later tests check their own calls against 0
 
 
 def test_exact_lattice_k_and_coverage(ctx, oracle, ascii_set):
@@ -526,6 +528,7 @@ def test_exact_lattice_k_and_coverage(ctx, oracle, ascii_set):
     assert got.max() == 255 and got.min() == 0
     with pytest.raises(fr.FrError):
         fr.exact_lattice(g, 9, 0, 0, 4, 4, ctx=ctx)          # K > 8 could leave the 128-bit range
+    oracle.diag_reset()                   # K > 1 leaves the i64 domain on purpose; later tests check their own calls against 0
 
 
 def test_full_size_properties_config3(ctx):
@@ -790,11 +793,7 @@ def test_whole_font_from_the_c_side_producer(ctx, oracle):
     """SURVEY §8f-1 end to end: TrueType bytes -> fr_font_* (C++ contour producer) -> glyph set ->
     one atlas of every glyph the reference could load (DejaVuSerif-Italic: ~3 000 glyphs incl.
     composites), 16 samples/pixel; 48 random cells against the oracle."""
-    import os
-    path = "/usr/local/lib/python3.10/dist-packages/matplotlib/mpl-data/fonts/ttf/DejaVuSerif-Italic.ttf"
-    if not os.path.exists(path):
-        pytest.skip("font not present")
-    font = fr.Font.initTTF(path)
+    font = load_font("DejaVuSerif-Italic.ttf")             # tests/golden/fonts/
     gs, kept = font.glyphset()
     assert len(kept) > 3000
     cell, cols = 48, 64

@@ -9,6 +9,7 @@ import pytest
 
 import font_renderer_amd as fr
 import oracle_lib as O
+from fixtures import load_font
 from font_renderer_amd import render_glyph as rg
 from font_renderer_amd.atlas import atlas_shape, cell_jobs, glyph_dims_jobs
 from font_renderer_amd.glyph import Box, Contour, Glyph, GlyphSet
@@ -188,12 +189,8 @@ def test_full_size_properties_config5_shard_of_the_real_font(ctx, oracle):
     """BASELINE configs[4] as stated — per-pixel SDF at 512 x 512 per glyph, whole font — at one GPU's share of
     DejaVuSerif-Italic through the C-side producer (the first 384 loadable glyphs): deterministic (two renders equal),
     8 sub-shards == unsharded, culls on == culls off, four cells == the CPU twin."""
-    import os
     import torch
-    path = "/usr/local/lib/python3.10/dist-packages/matplotlib/mpl-data/fonts/ttf/DejaVuSerif-Italic.ttf"
-    if not os.path.exists(path):
-        pytest.skip("DejaVuSerif-Italic.ttf not in this image")
-    font = fr.Font.initTTF(path)
+    font = load_font("DejaVuSerif-Italic.ttf")             # tests/golden/fonts/
     gs_all, kept = font.glyphset()
     G, cell, cols = 384, 512, 16
     gs = gs_all.subset(0, G)
@@ -263,12 +260,8 @@ def test_whole_font_at_renderglyph_sizes_properties(ctx, oracle):
     """the reference's literal product on a whole real font (every loadable glyph of DejaVuSerif-Italic through the C-side
     producer, three font sizes, ~9 400 images shelf-packed): nothing on the general kernel, two renders equal, the bytes
     around the images untouched, and 90 images spread over the batch == the oracle (gray map and 16-sample coverage)."""
-    import os
     import torch
-    path = "/usr/local/lib/python3.10/dist-packages/matplotlib/mpl-data/fonts/ttf/DejaVuSerif-Italic.ttf"
-    if not os.path.exists(path):
-        pytest.skip("DejaVuSerif-Italic.ttf not in this image")
-    font = fr.Font.initTTF(path)
+    font = load_font("DejaVuSerif-Italic.ttf")             # tests/golden/fonts/
     gs, kept = font.glyphset()
     upm = font.information.units_per_em
     parts, y, W = [], 0, 4099
