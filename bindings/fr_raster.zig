@@ -27,6 +27,8 @@ pub const Status = enum(c_int) { ok = 0, invalid = -1, hip = -2, nomem = -3, uns
 pub const Mode = enum(i32) { winding_i16 = 0, gray_debug = 1, mask_nonzero = 2, coverage_u8 = 3, sdf_u8 = 4 };
 pub const SamplePhase = enum(i32) { corner = 0, center = 1 };
 pub const FR_FONT_ALLOW_HINTED: u32 = 1;
+/// crossing-rule flag of the _ex entry points (fr_raster.h: FR_FILL_CONSISTENT)
+pub const FR_FILL_CONSISTENT: u32 = 1;
 
 pub const RasterParams = extern struct {
     mode: i32,
@@ -61,6 +63,7 @@ pub extern "c" fn fr_glyphset_prepare(gs: *fr_glyphset) c_int;
 pub extern "c" fn fr_glyphset_stats(gs: *const fr_glyphset, n_segments: ?*u64, n_records: ?*u64) c_int;
 // ---- batched rasterization
 pub extern "c" fn fr_plan_create(ctx: *fr_ctx, gs: *const fr_glyphset, jobs: [*]const Job, n_jobs: u32, params: *const RasterParams, out: *?*fr_plan) c_int;
+pub extern "c" fn fr_plan_create_ex(ctx: *fr_ctx, gs: *const fr_glyphset, jobs: [*]const Job, n_jobs: u32, params: *const RasterParams, flags: u32, out: *?*fr_plan) c_int;
 pub extern "c" fn fr_plan_destroy(plan: ?*fr_plan) void;
 pub extern "c" fn fr_plan_render(plan: *fr_plan, out_dev: *anyopaque, out_stride: usize, out_rows: usize) c_int;
 pub extern "c" fn fr_plan_render_timed(plan: *fr_plan, out_dev: *anyopaque, out_stride: usize, out_rows: usize, ms: *f32) c_int;
@@ -70,9 +73,11 @@ pub extern "c" fn fr_plan_describe(plan: *const fr_plan, buf: [*]u8, cap: usize)
 pub extern "c" fn fr_allgather_bands(ctx: *fr_ctx, nccl_comm: *anyopaque, atlas_dev: *anyopaque, band_bytes: usize) c_int;
 pub extern "c" fn fr_gather_bands(ctx: *fr_ctx, nccl_comm: *anyopaque, atlas_dev: *anyopaque, band_bytes: usize, root: c_int) c_int;
 pub extern "c" fn fr_render_batch(ctx: *fr_ctx, gs: *const fr_glyphset, jobs: [*]const Job, n_jobs: u32, params: *const RasterParams, out_host: *anyopaque, out_stride: usize, out_rows: usize) c_int;
+pub extern "c" fn fr_render_batch_ex(ctx: *fr_ctx, gs: *const fr_glyphset, jobs: [*]const Job, n_jobs: u32, params: *const RasterParams, flags: u32, out_host: *anyopaque, out_stride: usize, out_rows: usize) c_int;
 // ---- renderGlyph drop-in
 pub extern "c" fn fr_render_glyph_dims(box: *const [4]i16, units_per_em: u16, font_size: u16, min_corner: *[2]i16, max_corner: *[2]i16, width: *u16, height: *u16, scale: ?*f32) c_int;
 pub extern "c" fn fr_render_glyph(ctx: *fr_ctx, points_xy: [*]const i16, contour_start: [*]const u32, n_contours: u32, box: *const [4]i16, units_per_em: u16, font_size: u16, mode: i32, out_host: *anyopaque) c_int;
+pub extern "c" fn fr_render_glyph_ex(ctx: *fr_ctx, points_xy: [*]const i16, contour_start: [*]const u32, n_contours: u32, box: *const [4]i16, units_per_em: u16, font_size: u16, mode: i32, flags: u32, out_host: *anyopaque) c_int;
 // ---- exact-integer path
 pub extern "c" fn fr_glyph_info_init(ctx: *fr_ctx, points_xy: [*]const i16, contour_start: [*]const u32, n_contours: u32, curve_type: [*]u8, include_p0: [*]u8) c_int;
 pub extern "c" fn fr_winding_in_glyph(ctx: *fr_ctx, points_xy: [*]const i16, contour_start: [*]const u32, n_contours: u32, query_xy: [*]const i16, n_query: u32, out_winding: [*]i16) c_int;

@@ -8,6 +8,7 @@ import os
 
 FR_WINDING_I16, FR_GRAY_DEBUG, FR_MASK_NONZERO, FR_COVERAGE_U8, FR_SDF_U8 = 0, 1, 2, 3, 4
 FR_SAMPLE_CORNER, FR_SAMPLE_CENTER = 0, 1
+FR_FILL_CONSISTENT = 1           # crossing-rule flag of the _ex entry points (include/fr_raster.h)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -50,6 +51,7 @@ SYMBOLS = [
     ("fr_glyphset_prepare", C.c_int, [_P]),
     ("fr_glyphset_stats", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("fr_plan_create", C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(RasterParams), C.POINTER(_P)]),
+    ("fr_plan_create_ex", C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(RasterParams), C.c_uint32, C.POINTER(_P)]),
     ("fr_plan_destroy", None, [_P]),
     ("fr_plan_render", C.c_int, [_P, _P, C.c_size_t, C.c_size_t]),
     ("fr_plan_render_timed", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, C.POINTER(C.c_float)]),
@@ -59,9 +61,11 @@ SYMBOLS = [
     ("fr_allgather_bands", C.c_int, [_P, _P, _P, C.c_size_t]),
     ("fr_gather_bands", C.c_int, [_P, _P, _P, C.c_size_t, C.c_int]),
     ("fr_render_batch", C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(RasterParams), _P, C.c_size_t, C.c_size_t]),
+    ("fr_render_batch_ex", C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(RasterParams), C.c_uint32, _P, C.c_size_t, C.c_size_t]),
     ("fr_render_glyph_dims", C.c_int, [_P, C.c_uint16, C.c_uint16, _P, _P, C.POINTER(C.c_uint16),
                                        C.POINTER(C.c_uint16), C.POINTER(C.c_float)]),
     ("fr_render_glyph", C.c_int, [_P, _P, _P, C.c_uint32, _P, C.c_uint16, C.c_uint16, C.c_int32, _P]),
+    ("fr_render_glyph_ex", C.c_int, [_P, _P, _P, C.c_uint32, _P, C.c_uint16, C.c_uint16, C.c_int32, C.c_uint32, _P]),
     ("fr_glyph_info_init", C.c_int, [_P, _P, _P, C.c_uint32, _P, _P]),
     ("fr_winding_in_glyph", C.c_int, [_P, _P, _P, C.c_uint32, _P, C.c_uint32, _P]),
     ("fr_winding_lattice", C.c_int, [_P, _P, _P, C.c_uint32, _P, _P]),

@@ -17,12 +17,13 @@
 #include <vector>
 
 namespace fr {
+// fill = 1: the FR_FILL_CONSISTENT instances (fr_records.hpp)
 void launch_prepare(const int16_t *, const uint32_t *, const uint32_t *, const uint32_t *, uint32_t, Rec *,
-                    uint32_t *, hipStream_t);
-hipError_t launch_render(const RenderArgs &, int mode, int n, hipStream_t, bool launch = true, char *name = nullptr, size_t name_cap = 0);
+                    uint32_t *, hipStream_t, int fill = 0);
+hipError_t launch_render(const RenderArgs &, int mode, int n, hipStream_t, bool launch = true, char *name = nullptr, size_t name_cap = 0, int fill = 0);
 uint32_t render_wg_waves();
-hipError_t launch_cov4(const RenderArgs &, uint32_t rec_cap, int ns, hipStream_t, bool launch = true, char *name = nullptr, size_t name_cap = 0);
-hipError_t launch_win1(const RenderArgs &, int mode1, uint32_t rec_cap, hipStream_t, bool launch = true, char *name = nullptr, size_t name_cap = 0);
+hipError_t launch_cov4(const RenderArgs &, uint32_t rec_cap, int ns, hipStream_t, bool launch = true, char *name = nullptr, size_t name_cap = 0, int fill = 0);
+hipError_t launch_win1(const RenderArgs &, int mode1, uint32_t rec_cap, hipStream_t, bool launch = true, char *name = nullptr, size_t name_cap = 0, int fill = 0);
 uint32_t cov4_wg_waves();
 uint32_t cov4_max_segments();
 hipError_t launch_sdf(const RenderArgs &, uint32_t, uint32_t, uint32_t max_seg, int cull, hipStream_t);
@@ -124,6 +125,7 @@ struct fr_plan {
     uint32_t gen_bands = 0, gen_strips = 0;
     bool gen_uniform = false;
     fr_raster_params params{};
+    uint32_t flags = 0;                // fr_plan_create_ex's flags (FR_FILL_CONSISTENT)
     uint32_t bands = 0, strips = 0, strip_w = 0, max_w = 0, max_h = 0;
     bool uniform = false;        // see fr_plan_create
     uint64_t pixels = 0, need_cols = 0, need_rows = 0;
@@ -529,11 +531,24 @@ void fr_plan_destroy(fr_plan *plan)
     delete plan;
 }
 
+static int check_flags(uint32_t flags)
+{
+    if (flags & ~(uint32_t)FR_FILL_CONSISTENT) return fail(FR_E_INVALID, "unknown flag bits 0x%x", flags & ~(uint32_t)FR_FILL_CONSISTENT);
+    return FR_OK;
+}
+
 int fr_plan_create(fr_ctx *ctx, const fr_glyphset *gs, const fr_job *jobs, uint32_t n_jobs,
                    const fr_raster_params *params, fr_plan **out)
 {
+    return fr_plan_create_ex(ctx, gs, jobs, n_jobs, params, 0u, out);
+}
+
+int fr_plan_create_ex(fr_ctx *ctx, const fr_glyphset *gs, const fr_job *jobs, uint32_t n_jobs,
+                      const fr_raster_params *params, uint32_t flags, fr_plan **out)
+{
     if (!ctx || !gs || !out) return fail(FR_E_INVALID, "fr_plan_create: NULL argument");
     *out = nullptr;
+    if (const int frc = check_flags(flags)) return frc;
     if (gs->ctx != ctx) return fail(FR_E_INVALID, "glyph set belongs to another context");
     int rc = check_params(params);
     if (rc) return rc;
@@ -562,7 +577,7 @@ int fr_plan_create(fr_ctx *ctx, const fr_glyphset *gs, const fr_job *jobs, uint3
     }
     fr_plan *p = new (std::nothrow) fr_plan;
     if (!p) return fail(FR_E_NOMEM, "fr_plan_create: host allocation");
-    p->ctx = ctx; p->gs = gs; p->n_jobs = n_jobs; p->params = *params;
+    p->ctx = ctx; p->gs = gs; p->n_jobs = n_jobs; p->params = *params; p->flags = flags;
     p->pixels = pixels; p->need_cols = need_cols; p->need_rows = need_rows;
     p->max_w = max_w; p->max_h = max_h;
     const uint32_t band = 64u / n;                                      // pixel rows per wave band
@@ -696,18 +711,19 @@ int fr_plan_describe(const fr_plan *plan, char *buf, size_t cap)
     a.kmax = plan->ctx->kmax;
     char name[96];
     const int pm = plan->params.mode;
+    const int fill = (plan->flags & FR_FILL_CONSISTENT) ? 1 : 0;
     for (const auto &pt : plan->parts) {
         a.strip_w = 16u << pt.wlog;
         name[0] = 0;
-        if (plan->fast_ns > 1) (void)fr::launch_cov4(a, pt.rec_cap, plan->fast_ns, nullptr, false, name, sizeof name);
-        else (void)fr::launch_win1(a, pm == FR_WINDING_I16 ? 0 : (pm == FR_GRAY_DEBUG ? 1 : (pm == FR_SDF_U8 ? 3 : 2)), pt.rec_cap, nullptr, false, name, sizeof name);
+        if (plan->fast_ns > 1) (void)fr::launch_cov4(a, pt.rec_cap, plan->fast_ns, nullptr, false, name, sizeof name, fill);
+        else (void)fr::launch_win1(a, pm == FR_WINDING_I16 ? 0 : (pm == FR_GRAY_DEBUG ? 1 : (pm == FR_SDF_U8 ? 3 : 2)), pt.rec_cap, nullptr, false, name, sizeof name, fill);
         add(name, pt.cnt);
     }
     if (plan->n_jobs > plan->n_fast) {
         a.strip_w = plan->strip_w; a.uniform = plan->uniform ? 1u : 0u;
         name[0] = 0;
-        if (pm == FR_SDF_U8) (void)fr::launch_render(a, FR_COVERAGE_U8, 1, nullptr, false, name, sizeof name);
-        else (void)fr::launch_render(a, pm, plan->params.samples_per_axis, nullptr, false, name, sizeof name);
+        if (pm == FR_SDF_U8) (void)fr::launch_render(a, FR_COVERAGE_U8, 1, nullptr, false, name, sizeof name, fill);
+        else (void)fr::launch_render(a, pm, plan->params.samples_per_axis, nullptr, false, name, sizeof name, fill);
         add(name, plan->n_jobs - plan->n_fast);
     }
     if (pm == FR_SDF_U8 && plan->n_jobs) add(plan->gs->max_seg_per_glyph > 64u ? "fr::sdf_kernel<true>" : "fr::sdf_kernel<false>", plan->n_jobs);
@@ -746,6 +762,7 @@ static int plan_launch_direct(fr_plan *plan, void *out_dev, size_t out_stride, s
     HIP_TRY(hipSetDevice(plan->ctx->device));
     const uint32_t n_fast = plan->n_fast, n_gen = plan->n_jobs - plan->n_fast;
     const bool sdf = plan->params.mode == FR_SDF_U8;
+    const int fill = (plan->flags & FR_FILL_CONSISTENT) ? 1 : 0;
     fr::RenderArgs a;
     a.glyph_seg_start = plan->gs->d_glyph_seg_start;
     a.glyph_rec_count = plan->gs->d_rec_count;
@@ -797,12 +814,17 @@ static int plan_launch_direct(fr_plan *plan, void *out_dev, size_t out_stride, s
     auto launch_parts = [&]() -> int {
     // a render always starts from the glyph POINTS: inside the kernels (fused) or by re-running the stand-alone
     // precompute first, for the glyphs that need it
-    if (n_gen && !a.fused)
-        fr::launch_prepare(plan->gs->d_pts, plan->gs->d_seg_p0, plan->gs->d_glyph_seg_start, nullptr, plan->gs->n_glyphs,
-                           plan->gs->d_recs, plan->gs->d_rec_count, gst);
-    else if (n_gen && plan->n_large)
-        fr::launch_prepare(plan->gs->d_pts, plan->gs->d_seg_p0, plan->gs->d_glyph_seg_start, plan->d_large, plan->n_large,
-                           plan->gs->d_recs, plan->gs->d_rec_count, gst);
+    // (FR_FILL_CONSISTENT: its own records, the reference's are rebuilt behind the render: the glyph set's records and
+    // counts are the reference's outside a render, fr_glyphset_stats included)
+    auto prepare = [&](int f) {
+        if (n_gen && !a.fused)
+            fr::launch_prepare(plan->gs->d_pts, plan->gs->d_seg_p0, plan->gs->d_glyph_seg_start, nullptr, plan->gs->n_glyphs,
+                               plan->gs->d_recs, plan->gs->d_rec_count, gst, f);
+        else if (n_gen && plan->n_large)
+            fr::launch_prepare(plan->gs->d_pts, plan->gs->d_seg_p0, plan->gs->d_glyph_seg_start, plan->d_large, plan->n_large,
+                               plan->gs->d_recs, plan->gs->d_rec_count, gst, f);
+    };
+    prepare(fill);
     if (n_gen) {
         a.jobs = plan->d_jobs + n_fast;
         a.job_seg = plan->d_job_seg + 2u * (size_t)n_fast;
@@ -810,8 +832,9 @@ static int plan_launch_direct(fr_plan *plan, void *out_dev, size_t out_stride, s
         split_bands(fr::render_wg_waves(), n_gen, plan->gen_bands, plan->gen_strips);
         // SDF, sign first: the 1-sample coverage (255 where the reference's winding is non-zero, same sample points)
         // lands in the output; the distance kernel reads it and overwrites it
-        if (sdf) HIP_TRY(fr::launch_render(a, FR_COVERAGE_U8, 1, gst));
-        else HIP_TRY(fr::launch_render(a, plan->params.mode, plan->params.samples_per_axis, gst));
+        if (sdf) HIP_TRY(fr::launch_render(a, FR_COVERAGE_U8, 1, gst, true, nullptr, 0, fill));
+        else HIP_TRY(fr::launch_render(a, plan->params.mode, plan->params.samples_per_axis, gst, true, nullptr, 0, fill));
+        if (fill) prepare(0);
     }
     for (size_t i = 0; i < plan->parts.size(); ++i) {
         // cov4_kernel / win1_kernel, one launch per (strip width, record slots) class that occurs in the plan
@@ -823,16 +846,16 @@ static int plan_launch_direct(fr_plan *plan, void *out_dev, size_t out_stride, s
         split_bands(fr::cov4_wg_waves(), pt.cnt, pt.bands, pt.strips);
         const int pm = plan->params.mode;
         hipStream_t pst = (forked && i != big) ? ctx->aux : ctx->stream;
-        if (plan->fast_ns > 1) HIP_TRY(fr::launch_cov4(a, pt.rec_cap, plan->fast_ns, pst));
+        if (plan->fast_ns > 1) HIP_TRY(fr::launch_cov4(a, pt.rec_cap, plan->fast_ns, pst, true, nullptr, 0, fill));
         else if (sdf && plan->d_bits) {
             // the sign pass of FR_SDF_U8: one bit per pixel into the job's own bit plane
             void *const keep = a.out;
             a.out = plan->d_bits; a.job_bits = plan->d_job_bits + pt.first;
-            const hipError_t le = fr::launch_win1(a, 3, pt.rec_cap, pst);
+            const hipError_t le = fr::launch_win1(a, 3, pt.rec_cap, pst, true, nullptr, 0, fill);
             a.out = keep; a.job_bits = nullptr;
             HIP_TRY(le);
         }
-        else HIP_TRY(fr::launch_win1(a, pm == FR_WINDING_I16 ? 0 : (pm == FR_GRAY_DEBUG ? 1 : 2), pt.rec_cap, pst));
+        else HIP_TRY(fr::launch_win1(a, pm == FR_WINDING_I16 ? 0 : (pm == FR_GRAY_DEBUG ? 1 : 2), pt.rec_cap, pst, true, nullptr, 0, fill));
     }
     return FR_OK;
     };
@@ -978,8 +1001,14 @@ int fr_plan_render_timed(fr_plan *plan, void *out_dev, size_t out_stride, size_t
 int fr_render_batch(fr_ctx *ctx, const fr_glyphset *gs, const fr_job *jobs, uint32_t n_jobs,
                     const fr_raster_params *params, void *out_host, size_t out_stride, size_t out_rows)
 {
+    return fr_render_batch_ex(ctx, gs, jobs, n_jobs, params, 0u, out_host, out_stride, out_rows);
+}
+
+int fr_render_batch_ex(fr_ctx *ctx, const fr_glyphset *gs, const fr_job *jobs, uint32_t n_jobs,
+                       const fr_raster_params *params, uint32_t flags, void *out_host, size_t out_stride, size_t out_rows)
+{
     fr_plan *plan = nullptr;
-    int rc = fr_plan_create(ctx, gs, jobs, n_jobs, params, &plan);
+    int rc = fr_plan_create_ex(ctx, gs, jobs, n_jobs, params, flags, &plan);
     if (rc) return rc;
     if (n_jobs == 0) { fr_plan_destroy(plan); return FR_OK; }
     if (!out_host) { fr_plan_destroy(plan); return fail(FR_E_INVALID, "out_host is NULL"); }
@@ -1034,7 +1063,15 @@ int fr_render_glyph(fr_ctx *ctx, const int16_t *points_xy, const uint32_t *conto
                     uint32_t n_contours, const int16_t box[4], uint16_t units_per_em,
                     uint16_t font_size, int32_t mode, void *out_host)
 {
+    return fr_render_glyph_ex(ctx, points_xy, contour_start, n_contours, box, units_per_em, font_size, mode, 0u, out_host);
+}
+
+int fr_render_glyph_ex(fr_ctx *ctx, const int16_t *points_xy, const uint32_t *contour_start,
+                       uint32_t n_contours, const int16_t box[4], uint16_t units_per_em,
+                       uint16_t font_size, int32_t mode, uint32_t flags, void *out_host)
+{
     if (!ctx) return fail(FR_E_INVALID, "ctx is NULL");
+    if (const int frc = check_flags(flags)) return frc;
     int16_t mn[2], mx[2];
     uint16_t w, h;
     float scale;
@@ -1100,7 +1137,7 @@ int fr_render_glyph(fr_ctx *ctx, const int16_t *points_xy, const uint32_t *conto
     gs.d_seg_p0 = reinterpret_cast<uint32_t *>(A0 + o_p0); gs.d_glyph_seg_start = reinterpret_cast<uint32_t *>(A0 + o_gseg);
     gs.d_rec_count = reinterpret_cast<uint32_t *>(A0 + o_cnt); gs.d_recs = reinterpret_cast<fr::Rec *>(A0 + o_recs);
     fr_plan pl;
-    pl.ctx = ctx; pl.gs = &gs; pl.n_jobs = 1; pl.n_fast = 0; pl.params = prm;
+    pl.ctx = ctx; pl.gs = &gs; pl.n_jobs = 1; pl.n_fast = 0; pl.params = prm; pl.flags = flags;
     {
         // the same per-job rule as fr_plan_create: the image takes win1_kernel (64- / 128- / 256-pixel strips by its
         // own width) unless the glyph is too large for it

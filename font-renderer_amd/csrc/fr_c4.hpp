@@ -126,7 +126,9 @@ __device__ __forceinline__ void c4_store16(void *dst, uint4 v)
     __builtin_nontemporal_store(w, reinterpret_cast<u32x4_u *>(dst));
 }
 
-// a settled candidate as the kernels keep it (40 bytes): row range [ra, re) in the low bits of `fr`
+// a settled candidate as the kernels keep it (40 bytes): row range [ra, re) in the low bits of `fr`.
+// FILL = 1 (FR_FILL_CONSISTENT): zb == cb == the piece's step code (flags & 2, fr_records.hpp), whatever dy says.
+template <int FILL = 0>
 __device__ __forceinline__ Rec40 c4_make_rec40(const Rec &r, uint32_t ra, uint32_t re)
 {
     Rec40 m;
@@ -135,7 +137,7 @@ __device__ __forceinline__ Rec40 c4_make_rec40(const Rec &r, uint32_t ra, uint32
     m.b = r.b; m.c1 = lin ? 0.0f : r.c1; m.c2 = r.c2;
     m.ax = r.ax; m.bx = r.bx; m.p0x = r.p0x; m.rden = r.rden;
     m.sgn = r.sqsign ? -1.0f : 1.0f;
-    const uint32_t cb = lin ? (r.flags & REC_LIN_PLUS) : 2u, zb = lin ? cb : 0u;
+    const uint32_t cb = (lin || FILL) ? (r.flags & 2u) : 2u, zb = (lin || FILL) ? cb : 0u;
     m.fr = ra | (re << 12) | (cb << 24) | (zb << 26) | (lin ? 0x80000000u : 0u);
     return m;
 }
@@ -146,7 +148,7 @@ __device__ __forceinline__ Rec40 c4_make_rec40(const Rec &r, uint32_t ra, uint32
 // on) wait.  Here every wave prepares the same 64 candidates and looks at ONE of the four rows (wave 0: ra - 1,
 // 1: ra, 2: re - 1, 3: re); wave 0 takes the guess when the four classes confirm it — exactly the condition under
 // which record_settle's walks would not move — and walks as before otherwise.  Same records, same order.
-template <uint32_t RCAP, int N, uint32_t NCOL>
+template <uint32_t RCAP, int N, uint32_t NCOL, int FILL>
 __device__ __forceinline__ uint32_t c4_setup_small(const RenderArgs &A, const Job &job, uint32_t seg0, uint32_t nseg, uint32_t x0s,
                                                    int phase, float *s_cxp, Rec40 *s_rec, uint32_t *s_wcnt, uint32_t *s_tmp, const float *cyt = nullptr)
 {
@@ -157,13 +159,14 @@ __device__ __forceinline__ uint32_t c4_setup_small(const RenderArgs &A, const Jo
     const bool have = lane < 2u * nseg;
     Rec r;
     RowGuess g;
+    Piece pc;
     g.empty = true; g.ra = 1u; g.re = 0u;
     uint32_t cls = 3u;                                  // 3: no such row / not asked — the condition it stands for holds
     if (have) {
-        record_prep(A.seg_pts + 6u * (size_t)(seg0 + (lane >> 1)), lane & 1u, geo, r, g);
+        record_prep<FILL>(A.seg_pts + 6u * (size_t)(seg0 + (lane >> 1)), lane & 1u, geo, r, g, &pc);
         if (!g.empty) {
             const uint32_t row = (wave == 0u) ? g.ra - 1u : (wave == 1u) ? g.ra : (wave == 2u) ? g.re - 1u : g.re;   // (ra - 1 wraps past the cell at ra = 0)
-            if (row < Hs && (wave != 2u || g.re > g.ra)) cls = (uint32_t)classify_row(r, geo.cy(row));
+            if (row < Hs && (wave != 2u || g.re > g.ra)) cls = (uint32_t)row_class<FILL>(r, pc, geo.cy(row));
         }
     }
     s_tmp[tid] = cls;
@@ -185,10 +188,10 @@ __device__ __forceinline__ uint32_t c4_setup_small(const RenderArgs &A, const Jo
                 // record_settle would leave (ra, re) alone iff: the row above ra is rejected from above (class 2), ra is
                 // not (class <= 1), re >= ra, the row before re is accepted (class >= 1), re is below the set (class 0)
                 const bool ok = (c0 >= 2u) && (c1 <= 1u || c1 == 3u) && re >= ra && (c2 >= 1u) && (c3 == 0u || c3 == 3u);
-                if (!ok) record_settle(r, geo, ra, re);
+                if (!ok) record_settle<FILL>(r, geo, ra, re, &pc);
             }
             live = ra < re;
-            mine = c4_make_rec40(r, ra, re);
+            mine = c4_make_rec40<FILL>(r, ra, re);
         }
         // quadratic records first, linear ones last (as c4_setup)
         const bool linr = live && (int32_t)mine.fr < 0;
@@ -207,7 +210,7 @@ __device__ __forceinline__ uint32_t c4_setup_small(const RenderArgs &A, const Jo
 // The same for 33 .. 64 segments (<= 128 candidate roots: one per lane of waves 0 and 1).  Thread c + 128 h looks at the
 // rows around the upper end (h = 0: ra - 1 and ra) or the lower end (h = 1: re - 1 and re) of candidate c; the owners
 // (h = 0) take the guess when all four classes confirm it and walk otherwise.
-template <uint32_t RCAP, int N, uint32_t NCOL>
+template <uint32_t RCAP, int N, uint32_t NCOL, int FILL>
 __device__ __forceinline__ uint32_t c4_setup_mid(const RenderArgs &A, const Job &job, uint32_t seg0, uint32_t nseg, uint32_t x0s,
                                                  int phase, float *s_cxp, Rec40 *s_rec, uint32_t *s_wcnt, uint32_t *s_tmp, const float *cyt = nullptr)
 {
@@ -219,14 +222,15 @@ __device__ __forceinline__ uint32_t c4_setup_mid(const RenderArgs &A, const Job 
     const bool have = c < 2u * nseg;
     Rec r;
     RowGuess g;
+    Piece pc;
     g.empty = true; g.ra = 1u; g.re = 0u;
     uint32_t cls0 = 3u, cls1 = 3u;                      // 3: no such row / not asked
     if (have) {
-        record_prep(A.seg_pts + 6u * (size_t)(seg0 + (c >> 1)), c & 1u, geo, r, g);
+        record_prep<FILL>(A.seg_pts + 6u * (size_t)(seg0 + (c >> 1)), c & 1u, geo, r, g, &pc);
         if (!g.empty) {
             const uint32_t end = h ? g.re : g.ra;       // rows end - 1 and end
-            if (end - 1u < Hs && (h == 0u || g.re > g.ra)) cls0 = (uint32_t)classify_row(r, geo.cy(end - 1u));
-            if (end < Hs) cls1 = (uint32_t)classify_row(r, geo.cy(end));
+            if (end - 1u < Hs && (h == 0u || g.re > g.ra)) cls0 = (uint32_t)row_class<FILL>(r, pc, geo.cy(end - 1u));
+            if (end < Hs) cls1 = (uint32_t)row_class<FILL>(r, pc, geo.cy(end));
         }
     }
     s_tmp[tid] = cls0 | (cls1 << 8);
@@ -245,10 +249,10 @@ __device__ __forceinline__ uint32_t c4_setup_mid(const RenderArgs &A, const Job 
             const uint32_t up = s_tmp[c], dn = s_tmp[128u + c];
             const uint32_t c0 = up & 0xffu, c1 = up >> 8, c2 = dn & 0xffu, c3 = dn >> 8;
             const bool ok = (c0 >= 2u) && (c1 <= 1u || c1 == 3u) && re >= ra && (c2 >= 1u) && (c3 == 0u || c3 == 3u);
-            if (!ok) record_settle(r, geo, ra, re);
+            if (!ok) record_settle<FILL>(r, geo, ra, re, &pc);
         }
         live = ra < re;
-        mine = c4_make_rec40(r, ra, re);
+        mine = c4_make_rec40<FILL>(r, ra, re);
     }
     // quadratic records first, linear ones last (as c4_setup): waves 0 and 1 hold them
     const bool linr = live && (int32_t)mine.fr < 0;
@@ -269,14 +273,14 @@ __device__ __forceinline__ uint32_t c4_setup_mid(const RenderArgs &A, const Job 
 // exact range of this cell's sample rows that accept each (fr_records.hpp), compacted into s_rec (<= RCAP kept), and
 // the padded table of the strip's exact sample abscissae.  Two workgroup barriers.  -> number of records.
 // N: samples per pixel axis (4: cov4_kernel, 1: win1_kernel); NCOL: sample columns of the strip.
-template <uint32_t NW, uint32_t RCAP, int N, uint32_t NCOL>
+template <uint32_t NW, uint32_t RCAP, int N, uint32_t NCOL, int FILL = 0>
 __device__ __forceinline__ uint32_t c4_setup(const RenderArgs &A, const Job &job, uint32_t seg0, uint32_t nseg, uint32_t x0s,
                                              int phase, float *s_cxp, Rec40 *s_rec, uint32_t *s_wcnt, uint32_t *s_tmp, const float *cyt = nullptr)
 {
     if (NW == 4u && 2u * nseg <= 64u)                                        // (workgroup-uniform; s_tmp: 1 KB, free until the bands start)
-        return c4_setup_small<RCAP, N, NCOL>(A, job, seg0, nseg, x0s, phase, s_cxp, s_rec, s_wcnt, s_tmp, cyt);
+        return c4_setup_small<RCAP, N, NCOL, FILL>(A, job, seg0, nseg, x0s, phase, s_cxp, s_rec, s_wcnt, s_tmp, cyt);
     if (NW == 4u && 2u * nseg <= 128u)
-        return c4_setup_mid<RCAP, N, NCOL>(A, job, seg0, nseg, x0s, phase, s_cxp, s_rec, s_wcnt, s_tmp, cyt);
+        return c4_setup_mid<RCAP, N, NCOL, FILL>(A, job, seg0, nseg, x0s, phase, s_cxp, s_rec, s_wcnt, s_tmp, cyt);
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t Hs = job.h * (uint32_t)N;
     // candidates per thread: <= 768 segments where 1024 records are kept, <= 384 where 512, else <= 256
@@ -295,10 +299,10 @@ __device__ __forceinline__ uint32_t c4_setup(const RenderArgs &A, const Job &job
             Rec r;
             RowGeom geo;
             geo.max_y = job.max_y; geo.scale = job.scale; geo.rows = Hs; geo.n = N; geo.phase = phase; geo.cyt = cyt;
-            build_record_rows(A.seg_pts + 6u * (size_t)(seg0 + (c >> 1)), c & 1u, geo, r);
+            build_record_rows<FILL>(A.seg_pts + 6u * (size_t)(seg0 + (c >> 1)), c & 1u, geo, r);
             const uint32_t ra = __builtin_bit_cast(uint32_t, r.lo), re = __builtin_bit_cast(uint32_t, r.hi);
             live = ra < re;
-            mine[it] = c4_make_rec40(r, ra, re);
+            mine[it] = c4_make_rec40<FILL>(r, ra, re);
         }
         // quadratic records first, linear ones (the a == 0 branch) last: the pair sequence follows the record order,
         // so an evaluation trip is almost always all-quadratic or all-linear and takes a body without the other's work

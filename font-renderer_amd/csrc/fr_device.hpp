@@ -136,10 +136,26 @@ __device__ __forceinline__ float rec_t_lin(const Rec &r, float cy)
 // the reference's decision for one record at ray height cy (:49-69): is the root accepted,
 // where does it cross (xx) and which sign does it add.  [lo, hi] only brackets the accepted
 // set, so the three rejection tests (:52, :59, :64) are applied here exactly as written.
+// FILL = 1 (FR_FILL_CONSISTENT, fr_records.hpp): the record's [lo, hi] / row range is exactly the set of heights that
+// cross its piece, so nothing is rejected here; the step is the piece's ((flags & 2): +1 falling, -1 rising) and delta
+// is clamped at 0 (a crossing height can lie a few ulps past the rounded delta = 0).
+template <int FILL = 0>
 __device__ __forceinline__ bool rec_cross(const Rec &r, float cy, float &xx, int &sgn)
 {
     float t;
     bool ok;
+    if constexpr (FILL != 0) {
+        if (r.flags & REC_LINEAR) {
+            t = rec_t_lin(r, cy);
+        } else {
+            const float delta = __builtin_fmaxf(cy * r.a + r.c1 - r.c2, 0.0f);
+            const float sq = __builtin_sqrtf(delta);
+            t = ((r.flags & REC_NEG_ROOT) ? (r.b - sq) : (r.b + sq)) / r.a;
+        }
+        sgn = (r.flags & 2u) ? 1 : -1;
+        xx = (r.ax * t + r.bx) * t + r.p0x;
+        return true;
+    }
     if (r.flags & REC_LINEAR) {
         t = rec_t_lin(r, cy);
         ok = !(t < 0.0f || t >= 1.0f);                                  // :52
@@ -157,6 +173,7 @@ __device__ __forceinline__ bool rec_cross(const Rec &r, float cy, float &xx, int
 
 // direct sum over a glyph's records — the reference's own loop shape (render_glyph.zig:37-71):
 // used for the sign of the SDF (the render kernel's over-full rows use rec_cross directly)
+template <int FILL = 0>
 __device__ inline int brute_winding(const Rec *__restrict__ recs, uint32_t n, float cx, float cy)
 {
     int w = 0;
@@ -164,7 +181,7 @@ __device__ inline int brute_winding(const Rec *__restrict__ recs, uint32_t n, fl
         const Rec r = recs[c];
         if (cy >= r.lo && cy <= r.hi) {
             float xx; int sgn;
-            if (rec_cross(r, cy, xx, sgn) && !(xx < cx)) w += sgn;
+            if (rec_cross<FILL>(r, cy, xx, sgn) && !(xx < cx)) w += sgn;
         }
     }
     return w;

@@ -9,7 +9,9 @@ namespace fr {
 // candidate 2s / 2s+1 are the t+ / t- roots of segment s (2s alone for a == 0);
 // survivors (records whose bracket is not provably empty) are compacted with a ballot + prefix popcount into the glyph's slice
 // [2*seg_start[g], ...) of the record arrays.
-__global__ __launch_bounds__(64) void prepare_kernel(const int16_t *__restrict__ pts,
+// FILL = 1: the records of FR_FILL_CONSISTENT (fr_records.hpp, build_record_fill)
+template <int FILL>
+__device__ __forceinline__ void prepare_body(const int16_t *__restrict__ pts,
                                                      const uint32_t *__restrict__ seg_p0,
                                                      const uint32_t *__restrict__ glyph_seg_start,
                                                      const uint32_t *__restrict__ glyph_list,
@@ -29,7 +31,7 @@ __global__ __launch_bounds__(64) void prepare_kernel(const int16_t *__restrict__
         const uint32_t c = base + lane;
         bool valid = false;
         Rec r;
-        if (c < n_cand) valid = build_record(pts + 2u * (size_t)seg_p0[s0 + (c >> 1)], c & 1u, r);
+        if (c < n_cand) valid = FILL ? build_record_fill(pts + 2u * (size_t)seg_p0[s0 + (c >> 1)], c & 1u, r) : build_record(pts + 2u * (size_t)seg_p0[s0 + (c >> 1)], c & 1u, r);
         const unsigned long long m = __ballot(valid);
         if (valid) {
             const uint32_t pos = n_out + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
@@ -39,13 +41,33 @@ __global__ __launch_bounds__(64) void prepare_kernel(const int16_t *__restrict__
     }
     if (lane == 0) glyph_rec_count[g] = n_out;
 }
+__global__ __launch_bounds__(64) void prepare_kernel(const int16_t *__restrict__ pts,
+                                                     const uint32_t *__restrict__ seg_p0,
+                                                     const uint32_t *__restrict__ glyph_seg_start,
+                                                     const uint32_t *__restrict__ glyph_list,
+                                                     uint32_t n_glyphs,
+                                                     Rec *__restrict__ out_recs,
+                                                     uint32_t *__restrict__ glyph_rec_count)
+{
+    prepare_body<0>(pts, seg_p0, glyph_seg_start, glyph_list, n_glyphs, out_recs, glyph_rec_count);
+}
+__global__ __launch_bounds__(64) void prepare_fill_kernel(const int16_t *__restrict__ pts,
+                                                     const uint32_t *__restrict__ seg_p0,
+                                                     const uint32_t *__restrict__ glyph_seg_start,
+                                                     const uint32_t *__restrict__ glyph_list,
+                                                     uint32_t n_glyphs,
+                                                     Rec *__restrict__ out_recs,
+                                                     uint32_t *__restrict__ glyph_rec_count)
+{
+    prepare_body<1>(pts, seg_p0, glyph_seg_start, glyph_list, n_glyphs, out_recs, glyph_rec_count);
+}
 
 void launch_prepare(const int16_t *pts, const uint32_t *seg_p0, const uint32_t *glyph_seg_start,
                     const uint32_t *glyph_list, uint32_t n_glyphs, Rec *out_recs, uint32_t *glyph_rec_count,
-                    hipStream_t stream)
+                    hipStream_t stream, int fill)
 {
     if (n_glyphs == 0) return;
-    hipLaunchKernelGGL(prepare_kernel, dim3(n_glyphs), dim3(64), 0, stream, pts, seg_p0,
+    hipLaunchKernelGGL(fill ? prepare_fill_kernel : prepare_kernel, dim3(n_glyphs), dim3(64), 0, stream, pts, seg_p0,
                        glyph_seg_start, glyph_list, n_glyphs, out_recs, glyph_rec_count);
 }
 

@@ -191,6 +191,42 @@ __device__ __forceinline__ int classify_row(const Rec &r, float cy)
     return cl;
 }
 
+// ---------------------------------------------------------------------------------------------
+// FR_FILL_CONSISTENT (include/fr_raster.h): the same sample points, a different crossing rule.
+// Every record (t+ / t- root, or the a == 0 root) is one y-monotone PIECE of its segment — the t+ root is the half
+// that rises along t, the t- root the half that falls, the a == 0 root the whole line — and a piece with end heights
+// ylo < yhi is crossed by the ray at height cy iff  ylo <= cy < yhi  (exact; a piece of zero height is never
+// crossed), with step -1 if it rises, +1 if it falls: the step code is (flags & 2) for every record (REC_NEG_ROOT ==
+// REC_LIN_PLUS == 2).  The end heights are the integers p0y, p2y and the vertex height y_v = p0y - b^2 / a; the vertex
+// test  cy >= y_v  <=>  a (cy - y_v) = a cy + (b^2 - a p0y) has the sign of a (or is 0)  is one f64 FMA of exact
+// operands (|a| <= 2^17, cy has 24 significant bits, b^2 - a p0y an integer below 2^34): its rounded result has the
+// sign of the exact one.  A pure interval test, so the class is monotone in cy as record_settle needs.
+struct Piece {
+    float ylo, yhi;      // end heights: exact integers, except the vertex end (vend), where it is an estimate (guess only)
+    float a;             // p0y - 2 p1y + p2y
+    double cv;           // b^2 - a p0y, exact
+    uint32_t vend;       // 0: both ends are on-curve points, 1: the low end is the vertex, 2: the high end is
+};
+__device__ __forceinline__ bool fill_at_or_above_vertex(const Piece &pc, float cy)
+{
+    const double d = __builtin_fma((double)pc.a, (double)cy, pc.cv);
+    return pc.a > 0.0f ? d >= 0.0 : d <= 0.0;
+}
+// 0 = cy below the piece, 1 = crossed, 2 = at or above its top
+__device__ __forceinline__ int classify_fill(const Piece &pc, float cy)
+{
+    const bool above = (pc.vend == 2u) ? fill_at_or_above_vertex(pc, cy) : (cy >= pc.yhi);
+    const bool below = (pc.vend == 1u) ? !fill_at_or_above_vertex(pc, cy) : (cy < pc.ylo);
+    return above ? 2 : (below ? 0 : 1);
+}
+// the class a record build walks with: the reference's acceptance (FILL = 0) or the piece's (FILL = 1)
+template <int FILL>
+__device__ __forceinline__ int row_class(const Rec &r, const Piece &pc, float cy)
+{
+    if constexpr (FILL != 0) return classify_fill(pc, cy);
+    else return classify_row(r, cy);
+}
+
 // As build_record, but the bracket is this cell's exact sample-row range, written as integers
 // into the lo / hi slots of the record (ra, re).  An empty range is ra = 1, re = 0.
 // In three pieces, so that a set-up with lanes to spare can look at the four rows around the guessed
@@ -201,7 +237,8 @@ struct RowGuess {
     bool empty;          // the candidate is discarded without a probe (see above)
 };
 
-__device__ __forceinline__ void record_prep(const int16_t *p, uint32_t root, const RowGeom &G, Rec &r, RowGuess &g)
+template <int FILL = 0>
+__device__ __forceinline__ void record_prep(const int16_t *p, uint32_t root, const RowGeom &G, Rec &r, RowGuess &g, Piece *pc = nullptr)
 {
     const float p0x = (float)p[0], p0y = (float)p[1];
     const float p1x = (float)p[2], p1y = (float)p[3];
@@ -238,6 +275,29 @@ __device__ __forceinline__ void record_prep(const int16_t *p, uint32_t root, con
             empty = tv_lt0;
             if (!tv_ge1) { c_stop = yv; stop_incl = true; }
         }
+        if constexpr (FILL != 0) {
+            // the piece: far side t in [max(0, t_v), 1], near side t in [0, min(1, t_v)] (t_v = b / a); its vertex end,
+            // if any, is its lowest point when a > 0 and its highest when a < 0.  Near side with t_v = 0: a single point.
+            const bool has_v = far_side ? !tv_le0 : !tv_ge1;
+            if (!far_side && b == 0.0f) empty = true;
+            const float other = far_side ? p2y : p0y;
+            pc->a = a;
+            pc->cv = (double)b * (double)b - (double)a * (double)p0y;
+            pc->vend = has_v ? (a > 0.0f ? 1u : 2u) : 0u;
+            pc->ylo = has_v ? (a > 0.0f ? yv : other) : fminf(p0y, p2y);
+            pc->yhi = has_v ? (a > 0.0f ? other : yv) : fmaxf(p0y, p2y);
+            if (!has_v && p0y == p2y) empty = true;
+            c_start = pc->yhi; c_stop = pc->ylo;                    // (guesses: the first row below yhi, the first below ylo)
+            stop_incl = true;
+        }
+    }
+    if constexpr (FILL != 0) {
+        if (lin) {
+            pc->a = 1.0f; pc->cv = 0.0; pc->vend = 0u;
+            pc->ylo = fminf(p0y, p2y); pc->yhi = fmaxf(p0y, p2y);
+            c_start = pc->yhi; c_stop = pc->ylo;
+            stop_incl = true;
+        }
     }
     g.empty = empty;
     g.ra = 1u; g.re = 0u;
@@ -246,7 +306,7 @@ __device__ __forceinline__ void record_prep(const int16_t *p, uint32_t root, con
         const float top = (float)G.rows;
         const bool start_hi = c_start >= c_stop;
         const float xh = G.row_of(start_hi ? c_start : c_stop), xl = G.row_of(start_hi ? c_stop : c_start);
-        const bool hi_incl = start_hi ? true : stop_incl, lo_incl = start_hi ? stop_incl : true;
+        const bool hi_incl = (FILL != 0) ? false : (start_hi ? true : stop_incl), lo_incl = start_hi ? stop_incl : true;
         const float fa = hi_incl ? __builtin_ceilf(xh) : __builtin_floorf(xh) + 1.0f;    // first row accepted
         const float fe = lo_incl ? __builtin_floorf(xl) + 1.0f : __builtin_ceilf(xl);    // first row past it
         g.ra = (uint32_t)fminf(fmaxf(fa, 0.0f), top);
@@ -255,8 +315,13 @@ __device__ __forceinline__ void record_prep(const int16_t *p, uint32_t root, con
 }
 
 // the exact ends from any starting guess: walk while the class of the row says so
-__device__ __forceinline__ void record_settle(const Rec &r, const RowGeom &G, uint32_t &ra, uint32_t &re)
+template <int FILL = 0>
+__device__ __forceinline__ void record_settle(const Rec &r, const RowGeom &G, uint32_t &ra, uint32_t &re, const Piece *pc = nullptr)
 {
+    auto classify_row = [&](const Rec &rr, float cy) {
+        if constexpr (FILL != 0) return classify_fill(*pc, cy);
+        else return fr::classify_row(rr, cy);
+    };
     // (one trip each when the guess is right: keep the compiler from unrolling them)
 #pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
     while (ra > 0u && classify_row(r, G.cy(ra - 1u)) <= 1) --ra;
@@ -269,14 +334,43 @@ __device__ __forceinline__ void record_settle(const Rec &r, const RowGeom &G, ui
     while (re < G.rows && classify_row(r, G.cy(re)) >= 1) ++re;
 }
 
+template <int FILL = 0>
 __device__ __forceinline__ void build_record_rows(const int16_t *p, uint32_t root, const RowGeom &G, Rec &r)
 {
     RowGuess g;
-    record_prep(p, root, G, r, g);
+    Piece pc;
+    record_prep<FILL>(p, root, G, r, g, &pc);
     uint32_t ra = g.ra, re = g.re;
-    if (!g.empty) record_settle(r, G, ra, re);
+    if (!g.empty) record_settle<FILL>(r, G, ra, re, &pc);
     r.lo = __builtin_bit_cast(float, ra);
     r.hi = __builtin_bit_cast(float, re);
 }
 
+
+// FR_FILL_CONSISTENT form of build_record (prepare_kernel's records for the general kernel's large glyphs): the same
+// fields, and [lo, hi] = the closed binary32 interval of the heights ylo <= cy < yhi that cross the piece, found by
+// bisection over the ordered binary32 keys with the exact class (two times 32 steps per candidate).
+__device__ inline bool build_record_fill(const int16_t *p, uint32_t root, Rec &r)
+{
+    RowGeom G;                                     // (no cell: record_prep's row guesses are not used)
+    G.max_y = 0; G.scale = 1.0f; G.rows = 0u; G.n = 1; G.phase = 0;
+    RowGuess g;
+    Piece pc;
+    record_prep<1>(p, root, G, r, g, &pc);
+    if (g.empty) return false;
+    const uint32_t kmin = f2key(-3.402823466e+38f), kmax = f2key(3.402823466e+38f);
+    auto first_at_least = [&](int T) {            // smallest key whose class is >= T (the class is monotone)
+        uint32_t L = kmin, H = kmax + 1u;
+        while (L < H) {
+            const uint32_t mid = L + ((H - L) >> 1);
+            if (classify_fill(pc, key2f(mid)) >= T) H = mid; else L = mid + 1u;
+        }
+        return L;
+    };
+    const uint32_t LB = first_at_least(1), HB = first_at_least(2);
+    if (LB >= HB) return false;
+    r.lo = key2f(LB);
+    r.hi = key2f(HB - 1u);
+    return true;
+}
 }  // namespace fr

@@ -106,16 +106,17 @@ def make_jobs(rows: Sequence) -> np.ndarray:
 
 
 class Plan:
-    """fr_plan: a job table resident on the device."""
+    """fr_plan: a job table resident on the device.  flags: FR_FILL_CONSISTENT or 0 (the reference's crossing rule)."""
 
     def __init__(self, dgs: DeviceGlyphSet, jobs: np.ndarray, mode: int, samples_per_axis: int = 1,
-                 sample_phase: int = L.FR_SAMPLE_CORNER):
+                 sample_phase: int = L.FR_SAMPLE_CORNER, flags: int = 0):
         assert jobs.dtype.itemsize == 32
         self.ctx, self.dgs, self.mode = dgs.ctx, dgs, mode
         self.params = L.RasterParams(mode, samples_per_axis, sample_phase, 0)
         jobs = np.ascontiguousarray(jobs)
         h = C.c_void_p()
-        L.check(self.ctx._lib.fr_plan_create(self.ctx._h, dgs._h, L.ptr(jobs), len(jobs), C.byref(self.params), C.byref(h)))
+        L.check(self.ctx._lib.fr_plan_create_ex(self.ctx._h, dgs._h, L.ptr(jobs), len(jobs), C.byref(self.params), flags,
+                                                C.byref(h)))
         self._h = h
         self.n_jobs = len(jobs)
 
@@ -157,14 +158,14 @@ class Plan:
 
 
 def render_batch(dgs: DeviceGlyphSet, jobs: np.ndarray, mode: int, out: np.ndarray, samples_per_axis: int = 1,
-                 sample_phase: int = L.FR_SAMPLE_CORNER) -> np.ndarray:
+                 sample_phase: int = L.FR_SAMPLE_CORNER, flags: int = 0) -> np.ndarray:
     """fr_render_batch into a HOST array `out` (2-D, u8 or i16 for FR_WINDING_I16)."""
     want = np.int16 if mode == L.FR_WINDING_I16 else np.uint8
     assert out.dtype == want and out.ndim == 2 and out.flags.c_contiguous
     prm = L.RasterParams(mode, samples_per_axis, sample_phase, 0)
     jobs = np.ascontiguousarray(jobs)
-    L.check(dgs.ctx._lib.fr_render_batch(dgs.ctx._h, dgs._h, L.ptr(jobs), len(jobs), C.byref(prm), L.ptr(out),
-                                         out.shape[1], out.shape[0]))
+    L.check(dgs.ctx._lib.fr_render_batch_ex(dgs.ctx._h, dgs._h, L.ptr(jobs), len(jobs), C.byref(prm), flags, L.ptr(out),
+                                            out.shape[1], out.shape[0]))
     return out
 
 
@@ -179,28 +180,28 @@ def render_glyph_dims(box, units_per_em: int, font_size: int):
 
 
 def renderGlyph(glyph: Glyph, font_info: FontInformation, font_size: int, *, ctx: Optional[Context] = None,
-                mode: int = L.FR_GRAY_DEBUG) -> Gray:
+                mode: int = L.FR_GRAY_DEBUG, flags: int = 0) -> Gray:
     """render_glyph.zig:11 — `pub fn renderGlyph(glyph, font_info, font_size) !Image.Gray`."""
     ctx = ctx or default_context()
     _, _, w, h, _ = render_glyph_dims(glyph.box.as_array(), font_info.units_per_em, font_size)
     im = Gray.init(w, h)                                                     # :22
     pts, cstart, nc = _flat(glyph)
     box = glyph.box.as_array()
-    L.check(ctx._lib.fr_render_glyph(ctx._h, L.ptr(pts), L.ptr(cstart), nc, L.ptr(box), font_info.units_per_em,
-                                     font_size, mode, L.ptr(im.data)))
+    L.check(ctx._lib.fr_render_glyph_ex(ctx._h, L.ptr(pts), L.ptr(cstart), nc, L.ptr(box), font_info.units_per_em,
+                                        font_size, mode, flags, L.ptr(im.data)))
     return im
 
 
 def renderGlyphWinding(glyph: Glyph, font_info: FontInformation, font_size: int, *, ctx: Optional[Context] = None,
-                       scaler: int = 50, overflow_color: int = 150) -> Winding:
+                       scaler: int = 50, overflow_color: int = 150, flags: int = 0) -> Winding:
     """same grid as renderGlyph, raw i16 windings into an Image.Winding (Image.zig:85-130)"""
     ctx = ctx or default_context()
     _, _, w, h, _ = render_glyph_dims(glyph.box.as_array(), font_info.units_per_em, font_size)
     im = Winding.init(w, h, scaler, overflow_color)
     pts, cstart, nc = _flat(glyph)
     box = glyph.box.as_array()
-    L.check(ctx._lib.fr_render_glyph(ctx._h, L.ptr(pts), L.ptr(cstart), nc, L.ptr(box), font_info.units_per_em,
-                                     font_size, L.FR_WINDING_I16, L.ptr(im.data)))
+    L.check(ctx._lib.fr_render_glyph_ex(ctx._h, L.ptr(pts), L.ptr(cstart), nc, L.ptr(box), font_info.units_per_em,
+                                        font_size, L.FR_WINDING_I16, flags, L.ptr(im.data)))
     return im
 
 

@@ -64,6 +64,24 @@ typedef enum fr_mode {
  *   FR_SAMPLE_CENTER phase 1/2 — regular n x n grid centred in the pixel              */
 typedef enum fr_sample_phase { FR_SAMPLE_CORNER = 0, FR_SAMPLE_CENTER = 1 } fr_sample_phase;
 
+/* Crossing-rule flags of the _ex entry points (BUILD-DEFINED).  flags = 0 is the reference's rule —
+ * bit for bit what the entry points without _ex compute; any bit not defined here is FR_E_INVALID.
+ *   FR_FILL_CONSISTENT  the non-zero winding of the SAME sample points (cx, cy) (binary32 exactly as fr_job says) with a
+ *       consistent crossing rule instead of the reference's root acceptance 0 <= t < 1 (render_glyph.zig:49-69, which
+ *       counts false crossings on a ray through a vertex, an extremum or along a horizontal edge):
+ *       1. pieces: a segment with a == 0 is one piece p0 -> p2 (none if p0y == p2y); a quadratic one is split at its
+ *          y-extremum t_v = b / a (b = p0y - p1y) into its y-monotone halves (those with t in [0, 1]); a piece whose
+ *          y-extent is a single value contributes nothing;
+ *       2. a piece with exact end heights ylo < yhi (the integers p0y, p2y or the vertex height p0y - b^2 / a) is
+ *          crossed by the ray at height cy iff ylo <= cy < yhi, decided exactly on cy as the binary32 it is;
+ *       3. the crossing adds -1 if the piece rises along t, +1 if it falls;
+ *       4. its abscissa xx is the reference's expression (:51 / :60-61 for t, :53 / :65 for xx) with delta clamped at 0
+ *          before the square root, and it counts iff !(xx < cx), as in the reference.
+ *       So a vertex the outline passes through is counted once, an extremum twice with opposite signs (or not at all),
+ *       a horizontal edge never.  Every mode, n and phase; the exact-integer path (fr_exact_*, fr_winding_lattice,
+ *       fr_glyph_debug_render) has no flags and stays the reference's.                                                  */
+#define FR_FILL_CONSISTENT 1u
+
 typedef struct fr_raster_params {
     int32_t mode;              /* fr_mode                                              */
     int32_t samples_per_axis;  /* n in {1,2,4}; must be 1 unless mode = FR_COVERAGE_U8  */
@@ -140,6 +158,9 @@ int fr_glyphset_stats(const fr_glyphset *gs, uint64_t *n_segments, uint64_t *n_r
  * without host traffic (atlas pages, benchmark steps).                              */
 int fr_plan_create(fr_ctx *ctx, const fr_glyphset *gs, const fr_job *jobs, uint32_t n_jobs,
                    const fr_raster_params *params, fr_plan **out);
+/* the same with crossing-rule flags (FR_FILL_CONSISTENT); fr_plan_create is flags = 0                                 */
+int fr_plan_create_ex(fr_ctx *ctx, const fr_glyphset *gs, const fr_job *jobs, uint32_t n_jobs,
+                      const fr_raster_params *params, uint32_t flags, fr_plan **out);
 void fr_plan_destroy(fr_plan *plan);
 /* Every render starts from the glyph POINTS (nothing derived is reused between renders): the render
  * kernels build the root records of a glyph of <= 128 (general kernel) / <= 768 (cov4 / win1 kernels) segments
@@ -159,13 +180,16 @@ uint64_t fr_plan_pixels(const fr_plan *plan);   /* sum of w*h over the jobs */
  * everything else                                                                                              */
 int fr_plan_stats(const fr_plan *plan, uint32_t *n_jobs_cov4, uint32_t *n_jobs_general);
 /* the kernel instances one render of the plan launches, as rocprofv3 --kernel-trace names them, each with its job
- * count: "fr::cov4_kernel<4, 32, 4, 4> x20992; fr::render_kernel<3, 4, 32, -1> x3" (NUL-terminated, truncated to cap) */
+ * count: "fr::cov4_kernel<4, 32, 4, 4> x20992; fr::render_kernel<3, 4, 32, -1> x3" (NUL-terminated, truncated to cap);
+ * a FR_FILL_CONSISTENT plan's instances carry a trailing 1: "fr::cov4_kernel<4, 32, 4, 4, 1> x20992"                  */
 int fr_plan_describe(const fr_plan *plan, char *buf, size_t cap);
 
 /* One-shot: plan + render + copy back.  out_host: HOST buffer (caller-allocated,
  * e.g. Image.Gray.data / Image.Winding.data from the Zig allocator).  Synchronous.  */
 int fr_render_batch(fr_ctx *ctx, const fr_glyphset *gs, const fr_job *jobs, uint32_t n_jobs,
                     const fr_raster_params *params, void *out_host, size_t out_stride, size_t out_rows);
+int fr_render_batch_ex(fr_ctx *ctx, const fr_glyphset *gs, const fr_job *jobs, uint32_t n_jobs,
+                       const fr_raster_params *params, uint32_t flags, void *out_host, size_t out_stride, size_t out_rows);
 
 /* ---- renderGlyph drop-in (render_glyph.zig:11-33) -------------------------
  * fr_render_glyph_dims reproduces :13-19 on the host so the caller can size the
@@ -177,6 +201,9 @@ int fr_render_glyph_dims(const int16_t box[4], uint16_t units_per_em, uint16_t f
 int fr_render_glyph(fr_ctx *ctx, const int16_t *points_xy, const uint32_t *contour_start,
                     uint32_t n_contours, const int16_t box[4], uint16_t units_per_em,
                     uint16_t font_size, int32_t mode, void *out_host);
+int fr_render_glyph_ex(fr_ctx *ctx, const int16_t *points_xy, const uint32_t *contour_start,
+                       uint32_t n_contours, const int16_t box[4], uint16_t units_per_em,
+                       uint16_t font_size, int32_t mode, uint32_t flags, void *out_host);
 
 /* ---- exact-integer path (render_glyph.zig:76-300) -------------------------
  * fr_glyph_info_init: GlyphInfo.init (:110-146) — one CurveType (:84-95 enum order)
