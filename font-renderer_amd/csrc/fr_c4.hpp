@@ -1,7 +1,8 @@
 // fr_c4.hpp — what cov4_kernel (fr_cov4.hip, 16 samples per pixel) and win1_kernel (fr_win1.hip, 1 sample per pixel)
-// share: the 40-byte root record, wave64 DPP scans, the workgroup set-up (records with exact row ranges + cx table).
+// share: the 40-byte root record, the workgroup set-up (records with exact row ranges + cx table).
 #pragma once
 #include "fr_records.hpp"
+#include "fr_wave.hpp"
 
 namespace fr {
 
@@ -66,36 +67,6 @@ struct __attribute__((aligned(8))) Rec40 {
                     // the crossing's step code is (dy > 0) ? zb : cb   (2: +1, 0: -1; :55, :68)
 };
 
-template <int CTRL>
-__device__ __forceinline__ uint32_t c4_dpp0(uint32_t x)
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xf, 0xf, false);
-}
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t c4_dppm(uint32_t x)
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, ROW_MASK, 0xf, false);
-}
-__device__ __forceinline__ uint32_t c4_wave_incl_add(uint32_t x)
-{
-    x += c4_dppm<0x111, 0xf>(x);
-    x += c4_dppm<0x112, 0xf>(x);
-    x += c4_dppm<0x114, 0xf>(x);
-    x += c4_dppm<0x118, 0xf>(x);
-    x += c4_dppm<0x142, 0xa>(x);
-    x += c4_dppm<0x143, 0xc>(x);
-    return x;
-}
-__device__ __forceinline__ uint32_t c4_wave_incl_max(uint32_t x)
-{
-    x = max(x, c4_dppm<0x111, 0xf>(x));
-    x = max(x, c4_dppm<0x112, 0xf>(x));
-    x = max(x, c4_dppm<0x114, 0xf>(x));
-    x = max(x, c4_dppm<0x118, 0xf>(x));
-    x = max(x, c4_dppm<0x142, 0xa>(x));
-    x = max(x, c4_dppm<0x143, 0xc>(x));
-    return x;
-}
 // select on a wave mask held in SGPRs — the VOP3 form, whose cost does not depend on what wrote the mask
 // (a VOP2 v_cndmask reading a VCC that is not fresh costs 3-5 vector instructions: profiles/r02/issue_model3.txt)
 __device__ __forceinline__ uint32_t c4_sel(unsigned long long m, uint32_t if_set, uint32_t if_clear)
@@ -108,14 +79,6 @@ __device__ __forceinline__ float c4_self(unsigned long long m, float if_set, flo
 {
     return __builtin_bit_cast(float, c4_sel(m, __builtin_bit_cast(uint32_t, if_set), __builtin_bit_cast(uint32_t, if_clear)));
 }
-__device__ __forceinline__ void c4_wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-
 // 16-byte streaming store of finished pixels (never read again by this kernel): the non-temporal hint keeps them from
 // displacing the tables the kernel does re-read in L2
 __device__ __forceinline__ void c4_store16(void *dst, uint4 v)

@@ -34,44 +34,6 @@
 
 namespace fr {
 
-typedef unsigned short c4_u16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void c4_pce(uint32_t &a, uint32_t &b)
-{
-    const c4_u16x2 x = __builtin_bit_cast(c4_u16x2, a), y = __builtin_bit_cast(c4_u16x2, b);
-    a = __builtin_bit_cast(uint32_t, __builtin_elementwise_min(x, y));
-    b = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(x, y));
-}
-// 2H crossings packed two per register, ascending: low halves = s[0..H), high halves = s[H..2H)
-// (the packed odd-even merge network of fr_render.hip)
-template <int H>
-__device__ __forceinline__ void c4_packed_sort(uint32_t (&d)[16])
-{
-#pragma unroll
-    for (int p = 1; p < H; p *= 2)
-#pragma unroll
-        for (int k = p; k >= 1; k /= 2)
-#pragma unroll
-            for (int j = k % p; j + k < H; j += 2 * k)
-#pragma unroll
-                for (int i = 0; i < k; ++i)
-                    if (i + j + k < H && (i + j) / (2 * p) == (i + j + k) / (2 * p)) c4_pce(d[i + j], d[i + j + k]);
-#pragma unroll
-    for (int j = 0; j < H / 2; ++j) {
-        const uint32_t x = d[j], y = d[H - 1 - j];
-        const uint32_t ys = __builtin_amdgcn_alignbit(y, y, 16);
-        const c4_u16x2 xv = __builtin_bit_cast(c4_u16x2, x), yv = __builtin_bit_cast(c4_u16x2, ys);
-        const uint32_t mn = __builtin_bit_cast(uint32_t, __builtin_elementwise_min(xv, yv));
-        const uint32_t mx = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(xv, yv));
-        d[j] = __builtin_amdgcn_perm(mx, mn, 0x05040100u);
-        d[H - 1 - j] = __builtin_amdgcn_perm(mx, mn, 0x07060302u);
-    }
-#pragma unroll
-    for (int k = H / 2; k >= 1; k /= 2)
-#pragma unroll
-        for (int j = 0; j < H; ++j)
-            if (!(j & k)) c4_pce(d[j], d[j + k]);
-}
-
 #ifdef FR_C4_STATS
 __device__ unsigned long long g_c4_stats[16];
 #endif
@@ -165,7 +127,15 @@ extern "C" int fr_debug_read_c4_stats(unsigned long long *out16, int reset)
 uint32_t cov4_wg_waves() { return C4_WAVES; }
 uint32_t cov4_max_segments() { return 768u; }     // (with 1024 record slots; 384 with 512, 256 for the smaller instances: fr_plan_create)
 
-template <int WLOG, int RPL, int NS, int... FILLP>
+// FILL = 1: the FR_FILL_CONSISTENT twin of an instance (same launch shape and LDS)
+template <int WLOG, int CAP, int RPL, int NS, int FILL>
+static auto cov4_instance()
+{
+    if constexpr (FILL) return cov4_kernel<WLOG, CAP, RPL, NS, 1>;
+    else return cov4_kernel<WLOG, CAP, RPL, NS>;
+}
+
+template <int WLOG, int RPL, int NS, int FILL>
 static hipError_t cov4_launch_cap(const RenderArgs &a, dim3 grid, hipStream_t stream, char *name, size_t name_cap)
 {
     // glyphs of <= 128 candidate roots (RPL == 2) all but never put more than 16 crossings on a sample row (a real font:
@@ -175,38 +145,40 @@ static hipError_t cov4_launch_cap(const RenderArgs &a, dim3 grid, hipStream_t st
     // (the 1024-record instance — glyphs of 385 .. 768 segments, rare — exists with 32 kept crossings only)
     const int cap = RPL >= 16 ? 32 : (kmax <= 8 ? 8 : (kmax <= 16 ? 16 : 32));
     // the instance as rocprofv3 names it
-    if (name) snprintf(name, name_cap, sizeof...(FILLP) ? "fr::cov4_kernel<%d, %d, %d, %d, 1>" : "fr::cov4_kernel<%d, %d, %d, %d>", WLOG, cap, RPL, NS);
+    if (name) snprintf(name, name_cap, FILL ? "fr::cov4_kernel<%d, %d, %d, %d, 1>" : "fr::cov4_kernel<%d, %d, %d, %d>", WLOG, cap, RPL, NS);
     if (!grid.x) return hipSuccess;                // (name only)
+    // (only the 512- and 1024-record instances need more than the default 48 KB)
     const size_t lds = (cap == 8 ? C4Lds<WLOG, RPL, NS, 8>::TOTAL : (cap == 16 ? C4Lds<WLOG, RPL, NS, 16>::TOTAL : C4Lds<WLOG, RPL, NS, 32>::TOTAL)) + a.lds_pad;
-    auto launch = [&](auto kern) -> hipError_t {
-        if (lds > 48 * 1024) {                   // (the 512-record instance; below that the default limit is enough)
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL(kern, grid, dim3(64 * C4_WAVES), lds, stream, a);
-        return hipGetLastError();
-    };
+    const dim3 block(64 * C4_WAVES);
     if constexpr (RPL < 16) {
-        if (cap == 8) return launch(cov4_kernel<WLOG, 8, RPL, NS, FILLP...>);
-        if (cap == 16) return launch(cov4_kernel<WLOG, 16, RPL, NS, FILLP...>);
+        if (cap == 8) return launch_kernel(cov4_instance<WLOG, 8, RPL, NS, FILL>(), grid, block, lds, stream, a);
+        if (cap == 16) return launch_kernel(cov4_instance<WLOG, 16, RPL, NS, FILL>(), grid, block, lds, stream, a);
     }
-    return launch(cov4_kernel<WLOG, 32, RPL, NS, FILLP...>);
+    return launch_kernel(cov4_instance<WLOG, 32, RPL, NS, FILL>(), grid, block, lds, stream, a);
 }
 
-template <int WLOG, int NS, int... FILLP>
-static hipError_t cov4_launch_rpl_f(const RenderArgs &a, uint32_t rec_cap, dim3 grid, hipStream_t stream, char *name, size_t name_cap)
+template <int WLOG, int NS, int FILL>
+static hipError_t cov4_launch_rpl(const RenderArgs &a, uint32_t rec_cap, dim3 grid, hipStream_t stream, char *name, size_t name_cap)
 {
-    if (rec_cap <= 128u) return cov4_launch_cap<WLOG, 2, NS, FILLP...>(a, grid, stream, name, name_cap);
-    if (rec_cap <= 256u) return cov4_launch_cap<WLOG, 4, NS, FILLP...>(a, grid, stream, name, name_cap);
-    if (rec_cap > 512u) return cov4_launch_cap<WLOG, 16, NS, FILLP...>(a, grid, stream, name, name_cap);
-    return cov4_launch_cap<WLOG, 8, NS, FILLP...>(a, grid, stream, name, name_cap);
+    if (rec_cap <= 128u) return cov4_launch_cap<WLOG, 2, NS, FILL>(a, grid, stream, name, name_cap);
+    if (rec_cap <= 256u) return cov4_launch_cap<WLOG, 4, NS, FILL>(a, grid, stream, name, name_cap);
+    if (rec_cap > 512u) return cov4_launch_cap<WLOG, 16, NS, FILL>(a, grid, stream, name, name_cap);
+    return cov4_launch_cap<WLOG, 8, NS, FILL>(a, grid, stream, name, name_cap);
 }
-// fill: the FR_FILL_CONSISTENT twin of every instance (same launch shape and LDS)
-template <int WLOG, int NS>
-static hipError_t cov4_launch_rpl(const RenderArgs &a, uint32_t rec_cap, dim3 grid, hipStream_t stream, char *name, size_t name_cap, int fill)
+
+template <int FILL>
+static hipError_t cov4_launch_ns(const RenderArgs &a, uint32_t rec_cap, int ns, dim3 grid, hipStream_t stream, char *name, size_t name_cap)
 {
-    if (fill) return cov4_launch_rpl_f<WLOG, NS, 1>(a, rec_cap, grid, stream, name, name_cap);
-    return cov4_launch_rpl_f<WLOG, NS>(a, rec_cap, grid, stream, name, name_cap);
+    if (ns == 4) {
+        if (a.strip_w == 256u) return cov4_launch_rpl<4, 4, FILL>(a, rec_cap, grid, stream, name, name_cap);
+        if (a.strip_w == 128u) return cov4_launch_rpl<3, 4, FILL>(a, rec_cap, grid, stream, name, name_cap);
+        if (a.strip_w == 64u) return cov4_launch_rpl<2, 4, FILL>(a, rec_cap, grid, stream, name, name_cap);
+    } else if (ns == 2) {
+        if (a.strip_w == 256u) return cov4_launch_rpl<4, 2, FILL>(a, rec_cap, grid, stream, name, name_cap);
+        if (a.strip_w == 128u) return cov4_launch_rpl<3, 2, FILL>(a, rec_cap, grid, stream, name, name_cap);
+        if (a.strip_w == 64u) return cov4_launch_rpl<2, 2, FILL>(a, rec_cap, grid, stream, name, name_cap);
+    }
+    return hipErrorInvalidValue;
 }
 
 // jobs: cells of any size up to 2048 / ns sample rows (strips of a.strip_w in {64, 128, 256} pixels, wave bands of 64 / ns
@@ -216,17 +188,8 @@ static hipError_t cov4_launch_rpl(const RenderArgs &a, uint32_t rec_cap, dim3 gr
 hipError_t launch_cov4(const RenderArgs &a, uint32_t rec_cap, int ns, hipStream_t stream, bool launch, char *name, size_t name_cap, int fill)
 {
     const dim3 grid(launch ? (uint32_t)((size_t)a.n_jobs * a.band_groups * a.strips) : 0u);
-    if (ns == 4) {
-        if (a.strip_w == 256u) return cov4_launch_rpl<4, 4>(a, rec_cap, grid, stream, name, name_cap, fill);
-        if (a.strip_w == 128u) return cov4_launch_rpl<3, 4>(a, rec_cap, grid, stream, name, name_cap, fill);
-        if (a.strip_w == 64u) return cov4_launch_rpl<2, 4>(a, rec_cap, grid, stream, name, name_cap, fill);
-    } else if (ns == 2) {
-        if (a.strip_w == 256u) return cov4_launch_rpl<4, 2>(a, rec_cap, grid, stream, name, name_cap, fill);
-        if (a.strip_w == 128u) return cov4_launch_rpl<3, 2>(a, rec_cap, grid, stream, name, name_cap, fill);
-        if (a.strip_w == 64u) return cov4_launch_rpl<2, 2>(a, rec_cap, grid, stream, name, name_cap, fill);
-    }
-    return hipErrorInvalidValue;
+    if (fill) return cov4_launch_ns<1>(a, rec_cap, ns, grid, stream, name, name_cap);
+    return cov4_launch_ns<0>(a, rec_cap, ns, grid, stream, name, name_cap);
 }
 
 }  // namespace fr
-

@@ -111,7 +111,7 @@
                     csum += c[i];
                 }
             }
-            const uint32_t incl = c4_wave_incl_add(csum);
+            const uint32_t incl = wave_incl_add(csum);
             tot = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
             if (tot) {
                 off0 = incl - csum;
@@ -144,7 +144,7 @@
               for (uint32_t base = 0; base < npairs; base += (uint32_t)C4_PCAP) {
                 // markers: slot `off - base` of the chunk holds k + 1 where record k's run starts, 0 elsewhere
                 if (C4_PCAP >= 512 || lane < C4_PCAP / 8) reinterpret_cast<uint4 *>(s_pairs)[lane] = make_uint4(0, 0, 0, 0);
-                c4_wave_lds_sync();
+                wave_lds_sync();
                 {
                     uint32_t off = off0 - base;    // (wraps below the chunk: an unsigned compare takes both ends)
 #pragma unroll
@@ -153,15 +153,15 @@
                         off += c[i];
                     }
                 }
-                c4_wave_lds_sync();
+                wave_lds_sync();
                 const uint32_t nhere = min(npairs - base, (uint32_t)C4_PCAP);
                 // one pair per lane per trip; the marker max-scan of the NEXT 64 pairs is issued before the
                 // current 64 are evaluated (an independent chain that fills the evaluation's wait states)
-                uint32_t k_cur = max(c4_wave_incl_max((uint32_t)s_pairs[lane]), carry);
+                uint32_t k_cur = max(wave_incl_max((uint32_t)s_pairs[lane]), carry);
                 carry = (uint32_t)__builtin_amdgcn_readlane((int)k_cur, 63);
                 for (uint32_t p0 = 0; p0 < nhere && C4_ABL_KEEP(3); p0 += 64u) {
                     const uint32_t pn = min(p0 + 64u + lane, (uint32_t)C4_PCAP - 1u);
-                    const uint32_t s_next = c4_wave_incl_max((uint32_t)s_pairs[pn]);
+                    const uint32_t s_next = wave_incl_max((uint32_t)s_pairs[pn]);
                     {
                         const uint32_t p = base + p0 + lane, k1 = k_cur;
                         const bool livep = p < npairs;
@@ -177,10 +177,10 @@
 #endif
                         const Rec40 r = *reinterpret_cast<const Rec40 *>(smem + raddr);
                         const float cyr = s_cy[row & 63u];
-                        // records are ordered quadratic first, linear last, so a trip is nearly always of one kind:
-                        // KIND 1 = all quadratic, 2 = all linear (no delta, no square root), 0 = mixed (both + a select)
+                        // KIND 1 = all quadratic, 2 = all linear (no delta, no square root), 0 = mixed (both + a select).
+                        // Only KIND 0 is built: single-kind trips saved 87 vector instructions per wave on C3 but ran 2 % slower
+                        // (58 more branches); the body keeps its KIND-generic shape, which fixes its code generation.
                         const unsigned long long linm = __builtin_amdgcn_sicmp((int32_t)r.fr, 0, 40 /* ICMP_SLT */);
-                        const unsigned long long livem = __ballot(livep);
                         auto body = [&](auto kind) {
                             constexpr int KIND = decltype(kind)::value;
                             // the reference's operation order, one rounding per operation (:51, :58-61, :53/:65, :67);
@@ -226,20 +226,12 @@
                                 rowlist[min(pos, (uint32_t)CAP)] = (uint16_t)(((uint32_t)J << 2) | code);   // (slot CAP: the dump)
                             }
                         };
-#if defined(FR_C4_KINDS)
-                        // (measured: 87 vector instructions fewer per wave on C3, yet 2 % slower — 58 more branches; off)
-                        if ((linm & livem) == 0ull) body(std::integral_constant<int, 1>{});
-                        else if ((~linm & livem) == 0ull) body(std::integral_constant<int, 2>{});
-                        else body(std::integral_constant<int, 0>{});
-#else
-                        (void)livem;
                         body(std::integral_constant<int, 0>{});
-#endif
                     }
                     k_cur = max(s_next, carry);
                     carry = (uint32_t)__builtin_amdgcn_readlane((int)k_cur, 63);
                 }
-                c4_wave_lds_sync();
+                wave_lds_sync();
               }
             }
         };
@@ -260,7 +252,7 @@
                 if (!edge) c4_store16(dst, z);
                 else c4_store_clip(dst, z, yl < hlim ? (int)wlim - (int)(16u * wx) : 0);
             }
-            c4_wave_lds_sync();
+            wave_lds_sync();
             continue;
         }
         // ---- pull my list into registers and sort it by J (network size = the wave's fullest row)
@@ -277,13 +269,13 @@
                 for (int q = 0; q < 16; ++q) dd[q] = blank ? 0xfffdfffdu : dd[q];
             }
             if (CAP > 16 && __ballot(n > 16u && !blank) != 0ull) {
-                c4_packed_sort<16>(dd); H = 16u;
+                packed_sort<16>(dd); H = 16u;
                 mx = __ballot(n > 28u) ? 32u : (__ballot(n > 24u) ? 28u : (__ballot(n > 20u) ? 24u : 20u));
             } else if (CAP > 8 && __ballot(n > 8u && !blank) != 0ull) {
-                c4_packed_sort<8>(dd); H = 8u;
+                packed_sort<8>(dd); H = 8u;
                 mx = __ballot(n > 12u) ? 16u : 12u;
             } else {
-                c4_packed_sort<4>(dd); H = 4u;
+                packed_sort<4>(dd); H = 4u;
                 mx = __ballot(n > 4u) ? 8u : 4u;
             }
         };
@@ -314,7 +306,7 @@
                 eval_pass(NCOL / 2u, NCOL / 2u);             // J in (NCOL / 2, NCOL]
                 const uint32_t cr = s_cnt[lane];
                 pull_sort(d, cr, cr > (uint32_t)CAP, Hcur, maxcnt);
-                c4_wave_lds_sync();
+                wave_lds_sync();
                 init_lists();
                 eval_pass(0u, NCOL / 2u);                    // J in [1, NCOL / 2]
                 const uint32_t cl = s_cnt[lane];
@@ -329,7 +321,7 @@
         }
         if (!split) pull_sort(d, cnt, ovf, Hcur, maxcnt);
         const unsigned long long ovf_rows = __ballot(ovf);
-        c4_wave_lds_sync();                        // the list region becomes E below
+        wave_lds_sync();                        // the list region becomes E below
 #ifdef FR_C4_STATS
         // diagnostic build only (make variant NAME=c4stats DEFS=-DFR_C4_STATS): per wave band — sort tier, crossings, over-full rows
         if (lane == 0) {
@@ -338,7 +330,7 @@
             atomicAdd(&g_c4_stats[4], (unsigned long long)__popcll(ovf_rows));                 // over-full sample rows
         }
         {
-            const uint32_t csum = c4_wave_incl_add(cnt);
+            const uint32_t csum = wave_incl_add(cnt);
             if (lane == 63) atomicAdd(&g_c4_stats[5], (unsigned long long)csum);               // crossings kept (J > 0)
             const unsigned long long g8 = __ballot(cnt > 8u), g16 = __ballot(cnt > 16u), g32 = __ballot(cnt > 32u);
             if (lane == 0) {
@@ -359,7 +351,7 @@
             for (uint32_t q = 0; q < (NZ + 63u) / 64u; ++q)
                 if (NZ % 64u == 0u || lane + 64u * q < NZ) z[lane + 64u * q] = bias;
         }
-        c4_wave_lds_sync();
+        wave_lds_sync();
         // ---- toggles: right to left with the running winding; a crossing that changes zero <-> non-zero adds
         // its two differences to my pixel row's bytes
         if (C4_ABL_KEEP(2)) {
@@ -451,7 +443,7 @@
                 if constexpr (L::WD != 0u) {
                     for (uint32_t q = lane; q < NCOL * 2u / 16u; q += 64u)
                         reinterpret_cast<uint4 *>(s_wd)[q] = make_uint4(0x40004000u, 0x40004000u, 0x40004000u, 0x40004000u);
-                    c4_wave_lds_sync();
+                    wave_lds_sync();
                     auto add = [&](uint32_t k) {
                         int J; uint32_t step;
                         evaluate(k, cy_r, J, step);
@@ -487,7 +479,7 @@
                         for (int i = 0; i < RPL; ++i)
                             if ((hm[i] >> lane) & 1ull) add(per * lane + (uint32_t)i);
                     }
-                    c4_wave_lds_sync();
+                    wave_lds_sync();
                     int tot = 0;
                     if (16u * lane < NCOL) {
                         const uint4 lo4 = reinterpret_cast<const uint4 *>(s_wd)[2u * lane], hi4 = reinterpret_cast<const uint4 *>(s_wd)[2u * lane + 1u];
@@ -501,7 +493,7 @@
 #pragma unroll
                         for (int c = 0; c < 16; ++c) wcol[c] = 0;
                     }
-                    const uint32_t incl = c4_wave_incl_add((uint32_t)tot);
+                    const uint32_t incl = wave_incl_add((uint32_t)tot);
                     const int right = (int)((uint32_t)__builtin_amdgcn_readlane((int)incl, 63) - incl);   // everything right of my 16 columns
 #pragma unroll
                     for (int c = 0; c < 16; ++c) wcol[c] += right;
@@ -542,10 +534,10 @@
                                          ((uint32_t)(cq[4 * dq + 2] - cq[4 * dq + 1]) << 16) + ((uint32_t)(cq[4 * dq + 3] - cq[4 * dq + 2]) << 24);
                     if (16u * lane < NCOL) atomicAdd(reinterpret_cast<uint32_t *>(s_E + (r >> LN) * L::EROW) + lane * (uint32_t)(PPL / 4) + (uint32_t)dq, val);
                 }
-                c4_wave_lds_sync();
+                wave_lds_sync();
             }
         }
-        c4_wave_lds_sync();
+        wave_lds_sync();
 
         // ---- windows: lane = one 16-pixel window of one pixel row; integrate, map, one 16-byte store
         constexpr uint32_t K1 = 0x01010101u;
@@ -576,16 +568,16 @@
             const uint32_t T = (x3 >> 24) - 16u;                            // my window's total (signed)
             uint32_t inc = T;
             if (WLOG == 4) {
-                inc += c4_dpp0<0x111>(inc);                                 // row_shr:1 within the 16 lanes of my pixel row
-                inc += c4_dpp0<0x112>(inc);
-                inc += c4_dpp0<0x114>(inc);
-                inc += c4_dpp0<0x118>(inc);
+                inc += dpp<0x111>(inc);                                 // row_shr:1 within the 16 lanes of my pixel row
+                inc += dpp<0x112>(inc);
+                inc += dpp<0x114>(inc);
+                inc += dpp<0x118>(inc);
             } else {
                 // 8 (4) windows per pixel row: two (four) pixel rows share a DPP row — keep the scan inside each part
                 uint32_t s;
-                s = c4_dpp0<0x111>(inc); inc += (wxw >= 1u) ? s : 0u;
-                s = c4_dpp0<0x112>(inc); inc += (wxw >= 2u) ? s : 0u;
-                if (WLOG == 3) { s = c4_dpp0<0x114>(inc); inc += (wxw >= 4u) ? s : 0u; }
+                s = dpp<0x111>(inc); inc += (wxw >= 1u) ? s : 0u;
+                s = dpp<0x112>(inc); inc += (wxw >= 2u) ? s : 0u;
+                if (WLOG == 3) { s = dpp<0x114>(inc); inc += (wxw >= 4u) ? s : 0u; }
             }
             const uint32_t cin = inc - T;                                   // in [0, NS^2]
             const uint32_t cb4 = __builtin_amdgcn_perm(cin, cin, 0x00000000u);
@@ -619,5 +611,5 @@
                 for (uint32_t it = 0; it < (PRB * NWIN) / 64u; ++it) window_pass(it, std::true_type{});
             }
         }
-        c4_wave_lds_sync();                        // E is the next band's list region
+        wave_lds_sync();                        // E is the next band's list region
     }

@@ -104,6 +104,19 @@ struct RenderArgs {
     uint32_t nwin_log, lds_region, lds_rec_bytes, lds_wave_bytes, lds_tail;   // filled by launch_render (LDS plan)
 };
 
+// one launch of a coverage / winding kernel with `lds` bytes of dynamic LDS (above the default 48 KB limit the kernel's
+// attribute is raised first) -> the launch's error
+template <typename K>
+inline hipError_t launch_kernel(K *kern, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const RenderArgs &a)
+{
+    if (lds > 48 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kern, grid, block, lds, stream, a);
+    return hipGetLastError();
+}
+
 // order-preserving map binary32 -> u32 (total order, -0 < +0)
 __host__ __device__ inline uint32_t f2key(float f)
 {

@@ -1,6 +1,6 @@
 // fr_render_kernel.inc — the body of render_kernel (fr_render.hip), included by its two kernel templates (FILL = 0 / 1).
     constexpr uint32_t WBAND = 64u / N;         // pixel rows per wave band (64 sample rows)
-    constexpr uint32_t PARTS = FR_BAND_PARTS;   // 1: whole band at once (8 KB of masks per wave); 2: two half bands (4 KB)
+    constexpr uint32_t PARTS = 1u;             // the whole band in one part (kept as a one-trip loop below: its shape fixes the register allocation)
     constexpr uint32_t PROWS_S = 64u / PARTS;   // sample rows per part
     constexpr uint32_t HROWS = PROWS_S / N;     // pixel rows per part
     constexpr int WCOLS = 16 * N;               // sample columns per 16-pixel window (<= 64)
@@ -10,7 +10,6 @@
     extern __shared__ __align__(16) unsigned char smem[];
 
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    STAMP_INIT();
     // workgroup -> (job, band group, strip); one workgroup per cell is the common case (no divisions)
     uint32_t bid = blockIdx.x, strip = 0, bgrp = 0;
     if (A.strips != 1u) { strip = bid % A.strips; bid /= A.strips; }
@@ -27,7 +26,7 @@
     const int phase = A.phase_center;
     const uint32_t nwin_log = UNI ? (uint32_t)(UNI ? WLOG : 0) : A.nwin_log;   // windows per row, padded to 2^k
     const uint32_t nwin_pad = 1u << nwin_log;
-    const uint32_t mrow = nwin_pad + FR_MASK_PAD;                // 64-bit words per mask line
+    const uint32_t mrow = nwin_pad + MASK_PAD;                // 64-bit words per mask line
 
     const uint32_t g = job.glyph;
     const uint32_t seg0 = A.job_seg[2u * (size_t)jidx], nseg = A.job_seg[2u * (size_t)jidx + 1u];   // (loaded with the job)
@@ -39,14 +38,14 @@
     const uint32_t rec_cnt = fused ? 2u * nseg : A.glyph_rec_count[g];
 
     // LDS: padded cx table | staged records (<= 256, read-only while waves walk them) |
-    //      per-wave half-band region (window masks or breakpoint rows) | per-wave fill[32]
+    //      per-wave band region (window masks or breakpoint rows) | per-wave fill[64]
     // s_cxp[0] = -inf, s_cxp[1 + j] = cx(j), s_cxp[1 + ncol] = +inf
     float *s_cxp = reinterpret_cast<float *>(smem);
     Rec *s_rec = reinterpret_cast<Rec *>(smem + A.lds_region);                          // [RCHUNK]
     unsigned char *wregion = smem + A.lds_region + A.lds_rec_bytes + (size_t)wave * A.lds_wave_bytes;
-    unsigned long long *s_mask = reinterpret_cast<unsigned long long *>(wregion);    // [32][nwin_pad]
-    uint32_t *s_row = reinterpret_cast<uint32_t *>(wregion);                         // [32][CAP]
-    uint32_t *s_fill = reinterpret_cast<uint32_t *>(smem + A.lds_tail + (size_t)wave * TAIL_BYTES);   // [PROWS_S]
+    unsigned long long *s_mask = reinterpret_cast<unsigned long long *>(wregion);    // [64][mrow]
+    uint32_t *s_row = reinterpret_cast<uint32_t *>(wregion);                         // [64][CAP]
+    uint32_t *s_fill = reinterpret_cast<uint32_t *>(smem + A.lds_tail + (size_t)wave * TAIL_BYTES);   // [64]
 
     // Every staged record swaps its bracket [lo, hi] (ray heights) for the EXACT half-open range
     // [ra, re) of this cell's sample rows whose cy lies in it — cy(r) is non-increasing in r, so
@@ -124,13 +123,9 @@
         rra[i] = have ? __builtin_bit_cast(uint32_t, s_rec[kk].lo) : 1u;
         rre[i] = have ? __builtin_bit_cast(uint32_t, s_rec[kk].hi) : 0u;
     }
-    STAMP(0);                                   // setup: job, record staging, cx table
 
   // wave w takes wave bands band_first + w, + 4, ...; every wave runs the same trip count so the
   // (rare) multi-chunk restaging barriers line up
-#if defined(FR_ABLATE) && FR_ABLATE == 20
-  if (A.n_jobs != 0xffffffffu) { if (rra[0] + rre[1] + rra[2] + rre[3] == 0x12345u) s_fill[0] = 1u; return; }   // timing-only: set-up alone
-#endif
   for (uint32_t band0 = band_first; band0 < band_end; band0 += NW) {
     const uint32_t band = band0 + wave;
     const bool band_valid = band < band_end;
@@ -177,21 +172,14 @@
     const uint32_t row_b0 = band * 64u;         // first sample row of my band (global in the cell)
     auto eval_pairs = [&]() {
         wave_lds_sync();
-        STAMP(1);                               // pair layout
-        COUNT(9, npairs);
         // one pair per lane: evaluate, find its sample column, append to its row's list.  `k1` = the
         // pair's record + 1 (from the marker scan).  Slots past npairs hold no marker (the buffer is
         // zeroed per band): lanes past the end decode the last record and a row that may lie outside
         // the band — they compute like the others (no divergence) and are kept from the table walk and
         // the append by `live`.
         auto eval_one = [&](uint32_t p, uint32_t k1) {
-#if defined(FR_ABLATE) && (FR_ABLATE == 10 || FR_ABLATE == 21)
-            const bool live = p < npairs && A.n_jobs == 0xffffffffu;    // timing-only: pairs are collected, never evaluated
-            if (live) {
-#else
             const bool live = p < npairs;
             {
-#endif
                 const uint32_t kk = k1 - 1u;
                 // (< 64 when live; a lane past the end lands on a row index < 128: still inside s_cy | s_cnt)
                 const uint32_t row = (uint32_t)((int32_t)p + (int32_t)s_roff[kk]);
@@ -224,22 +212,14 @@
                 const float gf = __builtin_amdgcn_fmed3f(__builtin_fmaf(xx, jscale, -joff), 0.0f, ncolf);
                 int J = (int)gf;
                 {
-#if defined(FR_ABLATE) && FR_ABLATE == 11
-                    const float c0 = xx, c1 = xx + 1.0f;             // timing-only: no table look-up
-#else
                     const float c0 = s_cxp[J], c1 = s_cxp[J + 1];    // one ds_read2_b32
-#endif
                     const bool good = (c0 <= xx) & (xx < c1);        // '&': both loads issue together
                     if (!good & live) {
                         while (s_cxp[J + 1] <= xx) ++J;          // +inf sentinel stops it at ncol
                         while (s_cxp[J] > xx) --J;               // -inf sentinel stops it at 0
                     }
                 }
-#if defined(FR_ABLATE) && FR_ABLATE == 12
-                if (live & accepted & (J > 0) && A.n_jobs == 0xffffffffu) {  // timing-only: evaluated, never appended
-#else
                 if (live & accepted & (J > 0)) {
-#endif
                     const uint32_t pos = atomicAdd(&s_cnt[row], 1u);
                     // a row's list has room for CAP slots + 8 of padding: slot 32 + is a dump nobody reads
                     uint16_t *rowlist = s_lists + __umul24(row, LSTRIDE);
@@ -261,7 +241,6 @@
         }
         wave_lds_sync();
         npairs = 0;
-        STAMP(2);                               // pair evaluation
     };
 
     // fast layout: all (<= 256) records in ONE prefix sum — a lane's four runs follow one another
@@ -275,9 +254,6 @@
             c[i] = r1 > r0[i] ? r1 - r0[i] : 0u;
             csum += c[i];
         }
-#if defined(FR_ABLATE) && FR_ABLATE == 8
-        csum = (A.n_jobs == 0xffffffffu) ? csum : 0u;                  // timing-only: no walk
-#endif
         const uint32_t incl = wave_incl_add(csum);
         const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
         if (tot <= PCAP) {                      // (wave-uniform) else: the generic path below, with flushes
@@ -285,11 +261,7 @@
             uint32_t ro[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-#if defined(FR_ABLATE) && FR_ABLATE == 8
-                if (c[i] && A.n_jobs == 0xffffffffu) {
-#else
                 if (c[i]) {
-#endif
                     s_pairs[off] = (uint16_t)(4u * lane + (uint32_t)i + 1u);
                 }
                 ro[i] = (r0[i] - row_b0 - off) & 0xffffu;           // row offset of the run (unused if the run is empty)
@@ -309,11 +281,7 @@
             if (tid < RCHUNK && base + tid < rec_cnt) s_rec[tid] = stage(grec[base + tid]);
             __syncthreads();
         }
-#if defined(FR_ABLATE) && FR_ABLATE == 8
-        const uint32_t nchunk = (A.n_jobs == 0xffffffffu) ? 1u : 0u;   // timing-only: no walk
-#else
         const uint32_t nchunk = min(RCHUNK, rec_cnt - base);
-#endif
         for (uint32_t cb = 0; cb < nchunk && nrows; cb += 64u) {
             // lane = record: clip its row range to my band, prefix-sum the run lengths
             const uint32_t k = cb + lane;
@@ -341,9 +309,6 @@
         if (npairs) { eval_pairs(); if (base + RCHUNK < rec_cnt) zero_markers(); }   // before the staged records are replaced / the band ends
     }
     cnt = s_cnt[lane];
-    COUNT(8, 1);                                // wave bands
-    COUNT(11, cnt);                             // crossings of lane 0's row (x64 ~ per band)
-    STAMP(1);                                   // pair layout (remainder)
     if (!nrows) continue;                       // this wave has no band in this round (no barriers below)
     if (__ballot(cnt != 0u) == 0ull) {
         // ---- no crossing on any of my 64 sample rows: every winding is 0 — store the band's
@@ -352,11 +317,7 @@
         const uint32_t prows_b = nrows / N;
         const uint32_t wx = lane & (nwin_pad - 1u);
         const uint32_t px0 = wx * 16u;
-#if defined(FR_ABLATE) && (FR_ABLATE == 21 || FR_ABLATE == 8)
-        if (px0 < sw && A.n_jobs == 0xffffffffu) {      // timing-only: no background stores
-#else
         if (px0 < sw) {
-#endif
             const uint32_t nvalid = min(16u, sw - px0);
             for (uint32_t yl = lane >> nwin_log; yl < prows_b; yl += (64u >> nwin_log)) {
                 const size_t eidx = ((size_t)job.out_y + y0 + yl) * A.out_stride + out_col0 + px0;
@@ -405,10 +366,7 @@
             maxcnt = __ballot(cnt > 4u) ? 8u : 4u;
         }
     }
-    COUNT(10, (unsigned long long)(maxcnt <= 8u) | ((unsigned long long)(maxcnt > 8u && maxcnt <= 12u) << 16) |
-                  ((unsigned long long)(maxcnt > 12u && maxcnt <= 16u) << 32) | ((unsigned long long)(maxcnt > 16u) << 48));
     wave_lds_sync();                            // the list region becomes the mask region below
-    STAMP(3);                                   // list pull + sort
     // rows with more than CAP crossings (combs, pathological outlines) take the direct sum over the
     // glyph's records — same integers, slow, rare: the coverage modes write the row's window masks from it,
     // the winding-value modes its pixels.
@@ -473,7 +431,7 @@
             {
                 uint4 *z = reinterpret_cast<uint4 *>(wregion);
                 if (nwin_log == 4u) {           // 256-px strip: a fixed number of stores per lane, no loop
-                    constexpr uint32_t NZ = PROWS_S * (16u + FR_MASK_PAD) / 2u;    // 16-byte units
+                    constexpr uint32_t NZ = PROWS_S * (16u + MASK_PAD) / 2u;    // 16-byte units
 #pragma unroll
                     for (uint32_t q = 0; q < (NZ + 63u) / 64u; ++q)
                         if (NZ % 64u == 0u || lane + 64u * q < NZ) z[lane + 64u * q] = make_uint4(0, 0, 0, 0);
@@ -483,11 +441,7 @@
             }
             wave_lds_sync();
             // ---- phase 1b: my row's toggles -> window masks (LDS, XOR), fill parity
-#if defined(FR_ABLATE) && FR_ABLATE == 2
-            if (mine_half && A.n_jobs == 0xffffffffu) {     // timing-only: no toggles
-#else
             if (mine_half) {
-#endif
                 unsigned long long *line = s_mask + mask_line(hrow) * mrow;
                 uint32_t fill = 0;
                 // right to left: `run` = winding right of the slots handled so far; a slot toggles
@@ -551,7 +505,6 @@
                 }
                 wave_lds_sync();
             }
-            STAMP(4);                           // phase 1b: zero + toggles (+ over-full rows)
 
             // ---- phase 2: one lane per 16-pixel window
             // window (yl, wx) = pixels [16 wx, 16 wx + 16) of the half's pixel row yl.  Whether 16-byte
@@ -560,11 +513,6 @@
             auto store_window = [&](uint32_t yl, uint32_t wxx, const uint32_t (&pk)[4]) {
                 const uint32_t px = wxx * 16u;
                 uint8_t *dst = out_half + (size_t)yl * A.out_stride + px;
-#if defined(FR_ABLATE) && FR_ABLATE == 13
-                if ((pk[0] ^ pk[1] ^ pk[2] ^ pk[3]) == 0x12345678u) {            // timing-only: windows computed, (almost) never stored
-                    *reinterpret_cast<uint4 *>(dst) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
-                }
-#else
                 if (sw - px >= 16u) {
                     // one 16-byte store, aligned or not (global memory takes unaligned vector stores)
                     const uint4 v = make_uint4(pk[0], pk[1], pk[2], pk[3]);
@@ -573,7 +521,6 @@
                     const uint32_t nvalid = min(16u, sw - px);
                     for (uint32_t p = 0; p < nvalid; ++p) dst[p] = (uint8_t)(pk[p >> 2] >> (8 * (p & 3)));
                 }
-#endif
             };
             auto popcount_window = [&](uint32_t yl, uint32_t wxx) {
                 unsigned long long mask[N];
@@ -631,12 +578,7 @@
                 store_window(yl, wxx, pk);
             };
             const uint32_t wx = lane & (nwin_pad - 1u);
-#if defined(FR_ABLATE) && FR_ABLATE == 3
-            const bool win_on = A.n_jobs == 0xffffffffu;    // timing-only: no windows, no stores
-#else
-            const bool win_on = true;
-#endif
-            if (wx * 16u < sw && win_on) {
+            if (wx * 16u < sw) {
                 if (nwin_log == 4u && prows == 16u && N == 4) {
                     // the common full case (256-px strip, 16 pixel rows): four windows per lane, no loop
 #pragma unroll
@@ -646,7 +588,6 @@
                 }
             }
             wave_lds_sync();                    // masks are re-zeroed by the next half / band
-            STAMP(5);                           // phase 2: windows + stores
         } else {
             // ---- winding-value modes (N == 1): breakpoints (b_i, winding on [b_{i-1}, b_i)) per row
             if (mine_half) {
@@ -749,4 +690,3 @@
         }
     }   // half band
   }   // band loop
-  STAMP_FLUSH();

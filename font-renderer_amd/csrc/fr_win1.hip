@@ -55,12 +55,6 @@ struct W1Lds {
     static constexpr uint32_t TOTAL = OFF_CYT + 1024u;
 };
 
-__device__ __forceinline__ uint32_t w1_gray(int w)
-{
-    const int v = w * 20 + 100;                     // render_glyph.zig:28
-    return (uint32_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
-}
-
 // the first m of a window's 16 pixels (m <= 0: none), ESZ bytes each: a (and b, the second half of 16 int16 values)
 template <uint32_t ESZ>
 __device__ __forceinline__ void w1_store_clip(unsigned char *dst, uint4 a, uint4 b, int m)
@@ -111,40 +105,43 @@ void win1_kernel(const RenderArgs A)
 
 uint32_t win1_band_rows() { return W1_ROWS; }
 
-template <int WLOG, int RPL, int... FILLP>
+// FILL = 1: the FR_FILL_CONSISTENT twin of an instance (same launch shape and LDS)
+template <int WLOG, int MODE, int RPL, int FILL>
+static auto win1_instance()
+{
+    if constexpr (FILL) return win1_kernel<WLOG, MODE, RPL, 1>;
+    else return win1_kernel<WLOG, MODE, RPL>;
+}
+
+template <int WLOG, int RPL, int FILL>
 static hipError_t win1_launch_mode(const RenderArgs &a, int mode, dim3 grid, hipStream_t stream, char *name, size_t name_cap)
 {
     const size_t lds = W1Lds<WLOG, RPL>::TOTAL + a.lds_pad;
-    if (name) snprintf(name, name_cap, sizeof...(FILLP) ? "fr::win1_kernel<%d, %d, %d, 1>" : "fr::win1_kernel<%d, %d, %d>", WLOG, mode, RPL);      // as rocprofv3 names the instance
+    if (name) snprintf(name, name_cap, FILL ? "fr::win1_kernel<%d, %d, %d, 1>" : "fr::win1_kernel<%d, %d, %d>", WLOG, mode, RPL);      // as rocprofv3 names the instance
     if (!grid.x) return hipSuccess;               // (name only)
-    auto launch = [&](auto kern) -> hipError_t {
-        if (lds > 48 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL(kern, grid, dim3(64 * C4_WAVES), lds, stream, a);
-        return hipGetLastError();
-    };
-    if (mode == MODE1_WINDING_I16) return launch(win1_kernel<WLOG, MODE1_WINDING_I16, RPL, FILLP...>);
-    if (mode == MODE1_GRAY_DEBUG) return launch(win1_kernel<WLOG, MODE1_GRAY_DEBUG, RPL, FILLP...>);
-    if (mode == MODE1_BITS) return launch(win1_kernel<WLOG, MODE1_BITS, RPL, FILLP...>);
-    return launch(win1_kernel<WLOG, MODE1_MASK, RPL, FILLP...>);
+    const dim3 block(64 * C4_WAVES);
+    if (mode == MODE1_WINDING_I16) return launch_kernel(win1_instance<WLOG, MODE1_WINDING_I16, RPL, FILL>(), grid, block, lds, stream, a);
+    if (mode == MODE1_GRAY_DEBUG) return launch_kernel(win1_instance<WLOG, MODE1_GRAY_DEBUG, RPL, FILL>(), grid, block, lds, stream, a);
+    if (mode == MODE1_BITS) return launch_kernel(win1_instance<WLOG, MODE1_BITS, RPL, FILL>(), grid, block, lds, stream, a);
+    return launch_kernel(win1_instance<WLOG, MODE1_MASK, RPL, FILL>(), grid, block, lds, stream, a);
 }
 
-template <int WLOG, int... FILLP>
-static hipError_t win1_launch_rpl_f(const RenderArgs &a, int mode, uint32_t rec_cap, dim3 grid, hipStream_t stream, char *name, size_t name_cap)
+template <int WLOG, int FILL>
+static hipError_t win1_launch_rpl(const RenderArgs &a, int mode, uint32_t rec_cap, dim3 grid, hipStream_t stream, char *name, size_t name_cap)
 {
-    if (rec_cap <= 128u) return win1_launch_mode<WLOG, 2, FILLP...>(a, mode, grid, stream, name, name_cap);
-    if (rec_cap <= 256u) return win1_launch_mode<WLOG, 4, FILLP...>(a, mode, grid, stream, name, name_cap);
-    if (rec_cap > 512u) return win1_launch_mode<WLOG, 16, FILLP...>(a, mode, grid, stream, name, name_cap);
-    return win1_launch_mode<WLOG, 8, FILLP...>(a, mode, grid, stream, name, name_cap);
+    if (rec_cap <= 128u) return win1_launch_mode<WLOG, 2, FILL>(a, mode, grid, stream, name, name_cap);
+    if (rec_cap <= 256u) return win1_launch_mode<WLOG, 4, FILL>(a, mode, grid, stream, name, name_cap);
+    if (rec_cap > 512u) return win1_launch_mode<WLOG, 16, FILL>(a, mode, grid, stream, name, name_cap);
+    return win1_launch_mode<WLOG, 8, FILL>(a, mode, grid, stream, name, name_cap);
 }
-// fill: the FR_FILL_CONSISTENT twin of every instance (same launch shape and LDS)
-template <int WLOG>
-static hipError_t win1_launch_rpl(const RenderArgs &a, int mode, uint32_t rec_cap, dim3 grid, hipStream_t stream, char *name, size_t name_cap, int fill)
+
+template <int FILL>
+static hipError_t win1_launch_strip(const RenderArgs &a, int mode, uint32_t rec_cap, dim3 grid, hipStream_t stream, char *name, size_t name_cap)
 {
-    if (fill) return win1_launch_rpl_f<WLOG, 1>(a, mode, rec_cap, grid, stream, name, name_cap);
-    return win1_launch_rpl_f<WLOG>(a, mode, rec_cap, grid, stream, name, name_cap);
+    if (a.strip_w == 256u) return win1_launch_rpl<4, FILL>(a, mode, rec_cap, grid, stream, name, name_cap);
+    if (a.strip_w == 128u) return win1_launch_rpl<3, FILL>(a, mode, rec_cap, grid, stream, name, name_cap);
+    if (a.strip_w == 64u) return win1_launch_rpl<2, FILL>(a, mode, rec_cap, grid, stream, name, name_cap);
+    return hipErrorInvalidValue;
 }
 
 // jobs: cells of any size up to 2048 rows (strips of a.strip_w in {64, 128, 256} pixels and bands of 16 rows; the last of
@@ -153,10 +150,8 @@ static hipError_t win1_launch_rpl(const RenderArgs &a, int mode, uint32_t rec_ca
 hipError_t launch_win1(const RenderArgs &a, int mode, uint32_t rec_cap, hipStream_t stream, bool launch, char *name, size_t name_cap, int fill)
 {
     const dim3 grid(launch ? (uint32_t)((size_t)a.n_jobs * a.band_groups * a.strips) : 0u);
-    if (a.strip_w == 256u) return win1_launch_rpl<4>(a, mode, rec_cap, grid, stream, name, name_cap, fill);
-    if (a.strip_w == 128u) return win1_launch_rpl<3>(a, mode, rec_cap, grid, stream, name, name_cap, fill);
-    if (a.strip_w == 64u) return win1_launch_rpl<2>(a, mode, rec_cap, grid, stream, name, name_cap, fill);
-    return hipErrorInvalidValue;
+    if (fill) return win1_launch_strip<1>(a, mode, rec_cap, grid, stream, name, name_cap);
+    return win1_launch_strip<0>(a, mode, rec_cap, grid, stream, name, name_cap);
 }
 
 }  // namespace fr

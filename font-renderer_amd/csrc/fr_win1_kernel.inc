@@ -98,7 +98,7 @@
                     c[i] = r1 > r0[i] ? r1 - r0[i] : 0u;
                     csum += c[i];
                 }
-                incl = c4_wave_incl_add(csum);
+                incl = wave_incl_add(csum);
                 tot = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
                 if (tot <= PCAP || span == 1u) break;
                 span >>= 1;
@@ -107,7 +107,7 @@
 #pragma unroll
                 for (uint32_t q = 0; q < (PCAP / 8u + 63u) / 64u; ++q)
                     if (PCAP / 8u % 64u == 0u || lane + 64u * q < PCAP / 8u) reinterpret_cast<uint4 *>(s_pairs)[lane + 64u * q] = make_uint4(0, 0, 0, 0);
-                c4_wave_lds_sync();
+                wave_lds_sync();
                 uint32_t off = incl - csum;
                 uint32_t ro[RPL];
 #pragma unroll
@@ -124,13 +124,13 @@
                         reinterpret_cast<uint4 *>(s_roff + (uint32_t)RPL * lane)[q8] = make_uint4(ro[8 * q8] | (ro[8 * q8 + 1] << 16), ro[8 * q8 + 2] | (ro[8 * q8 + 3] << 16),
                                                                                                   ro[8 * q8 + 4] | (ro[8 * q8 + 5] << 16), ro[8 * q8 + 6] | (ro[8 * q8 + 7] << 16));
                 }
-                c4_wave_lds_sync();
+                wave_lds_sync();
                 const uint32_t npairs = tot;
-                uint32_t k_cur = c4_wave_incl_max((uint32_t)s_pairs[lane]);
+                uint32_t k_cur = wave_incl_max((uint32_t)s_pairs[lane]);
                 uint32_t carry = (uint32_t)__builtin_amdgcn_readlane((int)k_cur, 63);
                 for (uint32_t p0 = 0; p0 < npairs; p0 += 64u) {
                     const uint32_t pn = min(p0 + 64u + lane, PCAP - 1u);
-                    const uint32_t s_next = c4_wave_incl_max((uint32_t)s_pairs[pn]);
+                    const uint32_t s_next = wave_incl_max((uint32_t)s_pairs[pn]);
                     {
                         const uint32_t p = p0 + lane, k1 = k_cur;
                         const bool livep = p < npairs;
@@ -174,11 +174,11 @@
                     k_cur = max(s_next, carry);
                     carry = (uint32_t)__builtin_amdgcn_readlane((int)k_cur, 63);
                 }
-                c4_wave_lds_sync();
+                wave_lds_sync();
             }
             rr0 += span;
         }
-        c4_wave_lds_sync();
+        wave_lds_sync();
         const uint32_t cnt = s_cnt[lane & 15u] & 0xffffu;
         // (bit planes: 32-byte rows, the plane of 256-pixel column x0s / 256 starts h rows after the previous one)
         const size_t row_bytes = (MODE == MODE1_BITS) ? (size_t)32u : (size_t)A.out_stride * ESZ;
@@ -198,7 +198,7 @@
             if (MODE == MODE1_BITS && WLOG == 4) {
                 // (a 256-pixel strip: the band's 512 bytes of sign bits in one store instruction, as below)
                 if (lane < 32u && (lane >> 1) < hlim) { const uint4 z = make_uint4(0, 0, 0, 0); __builtin_memcpy(out_band + 16u * lane, &z, 16); }
-                c4_wave_lds_sync();
+                wave_lds_sync();
                 continue;
             }
             for (uint32_t yl = lane >> WLOG; yl < W1_ROWS; yl += (64u >> WLOG)) {
@@ -211,7 +211,7 @@
                 else if (ESZ == 2u) { __builtin_memcpy(dst, &v, 16); __builtin_memcpy(dst + 16, &v, 16); }
                 else c4_store16(dst, v);
             }
-            c4_wave_lds_sync();
+            wave_lds_sync();
             continue;
         }
         // rows with more than 31 crossings could leave the byte range: the direct path, pixels stored from here
@@ -247,7 +247,7 @@
                 if constexpr (L::WD_LDS) {
                     for (uint32_t q = lane; q < NCOL * 2u / 16u; q += 64u)
                         reinterpret_cast<uint4 *>(s_wd)[q] = make_uint4(0x40004000u, 0x40004000u, 0x40004000u, 0x40004000u);
-                    c4_wave_lds_sync();
+                    wave_lds_sync();
 #pragma unroll
                     for (int i = 0; i < RPL; ++i) {
                         if (rra[i] <= grow && grow < rre[i]) {
@@ -256,7 +256,7 @@
                             if (J > 0) atomicAdd(&s_wd[(uint32_t)(J - 1) >> 1], step << (16u * ((uint32_t)(J - 1) & 1u)));
                         }
                     }
-                    c4_wave_lds_sync();
+                    wave_lds_sync();
                     int tot = 0;
                     if (16u * lane < NCOL) {
                         const uint4 lo4 = reinterpret_cast<const uint4 *>(s_wd)[2u * lane], hi4 = reinterpret_cast<const uint4 *>(s_wd)[2u * lane + 1u];
@@ -270,7 +270,7 @@
 #pragma unroll
                         for (int cc = 0; cc < 16; ++cc) wcol[cc] = 0;
                     }
-                    const uint32_t incl = c4_wave_incl_add((uint32_t)tot);
+                    const uint32_t incl = wave_incl_add((uint32_t)tot);
                     const int right = (int)((uint32_t)__builtin_amdgcn_readlane((int)incl, 63) - incl);
 #pragma unroll
                     for (int cc = 0; cc < 16; ++cc) wcol[cc] += right;
@@ -311,10 +311,10 @@
                         const int w = wcol[cc];
                         if (cc >= mlim) continue;
                         if (MODE == MODE1_WINDING_I16) reinterpret_cast<int16_t *>(dst)[cc] = (int16_t)w;
-                        else dst[cc] = (unsigned char)((MODE == MODE1_GRAY_DEBUG) ? w1_gray(w) : (w != 0 ? 255u : 0u));
+                        else dst[cc] = (unsigned char)((MODE == MODE1_GRAY_DEBUG) ? gray_debug(w) : (w != 0 ? 255u : 0u));
                     }
                 }
-                c4_wave_lds_sync();
+                wave_lds_sync();
             }
         }
 
@@ -329,9 +329,7 @@
         // the stores of a band went out one HBM round trip at a time.  An opaque copy of the lane per band keeps the
         // addresses where they are used: a few integer instructions per window instead.)
         uint32_t lane_w = lane;
-#ifndef FR_W1_LAUNDER_ALL
         if constexpr (!(WLOG == 4 && RPL == 2))
-#endif
         asm volatile("" : "+v"(lane_w));
         const uint32_t wx = lane_w & (NWIN - 1u);
         // my window of pass 0, in E and in the output (a 32-bit offset from the band's wave-uniform base: 16 rows of < 2^27
@@ -354,15 +352,15 @@
             const uint32_t T = (x3 >> 24) - 64u;                            // my window's total (signed)
             uint32_t inc = T;
             if (WLOG == 4) {
-                inc += c4_dpp0<0x111>(inc);
-                inc += c4_dpp0<0x112>(inc);
-                inc += c4_dpp0<0x114>(inc);
-                inc += c4_dpp0<0x118>(inc);
+                inc += dpp<0x111>(inc);
+                inc += dpp<0x112>(inc);
+                inc += dpp<0x114>(inc);
+                inc += dpp<0x118>(inc);
             } else {
                 uint32_t s;
-                s = c4_dpp0<0x111>(inc); inc += (wx >= 1u) ? s : 0u;
-                s = c4_dpp0<0x112>(inc); inc += (wx >= 2u) ? s : 0u;
-                if (WLOG == 3) { s = c4_dpp0<0x114>(inc); inc += (wx >= 4u) ? s : 0u; }
+                s = dpp<0x111>(inc); inc += (wx >= 1u) ? s : 0u;
+                s = dpp<0x112>(inc); inc += (wx >= 2u) ? s : 0u;
+                if (WLOG == 3) { s = dpp<0x114>(inc); inc += (wx >= 4u) ? s : 0u; }
             }
             const int w0 = (int)s_cnt[prow] >> 16;                           // w(0) of my pixel row
             const uint32_t cin = inc - T + 32u + (uint32_t)w0;              // winding entering my window, + 32: in [1, 63]
@@ -444,19 +442,19 @@
             // The band's sign bits are 16 rows x 32 bytes = 512 CONTIGUOUS bytes of the strip's bit plane: through LDS (E has
             // been read) they leave as 32 lanes x 16 bytes — four whole 128-byte lines in one store instruction.  (A row the
             // direct path stored keeps its bits: its two lanes skip.)
-            c4_wave_lds_sync();
+            wave_lds_sync();
             uint16_t *stage = reinterpret_cast<uint16_t *>(s_E);            // [16 rows][16 windows] u16
 #pragma unroll
             for (uint32_t it = 0; it < (W1_ROWS * NWIN) / 64u; ++it) {
                 const uint32_t prow = (lane >> WLOG) + it * (64u >> WLOG);
                 stage[prow * 16u + wx] = (uint16_t)band_bits[it];
             }
-            c4_wave_lds_sync();
+            wave_lds_sync();
             const uint32_t row = lane >> 1;
             if (lane < 32u && row < hlim && !((ovf_rows >> row) & 1u)) {
                 const uint4 v = *reinterpret_cast<const uint4 *>(s_E + 16u * lane);
                 __builtin_memcpy(out_band + 16u * lane, &v, 16);
             }
         }
-        c4_wave_lds_sync();                        // E is re-initialised by the next band
+        wave_lds_sync();                        // E is re-initialised by the next band
     }
