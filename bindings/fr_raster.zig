@@ -48,6 +48,25 @@ pub const Job = extern struct {
     scale: f32,
 };
 
+/// text runs (fr_raster.h: fr_glyph_place / fr_text_run; DESIGN.md section 5): a glyph at a pen position in 1/64 pixel
+/// and a baseline row — what Appli.addChar / getTransform place (src/Appli.zig:318-349) —, and a run that composites
+/// places[first .. first+count) into one w x h image at (out_x, out_y)
+pub const GlyphPlace = extern struct {
+    glyph: u32,
+    pen_x64: i32,
+    pen_y: i32,
+};
+
+pub const TextRun = extern struct {
+    first: u32,
+    count: u32,
+    w: u32,
+    h: u32,
+    out_x: u32,
+    out_y: u32,
+    scale: f32,
+};
+
 // ---- library / context
 pub extern "c" fn fr_abi_version() c_int;
 pub extern "c" fn fr_last_error() [*:0]const u8;
@@ -61,6 +80,7 @@ pub extern "c" fn fr_glyphset_create(ctx: *fr_ctx, points_xy: [*]const i16, cont
 pub extern "c" fn fr_glyphset_destroy(gs: ?*fr_glyphset) void;
 pub extern "c" fn fr_glyphset_prepare(gs: *fr_glyphset) c_int;
 pub extern "c" fn fr_glyphset_stats(gs: *const fr_glyphset, n_segments: ?*u64, n_records: ?*u64) c_int;
+pub extern "c" fn fr_glyphset_set_boxes(gs: *fr_glyphset, boxes: [*]const i16) c_int;
 // ---- batched rasterization
 pub extern "c" fn fr_plan_create(ctx: *fr_ctx, gs: *const fr_glyphset, jobs: [*]const Job, n_jobs: u32, params: *const RasterParams, out: *?*fr_plan) c_int;
 pub extern "c" fn fr_plan_create_ex(ctx: *fr_ctx, gs: *const fr_glyphset, jobs: [*]const Job, n_jobs: u32, params: *const RasterParams, flags: u32, out: *?*fr_plan) c_int;
@@ -70,6 +90,7 @@ pub extern "c" fn fr_plan_render_timed(plan: *fr_plan, out_dev: *anyopaque, out_
 pub extern "c" fn fr_plan_pixels(plan: *const fr_plan) u64;
 pub extern "c" fn fr_plan_stats(plan: *const fr_plan, n_jobs_cov4: ?*u32, n_jobs_general: ?*u32) c_int;
 pub extern "c" fn fr_plan_describe(plan: *const fr_plan, buf: [*]u8, cap: usize) c_int;
+pub extern "c" fn fr_text_plan_create(ctx: *fr_ctx, gs: *const fr_glyphset, places: [*]const GlyphPlace, n_places: u32, runs: [*]const TextRun, n_runs: u32, params: *const RasterParams, flags: u32, out: *?*fr_plan) c_int;
 pub extern "c" fn fr_allgather_bands(ctx: *fr_ctx, nccl_comm: *anyopaque, atlas_dev: *anyopaque, band_bytes: usize) c_int;
 pub extern "c" fn fr_gather_bands(ctx: *fr_ctx, nccl_comm: *anyopaque, atlas_dev: *anyopaque, band_bytes: usize, root: c_int) c_int;
 pub extern "c" fn fr_render_batch(ctx: *fr_ctx, gs: *const fr_glyphset, jobs: [*]const Job, n_jobs: u32, params: *const RasterParams, out_host: *anyopaque, out_stride: usize, out_rows: usize) c_int;
@@ -95,6 +116,7 @@ pub extern "c" fn fr_font_close(font: ?*fr_font) void;
 pub extern "c" fn fr_font_info(font: *const fr_font, units_per_em: ?*u16, num_glyphs: ?*u16, y0_baseline: ?*c_int) c_int;
 pub extern "c" fn fr_font_char_to_glyph(font: *const fr_font, codepoint: u32, glyph_index: *u16) c_int;
 pub extern "c" fn fr_font_glyph_advance(font: *const fr_font, glyph_index: u16, advance_width: *i16) c_int;
+pub extern "c" fn fr_text_layout(font: *const fr_font, codepoints: [*]const u32, n: u32, font_size: u16, glyph_index_out: [*]u16, pen_x64_out: [*]i32, end_pen_x64: ?*i32) c_int;
 pub extern "c" fn fr_font_glyph_measure(font: *fr_font, glyph_index: u16, n_contours: *u32, n_points: *u32, box: *[4]i16) c_int;
 pub extern "c" fn fr_font_glyph_fill(font: *fr_font, glyph_index: u16, points_xy: [*]i16, contour_start: [*]u32) c_int;
 // ---- QOI writer (host side; byte-compatible with tools/qoi.zig, which the Zig host keeps)

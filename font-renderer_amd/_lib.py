@@ -35,6 +35,15 @@ class RasterParams(C.Structure):  # == fr_raster_params
                 ("reserved", C.c_int32)]
 
 
+class GlyphPlace(C.Structure):   # == fr_glyph_place
+    _fields_ = [("glyph", C.c_uint32), ("pen_x64", C.c_int32), ("pen_y", C.c_int32)]
+
+
+class TextRun(C.Structure):      # == fr_text_run
+    _fields_ = [("first", C.c_uint32), ("count", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32),
+                ("out_x", C.c_uint32), ("out_y", C.c_uint32), ("scale", C.c_float)]
+
+
 # every symbol include/fr_raster.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 _I16P, _U32P, _U8P = C.POINTER(C.c_int16), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)
@@ -50,6 +59,7 @@ SYMBOLS = [
     ("fr_glyphset_destroy", None, [_P]),
     ("fr_glyphset_prepare", C.c_int, [_P]),
     ("fr_glyphset_stats", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("fr_glyphset_set_boxes", C.c_int, [_P, _P]),
     ("fr_plan_create", C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(RasterParams), C.POINTER(_P)]),
     ("fr_plan_create_ex", C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(RasterParams), C.c_uint32, C.POINTER(_P)]),
     ("fr_plan_destroy", None, [_P]),
@@ -58,6 +68,8 @@ SYMBOLS = [
     ("fr_plan_pixels", C.c_uint64, [_P]),
     ("fr_plan_stats", C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("fr_plan_describe", C.c_int, [_P, C.c_char_p, C.c_size_t]),
+    ("fr_text_plan_create", C.c_int, [_P, _P, _P, C.c_uint32, _P, C.c_uint32, C.POINTER(RasterParams), C.c_uint32,
+                                      C.POINTER(_P)]),
     ("fr_allgather_bands", C.c_int, [_P, _P, _P, C.c_size_t]),
     ("fr_gather_bands", C.c_int, [_P, _P, _P, C.c_size_t, C.c_int]),
     ("fr_render_batch", C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(RasterParams), _P, C.c_size_t, C.c_size_t]),
@@ -81,6 +93,7 @@ SYMBOLS = [
     ("fr_font_info", C.c_int, [_P, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), C.POINTER(C.c_int)]),
     ("fr_font_char_to_glyph", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint16)]),
     ("fr_font_glyph_advance", C.c_int, [_P, C.c_uint16, C.POINTER(C.c_int16)]),
+    ("fr_text_layout", C.c_int, [_P, _P, C.c_uint32, C.c_uint16, _P, _P, C.POINTER(C.c_int32)]),
     ("fr_font_glyph_measure", C.c_int, [_P, C.c_uint16, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _P]),
     ("fr_font_glyph_fill", C.c_int, [_P, C.c_uint16, _P, _P]),
     ("fr_qoi_bound", C.c_size_t, [C.c_uint32, C.c_uint32]),

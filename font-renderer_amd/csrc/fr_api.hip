@@ -6,6 +6,7 @@
 // without a usable gfx950 device every compute entry point returns FR_E_HIP.
 #include "../../include/fr_raster.h"
 #include "fr_device.hpp"
+#include "fr_text.hpp"
 
 #include <cmath>
 #include <cstdarg>
@@ -14,6 +15,7 @@
 #include <new>
 #include <algorithm>
 #include <dlfcn.h>
+#include <type_traits>
 #include <vector>
 
 namespace fr {
@@ -103,6 +105,7 @@ struct fr_glyphset {
     std::vector<uint32_t> h_glyph_seg_start;    // host copy: plans attach each job's segment range to it
     std::vector<uint32_t> h_root_bound;         // per glyph: candidate roots the vertex rule cannot discard (>= live records)
     std::vector<uint32_t> h_ray_bound;          // per glyph: estimated maximum of the crossings of one horizontal ray
+    std::vector<int16_t> h_box;                 // fr_glyphset_set_boxes: Glyph.box per glyph (x_min, y_min, x_max, y_max); empty until set
 };
 
 struct fr_plan {
@@ -135,6 +138,15 @@ struct fr_plan {
     void *g_out = nullptr;
     size_t g_stride = 0, g_rows = 0;
     uint32_t g_epoch = 0;
+    // a text plan (fr_text_plan_create): its tables (fr_text.hpp), the distinct glyphs whose records prepare_kernel rebuilds
+    // into plan-owned memory before every render, and its counts
+    bool text = false;
+    fr::TextTile *d_tiles = nullptr;
+    fr::TextRun *d_runs = nullptr;
+    fr::TextInst *d_insts = nullptr;
+    uint32_t *d_tlist = nullptr, *d_tglyphs = nullptr, *d_trec_count = nullptr;
+    fr::Rec *d_trecs = nullptr;
+    uint32_t n_tiles = 0, n_insts = 0, n_tglyphs = 0;
 };
 
 template <class T> static void dfree(T *&p) { if (p) { (void)hipFree(p); p = nullptr; } }
@@ -525,6 +537,8 @@ void fr_plan_destroy(fr_plan *plan)
     (void)hipSetDevice(plan->ctx->device);
     (void)hipStreamSynchronize(plan->ctx->stream);
     dfree(plan->d_jobs); dfree(plan->d_job_seg); dfree(plan->d_large); dfree(plan->d_bits); dfree(plan->d_job_bits);
+    dfree(plan->d_tiles); dfree(plan->d_runs); dfree(plan->d_insts); dfree(plan->d_tlist); dfree(plan->d_tglyphs);
+    dfree(plan->d_trec_count); dfree(plan->d_trecs);
     if (plan->ev0) (void)hipEventDestroy(plan->ev0);
     if (plan->ev1) (void)hipEventDestroy(plan->ev1);
     if (plan->gexec) (void)hipGraphExecDestroy(plan->gexec);
@@ -687,11 +701,170 @@ int fr_plan_create_ex(fr_ctx *ctx, const fr_glyphset *gs, const fr_job *jobs, ui
     return FR_OK;
 }
 
+// ---- text runs (include/fr_raster.h) -----------------------------------------------------------
+int fr_glyphset_set_boxes(fr_glyphset *gs, const int16_t *boxes)
+{
+    if (!gs || (gs->n_glyphs && !boxes)) return fail(FR_E_INVALID, "fr_glyphset_set_boxes: NULL argument");
+    for (uint32_t g = 0; g < gs->n_glyphs; ++g)
+        if (boxes[4 * (size_t)g] > boxes[4 * (size_t)g + 2] || boxes[4 * (size_t)g + 1] > boxes[4 * (size_t)g + 3])
+            return fail(FR_E_INVALID, "glyph %u: box min above max", g);
+    gs->h_box.assign(boxes, boxes + 4 * (size_t)gs->n_glyphs);
+    return FR_OK;
+}
+
+int fr_text_plan_create(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place *places, uint32_t n_places,
+                        const fr_text_run *runs, uint32_t n_runs, const fr_raster_params *params, uint32_t flags,
+                        fr_plan **out)
+{
+    if (!ctx || !gs || !out) return fail(FR_E_INVALID, "fr_text_plan_create: NULL argument");
+    *out = nullptr;
+    if (const int frc = check_flags(flags)) return frc;
+    if (gs->ctx != ctx) return fail(FR_E_INVALID, "glyph set belongs to another context");
+    if (!params) return fail(FR_E_INVALID, "params is NULL");
+    if (params->mode < FR_WINDING_I16 || params->mode > FR_SDF_U8) return fail(FR_E_INVALID, "unknown mode %d", params->mode);
+    if (params->sample_phase != FR_SAMPLE_CORNER && params->sample_phase != FR_SAMPLE_CENTER)
+        return fail(FR_E_INVALID, "unknown sample_phase %d", params->sample_phase);
+    const int n = params->samples_per_axis;
+    if (params->mode != FR_COVERAGE_U8 && params->mode != FR_MASK_NONZERO)
+        return fail(FR_E_UNSUPPORTED, "text runs: mode %d has no meaning for overlapping instances", params->mode);
+    if (params->mode == FR_COVERAGE_U8 ? (n != 1 && n != 2 && n != 4) : n != 1)
+        return fail(FR_E_UNSUPPORTED, "text runs: samples_per_axis %d with mode %d", n, params->mode);
+    if (n_places && !places) return fail(FR_E_INVALID, "places is NULL");
+    if (n_runs && !runs) return fail(FR_E_INVALID, "runs is NULL");
+    if (gs->n_glyphs && gs->h_box.empty()) return fail(FR_E_INVALID, "text runs need the glyph boxes: fr_glyphset_set_boxes");
+    const int64_t LIM = (int64_t)1 << 22;
+    uint64_t pixels = 0, need_cols = 0, need_rows = 0, n_tiles = 0;
+    for (uint32_t r = 0; r < n_runs; ++r) {
+        const fr_text_run &rn = runs[r];
+        if ((uint64_t)rn.first + rn.count > n_places) return fail(FR_E_INVALID, "run %u: places %u + %u of %u", r, rn.first, rn.count, n_places);
+        if (!(rn.scale > 0.0f) || !std::isfinite(rn.scale)) return fail(FR_E_INVALID, "run %u: scale must be finite and > 0", r);
+        if (rn.scale < 9.5367431640625e-07f || rn.scale > 1048576.0f) return fail(FR_E_UNSUPPORTED, "run %u: scale outside [2^-20, 2^20]", r);
+        if (rn.w > 65535u || rn.h > 65535u) return fail(FR_E_UNSUPPORTED, "run %u: larger than 65535", r);
+        for (uint32_t k = rn.first; k < rn.first + rn.count; ++k) {
+            const fr_glyph_place &pl = places[k];
+            if (pl.glyph >= gs->n_glyphs) return fail(FR_E_INVALID, "place %u: glyph %u of %u", k, pl.glyph, gs->n_glyphs);
+            if ((pl.pen_x64 >> 6) < -LIM || (pl.pen_x64 >> 6) > LIM || pl.pen_y < -LIM || pl.pen_y > LIM)
+                return fail(FR_E_UNSUPPORTED, "place %u: pen beyond +-2^22 pixels", k);
+        }
+        pixels += (uint64_t)rn.w * rn.h;
+        if (rn.w && rn.h) {
+            need_cols = std::max<uint64_t>(need_cols, (uint64_t)rn.out_x + rn.w);
+            need_rows = std::max<uint64_t>(need_rows, (uint64_t)rn.out_y + rn.h);
+            n_tiles += (uint64_t)((rn.w + fr::TEXT_TILE_W - 1) / fr::TEXT_TILE_W) * ((rn.h + fr::TEXT_TILE_H - 1) / fr::TEXT_TILE_H);
+        }
+    }
+    if (n_tiles > 0x7fffffffull) return fail(FR_E_UNSUPPORTED, "text plan needs more than 2^31 workgroups; split it");
+    // runs own their rectangles: no two may overlap (sweep down the rows)
+    {
+        std::vector<uint32_t> ord;
+        for (uint32_t r = 0; r < n_runs; ++r)
+            if (runs[r].w && runs[r].h) ord.push_back(r);
+        std::sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return runs[a].out_y < runs[b].out_y; });
+        for (size_t i = 0; i < ord.size(); ++i) {
+            const fr_text_run &A = runs[ord[i]];
+            for (size_t j = i + 1; j < ord.size() && runs[ord[j]].out_y < (uint64_t)A.out_y + A.h; ++j) {
+                const fr_text_run &B = runs[ord[j]];
+                if (B.out_x < (uint64_t)A.out_x + A.w && A.out_x < (uint64_t)B.out_x + B.w)
+                    return fail(FR_E_INVALID, "runs %u and %u overlap", ord[i], ord[j]);
+            }
+        }
+    }
+    // instances: each placement's cell (renderGlyph's grid at the run's scale, one column wider when fx != 0) clipped to its
+    // run; tiles: every 64 x 16 tile of every run, with the instances whose clipped cell meets it (counting sort by tile)
+    std::vector<fr::TextRun> trun(n_runs);
+    std::vector<fr::TextTile> tiles((size_t)n_tiles);
+    std::vector<fr::TextInst> insts;
+    std::vector<std::pair<uint32_t, uint32_t>> hits;            // (tile, instance)
+    std::vector<uint8_t> used(gs->n_glyphs, 0);
+    uint32_t tbase = 0;
+    for (uint32_t r = 0; r < n_runs; ++r) {
+        const fr_text_run &rn = runs[r];
+        trun[r] = fr::TextRun{rn.w, rn.h, rn.out_x, rn.out_y, rn.scale, {0, 0, 0}};
+        if (!rn.w || !rn.h) continue;
+        const uint32_t tx = (rn.w + fr::TEXT_TILE_W - 1) / fr::TEXT_TILE_W, ty = (rn.h + fr::TEXT_TILE_H - 1) / fr::TEXT_TILE_H;
+        for (uint32_t y = 0; y < ty; ++y)
+            for (uint32_t x = 0; x < tx; ++x)
+                tiles[tbase + y * tx + x] = fr::TextTile{r, x * fr::TEXT_TILE_W, y * fr::TEXT_TILE_H, 0, 0, {0, 0, 0}};
+        const float s = rn.scale;
+        for (uint32_t k = rn.first; k < rn.first + rn.count; ++k) {
+            const fr_glyph_place &pl = places[k];
+            const uint32_t g = pl.glyph;
+            if (gs->h_glyph_seg_start[g + 1] == gs->h_glyph_seg_start[g]) continue;        // no segment: no winding anywhere
+            const int16_t *b = &gs->h_box[4 * (size_t)g];
+            // render_glyph.zig:13-17 in binary32, as fr_render_glyph_dims / fr_atlas_layout
+            const int64_t mnx = (int64_t)std::floor((float)b[0] * s), mny = (int64_t)std::floor((float)b[1] * s);
+            const int64_t mxx = (int64_t)std::ceil((float)b[2] * s), mxy = (int64_t)std::ceil((float)b[3] * s);
+            const int64_t ix = pl.pen_x64 >> 6;
+            const uint32_t fx64 = (uint32_t)pl.pen_x64 & 63u;
+            const int64_t cw = mxx - mnx + 1 + (fx64 ? 1 : 0), ch = mxy - mny + 1;
+            if (mnx < -LIM || mxx > LIM || mny < -LIM || mxy > LIM || cw > 65535 || ch > 65535)
+                return fail(FR_E_UNSUPPORTED, "place %u: cell beyond +-2^22 pixels or larger than 65535", k);
+            const int64_t c0 = ix + mnx, r0 = (int64_t)pl.pen_y - mxy;
+            const int64_t x0 = std::max<int64_t>(c0, 0), x1 = std::min<int64_t>(c0 + cw, rn.w);
+            const int64_t y0 = std::max<int64_t>(r0, 0), y1 = std::min<int64_t>(r0 + ch, rn.h);
+            if (x0 >= x1 || y0 >= y1) continue;                                            // clipped away
+            const uint32_t id = (uint32_t)insts.size();
+            insts.push_back(fr::TextInst{(int32_t)ix, pl.pen_y, (int32_t)x0, (int32_t)x1, (int32_t)y0, (int32_t)y1, g,
+                                         2u * gs->h_glyph_seg_start[g], fx64, {0, 0, 0}});
+            used[g] = 1;
+            for (int64_t y = y0 / fr::TEXT_TILE_H; y <= (y1 - 1) / fr::TEXT_TILE_H; ++y)
+                for (int64_t x = x0 / fr::TEXT_TILE_W; x <= (x1 - 1) / fr::TEXT_TILE_W; ++x)
+                    hits.emplace_back(tbase + (uint32_t)(y * tx + x), id);
+        }
+        tbase += tx * ty;
+    }
+    if (hits.size() > 0xffffffffull) return fail(FR_E_UNSUPPORTED, "text plan: too many tile / instance pairs; split it");
+    std::vector<uint32_t> list(hits.size());
+    for (const auto &h : hits) ++tiles[h.first].lend;
+    uint32_t at = 0;
+    for (auto &t : tiles) { t.lbeg = at; at += t.lend; t.lend = t.lbeg; }
+    for (const auto &h : hits) list[tiles[h.first].lend++] = h.second;
+    std::vector<uint32_t> glyphs;
+    for (uint32_t g = 0; g < gs->n_glyphs; ++g)
+        if (used[g]) glyphs.push_back(g);
+
+    fr_plan *p = new (std::nothrow) fr_plan;
+    if (!p) return fail(FR_E_NOMEM, "fr_text_plan_create: host allocation");
+    p->ctx = ctx; p->gs = gs; p->params = *params; p->flags = flags; p->text = true;
+    p->pixels = pixels; p->need_cols = need_cols; p->need_rows = need_rows;
+    p->n_tiles = (uint32_t)n_tiles; p->n_insts = (uint32_t)insts.size(); p->n_tglyphs = (uint32_t)glyphs.size();
+    hipStream_t st = ctx->stream;
+    hipError_t e = hipSetDevice(ctx->device);
+    auto upload = [&](auto *&dst, const auto &v) {
+        using T = typename std::remove_reference<decltype(v)>::type::value_type;
+        if (e != hipSuccess || v.empty()) return;
+        e = hipMalloc(&dst, v.size() * sizeof(T));
+        if (e == hipSuccess) e = hipMemcpyAsync(dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, st);
+    };
+    upload(p->d_tiles, tiles);
+    upload(p->d_runs, trun);
+    upload(p->d_insts, insts);
+    upload(p->d_tlist, list);
+    upload(p->d_tglyphs, glyphs);
+    if (e == hipSuccess && p->n_tglyphs) e = hipMalloc(&p->d_trecs, 2 * (size_t)gs->n_seg * sizeof(fr::Rec));
+    if (e == hipSuccess && p->n_tglyphs) e = hipMalloc(&p->d_trec_count, ((size_t)gs->n_glyphs + 1) * 4);
+    if (e == hipSuccess && p->n_tglyphs) e = hipMemsetAsync(p->d_trec_count, 0, ((size_t)gs->n_glyphs + 1) * 4, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipEventCreate(&p->ev0);
+    if (e == hipSuccess) e = hipEventCreate(&p->ev1);
+    if (e != hipSuccess) {
+        fr_plan_destroy(p);
+        return fail(e == hipErrorOutOfMemory ? FR_E_NOMEM : FR_E_HIP, "fr_text_plan_create: %s", hipGetErrorString(e));
+    }
+    *out = p;
+    return FR_OK;
+}
+
 uint64_t fr_plan_pixels(const fr_plan *plan) { return plan ? plan->pixels : 0; }
 
 int fr_plan_stats(const fr_plan *plan, uint32_t *n_jobs_cov4, uint32_t *n_jobs_general)
 {
     if (!plan) return fail(FR_E_INVALID, "fr_plan_stats: NULL");
+    if (plan->text) {                  // every instance: text_kernel, a direct sum over the glyph's records (fr_text.hip)
+        if (n_jobs_cov4) *n_jobs_cov4 = 0;
+        if (n_jobs_general) *n_jobs_general = plan->n_insts;
+        return FR_OK;
+    }
     if (n_jobs_cov4) *n_jobs_cov4 = plan->n_fast;
     if (n_jobs_general) *n_jobs_general = plan->n_jobs - plan->n_fast;
     return FR_OK;
@@ -712,6 +885,13 @@ int fr_plan_describe(const fr_plan *plan, char *buf, size_t cap)
     char name[96];
     const int pm = plan->params.mode;
     const int fill = (plan->flags & FR_FILL_CONSISTENT) ? 1 : 0;
+    if (plan->text) {
+        if (plan->n_tglyphs) add(fill ? "fr::prepare_fill_kernel" : "fr::prepare_kernel", plan->n_tglyphs);
+        name[0] = 0;
+        (void)fr::launch_text(fr::TextArgs{}, plan->params.samples_per_axis, fill, 0u, nullptr, name, sizeof name);
+        if (plan->n_tiles) add(name, plan->n_insts);
+        return FR_OK;
+    }
     for (const auto &pt : plan->parts) {
         a.strip_w = 16u << pt.wlog;
         name[0] = 0;
@@ -743,7 +923,7 @@ static int ensure_aux(fr_ctx *ctx)
 static int plan_check(fr_plan *plan, void *out_dev, size_t out_stride, size_t out_rows)
 {
     if (!plan) return fail(FR_E_INVALID, "plan is NULL");
-    if (plan->n_jobs == 0) return FR_OK;
+    if (plan->n_jobs == 0 && plan->n_tiles == 0) return FR_OK;
     if (!out_dev) return fail(FR_E_INVALID, "out is NULL");
     if (plan->need_cols > out_stride || plan->need_rows > out_rows)
         return fail(FR_E_INVALID, "jobs need %llu x %llu elements, output is %zu x %zu",
@@ -754,10 +934,34 @@ static int plan_check(fr_plan *plan, void *out_dev, size_t out_stride, size_t ou
     return FR_OK;
 }
 
+// one render of a text plan: the records of its glyphs from their points (plan-owned, so a plain plan's records are
+// never touched), then text_kernel over every tile of every run — two launches in stream order, nothing to fork
+static int text_launch(fr_plan *plan, void *out_dev, size_t out_stride)
+{
+    if (plan->n_tiles == 0) return FR_OK;
+    HIP_TRY(hipSetDevice(plan->ctx->device));
+    const int fill = (plan->flags & FR_FILL_CONSISTENT) ? 1 : 0;
+    hipStream_t st = plan->ctx->stream;
+    if (plan->n_tglyphs) {
+        fr::launch_prepare(plan->gs->d_pts, plan->gs->d_seg_p0, plan->gs->d_glyph_seg_start, plan->d_tglyphs, plan->n_tglyphs,
+                           plan->d_trecs, plan->d_trec_count, st, fill);
+        HIP_TRY(hipGetLastError());
+    }
+    fr::TextArgs a;
+    a.tiles = plan->d_tiles; a.runs = plan->d_runs; a.insts = plan->d_insts; a.list = plan->d_tlist;
+    a.recs = plan->d_trecs; a.rec_count = plan->d_trec_count;
+    a.out = static_cast<uint8_t *>(out_dev);
+    a.out_stride = out_stride;
+    a.phase_center = plan->params.sample_phase == FR_SAMPLE_CENTER ? 1 : 0;
+    HIP_TRY(fr::launch_text(a, plan->params.samples_per_axis, fill, plan->n_tiles, st));
+    return FR_OK;
+}
+
 // the launches of one render, issued on the context's stream(s)
 static int plan_launch_direct(fr_plan *plan, void *out_dev, size_t out_stride, size_t out_rows)
 {
     if (const int rc = plan_check(plan, out_dev, out_stride, out_rows)) return rc;
+    if (plan->text) return text_launch(plan, out_dev, out_stride);
     if (plan->n_jobs == 0) return FR_OK;
     HIP_TRY(hipSetDevice(plan->ctx->device));
     const uint32_t n_fast = plan->n_fast, n_gen = plan->n_jobs - plan->n_fast;
@@ -882,7 +1086,7 @@ static int plan_launch_direct(fr_plan *plan, void *out_dev, size_t out_stride, s
 static int plan_launch(fr_plan *plan, void *out_dev, size_t out_stride, size_t out_rows)
 {
     if (const int rc = plan_check(plan, out_dev, out_stride, out_rows)) return rc;
-    if (plan->n_jobs == 0) return FR_OK;
+    if (plan->n_jobs == 0 && plan->n_tiles == 0) return FR_OK;
     fr_ctx *const ctx = plan->ctx;
     if (!ctx->graph) return plan_launch_direct(plan, out_dev, out_stride, out_rows);
     HIP_TRY(hipSetDevice(ctx->device));

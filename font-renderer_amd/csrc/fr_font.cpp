@@ -452,6 +452,33 @@ int fr_font_char_to_glyph(const fr_font *font, uint32_t ch, uint16_t *glyph_inde
     return FR_OK;
 }
 
+// The reference's pen walk (Appli.zig:318-349): glyph k at the pen E_k = sum of the advance widths before it (font units,
+// curr_em_pos += advance_width), in 1/64 pixel rounded half up: floor((128 * font_size * E_k + upm) / (2 * upm)), exact.
+int fr_text_layout(const fr_font *font, const uint32_t *codepoints, uint32_t n, uint16_t font_size,
+                   uint16_t *glyph_index_out, int32_t *pen_x64_out, int32_t *end_pen_x64)
+{
+    if (!font || (n && (!codepoints || !glyph_index_out || !pen_x64_out))) return set_error(FR_E_INVALID, "fr_text_layout: NULL argument");
+    const int64_t upm = font->units_per_em;
+    if (upm <= 0) return set_error(FR_E_INVALID, "fr_text_layout: units_per_em is 0");
+    auto pen = [&](int64_t e, int32_t *dst) {
+        const __int128 num = (__int128)128 * font_size * e + upm, den = 2 * upm;
+        const __int128 q = num / den - ((num % den != 0 && num < 0) ? 1 : 0);               // floor division
+        if (q < INT32_MIN || q > INT32_MAX) return set_error(FR_E_INVALID, "fr_text_layout: pen beyond int32 (1/64 pixel)");
+        *dst = (int32_t)q;
+        return (int)FR_OK;
+    };
+    int64_t e = 0;                                        // |e| <= 2^32 * 2^15 (the product above: 128-bit)
+    for (uint32_t k = 0; k < n; ++k) {
+        if (const int rc = fr_font_char_to_glyph(font, codepoints[k], &glyph_index_out[k])) return rc;
+        if (const int rc = pen(e, &pen_x64_out[k])) return rc;
+        int16_t adv = 0;
+        if (const int rc = fr_font_glyph_advance(font, glyph_index_out[k], &adv)) return rc;
+        e += adv;
+    }
+    if (end_pen_x64) return pen(e, end_pen_x64);
+    return FR_OK;
+}
+
 int fr_font_glyph_measure(fr_font *font, uint16_t glyph_index, uint32_t *n_contours, uint32_t *n_points, int16_t box[4])
 {
     int rc = ensure_loaded(font, glyph_index);

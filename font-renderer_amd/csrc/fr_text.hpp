@@ -1,0 +1,44 @@
+// fr_text.hpp — the tables of a text plan (fr_api.hip builds them, text_kernel in fr_text.hip reads them)
+#pragma once
+#include "fr_device.hpp"
+
+namespace fr {
+
+struct TextInst {      // one placement, resolved on the host (fr_api.hip)
+    int32_t ix;        // floor(pen_x64 / 64)
+    int32_t pen_y;     // baseline row
+    int32_t x0, x1;    // the cell's columns [x0, x1), clipped to the run (image coordinates)
+    int32_t y0, y1;    // its rows [y0, y1), clipped likewise
+    uint32_t glyph;    // glyph index (record count: rec_count[glyph])
+    uint32_t rec;      // first record of the glyph: 2 * glyph_seg_start[glyph]
+    uint32_t fx64;     // pen_x64 mod 64
+    uint32_t pad[3];
+};
+struct TextRun {       // == fr_text_run's geometry
+    uint32_t w, h, out_x, out_y;
+    float scale;
+    uint32_t pad[3];
+};
+struct TextTile {      // one 64 x 16 tile of a run and its instance list list[lbeg .. lend)
+    uint32_t run, x0, y0, lbeg, lend;
+    uint32_t pad[3];
+};
+struct TextArgs {
+    const TextTile *tiles;
+    const TextRun *runs;
+    const TextInst *insts;
+    const uint32_t *list;
+    const Rec *recs;
+    const uint32_t *rec_count;
+    uint8_t *out;
+    uint64_t out_stride;
+    int32_t phase_center;
+};
+static_assert(sizeof(TextInst) == 48 && sizeof(TextRun) == 32 && sizeof(TextTile) == 32, "text tables");
+
+constexpr int TEXT_TILE_W = 64, TEXT_TILE_H = 16, TEXT_WAVES = 4;
+
+// n in {1, 2, 4}; n_tiles = 0: only name the instance (as rocprofv3 names it) into name[name_cap]
+hipError_t launch_text(const TextArgs &a, int n, int fill, uint32_t n_tiles, hipStream_t stream, char *name = nullptr, size_t name_cap = 0);
+
+}  // namespace fr

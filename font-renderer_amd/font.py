@@ -53,6 +53,16 @@ class Font:
         L.check(self._lib.fr_font_glyph_advance(self._h, gi, C.byref(a)))
         return a.value
 
+    def layout(self, text, font_size: int):
+        """fr_text_layout: the reference's pen walk (Appli.zig:318-349) over `text` (a str or code points) ->
+        (glyph indices u16, pen_x64 i32 — 1/64 pixel, half up —, end pen_x64).  No kerning, no line breaking."""
+        cps = np.array([ord(c) for c in text] if isinstance(text, str) else list(text), np.uint32)
+        gi = np.zeros(max(len(cps), 1), np.uint16)
+        pen = np.zeros(max(len(cps), 1), np.int32)
+        end = C.c_int32()
+        L.check(self._lib.fr_text_layout(self._h, L.ptr(cps), len(cps), font_size, L.ptr(gi), L.ptr(pen), C.byref(end)))
+        return gi[:len(cps)], pen[:len(cps)], end.value
+
     def getGlyph(self, char: int):                                     # Font.zig:161-169 -> struct {Glyph, i16}
         gi = self.glyph_index(char)
         return self.glyph_by_index(gi), self.advance_width(gi)

@@ -74,6 +74,8 @@ class DeviceGlyphSet:
         L.check(ctx._lib.fr_glyphset_create(ctx._h, L.ptr(gs.points_xy), L.ptr(gs.contour_start), gs.n_contours,
                                             L.ptr(gs.glyph_start), len(gs), C.byref(h)))
         self._h = h
+        boxes = np.ascontiguousarray(gs.boxes, np.int16)               # Glyph.box: what text plans size their cells from
+        L.check(ctx._lib.fr_glyphset_set_boxes(self._h, L.ptr(boxes)))
 
     def prepare(self) -> None:
         L.check(self.ctx._lib.fr_glyphset_prepare(self._h))
@@ -155,6 +157,39 @@ class Plan:
             self.close()
         except Exception:
             pass
+
+
+PLACE_DTYPE = np.dtype([("glyph", "<u4"), ("pen_x64", "<i4"), ("pen_y", "<i4")])
+RUN_DTYPE = np.dtype([("first", "<u4"), ("count", "<u4"), ("w", "<u4"), ("h", "<u4"), ("out_x", "<u4"), ("out_y", "<u4"),
+                      ("scale", "<f4")])
+
+
+def make_places(rows: Sequence) -> np.ndarray:
+    """rows of (glyph, pen_x64, pen_y) -> fr_glyph_place array"""
+    return np.array([tuple(r) for r in rows], PLACE_DTYPE)
+
+
+def make_runs(rows: Sequence) -> np.ndarray:
+    """rows of (first, count, w, h, out_x, out_y, scale) -> fr_text_run array"""
+    return np.array([tuple(r) for r in rows], RUN_DTYPE)
+
+
+class TextPlan(Plan):
+    """fr_text_plan_create: glyph placements and the runs that composite them (include/fr_raster.h).  An ordinary
+    fr_plan: render / render_timed / describe / stats / pixels / close as Plan.  mode: FR_COVERAGE_U8 (n in {1, 2, 4})
+    or FR_MASK_NONZERO (n = 1)."""
+
+    def __init__(self, dgs: DeviceGlyphSet, places: np.ndarray, runs: np.ndarray, mode: int = L.FR_COVERAGE_U8,
+                 samples_per_axis: int = 4, sample_phase: int = L.FR_SAMPLE_CENTER, flags: int = 0):
+        places = np.ascontiguousarray(places, PLACE_DTYPE)
+        runs = np.ascontiguousarray(runs, RUN_DTYPE)
+        self.ctx, self.dgs, self.mode = dgs.ctx, dgs, mode
+        self.params = L.RasterParams(mode, samples_per_axis, sample_phase, 0)
+        h = C.c_void_p()
+        L.check(self.ctx._lib.fr_text_plan_create(self.ctx._h, dgs._h, L.ptr(places), len(places), L.ptr(runs), len(runs),
+                                                  C.byref(self.params), flags, C.byref(h)))
+        self._h = h
+        self.n_places, self.n_runs = len(places), len(runs)
 
 
 def render_batch(dgs: DeviceGlyphSet, jobs: np.ndarray, mode: int, out: np.ndarray, samples_per_axis: int = 1,

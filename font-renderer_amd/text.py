@@ -1,0 +1,63 @@
+"""Text runs: a string laid out by the reference's pen walk (Appli.zig:318-349) and rendered as one anti-aliased image
+through a text plan (fr_text_plan_create, include/fr_raster.h).  Nothing is computed in Python but the image size."""
+from __future__ import annotations
+
+import math
+from typing import Optional
+
+import numpy as np
+
+from . import _lib as L
+from .font import Font
+from .image import Gray
+from .render_glyph import Context, DeviceGlyphSet, TextPlan, default_context, make_places, make_runs
+
+
+def instance_cell(box, scale: float, pen_x64: int, pen_y: int):
+    """an instance's cell in image coordinates, unclipped -> (column 0, row 0, width, height): renderGlyph's grid at
+    `scale` (binary32 as render_glyph.zig:13-17), one column wider when the pen has a fractional part"""
+    s = np.float32(scale)
+    b = np.asarray(box, np.int16).astype(np.float32) * s
+    mn_x, mn_y = math.floor(b[0]), math.floor(b[1])
+    mx_x, mx_y = math.ceil(b[2]), math.ceil(b[3])
+    ix, fx64 = pen_x64 >> 6, pen_x64 & 63
+    return ix + mn_x, pen_y - mx_y, mx_x - mn_x + 1 + (fx64 != 0), mx_y - mn_y + 1
+
+
+def render_text(font: Font, text, font_size: int, *, samples_per_axis: int = 4, mode: int = L.FR_COVERAGE_U8,
+                phase: int = L.FR_SAMPLE_CENTER, flags: int = 0, ctx: Optional[Context] = None) -> Gray:
+    """One line of text as one image: every glyph at its sub-pixel pen, overlapping glyphs unioned per sample.
+    The image is the union of the instance cells: the pen origin at its left edge (moved right by whole pixels if a cell
+    reaches left of it) and the baseline at row ceil(max y_max * scale)."""
+    import torch
+
+    ctx = ctx or default_context()
+    gi, pen, _ = font.layout(text, font_size)
+    distinct = sorted(set(int(g) for g in gi))
+    gs, kept = font.glyphset(distinct, skip_unsupported=False)
+    local = {g: k for k, g in enumerate(kept)}
+    scale = np.float32(font_size) / np.float32(font.information.units_per_em)
+    cells = [instance_cell(gs.boxes[local[int(g)]], scale, int(p), 0) for g, p in zip(gi, pen)
+             if gs.segments_per_glyph()[local[int(g)]] > 0]
+    if not cells:
+        return Gray.init(0, 0)
+    left = min(c[0] for c in cells)
+    shift = -left if left < 0 else 0                       # whole pixels: the fractional pens stay as laid out
+    top = min(c[1] for c in cells)                         # the baseline row is -top = ceil(max y_max * scale)
+    width = max(c[0] + c[2] for c in cells) + shift
+    height = max(c[1] + c[3] for c in cells) - top
+    places = make_places([(local[int(g)], int(p) + 64 * shift, -top) for g, p in zip(gi, pen)])
+    runs = make_runs([(0, len(places), width, height, 0, 0, scale)])
+    dgs = DeviceGlyphSet(ctx, gs)
+    plan = TextPlan(dgs, places, runs, mode, samples_per_axis, phase, flags)
+    try:
+        buf = torch.empty((height, width), dtype=torch.uint8, device=f"cuda:{ctx.device}")
+        torch.cuda.synchronize(ctx.device)
+        plan.render(buf.data_ptr(), width, height)
+        ctx.sync()
+        im = Gray.init(width, height)
+        im.data[:] = buf.cpu().numpy().reshape(-1)
+    finally:
+        plan.close()
+        dgs.close()
+    return im

@@ -152,6 +152,9 @@ void fr_glyphset_destroy(fr_glyphset *gs);
 int fr_glyphset_prepare(fr_glyphset *gs);
 /* totals, for reporting: segments (curves) and surviving root records */
 int fr_glyphset_stats(const fr_glyphset *gs, uint64_t *n_segments, uint64_t *n_records);
+/* the glyphs' boxes (Glyph.box: x_min, y_min, x_max, y_max per glyph, font units; n_glyphs x 4 i16), which text plans
+ * size their instance cells from (fr_text_plan_create); copied, host side.  Until set, fr_text_plan_create fails.       */
+int fr_glyphset_set_boxes(fr_glyphset *gs, const int16_t *boxes);
 
 /* ---- batched rasterization ----------------------------------------------
  * A plan keeps the job table resident on the device so a batch can be re-rendered
@@ -183,6 +186,50 @@ int fr_plan_stats(const fr_plan *plan, uint32_t *n_jobs_cov4, uint32_t *n_jobs_g
  * count: "fr::cov4_kernel<4, 32, 4, 4> x20992; fr::render_kernel<3, 4, 32, -1> x3" (NUL-terminated, truncated to cap);
  * a FR_FILL_CONSISTENT plan's instances carry a trailing 1: "fr::cov4_kernel<4, 32, 4, 4, 1> x20992"                  */
 int fr_plan_describe(const fr_plan *plan, char *buf, size_t cap);
+
+/* ---- text runs (BUILD-DEFINED) ---------------------------------------------------------------
+ * The reference draws a line of text: each glyph at a pen position in font units, the pen advanced by the glyph's
+ * advance_width (Appli.zig:318-349), every instance into one MSAA framebuffer, a sample lit if ANY instance covers it.
+ * A text plan renders sets of such instances ("runs"), each into one finished image.
+ *   Placement {glyph, pen_x64, pen_y}: pen_x64 is the image x of the glyph's font-unit origin in 1/64 pixel (26.6 fixed
+ *     point); pen_y is the baseline's image row (whole rows: baselines are not sub-pixel).  Image coordinates are the
+ *     run's own: (0, 0) is its top-left pixel.
+ *   Run {first, count, w, h, out_x, out_y, scale}: placements places[first .. first+count); it owns the whole w x h
+ *     rectangle at (out_x, out_y) of the output and writes every pixel of it (0 where no glyph reaches).  Runs must not
+ *     overlap each other.
+ *   Instance cell: ix = floor(pen_x64 / 64), fx = (pen_x64 mod 64) / 64; renderGlyph's grid of the glyph at the run's
+ *     scale (min_x = floor(x_min*scale), max_x = ceil(x_max*scale), min_y, max_y likewise, binary32 as fr_atlas_layout)
+ *     gives a cell of (max_x - min_x + 1 + (fx != 0)) x (max_y - min_y + 1) pixels whose column 0 sits at image column
+ *     ix + min_x and whose row 0 at image row pen_y - max_y; the cell is clipped to the run.
+ *   Sample (i, j) of image pixel (X, Y) inside the cell:
+ *       cx = (f32(X - ix) + (off(i) - fx)) / scale,   cy = (f32(pen_y - Y) - off(j)) / scale,   off(k) = (k + phase)/n
+ *     (off(i) - fx is exact: both are multiples of 1/64 in (-1, 1)).  So an instance is an ordinary fr_job whose column
+ *     offsets are shifted by fx, and with fx = 0 it is that job.  Outside its cell an instance contributes nothing.
+ *   Value: the union over instances of the non-zero test.  FR_COVERAGE_U8 (n in {1, 2, 4}): round_half_up(255 k / n^2),
+ *     k = # of sub-samples at which SOME instance has winding != 0; FR_MASK_NONZERO (n = 1): 255 if any instance's
+ *     winding != 0.  Both phases; FR_FILL_CONSISTENT applies per instance.  FR_WINDING_I16, FR_GRAY_DEBUG and FR_SDF_U8
+ *     have no meaning for overlapping instances: FR_E_UNSUPPORTED.                                                      */
+typedef struct fr_glyph_place {
+    uint32_t glyph;            /* index into the glyph set                                      */
+    int32_t  pen_x64;          /* image x of the glyph's font-unit origin, 1/64 pixel            */
+    int32_t  pen_y;            /* image row of the baseline                                      */
+} fr_glyph_place;
+
+typedef struct fr_text_run {
+    uint32_t first, count;     /* places[first .. first + count)                                 */
+    uint32_t w, h;             /* the run's image, pixels: every one of them is written          */
+    uint32_t out_x, out_y;     /* its (0, 0) in the output, elements / rows                      */
+    float    scale;            /* font_size / units_per_em                                       */
+} fr_text_run;
+
+/* An ordinary fr_plan (fr_plan_render / _render_timed / _describe / _stats / _pixels / _destroy and the "graph" /
+ * "overlap" options all apply; fr_plan_pixels is the sum of the runs' w*h, fr_plan_stats counts every instance as
+ * general: text_kernel evaluates the records of any glyph directly).  FR_E_INVALID: overlapping runs, a placement
+ * range or glyph index out of range, unknown flag bits; FR_E_UNSUPPORTED: a mode / n outside the definition above;
+ * the scale and coordinate limits of fr_plan_create apply to every run and instance cell.                          */
+int fr_text_plan_create(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place *places, uint32_t n_places,
+                        const fr_text_run *runs, uint32_t n_runs, const fr_raster_params *params, uint32_t flags,
+                        fr_plan **out);
 
 /* One-shot: plan + render + copy back.  out_host: HOST buffer (caller-allocated,
  * e.g. Image.Gray.data / Image.Winding.data from the Zig allocator).  Synchronous.  */
@@ -301,6 +348,14 @@ int fr_font_char_to_glyph(const fr_font *font, uint32_t codepoint, uint16_t *gly
 int fr_font_glyph_advance(const fr_font *font, uint16_t glyph_index, int16_t *advance_width);
 int fr_font_glyph_measure(fr_font *font, uint16_t glyph_index, uint32_t *n_contours, uint32_t *n_points, int16_t box[4]);
 int fr_font_glyph_fill(fr_font *font, uint16_t glyph_index, int16_t *points_xy, uint32_t *contour_start);
+
+/* The reference's pen walk (Appli.zig:318-349; host only): glyph_index_out[k] = cmap(codepoints[k]) (0 if unmapped),
+ * E_k = sum_{m<k} advance_width(m) in font units (the i16 of fr_font_glyph_advance), and
+ *     pen_x64_out[k] = floor((128 * font_size * E_k + upm) / (2 * upm))     (exact int64: E_k * font_size / upm in 1/64
+ * pixel, rounded half up); *end_pen_x64 (if not NULL) the same for E_n.  No kerning and no line breaking: the reference
+ * has neither.                                                                                                         */
+int fr_text_layout(const fr_font *font, const uint32_t *codepoints, uint32_t n, uint16_t font_size,
+                   uint16_t *glyph_index_out, int32_t *pen_x64_out, int32_t *end_pen_x64);
 
 /* ---- QOI writer (host side), byte-compatible with tools/qoi.zig:25-88 saveRGB -----------
  * RGB-only stream, op order RUN -> INDEX -> DIFF -> LUMA -> RGB, run cap 62, BE header, 8-byte

@@ -1,0 +1,107 @@
+"""Text-run benchmark: 4 096 lines of 64 printable ASCII characters, one run per line, one plan,
+4 x 4 samples, for DejaVuSans and DejaVuSerif-Italic at font sizes 16 and 32.  Reports per configuration the ms per render
+of the text plan and its Mpixel/s of run area, and the same instances as separate cells (renderGlyph's grid, whole-pixel
+origins, disjoint) in a plain plan, which prices the composition.  Under rocprofv3 --kernel-trace --stats the kernel
+shares come from the trace (prepare_kernel vs text_kernel).  Prints one JSON line per configuration.
+
+    python tools/bench_text.py [--lines 4096] [--chars 64] [--steps 20] [--warmup 3]"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+import font_renderer_amd as fr  # noqa: E402
+from font_renderer_amd import render_glyph as rg  # noqa: E402
+from fixtures import load_font  # noqa: E402
+
+
+def workload(font, n_lines, n_chars, size, seed):
+    rng = np.random.default_rng(seed)
+    alphabet = [chr(c) for c in range(0x20, 0x7f)]
+    lines = ["".join(rng.choice(alphabet, n_chars)) for _ in range(n_lines)]
+    lay = [font.layout(s, size) for s in lines]
+    distinct = sorted({int(g) for gi, _, _ in lay for g in gi})
+    gs, kept = font.glyphset(distinct, skip_unsupported=False)
+    local = {g: k for k, g in enumerate(kept)}
+    scale = np.float32(size) / np.float32(font.information.units_per_em)
+    seg = gs.segments_per_glyph()
+    places, runs, jobs = [], [], []
+    y, W, jy, JW = 0, 0, 0, 0
+    for gi, pen, _ in lay:
+        cells = [fr.instance_cell(gs.boxes[local[int(g)]], scale, int(p), 0) for g, p in zip(gi, pen) if seg[local[int(g)]]]
+        left, top = min(c[0] for c in cells), min(c[1] for c in cells)
+        shift = max(-left, 0)
+        w = max(c[0] + c[2] for c in cells) + shift
+        h = max(c[1] + c[3] for c in cells) - top
+        runs.append((len(places), len(gi), w, h, 0, y, scale))
+        places += [(local[int(g)], int(p) + 64 * shift, -top) for g, p in zip(gi, pen)]
+        y += h
+        W = max(W, w)
+        # the same instances as plain jobs: renderGlyph's grid, side by side on a row of their own
+        x, jh = 0, 0
+        for g, p in zip(gi, pen):
+            if not seg[local[int(g)]]:
+                continue
+            c0, r0, cw, ch = fr.instance_cell(gs.boxes[local[int(g)]], scale, 0, 0)
+            jobs.append((local[int(g)], c0, -r0, cw, ch, x, jy, scale))
+            x += cw
+            jh = max(jh, ch)
+        jy += jh
+        JW = max(JW, x)
+    return gs, rg.make_places(places), rg.make_runs(runs), (y, W), rg.make_jobs(jobs), (jy, JW)
+
+
+def timed(plan, buf, shape, steps, warmup):
+    for _ in range(warmup):
+        plan.render_timed(buf.data_ptr(), shape[1], shape[0])
+    ms = sorted(plan.render_timed(buf.data_ptr(), shape[1], shape[0]) for _ in range(steps))
+    return ms[len(ms) // 2]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--lines", type=int, default=4096)
+    ap.add_argument("--chars", type=int, default=64)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    args = ap.parse_args()
+    import torch
+    ctx = fr.Context(0)
+    for fi, name in enumerate(["DejaVuSans.ttf", "DejaVuSerif-Italic.ttf"]):
+        font = load_font(name, allow_hinted=True)        # (DejaVuSans carries hinting instructions)
+        for size in (16, 32):
+            gs, places, runs, shape, jobs, jshape = workload(font, args.lines, args.chars, size, seed=100 * fi + size)
+            dgs = fr.DeviceGlyphSet(ctx, gs)
+            plan = fr.TextPlan(dgs, places, runs, fr.FR_COVERAGE_U8, 4, fr.FR_SAMPLE_CENTER)
+            buf = torch.empty(shape, dtype=torch.uint8, device="cuda:0")
+            torch.cuda.synchronize()
+            ms = timed(plan, buf, shape, args.steps, args.warmup)
+            px = plan.pixels
+            desc = plan.describe()
+            plan.close()
+            del buf
+            cells = fr.Plan(dgs, jobs, fr.FR_COVERAGE_U8, 4, fr.FR_SAMPLE_CENTER)
+            jbuf = torch.empty(jshape, dtype=torch.uint8, device="cuda:0")
+            torch.cuda.synchronize()
+            ms_cells = timed(cells, jbuf, jshape, args.steps, args.warmup)
+            cpx, cdesc = cells.pixels, cells.describe()
+            cells.close()
+            del jbuf
+            dgs.close()
+            print(json.dumps({
+                "font": name, "font_size": size, "lines": args.lines, "chars": args.chars, "samples": 16,
+                "instances": int(len(places)), "run_mpixel": round(px / 1e6, 3), "text_ms": round(ms, 4),
+                "text_mpixel_per_s": round(px / 1e6 / (ms / 1e3), 1), "text_plan": desc,
+                "cells_mpixel": round(cpx / 1e6, 3), "cells_ms": round(ms_cells, 4),
+                "cells_mpixel_per_s": round(cpx / 1e6 / (ms_cells / 1e3), 1), "cells_plan": cdesc,
+                "text_over_cells": round(ms / ms_cells, 2)}), flush=True)
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
