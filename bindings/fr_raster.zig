@@ -91,6 +91,9 @@ pub extern "c" fn fr_plan_pixels(plan: *const fr_plan) u64;
 pub extern "c" fn fr_plan_stats(plan: *const fr_plan, n_jobs_cov4: ?*u32, n_jobs_general: ?*u32) c_int;
 pub extern "c" fn fr_plan_describe(plan: *const fr_plan, buf: [*]u8, cap: usize) c_int;
 pub extern "c" fn fr_text_plan_create(ctx: *fr_ctx, gs: *const fr_glyphset, places: [*]const GlyphPlace, n_places: u32, runs: [*]const TextRun, n_runs: u32, params: *const RasterParams, flags: u32, out: *?*fr_plan) c_int;
+/// RGBA text plans (DESIGN.md section 5): place_rgba = 4 bytes (R, G, B, A) per placement, run_clear_rgba = 4 per run;
+/// the plan renders RGBA pixels (4-byte aligned output, strides in pixels)
+pub extern "c" fn fr_text_plan_create_rgba(ctx: *fr_ctx, gs: *const fr_glyphset, places: [*]const GlyphPlace, place_rgba: [*]const u8, n_places: u32, runs: [*]const TextRun, run_clear_rgba: [*]const u8, n_runs: u32, params: *const RasterParams, flags: u32, out: *?*fr_plan) c_int;
 pub extern "c" fn fr_allgather_bands(ctx: *fr_ctx, nccl_comm: *anyopaque, atlas_dev: *anyopaque, band_bytes: usize) c_int;
 pub extern "c" fn fr_gather_bands(ctx: *fr_ctx, nccl_comm: *anyopaque, atlas_dev: *anyopaque, band_bytes: usize, root: c_int) c_int;
 pub extern "c" fn fr_render_batch(ctx: *fr_ctx, gs: *const fr_glyphset, jobs: [*]const Job, n_jobs: u32, params: *const RasterParams, out_host: *anyopaque, out_stride: usize, out_rows: usize) c_int;
@@ -123,6 +126,8 @@ pub extern "c" fn fr_font_glyph_fill(font: *fr_font, glyph_index: u16, points_xy
 pub extern "c" fn fr_qoi_bound(width: u32, height: u32) usize;
 pub extern "c" fn fr_qoi_encode_rgb(rgb: [*]const u8, width: u32, height: u32, out: [*]u8, cap: usize, n_out: *usize) c_int;
 pub extern "c" fn fr_qoi_encode_gray(gray: [*]const u8, width: u32, height: u32, stride: usize, out: [*]u8, cap: usize, n_out: *usize) c_int;
+/// a standard 4-channel QOI stream (the QOI specification; tools/qoi.zig writes RGB only)
+pub extern "c" fn fr_qoi_encode_rgba(rgba: [*]const u8, width: u32, height: u32, stride_px: usize, out: [*]u8, cap: usize, n_out: *usize) c_int;
 // ---- self-tests of the two arithmetic shortcuts (device-side, exhaustive)
 pub extern "c" fn fr_selftest_division(d_lo: u32, d_hi: u32, mismatches: *u64, bad_divisor: ?*u32, bad_x_bits: ?*u32) c_int;
 pub extern "c" fn fr_selftest_sqrt(mismatches: *u64, bad_x_bits: ?*u32) c_int;

@@ -70,6 +70,8 @@ SYMBOLS = [
     ("fr_plan_describe", C.c_int, [_P, C.c_char_p, C.c_size_t]),
     ("fr_text_plan_create", C.c_int, [_P, _P, _P, C.c_uint32, _P, C.c_uint32, C.POINTER(RasterParams), C.c_uint32,
                                       C.POINTER(_P)]),
+    ("fr_text_plan_create_rgba", C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, C.POINTER(RasterParams),
+                                           C.c_uint32, C.POINTER(_P)]),
     ("fr_allgather_bands", C.c_int, [_P, _P, _P, C.c_size_t]),
     ("fr_gather_bands", C.c_int, [_P, _P, _P, C.c_size_t, C.c_int]),
     ("fr_render_batch", C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(RasterParams), _P, C.c_size_t, C.c_size_t]),
@@ -99,6 +101,7 @@ SYMBOLS = [
     ("fr_qoi_bound", C.c_size_t, [C.c_uint32, C.c_uint32]),
     ("fr_qoi_encode_rgb", C.c_int, [_P, C.c_uint32, C.c_uint32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("fr_qoi_encode_gray", C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("fr_qoi_encode_rgba", C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("fr_selftest_sqrt", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     ("fr_selftest_division", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
 ]

@@ -141,6 +141,8 @@ struct fr_plan {
     // a text plan (fr_text_plan_create): its tables (fr_text.hpp), the distinct glyphs whose records prepare_kernel rebuilds
     // into plan-owned memory before every render, and its counts
     bool text = false;
+    bool rgba = false;                 // fr_text_plan_create_rgba: RGBA pixels, text_rgba_kernel
+    int blend = 0;                     // (rgba) 1 unless every placement colour is opaque
     fr::TextTile *d_tiles = nullptr;
     fr::TextRun *d_runs = nullptr;
     fr::TextInst *d_insts = nullptr;
@@ -702,6 +704,12 @@ int fr_plan_create_ex(fr_ctx *ctx, const fr_glyphset *gs, const fr_job *jobs, ui
 }
 
 // ---- text runs (include/fr_raster.h) -----------------------------------------------------------
+// the 4 bytes R G B A as one little-endian word, R in the low byte (fr_text.hpp: TextInst::rgba, TextRun::clear)
+static uint32_t rgba_word(const uint8_t *c)
+{
+    return (uint32_t)c[0] | (uint32_t)c[1] << 8 | (uint32_t)c[2] << 16 | (uint32_t)c[3] << 24;
+}
+
 int fr_glyphset_set_boxes(fr_glyphset *gs, const int16_t *boxes)
 {
     if (!gs || (gs->n_glyphs && !boxes)) return fail(FR_E_INVALID, "fr_glyphset_set_boxes: NULL argument");
@@ -712,11 +720,14 @@ int fr_glyphset_set_boxes(fr_glyphset *gs, const int16_t *boxes)
     return FR_OK;
 }
 
-int fr_text_plan_create(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place *places, uint32_t n_places,
-                        const fr_text_run *runs, uint32_t n_runs, const fr_raster_params *params, uint32_t flags,
-                        fr_plan **out)
+// fr_text_plan_create and fr_text_plan_create_rgba: one set of checks and tables.  rgba: place_rgba / run_clear_rgba are
+// the colours (4 bytes each), the mode must be FR_COVERAGE_U8, and the plan renders with text_rgba_kernel.
+static int text_plan_build(const char *fn, fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place *places,
+                           const uint8_t *place_rgba, uint32_t n_places, const fr_text_run *runs,
+                           const uint8_t *run_clear_rgba, uint32_t n_runs, const fr_raster_params *params, uint32_t flags,
+                           bool rgba, fr_plan **out)
 {
-    if (!ctx || !gs || !out) return fail(FR_E_INVALID, "fr_text_plan_create: NULL argument");
+    if (!ctx || !gs || !out) return fail(FR_E_INVALID, "%s: NULL argument", fn);
     *out = nullptr;
     if (const int frc = check_flags(flags)) return frc;
     if (gs->ctx != ctx) return fail(FR_E_INVALID, "glyph set belongs to another context");
@@ -725,12 +736,20 @@ int fr_text_plan_create(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place
     if (params->sample_phase != FR_SAMPLE_CORNER && params->sample_phase != FR_SAMPLE_CENTER)
         return fail(FR_E_INVALID, "unknown sample_phase %d", params->sample_phase);
     const int n = params->samples_per_axis;
-    if (params->mode != FR_COVERAGE_U8 && params->mode != FR_MASK_NONZERO)
-        return fail(FR_E_UNSUPPORTED, "text runs: mode %d has no meaning for overlapping instances", params->mode);
-    if (params->mode == FR_COVERAGE_U8 ? (n != 1 && n != 2 && n != 4) : n != 1)
-        return fail(FR_E_UNSUPPORTED, "text runs: samples_per_axis %d with mode %d", n, params->mode);
+    if (rgba) {
+        if (params->mode != FR_COVERAGE_U8)
+            return fail(FR_E_UNSUPPORTED, "RGBA text runs: mode %d (only FR_COVERAGE_U8)", params->mode);
+        if (n != 1 && n != 2 && n != 4) return fail(FR_E_UNSUPPORTED, "RGBA text runs: samples_per_axis %d", n);
+    } else {
+        if (params->mode != FR_COVERAGE_U8 && params->mode != FR_MASK_NONZERO)
+            return fail(FR_E_UNSUPPORTED, "text runs: mode %d has no meaning for overlapping instances", params->mode);
+        if (params->mode == FR_COVERAGE_U8 ? (n != 1 && n != 2 && n != 4) : n != 1)
+            return fail(FR_E_UNSUPPORTED, "text runs: samples_per_axis %d with mode %d", n, params->mode);
+    }
     if (n_places && !places) return fail(FR_E_INVALID, "places is NULL");
     if (n_runs && !runs) return fail(FR_E_INVALID, "runs is NULL");
+    if (rgba && n_places && !place_rgba) return fail(FR_E_INVALID, "place_rgba is NULL");
+    if (rgba && n_runs && !run_clear_rgba) return fail(FR_E_INVALID, "run_clear_rgba is NULL");
     if (gs->n_glyphs && gs->h_box.empty()) return fail(FR_E_INVALID, "text runs need the glyph boxes: fr_glyphset_set_boxes");
     const int64_t LIM = (int64_t)1 << 22;
     uint64_t pixels = 0, need_cols = 0, need_rows = 0, n_tiles = 0;
@@ -779,7 +798,7 @@ int fr_text_plan_create(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place
     uint32_t tbase = 0;
     for (uint32_t r = 0; r < n_runs; ++r) {
         const fr_text_run &rn = runs[r];
-        trun[r] = fr::TextRun{rn.w, rn.h, rn.out_x, rn.out_y, rn.scale, {0, 0, 0}};
+        trun[r] = fr::TextRun{rn.w, rn.h, rn.out_x, rn.out_y, rn.scale, rgba ? rgba_word(run_clear_rgba + 4 * (size_t)r) : 0u, {0, 0}};
         if (!rn.w || !rn.h) continue;
         const uint32_t tx = (rn.w + fr::TEXT_TILE_W - 1) / fr::TEXT_TILE_W, ty = (rn.h + fr::TEXT_TILE_H - 1) / fr::TEXT_TILE_H;
         for (uint32_t y = 0; y < ty; ++y)
@@ -805,7 +824,8 @@ int fr_text_plan_create(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place
             if (x0 >= x1 || y0 >= y1) continue;                                            // clipped away
             const uint32_t id = (uint32_t)insts.size();
             insts.push_back(fr::TextInst{(int32_t)ix, pl.pen_y, (int32_t)x0, (int32_t)x1, (int32_t)y0, (int32_t)y1, g,
-                                         2u * gs->h_glyph_seg_start[g], fx64, {0, 0, 0}});
+                                         2u * gs->h_glyph_seg_start[g], fx64, rgba ? rgba_word(place_rgba + 4 * (size_t)k) : 0u,
+                                         {0, 0}});
             used[g] = 1;
             for (int64_t y = y0 / fr::TEXT_TILE_H; y <= (y1 - 1) / fr::TEXT_TILE_H; ++y)
                 for (int64_t x = x0 / fr::TEXT_TILE_W; x <= (x1 - 1) / fr::TEXT_TILE_W; ++x)
@@ -824,8 +844,11 @@ int fr_text_plan_create(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place
         if (used[g]) glyphs.push_back(g);
 
     fr_plan *p = new (std::nothrow) fr_plan;
-    if (!p) return fail(FR_E_NOMEM, "fr_text_plan_create: host allocation");
+    if (!p) return fail(FR_E_NOMEM, "%s: host allocation", fn);
     p->ctx = ctx; p->gs = gs; p->params = *params; p->flags = flags; p->text = true;
+    p->rgba = rgba;
+    for (uint32_t k = 0; rgba && k < n_places; ++k)
+        if (place_rgba[4 * (size_t)k + 3] != 255) { p->blend = 1; break; }
     p->pixels = pixels; p->need_cols = need_cols; p->need_rows = need_rows;
     p->n_tiles = (uint32_t)n_tiles; p->n_insts = (uint32_t)insts.size(); p->n_tglyphs = (uint32_t)glyphs.size();
     hipStream_t st = ctx->stream;
@@ -849,10 +872,26 @@ int fr_text_plan_create(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place
     if (e == hipSuccess) e = hipEventCreate(&p->ev1);
     if (e != hipSuccess) {
         fr_plan_destroy(p);
-        return fail(e == hipErrorOutOfMemory ? FR_E_NOMEM : FR_E_HIP, "fr_text_plan_create: %s", hipGetErrorString(e));
+        return fail(e == hipErrorOutOfMemory ? FR_E_NOMEM : FR_E_HIP, "%s: %s", fn, hipGetErrorString(e));
     }
     *out = p;
     return FR_OK;
+}
+
+int fr_text_plan_create(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place *places, uint32_t n_places,
+                        const fr_text_run *runs, uint32_t n_runs, const fr_raster_params *params, uint32_t flags,
+                        fr_plan **out)
+{
+    return text_plan_build("fr_text_plan_create", ctx, gs, places, nullptr, n_places, runs, nullptr, n_runs, params, flags,
+                           false, out);
+}
+
+int fr_text_plan_create_rgba(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place *places, const uint8_t *place_rgba,
+                             uint32_t n_places, const fr_text_run *runs, const uint8_t *run_clear_rgba, uint32_t n_runs,
+                             const fr_raster_params *params, uint32_t flags, fr_plan **out)
+{
+    return text_plan_build("fr_text_plan_create_rgba", ctx, gs, places, place_rgba, n_places, runs, run_clear_rgba, n_runs,
+                           params, flags, true, out);
 }
 
 uint64_t fr_plan_pixels(const fr_plan *plan) { return plan ? plan->pixels : 0; }
@@ -888,7 +927,10 @@ int fr_plan_describe(const fr_plan *plan, char *buf, size_t cap)
     if (plan->text) {
         if (plan->n_tglyphs) add(fill ? "fr::prepare_fill_kernel" : "fr::prepare_kernel", plan->n_tglyphs);
         name[0] = 0;
-        (void)fr::launch_text(fr::TextArgs{}, plan->params.samples_per_axis, fill, 0u, nullptr, name, sizeof name);
+        if (plan->rgba)
+            (void)fr::launch_text_rgba(fr::TextArgs{}, plan->params.samples_per_axis, fill, plan->blend, 0u, nullptr, name, sizeof name);
+        else
+            (void)fr::launch_text(fr::TextArgs{}, plan->params.samples_per_axis, fill, 0u, nullptr, name, sizeof name);
         if (plan->n_tiles) add(name, plan->n_insts);
         return FR_OK;
     }
@@ -931,6 +973,7 @@ static int plan_check(fr_plan *plan, void *out_dev, size_t out_stride, size_t ou
     // (the fast kernels address the rows of a wave band by 32-bit offsets from the band's base: 32 rows of the pitch)
     if (out_stride > ((size_t)1 << 26))
         return fail(FR_E_INVALID, "row pitch of %zu elements: at most 2^26", out_stride);
+    if (plan->rgba && ((uintptr_t)out_dev & 3u)) return fail(FR_E_INVALID, "RGBA output %p is not 4-byte aligned", out_dev);
     return FR_OK;
 }
 
@@ -953,7 +996,8 @@ static int text_launch(fr_plan *plan, void *out_dev, size_t out_stride)
     a.out = static_cast<uint8_t *>(out_dev);
     a.out_stride = out_stride;
     a.phase_center = plan->params.sample_phase == FR_SAMPLE_CENTER ? 1 : 0;
-    HIP_TRY(fr::launch_text(a, plan->params.samples_per_axis, fill, plan->n_tiles, st));
+    if (plan->rgba) HIP_TRY(fr::launch_text_rgba(a, plan->params.samples_per_axis, fill, plan->blend, plan->n_tiles, st));
+    else HIP_TRY(fr::launch_text(a, plan->params.samples_per_axis, fill, plan->n_tiles, st));
     return FR_OK;
 }
 

@@ -86,4 +86,60 @@ int fr_qoi_encode_gray(const uint8_t *gray, uint32_t width, uint32_t height, siz
     return encode([&](size_t i) { const uint8_t v = gray[(i / width) * stride + (i % width)]; return Px{v, v, v}; }, width, height, out, cap, n_out);
 }
 
+// A standard 4-channel QOI stream, as the QOI specification writes it (the reference's encoder has no alpha): the
+// index hash includes alpha, QOI_OP_RGBA whenever alpha changes, the previous pixel starts at (0, 0, 0, 255) and the
+// running table at all zeros, and a run is flushed at 62 pixels or at the end of the image.
+int fr_qoi_encode_rgba(const uint8_t *rgba, uint32_t width, uint32_t height, size_t stride_px, uint8_t *out, size_t cap, size_t *n_out)
+{
+    if (!rgba || !out) return fr::set_error(FR_E_INVALID, "fr_qoi_encode_rgba: NULL argument");
+    if (stride_px < width) return fr::set_error(FR_E_INVALID, "stride < width");
+    struct Px4 { uint8_t r, g, b, a; };
+    auto eq = [](Px4 x, Px4 y) { return x.r == y.r && x.g == y.g && x.b == y.b && x.a == y.a; };
+    const size_t total = (size_t)width * height;
+    size_t o = 0;
+    auto put = [&](uint8_t b) { if (o < cap) out[o] = b; ++o; };
+    put('q'); put('o'); put('i'); put('f');
+    put(width >> 24); put(width >> 16); put(width >> 8); put(width);
+    put(height >> 24); put(height >> 16); put(height >> 8); put(height);
+    put(4); put(0);
+    Px4 index[64];
+    memset(index, 0, sizeof index);
+    Px4 prev{0, 0, 0, 255};
+    uint32_t run = 0;
+    for (size_t i = 0; i < total; ++i) {
+        const uint8_t *q = rgba + 4 * ((i / width) * stride_px + (i % width));
+        const Px4 px{q[0], q[1], q[2], q[3]};
+        if (eq(px, prev)) {
+            if (++run == 62 || i + 1 == total) { put(0xC0 | (run - 1)); run = 0; }
+            continue;
+        }
+        if (run) { put(0xC0 | (run - 1)); run = 0; }
+        const uint8_t h = (uint8_t)((px.r * 3 + px.g * 5 + px.b * 7 + px.a * 11) & 63);
+        if (eq(index[h], px)) {
+            put(h);
+        } else {
+            index[h] = px;
+            if (px.a == prev.a) {
+                const int dr = (int8_t)(uint8_t)(px.r - prev.r), dg = (int8_t)(uint8_t)(px.g - prev.g), db = (int8_t)(uint8_t)(px.b - prev.b);
+                const int dgr = dr - dg, dgb = db - dg;
+                if (dr > -3 && dr < 2 && dg > -3 && dg < 2 && db > -3 && db < 2) {
+                    put(0x40 | (dr + 2) << 4 | (dg + 2) << 2 | (db + 2));
+                } else if (dgr > -9 && dgr < 8 && dg > -33 && dg < 32 && dgb > -9 && dgb < 8) {
+                    put(0x80 | (dg + 32)); put((dgr + 8) << 4 | (dgb + 8));
+                } else {
+                    put(0xFE); put(px.r); put(px.g); put(px.b);
+                }
+            } else {
+                put(0xFF); put(px.r); put(px.g); put(px.b); put(px.a);
+            }
+        }
+        prev = px;
+    }
+    for (int i = 0; i < 7; ++i) put(0);
+    put(1);
+    if (n_out) *n_out = o;
+    if (o > cap) return fr::set_error(FR_E_INVALID, "QOI output needs %zu bytes, buffer has %zu", o, cap);
+    return FR_OK;
+}
+
 }  // extern "C"

@@ -82,6 +82,26 @@ class RGB:                      # Image.zig:132-170
 
 
 @dataclass
+class RGBA:                     # an RGBA text plan's image (fr_text_plan_create_rgba): the framebuffer's bytes
+    width: int
+    height: int
+    data: np.ndarray            # (height*width, 4) u8, R G B A, not premultiplied
+
+    @staticmethod
+    def init(width: int, height: int) -> "RGBA":
+        return RGBA(width, height, np.zeros((width * height, 4), np.uint8))
+
+    def getWidth(self) -> int:
+        return self.width
+
+    def getHeight(self) -> int:
+        return self.height
+
+    def as_3d(self) -> np.ndarray:
+        return self.data.reshape(self.height, self.width, 4)
+
+
+@dataclass
 class GlyphDebug:               # Image.zig:173-241
     """Image.GlyphDebug: the exact-integer winding lattice (1 px per font unit, 1-unit border) coloured by
     setWindingLinear with the glyph's points marked; `render` runs on the device through fr_glyph_debug_render."""

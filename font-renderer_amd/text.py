@@ -1,5 +1,6 @@
 """Text runs: a string laid out by the reference's pen walk (Appli.zig:318-349) and rendered as one anti-aliased image
-through a text plan (fr_text_plan_create, include/fr_raster.h).  Nothing is computed in Python but the image size."""
+through a text plan (fr_text_plan_create, include/fr_raster.h), or as one RGBA image through an RGBA text plan
+(fr_text_plan_create_rgba).  Nothing is computed in Python but the image size."""
 from __future__ import annotations
 
 import math
@@ -9,8 +10,8 @@ import numpy as np
 
 from . import _lib as L
 from .font import Font
-from .image import Gray
-from .render_glyph import Context, DeviceGlyphSet, TextPlan, default_context, make_places, make_runs
+from .image import RGBA, Gray
+from .render_glyph import Context, DeviceGlyphSet, TextPlan, TextPlanRGBA, default_context, make_places, make_runs
 
 
 def instance_cell(box, scale: float, pen_x64: int, pen_y: int):
@@ -24,14 +25,10 @@ def instance_cell(box, scale: float, pen_x64: int, pen_y: int):
     return ix + mn_x, pen_y - mx_y, mx_x - mn_x + 1 + (fx64 != 0), mx_y - mn_y + 1
 
 
-def render_text(font: Font, text, font_size: int, *, samples_per_axis: int = 4, mode: int = L.FR_COVERAGE_U8,
-                phase: int = L.FR_SAMPLE_CENTER, flags: int = 0, ctx: Optional[Context] = None) -> Gray:
-    """One line of text as one image: every glyph at its sub-pixel pen, overlapping glyphs unioned per sample.
-    The image is the union of the instance cells: the pen origin at its left edge (moved right by whole pixels if a cell
-    reaches left of it) and the baseline at row ceil(max y_max * scale)."""
-    import torch
-
-    ctx = ctx or default_context()
+def _line(font: Font, text, font_size: int):
+    """one line laid out as one run: (glyph set, places, runs, width, height), or None when nothing is drawn.  The image
+    is the union of the instance cells: the pen origin at its left edge (moved right by whole pixels if a cell reaches
+    left of it) and the baseline at row ceil(max y_max * scale)."""
     gi, pen, _ = font.layout(text, font_size)
     distinct = sorted(set(int(g) for g in gi))
     gs, kept = font.glyphset(distinct, skip_unsupported=False)
@@ -40,7 +37,7 @@ def render_text(font: Font, text, font_size: int, *, samples_per_axis: int = 4, 
     cells = [instance_cell(gs.boxes[local[int(g)]], scale, int(p), 0) for g, p in zip(gi, pen)
              if gs.segments_per_glyph()[local[int(g)]] > 0]
     if not cells:
-        return Gray.init(0, 0)
+        return None
     left = min(c[0] for c in cells)
     shift = -left if left < 0 else 0                       # whole pixels: the fractional pens stay as laid out
     top = min(c[1] for c in cells)                         # the baseline row is -top = ceil(max y_max * scale)
@@ -48,6 +45,21 @@ def render_text(font: Font, text, font_size: int, *, samples_per_axis: int = 4, 
     height = max(c[1] + c[3] for c in cells) - top
     places = make_places([(local[int(g)], int(p) + 64 * shift, -top) for g, p in zip(gi, pen)])
     runs = make_runs([(0, len(places), width, height, 0, 0, scale)])
+    return gs, places, runs, width, height
+
+
+def render_text(font: Font, text, font_size: int, *, samples_per_axis: int = 4, mode: int = L.FR_COVERAGE_U8,
+                phase: int = L.FR_SAMPLE_CENTER, flags: int = 0, ctx: Optional[Context] = None) -> Gray:
+    """One line of text as one image: every glyph at its sub-pixel pen, overlapping glyphs unioned per sample.
+    The image is the union of the instance cells: the pen origin at its left edge (moved right by whole pixels if a cell
+    reaches left of it) and the baseline at row ceil(max y_max * scale)."""
+    import torch
+
+    ctx = ctx or default_context()
+    line = _line(font, text, font_size)
+    if line is None:
+        return Gray.init(0, 0)
+    gs, places, runs, width, height = line
     dgs = DeviceGlyphSet(ctx, gs)
     plan = TextPlan(dgs, places, runs, mode, samples_per_axis, phase, flags)
     try:
@@ -57,6 +69,49 @@ def render_text(font: Font, text, font_size: int, *, samples_per_axis: int = 4, 
         ctx.sync()
         im = Gray.init(width, height)
         im.data[:] = buf.cpu().numpy().reshape(-1)
+    finally:
+        plan.close()
+        dgs.close()
+    return im
+
+
+def _rgba(c) -> tuple:
+    """an (R, G, B) or (R, G, B, A) colour -> (R, G, B, A), A = 255 when omitted"""
+    c = tuple(int(v) for v in c)
+    if len(c) == 3:
+        c += (255,)
+    if len(c) != 4 or not all(0 <= v <= 255 for v in c):
+        raise ValueError(f"colour {c}: expected 3 or 4 values in [0, 255]")
+    return c
+
+
+def render_text_rgba(font: Font, text, font_size: int, color=(225, 105, 180, 255), background=(0, 0, 0, 0), colors=None,
+                     *, samples_per_axis: int = 4, phase: int = L.FR_SAMPLE_CENTER, flags: int = 0,
+                     ctx: Optional[Context] = None) -> RGBA:
+    """One line of text as one RGBA image (fr_text_plan_create_rgba): every glyph blended per sample in order over
+    `background`, in `color` or, if `colors` is given, in colors[k] for character k (e.g. to highlight a word).  The
+    defaults are the reference's frame: pink text (shader.slang) on a transparent clear colour.  Sized as render_text."""
+    import torch
+
+    ctx = ctx or default_context()
+    n_chars = len(text)
+    if colors is not None and len(colors) != n_chars:
+        raise ValueError(f"colors: {len(colors)} colours for {n_chars} characters")
+    per_char = [_rgba(c) for c in colors] if colors is not None else [_rgba(color)] * n_chars
+    clear = _rgba(background)
+    line = _line(font, text, font_size)
+    if line is None:
+        return RGBA.init(0, 0)
+    gs, places, runs, width, height = line
+    dgs = DeviceGlyphSet(ctx, gs)
+    plan = TextPlanRGBA(dgs, places, per_char, runs, [clear], samples_per_axis, phase, flags)
+    try:
+        buf = torch.empty((height, width, 4), dtype=torch.uint8, device=f"cuda:{ctx.device}")
+        torch.cuda.synchronize(ctx.device)
+        plan.render(buf.data_ptr(), width, height)
+        ctx.sync()
+        im = RGBA.init(width, height)
+        im.data[:] = buf.cpu().numpy().reshape(-1, 4)
     finally:
         plan.close()
         dgs.close()

@@ -231,6 +231,36 @@ int fr_text_plan_create(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place
                         const fr_text_run *runs, uint32_t n_runs, const fr_raster_params *params, uint32_t flags,
                         fr_plan **out);
 
+/* ---- RGBA text runs (BUILD-DEFINED) ------------------------------------------------------------
+ * The reference's visible product: text in a colour (shaders/shader.slang: (225, 105, 180), alpha 1) blended into an
+ * RGBA MSAA framebuffer cleared to (0, 0, 0, 0) (VulkanContext.zig:59, :188-192), glyphs drawn in order, the samples
+ * averaged by the resolve.  An RGBA text plan has the placements, runs, cells, clipping, sample points and per-instance
+ * non-zero test of a text plan (above), and colours: placement k has C_k = place_rgba[4k .. 4k+4) = (R, G, B, A), run r
+ * the clear colour Q_r = run_clear_rgba[4r .. 4r+4).
+ *   Every sub-sample s of every pixel of run r starts at Q_r.  The run's instances are applied in placement order: an
+ *   instance k whose cell holds the pixel and whose winding at s is non-zero updates the sample by the reference's blend
+ *   state (colour src*srcAlpha + dst*(1 - srcAlpha); alpha factors ONE, ZERO: VulkanContext.zig:1296-1305) in integers,
+ *       c' = (C_k.c * A + c * (255 - A) + 127) div 255    for c in R, G, B    (round to nearest; no ties occur)
+ *       a' = A                                                               (alpha replaced)
+ *   Resolve: each channel of the pixel is (sum over the n x n sub-samples of v_s + n^2/2) div n^2, n in {1, 2, 4}
+ *   (n = 1 is the reference's MSAA off).
+ * So: clear (0,0,0,0) with every instance (255,255,255,255) gives every channel equal to the text plan's FR_COVERAGE_U8
+ * byte; with A = 255 the last covering instance wins per sample; an instance with A = 0 keeps RGB and sets alpha to 0;
+ * the order of overlapping placements matters.
+ * The output element is 4 bytes, R G B A in memory, NOT premultiplied: the framebuffer's bytes.  With a (0,0,0,0) clear
+ * colour and opaque text, RGB comes out premultiplied by the coverage, as in the reference's transparent window.
+ * Blending is on the stored 8-bit values, as on a UNORM framebuffer; the reference's B8G8R8A8_SRGB swapchain blends in
+ * linear light, which is not done here (nor BGRA order).
+ * params->mode must be FR_COVERAGE_U8 with n in {1, 2, 4}, either phase (another mode or n: FR_E_UNSUPPORTED; an unknown
+ * mode value stays FR_E_INVALID, as for fr_text_plan_create); FR_FILL_CONSISTENT
+ * applies per instance.  A NULL colour array with a non-zero count is FR_E_INVALID; every other check of
+ * fr_text_plan_create applies.  The result is an ordinary fr_plan; out_dev must be 4-byte aligned (FR_E_INVALID), and
+ * out_stride / out_x / out_rows and the 2^26 pitch limit count RGBA pixels.  fr_plan_pixels stays a pixel count;
+ * fr_plan_describe names text_rgba_kernel<n, fill, blend> (blend = 0 when every placement colour has A = 255).          */
+int fr_text_plan_create_rgba(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place *places, const uint8_t *place_rgba,
+                             uint32_t n_places, const fr_text_run *runs, const uint8_t *run_clear_rgba, uint32_t n_runs,
+                             const fr_raster_params *params, uint32_t flags, fr_plan **out);
+
 /* One-shot: plan + render + copy back.  out_host: HOST buffer (caller-allocated,
  * e.g. Image.Gray.data / Image.Winding.data from the Zig allocator).  Synchronous.  */
 int fr_render_batch(fr_ctx *ctx, const fr_glyphset *gs, const fr_job *jobs, uint32_t n_jobs,
@@ -364,6 +394,10 @@ int fr_text_layout(const fr_font *font, const uint32_t *codepoints, uint32_t n, 
 size_t fr_qoi_bound(uint32_t width, uint32_t height);
 int fr_qoi_encode_rgb(const uint8_t *rgb, uint32_t width, uint32_t height, uint8_t *out, size_t cap, size_t *n_out);
 int fr_qoi_encode_gray(const uint8_t *gray, uint32_t width, uint32_t height, size_t stride, uint8_t *out, size_t cap, size_t *n_out);
+/* A standard 4-channel QOI stream (the QOI specification, not tools/qoi.zig, which writes RGB only): channels tag 4,
+ * QOI_OP_RGBA when alpha changes, the index hash r*3 + g*5 + b*7 + a*11, previous pixel (0,0,0,255) before the first.
+ * rgba: 4 bytes per pixel, rows stride_px pixels apart (>= width).  Worst case 22 + 5 * width * height bytes.          */
+int fr_qoi_encode_rgba(const uint8_t *rgba, uint32_t width, uint32_t height, size_t stride_px, uint8_t *out, size_t cap, size_t *n_out);
 
 /* ---- self-test: exhaustive device-side check of an arithmetic shortcut ----------
  * The render kernel computes t = num / d (render_glyph.zig:51,60-61; d an integer, |d| <= 2^17)

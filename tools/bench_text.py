@@ -4,7 +4,11 @@ of the text plan and its Mpixel/s of run area, and the same instances as separat
 origins, disjoint) in a plain plan, which prices the composition.  Under rocprofv3 --kernel-trace --stats the kernel
 shares come from the trace (prepare_kernel vs text_kernel).  Prints one JSON line per configuration.
 
-    python tools/bench_text.py [--lines 4096] [--chars 64] [--steps 20] [--warmup 3]"""
+--rgba adds the same lines as RGBA text plans (fr_text_plan_create_rgba), which prices colour against the coverage plan
+on the same box: alternating per-word colours, all opaque (text_rgba_kernel<4, 0, 0>), and the same with the first line
+in translucent colours (so the plan blends: text_rgba_kernel<4, 0, 1>).
+
+    python tools/bench_text.py [--lines 4096] [--chars 64] [--steps 20] [--warmup 3] [--rgba]"""
 import argparse
 import json
 import os
@@ -53,7 +57,7 @@ def workload(font, n_lines, n_chars, size, seed):
             jh = max(jh, ch)
         jy += jh
         JW = max(JW, x)
-    return gs, rg.make_places(places), rg.make_runs(runs), (y, W), rg.make_jobs(jobs), (jy, JW)
+    return gs, rg.make_places(places), rg.make_runs(runs), (y, W), rg.make_jobs(jobs), (jy, JW), lines
 
 
 def timed(plan, buf, shape, steps, warmup):
@@ -69,13 +73,14 @@ def main():
     ap.add_argument("--chars", type=int, default=64)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--rgba", action="store_true", help="also render the lines as RGBA text plans")
     args = ap.parse_args()
     import torch
     ctx = fr.Context(0)
     for fi, name in enumerate(["DejaVuSans.ttf", "DejaVuSerif-Italic.ttf"]):
         font = load_font(name, allow_hinted=True)        # (DejaVuSans carries hinting instructions)
         for size in (16, 32):
-            gs, places, runs, shape, jobs, jshape = workload(font, args.lines, args.chars, size, seed=100 * fi + size)
+            gs, places, runs, shape, jobs, jshape, lines = workload(font, args.lines, args.chars, size, seed=100 * fi + size)
             dgs = fr.DeviceGlyphSet(ctx, gs)
             plan = fr.TextPlan(dgs, places, runs, fr.FR_COVERAGE_U8, 4, fr.FR_SAMPLE_CENTER)
             buf = torch.empty(shape, dtype=torch.uint8, device="cuda:0")
@@ -85,6 +90,24 @@ def main():
             desc = plan.describe()
             plan.close()
             del buf
+            rgba = {}
+            if args.rgba:
+                words = [(225, 105, 180, 255), (40, 200, 90, 255)]
+                cols = np.array([words[s[:k].count(" ") % 2] for s in lines for k in range(len(s))], np.uint8)
+                clears = np.zeros((len(runs), 4), np.uint8)
+                rbuf = torch.empty(shape + (4,), dtype=torch.uint8, device="cuda:0")
+                for key, translucent in (("opaque", False), ("translucent", True)):
+                    c = cols.copy()
+                    if translucent:
+                        c[:int(runs[0]["count"]), 3] = 160
+                    rplan = fr.TextPlanRGBA(dgs, places, c, runs, clears, 4, fr.FR_SAMPLE_CENTER)
+                    torch.cuda.synchronize()
+                    rms = timed(rplan, rbuf, shape, args.steps, args.warmup)
+                    rgba[f"rgba_{key}_ms"] = round(rms, 4)
+                    rgba[f"rgba_{key}_over_text"] = round(rms / ms, 3)
+                    rgba[f"rgba_{key}_plan"] = rplan.describe()
+                    rplan.close()
+                del rbuf
             cells = fr.Plan(dgs, jobs, fr.FR_COVERAGE_U8, 4, fr.FR_SAMPLE_CENTER)
             jbuf = torch.empty(jshape, dtype=torch.uint8, device="cuda:0")
             torch.cuda.synchronize()
@@ -99,7 +122,7 @@ def main():
                 "text_mpixel_per_s": round(px / 1e6 / (ms / 1e3), 1), "text_plan": desc,
                 "cells_mpixel": round(cpx / 1e6, 3), "cells_ms": round(ms_cells, 4),
                 "cells_mpixel_per_s": round(cpx / 1e6 / (ms_cells / 1e3), 1), "cells_plan": cdesc,
-                "text_over_cells": round(ms / ms_cells, 2)}), flush=True)
+                "text_over_cells": round(ms / ms_cells, 2), **rgba}), flush=True)
     ctx.close()
 
 
