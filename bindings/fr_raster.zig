@@ -29,6 +29,9 @@ pub const SamplePhase = enum(i32) { corner = 0, center = 1 };
 pub const FR_FONT_ALLOW_HINTED: u32 = 1;
 /// crossing-rule flag of the _ex entry points (fr_raster.h: FR_FILL_CONSISTENT)
 pub const FR_FILL_CONSISTENT: u32 = 1;
+/// flags of fr_text_plan_create_rgba only (fr_raster.h): blend and resolve in linear light (sRGB framebuffer), B G R A output
+pub const FR_TEXT_BGRA: u32 = 4;
+pub const FR_TEXT_SRGB: u32 = 8;
 
 pub const RasterParams = extern struct {
     mode: i32,
@@ -128,6 +131,9 @@ pub extern "c" fn fr_qoi_encode_rgb(rgb: [*]const u8, width: u32, height: u32, o
 pub extern "c" fn fr_qoi_encode_gray(gray: [*]const u8, width: u32, height: u32, stride: usize, out: [*]u8, cap: usize, n_out: *usize) c_int;
 /// a standard 4-channel QOI stream (the QOI specification; tools/qoi.zig writes RGB only)
 pub extern "c" fn fr_qoi_encode_rgba(rgba: [*]const u8, width: u32, height: u32, stride_px: usize, out: [*]u8, cap: usize, n_out: *usize) c_int;
+/// the sRGB conversions of FR_TEXT_SRGB plans: 8-bit sRGB -> 16-bit linear light, and back (rounded in the encoded domain)
+pub extern "c" fn fr_srgb_decode(in: [*]const u8, n: usize, out: [*]u16) c_int;
+pub extern "c" fn fr_srgb_encode(in: [*]const u16, n: usize, out: [*]u8) c_int;
 // ---- self-tests of the two arithmetic shortcuts (device-side, exhaustive)
 pub extern "c" fn fr_selftest_division(d_lo: u32, d_hi: u32, mismatches: *u64, bad_divisor: ?*u32, bad_x_bits: ?*u32) c_int;
 pub extern "c" fn fr_selftest_sqrt(mismatches: *u64, bad_x_bits: ?*u32) c_int;

@@ -9,6 +9,7 @@ import os
 FR_WINDING_I16, FR_GRAY_DEBUG, FR_MASK_NONZERO, FR_COVERAGE_U8, FR_SDF_U8 = 0, 1, 2, 3, 4
 FR_SAMPLE_CORNER, FR_SAMPLE_CENTER = 0, 1
 FR_FILL_CONSISTENT = 1           # crossing-rule flag of the _ex entry points (include/fr_raster.h)
+FR_TEXT_SRGB, FR_TEXT_BGRA = 8, 4  # flags of fr_text_plan_create_rgba only: linear-light blending, B G R A output
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -102,6 +103,8 @@ SYMBOLS = [
     ("fr_qoi_encode_rgb", C.c_int, [_P, C.c_uint32, C.c_uint32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("fr_qoi_encode_gray", C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("fr_qoi_encode_rgba", C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("fr_srgb_decode", C.c_int, [_P, C.c_size_t, _P]),
+    ("fr_srgb_encode", C.c_int, [_P, C.c_size_t, _P]),
     ("fr_selftest_sqrt", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     ("fr_selftest_division", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
 ]

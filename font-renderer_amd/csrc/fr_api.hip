@@ -6,6 +6,7 @@
 // without a usable gfx950 device every compute entry point returns FR_E_HIP.
 #include "../../include/fr_raster.h"
 #include "fr_device.hpp"
+#include "fr_srgb.hpp"
 #include "fr_text.hpp"
 
 #include <cmath>
@@ -142,6 +143,7 @@ struct fr_plan {
     // into plan-owned memory before every render, and its counts
     bool text = false;
     bool rgba = false;                 // fr_text_plan_create_rgba: RGBA pixels, text_rgba_kernel
+    bool srgb = false;                 // (rgba) FR_TEXT_SRGB: text_srgb_kernel
     int blend = 0;                     // (rgba) 1 unless every placement colour is opaque
     fr::TextTile *d_tiles = nullptr;
     fr::TextRun *d_runs = nullptr;
@@ -547,9 +549,11 @@ void fr_plan_destroy(fr_plan *plan)
     delete plan;
 }
 
-static int check_flags(uint32_t flags)
+// also: the bits an entry point takes besides FR_FILL_CONSISTENT (fr_text_plan_create_rgba: FR_TEXT_SRGB, FR_TEXT_BGRA)
+static int check_flags(uint32_t flags, uint32_t also = 0u)
 {
-    if (flags & ~(uint32_t)FR_FILL_CONSISTENT) return fail(FR_E_INVALID, "unknown flag bits 0x%x", flags & ~(uint32_t)FR_FILL_CONSISTENT);
+    const uint32_t known = (uint32_t)FR_FILL_CONSISTENT | also;
+    if (flags & ~known) return fail(FR_E_INVALID, "unknown flag bits 0x%x", flags & ~known);
     return FR_OK;
 }
 
@@ -704,10 +708,18 @@ int fr_plan_create_ex(fr_ctx *ctx, const fr_glyphset *gs, const fr_job *jobs, ui
 }
 
 // ---- text runs (include/fr_raster.h) -----------------------------------------------------------
-// the 4 bytes R G B A as one little-endian word, R in the low byte (fr_text.hpp: TextInst::rgba, TextRun::clear)
-static uint32_t rgba_word(const uint8_t *c)
+// the 4 bytes R G B A as one little-endian word, R in the low byte (fr_text.hpp: TextInst::rgba, TextRun::clear); bgra
+// (FR_TEXT_BGRA): B in the low byte, so that the kernels, which treat R and B alike, write B G R A
+static uint32_t rgba_word(const uint8_t *c, bool bgra)
 {
-    return (uint32_t)c[0] | (uint32_t)c[1] << 8 | (uint32_t)c[2] << 16 | (uint32_t)c[3] << 24;
+    return (uint32_t)c[bgra ? 2 : 0] | (uint32_t)c[1] << 8 | (uint32_t)c[bgra ? 0 : 2] << 16 | (uint32_t)c[3] << 24;
+}
+
+// an sRGB text plan's linear colour of a packed word (fr_text.hpp: TextInst::pad, TextRun::pad; fr_srgb.hpp)
+static void linear_words(uint32_t w, uint32_t pad[2])
+{
+    pad[0] = (uint32_t)fr::SRGB_D[w & 0xffu] | (uint32_t)fr::SRGB_D[(w >> 8) & 0xffu] << 16;
+    pad[1] = fr::SRGB_D[(w >> 16) & 0xffu];
 }
 
 int fr_glyphset_set_boxes(fr_glyphset *gs, const int16_t *boxes)
@@ -721,7 +733,8 @@ int fr_glyphset_set_boxes(fr_glyphset *gs, const int16_t *boxes)
 }
 
 // fr_text_plan_create and fr_text_plan_create_rgba: one set of checks and tables.  rgba: place_rgba / run_clear_rgba are
-// the colours (4 bytes each), the mode must be FR_COVERAGE_U8, and the plan renders with text_rgba_kernel.
+// the colours (4 bytes each), the mode must be FR_COVERAGE_U8, the flags may add FR_TEXT_SRGB and FR_TEXT_BGRA, and the
+// plan renders with text_rgba_kernel (text_srgb_kernel under FR_TEXT_SRGB).
 static int text_plan_build(const char *fn, fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place *places,
                            const uint8_t *place_rgba, uint32_t n_places, const fr_text_run *runs,
                            const uint8_t *run_clear_rgba, uint32_t n_runs, const fr_raster_params *params, uint32_t flags,
@@ -729,13 +742,14 @@ static int text_plan_build(const char *fn, fr_ctx *ctx, const fr_glyphset *gs, c
 {
     if (!ctx || !gs || !out) return fail(FR_E_INVALID, "%s: NULL argument", fn);
     *out = nullptr;
-    if (const int frc = check_flags(flags)) return frc;
+    if (const int frc = check_flags(flags, rgba ? FR_TEXT_SRGB | FR_TEXT_BGRA : 0u)) return frc;
     if (gs->ctx != ctx) return fail(FR_E_INVALID, "glyph set belongs to another context");
     if (!params) return fail(FR_E_INVALID, "params is NULL");
     if (params->mode < FR_WINDING_I16 || params->mode > FR_SDF_U8) return fail(FR_E_INVALID, "unknown mode %d", params->mode);
     if (params->sample_phase != FR_SAMPLE_CORNER && params->sample_phase != FR_SAMPLE_CENTER)
         return fail(FR_E_INVALID, "unknown sample_phase %d", params->sample_phase);
     const int n = params->samples_per_axis;
+    const bool srgb = (flags & FR_TEXT_SRGB) != 0, bgra = (flags & FR_TEXT_BGRA) != 0;
     if (rgba) {
         if (params->mode != FR_COVERAGE_U8)
             return fail(FR_E_UNSUPPORTED, "RGBA text runs: mode %d (only FR_COVERAGE_U8)", params->mode);
@@ -798,7 +812,8 @@ static int text_plan_build(const char *fn, fr_ctx *ctx, const fr_glyphset *gs, c
     uint32_t tbase = 0;
     for (uint32_t r = 0; r < n_runs; ++r) {
         const fr_text_run &rn = runs[r];
-        trun[r] = fr::TextRun{rn.w, rn.h, rn.out_x, rn.out_y, rn.scale, rgba ? rgba_word(run_clear_rgba + 4 * (size_t)r) : 0u, {0, 0}};
+        trun[r] = fr::TextRun{rn.w, rn.h, rn.out_x, rn.out_y, rn.scale, rgba ? rgba_word(run_clear_rgba + 4 * (size_t)r, bgra) : 0u, {0, 0}};
+        if (srgb) linear_words(trun[r].clear, trun[r].pad);
         if (!rn.w || !rn.h) continue;
         const uint32_t tx = (rn.w + fr::TEXT_TILE_W - 1) / fr::TEXT_TILE_W, ty = (rn.h + fr::TEXT_TILE_H - 1) / fr::TEXT_TILE_H;
         for (uint32_t y = 0; y < ty; ++y)
@@ -824,8 +839,9 @@ static int text_plan_build(const char *fn, fr_ctx *ctx, const fr_glyphset *gs, c
             if (x0 >= x1 || y0 >= y1) continue;                                            // clipped away
             const uint32_t id = (uint32_t)insts.size();
             insts.push_back(fr::TextInst{(int32_t)ix, pl.pen_y, (int32_t)x0, (int32_t)x1, (int32_t)y0, (int32_t)y1, g,
-                                         2u * gs->h_glyph_seg_start[g], fx64, rgba ? rgba_word(place_rgba + 4 * (size_t)k) : 0u,
+                                         2u * gs->h_glyph_seg_start[g], fx64, rgba ? rgba_word(place_rgba + 4 * (size_t)k, bgra) : 0u,
                                          {0, 0}});
+            if (srgb) linear_words(insts.back().rgba, insts.back().pad);
             used[g] = 1;
             for (int64_t y = y0 / fr::TEXT_TILE_H; y <= (y1 - 1) / fr::TEXT_TILE_H; ++y)
                 for (int64_t x = x0 / fr::TEXT_TILE_W; x <= (x1 - 1) / fr::TEXT_TILE_W; ++x)
@@ -847,6 +863,7 @@ static int text_plan_build(const char *fn, fr_ctx *ctx, const fr_glyphset *gs, c
     if (!p) return fail(FR_E_NOMEM, "%s: host allocation", fn);
     p->ctx = ctx; p->gs = gs; p->params = *params; p->flags = flags; p->text = true;
     p->rgba = rgba;
+    p->srgb = srgb;
     for (uint32_t k = 0; rgba && k < n_places; ++k)
         if (place_rgba[4 * (size_t)k + 3] != 255) { p->blend = 1; break; }
     p->pixels = pixels; p->need_cols = need_cols; p->need_rows = need_rows;
@@ -894,6 +911,24 @@ int fr_text_plan_create_rgba(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_
                            params, flags, true, out);
 }
 
+// the conversions of FR_TEXT_SRGB plans, from the tables text_srgb_kernel reads (fr_srgb.hpp)
+int fr_srgb_decode(const uint8_t *in, size_t n, uint16_t *out)
+{
+    if (n && (!in || !out)) return fail(FR_E_INVALID, "fr_srgb_decode: NULL argument");
+    for (size_t i = 0; i < n; ++i) out[i] = fr::SRGB_D[in[i]];
+    return FR_OK;
+}
+
+int fr_srgb_encode(const uint16_t *in, size_t n, uint8_t *out)
+{
+    if (n && (!in || !out)) return fail(FR_E_INVALID, "fr_srgb_encode: NULL argument");
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t L = in[i], k = fr::SRGB_K[L >> 4];
+        out[i] = (uint8_t)((k & 0xffu) + ((L & 15u) >= (k >> 8) ? 1u : 0u));
+    }
+    return FR_OK;
+}
+
 uint64_t fr_plan_pixels(const fr_plan *plan) { return plan ? plan->pixels : 0; }
 
 int fr_plan_stats(const fr_plan *plan, uint32_t *n_jobs_cov4, uint32_t *n_jobs_general)
@@ -927,7 +962,9 @@ int fr_plan_describe(const fr_plan *plan, char *buf, size_t cap)
     if (plan->text) {
         if (plan->n_tglyphs) add(fill ? "fr::prepare_fill_kernel" : "fr::prepare_kernel", plan->n_tglyphs);
         name[0] = 0;
-        if (plan->rgba)
+        if (plan->srgb)
+            (void)fr::launch_text_srgb(fr::TextArgs{}, plan->params.samples_per_axis, fill, plan->blend, 0u, nullptr, name, sizeof name);
+        else if (plan->rgba)
             (void)fr::launch_text_rgba(fr::TextArgs{}, plan->params.samples_per_axis, fill, plan->blend, 0u, nullptr, name, sizeof name);
         else
             (void)fr::launch_text(fr::TextArgs{}, plan->params.samples_per_axis, fill, 0u, nullptr, name, sizeof name);
@@ -996,7 +1033,8 @@ static int text_launch(fr_plan *plan, void *out_dev, size_t out_stride)
     a.out = static_cast<uint8_t *>(out_dev);
     a.out_stride = out_stride;
     a.phase_center = plan->params.sample_phase == FR_SAMPLE_CENTER ? 1 : 0;
-    if (plan->rgba) HIP_TRY(fr::launch_text_rgba(a, plan->params.samples_per_axis, fill, plan->blend, plan->n_tiles, st));
+    if (plan->srgb) HIP_TRY(fr::launch_text_srgb(a, plan->params.samples_per_axis, fill, plan->blend, plan->n_tiles, st));
+    else if (plan->rgba) HIP_TRY(fr::launch_text_rgba(a, plan->params.samples_per_axis, fill, plan->blend, plan->n_tiles, st));
     else HIP_TRY(fr::launch_text(a, plan->params.samples_per_axis, fill, plan->n_tiles, st));
     return FR_OK;
 }

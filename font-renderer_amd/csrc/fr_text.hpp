@@ -1,4 +1,5 @@
-// fr_text.hpp — the tables of a text plan (fr_api.hip builds them, text_kernel / text_rgba_kernel in fr_text.hip read them)
+// fr_text.hpp — the tables of a text plan (fr_api.hip builds them, text_kernel / text_rgba_kernel / text_srgb_kernel in
+// fr_text.hip read them)
 #pragma once
 #include "fr_device.hpp"
 
@@ -13,13 +14,13 @@ struct TextInst {      // one placement, resolved on the host (fr_api.hip)
     uint32_t rec;      // first record of the glyph: 2 * glyph_seg_start[glyph]
     uint32_t fx64;     // pen_x64 mod 64
     uint32_t rgba;     // an RGBA text plan's placement colour, R in the low byte (the bytes R G B A in memory); else 0
-    uint32_t pad[2];
+    uint32_t pad[2];   // an sRGB text plan's linear colour: D[R] | D[G] << 16, D[B] (fr_srgb.hpp); else 0
 };
 struct TextRun {       // == fr_text_run's geometry
     uint32_t w, h, out_x, out_y;
     float scale;
     uint32_t clear;    // an RGBA text plan's clear colour, packed as TextInst::rgba; else 0
-    uint32_t pad[2];
+    uint32_t pad[2];   // an sRGB text plan's linear clear colour, packed as TextInst::pad; else 0
 };
 struct TextTile {      // one 64 x 16 tile of a run and its instance list list[lbeg .. lend)
     uint32_t run, x0, y0, lbeg, lend;
@@ -44,6 +45,9 @@ constexpr int TEXT_TILE_W = 64, TEXT_TILE_H = 16, TEXT_WAVES = 4;
 hipError_t launch_text(const TextArgs &a, int n, int fill, uint32_t n_tiles, hipStream_t stream, char *name = nullptr, size_t name_cap = 0);
 // the same for RGBA text plans: blend = 0 when every placement colour of the plan is opaque (A = 255), else 1
 hipError_t launch_text_rgba(const TextArgs &a, int n, int fill, int blend, uint32_t n_tiles, hipStream_t stream,
+                            char *name = nullptr, size_t name_cap = 0);
+// the same for FR_TEXT_SRGB plans (text_srgb_kernel): blending and resolve in linear light
+hipError_t launch_text_srgb(const TextArgs &a, int n, int fill, int blend, uint32_t n_tiles, hipStream_t stream,
                             char *name = nullptr, size_t name_cap = 0);
 
 }  // namespace fr

@@ -243,6 +243,25 @@ def render_glyph_dims(box, units_per_em: int, font_size: int):
     return (int(mn[0]), int(mn[1])), (int(mx[0]), int(mx[1])), w.value, h.value, s.value
 
 
+def srgb_to_linear16(values) -> np.ndarray:
+    """fr_srgb_decode: 8-bit sRGB values -> 16-bit linear light (u16, same shape), as FR_TEXT_SRGB plans decode them"""
+    a = np.ascontiguousarray(values, np.uint8)
+    out = np.empty(a.shape, np.uint16)
+    L.check(L.load_library().fr_srgb_decode(L.ptr(a), a.size, L.ptr(out)))
+    return out
+
+
+def linear16_to_srgb(values) -> np.ndarray:
+    """fr_srgb_encode: 16-bit linear light -> 8-bit sRGB (u8, same shape), rounded to nearest in the encoded domain"""
+    a = np.asarray(values)
+    if a.size and (a.min() < 0 or a.max() > 65535):
+        raise ValueError("linear16_to_srgb: values outside [0, 65535]")
+    a = np.ascontiguousarray(a, np.uint16)
+    out = np.empty(a.shape, np.uint8)
+    L.check(L.load_library().fr_srgb_encode(L.ptr(a), a.size, L.ptr(out)))
+    return out
+
+
 def renderGlyph(glyph: Glyph, font_info: FontInformation, font_size: int, *, ctx: Optional[Context] = None,
                 mode: int = L.FR_GRAY_DEBUG, flags: int = 0) -> Gray:
     """render_glyph.zig:11 — `pub fn renderGlyph(glyph, font_info, font_size) !Image.Gray`."""

@@ -86,14 +86,17 @@ def _rgba(c) -> tuple:
 
 
 def render_text_rgba(font: Font, text, font_size: int, color=(225, 105, 180, 255), background=(0, 0, 0, 0), colors=None,
-                     *, samples_per_axis: int = 4, phase: int = L.FR_SAMPLE_CENTER, flags: int = 0,
-                     ctx: Optional[Context] = None) -> RGBA:
+                     *, samples_per_axis: int = 4, phase: int = L.FR_SAMPLE_CENTER, flags: int = 0, srgb: bool = False,
+                     bgra: bool = False, ctx: Optional[Context] = None) -> RGBA:
     """One line of text as one RGBA image (fr_text_plan_create_rgba): every glyph blended per sample in order over
     `background`, in `color` or, if `colors` is given, in colors[k] for character k (e.g. to highlight a word).  The
-    defaults are the reference's frame: pink text (shader.slang) on a transparent clear colour.  Sized as render_text."""
+    defaults are the reference's frame: pink text (shader.slang) on a transparent clear colour.  Sized as render_text.
+    srgb: blend and resolve in linear light, as the reference's sRGB swapchain does (FR_TEXT_SRGB); bgra: the pixels'
+    bytes are B G R A (FR_TEXT_BGRA; the colours stay R G B A)."""
     import torch
 
     ctx = ctx or default_context()
+    flags |= (L.FR_TEXT_SRGB if srgb else 0) | (L.FR_TEXT_BGRA if bgra else 0)
     n_chars = len(text)
     if colors is not None and len(colors) != n_chars:
         raise ValueError(f"colors: {len(colors)} colours for {n_chars} characters")

@@ -249,14 +249,39 @@ int fr_text_plan_create(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place
  * the order of overlapping placements matters.
  * The output element is 4 bytes, R G B A in memory, NOT premultiplied: the framebuffer's bytes.  With a (0,0,0,0) clear
  * colour and opaque text, RGB comes out premultiplied by the coverage, as in the reference's transparent window.
- * Blending is on the stored 8-bit values, as on a UNORM framebuffer; the reference's B8G8R8A8_SRGB swapchain blends in
- * linear light, which is not done here (nor BGRA order).
+ * Without FR_TEXT_SRGB, blending is on the stored 8-bit values, as on a UNORM framebuffer.
  * params->mode must be FR_COVERAGE_U8 with n in {1, 2, 4}, either phase (another mode or n: FR_E_UNSUPPORTED; an unknown
  * mode value stays FR_E_INVALID, as for fr_text_plan_create); FR_FILL_CONSISTENT
  * applies per instance.  A NULL colour array with a non-zero count is FR_E_INVALID; every other check of
  * fr_text_plan_create applies.  The result is an ordinary fr_plan; out_dev must be 4-byte aligned (FR_E_INVALID), and
  * out_stride / out_x / out_rows and the 2^26 pitch limit count RGBA pixels.  fr_plan_pixels stays a pixel count;
- * fr_plan_describe names text_rgba_kernel<n, fill, blend> (blend = 0 when every placement colour has A = 255).          */
+ * fr_plan_describe names text_rgba_kernel<n, fill, blend> (blend = 0 when every placement colour has A = 255), or
+ * text_srgb_kernel<n, fill, blend> for an FR_TEXT_SRGB plan.
+ *
+ * Flags of fr_text_plan_create_rgba only (every other entry point that takes flags keeps returning FR_E_INVALID for
+ * them); both combine with each other and with FR_FILL_CONSISTENT.  Bit 2 is not assigned: it stays FR_E_INVALID everywhere,
+as it was for fr_text_plan_create_rgba before these flags existed:
+ *   FR_TEXT_SRGB  blend and resolve in linear light, as the reference's B8G8R8A8_SRGB / SRGB_NONLINEAR swapchain
+ *       (VulkanContext.zig:834) does: the stored bytes are sRGB, decoded before blending and encoded after it, per sample.
+ *       With f the IEC 61966-2-1 decode (c <= 0.04045 ? c / 12.92 : ((c + 0.055) / 1.055)^2.4) in binary64:
+ *           D[v] = floor(65535 f(v / 255) + 1/2)                v in 0 .. 255   (fr_srgb_decode: 16-bit linear light)
+ *           E(L) = #{k in 1 .. 255 : L >= T[k]},  T[k] = ceil(65535 f((k - 1/2) / 255))   (fr_srgb_encode: round to
+ *                  nearest in the encoded domain, L in 0 .. 65535)
+ *       A sample starts at Q_r; an instance k with C_k = (R, G, B, A) whose winding at it is non-zero updates it by
+ *           c' = E((D[C_k.c] * A + D[c] * (255 - A) + 127) div 255)    for c in R, G, B
+ *           a' = A                                                    (alpha is stored linearly, the blend unchanged)
+ *       Resolve: each colour channel is E((sum over the n x n sub-samples of D[v_s] + n^2/2) div n^2); alpha as above.
+ *       So: with n = 1 and every A = 255 the output equals the plan without FR_TEXT_SRGB byte for byte; the alpha channel
+ *       always equals it; A = 0 keeps RGB; with A = 255 the last covering instance wins per sample; white (255,255,255,
+ *       255) over (0,0,0,0) gives RGB = E(round(65535 k / n^2)) for the k of n^2 samples the text plan lights (50 % of
+ *       white over black: 188, not 128).  Vulkan leaves the precision of blending to the implementation, so this integer
+ *       form is the definition here, not a claim of bit parity with any driver.
+ *   FR_TEXT_BGRA  the output element is B G R A in memory instead of R G B A (the swapchain's order); the colour arrays
+ *       stay R G B A.  Equivalent to swapping R and B in every placement and clear colour, with or without FR_TEXT_SRGB.
+ */
+#define FR_TEXT_BGRA 4u
+#define FR_TEXT_SRGB 8u
+
 int fr_text_plan_create_rgba(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place *places, const uint8_t *place_rgba,
                              uint32_t n_places, const fr_text_run *runs, const uint8_t *run_clear_rgba, uint32_t n_runs,
                              const fr_raster_params *params, uint32_t flags, fr_plan **out);
@@ -398,6 +423,12 @@ int fr_qoi_encode_gray(const uint8_t *gray, uint32_t width, uint32_t height, siz
  * QOI_OP_RGBA when alpha changes, the index hash r*3 + g*5 + b*7 + a*11, previous pixel (0,0,0,255) before the first.
  * rgba: 4 bytes per pixel, rows stride_px pixels apart (>= width).  Worst case 22 + 5 * width * height bytes.          */
 int fr_qoi_encode_rgba(const uint8_t *rgba, uint32_t width, uint32_t height, size_t stride_px, uint8_t *out, size_t cap, size_t *n_out);
+
+/* ---- sRGB conversions (host side) of FR_TEXT_SRGB plans: D and E as defined at fr_text_plan_create_rgba -------------
+ * fr_srgb_decode: out[i] = D[in[i]] (16-bit linear light); fr_srgb_encode: out[i] = E(in[i]).  n values each; NULL with
+ * n > 0 is FR_E_INVALID.                                                                                               */
+int fr_srgb_decode(const uint8_t *in, size_t n, uint16_t *out);
+int fr_srgb_encode(const uint16_t *in, size_t n, uint8_t *out);
 
 /* ---- self-test: exhaustive device-side check of an arithmetic shortcut ----------
  * The render kernel computes t = num / d (render_glyph.zig:51,60-61; d an integer, |d| <= 2^17)

@@ -8,7 +8,10 @@ shares come from the trace (prepare_kernel vs text_kernel).  Prints one JSON lin
 on the same box: alternating per-word colours, all opaque (text_rgba_kernel<4, 0, 0>), and the same with the first line
 in translucent colours (so the plan blends: text_rgba_kernel<4, 0, 1>).
 
-    python tools/bench_text.py [--lines 4096] [--chars 64] [--steps 20] [--warmup 3] [--rgba]"""
+--srgb adds the same two colourings as sRGB text plans (FR_TEXT_SRGB: blending and resolve in linear light,
+text_srgb_kernel<4, 0, 0> / <4, 0, 1>), priced against the coverage plan (and the RGBA plans, with --rgba) in the same run.
+
+    python tools/bench_text.py [--lines 4096] [--chars 64] [--steps 20] [--warmup 3] [--rgba] [--srgb]"""
 import argparse
 import json
 import os
@@ -74,6 +77,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rgba", action="store_true", help="also render the lines as RGBA text plans")
+    ap.add_argument("--srgb", action="store_true", help="also render the lines as sRGB (linear-light) RGBA text plans")
     args = ap.parse_args()
     import torch
     ctx = fr.Context(0)
@@ -91,7 +95,8 @@ def main():
             plan.close()
             del buf
             rgba = {}
-            if args.rgba:
+            kinds = ([("rgba", 0)] if args.rgba else []) + ([("srgb", fr.FR_TEXT_SRGB)] if args.srgb else [])
+            if kinds:
                 words = [(225, 105, 180, 255), (40, 200, 90, 255)]
                 cols = np.array([words[s[:k].count(" ") % 2] for s in lines for k in range(len(s))], np.uint8)
                 clears = np.zeros((len(runs), 4), np.uint8)
@@ -100,13 +105,16 @@ def main():
                     c = cols.copy()
                     if translucent:
                         c[:int(runs[0]["count"]), 3] = 160
-                    rplan = fr.TextPlanRGBA(dgs, places, c, runs, clears, 4, fr.FR_SAMPLE_CENTER)
-                    torch.cuda.synchronize()
-                    rms = timed(rplan, rbuf, shape, args.steps, args.warmup)
-                    rgba[f"rgba_{key}_ms"] = round(rms, 4)
-                    rgba[f"rgba_{key}_over_text"] = round(rms / ms, 3)
-                    rgba[f"rgba_{key}_plan"] = rplan.describe()
-                    rplan.close()
+                    for kind, flags in kinds:
+                        rplan = fr.TextPlanRGBA(dgs, places, c, runs, clears, 4, fr.FR_SAMPLE_CENTER, flags)
+                        torch.cuda.synchronize()
+                        rms = timed(rplan, rbuf, shape, args.steps, args.warmup)
+                        rgba[f"{kind}_{key}_ms"] = round(rms, 4)
+                        rgba[f"{kind}_{key}_over_text"] = round(rms / ms, 3)
+                        rgba[f"{kind}_{key}_plan"] = rplan.describe()
+                        rplan.close()
+                    if args.rgba and args.srgb:
+                        rgba[f"srgb_{key}_over_rgba"] = round(rgba[f"srgb_{key}_ms"] / rgba[f"rgba_{key}_ms"], 3)
                 del rbuf
             cells = fr.Plan(dgs, jobs, fr.FR_COVERAGE_U8, 4, fr.FR_SAMPLE_CENTER)
             jbuf = torch.empty(jshape, dtype=torch.uint8, device="cuda:0")
