@@ -32,6 +32,8 @@ pub const FR_FILL_CONSISTENT: u32 = 1;
 /// flags of fr_text_plan_create_rgba only (fr_raster.h): blend and resolve in linear light (sRGB framebuffer), B G R A output
 pub const FR_TEXT_BGRA: u32 = 4;
 pub const FR_TEXT_SRGB: u32 = 8;
+/// flag of fr_text_plan_create_rgba only (fr_raster.h): draw over the pixels already in the output
+pub const FR_TEXT_LOAD: u32 = 32;
 
 pub const RasterParams = extern struct {
     mode: i32,

@@ -10,6 +10,7 @@ FR_WINDING_I16, FR_GRAY_DEBUG, FR_MASK_NONZERO, FR_COVERAGE_U8, FR_SDF_U8 = 0, 1
 FR_SAMPLE_CORNER, FR_SAMPLE_CENTER = 0, 1
 FR_FILL_CONSISTENT = 1           # crossing-rule flag of the _ex entry points (include/fr_raster.h)
 FR_TEXT_SRGB, FR_TEXT_BGRA = 8, 4  # flags of fr_text_plan_create_rgba only: linear-light blending, B G R A output
+FR_TEXT_LOAD = 32                  # fr_text_plan_create_rgba only: draw over the pixels already in the output
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 

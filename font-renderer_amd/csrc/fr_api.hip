@@ -144,6 +144,7 @@ struct fr_plan {
     bool text = false;
     bool rgba = false;                 // fr_text_plan_create_rgba: RGBA pixels, text_rgba_kernel
     bool srgb = false;                 // (rgba) FR_TEXT_SRGB: text_srgb_kernel
+    bool load = false;                 // (rgba) FR_TEXT_LOAD: text_rgba_load_kernel / text_srgb_load_kernel, occupied tiles only
     int blend = 0;                     // (rgba) 1 unless every placement colour is opaque
     fr::TextTile *d_tiles = nullptr;
     fr::TextRun *d_runs = nullptr;
@@ -549,7 +550,8 @@ void fr_plan_destroy(fr_plan *plan)
     delete plan;
 }
 
-// also: the bits an entry point takes besides FR_FILL_CONSISTENT (fr_text_plan_create_rgba: FR_TEXT_SRGB, FR_TEXT_BGRA)
+// also: the bits an entry point takes besides FR_FILL_CONSISTENT (fr_text_plan_create_rgba: FR_TEXT_SRGB, FR_TEXT_BGRA,
+// FR_TEXT_LOAD)
 static int check_flags(uint32_t flags, uint32_t also = 0u)
 {
     const uint32_t known = (uint32_t)FR_FILL_CONSISTENT | also;
@@ -733,8 +735,9 @@ int fr_glyphset_set_boxes(fr_glyphset *gs, const int16_t *boxes)
 }
 
 // fr_text_plan_create and fr_text_plan_create_rgba: one set of checks and tables.  rgba: place_rgba / run_clear_rgba are
-// the colours (4 bytes each), the mode must be FR_COVERAGE_U8, the flags may add FR_TEXT_SRGB and FR_TEXT_BGRA, and the
-// plan renders with text_rgba_kernel (text_srgb_kernel under FR_TEXT_SRGB).
+// the colours (4 bytes each), the mode must be FR_COVERAGE_U8, the flags may add FR_TEXT_SRGB, FR_TEXT_BGRA and
+// FR_TEXT_LOAD, and the plan renders with text_rgba_kernel (text_srgb_kernel under FR_TEXT_SRGB; their _load_ forms
+// under FR_TEXT_LOAD, which ignores run_clear_rgba and launches only the tiles some instance meets).
 static int text_plan_build(const char *fn, fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place *places,
                            const uint8_t *place_rgba, uint32_t n_places, const fr_text_run *runs,
                            const uint8_t *run_clear_rgba, uint32_t n_runs, const fr_raster_params *params, uint32_t flags,
@@ -742,14 +745,14 @@ static int text_plan_build(const char *fn, fr_ctx *ctx, const fr_glyphset *gs, c
 {
     if (!ctx || !gs || !out) return fail(FR_E_INVALID, "%s: NULL argument", fn);
     *out = nullptr;
-    if (const int frc = check_flags(flags, rgba ? FR_TEXT_SRGB | FR_TEXT_BGRA : 0u)) return frc;
+    if (const int frc = check_flags(flags, rgba ? FR_TEXT_SRGB | FR_TEXT_BGRA | FR_TEXT_LOAD : 0u)) return frc;
     if (gs->ctx != ctx) return fail(FR_E_INVALID, "glyph set belongs to another context");
     if (!params) return fail(FR_E_INVALID, "params is NULL");
     if (params->mode < FR_WINDING_I16 || params->mode > FR_SDF_U8) return fail(FR_E_INVALID, "unknown mode %d", params->mode);
     if (params->sample_phase != FR_SAMPLE_CORNER && params->sample_phase != FR_SAMPLE_CENTER)
         return fail(FR_E_INVALID, "unknown sample_phase %d", params->sample_phase);
     const int n = params->samples_per_axis;
-    const bool srgb = (flags & FR_TEXT_SRGB) != 0, bgra = (flags & FR_TEXT_BGRA) != 0;
+    const bool srgb = (flags & FR_TEXT_SRGB) != 0, bgra = (flags & FR_TEXT_BGRA) != 0, load = (flags & FR_TEXT_LOAD) != 0;
     if (rgba) {
         if (params->mode != FR_COVERAGE_U8)
             return fail(FR_E_UNSUPPORTED, "RGBA text runs: mode %d (only FR_COVERAGE_U8)", params->mode);
@@ -763,7 +766,7 @@ static int text_plan_build(const char *fn, fr_ctx *ctx, const fr_glyphset *gs, c
     if (n_places && !places) return fail(FR_E_INVALID, "places is NULL");
     if (n_runs && !runs) return fail(FR_E_INVALID, "runs is NULL");
     if (rgba && n_places && !place_rgba) return fail(FR_E_INVALID, "place_rgba is NULL");
-    if (rgba && n_runs && !run_clear_rgba) return fail(FR_E_INVALID, "run_clear_rgba is NULL");
+    if (rgba && !load && n_runs && !run_clear_rgba) return fail(FR_E_INVALID, "run_clear_rgba is NULL");
     if (gs->n_glyphs && gs->h_box.empty()) return fail(FR_E_INVALID, "text runs need the glyph boxes: fr_glyphset_set_boxes");
     const int64_t LIM = (int64_t)1 << 22;
     uint64_t pixels = 0, need_cols = 0, need_rows = 0, n_tiles = 0;
@@ -812,7 +815,8 @@ static int text_plan_build(const char *fn, fr_ctx *ctx, const fr_glyphset *gs, c
     uint32_t tbase = 0;
     for (uint32_t r = 0; r < n_runs; ++r) {
         const fr_text_run &rn = runs[r];
-        trun[r] = fr::TextRun{rn.w, rn.h, rn.out_x, rn.out_y, rn.scale, rgba ? rgba_word(run_clear_rgba + 4 * (size_t)r, bgra) : 0u, {0, 0}};
+        const bool clear = rgba && !load;                                                  // (FR_TEXT_LOAD: no clear colour)
+        trun[r] = fr::TextRun{rn.w, rn.h, rn.out_x, rn.out_y, rn.scale, clear ? rgba_word(run_clear_rgba + 4 * (size_t)r, bgra) : 0u, {0, 0}};
         if (srgb) linear_words(trun[r].clear, trun[r].pad);
         if (!rn.w || !rn.h) continue;
         const uint32_t tx = (rn.w + fr::TEXT_TILE_W - 1) / fr::TEXT_TILE_W, ty = (rn.h + fr::TEXT_TILE_H - 1) / fr::TEXT_TILE_H;
@@ -855,6 +859,8 @@ static int text_plan_build(const char *fn, fr_ctx *ctx, const fr_glyphset *gs, c
     uint32_t at = 0;
     for (auto &t : tiles) { t.lbeg = at; at += t.lend; t.lend = t.lbeg; }
     for (const auto &h : hits) list[tiles[h.first].lend++] = h.second;
+    if (load)                          // FR_TEXT_LOAD: a tile no instance meets leaves its pixels as they are: not launched
+        tiles.erase(std::remove_if(tiles.begin(), tiles.end(), [](const fr::TextTile &t) { return t.lbeg == t.lend; }), tiles.end());
     std::vector<uint32_t> glyphs;
     for (uint32_t g = 0; g < gs->n_glyphs; ++g)
         if (used[g]) glyphs.push_back(g);
@@ -864,10 +870,11 @@ static int text_plan_build(const char *fn, fr_ctx *ctx, const fr_glyphset *gs, c
     p->ctx = ctx; p->gs = gs; p->params = *params; p->flags = flags; p->text = true;
     p->rgba = rgba;
     p->srgb = srgb;
+    p->load = load;
     for (uint32_t k = 0; rgba && k < n_places; ++k)
         if (place_rgba[4 * (size_t)k + 3] != 255) { p->blend = 1; break; }
     p->pixels = pixels; p->need_cols = need_cols; p->need_rows = need_rows;
-    p->n_tiles = (uint32_t)n_tiles; p->n_insts = (uint32_t)insts.size(); p->n_tglyphs = (uint32_t)glyphs.size();
+    p->n_tiles = (uint32_t)tiles.size(); p->n_insts = (uint32_t)insts.size(); p->n_tglyphs = (uint32_t)glyphs.size();
     hipStream_t st = ctx->stream;
     hipError_t e = hipSetDevice(ctx->device);
     auto upload = [&](auto *&dst, const auto &v) {
@@ -962,7 +969,10 @@ int fr_plan_describe(const fr_plan *plan, char *buf, size_t cap)
     if (plan->text) {
         if (plan->n_tglyphs) add(fill ? "fr::prepare_fill_kernel" : "fr::prepare_kernel", plan->n_tglyphs);
         name[0] = 0;
-        if (plan->srgb)
+        if (plan->load)
+            (void)fr::launch_text_load(fr::TextArgs{}, plan->params.samples_per_axis, fill, plan->blend, plan->srgb, 0u, nullptr, name,
+                                       sizeof name);
+        else if (plan->srgb)
             (void)fr::launch_text_srgb(fr::TextArgs{}, plan->params.samples_per_axis, fill, plan->blend, 0u, nullptr, name, sizeof name);
         else if (plan->rgba)
             (void)fr::launch_text_rgba(fr::TextArgs{}, plan->params.samples_per_axis, fill, plan->blend, 0u, nullptr, name, sizeof name);
@@ -1002,7 +1012,9 @@ static int ensure_aux(fr_ctx *ctx)
 static int plan_check(fr_plan *plan, void *out_dev, size_t out_stride, size_t out_rows)
 {
     if (!plan) return fail(FR_E_INVALID, "plan is NULL");
-    if (plan->n_jobs == 0 && plan->n_tiles == 0) return FR_OK;
+    // (a FR_TEXT_LOAD plan whose instances are all clipped away launches no tile, but its runs still need the output the
+    // same plan with a visible glyph would: it is checked as that plan is)
+    if (plan->n_jobs == 0 && plan->n_tiles == 0 && !(plan->load && plan->pixels)) return FR_OK;
     if (!out_dev) return fail(FR_E_INVALID, "out is NULL");
     if (plan->need_cols > out_stride || plan->need_rows > out_rows)
         return fail(FR_E_INVALID, "jobs need %llu x %llu elements, output is %zu x %zu",
@@ -1033,7 +1045,8 @@ static int text_launch(fr_plan *plan, void *out_dev, size_t out_stride)
     a.out = static_cast<uint8_t *>(out_dev);
     a.out_stride = out_stride;
     a.phase_center = plan->params.sample_phase == FR_SAMPLE_CENTER ? 1 : 0;
-    if (plan->srgb) HIP_TRY(fr::launch_text_srgb(a, plan->params.samples_per_axis, fill, plan->blend, plan->n_tiles, st));
+    if (plan->load) HIP_TRY(fr::launch_text_load(a, plan->params.samples_per_axis, fill, plan->blend, plan->srgb, plan->n_tiles, st));
+    else if (plan->srgb) HIP_TRY(fr::launch_text_srgb(a, plan->params.samples_per_axis, fill, plan->blend, plan->n_tiles, st));
     else if (plan->rgba) HIP_TRY(fr::launch_text_rgba(a, plan->params.samples_per_axis, fill, plan->blend, plan->n_tiles, st));
     else HIP_TRY(fr::launch_text(a, plan->params.samples_per_axis, fill, plan->n_tiles, st));
     return FR_OK;

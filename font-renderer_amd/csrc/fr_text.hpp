@@ -1,5 +1,5 @@
-// fr_text.hpp — the tables of a text plan (fr_api.hip builds them, text_kernel / text_rgba_kernel / text_srgb_kernel in
-// fr_text.hip read them)
+// fr_text.hpp — the tables of a text plan (fr_api.hip builds them, text_kernel / text_rgba_kernel / text_srgb_kernel and
+// their FR_TEXT_LOAD forms in fr_text.hip read them)
 #pragma once
 #include "fr_device.hpp"
 
@@ -48,6 +48,10 @@ hipError_t launch_text_rgba(const TextArgs &a, int n, int fill, int blend, uint3
                             char *name = nullptr, size_t name_cap = 0);
 // the same for FR_TEXT_SRGB plans (text_srgb_kernel): blending and resolve in linear light
 hipError_t launch_text_srgb(const TextArgs &a, int n, int fill, int blend, uint32_t n_tiles, hipStream_t stream,
+                            char *name = nullptr, size_t name_cap = 0);
+// the same for FR_TEXT_LOAD plans (text_rgba_load_kernel, or text_srgb_load_kernel when srgb): the samples start at the
+// output's pixels; n_tiles counts only the tiles with a non-empty instance list
+hipError_t launch_text_load(const TextArgs &a, int n, int fill, int blend, int srgb, uint32_t n_tiles, hipStream_t stream,
                             char *name = nullptr, size_t name_cap = 0);
 
 }  // namespace fr

@@ -203,19 +203,20 @@ def _colors(rows, n: int, what: str) -> np.ndarray:
 class TextPlanRGBA(Plan):
     """fr_text_plan_create_rgba: a text plan whose placements carry colours (n_places x 4 u8, R G B A) blended per sample
     in placement order over each run's clear colour (n_runs x 4 u8); renders RGBA pixels (4 bytes each, 4-byte aligned
-    output; strides and rows count pixels).  FR_COVERAGE_U8 only, n in {1, 2, 4}."""
+    output; strides and rows count pixels).  FR_COVERAGE_U8 only, n in {1, 2, 4}.  With FR_TEXT_LOAD in `flags` the
+    samples start at the pixels already in the output instead, and run_clear_rgba may be None (it is ignored)."""
 
     def __init__(self, dgs: DeviceGlyphSet, places: np.ndarray, place_rgba, runs: np.ndarray, run_clear_rgba,
                  samples_per_axis: int = 4, sample_phase: int = L.FR_SAMPLE_CENTER, flags: int = 0):
         places = np.ascontiguousarray(places, PLACE_DTYPE)
         runs = np.ascontiguousarray(runs, RUN_DTYPE)
         pc = _colors(place_rgba, len(places), "place_rgba")
-        rc = _colors(run_clear_rgba, len(runs), "run_clear_rgba")
+        rc = None if run_clear_rgba is None else _colors(run_clear_rgba, len(runs), "run_clear_rgba")     # (None: NULL)
         self.ctx, self.dgs, self.mode = dgs.ctx, dgs, L.FR_COVERAGE_U8
         self.params = L.RasterParams(L.FR_COVERAGE_U8, samples_per_axis, sample_phase, 0)
         h = C.c_void_p()
         L.check(self.ctx._lib.fr_text_plan_create_rgba(self.ctx._h, dgs._h, L.ptr(places), L.ptr(pc), len(places),
-                                                       L.ptr(runs), L.ptr(rc), len(runs), C.byref(self.params), flags,
+                                                       L.ptr(runs), None if rc is None else L.ptr(rc), len(runs), C.byref(self.params), flags,
                                                        C.byref(h)))
         self._h = h
         self.n_places, self.n_runs = len(places), len(runs)

@@ -1,6 +1,7 @@
 """Text runs: a string laid out by the reference's pen walk (Appli.zig:318-349) and rendered as one anti-aliased image
 through a text plan (fr_text_plan_create, include/fr_raster.h), or as one RGBA image through an RGBA text plan
-(fr_text_plan_create_rgba).  Nothing is computed in Python but the image size."""
+(fr_text_plan_create_rgba), or drawn over an RGBA image the caller has (FR_TEXT_LOAD).  Nothing is computed in Python but
+the image size and the pen positions."""
 from __future__ import annotations
 
 import math
@@ -119,3 +120,53 @@ def render_text_rgba(font: Font, text, font_size: int, color=(225, 105, 180, 255
         plan.close()
         dgs.close()
     return im
+
+
+def draw_text_rgba(image: RGBA, font: Font, text, font_size: int, x: float, y: int, color=(225, 105, 180, 255), colors=None,
+                   *, samples_per_axis: int = 4, phase: int = L.FR_SAMPLE_CENTER, flags: int = 0, srgb: bool = False,
+                   bgra: bool = False, ctx: Optional[Context] = None) -> RGBA:
+    """One line of text drawn in place into `image` (FR_TEXT_LOAD): every sample starts at the pixel already there, and
+    the glyphs are blended over it per sample in order, in `color` or colors[k] for character k.  x: the pen origin's
+    image x in pixels (fractional x is kept to 1/64 pixel: pen_x64 = floor(64 x + 1/2)); y: the baseline's row.  The
+    line is one run covering the whole image, so glyphs are clipped at its edges.  The whole image is copied to the
+    device and back; on the device only the 64 x 16 tiles that some glyph cell meets are read (and, where needed,
+    written), and every pixel no glyph sample reaches comes back with its bytes unchanged.  srgb / bgra as
+    render_text_rgba: the image's bytes are sRGB / B G R A.  image.data must be a (height * width, 4) uint8 array
+    (ValueError otherwise).  Returns `image`."""
+    import torch
+
+    w, h, data = image.width, image.height, image.data
+    if not (isinstance(w, (int, np.integer)) and isinstance(h, (int, np.integer)) and w >= 0 and h >= 0):
+        raise ValueError(f"image: width {w!r} and height {h!r} must be non-negative integers")
+    if not isinstance(data, np.ndarray) or data.dtype != np.uint8 or data.shape != (h * w, 4):
+        raise ValueError(f"image.data: expected a ({h * w}, 4) uint8 array for {w} x {h} pixels, got "
+                         f"{getattr(data, 'shape', None)} {getattr(data, 'dtype', type(data).__name__)}")
+    ctx = ctx or default_context()
+    flags |= L.FR_TEXT_LOAD | (L.FR_TEXT_SRGB if srgb else 0) | (L.FR_TEXT_BGRA if bgra else 0)
+    n_chars = len(text)
+    if colors is not None and len(colors) != n_chars:
+        raise ValueError(f"colors: {len(colors)} colours for {n_chars} characters")
+    per_char = [_rgba(c) for c in colors] if colors is not None else [_rgba(color)] * n_chars
+    if n_chars == 0 or image.width == 0 or image.height == 0:
+        return image
+    gi, pen, _ = font.layout(text, font_size)
+    gs, kept = font.glyphset(sorted(set(int(g) for g in gi)), skip_unsupported=False)
+    local = {g: k for k, g in enumerate(kept)}
+    scale = np.float32(font_size) / np.float32(font.information.units_per_em)
+    x64 = math.floor(64.0 * float(x) + 0.5)
+    places = make_places([(local[int(g)], x64 + int(p), int(y)) for g, p in zip(gi, pen)])
+    runs = make_runs([(0, len(places), image.width, image.height, 0, 0, scale)])
+    dgs = DeviceGlyphSet(ctx, gs)
+    try:
+        plan = TextPlanRGBA(dgs, places, per_char, runs, None, samples_per_axis, phase, flags)
+        try:
+            buf = torch.from_numpy(np.ascontiguousarray(image.data)).to(f"cuda:{ctx.device}")
+            torch.cuda.synchronize(ctx.device)
+            plan.render(buf.data_ptr(), image.width, image.height)
+            ctx.sync()
+            image.data[:] = buf.cpu().numpy()
+        finally:
+            plan.close()
+    finally:
+        dgs.close()
+    return image

@@ -282,6 +282,30 @@ as it was for fr_text_plan_create_rgba before these flags existed:
 #define FR_TEXT_BGRA 4u
 #define FR_TEXT_SRGB 8u
 
+/* FR_TEXT_LOAD  (fr_text_plan_create_rgba only) draw over the pixels already in the output, as Vulkan's
+ *       VK_ATTACHMENT_LOAD_OP_LOAD does: the same as drawing the existing image into the MSAA target as an opaque
+ *       full-screen quad before the glyphs.
+ *   Start value: every sub-sample of a pixel P of run r starts at the value P holds in the output when the render
+ *       reaches it in stream order; Q_r is not used.  With FR_TEXT_SRGB the stored bytes are sRGB, decoded by D above;
+ *       with FR_TEXT_BGRA the stored element is read as B G R A, as it is written.  The per-sample non-zero test, the
+ *       blend in placement order (alpha replaced by A), the resolve, the cells and the clipping are unchanged.
+ *   Consequences:
+ *     1. A pixel at which no instance lights any sample comes back byte-identical: (n^2 v + n^2/2) div n^2 = v, and for
+ *        sRGB E(D[v]) = v for all 256 values (true of the tables above).
+ *     2. If the output holds Q_r in every pixel of run r, the result equals the same plan without FR_TEXT_LOAD and with
+ *        clear colour Q_r, byte for byte.
+ *     3. A render is not idempotent: rendering twice composites over the first result, which starts from resolved pixels.
+ *   run_clear_rgba may be NULL and is ignored.  Runs still must not overlap; a pixel outside every run is neither read
+ *   nor written.  Within a run the unit is the 64 x 16 tile (from the run's top-left pixel): only the tiles some clipped
+ *   instance cell meets are launched, and a pixel of any other tile is neither read nor written, so text on a large
+ *   image costs the tiles under the text.  In a launched tile every pixel of the run is read, and may be written back
+ *   (unchanged, by consequence 1, where no sample is lit).  A plan whose instances are all clipped away launches
+ *   nothing, but fr_plan_render still checks the output as for the same plan with a visible glyph.  Combines with FR_TEXT_SRGB,
+ *   FR_TEXT_BGRA and FR_FILL_CONSISTENT; every other entry point that takes flags returns FR_E_INVALID for it.
+ *   fr_plan_describe names text_rgba_load_kernel<n, fill, blend> (text_srgb_load_kernel<n, fill, blend> with
+ *   FR_TEXT_SRGB) with the instance count; fr_plan_pixels stays the sum of the runs' w*h.                              */
+#define FR_TEXT_LOAD 32u
+
 int fr_text_plan_create_rgba(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place *places, const uint8_t *place_rgba,
                              uint32_t n_places, const fr_text_run *runs, const uint8_t *run_clear_rgba, uint32_t n_runs,
                              const fr_raster_params *params, uint32_t flags, fr_plan **out);

@@ -11,7 +11,16 @@ in translucent colours (so the plan blends: text_rgba_kernel<4, 0, 1>).
 --srgb adds the same two colourings as sRGB text plans (FR_TEXT_SRGB: blending and resolve in linear light,
 text_srgb_kernel<4, 0, 0> / <4, 0, 1>), priced against the coverage plan (and the RGBA plans, with --rgba) in the same run.
 
-    python tools/bench_text.py [--lines 4096] [--chars 64] [--steps 20] [--warmup 3] [--rgba] [--srgb]"""
+--load adds FR_TEXT_LOAD (text drawn over the pixels already in the output): (a) the same lines and colourings as LOAD
+plans over a noise background, UNORM and sRGB (text_rgba_load_kernel / text_srgb_load_kernel), priced against the
+clear-colour plans of the same kind in the same run; (b) a sparse overlay, printed as its own JSON line: 16 lines of 64
+characters at size 32 on a 3840 x 2160 frame as one LOAD run covering the frame, against the same placements in one
+clear-colour run over the whole frame.  Every render of a LOAD plan, warm-up included, starts from a fresh device copy of
+the noise in a buffer of its own (the copy is outside the timed region); the clear-colour plans render into another
+buffer, after the same copy.  "tiles_load_computed" is the tile count recomputed here from the clipped cells, not observed: the launched
+grid is what a rocprofv3 --kernel-trace run shows (e.g. of --load --lines 1).
+
+    python tools/bench_text.py [--lines 4096] [--chars 64] [--steps 20] [--warmup 3] [--rgba] [--srgb] [--load]"""
 import argparse
 import json
 import os
@@ -63,6 +72,20 @@ def workload(font, n_lines, n_chars, size, seed):
     return gs, rg.make_places(places), rg.make_runs(runs), (y, W), rg.make_jobs(jobs), (jy, JW), lines
 
 
+def timed_over(plan, buf, src, shape, steps, warmup):
+    """the median ms of `steps` renders into buf, after `warmup`, each starting from a fresh copy of src (not timed)"""
+    import torch
+    ms = []
+    for i in range(warmup + steps):
+        buf.copy_(src)
+        torch.cuda.synchronize()
+        t = plan.render_timed(buf.data_ptr(), shape[1], shape[0])
+        if i >= warmup:
+            ms.append(t)
+    ms.sort()
+    return ms[len(ms) // 2]
+
+
 def timed(plan, buf, shape, steps, warmup):
     for _ in range(warmup):
         plan.render_timed(buf.data_ptr(), shape[1], shape[0])
@@ -78,6 +101,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rgba", action="store_true", help="also render the lines as RGBA text plans")
     ap.add_argument("--srgb", action="store_true", help="also render the lines as sRGB (linear-light) RGBA text plans")
+    ap.add_argument("--load", action="store_true", help="also draw the lines over a noise background (FR_TEXT_LOAD), each "
+                    "render from a fresh copy of it, and a sparse overlay on a 3840 x 2160 noise frame")
     args = ap.parse_args()
     import torch
     ctx = fr.Context(0)
@@ -95,12 +120,15 @@ def main():
             plan.close()
             del buf
             rgba = {}
-            kinds = ([("rgba", 0)] if args.rgba else []) + ([("srgb", fr.FR_TEXT_SRGB)] if args.srgb else [])
+            kinds = ([("rgba", 0)] if args.rgba or args.load else []) + ([("srgb", fr.FR_TEXT_SRGB)] if args.srgb or args.load else [])
             if kinds:
                 words = [(225, 105, 180, 255), (40, 200, 90, 255)]
                 cols = np.array([words[s[:k].count(" ") % 2] for s in lines for k in range(len(s))], np.uint8)
                 clears = np.zeros((len(runs), 4), np.uint8)
                 rbuf = torch.empty(shape + (4,), dtype=torch.uint8, device="cuda:0")
+                if args.load:                          # the noise background, and the LOAD plans' own buffer
+                    noise = torch.empty_like(rbuf).random_(0, 256, generator=torch.Generator("cuda:0").manual_seed(size))
+                    lbuf = torch.empty_like(rbuf)
                 for key, translucent in (("opaque", False), ("translucent", True)):
                     c = cols.copy()
                     if translucent:
@@ -108,14 +136,26 @@ def main():
                     for kind, flags in kinds:
                         rplan = fr.TextPlanRGBA(dgs, places, c, runs, clears, 4, fr.FR_SAMPLE_CENTER, flags)
                         torch.cuda.synchronize()
-                        rms = timed(rplan, rbuf, shape, args.steps, args.warmup)
+                        # (with --load the clear-colour plans too render after a copy of the noise: the same cache state)
+                        rms = (timed_over(rplan, rbuf, noise, shape, args.steps, args.warmup) if args.load
+                               else timed(rplan, rbuf, shape, args.steps, args.warmup))
                         rgba[f"{kind}_{key}_ms"] = round(rms, 4)
                         rgba[f"{kind}_{key}_over_text"] = round(rms / ms, 3)
                         rgba[f"{kind}_{key}_plan"] = rplan.describe()
                         rplan.close()
+                        if args.load:
+                            lplan = fr.TextPlanRGBA(dgs, places, c, runs, None, 4, fr.FR_SAMPLE_CENTER, flags | fr.FR_TEXT_LOAD)
+                            torch.cuda.synchronize()
+                            lms = timed_over(lplan, lbuf, noise, shape, args.steps, args.warmup)
+                            rgba[f"{kind}_load_{key}_ms"] = round(lms, 4)
+                            rgba[f"{kind}_load_{key}_over_{kind}"] = round(lms / rms, 3)
+                            rgba[f"{kind}_load_{key}_plan"] = lplan.describe()
+                            lplan.close()
                     if args.rgba and args.srgb:
                         rgba[f"srgb_{key}_over_rgba"] = round(rgba[f"srgb_{key}_ms"] / rgba[f"rgba_{key}_ms"], 3)
                 del rbuf
+                if args.load:
+                    del noise, lbuf
             cells = fr.Plan(dgs, jobs, fr.FR_COVERAGE_U8, 4, fr.FR_SAMPLE_CENTER)
             jbuf = torch.empty(jshape, dtype=torch.uint8, device="cuda:0")
             torch.cuda.synchronize()
@@ -131,7 +171,61 @@ def main():
                 "cells_mpixel": round(cpx / 1e6, 3), "cells_ms": round(ms_cells, 4),
                 "cells_mpixel_per_s": round(cpx / 1e6 / (ms_cells / 1e3), 1), "cells_plan": cdesc,
                 "text_over_cells": round(ms / ms_cells, 2), **rgba}), flush=True)
+    if args.load:
+        overlay(ctx, args)
     ctx.close()
+
+
+def tiles_met(places, run, gs, scale):
+    """the 64 x 16 tiles of `run` that some clipped instance cell meets (what a LOAD plan launches)"""
+    w, h, seg, met = int(run["w"]), int(run["h"]), gs.segments_per_glyph(), set()
+    for pl in places[int(run["first"]):int(run["first"]) + int(run["count"])]:
+        if not seg[int(pl["glyph"])]:
+            continue
+        c0, r0, cw, ch = fr.instance_cell(gs.boxes[int(pl["glyph"])], scale, int(pl["pen_x64"]), int(pl["pen_y"]))
+        x0, x1, y0, y1 = max(c0, 0), min(c0 + cw, w), max(r0, 0), min(r0 + ch, h)
+        if x0 < x1 and y0 < y1:
+            met |= {(ty, tx) for ty in range(y0 // 16, (y1 - 1) // 16 + 1) for tx in range(x0 // 64, (x1 - 1) // 64 + 1)}
+    return len(met)
+
+
+def overlay(ctx, args):
+    """(b): 16 lines of 64 characters, size 32, on a 3840 x 2160 frame: one LOAD run over the frame vs one clear-colour run"""
+    import torch
+    W, H, size, n_lines, n_chars = 3840, 2160, 32, 16, 64
+    font = load_font("DejaVuSans.ttf", allow_hinted=True)
+    rng = np.random.default_rng(7)
+    alphabet = [chr(c) for c in range(0x20, 0x7f)]
+    lay = [font.layout("".join(rng.choice(alphabet, n_chars)), size) for _ in range(n_lines)]
+    gs, kept = font.glyphset(sorted({int(g) for gi, _, _ in lay for g in gi}), skip_unsupported=False)
+    local = {g: k for k, g in enumerate(kept)}
+    scale = np.float32(size) / np.float32(font.information.units_per_em)
+    places = rg.make_places([(local[int(g)], 64 * 160 + 21 + int(p), 120 + 128 * i)
+                             for i, (gi, pen, _) in enumerate(lay) for g, p in zip(gi, pen)])
+    runs = rg.make_runs([(0, len(places), W, H, 0, 0, scale)])
+    cols = np.array([(255, 255, 255, 255)] * len(places), np.uint8)
+    dgs = fr.DeviceGlyphSet(ctx, gs)
+    noise = torch.empty((H, W, 4), dtype=torch.uint8, device="cuda:0").random_(0, 256, generator=torch.Generator("cuda:0").manual_seed(1))
+    cbuf, lbuf = torch.empty_like(noise), torch.empty_like(noise)     # the clear-colour plans' output; the LOAD plans'
+    out = {"case": "overlay", "frame": [W, H], "lines": n_lines, "chars": n_chars, "font_size": size,
+           "instances": int(len(places)), "tiles_clear": ((W + 63) // 64) * ((H + 15) // 16),
+           "tiles_load_computed": tiles_met(places, runs[0], gs, scale)}
+    for key, alpha in (("opaque", 255), ("translucent", 200)):
+        cols[:, 3] = alpha
+        for kind, flags in (("rgba", 0), ("srgb", fr.FR_TEXT_SRGB)):
+            for load in (False, True):
+                plan = fr.TextPlanRGBA(dgs, places, cols, runs, None if load else [(0, 0, 0, 0)], 4, fr.FR_SAMPLE_CENTER,
+                                       flags | (fr.FR_TEXT_LOAD if load else 0))
+                torch.cuda.synchronize()
+                tag = f"{kind}{'_load' if load else ''}_{key}"
+                ms = timed_over(plan, lbuf if load else cbuf, noise, (H, W), args.steps, args.warmup)
+                out[tag + "_ms"] = round(ms, 4)
+                out[tag + "_plan"] = plan.describe()
+                plan.close()
+            out[f"{kind}_{key}_clear_over_load"] = round(out[f"{kind}_{key}_ms"] / out[f"{kind}_load_{key}_ms"], 3)
+    del noise, cbuf, lbuf
+    dgs.close()
+    print(json.dumps(out), flush=True)
 
 
 if __name__ == "__main__":
