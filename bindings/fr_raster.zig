@@ -62,6 +62,16 @@ pub const GlyphPlace = extern struct {
     pen_y: i32,
 };
 
+/// a placement with its own size, slant and a baseline kept to 1/64 pixel (fr_raster.h: fr_glyph_place_ex): scale 0 is the
+/// run's scale; slant k draws a point (x, y) of the outline at (x + k*y, y); pen_y64 = 64 * pen_y is row pen_y
+pub const GlyphPlaceEx = extern struct {
+    glyph: u32,
+    pen_x64: i32,
+    pen_y64: i32,
+    scale: f32,
+    slant: f32,
+};
+
 pub const TextRun = extern struct {
     first: u32,
     count: u32,
@@ -99,6 +109,9 @@ pub extern "c" fn fr_text_plan_create(ctx: *fr_ctx, gs: *const fr_glyphset, plac
 /// RGBA text plans (DESIGN.md section 5): place_rgba = 4 bytes (R, G, B, A) per placement, run_clear_rgba = 4 per run;
 /// the plan renders RGBA pixels (4-byte aligned output, strides in pixels)
 pub extern "c" fn fr_text_plan_create_rgba(ctx: *fr_ctx, gs: *const fr_glyphset, places: [*]const GlyphPlace, place_rgba: [*]const u8, n_places: u32, runs: [*]const TextRun, run_clear_rgba: [*]const u8, n_runs: u32, params: *const RasterParams, flags: u32, out: *?*fr_plan) c_int;
+/// the two text plan entry points for GlyphPlaceEx placements (same runs, flags, colours and error codes)
+pub extern "c" fn fr_text_plan_create_ex(ctx: *fr_ctx, gs: *const fr_glyphset, places: [*]const GlyphPlaceEx, n_places: u32, runs: [*]const TextRun, n_runs: u32, params: *const RasterParams, flags: u32, out: *?*fr_plan) c_int;
+pub extern "c" fn fr_text_plan_create_rgba_ex(ctx: *fr_ctx, gs: *const fr_glyphset, places: [*]const GlyphPlaceEx, place_rgba: [*]const u8, n_places: u32, runs: [*]const TextRun, run_clear_rgba: [*]const u8, n_runs: u32, params: *const RasterParams, flags: u32, out: *?*fr_plan) c_int;
 pub extern "c" fn fr_allgather_bands(ctx: *fr_ctx, nccl_comm: *anyopaque, atlas_dev: *anyopaque, band_bytes: usize) c_int;
 pub extern "c" fn fr_gather_bands(ctx: *fr_ctx, nccl_comm: *anyopaque, atlas_dev: *anyopaque, band_bytes: usize, root: c_int) c_int;
 pub extern "c" fn fr_render_batch(ctx: *fr_ctx, gs: *const fr_glyphset, jobs: [*]const Job, n_jobs: u32, params: *const RasterParams, out_host: *anyopaque, out_stride: usize, out_rows: usize) c_int;

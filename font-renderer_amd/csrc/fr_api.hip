@@ -149,6 +149,8 @@ struct fr_plan {
     fr::TextTile *d_tiles = nullptr;
     fr::TextRun *d_runs = nullptr;
     fr::TextInst *d_insts = nullptr;
+    bool place_ex = false;             // fr_text_plan_create_ex / _rgba_ex: d_insts_ex and the kernels of fr_text_place.hip
+    fr::TextInstEx *d_insts_ex = nullptr;
     uint32_t *d_tlist = nullptr, *d_tglyphs = nullptr, *d_trec_count = nullptr;
     fr::Rec *d_trecs = nullptr;
     uint32_t n_tiles = 0, n_insts = 0, n_tglyphs = 0;
@@ -542,7 +544,7 @@ void fr_plan_destroy(fr_plan *plan)
     (void)hipSetDevice(plan->ctx->device);
     (void)hipStreamSynchronize(plan->ctx->stream);
     dfree(plan->d_jobs); dfree(plan->d_job_seg); dfree(plan->d_large); dfree(plan->d_bits); dfree(plan->d_job_bits);
-    dfree(plan->d_tiles); dfree(plan->d_runs); dfree(plan->d_insts); dfree(plan->d_tlist); dfree(plan->d_tglyphs);
+    dfree(plan->d_tiles); dfree(plan->d_runs); dfree(plan->d_insts); dfree(plan->d_insts_ex); dfree(plan->d_tlist); dfree(plan->d_tglyphs);
     dfree(plan->d_trec_count); dfree(plan->d_trecs);
     if (plan->ev0) (void)hipEventDestroy(plan->ev0);
     if (plan->ev1) (void)hipEventDestroy(plan->ev1);
@@ -738,8 +740,10 @@ int fr_glyphset_set_boxes(fr_glyphset *gs, const int16_t *boxes)
 // the colours (4 bytes each), the mode must be FR_COVERAGE_U8, the flags may add FR_TEXT_SRGB, FR_TEXT_BGRA and
 // FR_TEXT_LOAD, and the plan renders with text_rgba_kernel (text_srgb_kernel under FR_TEXT_SRGB; their _load_ forms
 // under FR_TEXT_LOAD, which ignores run_clear_rgba and launches only the tiles some instance meets).
+// The placements are places (fr_glyph_place) or, when that is NULL and ex is set, places_ex (fr_glyph_place_ex: own
+// scale, slant, sub-pixel baseline; TextInstEx and the kernels of fr_text_place.hip): only the cell differs.
 static int text_plan_build(const char *fn, fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place *places,
-                           const uint8_t *place_rgba, uint32_t n_places, const fr_text_run *runs,
+                           const fr_glyph_place_ex *places_ex, bool ex, const uint8_t *place_rgba, uint32_t n_places, const fr_text_run *runs,
                            const uint8_t *run_clear_rgba, uint32_t n_runs, const fr_raster_params *params, uint32_t flags,
                            bool rgba, fr_plan **out)
 {
@@ -763,7 +767,7 @@ static int text_plan_build(const char *fn, fr_ctx *ctx, const fr_glyphset *gs, c
         if (params->mode == FR_COVERAGE_U8 ? (n != 1 && n != 2 && n != 4) : n != 1)
             return fail(FR_E_UNSUPPORTED, "text runs: samples_per_axis %d with mode %d", n, params->mode);
     }
-    if (n_places && !places) return fail(FR_E_INVALID, "places is NULL");
+    if (n_places && !(ex ? (const void *)places_ex : (const void *)places)) return fail(FR_E_INVALID, "places is NULL");
     if (n_runs && !runs) return fail(FR_E_INVALID, "runs is NULL");
     if (rgba && n_places && !place_rgba) return fail(FR_E_INVALID, "place_rgba is NULL");
     if (rgba && !load && n_runs && !run_clear_rgba) return fail(FR_E_INVALID, "run_clear_rgba is NULL");
@@ -777,10 +781,19 @@ static int text_plan_build(const char *fn, fr_ctx *ctx, const fr_glyphset *gs, c
         if (rn.scale < 9.5367431640625e-07f || rn.scale > 1048576.0f) return fail(FR_E_UNSUPPORTED, "run %u: scale outside [2^-20, 2^20]", r);
         if (rn.w > 65535u || rn.h > 65535u) return fail(FR_E_UNSUPPORTED, "run %u: larger than 65535", r);
         for (uint32_t k = rn.first; k < rn.first + rn.count; ++k) {
-            const fr_glyph_place &pl = places[k];
-            if (pl.glyph >= gs->n_glyphs) return fail(FR_E_INVALID, "place %u: glyph %u of %u", k, pl.glyph, gs->n_glyphs);
-            if ((pl.pen_x64 >> 6) < -LIM || (pl.pen_x64 >> 6) > LIM || pl.pen_y < -LIM || pl.pen_y > LIM)
+            const uint32_t glyph = ex ? places_ex[k].glyph : places[k].glyph;
+            const int32_t px64 = ex ? places_ex[k].pen_x64 : places[k].pen_x64;
+            const int32_t py = ex ? places_ex[k].pen_y64 >> 6 : places[k].pen_y;
+            if (glyph >= gs->n_glyphs) return fail(FR_E_INVALID, "place %u: glyph %u of %u", k, glyph, gs->n_glyphs);
+            if ((px64 >> 6) < -LIM || (px64 >> 6) > LIM || py < -LIM || py > LIM)
                 return fail(FR_E_UNSUPPORTED, "place %u: pen beyond +-2^22 pixels", k);
+            if (!ex) continue;
+            const float ps = places_ex[k].scale, sl = places_ex[k].slant;
+            if (!(ps >= 0.0f) || !std::isfinite(ps)) return fail(FR_E_INVALID, "place %u: scale must be 0, or finite and > 0", k);
+            if (ps != 0.0f && (ps < 9.5367431640625e-07f || ps > 1048576.0f))
+                return fail(FR_E_UNSUPPORTED, "place %u: scale outside [2^-20, 2^20]", k);
+            if (!std::isfinite(sl)) return fail(FR_E_INVALID, "place %u: slant must be finite", k);
+            if (std::fabs(sl) > 4.0f) return fail(FR_E_UNSUPPORTED, "place %u: |slant| above 4", k);
         }
         pixels += (uint64_t)rn.w * rn.h;
         if (rn.w && rn.h) {
@@ -810,6 +823,7 @@ static int text_plan_build(const char *fn, fr_ctx *ctx, const fr_glyphset *gs, c
     std::vector<fr::TextRun> trun(n_runs);
     std::vector<fr::TextTile> tiles((size_t)n_tiles);
     std::vector<fr::TextInst> insts;
+    std::vector<fr::TextInstEx> insts_ex;
     std::vector<std::pair<uint32_t, uint32_t>> hits;            // (tile, instance)
     std::vector<uint8_t> used(gs->n_glyphs, 0);
     uint32_t tbase = 0;
@@ -823,29 +837,43 @@ static int text_plan_build(const char *fn, fr_ctx *ctx, const fr_glyphset *gs, c
         for (uint32_t y = 0; y < ty; ++y)
             for (uint32_t x = 0; x < tx; ++x)
                 tiles[tbase + y * tx + x] = fr::TextTile{r, x * fr::TEXT_TILE_W, y * fr::TEXT_TILE_H, 0, 0, {0, 0, 0}};
-        const float s = rn.scale;
         for (uint32_t k = rn.first; k < rn.first + rn.count; ++k) {
-            const fr_glyph_place &pl = places[k];
-            const uint32_t g = pl.glyph;
+            const uint32_t g = ex ? places_ex[k].glyph : places[k].glyph;
+            const int32_t pen_x64 = ex ? places_ex[k].pen_x64 : places[k].pen_x64;
+            const int32_t pen_y = ex ? places_ex[k].pen_y64 >> 6 : places[k].pen_y;              // iy
+            const uint32_t fy64 = ex ? (uint32_t)places_ex[k].pen_y64 & 63u : 0u;
+            const float s = ex && places_ex[k].scale != 0.0f ? places_ex[k].scale : rn.scale;
+            const float sl = ex ? places_ex[k].slant : 0.0f;
             if (gs->h_glyph_seg_start[g + 1] == gs->h_glyph_seg_start[g]) continue;        // no segment: no winding anywhere
             const int16_t *b = &gs->h_box[4 * (size_t)g];
             // render_glyph.zig:13-17 in binary32, as fr_render_glyph_dims / fr_atlas_layout
-            const int64_t mnx = (int64_t)std::floor((float)b[0] * s), mny = (int64_t)std::floor((float)b[1] * s);
-            const int64_t mxx = (int64_t)std::ceil((float)b[2] * s), mxy = (int64_t)std::ceil((float)b[3] * s);
-            const int64_t ix = pl.pen_x64 >> 6;
-            const uint32_t fx64 = (uint32_t)pl.pen_x64 & 63u;
-            const int64_t cw = mxx - mnx + 1 + (fx64 ? 1 : 0), ch = mxy - mny + 1;
+            // (fr_glyph_place_ex: the box sheared by the slant, lo = min(x_min + k*y_min, x_min + k*y_max), hi likewise,
+            // one rounding per operation; with k = 0 lo = x_min and hi = x_max.  One more row when fy != 0)
+            const float ky0 = sl * (float)b[1], ky1 = sl * (float)b[3];
+            const float lo = ex ? std::min((float)b[0] + ky0, (float)b[0] + ky1) : (float)b[0];
+            const float hi = ex ? std::max((float)b[2] + ky0, (float)b[2] + ky1) : (float)b[2];
+            const int64_t mnx = (int64_t)std::floor(lo * s), mny = (int64_t)std::floor((float)b[1] * s);
+            const int64_t mxx = (int64_t)std::ceil(hi * s), mxy = (int64_t)std::ceil((float)b[3] * s);
+            const int64_t ix = pen_x64 >> 6;
+            const uint32_t fx64 = (uint32_t)pen_x64 & 63u;
+            const int64_t cw = mxx - mnx + 1 + (fx64 ? 1 : 0), ch = mxy - mny + 1 + (fy64 ? 1 : 0);
             if (mnx < -LIM || mxx > LIM || mny < -LIM || mxy > LIM || cw > 65535 || ch > 65535)
                 return fail(FR_E_UNSUPPORTED, "place %u: cell beyond +-2^22 pixels or larger than 65535", k);
-            const int64_t c0 = ix + mnx, r0 = (int64_t)pl.pen_y - mxy;
+            const int64_t c0 = ix + mnx, r0 = (int64_t)pen_y - mxy;
             const int64_t x0 = std::max<int64_t>(c0, 0), x1 = std::min<int64_t>(c0 + cw, rn.w);
             const int64_t y0 = std::max<int64_t>(r0, 0), y1 = std::min<int64_t>(r0 + ch, rn.h);
             if (x0 >= x1 || y0 >= y1) continue;                                            // clipped away
-            const uint32_t id = (uint32_t)insts.size();
-            insts.push_back(fr::TextInst{(int32_t)ix, pl.pen_y, (int32_t)x0, (int32_t)x1, (int32_t)y0, (int32_t)y1, g,
-                                         2u * gs->h_glyph_seg_start[g], fx64, rgba ? rgba_word(place_rgba + 4 * (size_t)k, bgra) : 0u,
-                                         {0, 0}});
-            if (srgb) linear_words(insts.back().rgba, insts.back().pad);
+            const uint32_t id = (uint32_t)(ex ? insts_ex.size() : insts.size());
+            const uint32_t word = rgba ? rgba_word(place_rgba + 4 * (size_t)k, bgra) : 0u;
+            if (ex) {
+                insts_ex.push_back(fr::TextInstEx{(int32_t)ix, pen_y, (int32_t)x0, (int32_t)x1, (int32_t)y0, (int32_t)y1, g,
+                                                  2u * gs->h_glyph_seg_start[g], fx64, word, {0, 0}, fy64, s, sl, 0u});
+                if (srgb) linear_words(word, insts_ex.back().pad);
+            } else {
+                insts.push_back(fr::TextInst{(int32_t)ix, pen_y, (int32_t)x0, (int32_t)x1, (int32_t)y0, (int32_t)y1, g,
+                                             2u * gs->h_glyph_seg_start[g], fx64, word, {0, 0}});
+                if (srgb) linear_words(word, insts.back().pad);
+            }
             used[g] = 1;
             for (int64_t y = y0 / fr::TEXT_TILE_H; y <= (y1 - 1) / fr::TEXT_TILE_H; ++y)
                 for (int64_t x = x0 / fr::TEXT_TILE_W; x <= (x1 - 1) / fr::TEXT_TILE_W; ++x)
@@ -871,10 +899,11 @@ static int text_plan_build(const char *fn, fr_ctx *ctx, const fr_glyphset *gs, c
     p->rgba = rgba;
     p->srgb = srgb;
     p->load = load;
+    p->place_ex = ex;
     for (uint32_t k = 0; rgba && k < n_places; ++k)
         if (place_rgba[4 * (size_t)k + 3] != 255) { p->blend = 1; break; }
     p->pixels = pixels; p->need_cols = need_cols; p->need_rows = need_rows;
-    p->n_tiles = (uint32_t)tiles.size(); p->n_insts = (uint32_t)insts.size(); p->n_tglyphs = (uint32_t)glyphs.size();
+    p->n_tiles = (uint32_t)tiles.size(); p->n_insts = (uint32_t)(ex ? insts_ex.size() : insts.size()); p->n_tglyphs = (uint32_t)glyphs.size();
     hipStream_t st = ctx->stream;
     hipError_t e = hipSetDevice(ctx->device);
     auto upload = [&](auto *&dst, const auto &v) {
@@ -886,6 +915,7 @@ static int text_plan_build(const char *fn, fr_ctx *ctx, const fr_glyphset *gs, c
     upload(p->d_tiles, tiles);
     upload(p->d_runs, trun);
     upload(p->d_insts, insts);
+    upload(p->d_insts_ex, insts_ex);
     upload(p->d_tlist, list);
     upload(p->d_tglyphs, glyphs);
     if (e == hipSuccess && p->n_tglyphs) e = hipMalloc(&p->d_trecs, 2 * (size_t)gs->n_seg * sizeof(fr::Rec));
@@ -906,7 +936,7 @@ int fr_text_plan_create(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place
                         const fr_text_run *runs, uint32_t n_runs, const fr_raster_params *params, uint32_t flags,
                         fr_plan **out)
 {
-    return text_plan_build("fr_text_plan_create", ctx, gs, places, nullptr, n_places, runs, nullptr, n_runs, params, flags,
+    return text_plan_build("fr_text_plan_create", ctx, gs, places, nullptr, false, nullptr, n_places, runs, nullptr, n_runs, params, flags,
                            false, out);
 }
 
@@ -914,8 +944,25 @@ int fr_text_plan_create_rgba(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_
                              uint32_t n_places, const fr_text_run *runs, const uint8_t *run_clear_rgba, uint32_t n_runs,
                              const fr_raster_params *params, uint32_t flags, fr_plan **out)
 {
-    return text_plan_build("fr_text_plan_create_rgba", ctx, gs, places, place_rgba, n_places, runs, run_clear_rgba, n_runs,
-                           params, flags, true, out);
+    return text_plan_build("fr_text_plan_create_rgba", ctx, gs, places, nullptr, false, place_rgba, n_places, runs, run_clear_rgba,
+                           n_runs, params, flags, true, out);
+}
+
+// the same two for fr_glyph_place_ex placements: own scale, slant and sub-pixel baseline per placement (fr_text_place.hip)
+int fr_text_plan_create_ex(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place_ex *places, uint32_t n_places,
+                           const fr_text_run *runs, uint32_t n_runs, const fr_raster_params *params, uint32_t flags,
+                           fr_plan **out)
+{
+    return text_plan_build("fr_text_plan_create_ex", ctx, gs, nullptr, places, true, nullptr, n_places, runs, nullptr, n_runs,
+                           params, flags, false, out);
+}
+
+int fr_text_plan_create_rgba_ex(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place_ex *places, const uint8_t *place_rgba,
+                                uint32_t n_places, const fr_text_run *runs, const uint8_t *run_clear_rgba, uint32_t n_runs,
+                                const fr_raster_params *params, uint32_t flags, fr_plan **out)
+{
+    return text_plan_build("fr_text_plan_create_rgba_ex", ctx, gs, nullptr, places, true, place_rgba, n_places, runs,
+                           run_clear_rgba, n_runs, params, flags, true, out);
 }
 
 // the conversions of FR_TEXT_SRGB plans, from the tables text_srgb_kernel reads (fr_srgb.hpp)
@@ -969,7 +1016,10 @@ int fr_plan_describe(const fr_plan *plan, char *buf, size_t cap)
     if (plan->text) {
         if (plan->n_tglyphs) add(fill ? "fr::prepare_fill_kernel" : "fr::prepare_kernel", plan->n_tglyphs);
         name[0] = 0;
-        if (plan->load)
+        if (plan->place_ex)
+            (void)fr::launch_text_place(fr::TextPlaceArgs{}, plan->params.samples_per_axis, fill, plan->rgba, plan->blend, plan->srgb,
+                                        plan->load, 0u, nullptr, name, sizeof name);
+        else if (plan->load)
             (void)fr::launch_text_load(fr::TextArgs{}, plan->params.samples_per_axis, fill, plan->blend, plan->srgb, 0u, nullptr, name,
                                        sizeof name);
         else if (plan->srgb)
@@ -1038,6 +1088,17 @@ static int text_launch(fr_plan *plan, void *out_dev, size_t out_stride)
         fr::launch_prepare(plan->gs->d_pts, plan->gs->d_seg_p0, plan->gs->d_glyph_seg_start, plan->d_tglyphs, plan->n_tglyphs,
                            plan->d_trecs, plan->d_trec_count, st, fill);
         HIP_TRY(hipGetLastError());
+    }
+    if (plan->place_ex) {
+        fr::TextPlaceArgs a;
+        a.tiles = plan->d_tiles; a.runs = plan->d_runs; a.insts = plan->d_insts_ex; a.list = plan->d_tlist;
+        a.recs = plan->d_trecs; a.rec_count = plan->d_trec_count;
+        a.out = static_cast<uint8_t *>(out_dev);
+        a.out_stride = out_stride;
+        a.phase_center = plan->params.sample_phase == FR_SAMPLE_CENTER ? 1 : 0;
+        HIP_TRY(fr::launch_text_place(a, plan->params.samples_per_axis, fill, plan->rgba, plan->blend, plan->srgb, plan->load,
+                                      plan->n_tiles, st));
+        return FR_OK;
     }
     fr::TextArgs a;
     a.tiles = plan->d_tiles; a.runs = plan->d_runs; a.insts = plan->d_insts; a.list = plan->d_tlist;

@@ -16,6 +16,21 @@ struct TextInst {      // one placement, resolved on the host (fr_api.hip)
     uint32_t rgba;     // an RGBA text plan's placement colour, R in the low byte (the bytes R G B A in memory); else 0
     uint32_t pad[2];   // an sRGB text plan's linear colour: D[R] | D[G] << 16, D[B] (fr_srgb.hpp); else 0
 };
+struct TextInstEx {    // one fr_glyph_place_ex, resolved on the host: TextInst and the placement's own sample map
+    int32_t ix;        // floor(pen_x64 / 64)
+    int32_t iy;        // floor(pen_y64 / 64)
+    int32_t x0, x1;    // the (sheared) cell's columns [x0, x1), clipped to the run
+    int32_t y0, y1;    // its rows [y0, y1), clipped likewise
+    uint32_t glyph;
+    uint32_t rec;
+    uint32_t fx64;     // pen_x64 mod 64
+    uint32_t rgba;     // as TextInst::rgba
+    uint32_t pad[2];   // as TextInst::pad
+    uint32_t fy64;     // pen_y64 mod 64
+    float scale;       // the placement's scale (the run's when fr_glyph_place_ex::scale is 0)
+    float slant;       // k: cx = t - k * cy
+    uint32_t pad2;
+};
 struct TextRun {       // == fr_text_run's geometry
     uint32_t w, h, out_x, out_y;
     float scale;
@@ -37,6 +52,18 @@ struct TextArgs {
     uint64_t out_stride;   // elements
     int32_t phase_center;
 };
+struct TextPlaceArgs {     // TextArgs for the placement kernels (fr_text_place.hip): the instances are TextInstEx
+    const TextTile *tiles;
+    const TextRun *runs;
+    const TextInstEx *insts;
+    const uint32_t *list;
+    const Rec *recs;
+    const uint32_t *rec_count;
+    uint8_t *out;
+    uint64_t out_stride;
+    int32_t phase_center;
+};
+static_assert(sizeof(TextInstEx) == 64, "text tables");
 static_assert(sizeof(TextInst) == 48 && sizeof(TextRun) == 32 && sizeof(TextTile) == 32, "text tables");
 
 constexpr int TEXT_TILE_W = 64, TEXT_TILE_H = 16, TEXT_WAVES = 4;
@@ -53,5 +80,11 @@ hipError_t launch_text_srgb(const TextArgs &a, int n, int fill, int blend, uint3
 // output's pixels; n_tiles counts only the tiles with a non-empty instance list
 hipError_t launch_text_load(const TextArgs &a, int n, int fill, int blend, int srgb, uint32_t n_tiles, hipStream_t stream,
                             char *name = nullptr, size_t name_cap = 0);
+
+// the same five families for plans of fr_glyph_place_ex placements (fr_text_place.hip: text_place_kernel,
+// text_place_rgba_kernel, text_place_srgb_kernel, text_place_rgba_load_kernel, text_place_srgb_load_kernel).
+// rgba = 0: coverage / mask (blend, srgb and load are then 0)
+hipError_t launch_text_place(const TextPlaceArgs &a, int n, int fill, int rgba, int blend, int srgb, int load, uint32_t n_tiles,
+                             hipStream_t stream, char *name = nullptr, size_t name_cap = 0);
 
 }  // namespace fr

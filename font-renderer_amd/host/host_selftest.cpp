@@ -1,6 +1,9 @@
 // host_selftest.cpp — exercises the C++ host mirror (fr_host.hpp) against a known answer:
 // STIXGeneral 'A' at font_size 64.  Built by __graft_entry__.build();
 // run on the GPU box by tests/test_gpu_parity.py::test_cpp_host_mirror.
+// usage: host_selftest <points.bin: i16 pairs> <cstart.bin: u32> place ; prints the plans fr_host::PlacedText makes of the
+//        glyph (two fr_glyph_place_ex placements: oblique, and half size on a fractional baseline): "pixels | describe |
+//        describe of the RGBA FR_TEXT_LOAD plan"
 // usage: host_selftest <points.bin: i16 pairs> <cstart.bin: u32> ; prints "w h hist(-2,-1,0,1) fnv1a(gray) winding@(420,321) fnv1a(GlyphDebug) fnv1a(atlas)"
 #include <cstdio>
 #include <cstdlib>
@@ -35,6 +38,15 @@ int main(int argc, char **argv)
             g.contours.push_back(ct);
         }
         fr_host::Context ctx(0);
+        if (argc > 3 && std::string(argv[3]) == "place") {
+            const std::vector<fr_glyph_place_ex> places = {{0, 64 * 4 + 21, 64 * 50 + 16, 0.0f, 0.2f}, {0, 64 * 50, 64 * 30 + 63, 0.032f, -1.0f}};
+            const std::vector<fr_text_run> runs = {{0, 2, 120, 60, 0, 0, 0.064f}};
+            fr_host::PlacedText cov(ctx, {g}, places, runs, 4, FR_FILL_CONSISTENT);
+            const std::vector<uint8_t> rgba = {225, 105, 180, 255, 0, 0, 0, 128};
+            fr_host::PlacedText over(ctx, {g}, places, runs, 2, FR_TEXT_LOAD | FR_TEXT_SRGB, &rgba);
+            printf("%llu | %s | %s\n", (unsigned long long)cov.pixels(), cov.describe().c_str(), over.describe().c_str());
+            return 0;
+        }
         auto gray = fr_host::renderGlyph(ctx, g, {1000}, 64);
         auto wd = fr_host::renderGlyphWinding(ctx, g, {1000}, 64);
         std::map<int, int> hist;

@@ -160,6 +160,7 @@ class Plan:
 
 
 PLACE_DTYPE = np.dtype([("glyph", "<u4"), ("pen_x64", "<i4"), ("pen_y", "<i4")])
+PLACE_EX_DTYPE = np.dtype([("glyph", "<u4"), ("pen_x64", "<i4"), ("pen_y64", "<i4"), ("scale", "<f4"), ("slant", "<f4")])
 RUN_DTYPE = np.dtype([("first", "<u4"), ("count", "<u4"), ("w", "<u4"), ("h", "<u4"), ("out_x", "<u4"), ("out_y", "<u4"),
                       ("scale", "<f4")])
 
@@ -167,6 +168,17 @@ RUN_DTYPE = np.dtype([("first", "<u4"), ("count", "<u4"), ("w", "<u4"), ("h", "<
 def make_places(rows: Sequence) -> np.ndarray:
     """rows of (glyph, pen_x64, pen_y) -> fr_glyph_place array"""
     return np.array([tuple(r) for r in rows], PLACE_DTYPE)
+
+
+def make_places_ex(rows: Sequence) -> np.ndarray:
+    """rows of (glyph, pen_x64, pen_y64, scale, slant) -> fr_glyph_place_ex array (scale 0: the run's; slant 0: upright)"""
+    return np.array([tuple(r) for r in rows], PLACE_EX_DTYPE)
+
+
+def _places(places) -> tuple:
+    """a placement array of either dtype -> (C-contiguous array, whether it is fr_glyph_place_ex)"""
+    ex = getattr(places, "dtype", None) == PLACE_EX_DTYPE
+    return np.ascontiguousarray(places, PLACE_EX_DTYPE if ex else PLACE_DTYPE), ex
 
 
 def make_runs(rows: Sequence) -> np.ndarray:
@@ -177,17 +189,17 @@ def make_runs(rows: Sequence) -> np.ndarray:
 class TextPlan(Plan):
     """fr_text_plan_create: glyph placements and the runs that composite them (include/fr_raster.h).  An ordinary
     fr_plan: render / render_timed / describe / stats / pixels / close as Plan.  mode: FR_COVERAGE_U8 (n in {1, 2, 4})
-    or FR_MASK_NONZERO (n = 1)."""
+    or FR_MASK_NONZERO (n = 1).  places of PLACE_EX_DTYPE (make_places_ex) go through fr_text_plan_create_ex."""
 
     def __init__(self, dgs: DeviceGlyphSet, places: np.ndarray, runs: np.ndarray, mode: int = L.FR_COVERAGE_U8,
                  samples_per_axis: int = 4, sample_phase: int = L.FR_SAMPLE_CENTER, flags: int = 0):
-        places = np.ascontiguousarray(places, PLACE_DTYPE)
+        places, ex = _places(places)
         runs = np.ascontiguousarray(runs, RUN_DTYPE)
         self.ctx, self.dgs, self.mode = dgs.ctx, dgs, mode
         self.params = L.RasterParams(mode, samples_per_axis, sample_phase, 0)
         h = C.c_void_p()
-        L.check(self.ctx._lib.fr_text_plan_create(self.ctx._h, dgs._h, L.ptr(places), len(places), L.ptr(runs), len(runs),
-                                                  C.byref(self.params), flags, C.byref(h)))
+        create = self.ctx._lib.fr_text_plan_create_ex if ex else self.ctx._lib.fr_text_plan_create
+        L.check(create(self.ctx._h, dgs._h, L.ptr(places), len(places), L.ptr(runs), len(runs), C.byref(self.params), flags, C.byref(h)))
         self._h = h
         self.n_places, self.n_runs = len(places), len(runs)
 
@@ -204,20 +216,21 @@ class TextPlanRGBA(Plan):
     """fr_text_plan_create_rgba: a text plan whose placements carry colours (n_places x 4 u8, R G B A) blended per sample
     in placement order over each run's clear colour (n_runs x 4 u8); renders RGBA pixels (4 bytes each, 4-byte aligned
     output; strides and rows count pixels).  FR_COVERAGE_U8 only, n in {1, 2, 4}.  With FR_TEXT_LOAD in `flags` the
-    samples start at the pixels already in the output instead, and run_clear_rgba may be None (it is ignored)."""
+    samples start at the pixels already in the output instead, and run_clear_rgba may be None (it is ignored).  places of
+    PLACE_EX_DTYPE (make_places_ex) go through fr_text_plan_create_rgba_ex."""
 
     def __init__(self, dgs: DeviceGlyphSet, places: np.ndarray, place_rgba, runs: np.ndarray, run_clear_rgba,
                  samples_per_axis: int = 4, sample_phase: int = L.FR_SAMPLE_CENTER, flags: int = 0):
-        places = np.ascontiguousarray(places, PLACE_DTYPE)
+        places, ex = _places(places)
         runs = np.ascontiguousarray(runs, RUN_DTYPE)
         pc = _colors(place_rgba, len(places), "place_rgba")
         rc = None if run_clear_rgba is None else _colors(run_clear_rgba, len(runs), "run_clear_rgba")     # (None: NULL)
         self.ctx, self.dgs, self.mode = dgs.ctx, dgs, L.FR_COVERAGE_U8
         self.params = L.RasterParams(L.FR_COVERAGE_U8, samples_per_axis, sample_phase, 0)
         h = C.c_void_p()
-        L.check(self.ctx._lib.fr_text_plan_create_rgba(self.ctx._h, dgs._h, L.ptr(places), L.ptr(pc), len(places),
-                                                       L.ptr(runs), None if rc is None else L.ptr(rc), len(runs), C.byref(self.params), flags,
-                                                       C.byref(h)))
+        create = self.ctx._lib.fr_text_plan_create_rgba_ex if ex else self.ctx._lib.fr_text_plan_create_rgba
+        L.check(create(self.ctx._h, dgs._h, L.ptr(places), L.ptr(pc), len(places), L.ptr(runs), None if rc is None else L.ptr(rc),
+                       len(runs), C.byref(self.params), flags, C.byref(h)))
         self._h = h
         self.n_places, self.n_runs = len(places), len(runs)
 

@@ -1,7 +1,9 @@
 """Text runs: a string laid out by the reference's pen walk (Appli.zig:318-349) and rendered as one anti-aliased image
 through a text plan (fr_text_plan_create, include/fr_raster.h), or as one RGBA image through an RGBA text plan
-(fr_text_plan_create_rgba), or drawn over an RGBA image the caller has (FR_TEXT_LOAD).  Nothing is computed in Python but
-the image size and the pen positions."""
+(fr_text_plan_create_rgba), or drawn over an RGBA image the caller has (FR_TEXT_LOAD).  A slant, a fractional baseline,
+spans of several sizes on one baseline (render_spans) and the reference's zoomed and dragged frame (render_text_view)
+go through the placement form of those plans (fr_glyph_place_ex).  Nothing is computed in Python but the image size
+and the pen positions."""
 from __future__ import annotations
 
 import math
@@ -12,7 +14,8 @@ import numpy as np
 from . import _lib as L
 from .font import Font
 from .image import RGBA, Gray
-from .render_glyph import Context, DeviceGlyphSet, TextPlan, TextPlanRGBA, default_context, make_places, make_runs
+from .render_glyph import (Context, DeviceGlyphSet, TextPlan, TextPlanRGBA, default_context, make_places, make_places_ex,
+                           make_runs)
 
 
 def instance_cell(box, scale: float, pen_x64: int, pen_y: int):
@@ -26,7 +29,46 @@ def instance_cell(box, scale: float, pen_x64: int, pen_y: int):
     return ix + mn_x, pen_y - mx_y, mx_x - mn_x + 1 + (fx64 != 0), mx_y - mn_y + 1
 
 
-def _line(font: Font, text, font_size: int):
+def instance_cell_ex(box, scale: float, slant: float, pen_x64: int, pen_y64: int):
+    """instance_cell for an fr_glyph_place_ex (include/fr_raster.h): the grid of the box sheared by `slant`, one column /
+    row wider when the pen's x / y has a fractional part (binary32, one rounding per operation)"""
+    f = np.float32
+    s, k = f(scale), f(slant)
+    x_min, y_min, x_max, y_max = (f(int(v)) for v in box)
+    lo = min(f(x_min + f(k * y_min)), f(x_min + f(k * y_max)))
+    hi = max(f(x_max + f(k * y_min)), f(x_max + f(k * y_max)))
+    mn_x, mx_x = math.floor(f(lo * s)), math.ceil(f(hi * s))
+    mn_y, mx_y = math.floor(f(y_min * s)), math.ceil(f(y_max * s))
+    return ((pen_x64 >> 6) + mn_x, (pen_y64 >> 6) - mx_y, mx_x - mn_x + 1 + ((pen_x64 & 63) != 0),
+            mx_y - mn_y + 1 + ((pen_y64 & 63) != 0))
+
+
+def _slant(slant) -> float:
+    k = float(slant)
+    if not math.isfinite(k) or abs(k) > 4.0:
+        raise ValueError(f"slant {slant!r}: expected a finite value in [-4, 4]")
+    return k
+
+
+def _fit(gs, rows):
+    """rows of (local glyph, pen_x64, pen_y64, scale, slant) around the pen origin (0, 0) -> one run whose image is the
+    union of the instance cells, as _line sizes it: (places, runs, width, height), or None when nothing is drawn.  The
+    pens move by whole pixels only."""
+    seg = gs.segments_per_glyph()
+    cells = [instance_cell_ex(gs.boxes[g], s, k, x, y) for g, x, y, s, k in rows if seg[g] > 0]
+    if not cells:
+        return None
+    left = min(c[0] for c in cells)
+    shift = -left if left < 0 else 0
+    top = min(c[1] for c in cells)
+    width = max(c[0] + c[2] for c in cells) + shift
+    height = max(c[1] + c[3] for c in cells) - top
+    places = make_places_ex([(g, x + 64 * shift, y - 64 * top, s, k) for g, x, y, s, k in rows])
+    runs = make_runs([(0, len(places), width, height, 0, 0, rows[0][3])])
+    return places, runs, width, height
+
+
+def _line(font: Font, text, font_size: int, slant: float = 0.0):
     """one line laid out as one run: (glyph set, places, runs, width, height), or None when nothing is drawn.  The image
     is the union of the instance cells: the pen origin at its left edge (moved right by whole pixels if a cell reaches
     left of it) and the baseline at row ceil(max y_max * scale)."""
@@ -35,6 +77,9 @@ def _line(font: Font, text, font_size: int):
     gs, kept = font.glyphset(distinct, skip_unsupported=False)
     local = {g: k for k, g in enumerate(kept)}
     scale = np.float32(font_size) / np.float32(font.information.units_per_em)
+    if slant != 0.0:                                       # oblique: the placement form, cells of the sheared boxes
+        fit = _fit(gs, [(local[int(g)], int(p), 0, scale, slant) for g, p in zip(gi, pen)])
+        return None if fit is None else (gs,) + fit
     cells = [instance_cell(gs.boxes[local[int(g)]], scale, int(p), 0) for g, p in zip(gi, pen)
              if gs.segments_per_glyph()[local[int(g)]] > 0]
     if not cells:
@@ -50,17 +95,23 @@ def _line(font: Font, text, font_size: int):
 
 
 def render_text(font: Font, text, font_size: int, *, samples_per_axis: int = 4, mode: int = L.FR_COVERAGE_U8,
-                phase: int = L.FR_SAMPLE_CENTER, flags: int = 0, ctx: Optional[Context] = None) -> Gray:
+                phase: int = L.FR_SAMPLE_CENTER, flags: int = 0, slant: float = 0.0, ctx: Optional[Context] = None) -> Gray:
     """One line of text as one image: every glyph at its sub-pixel pen, overlapping glyphs unioned per sample.
     The image is the union of the instance cells: the pen origin at its left edge (moved right by whole pixels if a cell
-    reaches left of it) and the baseline at row ceil(max y_max * scale)."""
-    import torch
-
-    ctx = ctx or default_context()
-    line = _line(font, text, font_size)
+    reaches left of it) and the baseline at row ceil(max y_max * scale).  slant: a point (x, y) of every outline is drawn
+    at (x + slant * y, y) (0.2: an oblique of about 11 degrees); the advances do not change."""
+    line = _line(font, text, font_size, _slant(slant))
     if line is None:
         return Gray.init(0, 0)
-    gs, places, runs, width, height = line
+    ctx = ctx or default_context()
+    return _render_gray(ctx, *line, mode, samples_per_axis, phase, flags)
+
+
+def _render_gray(ctx: Context, gs, places, runs, width: int, height: int, mode: int, samples_per_axis: int, phase: int,
+                 flags: int) -> Gray:
+    """one text plan of either placement form, rendered into a width x height image"""
+    import torch
+
     dgs = DeviceGlyphSet(ctx, gs)
     plan = TextPlan(dgs, places, runs, mode, samples_per_axis, phase, flags)
     try:
@@ -88,14 +139,13 @@ def _rgba(c) -> tuple:
 
 def render_text_rgba(font: Font, text, font_size: int, color=(225, 105, 180, 255), background=(0, 0, 0, 0), colors=None,
                      *, samples_per_axis: int = 4, phase: int = L.FR_SAMPLE_CENTER, flags: int = 0, srgb: bool = False,
-                     bgra: bool = False, ctx: Optional[Context] = None) -> RGBA:
+                     bgra: bool = False, slant: float = 0.0, ctx: Optional[Context] = None) -> RGBA:
     """One line of text as one RGBA image (fr_text_plan_create_rgba): every glyph blended per sample in order over
     `background`, in `color` or, if `colors` is given, in colors[k] for character k (e.g. to highlight a word).  The
     defaults are the reference's frame: pink text (shader.slang) on a transparent clear colour.  Sized as render_text.
     srgb: blend and resolve in linear light, as the reference's sRGB swapchain does (FR_TEXT_SRGB); bgra: the pixels'
-    bytes are B G R A (FR_TEXT_BGRA; the colours stay R G B A)."""
-    import torch
-
+    bytes are B G R A (FR_TEXT_BGRA; the colours stay R G B A); slant as render_text."""
+    slant = _slant(slant)
     ctx = ctx or default_context()
     flags |= (L.FR_TEXT_SRGB if srgb else 0) | (L.FR_TEXT_BGRA if bgra else 0)
     n_chars = len(text)
@@ -103,10 +153,17 @@ def render_text_rgba(font: Font, text, font_size: int, color=(225, 105, 180, 255
         raise ValueError(f"colors: {len(colors)} colours for {n_chars} characters")
     per_char = [_rgba(c) for c in colors] if colors is not None else [_rgba(color)] * n_chars
     clear = _rgba(background)
-    line = _line(font, text, font_size)
+    line = _line(font, text, font_size, slant)
     if line is None:
         return RGBA.init(0, 0)
-    gs, places, runs, width, height = line
+    return _render_rgba(ctx, *line, per_char, clear, samples_per_axis, phase, flags)
+
+
+def _render_rgba(ctx: Context, gs, places, runs, width: int, height: int, per_char, clear, samples_per_axis: int, phase: int,
+                 flags: int) -> RGBA:
+    """one RGBA text plan of either placement form, rendered into a width x height image"""
+    import torch
+
     dgs = DeviceGlyphSet(ctx, gs)
     plan = TextPlanRGBA(dgs, places, per_char, runs, [clear], samples_per_axis, phase, flags)
     try:
@@ -122,12 +179,13 @@ def render_text_rgba(font: Font, text, font_size: int, color=(225, 105, 180, 255
     return im
 
 
-def draw_text_rgba(image: RGBA, font: Font, text, font_size: int, x: float, y: int, color=(225, 105, 180, 255), colors=None,
+def draw_text_rgba(image: RGBA, font: Font, text, font_size: int, x: float, y: float, color=(225, 105, 180, 255), colors=None,
                    *, samples_per_axis: int = 4, phase: int = L.FR_SAMPLE_CENTER, flags: int = 0, srgb: bool = False,
-                   bgra: bool = False, ctx: Optional[Context] = None) -> RGBA:
+                   bgra: bool = False, slant: float = 0.0, ctx: Optional[Context] = None) -> RGBA:
     """One line of text drawn in place into `image` (FR_TEXT_LOAD): every sample starts at the pixel already there, and
     the glyphs are blended over it per sample in order, in `color` or colors[k] for character k.  x: the pen origin's
-    image x in pixels (fractional x is kept to 1/64 pixel: pen_x64 = floor(64 x + 1/2)); y: the baseline's row.  The
+    image x in pixels (fractional x is kept to 1/64 pixel: pen_x64 = floor(64 x + 1/2)); y: the baseline's image y, kept
+    to 1/64 pixel likewise (pen_y64 = floor(64 y + 1/2); an integral y is that row); slant as render_text.  The
     line is one run covering the whole image, so glyphs are clipped at its edges.  The whole image is copied to the
     device and back; on the device only the 64 x 16 tiles that some glyph cell meets are read (and, where needed,
     written), and every pixel no glyph sample reaches comes back with its bytes unchanged.  srgb / bgra as
@@ -141,6 +199,9 @@ def draw_text_rgba(image: RGBA, font: Font, text, font_size: int, x: float, y: i
     if not isinstance(data, np.ndarray) or data.dtype != np.uint8 or data.shape != (h * w, 4):
         raise ValueError(f"image.data: expected a ({h * w}, 4) uint8 array for {w} x {h} pixels, got "
                          f"{getattr(data, 'shape', None)} {getattr(data, 'dtype', type(data).__name__)}")
+    slant = _slant(slant)
+    if not math.isfinite(float(y)):
+        raise ValueError(f"y {y!r}: expected a finite value")
     ctx = ctx or default_context()
     flags |= L.FR_TEXT_LOAD | (L.FR_TEXT_SRGB if srgb else 0) | (L.FR_TEXT_BGRA if bgra else 0)
     n_chars = len(text)
@@ -154,7 +215,11 @@ def draw_text_rgba(image: RGBA, font: Font, text, font_size: int, x: float, y: i
     local = {g: k for k, g in enumerate(kept)}
     scale = np.float32(font_size) / np.float32(font.information.units_per_em)
     x64 = math.floor(64.0 * float(x) + 0.5)
-    places = make_places([(local[int(g)], x64 + int(p), int(y)) for g, p in zip(gi, pen)])
+    y64 = math.floor(64.0 * float(y) + 0.5)
+    if slant == 0.0 and y64 % 64 == 0:
+        places = make_places([(local[int(g)], x64 + int(p), y64 // 64) for g, p in zip(gi, pen)])
+    else:
+        places = make_places_ex([(local[int(g)], x64 + int(p), y64, 0.0, slant) for g, p in zip(gi, pen)])
     runs = make_runs([(0, len(places), image.width, image.height, 0, 0, scale)])
     dgs = DeviceGlyphSet(ctx, gs)
     try:
@@ -170,3 +235,113 @@ def draw_text_rgba(image: RGBA, font: Font, text, font_size: int, x: float, y: i
     finally:
         dgs.close()
     return image
+
+
+def span_line(font: Font, spans):
+    """Spans (text, font_size, slant, rise, colour) laid out as one line on a common baseline by chaining fr_text_layout:
+    each span starts at the previous span's end pen (1/64 pixel where the size changes); rise: pixels above the baseline, kept to 1/64
+    pixel (pen_y64 = baseline - floor(64 rise + 1/2)); every placement carries its span's scale f32(font_size) /
+    f32(units_per_em) and slant.  -> (glyph set, fr_glyph_place_ex places, runs, width, height, per-character colours),
+    or None when nothing is drawn.  One run; the image is the union of the instance cells, as for render_text."""
+    spans = [tuple(sp) for sp in spans]
+    upm = np.float32(font.information.units_per_em)
+    for sp in spans:
+        if len(sp) != 5:
+            raise ValueError(f"span {sp!r}: expected (text, font_size, slant, rise, colour)")
+        _, size, slant, rise, colour = sp
+        if not isinstance(size, (int, np.integer)) or not 1 <= size <= 65535:
+            raise ValueError(f"span font_size {size!r}: expected an integer in [1, 65535]")
+        if not math.isfinite(float(rise)):
+            raise ValueError(f"span rise {rise!r}: expected a finite value")
+        _slant(slant), _rgba(colour)
+    # consecutive spans of one size are one fr_text_layout call (the pen walks on unrounded, as inside one string, so
+    # spans of a single size give exactly that string's pens); where the size changes the next call starts at the end pen
+    laid, start, k = [], 0, 0
+    while k < len(spans):
+        m = k
+        while m < len(spans) and spans[m][1] == spans[k][1]:
+            m += 1
+        texts = [[ord(c) for c in sp[0]] if isinstance(sp[0], str) else [int(c) for c in sp[0]] for sp in spans[k:m]]
+        gi, pen, end = font.layout([c for t in texts for c in t], int(spans[k][1]))
+        at = 0
+        for t, (_, size, slant, rise, colour) in zip(texts, spans[k:m]):
+            laid.append((gi[at:at + len(t)], pen[at:at + len(t)] + start, np.float32(size) / upm, _slant(slant),
+                         -math.floor(64.0 * float(rise) + 0.5), _rgba(colour)))
+            at += len(t)
+        start += end
+        k = m
+    distinct = sorted({int(g) for gi, *_ in laid for g in gi})
+    if not distinct:
+        return None
+    gs, kept = font.glyphset(distinct, skip_unsupported=False)
+    local = {g: k for k, g in enumerate(kept)}
+    rows = [(local[int(g)], int(p), y64, s, k) for gi, pen, s, k, y64, _ in laid for g, p in zip(gi, pen)]
+    colours = [c for gi, _, _, _, _, c in laid for _ in gi]
+    fit = _fit(gs, rows)
+    return None if fit is None else (gs,) + fit + (colours,)
+
+
+def render_spans(font: Font, spans, *, samples_per_axis: int = 4, mode: int = L.FR_COVERAGE_U8, phase: int = L.FR_SAMPLE_CENTER,
+                 flags: int = 0, ctx: Optional[Context] = None) -> Gray:
+    """One line made of spans (text, font_size, slant, rise, colour) — a heading word, a superscript, an oblique word
+    inside an upright line — as one image from one run (span_line; the colours are not used here)."""
+    line = span_line(font, spans)
+    if line is None:
+        return Gray.init(0, 0)
+    ctx = ctx or default_context()
+    return _render_gray(ctx, *line[:5], mode, samples_per_axis, phase, flags)
+
+
+def render_spans_rgba(font: Font, spans, background=(0, 0, 0, 0), *, samples_per_axis: int = 4, phase: int = L.FR_SAMPLE_CENTER,
+                      flags: int = 0, srgb: bool = False, bgra: bool = False, ctx: Optional[Context] = None) -> RGBA:
+    """render_spans as one RGBA image: every span's glyphs in its colour, blended per sample in order over `background`
+    (srgb / bgra as render_text_rgba)."""
+    flags |= (L.FR_TEXT_SRGB if srgb else 0) | (L.FR_TEXT_BGRA if bgra else 0)
+    clear = _rgba(background)
+    line = span_line(font, spans)
+    if line is None:
+        return RGBA.init(0, 0)
+    ctx = ctx or default_context()
+    return _render_rgba(ctx, *line[:5], line[5], clear, samples_per_axis, phase, flags)
+
+
+def view_line(font: Font, text, font_size: int, zoom: float, offset_x: float, offset_y: float, width: int, height: int,
+              slant: float = 0.0):
+    """The reference's frame (Appli.zig zoom / drag; shader.slang: position * transform.scale + transform.offset): the
+    line laid out at `font_size`, then every position multiplied by `zoom` and moved by the offset, in pixels.  Glyph k's
+    origin is at x = offset_x + zoom * pen_k and the baseline at y = offset_y, both kept to 1/64 pixel (floor(64 v +
+    1/2)); the scale is f32(f32(font_size) * f32(zoom)) / f32(units_per_em).  -> (glyph set, fr_glyph_place_ex places,
+    runs): one run of width x height pixels that clips the line, or None for an empty text or image."""
+    zoom = float(zoom)
+    if not (math.isfinite(zoom) and zoom > 0.0):
+        raise ValueError(f"zoom {zoom!r}: expected a finite value > 0")
+    if not (math.isfinite(float(offset_x)) and math.isfinite(float(offset_y))):
+        raise ValueError("offset_x / offset_y: expected finite values")
+    if not (isinstance(width, (int, np.integer)) and isinstance(height, (int, np.integer)) and 0 <= width <= 65535
+            and 0 <= height <= 65535):
+        raise ValueError(f"width {width!r} and height {height!r} must be integers in [0, 65535]")
+    slant = _slant(slant)
+    gi, pen, _ = font.layout(text, font_size)
+    if len(gi) == 0 or width == 0 or height == 0:
+        return None
+    gs, kept = font.glyphset(sorted(set(int(g) for g in gi)), skip_unsupported=False)
+    local = {g: k for k, g in enumerate(kept)}
+    scale = np.float32(np.float32(font_size) * np.float32(zoom)) / np.float32(font.information.units_per_em)
+    y64 = math.floor(64.0 * float(offset_y) + 0.5)
+    places = make_places_ex([(local[int(g)], math.floor(64.0 * float(offset_x) + zoom * int(p) + 0.5), y64, 0.0, slant)
+                             for g, p in zip(gi, pen)])
+    runs = make_runs([(0, len(places), int(width), int(height), 0, 0, scale)])
+    return gs, places, runs
+
+
+def render_text_view(font: Font, text, font_size: int, zoom: float, offset_x: float, offset_y: float, width: int, height: int,
+                     *, slant: float = 0.0, samples_per_axis: int = 4, mode: int = L.FR_COVERAGE_U8,
+                     phase: int = L.FR_SAMPLE_CENTER, flags: int = 0, ctx: Optional[Context] = None) -> Gray:
+    """One frame of the reference's view: `text` at font_size * zoom with its origin at the fractional pixel position
+    (offset_x, offset_y), clipped to a width x height image (view_line).  A slow zoom or drag moves the line by 1/64
+    pixel in both axes."""
+    line = view_line(font, text, font_size, zoom, offset_x, offset_y, width, height, slant)
+    if line is None:
+        return Gray.init(int(width), int(height))
+    ctx = ctx or default_context()
+    return _render_gray(ctx, *line, int(width), int(height), mode, samples_per_axis, phase, flags)

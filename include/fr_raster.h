@@ -192,7 +192,7 @@ int fr_plan_describe(const fr_plan *plan, char *buf, size_t cap);
  * advance_width (Appli.zig:318-349), every instance into one MSAA framebuffer, a sample lit if ANY instance covers it.
  * A text plan renders sets of such instances ("runs"), each into one finished image.
  *   Placement {glyph, pen_x64, pen_y}: pen_x64 is the image x of the glyph's font-unit origin in 1/64 pixel (26.6 fixed
- *     point); pen_y is the baseline's image row (whole rows: baselines are not sub-pixel).  Image coordinates are the
+ *     point); pen_y is the baseline's image row (whole rows; fr_glyph_place_ex, below, keeps the baseline to 1/64 pixel).  Image coordinates are the
  *     run's own: (0, 0) is its top-left pixel.
  *   Run {first, count, w, h, out_x, out_y, scale}: placements places[first .. first+count); it owns the whole w x h
  *     rectangle at (out_x, out_y) of the output and writes every pixel of it (0 where no glyph reaches).  Runs must not
@@ -309,6 +309,53 @@ as it was for fr_text_plan_create_rgba before these flags existed:
 int fr_text_plan_create_rgba(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place *places, const uint8_t *place_rgba,
                              uint32_t n_places, const fr_text_run *runs, const uint8_t *run_clear_rgba, uint32_t n_runs,
                              const fr_raster_params *params, uint32_t flags, fr_plan **out);
+
+/* ---- text placements with their own size, slant and sub-pixel baseline (BUILD-DEFINED) ---------
+ * fr_text_plan_create / fr_text_plan_create_rgba with a wider placement: the reference shows text under a view
+ * transform with a float offset in both axes (Appli.zig zoom / drag; shader.slang: position * transform.scale +
+ * transform.offset), so a line's baseline is not on a pixel row in general.  Runs, modes, n, phases, flags
+ * (FR_FILL_CONSISTENT; for the RGBA form FR_TEXT_SRGB, FR_TEXT_BGRA, FR_TEXT_LOAD), colours, blending, resolve, clipping
+ * to the run, "every pixel of the run is written" and the error codes are those of the two entry points above.  Only
+ * the instance geometry differs.  All arithmetic below is binary32, one rounding per written operation, no fused
+ * multiply-add.
+ *   For a placement let s = scale != 0 ? scale : run.scale, k = slant, ix = floor(pen_x64 / 64), fx = (pen_x64 mod 64)
+ *   / 64, iy = floor(pen_y64 / 64), fy = (pen_y64 mod 64) / 64 (floor and non-negative mod), and the glyph's box
+ *   (x_min, y_min, x_max, y_max) as floats.
+ *   Cell: lo = min(x_min + k*y_min, x_min + k*y_max), hi = max(x_max + k*y_min, x_max + k*y_max);
+ *     min_x = floor(lo * s), max_x = ceil(hi * s), min_y = floor(y_min * s), max_y = ceil(y_max * s).  The cell is
+ *     (max_x - min_x + 1 + (fx != 0)) columns by (max_y - min_y + 1 + (fy != 0)) rows; its column 0 is image column
+ *     ix + min_x, its row 0 image row iy - max_y.  It is clipped to the run.  Outside its cell an instance contributes
+ *     nothing (the cell is part of the definition: the reference's winding is not zero everywhere outside an outline).
+ *   Sample (i, j) of image pixel (X, Y) inside the cell, off(q) = (q + phase) / n:
+ *       cy = (f32(iy - Y) + (fy - off(j))) / s
+ *       t  = (f32(X - ix) + (off(i) - fx)) / s
+ *       cx = t - k * cy
+ *     (fy - off(j) and off(i) - fx are exact: multiples of 1/64 in (-1, 1)).  The winding at (cx, cy) is the reference's
+ *     (or FR_FILL_CONSISTENT's) for the glyph's own integer points, per instance: a point (x, y) of the outline is drawn
+ *     at (x + k*y, y), the outlines themselves are not sheared.
+ *   Validation: scale is 0 or finite, positive and inside the limits of a run's scale (2^-20 .. 2^20: FR_E_UNSUPPORTED
+ *     outside; NaN, infinite or negative: FR_E_INVALID); slant is finite (else FR_E_INVALID) and |slant| <= 4 (76
+ *     degrees; FR_E_UNSUPPORTED beyond); the pen and cell limits of fr_text_plan_create apply to iy and the sheared cell.
+ *   So: (1) with pen_y64 = 64 * pen_y, scale 0 (or the run's) and slant 0, cell and samples are those of fr_glyph_place
+ *   bit for bit; (2) adding 64 to every pen_y64 of a run moves its image down by exactly one row.
+ * fr_plan_describe names text_place_kernel<n, fill>, or text_place_rgba_kernel / text_place_srgb_kernel /
+ * text_place_rgba_load_kernel / text_place_srgb_load_kernel<n, fill, blend>, with the instance count.  Rotation is not
+ * offered: it makes the ray height differ per lane.                                             */
+typedef struct fr_glyph_place_ex {
+    uint32_t glyph;     /* index into the glyph set                                                  */
+    int32_t  pen_x64;   /* image x of the glyph's font-unit origin, 1/64 pixel (as fr_glyph_place)   */
+    int32_t  pen_y64;   /* image y of the baseline, 1/64 pixel, downwards: 64 * pen_y is row pen_y   */
+    float    scale;     /* this placement's font_size / units_per_em; 0: the run's scale             */
+    float    slant;     /* k: a point (x, y) of the outline is drawn at (x + k*y, y); 0: upright     */
+} fr_glyph_place_ex;
+
+int fr_text_plan_create_ex(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place_ex *places, uint32_t n_places,
+                           const fr_text_run *runs, uint32_t n_runs, const fr_raster_params *params, uint32_t flags,
+                           fr_plan **out);
+int fr_text_plan_create_rgba_ex(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place_ex *places,
+                                const uint8_t *place_rgba, uint32_t n_places, const fr_text_run *runs,
+                                const uint8_t *run_clear_rgba, uint32_t n_runs, const fr_raster_params *params,
+                                uint32_t flags, fr_plan **out);
 
 /* One-shot: plan + render + copy back.  out_host: HOST buffer (caller-allocated,
  * e.g. Image.Gray.data / Image.Winding.data from the Zig allocator).  Synchronous.  */

@@ -20,7 +20,16 @@ the noise in a buffer of its own (the copy is outside the timed region); the cle
 buffer, after the same copy.  "tiles_load_computed" is the tile count recomputed here from the clipped cells, not observed: the launched
 grid is what a rocprofv3 --kernel-trace run shows (e.g. of --load --lines 1).
 
-    python tools/bench_text.py [--lines 4096] [--chars 64] [--steps 20] [--warmup 3] [--rgba] [--srgb] [--load]"""
+--place prices the placement form (fr_text_plan_create_ex / _rgba_ex: own scale, slant and sub-pixel baseline per
+placement), printed as its own JSON lines ("case": "place"), one per font and size, for the coverage plan and the RGBA plan
+with opaque and with translucent colours: (a) the plan of the old entry point, (b) the _ex plan with degenerate
+parameters — the same pixels and records through the wider instance record —, (c) the _ex plan with slant 0.2 and a
+random baseline fraction per placement.  The three are timed alternately in the same process, --repeats times over;
+each figure is the median over the repeats of the median of --steps renders, with the smallest and largest repeat of
+(a) beside it: a difference of (b) from (a) inside that spread is not a difference.  (b) must render (a)'s bytes (checked).
+
+    python tools/bench_text.py [--lines 4096] [--chars 64] [--steps 20] [--warmup 3] [--rgba] [--srgb] [--load]
+                               [--place [--repeats 5] [--place-only]]"""
 import argparse
 import json
 import os
@@ -103,10 +112,18 @@ def main():
     ap.add_argument("--srgb", action="store_true", help="also render the lines as sRGB (linear-light) RGBA text plans")
     ap.add_argument("--load", action="store_true", help="also draw the lines over a noise background (FR_TEXT_LOAD), each "
                     "render from a fresh copy of it, and a sparse overlay on a 3840 x 2160 noise frame")
+    ap.add_argument("--place", action="store_true", help="also price the placement form (fr_glyph_place_ex) against the old "
+                    "entry points, alternating in the same run")
+    ap.add_argument("--repeats", type=int, default=5, help="--place: repeats of each alternated timing (at least 5)")
+    ap.add_argument("--place-only", action="store_true", help="--place without the other configurations")
     args = ap.parse_args()
+    if args.place and args.repeats < 5:
+        ap.error("--repeats: at least 5")
     import torch
     ctx = fr.Context(0)
-    for fi, name in enumerate(["DejaVuSans.ttf", "DejaVuSerif-Italic.ttf"]):
+    if args.place:
+        place(ctx, args)
+    for fi, name in enumerate([] if args.place and args.place_only else ["DejaVuSans.ttf", "DejaVuSerif-Italic.ttf"]):
         font = load_font(name, allow_hinted=True)        # (DejaVuSans carries hinting instructions)
         for size in (16, 32):
             gs, places, runs, shape, jobs, jshape, lines = workload(font, args.lines, args.chars, size, seed=100 * fi + size)
@@ -174,6 +191,53 @@ def main():
     if args.load:
         overlay(ctx, args)
     ctx.close()
+
+
+def place(ctx, args):
+    """--place: (a) old plan, (b) _ex degenerate, (c) _ex slanted with random baseline fractions; coverage, RGBA opaque
+    and RGBA translucent; alternated, --repeats times"""
+    import torch
+    med = lambda v: sorted(v)[len(v) // 2]
+    for fi, name in enumerate(["DejaVuSans.ttf", "DejaVuSerif-Italic.ttf"]):
+        font = load_font(name, allow_hinted=True)
+        for size in (16, 32):
+            gs, places, runs, shape, _, _, lines = workload(font, args.lines, args.chars, size, seed=100 * fi + size)
+            rng = np.random.default_rng(size)
+            degenerate = rg.make_places_ex([(int(p["glyph"]), int(p["pen_x64"]), 64 * int(p["pen_y"]), 0.0, 0.0) for p in places])
+            slanted = degenerate.copy()
+            slanted["pen_y64"] += rng.integers(0, 64, len(slanted)).astype(np.int32)
+            slanted["slant"] = 0.2
+            words = [(225, 105, 180, 255), (40, 200, 90, 255)]
+            cols = np.array([words[s[:k].count(" ") % 2] for s in lines for k in range(len(s))], np.uint8)
+            clears = np.zeros((len(runs), 4), np.uint8)
+            dgs = fr.DeviceGlyphSet(ctx, gs)
+            out = {"case": "place", "font": name, "font_size": size, "lines": args.lines, "chars": args.chars, "samples": 16,
+                   "instances": int(len(places)), "steps": args.steps, "repeats": args.repeats}
+            for kind in ("text", "rgba_opaque", "rgba_translucent"):
+                c = cols.copy()
+                if kind == "rgba_translucent":
+                    c[:int(runs[0]["count"]), 3] = 160
+                make = ((lambda pl: fr.TextPlan(dgs, pl, runs, fr.FR_COVERAGE_U8, 4, fr.FR_SAMPLE_CENTER)) if kind == "text" else
+                        (lambda pl: fr.TextPlanRGBA(dgs, pl, c, runs, clears, 4, fr.FR_SAMPLE_CENTER, 0)))
+                plans = {"a": make(places), "b": make(degenerate), "c": make(slanted)}
+                bufs = {k: torch.zeros(shape + (() if kind == "text" else (4,)), dtype=torch.uint8, device="cuda:0") for k in plans}
+                torch.cuda.synchronize()
+                ms = {k: [] for k in plans}
+                for _ in range(args.repeats):
+                    for k, plan in plans.items():
+                        ms[k].append(timed(plan, bufs[k], shape, args.steps, args.warmup))
+                if not torch.equal(bufs["a"], bufs["b"]):
+                    raise SystemExit(f"--place: {name} {size} {kind}: the degenerate _ex plan differs from the old plan")
+                a, b, cc = med(ms["a"]), med(ms["b"]), med(ms["c"])
+                out.update({f"{kind}_a_ms": round(a, 4), f"{kind}_a_min_ms": round(min(ms["a"]), 4), f"{kind}_a_max_ms": round(max(ms["a"]), 4),
+                            f"{kind}_b_ms": round(b, 4), f"{kind}_c_ms": round(cc, 4), f"{kind}_b_over_a": round(b / a, 3),
+                            f"{kind}_c_over_b": round(cc / b, 3), f"{kind}_a_plan": plans["a"].describe(),
+                            f"{kind}_b_plan": plans["b"].describe()})
+                for plan in plans.values():
+                    plan.close()
+                del bufs
+            dgs.close()
+            print(json.dumps(out), flush=True)
 
 
 def tiles_met(places, run, gs, scale):
