@@ -149,7 +149,7 @@ struct fr_plan {
     fr::TextTile *d_tiles = nullptr;
     fr::TextRun *d_runs = nullptr;
     fr::TextInst *d_insts = nullptr;
-    bool place_ex = false;             // fr_text_plan_create_ex / _rgba_ex: d_insts_ex and the kernels of fr_text_place.hip
+    bool place_ex = false;             // fr_text_plan_create_ex / _rgba_ex: d_insts_ex and the text_place_* kernels of fr_text.hip
     fr::TextInstEx *d_insts_ex = nullptr;
     uint32_t *d_tlist = nullptr, *d_tglyphs = nullptr, *d_trec_count = nullptr;
     fr::Rec *d_trecs = nullptr;
@@ -157,6 +157,24 @@ struct fr_plan {
 };
 
 template <class T> static void dfree(T *&p) { if (p) { (void)hipFree(p); p = nullptr; } }
+
+// launches the text kernel of a plan over n_tiles tiles for one placement form (ARGS: fr::TextArgs over the plan's TextInst
+// table, or fr::TextPlaceArgs over its TextInstEx table); n_tiles = 0: only names it, as rocprofv3 does, into name[name_cap]
+template <class ARGS>
+static hipError_t text_args_launch(const fr_plan *plan, void *out_dev, size_t out_stride, uint32_t n_tiles, char *name = nullptr,
+                                   size_t name_cap = 0)
+{
+    ARGS a;
+    a.tiles = plan->d_tiles; a.runs = plan->d_runs; a.list = plan->d_tlist;
+    if constexpr (std::is_same_v<ARGS, fr::TextPlaceArgs>) a.insts = plan->d_insts_ex;
+    else a.insts = plan->d_insts;
+    a.recs = plan->d_trecs; a.rec_count = plan->d_trec_count;
+    a.out = static_cast<uint8_t *>(out_dev);
+    a.out_stride = out_stride;
+    a.phase_center = plan->params.sample_phase == FR_SAMPLE_CENTER ? 1 : 0;
+    return fr::launch_text(a, plan->params.samples_per_axis, (plan->flags & FR_FILL_CONSISTENT) ? 1 : 0, plan->rgba, plan->blend,
+                           plan->srgb, plan->load, n_tiles, plan->ctx->stream, name, name_cap);
+}
 
 extern "C" {
 
@@ -741,7 +759,7 @@ int fr_glyphset_set_boxes(fr_glyphset *gs, const int16_t *boxes)
 // FR_TEXT_LOAD, and the plan renders with text_rgba_kernel (text_srgb_kernel under FR_TEXT_SRGB; their _load_ forms
 // under FR_TEXT_LOAD, which ignores run_clear_rgba and launches only the tiles some instance meets).
 // The placements are places (fr_glyph_place) or, when that is NULL and ex is set, places_ex (fr_glyph_place_ex: own
-// scale, slant, sub-pixel baseline; TextInstEx and the kernels of fr_text_place.hip): only the cell differs.
+// scale, slant, sub-pixel baseline; TextInstEx and the text_place_* kernels of fr_text.hip): only the cell differs.
 static int text_plan_build(const char *fn, fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place *places,
                            const fr_glyph_place_ex *places_ex, bool ex, const uint8_t *place_rgba, uint32_t n_places, const fr_text_run *runs,
                            const uint8_t *run_clear_rgba, uint32_t n_runs, const fr_raster_params *params, uint32_t flags,
@@ -948,7 +966,7 @@ int fr_text_plan_create_rgba(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_
                            n_runs, params, flags, true, out);
 }
 
-// the same two for fr_glyph_place_ex placements: own scale, slant and sub-pixel baseline per placement (fr_text_place.hip)
+// the same two for fr_glyph_place_ex placements: own scale, slant and sub-pixel baseline per placement (the text_place_* kernels)
 int fr_text_plan_create_ex(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place_ex *places, uint32_t n_places,
                            const fr_text_run *runs, uint32_t n_runs, const fr_raster_params *params, uint32_t flags,
                            fr_plan **out)
@@ -1016,18 +1034,8 @@ int fr_plan_describe(const fr_plan *plan, char *buf, size_t cap)
     if (plan->text) {
         if (plan->n_tglyphs) add(fill ? "fr::prepare_fill_kernel" : "fr::prepare_kernel", plan->n_tglyphs);
         name[0] = 0;
-        if (plan->place_ex)
-            (void)fr::launch_text_place(fr::TextPlaceArgs{}, plan->params.samples_per_axis, fill, plan->rgba, plan->blend, plan->srgb,
-                                        plan->load, 0u, nullptr, name, sizeof name);
-        else if (plan->load)
-            (void)fr::launch_text_load(fr::TextArgs{}, plan->params.samples_per_axis, fill, plan->blend, plan->srgb, 0u, nullptr, name,
-                                       sizeof name);
-        else if (plan->srgb)
-            (void)fr::launch_text_srgb(fr::TextArgs{}, plan->params.samples_per_axis, fill, plan->blend, 0u, nullptr, name, sizeof name);
-        else if (plan->rgba)
-            (void)fr::launch_text_rgba(fr::TextArgs{}, plan->params.samples_per_axis, fill, plan->blend, 0u, nullptr, name, sizeof name);
-        else
-            (void)fr::launch_text(fr::TextArgs{}, plan->params.samples_per_axis, fill, 0u, nullptr, name, sizeof name);
+        if (plan->place_ex) (void)text_args_launch<fr::TextPlaceArgs>(plan, nullptr, 0, 0u, name, sizeof name);
+        else (void)text_args_launch<fr::TextArgs>(plan, nullptr, 0, 0u, name, sizeof name);
         if (plan->n_tiles) add(name, plan->n_insts);
         return FR_OK;
     }
@@ -1089,27 +1097,8 @@ static int text_launch(fr_plan *plan, void *out_dev, size_t out_stride)
                            plan->d_trecs, plan->d_trec_count, st, fill);
         HIP_TRY(hipGetLastError());
     }
-    if (plan->place_ex) {
-        fr::TextPlaceArgs a;
-        a.tiles = plan->d_tiles; a.runs = plan->d_runs; a.insts = plan->d_insts_ex; a.list = plan->d_tlist;
-        a.recs = plan->d_trecs; a.rec_count = plan->d_trec_count;
-        a.out = static_cast<uint8_t *>(out_dev);
-        a.out_stride = out_stride;
-        a.phase_center = plan->params.sample_phase == FR_SAMPLE_CENTER ? 1 : 0;
-        HIP_TRY(fr::launch_text_place(a, plan->params.samples_per_axis, fill, plan->rgba, plan->blend, plan->srgb, plan->load,
-                                      plan->n_tiles, st));
-        return FR_OK;
-    }
-    fr::TextArgs a;
-    a.tiles = plan->d_tiles; a.runs = plan->d_runs; a.insts = plan->d_insts; a.list = plan->d_tlist;
-    a.recs = plan->d_trecs; a.rec_count = plan->d_trec_count;
-    a.out = static_cast<uint8_t *>(out_dev);
-    a.out_stride = out_stride;
-    a.phase_center = plan->params.sample_phase == FR_SAMPLE_CENTER ? 1 : 0;
-    if (plan->load) HIP_TRY(fr::launch_text_load(a, plan->params.samples_per_axis, fill, plan->blend, plan->srgb, plan->n_tiles, st));
-    else if (plan->srgb) HIP_TRY(fr::launch_text_srgb(a, plan->params.samples_per_axis, fill, plan->blend, plan->n_tiles, st));
-    else if (plan->rgba) HIP_TRY(fr::launch_text_rgba(a, plan->params.samples_per_axis, fill, plan->blend, plan->n_tiles, st));
-    else HIP_TRY(fr::launch_text(a, plan->params.samples_per_axis, fill, plan->n_tiles, st));
+    if (plan->place_ex) HIP_TRY(text_args_launch<fr::TextPlaceArgs>(plan, out_dev, out_stride, plan->n_tiles));
+    else HIP_TRY(text_args_launch<fr::TextArgs>(plan, out_dev, out_stride, plan->n_tiles));
     return FR_OK;
 }
 

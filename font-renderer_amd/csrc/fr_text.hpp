@@ -1,5 +1,4 @@
-// fr_text.hpp — the tables of a text plan (fr_api.hip builds them, text_kernel / text_rgba_kernel / text_srgb_kernel and
-// their FR_TEXT_LOAD forms in fr_text.hip read them)
+// fr_text.hpp — the tables of a text plan (fr_api.hip builds them, the text kernels of fr_text.hip read them)
 #pragma once
 #include "fr_device.hpp"
 
@@ -41,50 +40,32 @@ struct TextTile {      // one 64 x 16 tile of a run and its instance list list[l
     uint32_t run, x0, y0, lbeg, lend;
     uint32_t pad[3];
 };
-struct TextArgs {
+template <class INST>
+struct TextTables {        // what a text kernel reads, for either placement form
     const TextTile *tiles;
     const TextRun *runs;
-    const TextInst *insts;
+    const INST *insts;
     const uint32_t *list;
     const Rec *recs;
     const uint32_t *rec_count;
-    uint8_t *out;          // bytes, or the RGBA pixels (4-byte aligned) of text_rgba_kernel
+    uint8_t *out;          // bytes, or the RGBA pixels (4-byte aligned) of the colour kernels
     uint64_t out_stride;   // elements
     int32_t phase_center;
 };
-struct TextPlaceArgs {     // TextArgs for the placement kernels (fr_text_place.hip): the instances are TextInstEx
-    const TextTile *tiles;
-    const TextRun *runs;
-    const TextInstEx *insts;
-    const uint32_t *list;
-    const Rec *recs;
-    const uint32_t *rec_count;
-    uint8_t *out;
-    uint64_t out_stride;
-    int32_t phase_center;
-};
+struct TextArgs : TextTables<TextInst> {};         // fr_glyph_place placements: the text_*_kernel instances
+struct TextPlaceArgs : TextTables<TextInstEx> {};  // fr_glyph_place_ex placements: the text_place_*_kernel instances
 static_assert(sizeof(TextInstEx) == 64, "text tables");
 static_assert(sizeof(TextInst) == 48 && sizeof(TextRun) == 32 && sizeof(TextTile) == 32, "text tables");
 
 constexpr int TEXT_TILE_W = 64, TEXT_TILE_H = 16, TEXT_WAVES = 4;
 
-// n in {1, 2, 4}; n_tiles = 0: only name the instance (as rocprofv3 names it) into name[name_cap]
-hipError_t launch_text(const TextArgs &a, int n, int fill, uint32_t n_tiles, hipStream_t stream, char *name = nullptr, size_t name_cap = 0);
-// the same for RGBA text plans: blend = 0 when every placement colour of the plan is opaque (A = 255), else 1
-hipError_t launch_text_rgba(const TextArgs &a, int n, int fill, int blend, uint32_t n_tiles, hipStream_t stream,
-                            char *name = nullptr, size_t name_cap = 0);
-// the same for FR_TEXT_SRGB plans (text_srgb_kernel): blending and resolve in linear light
-hipError_t launch_text_srgb(const TextArgs &a, int n, int fill, int blend, uint32_t n_tiles, hipStream_t stream,
-                            char *name = nullptr, size_t name_cap = 0);
-// the same for FR_TEXT_LOAD plans (text_rgba_load_kernel, or text_srgb_load_kernel when srgb): the samples start at the
-// output's pixels; n_tiles counts only the tiles with a non-empty instance list
-hipError_t launch_text_load(const TextArgs &a, int n, int fill, int blend, int srgb, uint32_t n_tiles, hipStream_t stream,
-                            char *name = nullptr, size_t name_cap = 0);
-
-// the same five families for plans of fr_glyph_place_ex placements (fr_text_place.hip: text_place_kernel,
-// text_place_rgba_kernel, text_place_srgb_kernel, text_place_rgba_load_kernel, text_place_srgb_load_kernel).
-// rgba = 0: coverage / mask (blend, srgb and load are then 0)
-hipError_t launch_text_place(const TextPlaceArgs &a, int n, int fill, int rgba, int blend, int srgb, int load, uint32_t n_tiles,
-                             hipStream_t stream, char *name = nullptr, size_t name_cap = 0);
+// Launches the instance of a plan: n in {1, 2, 4}; rgba = 0: coverage / mask bytes (text_kernel; blend, srgb and load are
+// then ignored); else blend = 0 when every placement colour of the plan is opaque (A = 255), srgb for FR_TEXT_SRGB plans
+// (blending and resolve in linear light), load for FR_TEXT_LOAD plans (the samples start at the output's pixels; n_tiles
+// then counts only the tiles with a non-empty instance list).  n_tiles = 0: only name the instance (as rocprofv3 names
+// it) into name[name_cap].  ARGS: TextArgs or TextPlaceArgs.
+template <class ARGS>
+hipError_t launch_text(const ARGS &a, int n, int fill, int rgba, int blend, int srgb, int load, uint32_t n_tiles, hipStream_t stream,
+                       char *name = nullptr, size_t name_cap = 0);
 
 }  // namespace fr

@@ -1,5 +1,5 @@
 """Text-run benchmark: 4 096 lines of 64 printable ASCII characters, one run per line, one plan,
-4 x 4 samples, for DejaVuSans and DejaVuSerif-Italic at font sizes 16 and 32.  Reports per configuration the ms per render
+4 x 4 samples (--samples), for DejaVuSans and DejaVuSerif-Italic at font sizes 16 and 32.  Reports per configuration the ms per render
 of the text plan and its Mpixel/s of run area, and the same instances as separate cells (renderGlyph's grid, whole-pixel
 origins, disjoint) in a plain plan, which prices the composition.  Under rocprofv3 --kernel-trace --stats the kernel
 shares come from the trace (prepare_kernel vs text_kernel).  Prints one JSON line per configuration.
@@ -28,7 +28,11 @@ random baseline fraction per placement.  The three are timed alternately in the 
 each figure is the median over the repeats of the median of --steps renders, with the smallest and largest repeat of
 (a) beside it: a difference of (b) from (a) inside that spread is not a difference.  (b) must render (a)'s bytes (checked).
 
-    python tools/bench_text.py [--lines 4096] [--chars 64] [--steps 20] [--warmup 3] [--rgba] [--srgb] [--load]
+--samples {1,2,4} (default 4) and --fill (FR_FILL_CONSISTENT) go to every plan, so the kernel instances named below as
+<4, 0, ...> become <samples, fill, ...>.  All text kernels, those of the placement form included, live in csrc/fr_text.hip.
+
+    python tools/bench_text.py [--lines 4096] [--chars 64] [--steps 20] [--warmup 3] [--samples 4] [--fill]
+                               [--rgba] [--srgb] [--load]
                                [--place [--repeats 5] [--place-only]]"""
 import argparse
 import json
@@ -112,6 +116,8 @@ def main():
     ap.add_argument("--srgb", action="store_true", help="also render the lines as sRGB (linear-light) RGBA text plans")
     ap.add_argument("--load", action="store_true", help="also draw the lines over a noise background (FR_TEXT_LOAD), each "
                     "render from a fresh copy of it, and a sparse overlay on a 3840 x 2160 noise frame")
+    ap.add_argument("--samples", type=int, choices=(1, 2, 4), default=4, help="samples per axis of every plan")
+    ap.add_argument("--fill", action="store_true", help="build every plan with FR_FILL_CONSISTENT")
     ap.add_argument("--place", action="store_true", help="also price the placement form (fr_glyph_place_ex) against the old "
                     "entry points, alternating in the same run")
     ap.add_argument("--repeats", type=int, default=5, help="--place: repeats of each alternated timing (at least 5)")
@@ -120,6 +126,7 @@ def main():
     if args.place and args.repeats < 5:
         ap.error("--repeats: at least 5")
     import torch
+    ns, fill = args.samples, fr.FR_FILL_CONSISTENT if args.fill else 0
     ctx = fr.Context(0)
     if args.place:
         place(ctx, args)
@@ -128,7 +135,7 @@ def main():
         for size in (16, 32):
             gs, places, runs, shape, jobs, jshape, lines = workload(font, args.lines, args.chars, size, seed=100 * fi + size)
             dgs = fr.DeviceGlyphSet(ctx, gs)
-            plan = fr.TextPlan(dgs, places, runs, fr.FR_COVERAGE_U8, 4, fr.FR_SAMPLE_CENTER)
+            plan = fr.TextPlan(dgs, places, runs, fr.FR_COVERAGE_U8, ns, fr.FR_SAMPLE_CENTER, fill)
             buf = torch.empty(shape, dtype=torch.uint8, device="cuda:0")
             torch.cuda.synchronize()
             ms = timed(plan, buf, shape, args.steps, args.warmup)
@@ -151,7 +158,7 @@ def main():
                     if translucent:
                         c[:int(runs[0]["count"]), 3] = 160
                     for kind, flags in kinds:
-                        rplan = fr.TextPlanRGBA(dgs, places, c, runs, clears, 4, fr.FR_SAMPLE_CENTER, flags)
+                        rplan = fr.TextPlanRGBA(dgs, places, c, runs, clears, ns, fr.FR_SAMPLE_CENTER, flags | fill)
                         torch.cuda.synchronize()
                         # (with --load the clear-colour plans too render after a copy of the noise: the same cache state)
                         rms = (timed_over(rplan, rbuf, noise, shape, args.steps, args.warmup) if args.load
@@ -161,7 +168,7 @@ def main():
                         rgba[f"{kind}_{key}_plan"] = rplan.describe()
                         rplan.close()
                         if args.load:
-                            lplan = fr.TextPlanRGBA(dgs, places, c, runs, None, 4, fr.FR_SAMPLE_CENTER, flags | fr.FR_TEXT_LOAD)
+                            lplan = fr.TextPlanRGBA(dgs, places, c, runs, None, ns, fr.FR_SAMPLE_CENTER, flags | fr.FR_TEXT_LOAD | fill)
                             torch.cuda.synchronize()
                             lms = timed_over(lplan, lbuf, noise, shape, args.steps, args.warmup)
                             rgba[f"{kind}_load_{key}_ms"] = round(lms, 4)
@@ -173,7 +180,7 @@ def main():
                 del rbuf
                 if args.load:
                     del noise, lbuf
-            cells = fr.Plan(dgs, jobs, fr.FR_COVERAGE_U8, 4, fr.FR_SAMPLE_CENTER)
+            cells = fr.Plan(dgs, jobs, fr.FR_COVERAGE_U8, ns, fr.FR_SAMPLE_CENTER, fill)
             jbuf = torch.empty(jshape, dtype=torch.uint8, device="cuda:0")
             torch.cuda.synchronize()
             ms_cells = timed(cells, jbuf, jshape, args.steps, args.warmup)
@@ -182,7 +189,7 @@ def main():
             del jbuf
             dgs.close()
             print(json.dumps({
-                "font": name, "font_size": size, "lines": args.lines, "chars": args.chars, "samples": 16,
+                "font": name, "font_size": size, "lines": args.lines, "chars": args.chars, "samples": ns * ns,
                 "instances": int(len(places)), "run_mpixel": round(px / 1e6, 3), "text_ms": round(ms, 4),
                 "text_mpixel_per_s": round(px / 1e6 / (ms / 1e3), 1), "text_plan": desc,
                 "cells_mpixel": round(cpx / 1e6, 3), "cells_ms": round(ms_cells, 4),
@@ -197,6 +204,7 @@ def place(ctx, args):
     """--place: (a) old plan, (b) _ex degenerate, (c) _ex slanted with random baseline fractions; coverage, RGBA opaque
     and RGBA translucent; alternated, --repeats times"""
     import torch
+    ns, fill = args.samples, fr.FR_FILL_CONSISTENT if args.fill else 0
     med = lambda v: sorted(v)[len(v) // 2]
     for fi, name in enumerate(["DejaVuSans.ttf", "DejaVuSerif-Italic.ttf"]):
         font = load_font(name, allow_hinted=True)
@@ -211,14 +219,14 @@ def place(ctx, args):
             cols = np.array([words[s[:k].count(" ") % 2] for s in lines for k in range(len(s))], np.uint8)
             clears = np.zeros((len(runs), 4), np.uint8)
             dgs = fr.DeviceGlyphSet(ctx, gs)
-            out = {"case": "place", "font": name, "font_size": size, "lines": args.lines, "chars": args.chars, "samples": 16,
+            out = {"case": "place", "font": name, "font_size": size, "lines": args.lines, "chars": args.chars, "samples": ns * ns,
                    "instances": int(len(places)), "steps": args.steps, "repeats": args.repeats}
             for kind in ("text", "rgba_opaque", "rgba_translucent"):
                 c = cols.copy()
                 if kind == "rgba_translucent":
                     c[:int(runs[0]["count"]), 3] = 160
-                make = ((lambda pl: fr.TextPlan(dgs, pl, runs, fr.FR_COVERAGE_U8, 4, fr.FR_SAMPLE_CENTER)) if kind == "text" else
-                        (lambda pl: fr.TextPlanRGBA(dgs, pl, c, runs, clears, 4, fr.FR_SAMPLE_CENTER, 0)))
+                make = ((lambda pl: fr.TextPlan(dgs, pl, runs, fr.FR_COVERAGE_U8, ns, fr.FR_SAMPLE_CENTER, fill)) if kind == "text" else
+                        (lambda pl: fr.TextPlanRGBA(dgs, pl, c, runs, clears, ns, fr.FR_SAMPLE_CENTER, fill)))
                 plans = {"a": make(places), "b": make(degenerate), "c": make(slanted)}
                 bufs = {k: torch.zeros(shape + (() if kind == "text" else (4,)), dtype=torch.uint8, device="cuda:0") for k in plans}
                 torch.cuda.synchronize()
@@ -256,6 +264,7 @@ def tiles_met(places, run, gs, scale):
 def overlay(ctx, args):
     """(b): 16 lines of 64 characters, size 32, on a 3840 x 2160 frame: one LOAD run over the frame vs one clear-colour run"""
     import torch
+    ns, fill = args.samples, fr.FR_FILL_CONSISTENT if args.fill else 0
     W, H, size, n_lines, n_chars = 3840, 2160, 32, 16, 64
     font = load_font("DejaVuSans.ttf", allow_hinted=True)
     rng = np.random.default_rng(7)
@@ -278,8 +287,8 @@ def overlay(ctx, args):
         cols[:, 3] = alpha
         for kind, flags in (("rgba", 0), ("srgb", fr.FR_TEXT_SRGB)):
             for load in (False, True):
-                plan = fr.TextPlanRGBA(dgs, places, cols, runs, None if load else [(0, 0, 0, 0)], 4, fr.FR_SAMPLE_CENTER,
-                                       flags | (fr.FR_TEXT_LOAD if load else 0))
+                plan = fr.TextPlanRGBA(dgs, places, cols, runs, None if load else [(0, 0, 0, 0)], ns, fr.FR_SAMPLE_CENTER,
+                                       flags | (fr.FR_TEXT_LOAD if load else 0) | fill)
                 torch.cuda.synchronize()
                 tag = f"{kind}{'_load' if load else ''}_{key}"
                 ms = timed_over(plan, lbuf if load else cbuf, noise, (H, W), args.steps, args.warmup)
