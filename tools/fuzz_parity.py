@@ -17,6 +17,7 @@ cases = int(sys.argv[2]) if len(sys.argv) > 2 else 150
 rng = np.random.default_rng(seed)
 orc, asc, ctx = O.Oracle(), fixtures.load_ascii(), fr.Context(0)
 bad = 0
+reached = set()          # the kernel instances the plans launched, as fr_plan_describe names them
 for case in range(cases):
     kind = rng.random()
     if kind < 0.4:
@@ -57,7 +58,11 @@ for case in range(cases):
     dt = np.int16 if mode == 0 else np.uint8
     got, ref = np.full(shape, 9, dt), np.full(shape, 9, dt)
     dgs = fr.DeviceGlyphSet(ctx, gs)
-    rg.render_batch(dgs, jobs, mode, got, n, fr.FR_SAMPLE_CENTER if center else fr.FR_SAMPLE_CORNER)
+    phase = fr.FR_SAMPLE_CENTER if center else fr.FR_SAMPLE_CORNER
+    plan = fr.Plan(dgs, jobs, mode, n, phase)
+    reached.update(part.rsplit(" x", 1)[0] for part in plan.describe().split("; ") if part)
+    plan.close()
+    rg.render_batch(dgs, jobs, mode, got, n, phase)
     dgs.close()
     orc.render_batch(gs, jobs, mode, ref, n, center, 16)
     if not np.array_equal(got, ref):
@@ -65,4 +70,5 @@ for case in range(cases):
         d = np.argwhere(got != ref)
         print(f"MISMATCH case {case}: mode {mode} n {n} center {center} glyphs {len(gs)} first diff at {d[0].tolist()} ({len(d)} px)")
 print(f"fuzz seed {seed}: {cases} cases, {bad} mismatches")
+print(f"fuzz seed {seed}: {len(reached)} distinct kernel instances reached")
 sys.exit(1 if bad else 0)
