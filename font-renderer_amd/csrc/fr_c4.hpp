@@ -105,6 +105,20 @@ __device__ __forceinline__ Rec40 c4_make_rec40(const Rec &r, uint32_t ra, uint32
     return m;
 }
 
+// The strip's exact sample abscissae cx(j) = (f32(min_x + x) + off(i)) / scale (:26) into s_cxp[1 + j], thread `tid` of STEP.
+// Two loops, chosen once by the workgroup-uniform `sdiv.pow2` — written as one loop the compiler computes the quotient
+// both ways for every entry and selects.
+template <int N, uint32_t NCOL, uint32_t STEP>
+__device__ __forceinline__ void c4_fill_cx(float *s_cxp, uint32_t tid, int32_t min_xs, int phase, const ScaleDiv &sdiv)
+{
+    auto num = [&](uint32_t j) { return (float)(min_xs + (int32_t)(j / (uint32_t)N)) + sub_off((int)(j % (uint32_t)N), N, phase); };
+    if (sdiv.pow2) {
+        for (uint32_t j = tid; j < NCOL; j += STEP) s_cxp[1u + j] = num(j) * sdiv.inv;
+    } else {
+        for (uint32_t j = tid; j < NCOL; j += STEP) s_cxp[1u + j] = num(j) / sdiv.scale;
+    }
+}
+
 // Set-up for glyphs of <= 32 segments (<= 64 candidate roots: one per lane of ONE wave — ASCII-like glyphs), four
 // waves.  Settling a candidate's row range costs four evaluations of the reference's acceptance at the rows around
 // the two guessed ends; with the plain set-up wave 0 would do all of it while waves 1 - 3 (and the SIMDs they sit
@@ -117,8 +131,9 @@ __device__ __forceinline__ uint32_t c4_setup_small(const RenderArgs &A, const Jo
 {
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t Hs = job.h * (uint32_t)N;
+    const ScaleDiv sdiv = scale_div(job.scale);         // (a multiply when scale is a power of two: fr_device.hpp)
     RowGeom geo;
-    geo.max_y = job.max_y; geo.scale = job.scale; geo.rows = Hs; geo.n = N; geo.phase = phase; geo.cyt = cyt;
+    geo.max_y = job.max_y; geo.set_scale(sdiv); geo.rows = Hs; geo.n = N; geo.phase = phase; geo.cyt = cyt;
     const bool have = lane < 2u * nseg;
     Rec r;
     RowGuess g;
@@ -135,8 +150,7 @@ __device__ __forceinline__ uint32_t c4_setup_small(const RenderArgs &A, const Jo
     s_tmp[tid] = cls;
     // exact sample abscissae of this strip: cx(j) = (f32(min_x + x) + off(i)) / scale   (:26)
     const int32_t min_xs = job.min_x + (int32_t)x0s;
-    for (uint32_t j = tid; j < NCOL; j += 256u)
-        s_cxp[1u + j] = ((float)(min_xs + (int32_t)(j / (uint32_t)N)) + sub_off((int)(j % (uint32_t)N), N, phase)) / job.scale;
+    c4_fill_cx<N, NCOL, 256u>(s_cxp, tid, min_xs, phase, sdiv);
     if (tid == 2) s_cxp[0] = -__builtin_inff();
     if (tid == 3) s_cxp[1u + NCOL] = __builtin_inff();
     __syncthreads();
@@ -180,8 +194,9 @@ __device__ __forceinline__ uint32_t c4_setup_mid(const RenderArgs &A, const Job 
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t c = tid & 127u, h = tid >> 7;
     const uint32_t Hs = job.h * (uint32_t)N;
+    const ScaleDiv sdiv = scale_div(job.scale);
     RowGeom geo;
-    geo.max_y = job.max_y; geo.scale = job.scale; geo.rows = Hs; geo.n = N; geo.phase = phase; geo.cyt = cyt;
+    geo.max_y = job.max_y; geo.set_scale(sdiv); geo.rows = Hs; geo.n = N; geo.phase = phase; geo.cyt = cyt;
     const bool have = c < 2u * nseg;
     Rec r;
     RowGuess g;
@@ -198,8 +213,7 @@ __device__ __forceinline__ uint32_t c4_setup_mid(const RenderArgs &A, const Job 
     }
     s_tmp[tid] = cls0 | (cls1 << 8);
     const int32_t min_xs = job.min_x + (int32_t)x0s;
-    for (uint32_t j = tid; j < NCOL; j += 256u)
-        s_cxp[1u + j] = ((float)(min_xs + (int32_t)(j / (uint32_t)N)) + sub_off((int)(j % (uint32_t)N), N, phase)) / job.scale;
+    c4_fill_cx<N, NCOL, 256u>(s_cxp, tid, min_xs, phase, sdiv);
     if (tid == 2) s_cxp[0] = -__builtin_inff();
     if (tid == 3) s_cxp[1u + NCOL] = __builtin_inff();
     __syncthreads();
@@ -246,6 +260,7 @@ __device__ __forceinline__ uint32_t c4_setup(const RenderArgs &A, const Job &job
         return c4_setup_mid<RCAP, N, NCOL, FILL>(A, job, seg0, nseg, x0s, phase, s_cxp, s_rec, s_wcnt, s_tmp, cyt);
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t Hs = job.h * (uint32_t)N;
+    const ScaleDiv sdiv = scale_div(job.scale);
     // candidates per thread: <= 768 segments where 1024 records are kept, <= 384 where 512, else <= 256
     constexpr uint32_t CPT = (RCAP >= 1024u ? 1536u : (RCAP >= 512u ? 768u : 512u)) / (64u * NW);
     s_wcnt = s_tmp;                                                          // (2 CPT NW counters: the scratch block has the room)
@@ -261,7 +276,7 @@ __device__ __forceinline__ uint32_t c4_setup(const RenderArgs &A, const Job &job
         if (c < 2u * nseg) {
             Rec r;
             RowGeom geo;
-            geo.max_y = job.max_y; geo.scale = job.scale; geo.rows = Hs; geo.n = N; geo.phase = phase; geo.cyt = cyt;
+            geo.max_y = job.max_y; geo.set_scale(sdiv); geo.rows = Hs; geo.n = N; geo.phase = phase; geo.cyt = cyt;
             build_record_rows<FILL>(A.seg_pts + 6u * (size_t)(seg0 + (c >> 1)), c & 1u, geo, r);
             const uint32_t ra = __builtin_bit_cast(uint32_t, r.lo), re = __builtin_bit_cast(uint32_t, r.hi);
             live = ra < re;
@@ -276,8 +291,7 @@ __device__ __forceinline__ uint32_t c4_setup(const RenderArgs &A, const Job &job
     }
     // exact sample abscissae of this strip: cx(j) = (f32(min_x + x) + off(i)) / scale   (:26)
     const int32_t min_xs = job.min_x + (int32_t)x0s;
-    for (uint32_t j = tid; j < NCOL; j += 64u * NW)
-        s_cxp[1u + j] = ((float)(min_xs + (int32_t)(j / (uint32_t)N)) + sub_off((int)(j % (uint32_t)N), N, phase)) / job.scale;
+    c4_fill_cx<N, NCOL, 64u * NW>(s_cxp, tid, min_xs, phase, sdiv);
     if (tid == 2) s_cxp[0] = -__builtin_inff();
     if (tid == 3) s_cxp[1u + NCOL] = __builtin_inff();
     __syncthreads();

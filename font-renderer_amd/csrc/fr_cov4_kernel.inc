@@ -43,6 +43,7 @@
     if (tid == 0u) *s_next_band = band_first + NW;
     const uint32_t rec_cnt = c4_setup<NW, RCAP, NS, NCOL, FILL>(A, job, seg0, nseg, x0s, phase, s_cxp, s_rec, s_wcnt, reinterpret_cast<uint32_t *>(smem + L::OFF_WAVES));
     const int32_t min_xs = job.min_x + (int32_t)x0s;
+    const ScaleDiv sdiv = scale_div(job.scale);     // (workgroup-uniform: the bands' ray heights multiply when scale is a power of two)
     const float jscale = job.scale * (float)NS;
     const float joff = (float)min_xs * (float)NS + (phase ? 0.5f : 0.0f) - 1.0f;
     const float ncolf = (float)NCOL;
@@ -66,6 +67,17 @@
     uint32_t *s_cnt = reinterpret_cast<uint32_t *>(wregion + L::OFF_CNT);
     int16_t *s_roff = reinterpret_cast<int16_t *>(wregion + L::OFF_ROFF);
     unsigned char *s_E = wregion;
+    // The pair walk forms its LDS addresses from pre-scaled indices (below): base + index, one add each.  Where the register
+    // budget allows the wave region's offset is kept in a VGPR — an opaque copy — so that the add is a VOP2 of two VGPRs,
+    // the fast class of DESIGN.md section 4.0; with the base in an SGPR the same add is a normal-class instruction.  Not in
+    // the six-workgroup instances (held to 80 VGPRs) nor in the 512-record ones, which fill their 168 registers as it is:
+    // the copy took their scratch from 8 to 16 bytes per lane.
+    constexpr bool VBASE = c4_occ(CAP, WLOG, RPL) <= 4 && RPL != 8;
+    uint32_t wreg = L::OFF_WAVES + wave * L::WAVE;
+    if constexpr (VBASE) asm volatile("" : "+v"(wreg));
+    const uint32_t lane4 = lane << 2;
+    const uint32_t mk0 = 2u * (per * lane + 1u);       // the marker of my first record: 2 (k + 1)
+    static_assert(LSTRIDE % 2u == 0u && C4_PCAP % 64 == 0, "row lists are whole dwords; chunks are whole trips");
 
     C4_ABL_SETUP_ONLY();
     // (no workgroup barrier below: waves are independent.)  Every wave starts on band `wave` of the group and then takes
@@ -84,7 +96,7 @@
         const uint32_t y0 = band * PRB;
         const uint32_t row_b0 = band * 64u;
         // ray height of sample row `lane` of the band: cy = (f32(max_y - y) - off(jj)) / scale  (:27)
-        const float cy = ((float)(job.max_y - (int32_t)(y0 + (lane >> LN))) - sub_off((int)(lane & (uint32_t)(NS - 1)), NS, phase)) / job.scale;
+        const float cy = sdiv((float)(job.max_y - (int32_t)(y0 + (lane >> LN))) - sub_off((int)(lane & (uint32_t)(NS - 1)), NS, phase));
         uint16_t *mylist = s_lists + lane * LSTRIDE;
         auto init_lists = [&]() {
             const uint4 ones = make_uint4(0xfffdfffdu, 0xfffdfffdu, 0xfffdfffdu, 0xfffdfffdu);
@@ -119,7 +131,8 @@
                     uint32_t off = off0, ro[RPL];
 #pragma unroll
                     for (int i = 0; i < RPL; ++i) {
-                        ro[i] = (r0[i] - row_b0 - off) & 0xffffu;
+                        // (a pair's row is only ever used mod 64: kept as the byte offset of the row's dword, 4 (row & 63))
+                        ro[i] = ((r0[i] - row_b0 - off) & 63u) << 2;
                         off += c[i];
                     }
                     // my records' row offsets sit side by side: one store
@@ -142,14 +155,15 @@
                 const uint32_t npairs = tot;
                 uint32_t carry = 0u;               // record index (+ 1) of the last pair walked so far
               for (uint32_t base = 0; base < npairs; base += (uint32_t)C4_PCAP) {
-                // markers: slot `off - base` of the chunk holds k + 1 where record k's run starts, 0 elsewhere
+                // markers: slot `off - base` of the chunk holds 2 (k + 1) where record k's run starts, 0 elsewhere
+                // (monotone in k like k + 1, and at once the byte offset of the record's row offset — and half its record's)
                 if (C4_PCAP >= 512 || lane < C4_PCAP / 8) reinterpret_cast<uint4 *>(s_pairs)[lane] = make_uint4(0, 0, 0, 0);
                 wave_lds_sync();
                 {
                     uint32_t off = off0 - base;    // (wraps below the chunk: an unsigned compare takes both ends)
 #pragma unroll
                     for (int i = 0; i < RPL; ++i) {
-                        if (c[i] && off < (uint32_t)C4_PCAP) s_pairs[off] = (uint16_t)(per * lane + (uint32_t)i + 1u);
+                        if (c[i] && off < (uint32_t)C4_PCAP) s_pairs[off] = (uint16_t)(mk0 + 2u * (uint32_t)i);
                         off += c[i];
                     }
                 }
@@ -159,24 +173,34 @@
                 // current 64 are evaluated (an independent chain that fills the evaluation's wait states)
                 uint32_t k_cur = max(wave_incl_max((uint32_t)s_pairs[lane]), carry);
                 carry = (uint32_t)__builtin_amdgcn_readlane((int)k_cur, 63);
+                // (the byte offset of my marker of the next trip is a vector register advanced by a literal, not rebuilt
+                // from the scalar trip counter every trip)
+                uint32_t pn2 = 2u * lane + 128u;
                 for (uint32_t p0 = 0; p0 < nhere && C4_ABL_KEEP(3); p0 += 64u) {
-                    const uint32_t pn = min(p0 + 64u + lane, (uint32_t)C4_PCAP - 1u);
-                    const uint32_t s_next = wave_incl_max((uint32_t)s_pairs[pn]);
+                    const uint32_t s_next = wave_incl_max((uint32_t)*reinterpret_cast<const uint16_t *>(smem + (wreg + min(pn2, 2u * (uint32_t)C4_PCAP - 2u)) + L::OFF_PAIRS));
+                    pn2 += 128u;
                     {
-                        const uint32_t p = base + p0 + lane, k1 = k_cur;
-                        const bool livep = p < npairs;
+                        const uint32_t k2 = k_cur;                              // 2 (record index + 1)
+                        // pair base + p0 + lane of npairs (p0 < nhere: the scalar side does not wrap)
+                        const bool livep = lane < npairs - base - p0;
                         // (a lane past the end decodes the last record and a row that may lie outside the band:
                         // it computes like the others and is kept from the table walk and the append)
 #if C4_ABL_NODECODE
-                        const uint32_t row = (p + (k1 & 1u)) & 63u;                                 // timing-only: no dependent decode loads
-                        const uint32_t raddr = L::CX + ((lane & 3u) + (A.n_jobs == 0xffffffffu ? k1 : 0u)) * (uint32_t)sizeof(Rec40);
+                        const uint32_t row4 = (lane4 + ((k2 & 2u) << 1)) & 252u;                    // timing-only: no dependent decode loads
+                        const uint32_t raddr = L::CX + ((lane & 3u) + (A.n_jobs == 0xffffffffu ? (k2 >> 1) : 0u)) * (uint32_t)sizeof(Rec40);
 #else
-                        const uint32_t row = (uint32_t)((int32_t)p + (int32_t)s_roff[k1 - 1u]);
+                        // row = pair index + the record's row offset, mod 64 — and the pair index is my lane mod 64 (chunks and
+                        // trips are multiples of 64): 4 row is the byte offset of s_cy[row] and s_cnt[row]
+                        const uint32_t roff4 = *reinterpret_cast<const uint16_t *>(smem + (wreg + k2) + (L::OFF_ROFF - 2u));
+                        const uint32_t row4 = (lane4 + roff4) & 252u;
                         // (one 24-bit multiply-add for the record's LDS address, small offsets for its five 8-byte reads)
-                        const uint32_t raddr = __umul24(k1, (uint32_t)sizeof(Rec40)) + (L::CX - (uint32_t)sizeof(Rec40));
+                        const uint32_t raddr = __umul24(k2, (uint32_t)sizeof(Rec40) / 2u) + (L::CX - (uint32_t)sizeof(Rec40));
 #endif
-                        const Rec40 r = *reinterpret_cast<const Rec40 *>(smem + raddr);
-                        const float cyr = s_cy[row & 63u];
+                        // (k2 is even, so the address is a multiple of 8 like every record's: said to the compiler, which
+                        // otherwise reads the record in 4-byte pieces)
+                        const Rec40 r = *reinterpret_cast<const Rec40 *>(__builtin_assume_aligned(smem + raddr, 8));
+                        const uint32_t rowa = wreg + row4;
+                        const float cyr = *reinterpret_cast<const float *>(smem + rowa + L::OFF_CY);
                         // KIND 1 = all quadratic, 2 = all linear (no delta, no square root), 0 = mixed (both + a select).
                         // Only KIND 0 is built: single-kind trips saved 87 vector instructions per wave on C3 but ran 2 % slower
                         // (58 more branches); the body keeps its KIND-generic shape, which fixes its code generation.
@@ -221,8 +245,8 @@
                             bool keep = livep & (J > 0);
                             if constexpr (SPLIT) keep = livep & ((uint32_t)(J - 1) - jlo < jspan);
                             if (keep) {
-                                const uint32_t pos = atomicAdd(&s_cnt[row & 63u], 1u);
-                                uint16_t *rowlist = s_lists + __umul24(row & 63u, LSTRIDE);
+                                const uint32_t pos = atomicAdd(reinterpret_cast<uint32_t *>(smem + rowa + L::OFF_CNT), 1u);
+                                uint16_t *rowlist = reinterpret_cast<uint16_t *>(smem + (wreg + __umul24(row4, LSTRIDE / 2u)));
                                 rowlist[min(pos, (uint32_t)CAP)] = (uint16_t)(((uint32_t)J << 2) | code);   // (slot CAP: the dump)
                             }
                         };

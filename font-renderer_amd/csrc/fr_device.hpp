@@ -64,6 +64,45 @@ __device__ __forceinline__ float sqrt_rn(float x)
     r = (rp > 0.0f) ? sp : r;
     return r;
 }
+// The cheaper candidate for sqrt_rn: one Newton step from v_sqrt_f32 with h ~ 1 / (2 s), four or five instructions instead
+// of nine.  h is only accurate to 1 ulp, so the result is NOT taken on trust either: fr_selftest_sqrt_fast runs it against
+// __builtin_sqrtf over the same range as fr_selftest_sqrt, and the kernels use it only if that count is zero (DESIGN.md §10
+// has the outcome).  VARIANT 0: h = rcp(s) / 2, 1: h = rsq(x) / 2.  (h is capped so that x = 0 gives 0 * finite, not 0 * inf.)
+template <int VARIANT>
+__device__ __forceinline__ float sqrt_fast(float x)
+{
+    const float s = __builtin_amdgcn_sqrtf(x);
+    const float g = VARIANT == 0 ? __builtin_amdgcn_rcpf(s) : __builtin_amdgcn_rsqf(x);
+    const float h = __builtin_fminf(0.5f * g, 1.0e+30f);
+    const float r = __builtin_fmaf(-s, s, x);
+    return __builtin_fmaf(r, h, s);
+}
+// x / scale for a job's `scale`, which is the same for a whole workgroup.  When scale = +-2^k the quotient is x with its
+// exponent moved by k: x * 2^-k is that very binary32, bit for bit, as long as neither 2^-k nor the product leaves the
+// normal range.  Taken only for 2^-20 <= |scale| <= 2^20 — the range fr_plan_create accepts (fr_api.hip) — and the
+// dividends are 0 or sample coordinates, multiples of 1/8 with 1/8 <= |x| <= 2^22 + 1 (fr_plan_create bounds the cell), so
+// the product lies in [2^-23, 2^43): normal.  Zero keeps the sign the division gives it (sign x XOR sign scale).  The
+// decision is made from the bits of `scale` with scalar instructions (mantissa field 0, exponent field in 107 .. 147); the
+// multiply replaces the ~11 vector instructions of a correctly rounded divide.  Every other scale takes the IEEE division.
+struct ScaleDiv {
+    float scale = 1.0f, inv = 1.0f;
+    bool pow2 = false;
+    __device__ __forceinline__ float operator()(float x) const
+    {
+        if (pow2) return x * inv;
+        return x / scale;
+    }
+};
+__device__ __forceinline__ ScaleDiv scale_div(float scale)
+{
+    ScaleDiv d;
+    const uint32_t b = (uint32_t)__builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, scale));
+    const uint32_t e = (b >> 23) & 0xffu;
+    d.scale = scale;
+    d.pow2 = (b & 0x007fffffu) == 0u && e - 107u <= 40u;
+    d.inv = __builtin_bit_cast(float, (b & 0x80000000u) | ((254u - e) << 23));      // 2^-k, sign kept (used only if pow2)
+    return d;
+}
 enum : uint32_t {
     REC_LINEAR = 0x80000000u,   // a == 0 branch (the sign bit: one signed compare tests it)
     REC_NEG_ROOT = 2u,   // t- = (B - sqrt(delta)) / a ; otherwise t+

@@ -162,10 +162,15 @@ struct RowGeom {
     uint32_t rows;       // sample rows of the cell (h * N)
     int n, phase;
     const float *cyt = nullptr;   // optional: the ray heights of all the cell's rows, computed once by this very expression
+    float inv = 1.0f;             // scale = +-2^k inside the proven range (ScaleDiv, fr_device.hpp): 1 / scale, and the
+    bool pow2 = false;            // division below is this multiply — the same bits.  Left unset: always the division.
+    __device__ __forceinline__ void set_scale(const ScaleDiv &d) { scale = d.scale; inv = d.inv; pow2 = d.pow2; }
     __device__ __forceinline__ float cy(uint32_t r) const
     {
         if (cyt) return cyt[r];
-        return ((float)(max_y - (int32_t)(r / (uint32_t)n)) - sub_off((int)(r % (uint32_t)n), n, phase)) / scale;
+        const float num = (float)(max_y - (int32_t)(r / (uint32_t)n)) - sub_off((int)(r % (uint32_t)n), n, phase);
+        if (pow2) return num * inv;
+        return num / scale;
     }
     // fractional row index at which the ray height equals c (rows r >= x lie at or below c)
     __device__ __forceinline__ float row_of(float c) const

@@ -58,7 +58,57 @@ __global__ __launch_bounds__(256) void selftest_sqrt_kernel(uint32_t e_lo, unsig
     }
 }
 
+// the same sweep for the candidate sqrt_fast<VARIANT> (fr_device.hpp); thread 0 of block 0 also takes the two special
+// arguments: 0 must give 0 and a negative number a NaN, as sqrt_rn does
+template <int VARIANT>
+__global__ __launch_bounds__(256) void selftest_sqrt_fast_kernel(uint32_t e_lo, unsigned long long *mismatches, uint32_t *first_bad)
+{
+    const uint32_t e = e_lo + blockIdx.x / 32u, part = blockIdx.x % 32u;
+    uint32_t bad = 0, bad_x = 0;
+    for (uint32_t m = part * 256u + threadIdx.x; m < (1u << 23); m += 32u * 256u) {
+        const uint32_t bits = (e << 23) | m;
+        const float x = __uint_as_float(bits);
+        if (__float_as_uint(sqrt_fast<VARIANT>(x)) != __float_as_uint(__builtin_sqrtf(x))) { ++bad; bad_x = bits; }
+    }
+    if (blockIdx.x == 0u && threadIdx.x == 0u) {
+        // (opaque: the compiler must not fold the candidate at these two arguments)
+        float z = 0.0f, n = -2.0f;
+        asm volatile("" : "+v"(z), "+v"(n));
+        if (__float_as_uint(sqrt_fast<VARIANT>(z)) != 0u) { ++bad; bad_x = 0u; }
+        const float sn = sqrt_fast<VARIANT>(n);
+        if (sn == sn) { ++bad; bad_x = __float_as_uint(n); }
+    }
+    if (bad) {
+        atomicAdd(mismatches, (unsigned long long)bad);
+        first_bad[0] = bad_x;
+    }
+}
+
 }  // namespace fr
+
+extern "C" int fr_selftest_sqrt_fast(int variant, uint64_t *mismatches, uint32_t *bad_x_bits)
+{
+    if (!mismatches || variant < 0 || variant > 1) return FR_E_INVALID;
+    unsigned long long *d_m = nullptr;
+    uint32_t *d_b = nullptr;
+    if (hipMalloc(&d_m, 8) != hipSuccess || hipMalloc(&d_b, 8) != hipSuccess) return FR_E_HIP;
+    (void)hipMemset(d_m, 0, 8);
+    (void)hipMemset(d_b, 0, 8);
+    const uint32_t e_lo = 97u, e_hi = 192u;                        // [2^-30, 2^66), as fr_selftest_sqrt
+    const dim3 grid((e_hi - e_lo + 1u) * 32u), block(256);
+    if (variant == 0) hipLaunchKernelGGL(fr::selftest_sqrt_fast_kernel<0>, grid, block, 0, 0, e_lo, d_m, d_b);
+    else hipLaunchKernelGGL(fr::selftest_sqrt_fast_kernel<1>, grid, block, 0, 0, e_lo, d_m, d_b);
+    unsigned long long m = 0;
+    uint32_t b = 0;
+    hipError_t e = hipMemcpy(&m, d_m, 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(&b, d_b, 4, hipMemcpyDeviceToHost);
+    (void)hipFree(d_m);
+    (void)hipFree(d_b);
+    if (e != hipSuccess) return FR_E_HIP;
+    *mismatches = m;
+    if (bad_x_bits) *bad_x_bits = b;
+    return FR_OK;
+}
 
 extern "C" int fr_selftest_sqrt(uint64_t *mismatches, uint32_t *bad_x_bits)
 {

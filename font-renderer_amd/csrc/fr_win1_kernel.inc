@@ -33,12 +33,13 @@
     uint32_t *s_wcnt = reinterpret_cast<uint32_t *>(smem + L::OFF_WCNT);
 
     const float soff = phase ? 0.5f : 0.0f;
+    const ScaleDiv sdiv = scale_div(job.scale);     // (workgroup-uniform: a multiply when scale is a power of two, fr_device.hpp)
     // cells of up to 256 rows: every row's ray height cy = (f32(max_y - y) - off) / scale (:27) is computed once — the
     // set-up looks at four rows per candidate and every band at 16, each of them a division otherwise
     const float *cyt = nullptr;
     if (job.h <= 256u) {                                                    // (workgroup-uniform)
         float *t = reinterpret_cast<float *>(smem + L::OFF_CYT);
-        if (tid < job.h) t[tid] = ((float)(job.max_y - (int32_t)tid) - soff) / job.scale;
+        if (tid < job.h) t[tid] = sdiv((float)(job.max_y - (int32_t)tid) - soff);
         __syncthreads();
         cyt = t;
     }
@@ -72,7 +73,7 @@
         if (band >= band_end) break;               // (no workgroup barrier below: waves are independent)
         const uint32_t y0 = band * W1_ROWS;         // first pixel row = first sample row of my band
         // ray height of row `lane & 15`: cy = (f32(max_y - y) - off) / scale   (:27)
-        const float cy = cyt ? cyt[y0 + (lane & 15u)] : ((float)(job.max_y - (int32_t)(y0 + (lane & 15u))) - soff) / job.scale;
+        const float cy = cyt ? cyt[y0 + (lane & 15u)] : sdiv((float)(job.max_y - (int32_t)(y0 + (lane & 15u))) - soff);
         {
             uint4 *z = reinterpret_cast<uint4 *>(s_E);
             const uint4 bias = make_uint4(0x20202020u, 0x20202020u, 0x20202020u, 0x20202020u);
