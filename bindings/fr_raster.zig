@@ -72,6 +72,15 @@ pub const GlyphPlaceEx = extern struct {
     slant: f32,
 };
 
+/// a placement with a 2 x 2 matrix (fr_raster.h: fr_glyph_place_affine): m = xx, xy, yx, yy draws the font-unit point
+/// (x, y), y up, xx*x + xy*y pixels right of and yx*x + yy*y pixels above the pen; rotated, mirrored and sheared text
+pub const GlyphPlaceAffine = extern struct {
+    glyph: u32,
+    pen_x64: i32,
+    pen_y64: i32,
+    m: [4]f32,
+};
+
 pub const TextRun = extern struct {
     first: u32,
     count: u32,
@@ -112,6 +121,9 @@ pub extern "c" fn fr_text_plan_create_rgba(ctx: *fr_ctx, gs: *const fr_glyphset,
 /// the two text plan entry points for GlyphPlaceEx placements (same runs, flags, colours and error codes)
 pub extern "c" fn fr_text_plan_create_ex(ctx: *fr_ctx, gs: *const fr_glyphset, places: [*]const GlyphPlaceEx, n_places: u32, runs: [*]const TextRun, n_runs: u32, params: *const RasterParams, flags: u32, out: *?*fr_plan) c_int;
 pub extern "c" fn fr_text_plan_create_rgba_ex(ctx: *fr_ctx, gs: *const fr_glyphset, places: [*]const GlyphPlaceEx, place_rgba: [*]const u8, n_places: u32, runs: [*]const TextRun, run_clear_rgba: [*]const u8, n_runs: u32, params: *const RasterParams, flags: u32, out: *?*fr_plan) c_int;
+/// the same two for GlyphPlaceAffine placements (the text_affine_* kernels)
+pub extern "c" fn fr_text_plan_create_affine(ctx: *fr_ctx, gs: *const fr_glyphset, places: [*]const GlyphPlaceAffine, n_places: u32, runs: [*]const TextRun, n_runs: u32, params: *const RasterParams, flags: u32, out: *?*fr_plan) c_int;
+pub extern "c" fn fr_text_plan_create_rgba_affine(ctx: *fr_ctx, gs: *const fr_glyphset, places: [*]const GlyphPlaceAffine, place_rgba: [*]const u8, n_places: u32, runs: [*]const TextRun, run_clear_rgba: [*]const u8, n_runs: u32, params: *const RasterParams, flags: u32, out: *?*fr_plan) c_int;
 pub extern "c" fn fr_allgather_bands(ctx: *fr_ctx, nccl_comm: *anyopaque, atlas_dev: *anyopaque, band_bytes: usize) c_int;
 pub extern "c" fn fr_gather_bands(ctx: *fr_ctx, nccl_comm: *anyopaque, atlas_dev: *anyopaque, band_bytes: usize, root: c_int) c_int;
 pub extern "c" fn fr_render_batch(ctx: *fr_ctx, gs: *const fr_glyphset, jobs: [*]const Job, n_jobs: u32, params: *const RasterParams, out_host: *anyopaque, out_stride: usize, out_rows: usize) c_int;

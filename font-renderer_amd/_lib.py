@@ -46,6 +46,10 @@ class GlyphPlaceEx(C.Structure):  # == fr_glyph_place_ex
                 ("slant", C.c_float)]
 
 
+class GlyphPlaceAffine(C.Structure):  # == fr_glyph_place_affine
+    _fields_ = [("glyph", C.c_uint32), ("pen_x64", C.c_int32), ("pen_y64", C.c_int32), ("m", C.c_float * 4)]
+
+
 class TextRun(C.Structure):      # == fr_text_run
     _fields_ = [("first", C.c_uint32), ("count", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32),
                 ("out_x", C.c_uint32), ("out_y", C.c_uint32), ("scale", C.c_float)]
@@ -83,6 +87,10 @@ SYMBOLS = [
                                          C.POINTER(_P)]),
     ("fr_text_plan_create_rgba_ex", C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, C.POINTER(RasterParams),
                                               C.c_uint32, C.POINTER(_P)]),
+    ("fr_text_plan_create_affine", C.c_int, [_P, _P, _P, C.c_uint32, _P, C.c_uint32, C.POINTER(RasterParams), C.c_uint32,
+                                             C.POINTER(_P)]),
+    ("fr_text_plan_create_rgba_affine", C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, C.POINTER(RasterParams),
+                                                  C.c_uint32, C.POINTER(_P)]),
     ("fr_allgather_bands", C.c_int, [_P, _P, _P, C.c_size_t]),
     ("fr_gather_bands", C.c_int, [_P, _P, _P, C.c_size_t, C.c_int]),
     ("fr_render_batch", C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(RasterParams), _P, C.c_size_t, C.c_size_t]),

@@ -15,10 +15,13 @@
 // TextInst of fr_glyph_place, or TextInstEx of fr_glyph_place_ex with its own scale, slant and 1/64-pixel baseline, which
 // changes only the map from a sample to the glyph's font units (fr_text_mask_kernel.inc).  The two placement forms stay
 // separate instances because the wider record measured 0.7-1.5 % slower on fr_glyph_place plans.
+// A third form, TextInstAffine of fr_glyph_place_affine (a 2 x 2 matrix: every lane at its own ray height), uses the same
+// two bodies with a mask evaluation of its own; its instances live in fr_text_affine.hip.
 // The ten __global__ templates at the end only set the parameters of a body.  Some include it, some call it through
 // colour_rows; which, is decided by measurement and explained there.
 #include "fr_text.hpp"
 #include "fr_srgb.hpp"
+#include "fr_wave.hpp"
 
 #include <cstdio>
 #include <type_traits>
@@ -132,79 +135,47 @@ FR_TEXT_GLOBAL text_place_srgb_load_kernel(TextPlaceArgs a) { colour_rows<N, FIL
 
 namespace {
 
-struct Launch {
-    uint32_t n_tiles;
-    hipStream_t stream;
-    char *name;
-    size_t name_cap;
-};
+template <class ARGS>
+constexpr const char *text_form() { return std::is_same_v<ARGS, TextPlaceArgs> ? "place_" : ""; }
 
 // FAM: 0 coverage (its kernels have no BLEND: launch_text passes 0), 1 rgba, 2 srgb, 3 rgba load, 4 srgb load
 template <class ARGS, int FAM, int FILL, int BLEND, int N>
-hipError_t launch_instance(const ARGS &a, const Launch &l)
+constexpr auto text_kernel_of() -> void (*)(ARGS)
 {
     constexpr bool PLACE = std::is_same_v<ARGS, TextPlaceArgs>;
-    const char *family;                                                    // the instance and its name, chosen together
-    void (*kernel)(ARGS);
     if constexpr (FAM == 0) {
-        family = "";
-        if constexpr (PLACE) kernel = text_place_kernel<N, FILL>;
-        else kernel = text_kernel<N, FILL>;
+        if constexpr (PLACE) return text_place_kernel<N, FILL>;
+        else return text_kernel<N, FILL>;
     } else if constexpr (FAM == 1) {
-        family = "rgba_";
-        if constexpr (PLACE) kernel = text_place_rgba_kernel<N, FILL, BLEND>;
-        else kernel = text_rgba_kernel<N, FILL, BLEND>;
+        if constexpr (PLACE) return text_place_rgba_kernel<N, FILL, BLEND>;
+        else return text_rgba_kernel<N, FILL, BLEND>;
     } else if constexpr (FAM == 2) {
-        family = "srgb_";
-        if constexpr (PLACE) kernel = text_place_srgb_kernel<N, FILL, BLEND>;
-        else kernel = text_srgb_kernel<N, FILL, BLEND>;
+        if constexpr (PLACE) return text_place_srgb_kernel<N, FILL, BLEND>;
+        else return text_srgb_kernel<N, FILL, BLEND>;
     } else if constexpr (FAM == 3) {
-        family = "rgba_load_";
-        if constexpr (PLACE) kernel = text_place_rgba_load_kernel<N, FILL, BLEND>;
-        else kernel = text_rgba_load_kernel<N, FILL, BLEND>;
+        if constexpr (PLACE) return text_place_rgba_load_kernel<N, FILL, BLEND>;
+        else return text_rgba_load_kernel<N, FILL, BLEND>;
     } else {
-        family = "srgb_load_";
-        if constexpr (PLACE) kernel = text_place_srgb_load_kernel<N, FILL, BLEND>;
-        else kernel = text_srgb_load_kernel<N, FILL, BLEND>;
+        if constexpr (PLACE) return text_place_srgb_load_kernel<N, FILL, BLEND>;
+        else return text_srgb_load_kernel<N, FILL, BLEND>;
     }
-    if (l.name) {                                                          // as rocprofv3 names the instance
-        const char *form = PLACE ? "place_" : "";
-        if constexpr (FAM == 0) snprintf(l.name, l.name_cap, "fr::text_%skernel<%d, %d>", form, N, FILL);
-        else snprintf(l.name, l.name_cap, "fr::text_%s%skernel<%d, %d, %d>", form, family, N, FILL, BLEND);
-    }
-    if (!l.n_tiles) return hipSuccess;
-    hipLaunchKernelGGL(kernel, dim3(l.n_tiles), dim3(64 * TEXT_WAVES), 0, l.stream, a);
-    return hipGetLastError();
 }
 
-template <class ARGS, int FAM, int FILL, int BLEND>
-hipError_t launch_n(const ARGS &a, int n, const Launch &l)
-{
-    if (n == 4) return launch_instance<ARGS, FAM, FILL, BLEND, 4>(a, l);
-    if (n == 2) return launch_instance<ARGS, FAM, FILL, BLEND, 2>(a, l);
-    return launch_instance<ARGS, FAM, FILL, BLEND, 1>(a, l);
-}
-
-template <class ARGS, int FAM>
-hipError_t launch_family(const ARGS &a, int n, int fill, int blend, const Launch &l)
-{
-    if (blend) return fill ? launch_n<ARGS, FAM, 1, 1>(a, n, l) : launch_n<ARGS, FAM, 0, 1>(a, n, l);
-    return fill ? launch_n<ARGS, FAM, 1, 0>(a, n, l) : launch_n<ARGS, FAM, 0, 0>(a, n, l);
-}
+#include "fr_text_launch.inc"
 
 }  // namespace
 
-template <class ARGS>
-hipError_t launch_text(const ARGS &a, int n, int fill, int rgba, int blend, int srgb, int load, uint32_t n_tiles, hipStream_t stream,
+template <>
+hipError_t launch_text(const TextArgs &a, int n, int fill, int rgba, int blend, int srgb, int load, uint32_t n_tiles, hipStream_t stream,
                        char *name, size_t name_cap)
 {
-    const Launch l{n_tiles, stream, name, name_cap};
-    if (!rgba) return launch_family<ARGS, 0>(a, n, fill, 0, l);
-    if (load) return srgb ? launch_family<ARGS, 4>(a, n, fill, blend, l) : launch_family<ARGS, 3>(a, n, fill, blend, l);
-    return srgb ? launch_family<ARGS, 2>(a, n, fill, blend, l) : launch_family<ARGS, 1>(a, n, fill, blend, l);
+    return launch_any(a, n, fill, rgba, blend, srgb, load, Launch{n_tiles, stream, name, name_cap});
 }
-
-template hipError_t launch_text(const TextArgs &, int, int, int, int, int, int, uint32_t, hipStream_t, char *, size_t);
-template hipError_t launch_text(const TextPlaceArgs &, int, int, int, int, int, int, uint32_t, hipStream_t, char *, size_t);
+template <>
+hipError_t launch_text(const TextPlaceArgs &a, int n, int fill, int rgba, int blend, int srgb, int load, uint32_t n_tiles,
+                       hipStream_t stream, char *name, size_t name_cap)
+{
+    return launch_any(a, n, fill, rgba, blend, srgb, load, Launch{n_tiles, stream, name, name_cap});
+}
 
 }  // namespace fr

@@ -30,6 +30,21 @@ struct TextInstEx {    // one fr_glyph_place_ex, resolved on the host: TextInst 
     float slant;       // k: cx = t - k * cy
     uint32_t pad2;
 };
+struct TextInstAffine {  // one fr_glyph_place_affine, resolved on the host: the common fields and the inverse 2 x 2 matrix
+    int32_t ix;        // floor(pen_x64 / 64)
+    int32_t iy;        // floor(pen_y64 / 64)
+    int32_t x0, x1;    // the cell of the mapped box's four corners: columns [x0, x1), clipped to the run
+    int32_t y0, y1;    // its rows [y0, y1), clipped likewise
+    uint32_t glyph;
+    uint32_t rec;
+    uint32_t fx64;     // pen_x64 mod 64
+    uint32_t rgba;     // as TextInst::rgba
+    uint32_t pad[2];   // as TextInst::pad
+    uint32_t fy64;     // pen_y64 mod 64
+    float q00, q01;    // cx = f32(q00 * dx) + f32(q01 * dy)
+    float q10, q11;    // cy = f32(q10 * dx) + f32(q11 * dy): every lane has its own ray height
+    uint32_t pad2[3];
+};
 struct TextRun {       // == fr_text_run's geometry
     uint32_t w, h, out_x, out_y;
     float scale;
@@ -54,7 +69,9 @@ struct TextTables {        // what a text kernel reads, for either placement for
 };
 struct TextArgs : TextTables<TextInst> {};         // fr_glyph_place placements: the text_*_kernel instances
 struct TextPlaceArgs : TextTables<TextInstEx> {};  // fr_glyph_place_ex placements: the text_place_*_kernel instances
+struct TextAffineArgs : TextTables<TextInstAffine> {};  // fr_glyph_place_affine placements: the text_affine_*_kernel instances
 static_assert(sizeof(TextInstEx) == 64, "text tables");
+static_assert(sizeof(TextInstAffine) == 80, "text tables");
 static_assert(sizeof(TextInst) == 48 && sizeof(TextRun) == 32 && sizeof(TextTile) == 32, "text tables");
 
 constexpr int TEXT_TILE_W = 64, TEXT_TILE_H = 16, TEXT_WAVES = 4;
@@ -63,7 +80,7 @@ constexpr int TEXT_TILE_W = 64, TEXT_TILE_H = 16, TEXT_WAVES = 4;
 // then ignored); else blend = 0 when every placement colour of the plan is opaque (A = 255), srgb for FR_TEXT_SRGB plans
 // (blending and resolve in linear light), load for FR_TEXT_LOAD plans (the samples start at the output's pixels; n_tiles
 // then counts only the tiles with a non-empty instance list).  n_tiles = 0: only name the instance (as rocprofv3 names
-// it) into name[name_cap].  ARGS: TextArgs or TextPlaceArgs.
+// it) into name[name_cap].  ARGS: TextArgs or TextPlaceArgs (fr_text.hip), or TextAffineArgs (fr_text_affine.hip).
 template <class ARGS>
 hipError_t launch_text(const ARGS &a, int n, int fill, int rgba, int blend, int srgb, int load, uint32_t n_tiles, hipStream_t stream,
                        char *name = nullptr, size_t name_cap = 0);

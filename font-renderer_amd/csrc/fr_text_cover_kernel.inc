@@ -1,5 +1,5 @@
 // fr_text_cover_kernel.inc — the rows of one tile as coverage / mask bytes: the body of text_kernel and text_place_kernel
-// (fr_text.hip).  Uses INST, N, FILL, PLACE, a.  Text, not a function: see the note on the instances in fr_text.hip.
+// (fr_text.hip) and of text_affine_kernel (fr_text_affine.hip).  Uses INST, N, FILL, PLACE, a.  Text, not a function: see the note on the instances in fr_text.hip.
     const TextTile tl = a.tiles[blockIdx.x];
     const TextRun rn = a.runs[tl.run];
     const int lane = (int)(threadIdx.x & 63u);
@@ -16,7 +16,12 @@
             const INST in = a.insts[a.list[q]];
             if (Y < in.y0 || Y >= in.y1) continue;                       // (wave-uniform)
             const bool inside = X >= in.x0 && X < in.x1;
+            uint32_t m;
+            if constexpr (std::is_same_v<INST, TextInstAffine>) {
+#include "fr_text_affine_mask_kernel.inc"
+            } else {
 #include "fr_text_mask_kernel.inc"
+            }
             if (inside) mask |= m;
         }
         if (X < (int)rn.w) {                                               // every pixel of the run: 0 where no instance reaches

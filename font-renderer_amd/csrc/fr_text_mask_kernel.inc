@@ -1,5 +1,5 @@
 // fr_text_mask_kernel.inc — one instance's n^2-bit non-zero mask at pixel (X, Y), included inside the instance loops of
-// fr_text_cover_kernel.inc and fr_text_colour_kernel.inc.  Uses N, FILL, PLACE, a, rn, in, X, Y, off[N]; defines m (bit j*N + i: the
+// fr_text_cover_kernel.inc and fr_text_colour_kernel.inc.  Uses N, FILL, PLACE, a, rn, in, X, Y, off[N]; sets m (bit j*N + i: the
 // winding at sub-sample (i, j) is non-zero).  Text, not a function: as a function taking the instance by reference it
 // moved five n = 4 instances to another VGPR bracket (DESIGN.md 4.7).
 // The map from a sample to the glyph's font units (include/fr_raster.h):
@@ -57,6 +57,6 @@
                     }
                 }
             }
-            uint32_t m = 0u;
+            m = 0u;
 #pragma unroll
             for (int k = 0; k < N * N; ++k) m |= (wn[k] != 0 ? 1u : 0u) << k;

@@ -182,13 +182,52 @@ inline Image::Gray renderAtlas(Context &ctx, const std::vector<Glyph> &glyphs, F
 }
 
 // a text plan of fr_glyph_place_ex placements (include/fr_raster.h: own scale, slant and sub-pixel baseline per placement)
-// over a set of glyphs: coverage bytes, or RGBA pixels when place_rgba is given.  The plan renders into DEVICE memory
+// or of fr_glyph_place_affine placements (a 2 x 2 matrix per placement: rotated, mirrored and sheared text; the struct is
+// the C header's: uint32_t glyph, int32_t pen_x64, pen_y64, float m[4] = xx, xy, yx, yy) over a set of glyphs: coverage bytes, or RGBA pixels when place_rgba is given.  The plan renders into DEVICE memory
 // (fr_plan_render), which the host that owns the HIP stream allocates; this mirror owns the glyph set and the plan.
 class PlacedText {
 public:
     PlacedText(Context &ctx, const std::vector<Glyph> &glyphs, const std::vector<fr_glyph_place_ex> &places,
                const std::vector<fr_text_run> &runs, int samples_per_axis = 4, uint32_t flags = 0,
                const std::vector<uint8_t> *place_rgba = nullptr, const std::vector<uint8_t> *run_clear_rgba = nullptr)
+    {
+        init(ctx, glyphs, places, runs, samples_per_axis, flags, place_rgba, run_clear_rgba);
+    }
+    PlacedText(Context &ctx, const std::vector<Glyph> &glyphs, const std::vector<fr_glyph_place_affine> &places,
+               const std::vector<fr_text_run> &runs, int samples_per_axis = 4, uint32_t flags = 0,
+               const std::vector<uint8_t> *place_rgba = nullptr, const std::vector<uint8_t> *run_clear_rgba = nullptr)
+    {
+        init(ctx, glyphs, places, runs, samples_per_axis, flags, place_rgba, run_clear_rgba);
+    }
+    ~PlacedText() { fr_plan_destroy(plan_); fr_glyphset_destroy(gs_); }
+    PlacedText(const PlacedText &) = delete;
+    PlacedText &operator=(const PlacedText &) = delete;
+    fr_plan *get() const { return plan_; }
+    uint64_t pixels() const { return fr_plan_pixels(plan_); }
+    std::string describe() const
+    {
+        char buf[512];
+        check(fr_plan_describe(plan_, buf, sizeof buf));
+        return buf;
+    }
+    // asynchronous on the context's stream; out_dev is a DEVICE pointer (bytes, or 4-byte aligned RGBA pixels)
+    void render(void *out_dev, size_t out_stride, size_t out_rows) { check(fr_plan_render(plan_, out_dev, out_stride, out_rows)); }
+private:
+    static int create(fr_ctx *c, fr_glyphset *gs, const fr_glyph_place_ex *p, const uint8_t *rgba, uint32_t n, const fr_text_run *r,
+                      const uint8_t *clear, uint32_t nr, const fr_raster_params *prm, uint32_t flags, fr_plan **out)
+    {
+        return rgba ? fr_text_plan_create_rgba_ex(c, gs, p, rgba, n, r, clear, nr, prm, flags, out)
+                    : fr_text_plan_create_ex(c, gs, p, n, r, nr, prm, flags, out);
+    }
+    static int create(fr_ctx *c, fr_glyphset *gs, const fr_glyph_place_affine *p, const uint8_t *rgba, uint32_t n, const fr_text_run *r,
+                      const uint8_t *clear, uint32_t nr, const fr_raster_params *prm, uint32_t flags, fr_plan **out)
+    {
+        return rgba ? fr_text_plan_create_rgba_affine(c, gs, p, rgba, n, r, clear, nr, prm, flags, out)
+                    : fr_text_plan_create_affine(c, gs, p, n, r, nr, prm, flags, out);
+    }
+    template <class PLACE>
+    void init(Context &ctx, const std::vector<Glyph> &glyphs, const std::vector<PLACE> &places, const std::vector<fr_text_run> &runs,
+              int samples_per_axis, uint32_t flags, const std::vector<uint8_t> *place_rgba, const std::vector<uint8_t> *run_clear_rgba)
     {
         std::vector<int16_t> pts, boxes;
         std::vector<uint32_t> cstart{0}, gstart{0};
@@ -206,30 +245,14 @@ public:
         fr_raster_params prm{FR_COVERAGE_U8, samples_per_axis, FR_SAMPLE_CENTER, 0};
         int rc = fr_glyphset_set_boxes(gs_, boxes.data());
         if (rc == FR_OK)
-            rc = place_rgba ? fr_text_plan_create_rgba_ex(ctx.get(), gs_, places.data(), place_rgba->data(), (uint32_t)places.size(),
-                                                          runs.data(), run_clear_rgba ? run_clear_rgba->data() : nullptr,
-                                                          (uint32_t)runs.size(), &prm, flags, &plan_)
-                            : fr_text_plan_create_ex(ctx.get(), gs_, places.data(), (uint32_t)places.size(), runs.data(),
-                                                     (uint32_t)runs.size(), &prm, flags, &plan_);
+            rc = create(ctx.get(), gs_, places.data(), place_rgba ? place_rgba->data() : nullptr, (uint32_t)places.size(), runs.data(),
+                        run_clear_rgba ? run_clear_rgba->data() : nullptr, (uint32_t)runs.size(), &prm, flags, &plan_);
         if (rc != FR_OK) {
             fr_glyphset_destroy(gs_);
+            gs_ = nullptr;
             check(rc);
         }
     }
-    ~PlacedText() { fr_plan_destroy(plan_); fr_glyphset_destroy(gs_); }
-    PlacedText(const PlacedText &) = delete;
-    PlacedText &operator=(const PlacedText &) = delete;
-    fr_plan *get() const { return plan_; }
-    uint64_t pixels() const { return fr_plan_pixels(plan_); }
-    std::string describe() const
-    {
-        char buf[512];
-        check(fr_plan_describe(plan_, buf, sizeof buf));
-        return buf;
-    }
-    // asynchronous on the context's stream; out_dev is a DEVICE pointer (bytes, or 4-byte aligned RGBA pixels)
-    void render(void *out_dev, size_t out_stride, size_t out_rows) { check(fr_plan_render(plan_, out_dev, out_stride, out_rows)); }
-private:
     fr_glyphset *gs_ = nullptr;
     fr_plan *plan_ = nullptr;
 };

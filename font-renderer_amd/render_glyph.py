@@ -161,6 +161,7 @@ class Plan:
 
 PLACE_DTYPE = np.dtype([("glyph", "<u4"), ("pen_x64", "<i4"), ("pen_y", "<i4")])
 PLACE_EX_DTYPE = np.dtype([("glyph", "<u4"), ("pen_x64", "<i4"), ("pen_y64", "<i4"), ("scale", "<f4"), ("slant", "<f4")])
+PLACE_AFFINE_DTYPE = np.dtype([("glyph", "<u4"), ("pen_x64", "<i4"), ("pen_y64", "<i4"), ("m", "<f4", (4,))])
 RUN_DTYPE = np.dtype([("first", "<u4"), ("count", "<u4"), ("w", "<u4"), ("h", "<u4"), ("out_x", "<u4"), ("out_y", "<u4"),
                       ("scale", "<f4")])
 
@@ -175,10 +176,22 @@ def make_places_ex(rows: Sequence) -> np.ndarray:
     return np.array([tuple(r) for r in rows], PLACE_EX_DTYPE)
 
 
+def make_places_affine(rows: Sequence) -> np.ndarray:
+    """rows of (glyph, pen_x64, pen_y64, xx, xy, yx, yy) -> fr_glyph_place_affine array: the font-unit point (x, y), y up, is
+    drawn xx*x + xy*y pixels right of and yx*x + yy*y pixels above the pen"""
+    out = np.zeros(len(rows), PLACE_AFFINE_DTYPE)
+    for k, r in enumerate(rows):
+        out[k] = (r[0], r[1], r[2], tuple(r[3:7]))
+    return out
+
+
 def _places(places) -> tuple:
-    """a placement array of either dtype -> (C-contiguous array, whether it is fr_glyph_place_ex)"""
-    ex = getattr(places, "dtype", None) == PLACE_EX_DTYPE
-    return np.ascontiguousarray(places, PLACE_EX_DTYPE if ex else PLACE_DTYPE), ex
+    """a placement array of any of the three dtypes -> (C-contiguous array, the suffix of its entry points)"""
+    dt = getattr(places, "dtype", None)
+    if dt == PLACE_AFFINE_DTYPE:
+        return np.ascontiguousarray(places, PLACE_AFFINE_DTYPE), "_affine"
+    ex = dt == PLACE_EX_DTYPE
+    return np.ascontiguousarray(places, PLACE_EX_DTYPE if ex else PLACE_DTYPE), "_ex" if ex else ""
 
 
 def make_runs(rows: Sequence) -> np.ndarray:
@@ -189,7 +202,8 @@ def make_runs(rows: Sequence) -> np.ndarray:
 class TextPlan(Plan):
     """fr_text_plan_create: glyph placements and the runs that composite them (include/fr_raster.h).  An ordinary
     fr_plan: render / render_timed / describe / stats / pixels / close as Plan.  mode: FR_COVERAGE_U8 (n in {1, 2, 4})
-    or FR_MASK_NONZERO (n = 1).  places of PLACE_EX_DTYPE (make_places_ex) go through fr_text_plan_create_ex."""
+    or FR_MASK_NONZERO (n = 1).  places of PLACE_EX_DTYPE (make_places_ex) go through fr_text_plan_create_ex, places of
+    PLACE_AFFINE_DTYPE (make_places_affine) through fr_text_plan_create_affine."""
 
     def __init__(self, dgs: DeviceGlyphSet, places: np.ndarray, runs: np.ndarray, mode: int = L.FR_COVERAGE_U8,
                  samples_per_axis: int = 4, sample_phase: int = L.FR_SAMPLE_CENTER, flags: int = 0):
@@ -198,7 +212,7 @@ class TextPlan(Plan):
         self.ctx, self.dgs, self.mode = dgs.ctx, dgs, mode
         self.params = L.RasterParams(mode, samples_per_axis, sample_phase, 0)
         h = C.c_void_p()
-        create = self.ctx._lib.fr_text_plan_create_ex if ex else self.ctx._lib.fr_text_plan_create
+        create = getattr(self.ctx._lib, "fr_text_plan_create" + ex)
         L.check(create(self.ctx._h, dgs._h, L.ptr(places), len(places), L.ptr(runs), len(runs), C.byref(self.params), flags, C.byref(h)))
         self._h = h
         self.n_places, self.n_runs = len(places), len(runs)
@@ -217,7 +231,8 @@ class TextPlanRGBA(Plan):
     in placement order over each run's clear colour (n_runs x 4 u8); renders RGBA pixels (4 bytes each, 4-byte aligned
     output; strides and rows count pixels).  FR_COVERAGE_U8 only, n in {1, 2, 4}.  With FR_TEXT_LOAD in `flags` the
     samples start at the pixels already in the output instead, and run_clear_rgba may be None (it is ignored).  places of
-    PLACE_EX_DTYPE (make_places_ex) go through fr_text_plan_create_rgba_ex."""
+    PLACE_EX_DTYPE (make_places_ex) go through fr_text_plan_create_rgba_ex, places of PLACE_AFFINE_DTYPE
+    (make_places_affine) through fr_text_plan_create_rgba_affine."""
 
     def __init__(self, dgs: DeviceGlyphSet, places: np.ndarray, place_rgba, runs: np.ndarray, run_clear_rgba,
                  samples_per_axis: int = 4, sample_phase: int = L.FR_SAMPLE_CENTER, flags: int = 0):
@@ -228,7 +243,7 @@ class TextPlanRGBA(Plan):
         self.ctx, self.dgs, self.mode = dgs.ctx, dgs, L.FR_COVERAGE_U8
         self.params = L.RasterParams(L.FR_COVERAGE_U8, samples_per_axis, sample_phase, 0)
         h = C.c_void_p()
-        create = self.ctx._lib.fr_text_plan_create_rgba_ex if ex else self.ctx._lib.fr_text_plan_create_rgba
+        create = getattr(self.ctx._lib, "fr_text_plan_create_rgba" + ex)
         L.check(create(self.ctx._h, dgs._h, L.ptr(places), L.ptr(pc), len(places), L.ptr(runs), None if rc is None else L.ptr(rc),
                        len(runs), C.byref(self.params), flags, C.byref(h)))
         self._h = h

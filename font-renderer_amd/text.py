@@ -2,7 +2,8 @@
 through a text plan (fr_text_plan_create, include/fr_raster.h), or as one RGBA image through an RGBA text plan
 (fr_text_plan_create_rgba), or drawn over an RGBA image the caller has (FR_TEXT_LOAD).  A slant, a fractional baseline,
 spans of several sizes on one baseline (render_spans) and the reference's zoomed and dragged frame (render_text_view)
-go through the placement form of those plans (fr_glyph_place_ex).  Nothing is computed in Python but the image size
+go through the placement form of those plans (fr_glyph_place_ex); a line along any direction (render_text_rotated) goes
+through the matrix form (fr_glyph_place_affine).  Nothing is computed in Python but the image size
 and the pen positions."""
 from __future__ import annotations
 
@@ -14,8 +15,8 @@ import numpy as np
 from . import _lib as L
 from .font import Font
 from .image import RGBA, Gray
-from .render_glyph import (Context, DeviceGlyphSet, TextPlan, TextPlanRGBA, default_context, make_places, make_places_ex,
-                           make_runs)
+from .render_glyph import (Context, DeviceGlyphSet, TextPlan, TextPlanRGBA, default_context, make_places, make_places_affine,
+                           make_places_ex, make_runs)
 
 
 def instance_cell(box, scale: float, pen_x64: int, pen_y: int):
@@ -39,6 +40,20 @@ def instance_cell_ex(box, scale: float, slant: float, pen_x64: int, pen_y64: int
     hi = max(f(x_max + f(k * y_min)), f(x_max + f(k * y_max)))
     mn_x, mx_x = math.floor(f(lo * s)), math.ceil(f(hi * s))
     mn_y, mx_y = math.floor(f(y_min * s)), math.ceil(f(y_max * s))
+    return ((pen_x64 >> 6) + mn_x, (pen_y64 >> 6) - mx_y, mx_x - mn_x + 1 + ((pen_x64 & 63) != 0),
+            mx_y - mn_y + 1 + ((pen_y64 & 63) != 0))
+
+
+def instance_cell_affine(box, m, pen_x64: int, pen_y64: int):
+    """instance_cell for an fr_glyph_place_affine (include/fr_raster.h): the grid of the box's four corners mapped by
+    m = (xx, xy, yx, yy), one column / row wider when the pen's x / y has a fractional part (binary32, one rounding per
+    operation)"""
+    f = np.float32
+    xx, xy, yx, yy = (f(v) for v in m)
+    x_min, y_min, x_max, y_max = (f(int(v)) for v in box)
+    u = [f(f(xx * x) + f(xy * y)) for x in (x_min, x_max) for y in (y_min, y_max)]
+    v = [f(f(yx * x) + f(yy * y)) for x in (x_min, x_max) for y in (y_min, y_max)]
+    mn_x, mx_x, mn_y, mx_y = math.floor(min(u)), math.ceil(max(u)), math.floor(min(v)), math.ceil(max(v))
     return ((pen_x64 >> 6) + mn_x, (pen_y64 >> 6) - mx_y, mx_x - mn_x + 1 + ((pen_x64 & 63) != 0),
             mx_y - mn_y + 1 + ((pen_y64 & 63) != 0))
 
@@ -345,3 +360,78 @@ def render_text_view(font: Font, text, font_size: int, zoom: float, offset_x: fl
         return Gray.init(int(width), int(height))
     ctx = ctx or default_context()
     return _render_gray(ctx, *line, int(width), int(height), mode, samples_per_axis, phase, flags)
+
+
+def _cos_sin(angle_deg: float):
+    """cos and sin of an angle in degrees; at the quarter turns exactly 0 and +-1"""
+    a = math.fmod(float(angle_deg), 360.0)
+    if a == math.floor(a) and int(a) % 90 == 0:
+        return ((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0))[(int(a) // 90) % 4]
+    r = math.radians(a)
+    return math.cos(r), math.sin(r)
+
+
+def rotated_line(font: Font, text, font_size: int, angle_deg: float, x: float, y: float, width: int, height: int,
+                 zoom: float = 1.0, slant: float = 0.0):
+    """A line along a direction: laid out at `font_size` by font.layout, its origin at the pixel position (x, y) (y
+    downwards) and its baseline turned by angle_deg counter-clockwise.  Glyph k's pen is at (x + cos * zoom * pen_k / 64,
+    y - sin * zoom * pen_k / 64), kept to 1/64 pixel (floor(64 v + 1/2)); every placement's matrix is
+    s * R(angle) * [[1, slant], [0, 1]] with s = font_size * zoom / units_per_em, computed in binary64 and rounded once to
+    binary32.  At the quarter turns cos and sin are exactly 0 and +-1, so those matrices are exact.  -> (glyph set,
+    fr_glyph_place_affine places, runs): one run of width x height pixels that clips the line, or None for an empty text
+    or image."""
+    zoom = float(zoom)
+    if not (math.isfinite(zoom) and zoom > 0.0):
+        raise ValueError(f"zoom {zoom!r}: expected a finite value > 0")
+    if not (math.isfinite(float(x)) and math.isfinite(float(y)) and math.isfinite(float(angle_deg))):
+        raise ValueError("x / y / angle_deg: expected finite values")
+    if not (isinstance(width, (int, np.integer)) and isinstance(height, (int, np.integer)) and 0 <= width <= 65535
+            and 0 <= height <= 65535):
+        raise ValueError(f"width {width!r} and height {height!r} must be integers in [0, 65535]")
+    k = _slant(slant)
+    gi, pen, _ = font.layout(text, font_size)
+    if len(gi) == 0 or width == 0 or height == 0:
+        return None
+    gs, kept = font.glyphset(sorted(set(int(g) for g in gi)), skip_unsupported=False)
+    local = {g: i for i, g in enumerate(kept)}
+    c, sn = _cos_sin(angle_deg)
+    s = float(font_size) * zoom / float(font.information.units_per_em)
+    m = (s * c, s * (c * k - sn), s * sn, s * (sn * k + c))
+    places = make_places_affine([(local[int(g)], math.floor(64.0 * (float(x) + c * zoom * int(p) / 64.0) + 0.5),
+                                  math.floor(64.0 * (float(y) - sn * zoom * int(p) / 64.0) + 0.5)) + m for g, p in zip(gi, pen)])
+    runs = make_runs([(0, len(places), int(width), int(height), 0, 0, 1.0)])
+    return gs, places, runs
+
+
+def render_text_rotated(font: Font, text, font_size: int, angle_deg: float, x: float, y: float, width: int, height: int, *,
+                        zoom: float = 1.0, slant: float = 0.0, samples_per_axis: int = 4, mode: int = L.FR_COVERAGE_U8,
+                        phase: int = L.FR_SAMPLE_CENTER, flags: int = L.FR_FILL_CONSISTENT, ctx: Optional[Context] = None) -> Gray:
+    """`text` along a direction (rotated_line), clipped to a width x height image: a vertical axis title is angle_deg = 90
+    with (x, y) at its lower end.  FR_FILL_CONSISTENT is the default here: under a rotation the reference's false
+    windings on rows through vertices become slanted streaks (include/fr_raster.h)."""
+    line = rotated_line(font, text, font_size, angle_deg, x, y, width, height, zoom, slant)
+    if line is None:
+        return Gray.init(int(width), int(height))
+    ctx = ctx or default_context()
+    return _render_gray(ctx, *line, int(width), int(height), mode, samples_per_axis, phase, flags)
+
+
+def render_text_rgba_rotated(font: Font, text, font_size: int, angle_deg: float, x: float, y: float, width: int, height: int,
+                             color=(225, 105, 180, 255), background=(0, 0, 0, 0), colors=None, *, zoom: float = 1.0,
+                             slant: float = 0.0, samples_per_axis: int = 4, phase: int = L.FR_SAMPLE_CENTER,
+                             flags: int = L.FR_FILL_CONSISTENT, srgb: bool = False, bgra: bool = False,
+                             ctx: Optional[Context] = None) -> RGBA:
+    """render_text_rotated as one RGBA image: colours, background, srgb and bgra as render_text_rgba"""
+    flags |= (L.FR_TEXT_SRGB if srgb else 0) | (L.FR_TEXT_BGRA if bgra else 0)
+    n_chars = len(text)
+    if colors is not None and len(colors) != n_chars:
+        raise ValueError(f"colors: {len(colors)} colours for {n_chars} characters")
+    per_char = [_rgba(c) for c in colors] if colors is not None else [_rgba(color)] * n_chars
+    clear = _rgba(background)
+    line = rotated_line(font, text, font_size, angle_deg, x, y, width, height, zoom, slant)
+    if line is None:
+        im = RGBA.init(int(width), int(height))
+        im.data[:] = clear
+        return im
+    ctx = ctx or default_context()
+    return _render_rgba(ctx, *line, int(width), int(height), per_char, clear, samples_per_axis, phase, flags)

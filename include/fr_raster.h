@@ -339,8 +339,8 @@ int fr_text_plan_create_rgba(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_
  *   So: (1) with pen_y64 = 64 * pen_y, scale 0 (or the run's) and slant 0, cell and samples are those of fr_glyph_place
  *   bit for bit; (2) adding 64 to every pen_y64 of a run moves its image down by exactly one row.
  * fr_plan_describe names text_place_kernel<n, fill>, or text_place_rgba_kernel / text_place_srgb_kernel /
- * text_place_rgba_load_kernel / text_place_srgb_load_kernel<n, fill, blend>, with the instance count.  Rotation is not
- * offered: it makes the ray height differ per lane.                                             */
+ * text_place_rgba_load_kernel / text_place_srgb_load_kernel<n, fill, blend>, with the instance count.  Rotation is
+ * fr_glyph_place_affine, below: it makes the ray height differ per lane and has its own kernels.                       */
 typedef struct fr_glyph_place_ex {
     uint32_t glyph;     /* index into the glyph set                                                  */
     int32_t  pen_x64;   /* image x of the glyph's font-unit origin, 1/64 pixel (as fr_glyph_place)   */
@@ -356,6 +356,58 @@ int fr_text_plan_create_rgba_ex(fr_ctx *ctx, const fr_glyphset *gs, const fr_gly
                                 const uint8_t *place_rgba, uint32_t n_places, const fr_text_run *runs,
                                 const uint8_t *run_clear_rgba, uint32_t n_runs, const fr_raster_params *params,
                                 uint32_t flags, fr_plan **out);
+
+/* ---- text placements with a 2 x 2 matrix: rotated, mirrored and sheared text (BUILD-DEFINED) ----
+ * fr_text_plan_create_ex / fr_text_plan_create_rgba_ex with a matrix per placement: vertical axis titles, text along a
+ * direction, a rotated view, mirrored text.  Runs, modes, n in {1, 2, 4}, both phases, the flags (FR_FILL_CONSISTENT; for
+ * the RGBA form FR_TEXT_SRGB, FR_TEXT_BGRA, FR_TEXT_LOAD), colours, blend order, resolve, clipping to the run, "every
+ * pixel of the run is written", the LOAD tile rule and the error codes are those of the _ex entry points.
+ * fr_text_run::scale is validated as before but not used by these placements.  Only the instance geometry differs.  All
+ * arithmetic below is binary32 with one rounding per written operation and no fused multiply-add, except the inverse
+ * matrix, which is binary64.
+ *   For a placement let (xx, xy, yx, yy) = m: the font-unit point (x, y), y up, is drawn xx*x + xy*y pixels right of and
+ *   yx*x + yy*y pixels above the pen.  ix, fx, iy, fy come from pen_x64 and pen_y64 exactly as for fr_glyph_place_ex.
+ *   Inverse (host, once per placement, binary64 from the four floats): D = xx*yy - xy*yx as two rounded products and one
+ *     rounded difference, no fused multiply-add; q00 = f32(yy / D), q01 = f32(-xy / D), q10 = f32(-yx / D),
+ *     q11 = f32(xx / D).
+ *   Cell: for the four corners (x, y) of the glyph's box as floats, u = f32(xx*x) + f32(xy*y), v = f32(yx*x) + f32(yy*y);
+ *     min_x = floor(min u), max_x = ceil(max u), min_y = floor(min v), max_y = ceil(max v).  The cell is
+ *     (max_x - min_x + 1 + (fx != 0)) columns by (max_y - min_y + 1 + (fy != 0)) rows; its column 0 is image column
+ *     ix + min_x, its row 0 image row iy - max_y.  It is clipped to the run.  Outside its cell an instance contributes
+ *     nothing; inside it every sample counts: there is no further gate in glyph space.  Without FR_FILL_CONSISTENT the
+ *     reference's false windings on sample rows through vertices are therefore reproduced wherever the cell reaches, and
+ *     under a rotation such a row is a slanted line across the cell, not an image row: FR_FILL_CONSISTENT is recommended
+ *     for rotated text.
+ *   Sample (i, j) of image pixel (X, Y) inside the cell, off(q) = (q + phase) / n:
+ *       dx = f32(X - ix) + (off(i) - fx)            dy = f32(iy - Y) + (fy - off(j))
+ *       cx = f32(q00 * dx) + f32(q01 * dy)          cy = f32(q10 * dx) + f32(q11 * dy)
+ *     The winding at (cx, cy) is the reference's (or FR_FILL_CONSISTENT's) for the glyph's own integer points, per
+ *     instance.  A negative D (mirrored text) is valid: the non-zero test does not depend on orientation.
+ *   Validation: any m not finite, or D == 0: FR_E_INVALID.  Any |m| > 2^20 or any |q| > 2^20: FR_E_UNSUPPORTED.  The pen
+ *     and cell limits of fr_text_plan_create apply to iy and the cell above.
+ *   So: (1) with m = {s, s*k, 0, s} and s a power of two, the cell and every sample are bit for bit those of
+ *   fr_glyph_place_ex with scale s and slant k (multiplying by the exact 1/s and by -k/s rounds as the division and the
+ *   product do); (2) adding 64 to every pen_y64 of a run moves its image down by exactly one row, and adding 64 to every
+ *   pen_x64 moves it right by exactly one column; (3) m = {0, -s, s, 0} is a quarter turn counter-clockwise.
+ * fr_plan_describe names text_affine_kernel<n, fill>, or text_affine_rgba_kernel / text_affine_srgb_kernel /
+ * text_affine_rgba_load_kernel / text_affine_srgb_load_kernel<n, fill, blend>, with the instance count.  Every lane
+ * solves every record at its own ray height, so these plans cost more than the upright forms, most at a quarter turn
+ * (DESIGN.md section 4.7).  Perspective and one matrix per run are not offered.                 */
+typedef struct fr_glyph_place_affine {
+    uint32_t glyph;     /* index into the glyph set                                                       */
+    int32_t  pen_x64;   /* image x of the glyph's font-unit origin, 1/64 pixel                            */
+    int32_t  pen_y64;   /* image y of it, 1/64 pixel, downwards (as fr_glyph_place_ex)                    */
+    float    m[4];      /* xx, xy, yx, yy: the font-unit point (x, y), y up, is drawn                     */
+                        /* xx*x + xy*y pixels right of and yx*x + yy*y pixels above the pen               */
+} fr_glyph_place_affine;
+
+int fr_text_plan_create_affine(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place_affine *places, uint32_t n_places,
+                               const fr_text_run *runs, uint32_t n_runs, const fr_raster_params *params, uint32_t flags,
+                               fr_plan **out);
+int fr_text_plan_create_rgba_affine(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place_affine *places,
+                                    const uint8_t *place_rgba, uint32_t n_places, const fr_text_run *runs,
+                                    const uint8_t *run_clear_rgba, uint32_t n_runs, const fr_raster_params *params,
+                                    uint32_t flags, fr_plan **out);
 
 /* One-shot: plan + render + copy back.  out_host: HOST buffer (caller-allocated,
  * e.g. Image.Gray.data / Image.Winding.data from the Zig allocator).  Synchronous.  */

@@ -28,12 +28,22 @@ random baseline fraction per placement.  The three are timed alternately in the 
 each figure is the median over the repeats of the median of --steps renders, with the smallest and largest repeat of
 (a) beside it: a difference of (b) from (a) inside that spread is not a difference.  (b) must render (a)'s bytes (checked).
 
+--affine prices the matrix form (fr_text_plan_create_affine: a 2 x 2 matrix per placement, every lane solving every
+record at its own ray height, fr_text_affine.hip), printed as its own JSON lines ("case": "affine"), one per font and
+size, coverage plans: (a) the _ex plan of the lines, (b) the affine plan at 0 degrees, where the kernel's cull removes
+nearly every record, (c) at 5, (d) at 45 and (e) at 90 degrees, where a wave's row spans the glyph's whole height and
+the cull removes nothing.  Every line keeps a run of its own, as large as the union of its rotated cells (so at 45
+degrees the runs are squares around a diagonal line: "run_mpixel" is reported per form), shelf-packed into one image.
+The five are timed alternately in the same process, --repeats times over; figures as for --place.  --affine-only
+leaves the other configurations out.
+
 --samples {1,2,4} (default 4) and --fill (FR_FILL_CONSISTENT) go to every plan, so the kernel instances named below as
-<4, 0, ...> become <samples, fill, ...>.  All text kernels, those of the placement form included, live in csrc/fr_text.hip.
+<4, 0, ...> become <samples, fill, ...>.  The text kernels live in csrc/fr_text.hip, those of the matrix form in
+csrc/fr_text_affine.hip.
 
     python tools/bench_text.py [--lines 4096] [--chars 64] [--steps 20] [--warmup 3] [--samples 4] [--fill]
                                [--rgba] [--srgb] [--load]
-                               [--place [--repeats 5] [--place-only]]"""
+                               [--place [--repeats 5] [--place-only]] [--affine [--affine-only]]"""
 import argparse
 import json
 import os
@@ -122,15 +132,20 @@ def main():
                     "entry points, alternating in the same run")
     ap.add_argument("--repeats", type=int, default=5, help="--place: repeats of each alternated timing (at least 5)")
     ap.add_argument("--place-only", action="store_true", help="--place without the other configurations")
+    ap.add_argument("--affine", action="store_true", help="also price the matrix form (fr_glyph_place_affine) at 0, 5, 45 and 90 "
+                    "degrees against the _ex plan, alternating in the same run (--repeats)")
+    ap.add_argument("--affine-only", action="store_true", help="--affine without the other configurations")
     args = ap.parse_args()
-    if args.place and args.repeats < 5:
+    if (args.place or args.affine) and args.repeats < 5:
         ap.error("--repeats: at least 5")
     import torch
     ns, fill = args.samples, fr.FR_FILL_CONSISTENT if args.fill else 0
     ctx = fr.Context(0)
     if args.place:
         place(ctx, args)
-    for fi, name in enumerate([] if args.place and args.place_only else ["DejaVuSans.ttf", "DejaVuSerif-Italic.ttf"]):
+    if args.affine:
+        affine(ctx, args)
+    for fi, name in enumerate([] if (args.place and args.place_only) or (args.affine and args.affine_only) else ["DejaVuSans.ttf", "DejaVuSerif-Italic.ttf"]):
         font = load_font(name, allow_hinted=True)        # (DejaVuSans carries hinting instructions)
         for size in (16, 32):
             gs, places, runs, shape, jobs, jshape, lines = workload(font, args.lines, args.chars, size, seed=100 * fi + size)
@@ -244,6 +259,79 @@ def place(ctx, args):
                 for plan in plans.values():
                     plan.close()
                 del bufs
+            dgs.close()
+            print(json.dumps(out), flush=True)
+
+
+def rotated_runs(gs, places, runs, scale, angle_deg, width=16384):
+    """the workload's lines turned by angle_deg about each line's pen origin, as fr_glyph_place_affine placements with
+    m = scale * R(angle): every line in a run of its own that is the union of its instance cells (include/fr_raster.h),
+    the runs shelf-packed into an image at most `width` columns wide -> (places, runs, shape)"""
+    import math
+    f = np.float32
+    c, sn = {0: (1.0, 0.0), 90: (0.0, 1.0)}.get(angle_deg, (math.cos(math.radians(angle_deg)), math.sin(math.radians(angle_deg))))
+    s = float(scale)
+    m = np.array([s * c, -s * sn, s * sn, s * c]).astype(f)
+    out = np.zeros(len(places), rg.PLACE_AFFINE_DTYPE)
+    out["glyph"], out["m"] = places["glyph"], m
+    first = runs["first"].astype(np.int64)
+    pen0 = np.repeat(places["pen_x64"][first], runs["count"].astype(np.int64))
+    p = (places["pen_x64"] - pen0).astype(np.float64)                        # along the baseline, 1/64 pixel
+    px, py = np.floor(c * p + 0.5).astype(np.int64), np.floor(-sn * p + 0.5).astype(np.int64)
+    box = gs.boxes[places["glyph"]].astype(f)
+    xs, ys = box[:, [0, 0, 2, 2]], box[:, [1, 3, 1, 3]]
+    u = (m[0] * xs).astype(f) + (m[1] * ys).astype(f)
+    v = (m[2] * xs).astype(f) + (m[3] * ys).astype(f)
+    mnx, mxx = np.floor(u.min(1)).astype(np.int64), np.ceil(u.max(1)).astype(np.int64)
+    mny, mxy = np.floor(v.min(1)).astype(np.int64), np.ceil(v.max(1)).astype(np.int64)
+    x0, y0 = (px >> 6) + mnx, (py >> 6) - mxy
+    x1, y1 = x0 + (mxx - mnx + 1 + ((px & 63) != 0)), y0 + (mxy - mny + 1 + ((py & 63) != 0))
+    left, top = np.minimum.reduceat(x0, first), np.minimum.reduceat(y0, first)
+    w, h = np.maximum.reduceat(x1, first) - left, np.maximum.reduceat(y1, first) - top
+    cnt = runs["count"].astype(np.int64)
+    out["pen_x64"], out["pen_y64"] = px - 64 * np.repeat(left, cnt), py - 64 * np.repeat(top, cnt)
+    rows, x, y, shelf = [], 0, 0, 0
+    for r in range(len(runs)):
+        if x + int(w[r]) > width:
+            x, y, shelf = 0, y + shelf, 0
+        rows.append((int(first[r]), int(cnt[r]), int(w[r]), int(h[r]), x, y, 1.0))
+        x, shelf = x + int(w[r]), max(shelf, int(h[r]))
+    return out, rg.make_runs(rows), (y + shelf, min(width, max(int(w.max()), max(r[4] + r[2] for r in rows))))
+
+
+def affine(ctx, args):
+    """--affine: (a) the _ex plan, (b)-(e) the affine plan at 0, 5, 45 and 90 degrees; coverage; alternated, --repeats times"""
+    import torch
+    ns, fill = args.samples, fr.FR_FILL_CONSISTENT if args.fill else 0
+    med = lambda v: sorted(v)[len(v) // 2]
+    for fi, name in enumerate(["DejaVuSans.ttf", "DejaVuSerif-Italic.ttf"]):
+        font = load_font(name, allow_hinted=True)
+        for size in (16, 32):
+            gs, places, runs, shape, _, _, _ = workload(font, args.lines, args.chars, size, seed=100 * fi + size)
+            ex = rg.make_places_ex([(int(p["glyph"]), int(p["pen_x64"]), 64 * int(p["pen_y"]), 0.0, 0.0) for p in places])
+            dgs = fr.DeviceGlyphSet(ctx, gs)
+            forms = {"a": (ex, runs, shape)}
+            for key, angle in (("b", 0), ("c", 5), ("d", 45), ("e", 90)):
+                forms[key] = rotated_runs(gs, places, runs, runs[0]["scale"], angle)
+            plans = {k: fr.TextPlan(dgs, pl, rn, fr.FR_COVERAGE_U8, ns, fr.FR_SAMPLE_CENTER, fill) for k, (pl, rn, _) in forms.items()}
+            bufs = {k: torch.zeros(sh, dtype=torch.uint8, device="cuda:0") for k, (_, _, sh) in forms.items()}
+            torch.cuda.synchronize()
+            ms = {k: [] for k in plans}
+            for _ in range(args.repeats):
+                for k, plan in plans.items():
+                    ms[k].append(timed(plan, bufs[k], forms[k][2], args.steps, args.warmup))
+            out = {"case": "affine", "font": name, "font_size": size, "lines": args.lines, "chars": args.chars, "samples": ns * ns,
+                   "instances": int(len(places)), "steps": args.steps, "repeats": args.repeats}
+            a = med(ms["a"])
+            for k, plan in plans.items():
+                out.update({f"{k}_ms": round(med(ms[k]), 4), f"{k}_min_ms": round(min(ms[k]), 4), f"{k}_max_ms": round(max(ms[k]), 4),
+                            f"{k}_run_mpixel": round(plan.pixels / 1e6, 1), f"{k}_lit_fraction": round(int(torch.count_nonzero(bufs[k])) / bufs[k].numel(), 4)})
+                if k != "a":
+                    out[f"{k}_over_a"] = round(med(ms[k]) / a, 2)
+            out.update({"a_plan": plans["a"].describe(), "e_plan": plans["e"].describe()})
+            for plan in plans.values():
+                plan.close()
+            del bufs
             dgs.close()
             print(json.dumps(out), flush=True)
 
