@@ -8,6 +8,7 @@
 #include "fr_device.hpp"
 #include "fr_srgb.hpp"
 #include "fr_text.hpp"
+#include "fr_text_plan.hpp"
 
 #include <cmath>
 #include <cstdarg>
@@ -109,6 +110,13 @@ struct fr_glyphset {
     std::vector<int16_t> h_box;                 // fr_glyphset_set_boxes: Glyph.box per glyph (x_min, y_min, x_max, y_max); empty until set
 };
 
+// the placement form of a text plan: fr_glyph_place (TextInst, the text_* kernels), fr_glyph_place_ex (TextInstEx,
+// text_place_*) or fr_glyph_place_affine (TextInstAffine, the text_affine_* kernels of fr_text_affine.hip)
+enum TextForm { TEXT_PLAIN, TEXT_EX, TEXT_AFFINE };
+static constexpr TextForm text_form_of(const fr_glyph_place *) { return TEXT_PLAIN; }
+static constexpr TextForm text_form_of(const fr_glyph_place_ex *) { return TEXT_EX; }
+static constexpr TextForm text_form_of(const fr_glyph_place_affine *) { return TEXT_AFFINE; }
+
 struct fr_plan {
     fr_ctx *ctx = nullptr;
     const fr_glyphset *gs = nullptr;
@@ -148,11 +156,8 @@ struct fr_plan {
     int blend = 0;                     // (rgba) 1 unless every placement colour is opaque
     fr::TextTile *d_tiles = nullptr;
     fr::TextRun *d_runs = nullptr;
-    fr::TextInst *d_insts = nullptr;
-    bool place_ex = false;             // fr_text_plan_create_ex / _rgba_ex: d_insts_ex and the text_place_* kernels of fr_text.hip
-    fr::TextInstEx *d_insts_ex = nullptr;
-    bool place_affine = false;         // fr_text_plan_create_affine / _rgba_affine: d_insts_affine and the text_affine_* kernels
-    fr::TextInstAffine *d_insts_affine = nullptr;   // of fr_text_affine.hip
+    TextForm text_form = TEXT_PLAIN;   // the placement form: which record d_insts holds and which kernels read it
+    void *d_insts = nullptr;           // TextInst, TextInstEx or TextInstAffine
     uint32_t *d_tlist = nullptr, *d_tglyphs = nullptr, *d_trec_count = nullptr;
     fr::Rec *d_trecs = nullptr;
     uint32_t n_tiles = 0, n_insts = 0, n_tglyphs = 0;
@@ -160,23 +165,33 @@ struct fr_plan {
 
 template <class T> static void dfree(T *&p) { if (p) { (void)hipFree(p); p = nullptr; } }
 
-// launches the text kernel of a plan over n_tiles tiles for one placement form (ARGS: fr::TextArgs over the plan's TextInst
-// table, fr::TextPlaceArgs over its TextInstEx table, or fr::TextAffineArgs over its TextInstAffine table); n_tiles = 0: only names it, as rocprofv3 does, into name[name_cap]
+// launches the text kernel of a plan over n_tiles tiles for one placement form (ARGS: fr::TextArgs, fr::TextPlaceArgs or
+// fr::TextAffineArgs, over the plan's instance table of that form); n_tiles = 0: only names it, as rocprofv3 does, into
+// name[name_cap]
 template <class ARGS>
 static hipError_t text_args_launch(const fr_plan *plan, void *out_dev, size_t out_stride, uint32_t n_tiles, char *name = nullptr,
                                    size_t name_cap = 0)
 {
     ARGS a;
     a.tiles = plan->d_tiles; a.runs = plan->d_runs; a.list = plan->d_tlist;
-    if constexpr (std::is_same_v<ARGS, fr::TextAffineArgs>) a.insts = plan->d_insts_affine;
-    else if constexpr (std::is_same_v<ARGS, fr::TextPlaceArgs>) a.insts = plan->d_insts_ex;
-    else a.insts = plan->d_insts;
+    a.insts = static_cast<decltype(a.insts)>(plan->d_insts);
     a.recs = plan->d_trecs; a.rec_count = plan->d_trec_count;
     a.out = static_cast<uint8_t *>(out_dev);
     a.out_stride = out_stride;
     a.phase_center = plan->params.sample_phase == FR_SAMPLE_CENTER ? 1 : 0;
     return fr::launch_text(a, plan->params.samples_per_axis, (plan->flags & FR_FILL_CONSISTENT) ? 1 : 0, plan->rgba, plan->blend,
                            plan->srgb, plan->load, n_tiles, plan->ctx->stream, name, name_cap);
+}
+
+// the same for the plan's own form: what a render launches (text_launch) and what fr_plan_describe names
+static hipError_t text_plan_launch(const fr_plan *plan, void *out_dev, size_t out_stride, uint32_t n_tiles, char *name = nullptr,
+                                   size_t name_cap = 0)
+{
+    switch (plan->text_form) {
+    case TEXT_AFFINE: return text_args_launch<fr::TextAffineArgs>(plan, out_dev, out_stride, n_tiles, name, name_cap);
+    case TEXT_EX: return text_args_launch<fr::TextPlaceArgs>(plan, out_dev, out_stride, n_tiles, name, name_cap);
+    default: return text_args_launch<fr::TextArgs>(plan, out_dev, out_stride, n_tiles, name, name_cap);
+    }
 }
 
 extern "C" {
@@ -565,7 +580,7 @@ void fr_plan_destroy(fr_plan *plan)
     (void)hipSetDevice(plan->ctx->device);
     (void)hipStreamSynchronize(plan->ctx->stream);
     dfree(plan->d_jobs); dfree(plan->d_job_seg); dfree(plan->d_large); dfree(plan->d_bits); dfree(plan->d_job_bits);
-    dfree(plan->d_tiles); dfree(plan->d_runs); dfree(plan->d_insts); dfree(plan->d_insts_ex); dfree(plan->d_insts_affine); dfree(plan->d_tlist); dfree(plan->d_tglyphs);
+    dfree(plan->d_tiles); dfree(plan->d_runs); dfree(plan->d_insts); dfree(plan->d_tlist); dfree(plan->d_tglyphs);
     dfree(plan->d_trec_count); dfree(plan->d_trecs);
     if (plan->ev0) (void)hipEventDestroy(plan->ev0);
     if (plan->ev1) (void)hipEventDestroy(plan->ev1);
@@ -733,20 +748,6 @@ int fr_plan_create_ex(fr_ctx *ctx, const fr_glyphset *gs, const fr_job *jobs, ui
 }
 
 // ---- text runs (include/fr_raster.h) -----------------------------------------------------------
-// the 4 bytes R G B A as one little-endian word, R in the low byte (fr_text.hpp: TextInst::rgba, TextRun::clear); bgra
-// (FR_TEXT_BGRA): B in the low byte, so that the kernels, which treat R and B alike, write B G R A
-static uint32_t rgba_word(const uint8_t *c, bool bgra)
-{
-    return (uint32_t)c[bgra ? 2 : 0] | (uint32_t)c[1] << 8 | (uint32_t)c[bgra ? 0 : 2] << 16 | (uint32_t)c[3] << 24;
-}
-
-// an sRGB text plan's linear colour of a packed word (fr_text.hpp: TextInst::pad, TextRun::pad; fr_srgb.hpp)
-static void linear_words(uint32_t w, uint32_t pad[2])
-{
-    pad[0] = (uint32_t)fr::SRGB_D[w & 0xffu] | (uint32_t)fr::SRGB_D[(w >> 8) & 0xffu] << 16;
-    pad[1] = fr::SRGB_D[(w >> 16) & 0xffu];
-}
-
 int fr_glyphset_set_boxes(fr_glyphset *gs, const int16_t *boxes)
 {
     if (!gs || (gs->n_glyphs && !boxes)) return fail(FR_E_INVALID, "fr_glyphset_set_boxes: NULL argument");
@@ -757,45 +758,55 @@ int fr_glyphset_set_boxes(fr_glyphset *gs, const int16_t *boxes)
     return FR_OK;
 }
 
-// D = xx*yy - xy*yx of an fr_glyph_place_affine in binary64: two rounded products and one rounded difference.  Not
-// inlined and compiled without contraction, so that no fused multiply-add can take the place of a product's rounding.
-#pragma clang fp contract(off)
-__attribute__((noinline)) static double affine_det(double xx, double xy, double yx, double yy)
-{
-    volatile double a = xx * yy, b = xy * yx;
-    return a - b;
-}
+}  // extern "C"
 
-// the inverse of an fr_glyph_place_affine's matrix (include/fr_raster.h) -> q[4]; FR_OK, or the code the header names
-static int affine_inverse(const float m[4], float q[4])
+// uploads the tables of text_plan_tables (fr_text_plan.hpp) and fills the text fields of a plan that its caller destroys on
+// failure
+template <class PLACE>
+static int text_plan_upload(const char *fn, fr_plan *p, const fr::TextPlanTables<PLACE> &t)
 {
-    for (int i = 0; i < 4; ++i)
-        if (!std::isfinite(m[i])) return FR_E_INVALID;
-    const double D = affine_det((double)m[0], (double)m[1], (double)m[2], (double)m[3]);
-    if (D == 0.0) return FR_E_INVALID;
-    for (int i = 0; i < 4; ++i)
-        if (std::fabs(m[i]) > 1048576.0f) return FR_E_UNSUPPORTED;
-    q[0] = (float)((double)m[3] / D);
-    q[1] = (float)(-(double)m[1] / D);
-    q[2] = (float)(-(double)m[2] / D);
-    q[3] = (float)((double)m[0] / D);
-    for (int i = 0; i < 4; ++i)
-        if (!(std::fabs(q[i]) <= 1048576.0f)) return FR_E_UNSUPPORTED;
+    fr_ctx *ctx = p->ctx;
+    const fr_glyphset *gs = p->gs;
+    p->text_form = text_form_of((const PLACE *)nullptr);
+    p->blend = t.blend;
+    p->pixels = t.pixels; p->need_cols = t.need_cols; p->need_rows = t.need_rows;
+    p->n_tiles = (uint32_t)t.tiles.size(); p->n_insts = (uint32_t)t.insts.size(); p->n_tglyphs = (uint32_t)t.glyphs.size();
+    hipStream_t st = ctx->stream;
+    hipError_t e = hipSetDevice(ctx->device);
+    auto upload = [&](auto *&dst, const auto &v) {
+        using T = typename std::remove_reference<decltype(v)>::type::value_type;
+        if (e != hipSuccess || v.empty()) return;
+        e = hipMalloc(&dst, v.size() * sizeof(T));
+        if (e == hipSuccess) e = hipMemcpyAsync(dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, st);
+    };
+    upload(p->d_tiles, t.tiles);
+    upload(p->d_runs, t.runs);
+    upload(p->d_insts, t.insts);
+    upload(p->d_tlist, t.list);
+    upload(p->d_tglyphs, t.glyphs);
+    if (e == hipSuccess && p->n_tglyphs) e = hipMalloc(&p->d_trecs, 2 * (size_t)gs->n_seg * sizeof(fr::Rec));
+    if (e == hipSuccess && p->n_tglyphs) e = hipMalloc(&p->d_trec_count, ((size_t)gs->n_glyphs + 1) * 4);
+    if (e == hipSuccess && p->n_tglyphs) e = hipMemsetAsync(p->d_trec_count, 0, ((size_t)gs->n_glyphs + 1) * 4, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipEventCreate(&p->ev0);
+    if (e == hipSuccess) e = hipEventCreate(&p->ev1);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? FR_E_NOMEM : FR_E_HIP, "%s: %s", fn, hipGetErrorString(e));
     return FR_OK;
 }
 
-// fr_text_plan_create and fr_text_plan_create_rgba: one set of checks and tables.  rgba: place_rgba / run_clear_rgba are
-// the colours (4 bytes each), the mode must be FR_COVERAGE_U8, the flags may add FR_TEXT_SRGB, FR_TEXT_BGRA and
-// FR_TEXT_LOAD, and the plan renders with text_rgba_kernel (text_srgb_kernel under FR_TEXT_SRGB; their _load_ forms
-// under FR_TEXT_LOAD, which ignores run_clear_rgba and launches only the tiles some instance meets).
-// The placements are places (fr_glyph_place) or, when that is NULL and ex is set, places_ex (fr_glyph_place_ex: own
-// scale, slant, sub-pixel baseline; TextInstEx and the text_place_* kernels of fr_text.hip), or, when places_af is given,
-// those (fr_glyph_place_affine: a 2 x 2 matrix; TextInstAffine and the text_affine_* kernels of fr_text_affine.hip; ex
-// is then set too, for the 1/64-pixel pen): only the cell differs.
-static int text_plan_build(const char *fn, fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place *places,
-                           const fr_glyph_place_ex *places_ex, bool ex, const uint8_t *place_rgba, uint32_t n_places, const fr_text_run *runs,
-                           const uint8_t *run_clear_rgba, uint32_t n_runs, const fr_raster_params *params, uint32_t flags,
-                           bool rgba, fr_plan **out, const fr_glyph_place_affine *places_af = nullptr, bool af = false)
+// The six text entry points: the checks that need the context and the raster parameters, then the tables from
+// text_plan_tables (fr_text_plan.cpp: plain host code, every check of the placements and runs and all the arithmetic),
+// then text_plan_upload.  PLACE is the placement form: fr_glyph_place (TextInst, the text_* kernels of fr_text.hip),
+// fr_glyph_place_ex (own scale, slant and sub-pixel baseline: TextInstEx, text_place_*) or fr_glyph_place_affine (a 2 x 2
+// matrix: TextInstAffine, the text_affine_* kernels of fr_text_affine.hip).  rgba: place_rgba / run_clear_rgba are the
+// colours (4 bytes each), the mode must be FR_COVERAGE_U8, the flags may add FR_TEXT_SRGB, FR_TEXT_BGRA and
+// FR_TEXT_LOAD (which ignores run_clear_rgba and launches only the tiles some instance meets).
+// (The parameter checks are not check_params: that one answers FR_E_INVALID with other words for n != 1 outside
+// coverage, and looks at n before the phase.)
+template <class PLACE>
+static int text_plan_create(const char *fn, fr_ctx *ctx, const fr_glyphset *gs, const PLACE *places, const uint8_t *place_rgba,
+                            uint32_t n_places, const fr_text_run *runs, const uint8_t *run_clear_rgba, uint32_t n_runs,
+                            const fr_raster_params *params, uint32_t flags, bool rgba, fr_plan **out)
 {
     if (!ctx || !gs || !out) return fail(FR_E_INVALID, "%s: NULL argument", fn);
     *out = nullptr;
@@ -806,7 +817,6 @@ static int text_plan_build(const char *fn, fr_ctx *ctx, const fr_glyphset *gs, c
     if (params->sample_phase != FR_SAMPLE_CORNER && params->sample_phase != FR_SAMPLE_CENTER)
         return fail(FR_E_INVALID, "unknown sample_phase %d", params->sample_phase);
     const int n = params->samples_per_axis;
-    const bool srgb = (flags & FR_TEXT_SRGB) != 0, bgra = (flags & FR_TEXT_BGRA) != 0, load = (flags & FR_TEXT_LOAD) != 0;
     if (rgba) {
         if (params->mode != FR_COVERAGE_U8)
             return fail(FR_E_UNSUPPORTED, "RGBA text runs: mode %d (only FR_COVERAGE_U8)", params->mode);
@@ -817,254 +827,69 @@ static int text_plan_build(const char *fn, fr_ctx *ctx, const fr_glyphset *gs, c
         if (params->mode == FR_COVERAGE_U8 ? (n != 1 && n != 2 && n != 4) : n != 1)
             return fail(FR_E_UNSUPPORTED, "text runs: samples_per_axis %d with mode %d", n, params->mode);
     }
-    if (n_places && !(af ? (const void *)places_af : ex ? (const void *)places_ex : (const void *)places))
-        return fail(FR_E_INVALID, "places is NULL");
-    if (n_runs && !runs) return fail(FR_E_INVALID, "runs is NULL");
-    if (rgba && n_places && !place_rgba) return fail(FR_E_INVALID, "place_rgba is NULL");
-    if (rgba && !load && n_runs && !run_clear_rgba) return fail(FR_E_INVALID, "run_clear_rgba is NULL");
-    if (gs->n_glyphs && gs->h_box.empty()) return fail(FR_E_INVALID, "text runs need the glyph boxes: fr_glyphset_set_boxes");
-    const int64_t LIM = (int64_t)1 << 22;
-    uint64_t pixels = 0, need_cols = 0, need_rows = 0, n_tiles = 0;
-    for (uint32_t r = 0; r < n_runs; ++r) {
-        const fr_text_run &rn = runs[r];
-        if ((uint64_t)rn.first + rn.count > n_places) return fail(FR_E_INVALID, "run %u: places %u + %u of %u", r, rn.first, rn.count, n_places);
-        if (!(rn.scale > 0.0f) || !std::isfinite(rn.scale)) return fail(FR_E_INVALID, "run %u: scale must be finite and > 0", r);
-        if (rn.scale < 9.5367431640625e-07f || rn.scale > 1048576.0f) return fail(FR_E_UNSUPPORTED, "run %u: scale outside [2^-20, 2^20]", r);
-        if (rn.w > 65535u || rn.h > 65535u) return fail(FR_E_UNSUPPORTED, "run %u: larger than 65535", r);
-        for (uint32_t k = rn.first; k < rn.first + rn.count; ++k) {
-            const uint32_t glyph = af ? places_af[k].glyph : ex ? places_ex[k].glyph : places[k].glyph;
-            const int32_t px64 = af ? places_af[k].pen_x64 : ex ? places_ex[k].pen_x64 : places[k].pen_x64;
-            const int32_t py = af ? places_af[k].pen_y64 >> 6 : ex ? places_ex[k].pen_y64 >> 6 : places[k].pen_y;
-            if (glyph >= gs->n_glyphs) return fail(FR_E_INVALID, "place %u: glyph %u of %u", k, glyph, gs->n_glyphs);
-            if ((px64 >> 6) < -LIM || (px64 >> 6) > LIM || py < -LIM || py > LIM)
-                return fail(FR_E_UNSUPPORTED, "place %u: pen beyond +-2^22 pixels", k);
-            if (af) {
-                float q[4];
-                const int frc = affine_inverse(places_af[k].m, q);
-                if (frc == FR_E_INVALID) return fail(frc, "place %u: matrix not finite or singular", k);
-                if (frc != FR_OK) return fail(frc, "place %u: matrix or its inverse beyond 2^20", k);
-                continue;
-            }
-            if (!ex) continue;
-            const float ps = places_ex[k].scale, sl = places_ex[k].slant;
-            if (!(ps >= 0.0f) || !std::isfinite(ps)) return fail(FR_E_INVALID, "place %u: scale must be 0, or finite and > 0", k);
-            if (ps != 0.0f && (ps < 9.5367431640625e-07f || ps > 1048576.0f))
-                return fail(FR_E_UNSUPPORTED, "place %u: scale outside [2^-20, 2^20]", k);
-            if (!std::isfinite(sl)) return fail(FR_E_INVALID, "place %u: slant must be finite", k);
-            if (std::fabs(sl) > 4.0f) return fail(FR_E_UNSUPPORTED, "place %u: |slant| above 4", k);
-        }
-        pixels += (uint64_t)rn.w * rn.h;
-        if (rn.w && rn.h) {
-            need_cols = std::max<uint64_t>(need_cols, (uint64_t)rn.out_x + rn.w);
-            need_rows = std::max<uint64_t>(need_rows, (uint64_t)rn.out_y + rn.h);
-            n_tiles += (uint64_t)((rn.w + fr::TEXT_TILE_W - 1) / fr::TEXT_TILE_W) * ((rn.h + fr::TEXT_TILE_H - 1) / fr::TEXT_TILE_H);
-        }
-    }
-    if (n_tiles > 0x7fffffffull) return fail(FR_E_UNSUPPORTED, "text plan needs more than 2^31 workgroups; split it");
-    // runs own their rectangles: no two may overlap (sweep down the rows)
-    {
-        std::vector<uint32_t> ord;
-        for (uint32_t r = 0; r < n_runs; ++r)
-            if (runs[r].w && runs[r].h) ord.push_back(r);
-        std::sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return runs[a].out_y < runs[b].out_y; });
-        for (size_t i = 0; i < ord.size(); ++i) {
-            const fr_text_run &A = runs[ord[i]];
-            for (size_t j = i + 1; j < ord.size() && runs[ord[j]].out_y < (uint64_t)A.out_y + A.h; ++j) {
-                const fr_text_run &B = runs[ord[j]];
-                if (B.out_x < (uint64_t)A.out_x + A.w && A.out_x < (uint64_t)B.out_x + B.w)
-                    return fail(FR_E_INVALID, "runs %u and %u overlap", ord[i], ord[j]);
-            }
-        }
-    }
-    // instances: each placement's cell (renderGlyph's grid at the run's scale, one column wider when fx != 0) clipped to its
-    // run; tiles: every 64 x 16 tile of every run, with the instances whose clipped cell meets it (counting sort by tile)
-    std::vector<fr::TextRun> trun(n_runs);
-    std::vector<fr::TextTile> tiles((size_t)n_tiles);
-    std::vector<fr::TextInst> insts;
-    std::vector<fr::TextInstEx> insts_ex;
-    std::vector<fr::TextInstAffine> insts_af;
-    std::vector<std::pair<uint32_t, uint32_t>> hits;            // (tile, instance)
-    std::vector<uint8_t> used(gs->n_glyphs, 0);
-    uint32_t tbase = 0;
-    for (uint32_t r = 0; r < n_runs; ++r) {
-        const fr_text_run &rn = runs[r];
-        const bool clear = rgba && !load;                                                  // (FR_TEXT_LOAD: no clear colour)
-        trun[r] = fr::TextRun{rn.w, rn.h, rn.out_x, rn.out_y, rn.scale, clear ? rgba_word(run_clear_rgba + 4 * (size_t)r, bgra) : 0u, {0, 0}};
-        if (srgb) linear_words(trun[r].clear, trun[r].pad);
-        if (!rn.w || !rn.h) continue;
-        const uint32_t tx = (rn.w + fr::TEXT_TILE_W - 1) / fr::TEXT_TILE_W, ty = (rn.h + fr::TEXT_TILE_H - 1) / fr::TEXT_TILE_H;
-        for (uint32_t y = 0; y < ty; ++y)
-            for (uint32_t x = 0; x < tx; ++x)
-                tiles[tbase + y * tx + x] = fr::TextTile{r, x * fr::TEXT_TILE_W, y * fr::TEXT_TILE_H, 0, 0, {0, 0, 0}};
-        for (uint32_t k = rn.first; k < rn.first + rn.count; ++k) {
-            const uint32_t g = af ? places_af[k].glyph : ex ? places_ex[k].glyph : places[k].glyph;
-            const int32_t pen_x64 = af ? places_af[k].pen_x64 : ex ? places_ex[k].pen_x64 : places[k].pen_x64;
-            const int32_t pen_y64 = af ? places_af[k].pen_y64 : ex ? places_ex[k].pen_y64 : 0;
-            const int32_t pen_y = ex ? pen_y64 >> 6 : places[k].pen_y;                          // iy
-            const uint32_t fy64 = ex ? (uint32_t)pen_y64 & 63u : 0u;
-            const float s = ex && !af && places_ex[k].scale != 0.0f ? places_ex[k].scale : rn.scale;
-            const float sl = ex && !af ? places_ex[k].slant : 0.0f;
-            if (gs->h_glyph_seg_start[g + 1] == gs->h_glyph_seg_start[g]) continue;        // no segment: no winding anywhere
-            const int16_t *b = &gs->h_box[4 * (size_t)g];
-            // render_glyph.zig:13-17 in binary32, as fr_render_glyph_dims / fr_atlas_layout
-            // (fr_glyph_place_ex: the box sheared by the slant, lo = min(x_min + k*y_min, x_min + k*y_max), hi likewise,
-            // one rounding per operation; with k = 0 lo = x_min and hi = x_max.  One more row when fy != 0)
-            const float ky0 = sl * (float)b[1], ky1 = sl * (float)b[3];
-            const float lo = ex ? std::min((float)b[0] + ky0, (float)b[0] + ky1) : (float)b[0];
-            const float hi = ex ? std::max((float)b[2] + ky0, (float)b[2] + ky1) : (float)b[2];
-            int64_t mnx = (int64_t)std::floor(lo * s), mny = (int64_t)std::floor((float)b[1] * s);
-            int64_t mxx = (int64_t)std::ceil(hi * s), mxy = (int64_t)std::ceil((float)b[3] * s);
-            float q[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-            if (af) {
-                // fr_glyph_place_affine: the box's four corners through the matrix, one rounding per operation (the products
-                // are stored before they are added: nothing here may be contracted)
-                const float *m = places_af[k].m;
-                (void)affine_inverse(m, q);                                              // (checked above)
-                float ulo = 0, uhi = 0, vlo = 0, vhi = 0;
-                for (int c = 0; c < 4; ++c) {
-                    const float x = (float)b[(c & 1) ? 2 : 0], y = (float)b[(c & 2) ? 3 : 1];
-                    volatile float ux = m[0] * x, uy = m[1] * y, vx = m[2] * x, vy = m[3] * y;
-                    const float u = ux + uy, v = vx + vy;
-                    ulo = c ? std::min(ulo, u) : u; uhi = c ? std::max(uhi, u) : u;
-                    vlo = c ? std::min(vlo, v) : v; vhi = c ? std::max(vhi, v) : v;
-                }
-                mnx = (int64_t)std::floor(ulo); mxx = (int64_t)std::ceil(uhi);
-                mny = (int64_t)std::floor(vlo); mxy = (int64_t)std::ceil(vhi);
-            }
-            const int64_t ix = pen_x64 >> 6;
-            const uint32_t fx64 = (uint32_t)pen_x64 & 63u;
-            const int64_t cw = mxx - mnx + 1 + (fx64 ? 1 : 0), ch = mxy - mny + 1 + (fy64 ? 1 : 0);
-            if (mnx < -LIM || mxx > LIM || mny < -LIM || mxy > LIM || cw > 65535 || ch > 65535)
-                return fail(FR_E_UNSUPPORTED, "place %u: cell beyond +-2^22 pixels or larger than 65535", k);
-            const int64_t c0 = ix + mnx, r0 = (int64_t)pen_y - mxy;
-            const int64_t x0 = std::max<int64_t>(c0, 0), x1 = std::min<int64_t>(c0 + cw, rn.w);
-            const int64_t y0 = std::max<int64_t>(r0, 0), y1 = std::min<int64_t>(r0 + ch, rn.h);
-            if (x0 >= x1 || y0 >= y1) continue;                                            // clipped away
-            const uint32_t id = (uint32_t)(af ? insts_af.size() : ex ? insts_ex.size() : insts.size());
-            const uint32_t word = rgba ? rgba_word(place_rgba + 4 * (size_t)k, bgra) : 0u;
-            if (af) {
-                insts_af.push_back(fr::TextInstAffine{(int32_t)ix, pen_y, (int32_t)x0, (int32_t)x1, (int32_t)y0, (int32_t)y1, g,
-                                                      2u * gs->h_glyph_seg_start[g], fx64, word, {0, 0}, fy64, q[0], q[1], q[2], q[3],
-                                                      {0u, 0u, 0u}});
-                if (srgb) linear_words(word, insts_af.back().pad);
-            } else if (ex) {
-                insts_ex.push_back(fr::TextInstEx{(int32_t)ix, pen_y, (int32_t)x0, (int32_t)x1, (int32_t)y0, (int32_t)y1, g,
-                                                  2u * gs->h_glyph_seg_start[g], fx64, word, {0, 0}, fy64, s, sl, 0u});
-                if (srgb) linear_words(word, insts_ex.back().pad);
-            } else {
-                insts.push_back(fr::TextInst{(int32_t)ix, pen_y, (int32_t)x0, (int32_t)x1, (int32_t)y0, (int32_t)y1, g,
-                                             2u * gs->h_glyph_seg_start[g], fx64, word, {0, 0}});
-                if (srgb) linear_words(word, insts.back().pad);
-            }
-            used[g] = 1;
-            for (int64_t y = y0 / fr::TEXT_TILE_H; y <= (y1 - 1) / fr::TEXT_TILE_H; ++y)
-                for (int64_t x = x0 / fr::TEXT_TILE_W; x <= (x1 - 1) / fr::TEXT_TILE_W; ++x)
-                    hits.emplace_back(tbase + (uint32_t)(y * tx + x), id);
-        }
-        tbase += tx * ty;
-    }
-    if (hits.size() > 0xffffffffull) return fail(FR_E_UNSUPPORTED, "text plan: too many tile / instance pairs; split it");
-    std::vector<uint32_t> list(hits.size());
-    for (const auto &h : hits) ++tiles[h.first].lend;
-    uint32_t at = 0;
-    for (auto &t : tiles) { t.lbeg = at; at += t.lend; t.lend = t.lbeg; }
-    for (const auto &h : hits) list[tiles[h.first].lend++] = h.second;
-    if (load)                          // FR_TEXT_LOAD: a tile no instance meets leaves its pixels as they are: not launched
-        tiles.erase(std::remove_if(tiles.begin(), tiles.end(), [](const fr::TextTile &t) { return t.lbeg == t.lend; }), tiles.end());
-    std::vector<uint32_t> glyphs;
-    for (uint32_t g = 0; g < gs->n_glyphs; ++g)
-        if (used[g]) glyphs.push_back(g);
+    fr::TextPlanIn in{};
+    in.runs = runs; in.n_runs = n_runs; in.n_places = n_places;
+    in.place_rgba = place_rgba; in.run_clear_rgba = run_clear_rgba;
+    in.rgba = rgba; in.flags = flags;
+    in.boxes = gs->h_box.empty() ? nullptr : gs->h_box.data();
+    in.glyph_seg_start = gs->h_glyph_seg_start.data(); in.n_glyphs = gs->n_glyphs;
+    fr::TextPlanTables<PLACE> t;
+    if (const int rc = fr::text_plan_tables(in, places, t)) return rc;
 
     fr_plan *p = new (std::nothrow) fr_plan;
     if (!p) return fail(FR_E_NOMEM, "%s: host allocation", fn);
     p->ctx = ctx; p->gs = gs; p->params = *params; p->flags = flags; p->text = true;
     p->rgba = rgba;
-    p->srgb = srgb;
-    p->load = load;
-    p->place_ex = ex && !af;
-    p->place_affine = af;
-    for (uint32_t k = 0; rgba && k < n_places; ++k)
-        if (place_rgba[4 * (size_t)k + 3] != 255) { p->blend = 1; break; }
-    p->pixels = pixels; p->need_cols = need_cols; p->need_rows = need_rows;
-    p->n_tiles = (uint32_t)tiles.size(); p->n_insts = (uint32_t)(af ? insts_af.size() : ex ? insts_ex.size() : insts.size()); p->n_tglyphs = (uint32_t)glyphs.size();
-    hipStream_t st = ctx->stream;
-    hipError_t e = hipSetDevice(ctx->device);
-    auto upload = [&](auto *&dst, const auto &v) {
-        using T = typename std::remove_reference<decltype(v)>::type::value_type;
-        if (e != hipSuccess || v.empty()) return;
-        e = hipMalloc(&dst, v.size() * sizeof(T));
-        if (e == hipSuccess) e = hipMemcpyAsync(dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, st);
-    };
-    upload(p->d_tiles, tiles);
-    upload(p->d_runs, trun);
-    upload(p->d_insts, insts);
-    upload(p->d_insts_ex, insts_ex);
-    upload(p->d_insts_affine, insts_af);
-    upload(p->d_tlist, list);
-    upload(p->d_tglyphs, glyphs);
-    if (e == hipSuccess && p->n_tglyphs) e = hipMalloc(&p->d_trecs, 2 * (size_t)gs->n_seg * sizeof(fr::Rec));
-    if (e == hipSuccess && p->n_tglyphs) e = hipMalloc(&p->d_trec_count, ((size_t)gs->n_glyphs + 1) * 4);
-    if (e == hipSuccess && p->n_tglyphs) e = hipMemsetAsync(p->d_trec_count, 0, ((size_t)gs->n_glyphs + 1) * 4, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = hipEventCreate(&p->ev0);
-    if (e == hipSuccess) e = hipEventCreate(&p->ev1);
-    if (e != hipSuccess) {
+    p->srgb = (flags & FR_TEXT_SRGB) != 0;
+    p->load = (flags & FR_TEXT_LOAD) != 0;
+    if (const int rc = text_plan_upload(fn, p, t)) {
         fr_plan_destroy(p);
-        return fail(e == hipErrorOutOfMemory ? FR_E_NOMEM : FR_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+        return rc;
     }
     *out = p;
     return FR_OK;
 }
 
+extern "C" {
+
 int fr_text_plan_create(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place *places, uint32_t n_places,
                         const fr_text_run *runs, uint32_t n_runs, const fr_raster_params *params, uint32_t flags,
                         fr_plan **out)
 {
-    return text_plan_build("fr_text_plan_create", ctx, gs, places, nullptr, false, nullptr, n_places, runs, nullptr, n_runs, params, flags,
-                           false, out);
+    return text_plan_create("fr_text_plan_create", ctx, gs, places, nullptr, n_places, runs, nullptr, n_runs, params, flags, false, out);
 }
-
 int fr_text_plan_create_rgba(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place *places, const uint8_t *place_rgba,
                              uint32_t n_places, const fr_text_run *runs, const uint8_t *run_clear_rgba, uint32_t n_runs,
                              const fr_raster_params *params, uint32_t flags, fr_plan **out)
 {
-    return text_plan_build("fr_text_plan_create_rgba", ctx, gs, places, nullptr, false, place_rgba, n_places, runs, run_clear_rgba,
-                           n_runs, params, flags, true, out);
+    return text_plan_create("fr_text_plan_create_rgba", ctx, gs, places, place_rgba, n_places, runs, run_clear_rgba, n_runs, params, flags, true, out);
 }
-
 // the same two for fr_glyph_place_ex placements: own scale, slant and sub-pixel baseline per placement (the text_place_* kernels)
 int fr_text_plan_create_ex(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place_ex *places, uint32_t n_places,
                            const fr_text_run *runs, uint32_t n_runs, const fr_raster_params *params, uint32_t flags,
                            fr_plan **out)
 {
-    return text_plan_build("fr_text_plan_create_ex", ctx, gs, nullptr, places, true, nullptr, n_places, runs, nullptr, n_runs,
-                           params, flags, false, out);
+    return text_plan_create("fr_text_plan_create_ex", ctx, gs, places, nullptr, n_places, runs, nullptr, n_runs, params, flags, false, out);
 }
-
 int fr_text_plan_create_rgba_ex(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place_ex *places, const uint8_t *place_rgba,
                                 uint32_t n_places, const fr_text_run *runs, const uint8_t *run_clear_rgba, uint32_t n_runs,
                                 const fr_raster_params *params, uint32_t flags, fr_plan **out)
 {
-    return text_plan_build("fr_text_plan_create_rgba_ex", ctx, gs, nullptr, places, true, place_rgba, n_places, runs,
-                           run_clear_rgba, n_runs, params, flags, true, out);
+    return text_plan_create("fr_text_plan_create_rgba_ex", ctx, gs, places, place_rgba, n_places, runs, run_clear_rgba, n_runs, params, flags, true, out);
 }
-
 // the same two for fr_glyph_place_affine placements: a 2 x 2 matrix per placement (the text_affine_* kernels)
 int fr_text_plan_create_affine(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place_affine *places, uint32_t n_places,
                                const fr_text_run *runs, uint32_t n_runs, const fr_raster_params *params, uint32_t flags,
                                fr_plan **out)
 {
-    return text_plan_build("fr_text_plan_create_affine", ctx, gs, nullptr, nullptr, true, nullptr, n_places, runs, nullptr, n_runs,
-                           params, flags, false, out, places, true);
+    return text_plan_create("fr_text_plan_create_affine", ctx, gs, places, nullptr, n_places, runs, nullptr, n_runs, params, flags, false, out);
 }
-
 int fr_text_plan_create_rgba_affine(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place_affine *places,
                                     const uint8_t *place_rgba, uint32_t n_places, const fr_text_run *runs,
                                     const uint8_t *run_clear_rgba, uint32_t n_runs, const fr_raster_params *params,
                                     uint32_t flags, fr_plan **out)
 {
-    return text_plan_build("fr_text_plan_create_rgba_affine", ctx, gs, nullptr, nullptr, true, place_rgba, n_places, runs,
-                           run_clear_rgba, n_runs, params, flags, true, out, places, true);
+    return text_plan_create("fr_text_plan_create_rgba_affine", ctx, gs, places, place_rgba, n_places, runs, run_clear_rgba, n_runs, params, flags, true, out);
 }
 
 // the conversions of FR_TEXT_SRGB plans, from the tables text_srgb_kernel reads (fr_srgb.hpp)
@@ -1118,9 +943,7 @@ int fr_plan_describe(const fr_plan *plan, char *buf, size_t cap)
     if (plan->text) {
         if (plan->n_tglyphs) add(fill ? "fr::prepare_fill_kernel" : "fr::prepare_kernel", plan->n_tglyphs);
         name[0] = 0;
-        if (plan->place_affine) (void)text_args_launch<fr::TextAffineArgs>(plan, nullptr, 0, 0u, name, sizeof name);
-        else if (plan->place_ex) (void)text_args_launch<fr::TextPlaceArgs>(plan, nullptr, 0, 0u, name, sizeof name);
-        else (void)text_args_launch<fr::TextArgs>(plan, nullptr, 0, 0u, name, sizeof name);
+        (void)text_plan_launch(plan, nullptr, 0, 0u, name, sizeof name);
         if (plan->n_tiles) add(name, plan->n_insts);
         return FR_OK;
     }
@@ -1182,9 +1005,7 @@ static int text_launch(fr_plan *plan, void *out_dev, size_t out_stride)
                            plan->d_trecs, plan->d_trec_count, st, fill);
         HIP_TRY(hipGetLastError());
     }
-    if (plan->place_affine) HIP_TRY(text_args_launch<fr::TextAffineArgs>(plan, out_dev, out_stride, plan->n_tiles));
-    else if (plan->place_ex) HIP_TRY(text_args_launch<fr::TextPlaceArgs>(plan, out_dev, out_stride, plan->n_tiles));
-    else HIP_TRY(text_args_launch<fr::TextArgs>(plan, out_dev, out_stride, plan->n_tiles));
+    HIP_TRY(text_plan_launch(plan, out_dev, out_stride, plan->n_tiles));
     return FR_OK;
 }
 

@@ -20,6 +20,7 @@
 // The ten __global__ templates at the end only set the parameters of a body.  Some include it, some call it through
 // colour_rows; which, is decided by measurement and explained there.
 #include "fr_text.hpp"
+#include "fr_text_colour.hpp"
 #include "fr_srgb.hpp"
 #include "fr_wave.hpp"
 
@@ -27,36 +28,6 @@
 #include <type_traits>
 
 namespace fr {
-
-// Two 8-bit channels at once, in bits 0-7 and 16-23 of a word: (x + 127) div 255 with x = C*A + c*(255 - A) in [0, 65025]
-// as (t + (t >> 8)) >> 8, t = x + 128 (exact over that whole domain: tests/test_text_rgba_ref.py checks every x).
-// t + (t >> 8) < 2^16, so the halves never carry into each other.  c2: the sample's two channels; cA2 = C2 * A + 128 each.
-__device__ __forceinline__ uint32_t blend2(uint32_t c2, uint32_t cA2, uint32_t ia)
-{
-    const uint32_t t = c2 * ia + cA2;
-    return ((t + ((t >> 8) & 0x00ff00ffu)) >> 8) & 0x00ff00ffu;
-}
-
-// E(L), L in [0, 65535], from the LDS copy of SRGB_K: one lookup and one compare (fr_srgb.hpp)
-__device__ __forceinline__ uint32_t srgb_encode(const uint16_t *K, uint32_t L)
-{
-    const uint32_t k = K[L >> 4];
-    return (k & 0xffu) + ((L & 15u) >= (k >> 8) ? 1u : 0u);
-}
-
-// (x + 127) div 255 for x = D[C] * A + D[c] * (255 - A) <= 65535 * 255, given y = x + 127 < 2^24: (y * 0x808081) >> 31,
-// a 24 x 24-bit product (v_mul_u32_u24, v_mul_hi_u32_u24; exact over that whole domain: tests/test_text_srgb_ref.py
-// checks every y)
-__device__ __forceinline__ uint32_t div255_24(uint32_t y)
-{
-    return (uint32_t)(((uint64_t)(y & 0xffffffu) * 0x808081u) >> 31);
-}
-
-// FR_TEXT_LOAD_SKIP=0 (an experiment build only: make variant) makes the LOAD kernels, those of both placement forms,
-// store every pixel, to price the store skip below.
-#ifndef FR_TEXT_LOAD_SKIP
-#define FR_TEXT_LOAD_SKIP 1
-#endif
 
 // The rows of one tile as RGBA pixels, one dword per lane (fr_text_colour_kernel.inc).
 // BLEND = 0: every placement colour is opaque, so a sample takes the colour of the last instance that covers it: the
@@ -70,7 +41,7 @@ __device__ __forceinline__ uint32_t div255_24(uint32_t y)
 // lane loads its pixel (guarded as the store is) before the instance walk, so the load's latency hides under the
 // wave-uniform root evaluations.  With BLEND = 0 a lane whose samples are all untaken holds that pixel exactly (the
 // resolve of n^2 equal values; for sRGB E(D[v]) = v), so it skips its store and a row costs only its reads where no
-// glyph reaches.  The plan launches only the tiles whose instance list is non-empty (fr_api.hip): a pixel of any other
+// glyph reaches.  The plan launches only the tiles whose instance list is non-empty (fr_text_plan.cpp): a pixel of any other
 // tile is neither read nor written.
 template <int N, int FILL, int BLEND, bool SRGB, bool LOAD, class INST>
 __device__ __forceinline__ void colour_rows(const TextTables<INST> &a)
@@ -78,11 +49,6 @@ __device__ __forceinline__ void colour_rows(const TextTables<INST> &a)
     constexpr bool PLACE = std::is_same_v<INST, TextInstEx>;
 #include "fr_text_colour_kernel.inc"
 }
-
-// T, as a type that depends on N: a body included straight into a kernel template names members of the other placement
-// form's instance under if constexpr (PLACE), which only a dependent type leaves unchecked in the discarded branch
-template <int N, class T>
-using dependent_t = std::conditional_t<(N > 0), T, void>;
 
 // The instances, under the names that rocprofv3 and fr_plan_describe show: each only sets the parameters of a body.
 // A body that reaches its kernel through a function is optimised in another order than one written into the kernel, and
@@ -165,17 +131,7 @@ constexpr auto text_kernel_of() -> void (*)(ARGS)
 
 }  // namespace
 
-template <>
-hipError_t launch_text(const TextArgs &a, int n, int fill, int rgba, int blend, int srgb, int load, uint32_t n_tiles, hipStream_t stream,
-                       char *name, size_t name_cap)
-{
-    return launch_any(a, n, fill, rgba, blend, srgb, load, Launch{n_tiles, stream, name, name_cap});
-}
-template <>
-hipError_t launch_text(const TextPlaceArgs &a, int n, int fill, int rgba, int blend, int srgb, int load, uint32_t n_tiles,
-                       hipStream_t stream, char *name, size_t name_cap)
-{
-    return launch_any(a, n, fill, rgba, blend, srgb, load, Launch{n_tiles, stream, name, name_cap});
-}
+FR_TEXT_LAUNCH_FOR(TextArgs)
+FR_TEXT_LAUNCH_FOR(TextPlaceArgs)
 
 }  // namespace fr

@@ -1,60 +1,10 @@
-// fr_text.hpp — the tables of a text plan (fr_api.hip builds them, the text kernels of fr_text.hip read them)
+// fr_text.hpp — what a text kernel reads (the tables of fr_text_tables.hpp, on the device) and how fr_api.hip launches it
 #pragma once
 #include "fr_device.hpp"
+#include "fr_text_tables.hpp"
 
 namespace fr {
 
-struct TextInst {      // one placement, resolved on the host (fr_api.hip)
-    int32_t ix;        // floor(pen_x64 / 64)
-    int32_t pen_y;     // baseline row
-    int32_t x0, x1;    // the cell's columns [x0, x1), clipped to the run (image coordinates)
-    int32_t y0, y1;    // its rows [y0, y1), clipped likewise
-    uint32_t glyph;    // glyph index (record count: rec_count[glyph])
-    uint32_t rec;      // first record of the glyph: 2 * glyph_seg_start[glyph]
-    uint32_t fx64;     // pen_x64 mod 64
-    uint32_t rgba;     // an RGBA text plan's placement colour, R in the low byte (the bytes R G B A in memory); else 0
-    uint32_t pad[2];   // an sRGB text plan's linear colour: D[R] | D[G] << 16, D[B] (fr_srgb.hpp); else 0
-};
-struct TextInstEx {    // one fr_glyph_place_ex, resolved on the host: TextInst and the placement's own sample map
-    int32_t ix;        // floor(pen_x64 / 64)
-    int32_t iy;        // floor(pen_y64 / 64)
-    int32_t x0, x1;    // the (sheared) cell's columns [x0, x1), clipped to the run
-    int32_t y0, y1;    // its rows [y0, y1), clipped likewise
-    uint32_t glyph;
-    uint32_t rec;
-    uint32_t fx64;     // pen_x64 mod 64
-    uint32_t rgba;     // as TextInst::rgba
-    uint32_t pad[2];   // as TextInst::pad
-    uint32_t fy64;     // pen_y64 mod 64
-    float scale;       // the placement's scale (the run's when fr_glyph_place_ex::scale is 0)
-    float slant;       // k: cx = t - k * cy
-    uint32_t pad2;
-};
-struct TextInstAffine {  // one fr_glyph_place_affine, resolved on the host: the common fields and the inverse 2 x 2 matrix
-    int32_t ix;        // floor(pen_x64 / 64)
-    int32_t iy;        // floor(pen_y64 / 64)
-    int32_t x0, x1;    // the cell of the mapped box's four corners: columns [x0, x1), clipped to the run
-    int32_t y0, y1;    // its rows [y0, y1), clipped likewise
-    uint32_t glyph;
-    uint32_t rec;
-    uint32_t fx64;     // pen_x64 mod 64
-    uint32_t rgba;     // as TextInst::rgba
-    uint32_t pad[2];   // as TextInst::pad
-    uint32_t fy64;     // pen_y64 mod 64
-    float q00, q01;    // cx = f32(q00 * dx) + f32(q01 * dy)
-    float q10, q11;    // cy = f32(q10 * dx) + f32(q11 * dy): every lane has its own ray height
-    uint32_t pad2[3];
-};
-struct TextRun {       // == fr_text_run's geometry
-    uint32_t w, h, out_x, out_y;
-    float scale;
-    uint32_t clear;    // an RGBA text plan's clear colour, packed as TextInst::rgba; else 0
-    uint32_t pad[2];   // an sRGB text plan's linear clear colour, packed as TextInst::pad; else 0
-};
-struct TextTile {      // one 64 x 16 tile of a run and its instance list list[lbeg .. lend)
-    uint32_t run, x0, y0, lbeg, lend;
-    uint32_t pad[3];
-};
 template <class INST>
 struct TextTables {        // what a text kernel reads, for either placement form
     const TextTile *tiles;
@@ -70,11 +20,6 @@ struct TextTables {        // what a text kernel reads, for either placement for
 struct TextArgs : TextTables<TextInst> {};         // fr_glyph_place placements: the text_*_kernel instances
 struct TextPlaceArgs : TextTables<TextInstEx> {};  // fr_glyph_place_ex placements: the text_place_*_kernel instances
 struct TextAffineArgs : TextTables<TextInstAffine> {};  // fr_glyph_place_affine placements: the text_affine_*_kernel instances
-static_assert(sizeof(TextInstEx) == 64, "text tables");
-static_assert(sizeof(TextInstAffine) == 80, "text tables");
-static_assert(sizeof(TextInst) == 48 && sizeof(TextRun) == 32 && sizeof(TextTile) == 32, "text tables");
-
-constexpr int TEXT_TILE_W = 64, TEXT_TILE_H = 16, TEXT_WAVES = 4;
 
 // Launches the instance of a plan: n in {1, 2, 4}; rgba = 0: coverage / mask bytes (text_kernel; blend, srgb and load are
 // then ignored); else blend = 0 when every placement colour of the plan is opaque (A = 255), srgb for FR_TEXT_SRGB plans

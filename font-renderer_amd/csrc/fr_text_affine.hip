@@ -6,6 +6,7 @@
 // range the row's samples cannot reach.  A translation unit of its own: the 54 instances compile beside the 108 of
 // fr_text.hip, and nothing here can move a register of those.
 #include "fr_text.hpp"
+#include "fr_text_colour.hpp"
 #include "fr_srgb.hpp"
 #include "fr_wave.hpp"
 
@@ -13,30 +14,6 @@
 #include <type_traits>
 
 namespace fr {
-
-// the colour arithmetic of fr_text_colour_kernel.inc (described in fr_text.hip)
-__device__ __forceinline__ uint32_t blend2(uint32_t c2, uint32_t cA2, uint32_t ia)
-{
-    const uint32_t t = c2 * ia + cA2;
-    return ((t + ((t >> 8) & 0x00ff00ffu)) >> 8) & 0x00ff00ffu;
-}
-__device__ __forceinline__ uint32_t srgb_encode(const uint16_t *K, uint32_t L)
-{
-    const uint32_t k = K[L >> 4];
-    return (k & 0xffu) + ((L & 15u) >= (k >> 8) ? 1u : 0u);
-}
-__device__ __forceinline__ uint32_t div255_24(uint32_t y)
-{
-    return (uint32_t)(((uint64_t)(y & 0xffffffu) * 0x808081u) >> 31);
-}
-#ifndef FR_TEXT_LOAD_SKIP
-#define FR_TEXT_LOAD_SKIP 1
-#endif
-
-// T, as a type that depends on N: the bodies name members of the other placement forms' instances in branches that
-// if constexpr discards, which only a dependent type leaves unchecked (as in fr_text.hip)
-template <int N, class T>
-using dependent_t = std::conditional_t<(N > 0), T, void>;
 
 template <int N, int FILL, int BLEND, bool SRGB, bool LOAD>
 __device__ __forceinline__ void affine_colour_rows(const TextAffineArgs &a)
@@ -83,11 +60,6 @@ constexpr auto text_kernel_of() -> void (*)(ARGS)
 
 }  // namespace
 
-template <>
-hipError_t launch_text(const TextAffineArgs &a, int n, int fill, int rgba, int blend, int srgb, int load, uint32_t n_tiles,
-                       hipStream_t stream, char *name, size_t name_cap)
-{
-    return launch_any(a, n, fill, rgba, blend, srgb, load, Launch{n_tiles, stream, name, name_cap});
-}
+FR_TEXT_LAUNCH_FOR(TextAffineArgs)
 
 }  // namespace fr

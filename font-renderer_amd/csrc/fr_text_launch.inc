@@ -1,7 +1,8 @@
 // fr_text_launch.inc — from a text plan's parameters to its kernel instance and that instance's name: the host half of
 // launch_text (fr_text.hpp), included into the unnamed namespace of each translation unit that defines text kernels
 // (fr_text.hip, fr_text_affine.hip).  The unit defines first: text_form<ARGS>() (the part of the name between "text_" and
-// the family) and text_kernel_of<ARGS, FAM, FILL, BLEND, N>() (the instance).
+// the family) and text_kernel_of<ARGS, FAM, FILL, BLEND, N>() (the instance).  After its unnamed namespace it states
+// FR_TEXT_LAUNCH_FOR(ARGS) once per argument type it serves: launch_text's specialisation for it.
 struct Launch {
     uint32_t n_tiles;
     hipStream_t stream;
@@ -45,3 +46,11 @@ hipError_t launch_any(const ARGS &a, int n, int fill, int rgba, int blend, int s
     if (load) return srgb ? launch_family<ARGS, 4>(a, n, fill, blend, l) : launch_family<ARGS, 3>(a, n, fill, blend, l);
     return srgb ? launch_family<ARGS, 2>(a, n, fill, blend, l) : launch_family<ARGS, 1>(a, n, fill, blend, l);
 }
+
+#define FR_TEXT_LAUNCH_FOR(ARGS)                                                                                            \
+    template <>                                                                                                             \
+    hipError_t launch_text(const ARGS &a, int n, int fill, int rgba, int blend, int srgb, int load, uint32_t n_tiles,      \
+                           hipStream_t stream, char *name, size_t name_cap)                                                 \
+    {                                                                                                                       \
+        return launch_any(a, n, fill, rgba, blend, srgb, load, Launch{n_tiles, stream, name, name_cap});                    \
+    }
