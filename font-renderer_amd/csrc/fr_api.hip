@@ -8,6 +8,7 @@
 #include "fr_device.hpp"
 #include "fr_srgb.hpp"
 #include "fr_text.hpp"
+#include "fr_raster_plan.hpp"
 #include "fr_text_plan.hpp"
 
 #include <cmath>
@@ -124,23 +125,13 @@ struct fr_plan {
     uint32_t *d_job_seg = nullptr;     // [n_jobs][2]: first segment and segment count of the job's glyph
     uint32_t *d_bits = nullptr;        // FR_SDF_U8: the sign bit planes of the fast kernels' jobs (one bit per pixel: fr_win1.hip)
     uint32_t *d_job_bits = nullptr;    // and each job's first word in them (0xffffffff: a general-kernel job)
-    uint32_t *d_large = nullptr;       // distinct glyphs of more than 128 segments among the jobs: their records are
-    uint32_t n_large = 0;              // rebuilt by prepare_kernel before every render (the others: inside the render kernel)
-    uint32_t n_jobs = 0;
-    // jobs cov4_kernel / win1_kernel take (fr_cov4.hip, fr_win1.hip): the first n_fast entries of d_jobs / d_job_seg, grouped
-    // into `parts` — one launch each, by strip width (64 / 128 / 256 pixels, from the job's own width) and by the record
-    // slots the glyph needs (128 / 256 / 512); the general kernel renders the other n_jobs - n_fast
-    uint32_t n_fast = 0;
-    struct Part { uint32_t first, cnt, wlog, rec_cap, bands, strips; uint64_t pixels; };
-    std::vector<Part> parts;
-    int fast_ns = 0;                   // samples per axis of the fast kernels' jobs (4 / 2: cov4_kernel, 1: win1_kernel)
-    uint32_t gen_bands = 0, gen_strips = 0;
-    bool gen_uniform = false;
+    uint32_t *d_large = nullptr;       // distinct glyphs of more than 128 segments among the general jobs (rp.n_large): their records
+                                       // are rebuilt by prepare_kernel before every render (the others: inside the render kernel)
+    // the job classes, the parts and the launch geometry (fr_raster_plan.hpp); d_jobs / d_job_seg hold the jobs in its order.
+    // A text plan uses its pixels, need_cols and need_rows only
+    fr::RasterPlan rp;
     fr_raster_params params{};
     uint32_t flags = 0;                // fr_plan_create_ex's flags (FR_FILL_CONSISTENT)
-    uint32_t bands = 0, strips = 0, strip_w = 0, max_w = 0, max_h = 0;
-    bool uniform = false;        // see fr_plan_create
-    uint64_t pixels = 0, need_cols = 0, need_rows = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // option "graph": the launches of one render as an instantiated hipGraph, and what it was captured for
     hipGraphExec_t gexec = nullptr;
@@ -164,6 +155,61 @@ struct fr_plan {
 };
 
 template <class T> static void dfree(T *&p) { if (p) { (void)hipFree(p); p = nullptr; } }
+
+static fr::RasterOpts raster_opts(const fr_ctx *ctx)
+{
+    return fr::RasterOpts{ctx->strip_px, ctx->cov4, ctx->fuse_prepare, ctx->min_wgs, ctx->overlap, fr::render_wg_waves(), fr::cov4_wg_waves()};
+}
+
+// what every launch of a raster plan's render shares; launch_entry adds the entry's jobs and geometry
+static fr::RenderArgs render_args(const fr_plan *plan, void *out_dev, size_t out_stride)
+{
+    fr::RenderArgs a{};
+    a.glyph_seg_start = plan->gs->d_glyph_seg_start;
+    a.glyph_rec_count = plan->gs->d_rec_count;
+    a.recs = plan->gs->d_recs;
+    a.pts = plan->gs->d_pts;
+    a.seg_p0 = plan->gs->d_seg_p0;
+    a.seg_pts = plan->gs->d_seg_pts;
+    // fused: the render kernel builds the records of every glyph of <= 128 segments (<= 256 candidate roots)
+    // in LDS itself — decided per job inside the kernel; larger glyphs are staged from HBM
+    a.fused = plan->ctx->fuse_prepare ? 1u : 0u;
+    a.out = out_dev;
+    a.out_stride = out_stride;
+    a.kmax = plan->ctx->kmax;
+    a.phase_center = plan->params.sample_phase == FR_SAMPLE_CENTER ? 1 : 0;
+    a.lds_pad = plan->ctx->lds_pad;
+    return a;
+}
+
+// one entry of a plan's launch list (fr_raster_plan.hpp) on stream `st`; launch = false: only names its kernel instance, as
+// rocprofv3 does, into name[name_cap]
+static hipError_t launch_entry(const fr_plan *plan, fr::RenderArgs a, const fr::RasterLaunch &e, hipStream_t st, bool launch = true,
+                               char *name = nullptr, size_t name_cap = 0)
+{
+    const fr_glyphset *gs = plan->gs;
+    const int fill = (plan->flags & FR_FILL_CONSISTENT) ? 1 : 0;
+    a.jobs = plan->d_jobs + e.first;
+    a.job_seg = plan->d_job_seg + 2u * (size_t)e.first;
+    a.n_jobs = e.cnt; a.bands = e.bands; a.strips = e.strips; a.strip_w = e.strip_w; a.uniform = e.uniform ? 1u : 0u;
+    a.bands_per_wg = e.bands_per_wg; a.band_groups = e.band_groups;
+    switch (e.family) {
+    case fr::RL_PREPARE:                                                                        // (no name-only mode: not described)
+        if (launch)
+            fr::launch_prepare(gs->d_pts, gs->d_seg_p0, gs->d_glyph_seg_start, e.cnt ? plan->d_large : nullptr,
+                               e.cnt ? e.cnt : gs->n_glyphs, gs->d_recs, gs->d_rec_count, st, e.mode);
+        return hipSuccess;
+    case fr::RL_RENDER: return fr::launch_render(a, e.mode, e.samples, st, launch, name, name_cap, fill);
+    case fr::RL_COV4: return fr::launch_cov4(a, e.rec_cap, e.samples, st, launch, name, name_cap, fill);
+    case fr::RL_WIN1:
+        if (e.mode == 3) { a.out = plan->d_bits; a.job_bits = plan->d_job_bits + e.first; }     // the sign pass writes the bit planes
+        return fr::launch_win1(a, e.mode, e.rec_cap, st, launch, name, name_cap, fill);
+    default:                                                                                    // RL_SDF
+        if (!launch) { snprintf(name, name_cap, "fr::sdf_kernel<%s>", e.mode ? "true" : "false"); return hipSuccess; }
+        a.bits = plan->d_bits; a.job_bits = plan->d_job_bits;
+        return fr::launch_sdf(a, plan->rp.max_w, plan->rp.max_h, gs->max_seg_per_glyph, (int)plan->ctx->sdf_cull, st);
+    }
+}
 
 // launches the text kernel of a plan over n_tiles tiles for one placement form (ARGS: fr::TextArgs, fr::TextPlaceArgs or
 // fr::TextAffineArgs, over the plan's instance table of that form); n_tiles = 0: only names it, as rocprofv3 does, into
@@ -213,6 +259,8 @@ int fr_ctx_create(int device, void *hip_stream, fr_ctx **out)
         return fail(FR_E_HIP, "fr_ctx_create: no HIP device (%s); this library has no CPU path",
                     e != hipSuccess ? hipGetErrorString(e) : "count = 0");
     if (device < 0 || device >= n) return fail(FR_E_INVALID, "fr_ctx_create: device %d of %d", device, n);
+    if (fr::cov4_max_segments() != fr::COV4_MAX_SEGMENTS)          // (fast_class, plain host code, against the kernel unit's own figure)
+        return fail(FR_E_UNSUPPORTED, "fr_ctx_create: fast_class takes %u segments, cov4_kernel %u", fr::COV4_MAX_SEGMENTS, fr::cov4_max_segments());
     HIP_TRY(hipSetDevice(device));
     fr_ctx *c = new (std::nothrow) fr_ctx;
     if (!c) return fail(FR_E_NOMEM, "fr_ctx_create: host allocation");
@@ -282,170 +330,7 @@ int fr_ctx_set_option(fr_ctx *ctx, const char *key, int64_t value)
     return fail(FR_E_INVALID, "fr_ctx_set_option: unknown key '%s'", key);
 }
 
-// ---- glyph tables --------------------------------------------------------
-// Builds, per curve, the point index of its p0 and of the previous curve's p0 in the
-// same contour (wrapping to the last curve: render_glyph.zig:126-127).
-static int flatten_segments(const uint32_t *contour_start, uint32_t n_contours, uint64_t *n_points,
-                            std::vector<uint32_t> &seg_p0, std::vector<uint32_t> &seg_prev,
-                            std::vector<uint32_t> *contour_seg_start)
-{
-    if (n_contours && !contour_start) return fail(FR_E_INVALID, "contour_start is NULL");
-    uint64_t np = n_contours ? contour_start[n_contours] : 0;
-    if (n_contours && contour_start[0] != 0) return fail(FR_E_INVALID, "contour_start[0] must be 0");
-    if (contour_seg_start) contour_seg_start->assign(1, 0u);
-    for (uint32_t c = 0; c < n_contours; ++c) {
-        if (contour_start[c + 1] < contour_start[c]) return fail(FR_E_INVALID, "contour_start not monotone at %u", c);
-        const uint32_t len = contour_start[c + 1] - contour_start[c];
-        // points.len = 2*curves + 1 (Glyph.zig:23); an even length would index past the
-        // slice in the reference (render_glyph.zig:42)
-        if (len != 0 && (len & 1u) == 0) return fail(FR_E_INVALID, "contour %u has even length %u", c, len);
-        const uint32_t curves = len / 2;                                    // render_glyph.zig:38
-        for (uint32_t k = 0; k < curves; ++k) {
-            seg_p0.push_back(contour_start[c] + 2 * k);
-            seg_prev.push_back(contour_start[c] + (k != 0 ? 2 * k - 2 : len - 3));
-        }
-        if (contour_seg_start) contour_seg_start->push_back((uint32_t)seg_p0.size());
-    }
-    *n_points = np;
-    return FR_OK;
-}
-
-}  // extern "C"
-
-// Upper bound of the root records a render can keep for a glyph (segments [s0, s1)): the two candidates of a segment
-// minus those build_record_rows (fr_records.hpp) discards without looking at a cell — a == 0: one root, none if
-// p2y == p0y (render_glyph.zig:49-50); else the far-side root when t_v = B/a >= 1 and the near-side root when t_v < 0.
-static uint32_t glyph_root_bound(const int16_t *points_xy, const uint32_t *seg_p0, uint32_t s0, uint32_t s1)
-{
-    uint32_t nb = 0;
-    for (uint32_t sgi = s0; sgi < s1; ++sgi) {
-        const int16_t *q = points_xy + 2u * (size_t)seg_p0[sgi];
-        const int32_t p0y = q[1], p1y = q[3], p2y = q[5];
-        const int32_t a = p0y - 2 * p1y + p2y, b = p0y - p1y;
-        if (a == 0) { nb += (p2y != p0y) ? 1u : 0u; continue; }
-        const int64_t ba = (int64_t)b * a;
-        const bool tv_lt0 = ba < 0, tv_ge1 = a > 0 ? b >= a : b <= a;
-        nb += (tv_ge1 ? 0u : 1u) + (tv_lt0 ? 0u : 1u);
-    }
-    return nb;
-}
-
-// Estimate of the most crossings one horizontal ray can have with a glyph: a sweep over the segments' y extents (the
-// control points bound the curve), counted once between the heights of its ends and twice where it overshoots them.
-// Glyphs that stay at or under 16 take the instance that keeps 16 crossings per sample row in registers (plan_classify).
-// `ev` is scratch: (2 y + [closing], +-weight) — openings sort before closings at one y.
-static uint32_t glyph_ray_bound(const int16_t *points_xy, const uint32_t *seg_p0, uint32_t s0, uint32_t s1,
-                                std::vector<std::pair<int32_t, int32_t>> &ev)
-{
-    ev.clear();
-    for (uint32_t sgi = s0; sgi < s1; ++sgi) {
-        const int16_t *q = points_xy + 2u * (size_t)seg_p0[sgi];
-        const int32_t p0y = q[1], p1y = q[3], p2y = q[5];
-        // between the heights of its two ends a quadratic is met once; where it overshoots them (towards the
-        // control point: the vertex lies inside) twice, and not at all between the ends' heights on that side
-        const int32_t clo = std::min(p0y, p2y), chi = std::max(p0y, p2y);
-        // (half-open at the ends' heights, as the reference's own t in [0, 1) is: two segments that meet at a
-        // vertex are not both counted there.  An estimate that steers jobs, not a proof: a row that does hold
-        // more than the instance keeps takes the exact direct sum)
-        ev.emplace_back(2 * clo, 1);
-        ev.emplace_back(2 * chi, -1);
-        // (the vertex overshoots the nearer end by at most half of what the control point does)
-        if (p1y > chi) { ev.emplace_back(2 * chi, 2); ev.emplace_back(2 * (chi + (p1y - chi + 1) / 2) + 1, -2); }
-        if (p1y < clo) { ev.emplace_back(2 * (clo - (clo - p1y + 1) / 2), 2); ev.emplace_back(2 * clo, -2); }
-    }
-    std::sort(ev.begin(), ev.end());
-    int32_t cur = 0, best = 0;
-    for (const auto &e : ev) { cur += e.second; best = std::max(best, cur); }
-    return (uint32_t)best;
-}
-
-// Which kernel renders a job.  cov4_kernel (ns x ns samples, ns in {2, 4}) and win1_kernel (one sample per pixel)
-// take cells of ANY width and height — renderGlyph's own image size (render_glyph.zig:14-19) included — up to 2048
-// sample rows, of glyphs with <= 384 segments and <= 512 root records the vertex rule cannot discard: in strips of
-// 64 / 128 / 256 pixels chosen from the job's own width (a 47 x 45 image does not pay for 256 columns) and bands of
-// 64 sample rows, the last strip and band clipped at the cell's border.  Everything else takes the general
-// render_kernel.  -> 0 (general) or 1 + 4 (wlog - 2) + record class (0: <= 128 slots and <= 16 crossings per ray
-// estimated, 1: <= 256 slots, 2: <= 512 (<= 384 segments), 3: <= 1024 (<= 768 segments: two workgroups per CU)).
-enum { FAST_RC = 4, FAST_CLASSES = 3 * FAST_RC };     // record classes (128 / 256 / 512 / 1024 slots) x strip widths (64 / 128 / 256)
-struct FastRule {
-    int ns = 0;             // samples per axis on the fast kernels (0: this plan has no fast kernel)
-    uint32_t wlog_max = 0;  // widest strip the context allows (option "strip_px")
-};
-static FastRule fast_rule(const fr_ctx *ctx, const fr_raster_params *params)
-{
-    FastRule r;
-    const int n = params->samples_per_axis;
-    const bool one = params->mode == FR_WINDING_I16 || params->mode == FR_GRAY_DEBUG || params->mode == FR_MASK_NONZERO ||
-                     (params->mode == FR_COVERAGE_U8 && n == 1) || params->mode == FR_SDF_U8;   // (SDF: its sign pass)
-    r.wlog_max = ctx->strip_px >= 256u ? 4u : (ctx->strip_px >= 128u ? 3u : (ctx->strip_px >= 64u ? 2u : 0u));
-    if (ctx->cov4 && r.wlog_max) r.ns = one ? 1 : ((params->mode == FR_COVERAGE_U8 && (n == 4 || n == 2)) ? n : 0);
-    return r;
-}
-static int fast_class(const FastRule &R, uint32_t w, uint32_t h, uint32_t nsg, uint32_t root_bound, uint32_t ray_bound)
-{
-    if (!R.ns || w == 0 || h == 0 || (uint64_t)h * (uint32_t)R.ns > 2048u) return 0;     // (12-bit sample-row fields)
-    if (nsg > fr::cov4_max_segments() || root_bound > 1024u) return 0;
-    const uint32_t wl = std::min(w <= 64u ? 2u : (w <= 128u ? 3u : 4u), R.wlog_max);
-    const int rc = (nsg <= 256u && root_bound <= 128u && ray_bound <= 16u) ? 0 : ((nsg <= 256u && root_bound <= 256u) ? 1 :
-                   ((nsg <= 384u && root_bound <= 512u) ? 2 : 3));
-    return 1 + FAST_RC * (int)(wl - 2u) + rc;
-}
-// classes of fewer than FAST_PART_MIN jobs move up into the next class that has jobs: same strip width and more record
-// slots first, then wider strips with at least as many record slots (class c = 3 (wlog - 2) + record class; cls[j] = c + 1)
-enum { FAST_PART_MIN = 64 };
-static void merge_small_classes(uint32_t counts[FAST_CLASSES], uint8_t *cls, uint32_t n_jobs)
-{
-    int remap[FAST_CLASSES];
-    bool any = false;
-    for (int c = 0; c < FAST_CLASSES; ++c) {
-        remap[c] = c;
-        if (counts[c] == 0 || counts[c] >= (uint32_t)FAST_PART_MIN) continue;
-        const int w = c / FAST_RC, r = c % FAST_RC;
-        int target = -1;
-        for (int w2 = w; w2 < 3 && target < 0; ++w2)
-            for (int r2 = (w2 == w ? r + 1 : r); r2 < FAST_RC; ++r2)
-                if (counts[FAST_RC * w2 + r2]) { target = FAST_RC * w2 + r2; break; }
-        if (target < 0) continue;
-        counts[target] += counts[c];          // (the target may be small itself: it is looked at later in this loop)
-        counts[c] = 0;
-        remap[c] = target;
-        any = true;
-    }
-    if (!any) return;
-    for (int c = 0; c < FAST_CLASSES; ++c) {             // chains: a -> b -> c
-        int t = remap[c];
-        while (remap[t] != t) t = remap[t];
-        remap[c] = t;
-    }
-    for (uint32_t j = 0; j < n_jobs; ++j)
-        if (cls[j]) cls[j] = (uint8_t)(remap[cls[j] - 1] + 1);
-}
-
-// the fast jobs of `order` (already grouped by class, `counts[c]` jobs of class c + 1) -> the plan's launches
-static void make_parts(fr_plan *p, const fr_job *sorted_jobs, const uint32_t counts[FAST_CLASSES], int ns)
-{
-    p->parts.clear();
-    p->fast_ns = ns;
-    if (ns <= 0) return;                                              // (no fast kernel in this plan)
-    const uint32_t prb = ns == 1 ? 16u : 64u / (uint32_t)ns;          // pixel rows of a band
-    uint32_t first = 0;
-    for (int c = 0; c < FAST_CLASSES; ++c) {
-        if (!counts[c]) continue;
-        fr_plan::Part pt{};
-        pt.first = first; pt.cnt = counts[c]; pt.wlog = 2u + (uint32_t)(c / FAST_RC); pt.rec_cap = 128u << (c % FAST_RC);
-        const uint32_t sw = 16u << pt.wlog;
-        for (uint32_t q = first; q < first + counts[c]; ++q) {
-            pt.bands = std::max(pt.bands, (sorted_jobs[q].h + prb - 1u) / prb);
-            pt.strips = std::max(pt.strips, (sorted_jobs[q].w + sw - 1u) / sw);
-            pt.pixels += (uint64_t)sorted_jobs[q].w * sorted_jobs[q].h;
-        }
-        p->parts.push_back(pt);
-        first += counts[c];
-    }
-}
-
-extern "C" {
-
+// ---- glyph tables (flatten_segments and the two glyph bounds: fr_raster_plan.cpp) ---------------------------------------
 void fr_glyphset_destroy(fr_glyphset *gs)
 {
     if (!gs) return;
@@ -477,7 +362,7 @@ int fr_glyphset_create(fr_ctx *ctx, const int16_t *points_xy, const uint32_t *co
         return fail(FR_E_INVALID, "glyph_start must run from 0 to n_contours");
     std::vector<uint32_t> seg_p0, seg_prev, cseg;
     uint64_t np = 0;
-    int rc = flatten_segments(contour_start, n_contours, &np, seg_p0, seg_prev, &cseg);
+    int rc = fr::flatten_segments(contour_start, n_contours, &np, seg_p0, seg_prev, &cseg);
     if (rc) return rc;
     if (np && !points_xy) return fail(FR_E_INVALID, "points_xy is NULL");
     if (seg_p0.size() > 0x7fffffffull) return fail(FR_E_UNSUPPORTED, "too many segments");
@@ -493,8 +378,8 @@ int fr_glyphset_create(fr_ctx *ctx, const int16_t *points_xy, const uint32_t *co
     {
         std::vector<std::pair<int32_t, int32_t>> ev;
         for (uint32_t g = 0; g < n_glyphs; ++g) {
-            root_bound[g] = glyph_root_bound(points_xy, seg_p0.data(), gseg[g], gseg[g + 1]);
-            ray_bound[g] = glyph_ray_bound(points_xy, seg_p0.data(), gseg[g], gseg[g + 1], ev);
+            root_bound[g] = fr::glyph_root_bound(points_xy, seg_p0.data(), gseg[g], gseg[g + 1]);
+            ray_bound[g] = fr::glyph_ray_bound(points_xy, seg_p0.data(), gseg[g], gseg[g + 1], ev);
         }
     }
     HIP_TRY(hipSetDevice(ctx->device));
@@ -597,6 +482,40 @@ static int check_flags(uint32_t flags, uint32_t also = 0u)
     return FR_OK;
 }
 
+}  // extern "C"
+
+// uploads the sorted jobs of raster_plan_build (fr_raster_plan.hpp), builds the other tables while that copy is under way
+// (raster_plan_tables) and uploads them, into a plan that its caller destroys on failure
+static int raster_plan_upload(fr_plan *p, const fr::RasterPlanIn &in, fr::RasterTables t)
+{
+    fr::RasterPlan &rp = p->rp;
+    hipStream_t st = p->ctx->stream;
+    hipError_t e = hipSetDevice(p->ctx->device);
+    auto upload = [&](auto *&dst, const void *src, size_t bytes) {
+        if (e != hipSuccess || !bytes) return;
+        e = hipMalloc(&dst, bytes);
+        if (e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st);
+    };
+    upload(p->d_jobs, t.sorted_jobs, (size_t)rp.n_jobs * sizeof(fr::Job));
+    std::vector<uint32_t> jseg((size_t)rp.n_jobs * 2), large(rp.n_jobs - rp.n_fast), jbits(in.params.mode == FR_SDF_U8 ? rp.n_jobs : 0u);
+    t.jseg = jseg.data(); t.large = large.data(); t.jbits = jbits.data();
+    fr::raster_plan_tables(in, t, rp);
+    upload(p->d_large, t.large, (size_t)rp.n_large * 4);
+    upload(p->d_job_seg, t.jseg, (size_t)rp.n_jobs * 8);
+    if (rp.bit_plane) {
+        if (rp.bit_words >= 0xffffffffull) e = hipErrorInvalidValue;
+        if (e == hipSuccess) e = hipMalloc(&p->d_bits, (size_t)(rp.bit_words ? rp.bit_words : 1) * 4);
+        upload(p->d_job_bits, t.jbits, (size_t)rp.n_jobs * 4);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipEventCreate(&p->ev0);
+    if (e == hipSuccess) e = hipEventCreate(&p->ev1);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? FR_E_NOMEM : FR_E_HIP, "fr_plan_create: %s", hipGetErrorString(e));
+    return FR_OK;
+}
+
+extern "C" {
+
 int fr_plan_create(fr_ctx *ctx, const fr_glyphset *gs, const fr_job *jobs, uint32_t n_jobs,
                    const fr_raster_params *params, fr_plan **out)
 {
@@ -613,9 +532,6 @@ int fr_plan_create_ex(fr_ctx *ctx, const fr_glyphset *gs, const fr_job *jobs, ui
     int rc = check_params(params);
     if (rc) return rc;
     if (n_jobs && !jobs) return fail(FR_E_INVALID, "jobs is NULL");
-    const uint32_t n = (uint32_t)params->samples_per_axis;
-    uint32_t max_w = 0, max_h = 0;
-    uint64_t pixels = 0, need_cols = 0, need_rows = 0;
     for (uint32_t j = 0; j < n_jobs; ++j) {
         const fr_job &jb = jobs[j];
         if (jb.glyph >= gs->n_glyphs) return fail(FR_E_INVALID, "job %u: glyph %u of %u", j, jb.glyph, gs->n_glyphs);
@@ -629,119 +545,26 @@ int fr_plan_create_ex(fr_ctx *ctx, const fr_glyphset *gs, const fr_job *jobs, ui
         if (jb.min_x < -(1 << 22) || (int64_t)jb.min_x + jb.w > (1 << 22) || jb.max_y > (1 << 22) ||
             (int64_t)jb.max_y - jb.h < -(1 << 22))
             return fail(FR_E_UNSUPPORTED, "job %u: pixel coordinates beyond +-2^22", j);
-        max_w = jb.w > max_w ? jb.w : max_w;
-        max_h = jb.h > max_h ? jb.h : max_h;
-        pixels += (uint64_t)jb.w * jb.h;
-        need_cols = std::max<uint64_t>(need_cols, (uint64_t)jb.out_x + jb.w);
-        need_rows = std::max<uint64_t>(need_rows, (uint64_t)jb.out_y + jb.h);
     }
     fr_plan *p = new (std::nothrow) fr_plan;
     if (!p) return fail(FR_E_NOMEM, "fr_plan_create: host allocation");
-    p->ctx = ctx; p->gs = gs; p->n_jobs = n_jobs; p->params = *params; p->flags = flags;
-    p->pixels = pixels; p->need_cols = need_cols; p->need_rows = need_rows;
-    p->max_w = max_w; p->max_h = max_h;
-    const uint32_t band = 64u / n;                                      // pixel rows per wave band
-    const uint32_t cap_w = ctx->strip_px;                               // strip width cap, pixels
-    // Per JOB: the fast kernels or the general one (fast_class above).  The job table is stored fast jobs first, grouped
-    // by class — one launch per class that occurs.
+    p->ctx = ctx; p->gs = gs; p->params = *params; p->flags = flags;
+    std::vector<uint8_t> cls(n_jobs);
     std::vector<uint32_t> order(n_jobs);
-    uint32_t n_fast = 0;
-    uint32_t counts[FAST_CLASSES] = {};
-    const FastRule rule = fast_rule(ctx, params);
-    {
-        std::vector<uint8_t> cls(n_jobs);
-        for (uint32_t j = 0; j < n_jobs; ++j) {
-            const fr_job &jb = jobs[j];
-            const uint32_t nsg = gs->h_glyph_seg_start[jb.glyph + 1] - gs->h_glyph_seg_start[jb.glyph];
-            cls[j] = (uint8_t)fast_class(rule, jb.w, jb.h, nsg, gs->h_root_bound[jb.glyph], gs->h_ray_bound[jb.glyph]);
-            if (cls[j]) { ++counts[cls[j] - 1]; ++n_fast; }
-        }
-        // A class with only a handful of jobs is not worth a launch of its own (a real font at renderGlyph's sizes: three or
-        // four glyphs per odd class, each launch a few microseconds on the second stream): its jobs join the next class up
-        // that exists — wider strips and / or more record slots render the same bytes (the stores are clipped, spare
-        // record slots stay empty), only a little less efficiently.
-        merge_small_classes(counts, cls.data(), n_jobs);
-        uint32_t at[FAST_CLASSES + 1], run = 0;
-        for (int c = 0; c < FAST_CLASSES; ++c) { at[c + 1] = run; run += counts[c]; }
-        at[0] = run;                                                      // the general kernel's jobs go last
-        for (uint32_t j = 0; j < n_jobs; ++j) order[at[cls[j]]++] = j;
-    }
-    p->n_fast = n_fast;
-    // the general list: uniform = every strip of every job is full (w a multiple of the strip width) and every wave
-    // band is full (h a multiple of 64 / n pixel rows) — atlas cells; the render kernel has instances for it
-    p->uniform = n_jobs > n_fast;
-    uint32_t gmax_w = 0, gmax_h = 0;
-    for (uint32_t q = n_fast; q < n_jobs; ++q) {
-        gmax_w = std::max(gmax_w, jobs[order[q]].w); gmax_h = std::max(gmax_h, jobs[order[q]].h);
-    }
-    uint32_t sw = (gmax_w + 15u) & ~15u;                                // the general kernel's strip width
-    if (sw > cap_w) sw = cap_w;
-    if (sw == 0) sw = 16;
-    p->strip_w = sw;
-    for (uint32_t q = n_fast; q < n_jobs; ++q) {
-        const fr_job &jb = jobs[order[q]];
-        if (jb.w == 0 || jb.h == 0 || jb.w % sw || jb.h % band) p->uniform = false;
-    }
-    p->gen_bands = gmax_h ? (gmax_h + band - 1) / band : 1;
-    p->gen_strips = gmax_w ? (gmax_w + sw - 1) / sw : 1;
-    p->bands = p->gen_bands; p->strips = p->gen_strips;
     std::vector<fr_job> sorted_jobs(n_jobs);
-    for (uint32_t q = 0; q < n_jobs; ++q) sorted_jobs[q] = jobs[order[q]];
-    make_parts(p, sorted_jobs.data(), counts, rule.ns);
-    {
-        bool too_many = (uint64_t)(n_jobs - n_fast) * p->gen_bands * p->gen_strips > 0x7fffffffull;
-        for (const auto &pt : p->parts) too_many = too_many || (uint64_t)pt.cnt * pt.bands * pt.strips > 0x7fffffffull;
-        if (too_many) {
-            delete p;
-            return fail(FR_E_UNSUPPORTED, "batch needs more than 2^31 workgroups; split it");
-        }
+    const fr::RasterTables t = {cls.data(), order.data(), sorted_jobs.data(), nullptr, nullptr, nullptr};
+    fr::RasterPlanIn in{};
+    in.jobs = jobs; in.n_jobs = n_jobs; in.params = *params;
+    in.glyph_seg_start = gs->h_glyph_seg_start.data(); in.root_bound = gs->h_root_bound.data(); in.ray_bound = gs->h_ray_bound.data();
+    in.sdf_fast = true; in.merge = true; in.uniform = true;
+    fr::raster_plan_build(in, raster_opts(ctx), t, p->rp);
+    if (p->rp.too_many) {
+        delete p;
+        return fail(FR_E_UNSUPPORTED, "batch needs more than 2^31 workgroups; split it");
     }
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e == hipSuccess && n_jobs) e = hipMalloc(&p->d_jobs, (size_t)n_jobs * sizeof(fr::Job));
-    if (e == hipSuccess && n_jobs)
-        e = hipMemcpyAsync(p->d_jobs, sorted_jobs.data(), (size_t)n_jobs * sizeof(fr::Job), hipMemcpyHostToDevice, ctx->stream);
-    // each job's segment range, next to the job: the render kernel starts on the glyph's points without a
-    // dependent look-up through the glyph table
-    std::vector<uint32_t> jseg((size_t)n_jobs * 2);
-    for (uint32_t q = 0; q < n_jobs; ++q) {
-        const uint32_t gl = sorted_jobs[q].glyph;
-        jseg[2 * (size_t)q] = gs->h_glyph_seg_start[gl];
-        jseg[2 * (size_t)q + 1] = gs->h_glyph_seg_start[gl + 1] - gs->h_glyph_seg_start[gl];
-    }
-    // glyphs too large for the in-kernel record build (> 128 segments) among the general kernel's jobs, each once
-    std::vector<uint32_t> large;
-    for (uint32_t q = n_fast; q < n_jobs; ++q)
-        if (jseg[2 * (size_t)q + 1] > 128u) large.push_back(sorted_jobs[q].glyph);
-    std::sort(large.begin(), large.end());
-    large.erase(std::unique(large.begin(), large.end()), large.end());
-    p->n_large = (uint32_t)large.size();
-    if (e == hipSuccess && p->n_large) e = hipMalloc(&p->d_large, large.size() * 4);
-    if (e == hipSuccess && p->n_large)
-        e = hipMemcpyAsync(p->d_large, large.data(), large.size() * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && n_jobs) e = hipMalloc(&p->d_job_seg, (size_t)n_jobs * 8);
-    if (e == hipSuccess && n_jobs)
-        e = hipMemcpyAsync(p->d_job_seg, jseg.data(), (size_t)n_jobs * 8, hipMemcpyHostToDevice, ctx->stream);
-    // FR_SDF_U8: the sign of a fast job travels as one bit per pixel in a plane of its own (win1_kernel's sign-bit mode
-    // writes it, sdf_kernel reads it and is then the only writer of the output)
-    std::vector<uint32_t> jbits;
-    if (params->mode == FR_SDF_U8 && n_fast) {
-        jbits.assign(n_jobs, 0xffffffffu);
-        uint64_t words = 0;
-        for (uint32_t q = 0; q < n_fast; ++q) {
-            jbits[q] = (uint32_t)words;
-            words += (uint64_t)((sorted_jobs[q].w + 255u) / 256u) * sorted_jobs[q].h * 8u;      // (one plane per 256-pixel column: h rows of 8 words)
-            if (words >= 0xffffffffull) { e = hipErrorInvalidValue; break; }
-        }
-        if (e == hipSuccess) e = hipMalloc(&p->d_bits, (size_t)(words ? words : 1) * 4);
-        if (e == hipSuccess) e = hipMalloc(&p->d_job_bits, (size_t)n_jobs * 4);
-        if (e == hipSuccess) e = hipMemcpyAsync(p->d_job_bits, jbits.data(), (size_t)n_jobs * 4, hipMemcpyHostToDevice, ctx->stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess) e = hipEventCreate(&p->ev0);
-    if (e == hipSuccess) e = hipEventCreate(&p->ev1);
-    if (e != hipSuccess) {
+    if (const int urc = raster_plan_upload(p, in, t)) {
         fr_plan_destroy(p);
-        return fail(e == hipErrorOutOfMemory ? FR_E_NOMEM : FR_E_HIP, "fr_plan_create: %s", hipGetErrorString(e));
+        return urc;
     }
     *out = p;
     return FR_OK;
@@ -769,7 +592,7 @@ static int text_plan_upload(const char *fn, fr_plan *p, const fr::TextPlanTables
     const fr_glyphset *gs = p->gs;
     p->text_form = text_form_of((const PLACE *)nullptr);
     p->blend = t.blend;
-    p->pixels = t.pixels; p->need_cols = t.need_cols; p->need_rows = t.need_rows;
+    p->rp.pixels = t.pixels; p->rp.need_cols = t.need_cols; p->rp.need_rows = t.need_rows;
     p->n_tiles = (uint32_t)t.tiles.size(); p->n_insts = (uint32_t)t.insts.size(); p->n_tglyphs = (uint32_t)t.glyphs.size();
     hipStream_t st = ctx->stream;
     hipError_t e = hipSetDevice(ctx->device);
@@ -910,7 +733,7 @@ int fr_srgb_encode(const uint16_t *in, size_t n, uint8_t *out)
     return FR_OK;
 }
 
-uint64_t fr_plan_pixels(const fr_plan *plan) { return plan ? plan->pixels : 0; }
+uint64_t fr_plan_pixels(const fr_plan *plan) { return plan ? plan->rp.pixels : 0; }
 
 int fr_plan_stats(const fr_plan *plan, uint32_t *n_jobs_cov4, uint32_t *n_jobs_general)
 {
@@ -920,8 +743,8 @@ int fr_plan_stats(const fr_plan *plan, uint32_t *n_jobs_cov4, uint32_t *n_jobs_g
         if (n_jobs_general) *n_jobs_general = plan->n_insts;
         return FR_OK;
     }
-    if (n_jobs_cov4) *n_jobs_cov4 = plan->n_fast;
-    if (n_jobs_general) *n_jobs_general = plan->n_jobs - plan->n_fast;
+    if (n_jobs_cov4) *n_jobs_cov4 = plan->rp.n_fast;
+    if (n_jobs_general) *n_jobs_general = plan->rp.n_jobs - plan->rp.n_fast;
     return FR_OK;
 }
 
@@ -935,10 +758,7 @@ int fr_plan_describe(const fr_plan *plan, char *buf, size_t cap)
         const int k = snprintf(buf + at, cap - at, "%s%s x%u", at ? "; " : "", name, cnt);
         if (k > 0) at = std::min(cap - 1, at + (size_t)k);
     };
-    fr::RenderArgs a{};
-    a.kmax = plan->ctx->kmax;
     char name[96];
-    const int pm = plan->params.mode;
     const int fill = (plan->flags & FR_FILL_CONSISTENT) ? 1 : 0;
     if (plan->text) {
         if (plan->n_tglyphs) add(fill ? "fr::prepare_fill_kernel" : "fr::prepare_kernel", plan->n_tglyphs);
@@ -947,21 +767,18 @@ int fr_plan_describe(const fr_plan *plan, char *buf, size_t cap)
         if (plan->n_tiles) add(name, plan->n_insts);
         return FR_OK;
     }
-    for (const auto &pt : plan->parts) {
-        a.strip_w = 16u << pt.wlog;
-        name[0] = 0;
-        if (plan->fast_ns > 1) (void)fr::launch_cov4(a, pt.rec_cap, plan->fast_ns, nullptr, false, name, sizeof name, fill);
-        else (void)fr::launch_win1(a, pm == FR_WINDING_I16 ? 0 : (pm == FR_GRAY_DEBUG ? 1 : (pm == FR_SDF_U8 ? 3 : 2)), pt.rec_cap, nullptr, false, name, sizeof name, fill);
-        add(name, pt.cnt);
-    }
-    if (plan->n_jobs > plan->n_fast) {
-        a.strip_w = plan->strip_w; a.uniform = plan->uniform ? 1u : 0u;
-        name[0] = 0;
-        if (pm == FR_SDF_U8) (void)fr::launch_render(a, FR_COVERAGE_U8, 1, nullptr, false, name, sizeof name, fill);
-        else (void)fr::launch_render(a, pm, plan->params.samples_per_axis, nullptr, false, name, sizeof name, fill);
-        add(name, plan->n_jobs - plan->n_fast);
-    }
-    if (pm == FR_SDF_U8 && plan->n_jobs) add(plan->gs->max_seg_per_glyph > 64u ? "fr::sdf_kernel<true>" : "fr::sdf_kernel<false>", plan->n_jobs);
+    fr::RasterLaunchList L;
+    fr::raster_launches(plan->rp, plan->params, plan->flags, raster_opts(plan->ctx), plan->gs->max_seg_per_glyph, L);
+    const fr::RenderArgs a = render_args(plan, nullptr, 0);
+    // (printed fast parts first, although a render launches the general kernel before them; prepare_kernel is not listed)
+    for (const bool fast : {true, false})
+        for (uint32_t i = 0; i < L.n; ++i) {
+            const fr::RasterLaunch &e = L.l[i];
+            if (e.family == fr::RL_PREPARE || (e.family == fr::RL_COV4 || e.family == fr::RL_WIN1) != fast) continue;
+            name[0] = 0;
+            (void)launch_entry(plan, a, e, nullptr, false, name, sizeof name);
+            add(name, e.cnt);
+        }
     return FR_OK;
 }
 
@@ -980,11 +797,11 @@ static int plan_check(fr_plan *plan, void *out_dev, size_t out_stride, size_t ou
     if (!plan) return fail(FR_E_INVALID, "plan is NULL");
     // (a FR_TEXT_LOAD plan whose instances are all clipped away launches no tile, but its runs still need the output the
     // same plan with a visible glyph would: it is checked as that plan is)
-    if (plan->n_jobs == 0 && plan->n_tiles == 0 && !(plan->load && plan->pixels)) return FR_OK;
+    if (plan->rp.n_jobs == 0 && plan->n_tiles == 0 && !(plan->load && plan->rp.pixels)) return FR_OK;
     if (!out_dev) return fail(FR_E_INVALID, "out is NULL");
-    if (plan->need_cols > out_stride || plan->need_rows > out_rows)
+    if (plan->rp.need_cols > out_stride || plan->rp.need_rows > out_rows)
         return fail(FR_E_INVALID, "jobs need %llu x %llu elements, output is %zu x %zu",
-                    (unsigned long long)plan->need_cols, (unsigned long long)plan->need_rows, out_stride, out_rows);
+                    (unsigned long long)plan->rp.need_cols, (unsigned long long)plan->rp.need_rows, out_stride, out_rows);
     // (the fast kernels address the rows of a wave band by 32-bit offsets from the band's base: 32 rows of the pitch)
     if (out_stride > ((size_t)1 << 26))
         return fail(FR_E_INVALID, "row pitch of %zu elements: at most 2^26", out_stride);
@@ -1014,122 +831,30 @@ static int plan_launch_direct(fr_plan *plan, void *out_dev, size_t out_stride, s
 {
     if (const int rc = plan_check(plan, out_dev, out_stride, out_rows)) return rc;
     if (plan->text) return text_launch(plan, out_dev, out_stride);
-    if (plan->n_jobs == 0) return FR_OK;
+    if (plan->rp.n_jobs == 0) return FR_OK;
     HIP_TRY(hipSetDevice(plan->ctx->device));
-    const uint32_t n_fast = plan->n_fast, n_gen = plan->n_jobs - plan->n_fast;
-    const bool sdf = plan->params.mode == FR_SDF_U8;
-    const int fill = (plan->flags & FR_FILL_CONSISTENT) ? 1 : 0;
-    fr::RenderArgs a;
-    a.glyph_seg_start = plan->gs->d_glyph_seg_start;
-    a.glyph_rec_count = plan->gs->d_rec_count;
-    a.recs = plan->gs->d_recs;
-    a.pts = plan->gs->d_pts;
-    a.seg_p0 = plan->gs->d_seg_p0;
-    a.seg_pts = plan->gs->d_seg_pts;
-    a.job_bits = nullptr; a.bits = nullptr;
-    // fused: the render kernel builds the records of every glyph of <= 128 segments (<= 256 candidate roots)
-    // in LDS itself — decided per job inside the kernel; larger glyphs are staged from HBM
-    a.fused = plan->ctx->fuse_prepare ? 1u : 0u;
-    a.out = out_dev;
-    a.out_stride = out_stride;
-    a.strip_w = plan->strip_w;
-    a.kmax = plan->ctx->kmax;
-    a.phase_center = plan->params.sample_phase == FR_SAMPLE_CENTER ? 1 : 0;
-    a.lds_pad = plan->ctx->lds_pad;
-    a.nwin_log = 0; a.lds_region = 0; a.lds_rec_bytes = 0; a.lds_wave_bytes = 0; a.lds_tail = 0;
-    // one workgroup walks all bands of its cell (cx table, job and records staged once)
-    // unless the batch is too small to fill the chip: then split the bands over workgroups
-    // (bands are wave bands of 64/n pixel rows; a workgroup's waves take them round-robin)
-    auto split_bands = [&](uint32_t nw, uint32_t njobs, uint32_t bands, uint32_t strips) {
-        uint32_t bpw = (bands + nw - 1u) / nw * nw;
-        while (bpw > nw && (uint64_t)njobs * strips * ((bands + bpw - 1) / bpw) < plan->ctx->min_wgs) bpw = ((bpw / 2) + nw - 1u) / nw * nw;
-        a.bands_per_wg = bpw;
-        a.band_groups = (bands + bpw - 1) / bpw;
-    };
-    // A mixed plan: the smaller launches (a real font's few glyphs of many segments: the 512-record instance, the
-    // general kernel) are short kernels with long critical paths — forked onto a second stream so that they run beside
-    // the large one instead of before / after it (the jobs' cells are disjoint); joined before anything else touches the
-    // output.
     fr_ctx *const ctx = plan->ctx;
-    hipStream_t gst = ctx->stream;
-    // (the largest fast launch stays on the context's stream; every other launch of the plan goes beside it)
-    size_t big = 0;
-    for (size_t i = 1; i < plan->parts.size(); ++i)
-        if (plan->parts[i].pixels > plan->parts[big].pixels) big = i;
-    const size_t n_launches = (n_gen ? 1u : 0u) + plan->parts.size();
-    // (a small plan — a font at renderGlyph's own sizes for one font size: a few megapixels — is quicker launch after launch
-    // on one stream than through a fork and a join: measured 0.038 vs 0.056 ms at 5.8 Mpixel, 0.373 vs 0.356 at 221 Mpixel)
-    const bool forked = ctx->overlap && n_fast && n_launches > 1 && (ctx->overlap == 2u || plan->pixels >= ((uint64_t)32 << 20));
-    if (forked) {
+    fr::RasterLaunchList L;
+    fr::raster_launches(plan->rp, plan->params, plan->flags, raster_opts(ctx), plan->gs->max_seg_per_glyph, L);
+    const fr::RenderArgs a = render_args(plan, out_dev, out_stride);
+    if (L.forked) {
         if (const int rc = ensure_aux(ctx)) return rc;
         HIP_TRY(hipEventRecord(ctx->ev_fork, ctx->stream));
         HIP_TRY(hipStreamWaitEvent(ctx->aux, ctx->ev_fork, 0));
-        gst = ctx->aux;
     }
+    auto run = [&](uint32_t i0, uint32_t i1, bool forked) -> int {
+        for (uint32_t i = i0; i < i1; ++i)
+            HIP_TRY(launch_entry(plan, a, L.l[i], (forked && !L.l[i].largest) ? ctx->aux : ctx->stream));
+        return FR_OK;
+    };
     // (whatever fails between the fork and the join: the context's stream still waits for the second one)
-    auto launch_parts = [&]() -> int {
-    // a render always starts from the glyph POINTS: inside the kernels (fused) or by re-running the stand-alone
-    // precompute first, for the glyphs that need it
-    // (FR_FILL_CONSISTENT: its own records, the reference's are rebuilt behind the render: the glyph set's records and
-    // counts are the reference's outside a render, fr_glyphset_stats included)
-    auto prepare = [&](int f) {
-        if (n_gen && !a.fused)
-            fr::launch_prepare(plan->gs->d_pts, plan->gs->d_seg_p0, plan->gs->d_glyph_seg_start, nullptr, plan->gs->n_glyphs,
-                               plan->gs->d_recs, plan->gs->d_rec_count, gst, f);
-        else if (n_gen && plan->n_large)
-            fr::launch_prepare(plan->gs->d_pts, plan->gs->d_seg_p0, plan->gs->d_glyph_seg_start, plan->d_large, plan->n_large,
-                               plan->gs->d_recs, plan->gs->d_rec_count, gst, f);
-    };
-    prepare(fill);
-    if (n_gen) {
-        a.jobs = plan->d_jobs + n_fast;
-        a.job_seg = plan->d_job_seg + 2u * (size_t)n_fast;
-        a.n_jobs = n_gen; a.bands = plan->gen_bands; a.strips = plan->gen_strips; a.uniform = plan->uniform ? 1u : 0u;
-        split_bands(fr::render_wg_waves(), n_gen, plan->gen_bands, plan->gen_strips);
-        // SDF, sign first: the 1-sample coverage (255 where the reference's winding is non-zero, same sample points)
-        // lands in the output; the distance kernel reads it and overwrites it
-        if (sdf) HIP_TRY(fr::launch_render(a, FR_COVERAGE_U8, 1, gst, true, nullptr, 0, fill));
-        else HIP_TRY(fr::launch_render(a, plan->params.mode, plan->params.samples_per_axis, gst, true, nullptr, 0, fill));
-        if (fill) prepare(0);
-    }
-    for (size_t i = 0; i < plan->parts.size(); ++i) {
-        // cov4_kernel / win1_kernel, one launch per (strip width, record slots) class that occurs in the plan
-        const fr_plan::Part &pt = plan->parts[i];
-        a.jobs = plan->d_jobs + pt.first;
-        a.job_seg = plan->d_job_seg + 2u * (size_t)pt.first;
-        a.n_jobs = pt.cnt; a.bands = pt.bands; a.strips = pt.strips; a.uniform = 1u;
-        a.strip_w = 16u << pt.wlog;
-        split_bands(fr::cov4_wg_waves(), pt.cnt, pt.bands, pt.strips);
-        const int pm = plan->params.mode;
-        hipStream_t pst = (forked && i != big) ? ctx->aux : ctx->stream;
-        if (plan->fast_ns > 1) HIP_TRY(fr::launch_cov4(a, pt.rec_cap, plan->fast_ns, pst, true, nullptr, 0, fill));
-        else if (sdf && plan->d_bits) {
-            // the sign pass of FR_SDF_U8: one bit per pixel into the job's own bit plane
-            void *const keep = a.out;
-            a.out = plan->d_bits; a.job_bits = plan->d_job_bits + pt.first;
-            const hipError_t le = fr::launch_win1(a, 3, pt.rec_cap, pst, true, nullptr, 0, fill);
-            a.out = keep; a.job_bits = nullptr;
-            HIP_TRY(le);
-        }
-        else HIP_TRY(fr::launch_win1(a, pm == FR_WINDING_I16 ? 0 : (pm == FR_GRAY_DEBUG ? 1 : 2), pt.rec_cap, pst, true, nullptr, 0, fill));
-    }
-    return FR_OK;
-    };
-    const int rc_parts = launch_parts();
-    if (forked) {
+    const int rc_parts = run(0, L.join_at, L.forked);
+    if (L.forked) {
         HIP_TRY(hipEventRecord(ctx->ev_join, ctx->aux));
         HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
     }
     if (rc_parts) return rc_parts;
-    if (sdf) {
-        a.strip_w = plan->strip_w;
-        a.bits = plan->d_bits; a.job_bits = plan->d_job_bits;
-        a.jobs = plan->d_jobs;
-        a.job_seg = plan->d_job_seg;
-        a.n_jobs = plan->n_jobs;
-        HIP_TRY(fr::launch_sdf(a, plan->max_w, plan->max_h, plan->gs->max_seg_per_glyph, (int)plan->ctx->sdf_cull, plan->ctx->stream));
-    }
-    return FR_OK;
+    return run(L.join_at, L.n, false);
 }
 
 // One render of a plan.  Option "graph": the same launches — the fork onto the second stream and the join included — are
@@ -1138,7 +863,7 @@ static int plan_launch_direct(fr_plan *plan, void *out_dev, size_t out_stride, s
 static int plan_launch(fr_plan *plan, void *out_dev, size_t out_stride, size_t out_rows)
 {
     if (const int rc = plan_check(plan, out_dev, out_stride, out_rows)) return rc;
-    if (plan->n_jobs == 0 && plan->n_tiles == 0) return FR_OK;
+    if (plan->rp.n_jobs == 0 && plan->n_tiles == 0) return FR_OK;
     fr_ctx *const ctx = plan->ctx;
     if (!ctx->graph) return plan_launch_direct(plan, out_dev, out_stride, out_rows);
     HIP_TRY(hipSetDevice(ctx->device));
@@ -1341,7 +1066,7 @@ int fr_render_glyph_ex(fr_ctx *ctx, const int16_t *points_xy, const uint32_t *co
     const uint32_t zero_start[1] = {0};
     std::vector<uint32_t> seg_p0, seg_prev;
     uint64_t np = 0;
-    rc = flatten_segments(n_contours ? contour_start : zero_start, n_contours, &np, seg_p0, seg_prev, nullptr);
+    rc = fr::flatten_segments(n_contours ? contour_start : zero_start, n_contours, &np, seg_p0, seg_prev, nullptr);
     if (rc) return rc;
     if (np && !points_xy) return fail(FR_E_INVALID, "points_xy is NULL");
     const uint32_t ns = (uint32_t)seg_p0.size();
@@ -1393,32 +1118,24 @@ int fr_render_glyph_ex(fr_ctx *ctx, const int16_t *points_xy, const uint32_t *co
     gs.d_seg_p0 = reinterpret_cast<uint32_t *>(A0 + o_p0); gs.d_glyph_seg_start = reinterpret_cast<uint32_t *>(A0 + o_gseg);
     gs.d_rec_count = reinterpret_cast<uint32_t *>(A0 + o_cnt); gs.d_recs = reinterpret_cast<fr::Rec *>(A0 + o_recs);
     fr_plan pl;
-    pl.ctx = ctx; pl.gs = &gs; pl.n_jobs = 1; pl.n_fast = 0; pl.params = prm; pl.flags = flags;
-    {
-        // the same per-job rule as fr_plan_create: the image takes win1_kernel (64- / 128- / 256-pixel strips by its
-        // own width) unless the glyph is too large for it
-        const FastRule rule = fast_rule(ctx, &prm);
-        std::vector<std::pair<int32_t, int32_t>> ev;
-        const int cls = fast_class(rule, w, h, ns, glyph_root_bound(points_xy, seg_p0.data(), 0, ns),
-                                   glyph_ray_bound(points_xy, seg_p0.data(), 0, ns, ev));
-        if (cls && mode != FR_SDF_U8) {            // (one SDF image: the sign comes as a byte from the general kernel, no bit plane)
-            uint32_t counts[FAST_CLASSES] = {};
-            counts[cls - 1] = 1;
-            pl.n_fast = 1;
-            make_parts(&pl, &jb, counts, rule.ns);
-        }
-    }
+    pl.ctx = ctx; pl.gs = &gs; pl.params = prm; pl.flags = flags;
     pl.d_jobs = reinterpret_cast<fr::Job *>(A0 + o_job); pl.d_job_seg = reinterpret_cast<uint32_t *>(A0 + o_jseg);
-    pl.d_large = reinterpret_cast<uint32_t *>(A0 + o_large); pl.n_large = (ns > 128u && !pl.n_fast) ? 1u : 0u;
-    pl.max_w = w; pl.max_h = h; pl.pixels = (uint64_t)w * h; pl.need_cols = w; pl.need_rows = h;
-    uint32_t sw = ((uint32_t)w + 15u) & ~15u;
-    if (sw > ctx->strip_px) sw = ctx->strip_px;
-    pl.strip_w = sw;
-    pl.bands = pl.gen_bands = ((uint32_t)h + 63u) / 64u;
-    pl.strips = pl.gen_strips = ((uint32_t)w + sw - 1u) / sw;
-    pl.uniform = false;
+    pl.d_large = reinterpret_cast<uint32_t *>(A0 + o_large);
+    {
+        // the same rules as fr_plan_create, for this one job: the image takes win1_kernel (64- / 128- / 256-pixel strips by its
+        // own width) unless the glyph is too large for it (single_glyph_in: what differs from a plan's job)
+        std::vector<std::pair<int32_t, int32_t>> ev;
+        const uint32_t root = fr::glyph_root_bound(points_xy, seg_p0.data(), 0, ns), ray = fr::glyph_ray_bound(points_xy, seg_p0.data(), 0, ns, ev);
+        const fr::RasterPlanIn in = fr::single_glyph_in(&jb, gseg, &root, &ray, prm);
+        uint8_t cls1;
+        uint32_t order1, jseg1[2], large1, jbits1;
+        fr_job sorted1;
+        const fr::RasterTables t1 = {&cls1, &order1, &sorted1, jseg1, &large1, &jbits1};
+        fr::raster_plan_build(in, raster_opts(ctx), t1, pl.rp);
+        fr::raster_plan_tables(in, t1, pl.rp);
+    }
     int lrc = FR_OK;
-    if (mode == FR_SDF_U8 || pl.n_large) {
+    if (mode == FR_SDF_U8 || pl.rp.n_large) {
         // the stand-alone records (float brackets): the staged path of a large glyph and the SDF's stand-alone users
         hipError_t e = hipMemsetAsync(gs.d_rec_count, 0, 8, ctx->stream);
         if (e != hipSuccess) lrc = fail(FR_E_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
@@ -1452,7 +1169,7 @@ static int exact_setup(fr_ctx *ctx, const int16_t *points_xy, const uint32_t *co
     if (!ctx) return fail(FR_E_INVALID, "ctx is NULL");
     std::vector<uint32_t> seg_p0, seg_prev;
     uint64_t np = 0;
-    int rc = flatten_segments(contour_start, n_contours, &np, seg_p0, seg_prev, nullptr);
+    int rc = fr::flatten_segments(contour_start, n_contours, &np, seg_p0, seg_prev, nullptr);
     if (rc) return rc;
     if (np && !points_xy) return fail(FR_E_INVALID, "points_xy is NULL");
     d.n_seg = (uint32_t)seg_p0.size();

@@ -2,7 +2,7 @@
 of the instance a plan gets.  Pure Python: no GPU, no library call.
 
 The raster side is one algorithm compiled into 246 instances (fr_cov4.hip, fr_win1.hip, fr_render.hip); which one a
-job gets is decided on the host in fr_api.hip (fast_rule, fast_class, merge_small_classes) and in the launch
+job gets is decided on the host in fr_raster_plan.cpp (fast_rule, fast_class, merge_small_classes) and in the launch
 functions.  `predicted_name` restates those rules, glyph_root_bound and glyph_ray_bound included, and returns the
 string fr_plan_describe prints for the plan's kernel.  `expected_instances` is written from the template parameter
 products alone, independently of the case table; tests/test_instance_cases.py holds the two together and
@@ -30,7 +30,7 @@ JOB_DTYPE = np.dtype([("glyph", "<u4"), ("min_x", "<i4"), ("max_y", "<i4"), ("w"
 Case = namedtuple("Case", "family mode n fill kmax center gs jobs shape key")
 
 
-# ---- the host rules (fr_api.hip) ----------------------------------------------------------------------------------
+# ---- the host rules (fr_raster_plan.cpp) --------------------------------------------------------------------------
 def glyph_segments(gs, g):
     """(S, 3, 2) int64: p0, p1, p2 of every segment of glyph g"""
     out = []

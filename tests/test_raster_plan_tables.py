@@ -1,0 +1,42 @@
+"""The host rules of raster plans (csrc/fr_raster_plan.cpp) on the CPU: host/raster_plan_selftest runs fast_rule,
+fast_class, merge_small_classes, split_bands, the plan builder with its launch list, the single-glyph call's use of it
+and the two glyph bounds on synthetic number tables and prints one line per case.
+tests/golden/raster_plan_tables.json holds those lines as minted from the rules' text as it stood in fr_api.hip, moved
+but not yet restructured."""
+import json
+import os
+import subprocess
+
+import numpy as np
+
+import instance_cases as ic
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "font-renderer_amd", "csrc")
+GOLDEN = os.path.join(ROOT, "tests", "golden", "raster_plan_tables.json")
+
+
+def _lines():
+    subprocess.check_call(["make", "-C", CSRC, "../host/raster_plan_selftest"], stdout=subprocess.DEVNULL)
+    run = subprocess.run([os.path.join(ROOT, "font-renderer_amd", "host", "raster_plan_selftest")], capture_output=True, text=True)
+    assert run.returncode == 0, run.stderr
+    return dict(line.split(" ", 1) for line in run.stdout.splitlines())
+
+
+def test_raster_plan_tables_match_golden():
+    got = _lines()
+    with open(GOLDEN) as f:
+        want = json.load(f)
+    assert list(got) == list(want), "the cases differ from the golden file's"
+    wrong = {k: (got[k], want[k]) for k in want if got[k] != want[k]}
+    assert not wrong, wrong
+
+
+def test_bounds_match_the_python_restatement():
+    """glyph_root_bound and glyph_ray_bound against root_bound and ray_bound of instance_cases.py, written independently"""
+    cases = {k: v for k, v in _lines().items() if k.startswith("bounds/")}
+    assert len(cases) >= 8
+    for name, text in cases.items():
+        fields = dict(f.split("=") for f in text.split(" "))
+        segs = np.array([int(v) for v in fields["segs"].split(",") if v], np.int64).reshape(-1, 3, 2)
+        assert (int(fields["root"]), int(fields["ray"])) == (ic.root_bound(segs), ic.ray_bound(segs)), name
