@@ -25,10 +25,10 @@ namespace fr {
 // fill = 1: the FR_FILL_CONSISTENT instances (fr_records.hpp)
 void launch_prepare(const int16_t *, const uint32_t *, const uint32_t *, const uint32_t *, uint32_t, Rec *,
                     uint32_t *, hipStream_t, int fill = 0);
-hipError_t launch_render(const RenderArgs &, int mode, int n, hipStream_t, bool launch = true, char *name = nullptr, size_t name_cap = 0, int fill = 0);
+hipError_t launch_render(const RenderArgs &, const RasterLaunch &, hipStream_t);
 uint32_t render_wg_waves();
-hipError_t launch_cov4(const RenderArgs &, uint32_t rec_cap, int ns, hipStream_t, bool launch = true, char *name = nullptr, size_t name_cap = 0, int fill = 0);
-hipError_t launch_win1(const RenderArgs &, int mode1, uint32_t rec_cap, hipStream_t, bool launch = true, char *name = nullptr, size_t name_cap = 0, int fill = 0);
+hipError_t launch_cov4(const RenderArgs &, const RasterLaunch &, hipStream_t);
+hipError_t launch_win1(const RenderArgs &, const RasterLaunch &, hipStream_t);
 uint32_t cov4_wg_waves();
 uint32_t cov4_max_segments();
 hipError_t launch_sdf(const RenderArgs &, uint32_t, uint32_t, uint32_t max_seg, int cull, hipStream_t);
@@ -158,7 +158,7 @@ template <class T> static void dfree(T *&p) { if (p) { (void)hipFree(p); p = nul
 
 static fr::RasterOpts raster_opts(const fr_ctx *ctx)
 {
-    return fr::RasterOpts{ctx->strip_px, ctx->cov4, ctx->fuse_prepare, ctx->min_wgs, ctx->overlap, fr::render_wg_waves(), fr::cov4_wg_waves()};
+    return fr::RasterOpts{ctx->strip_px, ctx->cov4, ctx->fuse_prepare, ctx->min_wgs, ctx->overlap, fr::render_wg_waves(), fr::cov4_wg_waves(), ctx->kmax};
 }
 
 // what every launch of a raster plan's render shares; launch_entry adds the entry's jobs and geometry
@@ -182,30 +182,25 @@ static fr::RenderArgs render_args(const fr_plan *plan, void *out_dev, size_t out
     return a;
 }
 
-// one entry of a plan's launch list (fr_raster_plan.hpp) on stream `st`; launch = false: only names its kernel instance, as
-// rocprofv3 does, into name[name_cap]
-static hipError_t launch_entry(const fr_plan *plan, fr::RenderArgs a, const fr::RasterLaunch &e, hipStream_t st, bool launch = true,
-                               char *name = nullptr, size_t name_cap = 0)
+// one entry of a plan's launch list (fr_raster_plan.hpp) on stream `st`
+static hipError_t launch_entry(const fr_plan *plan, fr::RenderArgs a, const fr::RasterLaunch &e, hipStream_t st)
 {
     const fr_glyphset *gs = plan->gs;
-    const int fill = (plan->flags & FR_FILL_CONSISTENT) ? 1 : 0;
     a.jobs = plan->d_jobs + e.first;
     a.job_seg = plan->d_job_seg + 2u * (size_t)e.first;
     a.n_jobs = e.cnt; a.bands = e.bands; a.strips = e.strips; a.strip_w = e.strip_w; a.uniform = e.uniform ? 1u : 0u;
     a.bands_per_wg = e.bands_per_wg; a.band_groups = e.band_groups;
     switch (e.family) {
-    case fr::RL_PREPARE:                                                                        // (no name-only mode: not described)
-        if (launch)
-            fr::launch_prepare(gs->d_pts, gs->d_seg_p0, gs->d_glyph_seg_start, e.cnt ? plan->d_large : nullptr,
-                               e.cnt ? e.cnt : gs->n_glyphs, gs->d_recs, gs->d_rec_count, st, e.mode);
+    case fr::RL_PREPARE:
+        fr::launch_prepare(gs->d_pts, gs->d_seg_p0, gs->d_glyph_seg_start, e.cnt ? plan->d_large : nullptr,
+                           e.cnt ? e.cnt : gs->n_glyphs, gs->d_recs, gs->d_rec_count, st, e.mode);
         return hipSuccess;
-    case fr::RL_RENDER: return fr::launch_render(a, e.mode, e.samples, st, launch, name, name_cap, fill);
-    case fr::RL_COV4: return fr::launch_cov4(a, e.rec_cap, e.samples, st, launch, name, name_cap, fill);
+    case fr::RL_RENDER: return fr::launch_render(a, e, st);
+    case fr::RL_COV4: return fr::launch_cov4(a, e, st);
     case fr::RL_WIN1:
         if (e.mode == 3) { a.out = plan->d_bits; a.job_bits = plan->d_job_bits + e.first; }     // the sign pass writes the bit planes
-        return fr::launch_win1(a, e.mode, e.rec_cap, st, launch, name, name_cap, fill);
+        return fr::launch_win1(a, e, st);
     default:                                                                                    // RL_SDF
-        if (!launch) { snprintf(name, name_cap, "fr::sdf_kernel<%s>", e.mode ? "true" : "false"); return hipSuccess; }
         a.bits = plan->d_bits; a.job_bits = plan->d_job_bits;
         return fr::launch_sdf(a, plan->rp.max_w, plan->rp.max_h, gs->max_seg_per_glyph, (int)plan->ctx->sdf_cull, st);
     }
@@ -769,14 +764,12 @@ int fr_plan_describe(const fr_plan *plan, char *buf, size_t cap)
     }
     fr::RasterLaunchList L;
     fr::raster_launches(plan->rp, plan->params, plan->flags, raster_opts(plan->ctx), plan->gs->max_seg_per_glyph, L);
-    const fr::RenderArgs a = render_args(plan, nullptr, 0);
     // (printed fast parts first, although a render launches the general kernel before them; prepare_kernel is not listed)
     for (const bool fast : {true, false})
         for (uint32_t i = 0; i < L.n; ++i) {
             const fr::RasterLaunch &e = L.l[i];
             if (e.family == fr::RL_PREPARE || (e.family == fr::RL_COV4 || e.family == fr::RL_WIN1) != fast) continue;
-            name[0] = 0;
-            (void)launch_entry(plan, a, e, nullptr, false, name, sizeof name);
+            fr::raster_launch_name(e, name, sizeof name);
             add(name, e.cnt);
         }
     return FR_OK;

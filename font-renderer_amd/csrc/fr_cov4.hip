@@ -4,6 +4,8 @@
 // /root/reference/src/tools/render_glyph.zig:35-73, non-zero fill :29, box filter = the MSAA average
 // resolve of VulkanContext.zig:307-313); a plan takes this kernel for every job it fits (any width and height up to
 // 2048 sample rows, glyphs of <= 768 segments: fr_api.hip, fast_class) and the general kernel for the rest.
+// Which instance a launch gets and how it is named is settled on the host, without HIP, by raster_launches and
+// raster_launch_name (fr_raster_plan.cpp); launch_cov4 at the end of this file only looks the instance up.
 //
 // What the round-2 measurements say (tools/ubench/issue_model*.hip, profiles/r02/issue_model*.txt):
 // the path is bound by VECTOR-ALU ISSUE TIME — scalar, LDS and branch instructions of one wave hide under
@@ -29,8 +31,7 @@
 // windows of the row — then maps 16 counts to bytes at once.  Integer all the way: the result is the same
 // count k of inside samples per pixel, u8 = 16 k - [k > 8] = round_half_up(255 k / 16).
 #include "fr_c4.hpp"
-#include <cstdio>
-#include <type_traits>
+#include "fr_raster_plan.hpp"
 
 namespace fr {
 
@@ -135,61 +136,23 @@ static auto cov4_instance()
     else return cov4_kernel<WLOG, CAP, RPL, NS>;
 }
 
-template <int WLOG, int RPL, int NS, int FILL>
-static hipError_t cov4_launch_cap(const RenderArgs &a, dim3 grid, hipStream_t stream, char *name, size_t name_cap)
-{
-    // glyphs of <= 128 candidate roots (RPL == 2) all but never put more than 16 crossings on a sample row (a real font:
-    // 1 row in 100 000): their instance keeps 16 per row in registers — half the list to initialise, pull and sort, 5 %
-    // faster — and the rare fuller row takes the direct sum like any over-full row
-    const uint32_t kmax = (RPL == 2 && a.kmax > 16u) ? 16u : a.kmax;
-    // (the 1024-record instance — glyphs of 385 .. 768 segments, rare — exists with 32 kept crossings only)
-    const int cap = RPL >= 16 ? 32 : (kmax <= 8 ? 8 : (kmax <= 16 ? 16 : 32));
-    // the instance as rocprofv3 names it
-    if (name) snprintf(name, name_cap, FILL ? "fr::cov4_kernel<%d, %d, %d, %d, 1>" : "fr::cov4_kernel<%d, %d, %d, %d>", WLOG, cap, RPL, NS);
-    if (!grid.x) return hipSuccess;                // (name only)
-    // (only the 512- and 1024-record instances need more than the default 48 KB)
-    const size_t lds = (cap == 8 ? C4Lds<WLOG, RPL, NS, 8>::TOTAL : (cap == 16 ? C4Lds<WLOG, RPL, NS, 16>::TOTAL : C4Lds<WLOG, RPL, NS, 32>::TOTAL)) + a.lds_pad;
-    const dim3 block(64 * C4_WAVES);
-    if constexpr (RPL < 16) {
-        if (cap == 8) return launch_kernel(cov4_instance<WLOG, 8, RPL, NS, FILL>(), grid, block, lds, stream, a);
-        if (cap == 16) return launch_kernel(cov4_instance<WLOG, 16, RPL, NS, FILL>(), grid, block, lds, stream, a);
-    }
-    return launch_kernel(cov4_instance<WLOG, 32, RPL, NS, FILL>(), grid, block, lds, stream, a);
-}
-
-template <int WLOG, int NS, int FILL>
-static hipError_t cov4_launch_rpl(const RenderArgs &a, uint32_t rec_cap, dim3 grid, hipStream_t stream, char *name, size_t name_cap)
-{
-    if (rec_cap <= 128u) return cov4_launch_cap<WLOG, 2, NS, FILL>(a, grid, stream, name, name_cap);
-    if (rec_cap <= 256u) return cov4_launch_cap<WLOG, 4, NS, FILL>(a, grid, stream, name, name_cap);
-    if (rec_cap > 512u) return cov4_launch_cap<WLOG, 16, NS, FILL>(a, grid, stream, name, name_cap);
-    return cov4_launch_cap<WLOG, 8, NS, FILL>(a, grid, stream, name, name_cap);
-}
-
-template <int FILL>
-static hipError_t cov4_launch_ns(const RenderArgs &a, uint32_t rec_cap, int ns, dim3 grid, hipStream_t stream, char *name, size_t name_cap)
-{
-    if (ns == 4) {
-        if (a.strip_w == 256u) return cov4_launch_rpl<4, 4, FILL>(a, rec_cap, grid, stream, name, name_cap);
-        if (a.strip_w == 128u) return cov4_launch_rpl<3, 4, FILL>(a, rec_cap, grid, stream, name, name_cap);
-        if (a.strip_w == 64u) return cov4_launch_rpl<2, 4, FILL>(a, rec_cap, grid, stream, name, name_cap);
-    } else if (ns == 2) {
-        if (a.strip_w == 256u) return cov4_launch_rpl<4, 2, FILL>(a, rec_cap, grid, stream, name, name_cap);
-        if (a.strip_w == 128u) return cov4_launch_rpl<3, 2, FILL>(a, rec_cap, grid, stream, name, name_cap);
-        if (a.strip_w == 64u) return cov4_launch_rpl<2, 2, FILL>(a, rec_cap, grid, stream, name, name_cap);
-    }
-    return hipErrorInvalidValue;
-}
+// the (CAP, RPL) pairs cov4_kernel is compiled for, each with every strip width, sample count and fill rule: the
+// two-records-per-lane instances keep at most 16 crossings per sample row, the 1024-record one exists with 32 only
+constexpr bool cov4_exists(int cap, int rpl) { return rpl == 16 ? cap == 32 : (rpl != 2 || cap <= 16); }
 
 // jobs: cells of any size up to 2048 / ns sample rows (strips of a.strip_w in {64, 128, 256} pixels, wave bands of 64 / ns
 // pixel rows; the last of each may be partial), ns x ns samples (ns in {2, 4}), every glyph with <= 384 segments and
-// <= rec_cap (128, 256 or 512) possible root records (checked by fr_plan_create).  launch = false: only name the
-// instance (as rocprofv3 prints it) into `name`.
-hipError_t launch_cov4(const RenderArgs &a, uint32_t rec_cap, int ns, hipStream_t stream, bool launch, char *name, size_t name_cap, int fill)
+// <= rec_cap (128, 256 or 512) possible root records (checked by fr_plan_create).  e.targ = WLOG, CAP, RPL, NS.
+hipError_t launch_cov4(const RenderArgs &a, const RasterLaunch &e, hipStream_t stream)
 {
-    const dim3 grid(launch ? (uint32_t)((size_t)a.n_jobs * a.band_groups * a.strips) : 0u);
-    if (fill) return cov4_launch_ns<1>(a, rec_cap, ns, grid, stream, name, name_cap);
-    return cov4_launch_ns<0>(a, rec_cap, ns, grid, stream, name, name_cap);
+    const dim3 grid((uint32_t)((size_t)a.n_jobs * a.band_groups * a.strips)), block(64 * C4_WAVES);
+    const int key[] = {e.targ[0], e.targ[1], e.targ[2], e.targ[3], e.fill};
+    return pick(key, [&](auto WLOG, auto CAP, auto RPL, auto NS, auto FILL) -> hipError_t {
+        // (only the 512- and 1024-record instances need more than the default 48 KB)
+        if constexpr (cov4_exists(CAP, RPL))
+            return launch_kernel(cov4_instance<WLOG, CAP, RPL, NS, FILL>(), grid, block, C4Lds<WLOG, RPL, NS, CAP>::TOTAL + a.lds_pad, stream, a);
+        else return hipErrorInvalidValue;
+    }, Among<2, 3, 4>{}, Among<8, 16, 32>{}, Among<2, 4, 8, 16>{}, Among<2, 4>{}, Among<0, 1>{});
 }
 
 }  // namespace fr

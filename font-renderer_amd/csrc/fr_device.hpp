@@ -8,6 +8,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #pragma clang fp contract(off)
 
@@ -154,6 +155,21 @@ inline hipError_t launch_kernel(K *kern, dim3 grid, dim3 block, size_t lds, hipS
     }
     hipLaunchKernelGGL(kern, grid, block, lds, stream, a);
     return hipGetLastError();
+}
+
+// The kernel units' instance look-up.  A launch of the list names its instance by run-time template arguments
+// (RasterLaunch::targ, fr_raster_plan.hpp); pick(x, f, Among<..>{}, Among<..>{}, ..) finds x[0] in the first list, x[1] in
+// the second and so on, and calls f with the matches as std::integral_constant values -> what f returns, or
+// hipErrorInvalidValue when an x[i] is in none of its list's values.  f is instantiated for the whole product of the lists:
+// it guards the combinations it has no kernel for with `if constexpr`.
+template <int... V> struct Among {};
+template <class F> inline hipError_t pick(const int *, F &&f) { return f(); }
+template <class F, int... V, class... L>
+inline hipError_t pick(const int *x, F &&f, Among<V...>, L... rest)
+{
+    hipError_t r = hipErrorInvalidValue;
+    (void)((*x == V && (r = pick(x + 1, [&](auto... c) { return f(std::integral_constant<int, V>{}, c...); }, rest...), true)) || ...);
+    return r;
 }
 
 // order-preserving map binary32 -> u32 (total order, -0 < +0)

@@ -2,6 +2,7 @@
 #include "fr_raster_plan.hpp"
 
 #include <algorithm>
+#include <cstdio>
 
 namespace fr {
 
@@ -278,9 +279,12 @@ void raster_launches(const RasterPlan &p, const fr_raster_params &params, uint32
     auto push = [&](RasterFamily f, int mode, int samples, uint32_t first, uint32_t cnt) -> RasterLaunch & {
         RasterLaunch &e = out.l[out.n++];
         e = RasterLaunch{};
-        e.family = f; e.mode = mode; e.samples = samples; e.first = first; e.cnt = cnt;
+        e.family = f; e.mode = mode; e.samples = samples; e.first = first; e.cnt = cnt; e.fill = fill != 0;
         return e;
     };
+    auto instance = [](RasterLaunch &e, int a, int b, int c, int d) { e.targ[0] = a; e.targ[1] = b; e.targ[2] = c; e.targ[3] = d; };
+    // crossings a sample row keeps in registers before it takes the direct sum: option kmax -> CAP
+    auto cap_of = [](uint32_t kmax) { return kmax <= 8u ? 8 : (kmax <= 16u ? 16 : 32); };
     auto geometry = [&](RasterLaunch &e, uint32_t nw, uint32_t strip_w, uint32_t bands, uint32_t strips, bool uniform) {
         e.strip_w = strip_w; e.bands = bands; e.strips = strips; e.uniform = uniform;
         const auto s = split_bands(nw, e.cnt, bands, strips, opt.min_wgs);
@@ -308,6 +312,12 @@ void raster_launches(const RasterPlan &p, const fr_raster_params &params, uint32
         // lands in the output; the distance kernel reads it and overwrites it
         RasterLaunch &e = push(RL_RENDER, sdf ? (int)FR_COVERAGE_U8 : pm, sdf ? 1 : params.samples_per_axis, p.n_fast, n_gen);
         geometry(e, opt.render_waves, p.strip_w, p.gen_bands, p.gen_strips, p.uniform);
+        // winding != 0 ? 255 : 0 is exactly the 1-sample coverage (round_half_up(255 k / 1), k in {0, 1}); uniform plans of
+        // 256- / 128-pixel strips (atlas cells) at 4 x 4 samples take the specialised instances
+        const bool cov = e.mode == FR_COVERAGE_U8;
+        const int wlog = (cov && e.samples == 4 && e.uniform) ? (e.strip_w == 256u ? 4 : (e.strip_w == 128u ? 3 : -1)) : -1;
+        const int kmode = (e.mode == FR_MASK_NONZERO && e.samples == 1) ? (int)FR_COVERAGE_U8 : e.mode;
+        instance(e, kmode, e.samples, cap_of(opt.kmax), wlog);
         if (fill) prepare(0);
     }
     // (the largest fast launch stays on the context's stream; every other launch of the plan goes beside it)
@@ -322,9 +332,34 @@ void raster_launches(const RasterPlan &p, const fr_raster_params &params, uint32
         RasterLaunch &e = p.fast_ns > 1 ? push(RL_COV4, 0, p.fast_ns, pt.first, pt.cnt) : push(RL_WIN1, m1, 1, pt.first, pt.cnt);
         e.rec_cap = pt.rec_cap; e.largest = i == big;
         geometry(e, opt.fast_waves, 16u << pt.wlog, pt.bands, pt.strips, true);
+        // root records per lane: 64 RPL record slots
+        const int rpl = pt.rec_cap <= 128u ? 2 : (pt.rec_cap <= 256u ? 4 : (pt.rec_cap > 512u ? 16 : 8));
+        if (e.family == RL_WIN1) { instance(e, (int)pt.wlog, e.mode, rpl, 0); continue; }
+        // glyphs of <= 128 candidate roots (RPL == 2) all but never put more than 16 crossings on a sample row (a real font:
+        // 1 row in 100 000): their instance keeps 16 per row in registers — half the list to initialise, pull and sort, 5 %
+        // faster — and the rare fuller row takes the direct sum like any over-full row
+        // (the 1024-record instance — glyphs of 385 .. 768 segments, rare — exists with 32 kept crossings only)
+        const int cap = rpl >= 16 ? 32 : cap_of((rpl == 2 && opt.kmax > 16u) ? 16u : opt.kmax);
+        instance(e, (int)pt.wlog, cap, rpl, e.samples);
     }
     out.join_at = out.n;
-    if (sdf) push(RL_SDF, max_seg > 64u ? 1 : 0, 0, 0, p.n_jobs).strip_w = p.strip_w;
+    if (sdf) {
+        RasterLaunch &e = push(RL_SDF, max_seg > 64u ? 1 : 0, 0, 0, p.n_jobs);
+        e.strip_w = p.strip_w; e.targ[0] = e.mode;
+    }
+}
+
+void raster_launch_name(const RasterLaunch &e, char *name, size_t cap)
+{
+    const int *t = e.targ;
+    const char *tail = e.fill ? ", 1>" : ">";
+    switch (e.family) {
+    case RL_RENDER: snprintf(name, cap, "fr::render_kernel<%d, %d, %d, %d%s", t[0], t[1], t[2], t[3], tail); break;
+    case RL_COV4: snprintf(name, cap, "fr::cov4_kernel<%d, %d, %d, %d%s", t[0], t[1], t[2], t[3], tail); break;
+    case RL_WIN1: snprintf(name, cap, "fr::win1_kernel<%d, %d, %d%s", t[0], t[1], t[2], tail); break;
+    case RL_SDF: snprintf(name, cap, "fr::sdf_kernel<%s>", t[0] ? "true" : "false"); break;
+    default: if (cap) name[0] = 0;
+    }
 }
 
 }  // namespace fr

@@ -2,9 +2,11 @@
 // the launch geometry, and the launches of one render as a list.  Plain C++: no HIP, no fr_ctx, no fr_plan.  fr_api.hip
 // checks the caller's arguments, calls raster_plan_build, uploads what it returns, and walks raster_launches twice: to
 // launch (plan_launch_direct) and to name (fr_plan_describe); host/raster_plan_selftest.cpp runs all of it on the CPU.
+// A launch of the list names its kernel instance completely: the kernel units only look it up (pick, fr_device.hpp).
 #pragma once
 #include "../../include/fr_raster.h"
 
+#include <cstddef>
 #include <utility>
 #include <vector>
 
@@ -21,6 +23,7 @@ constexpr uint32_t COV4_MAX_SEGMENTS = 768u;
 struct RasterOpts {
     uint32_t strip_px, cov4, fuse_prepare, min_wgs, overlap;
     uint32_t render_waves, fast_waves;
+    uint32_t kmax;                     // crossings a sample row keeps: which CAP instance (raster_launches)
 };
 
 struct RasterPlanIn {
@@ -98,6 +101,11 @@ struct RasterLaunch {
     int samples;                       // per axis (render, cov4)
     uint32_t first, cnt;               // sorted jobs [first, first + cnt); prepare: cnt glyphs of `large`, 0 = the whole glyph set
     uint32_t strip_w, rec_cap, bands, strips, bands_per_wg, band_groups;
+    // the kernel instance: its template arguments in the kernel's own order — cov4_kernel<WLOG, CAP, RPL, NS>,
+    // win1_kernel<WLOG, MODE, RPL>, render_kernel<MODE, N, CAP, WLOG> (WLOG -1: the ragged one), sdf_kernel<bool> — and
+    // whether it is the FILL twin.  Arguments the kernels have no instance of end the launch in hipErrorInvalidValue
+    int targ[4];
+    bool fill;
 };
 struct RasterLaunchList {
     RasterLaunch l[RASTER_MAX_LAUNCHES];
@@ -108,6 +116,8 @@ struct RasterLaunchList {
 // max_seg: segments of the glyph set's largest glyph (FR_SDF_U8: which distance kernel)
 void raster_launches(const RasterPlan &p, const fr_raster_params &params, uint32_t flags, const RasterOpts &opt, uint32_t max_seg,
                      RasterLaunchList &out);
+// the kernel of a render / cov4 / win1 / sdf launch as rocprofv3 names it, into name[cap] (a prepare launch: "")
+void raster_launch_name(const RasterLaunch &e, char *name, size_t cap);
 
 // one workgroup walks all bands of its cell unless the batch is too small to fill the chip: -> (bands per workgroup,
 // workgroups per cell column)

@@ -29,9 +29,11 @@
 // Per-pixel work is O(crossings of its row), not O(segments).  A row with more than CAP crossings takes
 // the direct sum over records (same integers, slower), inside the kernel.  DESIGN.md §3-§4 has the
 // arguments and the measurements.
+// Which instance a launch gets and how it is named is settled on the host, without HIP, by raster_launches and
+// raster_launch_name (fr_raster_plan.cpp); launch_render at the end of this file only looks the instance up.
 #include "fr_records.hpp"
 #include "fr_wave.hpp"
-#include <cstdio>
+#include "fr_raster_plan.hpp"
 
 namespace fr {
 
@@ -103,11 +105,8 @@ void render_lds_plan(uint32_t strip_w, int n, int mode, uint32_t cap, uint32_t *
 }
 
 template <int MODE, int N, int CAP, int WLOG, int FILL>
-static hipError_t launch_one(RenderArgs a, dim3 grid, hipStream_t stream, char *name, size_t name_cap)
+static hipError_t launch_one(RenderArgs a, dim3 grid, hipStream_t stream)
 {
-    // as rocprofv3 names the instance
-    if (name) snprintf(name, name_cap, FILL ? "fr::render_kernel<%d, %d, %d, %d, 1>" : "fr::render_kernel<%d, %d, %d, %d>", MODE, N, CAP, WLOG);
-    if (!grid.x) return hipSuccess;                     // (name only)
     size_t lds;
     render_lds_plan(a.strip_w, N, MODE, CAP, &a.nwin_log, &a.lds_region, &a.lds_rec_bytes, &a.lds_wave_bytes, &a.lds_tail, &lds);
     lds += a.lds_pad;
@@ -116,46 +115,22 @@ static hipError_t launch_one(RenderArgs a, dim3 grid, hipStream_t stream, char *
     else return launch_kernel(render_kernel<MODE, N, CAP, WLOG>, grid, dim3(64 * NW), lds, stream, a);
 }
 
-template <int MODE, int N, int WLOG, int FILL>
-static hipError_t launch_cap(const RenderArgs &a, dim3 grid, hipStream_t stream, char *name, size_t name_cap)
-{
-    if (a.kmax <= 8) return launch_one<MODE, N, 8, WLOG, FILL>(a, grid, stream, name, name_cap);
-    if (a.kmax <= 16) return launch_one<MODE, N, 16, WLOG, FILL>(a, grid, stream, name, name_cap);
-    return launch_one<MODE, N, 32, WLOG, FILL>(a, grid, stream, name, name_cap);
-}
-
-// FILL: the FR_FILL_CONSISTENT twin of every instance (same launch shape and LDS)
-template <int FILL>
-static hipError_t launch_mode(const RenderArgs &a, int mode, int n, dim3 grid, hipStream_t stream, char *name, size_t name_cap)
-{
-    if (mode == MODE_COVERAGE_U8) {
-        if (n == 1) return launch_cap<MODE_COVERAGE_U8, 1, -1, FILL>(a, grid, stream, name, name_cap);
-        if (n == 2) return launch_cap<MODE_COVERAGE_U8, 2, -1, FILL>(a, grid, stream, name, name_cap);
-        if (n == 4) {
-            // uniform plans of 256- / 128-pixel strips (atlas cells) take the specialised instances
-            if (a.uniform && a.strip_w == 256u) return launch_cap<MODE_COVERAGE_U8, 4, 4, FILL>(a, grid, stream, name, name_cap);
-            if (a.uniform && a.strip_w == 128u) return launch_cap<MODE_COVERAGE_U8, 4, 3, FILL>(a, grid, stream, name, name_cap);
-            return launch_cap<MODE_COVERAGE_U8, 4, -1, FILL>(a, grid, stream, name, name_cap);
-        }
-        return hipErrorInvalidValue;
-    }
-    if (n != 1) return hipErrorInvalidValue;
-    if (mode == MODE_WINDING_I16) return launch_cap<MODE_WINDING_I16, 1, -1, FILL>(a, grid, stream, name, name_cap);
-    if (mode == MODE_GRAY_DEBUG) return launch_cap<MODE_GRAY_DEBUG, 1, -1, FILL>(a, grid, stream, name, name_cap);
-    // winding != 0 ? 255 : 0 is exactly the 1-sample coverage (round_half_up(255 k / 1), k in {0, 1})
-    if (mode == MODE_MASK_NONZERO) return launch_cap<MODE_COVERAGE_U8, 1, -1, FILL>(a, grid, stream, name, name_cap);
-    return hipErrorInvalidValue;
-}
+// the (MODE, N, WLOG) triples render_kernel is compiled for, each with CAP 8 / 16 / 32 and both fill rules: coverage at
+// 1, 2 and 4 samples per axis, winding and gray at one; only 4 x 4 coverage has the uniform instances (WLOG 4 / 3)
+constexpr bool render_exists(int mode, int n, int wlog) { return mode == MODE_COVERAGE_U8 ? (wlog < 0 || n == 4) : (wlog < 0 && n == 1); }
 
 uint32_t render_wg_waves() { return NW; }
 
-// launch = false: only name the instance (as rocprofv3 prints it) into `name`
-hipError_t launch_render(const RenderArgs &a, int mode, int n, hipStream_t stream, bool launch, char *name, size_t name_cap, int fill)
+// e.targ = MODE, N, CAP, WLOG
+hipError_t launch_render(const RenderArgs &a, const RasterLaunch &e, hipStream_t stream)
 {
-    const dim3 grid(launch ? (uint32_t)((size_t)a.n_jobs * a.band_groups * a.strips) : 0u);
+    const dim3 grid((uint32_t)((size_t)a.n_jobs * a.band_groups * a.strips));
     if (a.strip_w == 0 || a.strip_w > 256u || (a.strip_w & 15u)) return hipErrorInvalidValue;
-    if (fill) return launch_mode<1>(a, mode, n, grid, stream, name, name_cap);
-    return launch_mode<0>(a, mode, n, grid, stream, name, name_cap);
+    const int key[] = {e.targ[0], e.targ[1], e.targ[2], e.targ[3], e.fill};
+    return pick(key, [&](auto MODE, auto N, auto CAP, auto WLOG, auto FILL) -> hipError_t {
+        if constexpr (render_exists(MODE, N, WLOG)) return launch_one<MODE, N, CAP, WLOG, FILL>(a, grid, stream);
+        else return hipErrorInvalidValue;
+    }, Among<MODE_WINDING_I16, MODE_GRAY_DEBUG, MODE_COVERAGE_U8>{}, Among<1, 2, 4>{}, Among<8, 16, 32>{}, Among<-1, 3, 4>{}, Among<0, 1>{});
 }
 
 }  // namespace fr

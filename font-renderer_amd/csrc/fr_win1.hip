@@ -14,9 +14,10 @@
 // after the scans) and hold |w| <= 31: a row with more than 31 crossings (it alone could leave that range) takes
 // the direct path — 16-bit differences, suffix scan, pixels written from there.  No lists, no sort, no toggles:
 // per 4 KB of gray output about half the vector instructions of cov4_kernel's 16-sample pixel.
+// Which instance a launch gets and how it is named is settled on the host, without HIP, by raster_launches and
+// raster_launch_name (fr_raster_plan.cpp); launch_win1 at the end of this file only looks the instance up.
 #include "fr_c4.hpp"
-#include <cstdio>
-#include <type_traits>
+#include "fr_raster_plan.hpp"
 
 namespace fr {
 
@@ -113,45 +114,16 @@ static auto win1_instance()
     else return win1_kernel<WLOG, MODE, RPL>;
 }
 
-template <int WLOG, int RPL, int FILL>
-static hipError_t win1_launch_mode(const RenderArgs &a, int mode, dim3 grid, hipStream_t stream, char *name, size_t name_cap)
-{
-    const size_t lds = W1Lds<WLOG, RPL>::TOTAL + a.lds_pad;
-    if (name) snprintf(name, name_cap, FILL ? "fr::win1_kernel<%d, %d, %d, 1>" : "fr::win1_kernel<%d, %d, %d>", WLOG, mode, RPL);      // as rocprofv3 names the instance
-    if (!grid.x) return hipSuccess;               // (name only)
-    const dim3 block(64 * C4_WAVES);
-    if (mode == MODE1_WINDING_I16) return launch_kernel(win1_instance<WLOG, MODE1_WINDING_I16, RPL, FILL>(), grid, block, lds, stream, a);
-    if (mode == MODE1_GRAY_DEBUG) return launch_kernel(win1_instance<WLOG, MODE1_GRAY_DEBUG, RPL, FILL>(), grid, block, lds, stream, a);
-    if (mode == MODE1_BITS) return launch_kernel(win1_instance<WLOG, MODE1_BITS, RPL, FILL>(), grid, block, lds, stream, a);
-    return launch_kernel(win1_instance<WLOG, MODE1_MASK, RPL, FILL>(), grid, block, lds, stream, a);
-}
-
-template <int WLOG, int FILL>
-static hipError_t win1_launch_rpl(const RenderArgs &a, int mode, uint32_t rec_cap, dim3 grid, hipStream_t stream, char *name, size_t name_cap)
-{
-    if (rec_cap <= 128u) return win1_launch_mode<WLOG, 2, FILL>(a, mode, grid, stream, name, name_cap);
-    if (rec_cap <= 256u) return win1_launch_mode<WLOG, 4, FILL>(a, mode, grid, stream, name, name_cap);
-    if (rec_cap > 512u) return win1_launch_mode<WLOG, 16, FILL>(a, mode, grid, stream, name, name_cap);
-    return win1_launch_mode<WLOG, 8, FILL>(a, mode, grid, stream, name, name_cap);
-}
-
-template <int FILL>
-static hipError_t win1_launch_strip(const RenderArgs &a, int mode, uint32_t rec_cap, dim3 grid, hipStream_t stream, char *name, size_t name_cap)
-{
-    if (a.strip_w == 256u) return win1_launch_rpl<4, FILL>(a, mode, rec_cap, grid, stream, name, name_cap);
-    if (a.strip_w == 128u) return win1_launch_rpl<3, FILL>(a, mode, rec_cap, grid, stream, name, name_cap);
-    if (a.strip_w == 64u) return win1_launch_rpl<2, FILL>(a, mode, rec_cap, grid, stream, name, name_cap);
-    return hipErrorInvalidValue;
-}
-
 // jobs: cells of any size up to 2048 rows (strips of a.strip_w in {64, 128, 256} pixels and bands of 16 rows; the last of
 // each may be partial), one sample per pixel, glyphs with <= 384 segments and <= rec_cap possible root records.
-// mode: 0 winding_i16, 1 gray_debug, 2 mask, 3 sign bits (one per pixel, job-local bit plane).  launch = false: only name the instance (as rocprofv3 prints it).
-hipError_t launch_win1(const RenderArgs &a, int mode, uint32_t rec_cap, hipStream_t stream, bool launch, char *name, size_t name_cap, int fill)
+// e.targ = WLOG, MODE (0 winding_i16, 1 gray_debug, 2 mask, 3 sign bits: one per pixel, job-local bit plane), RPL.
+hipError_t launch_win1(const RenderArgs &a, const RasterLaunch &e, hipStream_t stream)
 {
-    const dim3 grid(launch ? (uint32_t)((size_t)a.n_jobs * a.band_groups * a.strips) : 0u);
-    if (fill) return win1_launch_strip<1>(a, mode, rec_cap, grid, stream, name, name_cap);
-    return win1_launch_strip<0>(a, mode, rec_cap, grid, stream, name, name_cap);
+    const dim3 grid((uint32_t)((size_t)a.n_jobs * a.band_groups * a.strips)), block(64 * C4_WAVES);
+    const int key[] = {e.targ[0], e.targ[1], e.targ[2], e.fill};
+    return pick(key, [&](auto WLOG, auto MODE, auto RPL, auto FILL) {
+        return launch_kernel(win1_instance<WLOG, MODE, RPL, FILL>(), grid, block, W1Lds<WLOG, RPL>::TOTAL + a.lds_pad, stream, a);
+    }, Among<2, 3, 4>{}, Among<MODE1_WINDING_I16, MODE1_GRAY_DEBUG, MODE1_MASK, MODE1_BITS>{}, Among<2, 4, 8, 16>{}, Among<0, 1>{});
 }
 
 }  // namespace fr

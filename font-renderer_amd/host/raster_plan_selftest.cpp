@@ -1,6 +1,7 @@
 // raster_plan_selftest.cpp — the host rules of raster plans (csrc/fr_raster_plan.cpp) on the CPU: links fr_raster_plan.o
 // and nothing else of the library.  Every case is a synthetic number table (no font, no GPU); it prints one line per case,
 //   <case> <what the rule returned, field by field>
+// (name/ lines: the kernel instances of a launch list as raster_launch_name prints them, each with its job count)
 // which tests/test_raster_plan_tables.py compares with tests/golden/raster_plan_tables.json.  Job orders and tables of
 // more than 16 entries are printed as an FNV-1a 64 hash.
 #include "../csrc/fr_raster_plan.hpp"
@@ -20,7 +21,7 @@ namespace {
 struct G { uint32_t nseg, root, ray; };
 const G GLYPHS[] = {{10, 20, 4}, {200, 200, 10}, {300, 400, 10}, {700, 900, 10}, {800, 900, 10}, {129, 100, 4}, {0, 0, 0}, {129, 2000, 4}};
 
-const fr::RasterOpts DEFAULTS = {256u, 1u, 1u, 2048u, 1u, 4u, 4u};   // the context's defaults; both kernels: 4 waves
+const fr::RasterOpts DEFAULTS = {256u, 1u, 1u, 2048u, 1u, 4u, 4u, 32u};   // the context's defaults; both kernels: 4 waves
 
 std::string fmt(const char *f, ...)
 {
@@ -71,6 +72,40 @@ std::string launches(const fr::RasterPlan &p, const fr_raster_params &prm, uint3
                  e.samples, e.first, e.cnt, e.strip_w, e.rec_cap, e.bands, e.strips, (int)e.uniform, e.bands_per_wg, e.band_groups, (int)e.largest);
     }
     return s;
+}
+
+// the list's kernels as fr_plan_describe names them, in launch order (prepare launches have no name)
+std::string names(const fr::RasterPlan &p, const fr_raster_params &prm, uint32_t flags, const fr::RasterOpts &o, uint32_t max_seg)
+{
+    fr::RasterLaunchList L;
+    fr::raster_launches(p, prm, flags, o, max_seg, L);
+    std::string s;
+    for (uint32_t i = 0; i < L.n; ++i) {
+        char name[96];
+        fr::raster_launch_name(L.l[i], name, sizeof name);
+        if (name[0]) s += fmt("%s%s x%u", s.empty() ? "" : "; ", name, L.l[i].cnt);
+    }
+    return s;
+}
+
+// the name of one launch: a hand-made plan of one job, on the fast kernels (a part of strips 16 << wlog with rec_cap
+// record slots) or, rec_cap = 0, on the general one (strips of strip_w pixels)
+std::string one_name(const fr_raster_params &prm, uint32_t flags, uint32_t kmax, uint32_t wlog, uint32_t rec_cap, uint32_t strip_w = 0,
+                     bool uniform = false)
+{
+    fr::RasterOpts o = DEFAULTS;
+    o.kmax = kmax;
+    fr::RasterPlan p;
+    p.n_jobs = p.pixels = 1;
+    if (rec_cap) {
+        p.n_fast = p.n_parts = 1;
+        p.parts[0] = fr::RasterPart{0, 1, wlog, rec_cap, 1, 1, 1};
+        p.fast_ns = fr::fast_rule(o, &prm).ns;
+    } else {
+        p.strip_w = strip_w; p.gen_bands = p.gen_strips = 1; p.uniform = uniform;
+    }
+    const std::string s = names(p, prm, flags, o, 0u);
+    return s.substr(0, s.find(" x"));                                   // (FR_SDF_U8: the sign pass, not the distance kernel behind it)
 }
 
 struct Built {
@@ -130,6 +165,7 @@ void plan_case(const char *name, const std::vector<fr_job> &jobs, const fr_raste
         o.overlap = ov;
         printf("launch/%s/overlap%u %s\n", name, ov, launches(b.p, prm, flags, o, 800u).c_str());
     }
+    printf("name/plan/%s %s\n", name, names(b.p, prm, flags, o, 800u).c_str());
 }
 
 void single_case(const char *name, uint32_t w, uint32_t h, int mode, G g, fr::RasterOpts o = DEFAULTS, bool merge = false, bool uniform = false)
@@ -139,6 +175,7 @@ void single_case(const char *name, uint32_t w, uint32_t h, int mode, G g, fr::Ra
     build({job(0, w, h)}, prm, o, b, true, &g, merge, uniform);
     printf("single/%s n_fast=%u n_large=%u bit_plane=%d %s\n", name, b.p.n_fast, b.p.n_large, (int)b.p.bit_plane,
            launches(b.p, prm, 0u, o, g.nseg).c_str());
+    printf("name/single/%s %s\n", name, names(b.p, prm, 0u, o, g.nseg).c_str());
 }
 
 void bounds_case(const char *name, const std::vector<int16_t> &xy)         // xy: 6 numbers per segment (p0, p1, p2)
@@ -305,6 +342,35 @@ int main()
     single_case("129seg_fast", 47, 45, FR_MASK_NONZERO, GLYPHS[5]);
     single_case("0seg", 47, 45, FR_GRAY_DEBUG, GLYPHS[6]);
     single_case("2049rows", 10, 2049, FR_GRAY_DEBUG, GLYPHS[0]);
+    // ---- option kmax on both sides of 8, 16 and 32: the four record classes of cov4_kernel and the general kernel
+    for (uint32_t kmax : {1u, 8u, 9u, 16u, 17u, 32u, 128u}) {
+        for (uint32_t rec_cap : {128u, 256u, 512u, 1024u})
+            printf("name/kmax%u/cov4_rec%u %s\n", kmax, rec_cap, one_name(cov4, 0u, kmax, 4u, rec_cap).c_str());
+        printf("name/kmax%u/render %s\n", kmax, one_name(cov4, 0u, kmax, 0u, 0u, 256u).c_str());
+    }
+    // ---- every instance the rules can name: each value of each template argument, both fill rules
+    for (uint32_t flags : {0u, (uint32_t)FR_FILL_CONSISTENT}) {
+        std::string s;
+        auto add = [&](const std::string &name) { if (s.find(name + ";") == std::string::npos) s += name + "; "; };   // (each once)
+        for (int ns : {2, 4})
+            for (uint32_t wlog : {2u, 3u, 4u})
+                for (uint32_t rec_cap : {128u, 256u, 512u, 1024u})
+                    for (uint32_t kmax : {8u, 16u, 32u}) add(one_name(params(FR_COVERAGE_U8, ns), flags, kmax, wlog, rec_cap));
+        printf("name/sweep/cov4/fill%u %s\n", flags, s.c_str());
+        s.clear();
+        for (int mode : {FR_WINDING_I16, FR_GRAY_DEBUG, FR_MASK_NONZERO, FR_COVERAGE_U8, FR_SDF_U8})
+            for (uint32_t wlog : {2u, 3u, 4u})
+                for (uint32_t rec_cap : {128u, 256u, 512u, 1024u}) add(one_name(params(mode, 1), flags, 32u, wlog, rec_cap));
+        printf("name/sweep/win1/fill%u %s\n", flags, s.c_str());
+        s.clear();
+        for (int mode : {FR_WINDING_I16, FR_GRAY_DEBUG, FR_MASK_NONZERO, FR_COVERAGE_U8, FR_SDF_U8})
+            for (int n : {1, 2, 4})
+                for (uint32_t kmax : {8u, 16u, 32u})
+                    for (uint32_t strip_w : {48u, 64u, 128u, 256u})
+                        for (bool uniform : {false, true})
+                            if (n == 1 || mode == FR_COVERAGE_U8) add(one_name(params(mode, n), flags, kmax, 0u, 0u, strip_w, uniform));
+        printf("name/sweep/render/fill%u %s\n", flags, s.c_str());
+    }
     // ---- root and ray bounds of hand-written segments
     bounds_case("line", {0, 0, 5, 5, 10, 10});
     bounds_case("horizontal", {0, 7, 5, 7, 10, 7});

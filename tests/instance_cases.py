@@ -2,8 +2,9 @@
 of the instance a plan gets.  Pure Python: no GPU, no library call.
 
 The raster side is one algorithm compiled into 246 instances (fr_cov4.hip, fr_win1.hip, fr_render.hip); which one a
-job gets is decided on the host in fr_raster_plan.cpp (fast_rule, fast_class, merge_small_classes) and in the launch
-functions.  `predicted_name` restates those rules, glyph_root_bound and glyph_ray_bound included, and returns the
+job gets is decided on the host in fr_raster_plan.cpp (fast_rule, fast_class, merge_small_classes and, for the
+instance's template arguments, raster_launches), which also names it (raster_launch_name).  `predicted_name` restates
+those rules, glyph_root_bound and glyph_ray_bound included, and returns the
 string fr_plan_describe prints for the plan's kernel.  `expected_instances` is written from the template parameter
 products alone, independently of the case table; tests/test_instance_cases.py holds the two together and
 tests/test_gpu_instances.py renders every case against a CPU reference."""
@@ -126,10 +127,10 @@ def predicted_name(case):
     tail = ", 1>" if case.fill else ">"
     if cls:
         wlog, rpl = 2 + (cls - 1) // 4, 2 << ((cls - 1) % 4)
-        if fast_ns(case.family, case.mode, case.n) == 1:                       # win1_launch_*
+        if fast_ns(case.family, case.mode, case.n) == 1:                       # raster_launches: a fast part
             m = {WINDING_I16: 0, GRAY_DEBUG: 1, SDF_U8: 3}.get(case.mode, 2)
             return f"fr::win1_kernel<{wlog}, {m}, {rpl}{tail}"
-        kmax = 16 if (rpl == 2 and case.kmax > 16) else case.kmax              # cov4_launch_cap
+        kmax = 16 if (rpl == 2 and case.kmax > 16) else case.kmax              # (its two exceptions for CAP)
         cap = 32 if rpl >= 16 else _cap(kmax)
         return f"fr::cov4_kernel<{wlog}, {cap}, {rpl}, {case.n}{tail}"
     # the general kernel: strip width from the widest job, uniform = every strip and every wave band full

@@ -3,7 +3,11 @@ the bit plane and the second prepare all occur.  Two fast parts (64 cells of 20 
 16 x 520 of a 200-segment glyph, which at 4 x 4 samples is the general kernel's (2 080 sample rows) and needs
 prepare_kernel: as coverage, as FR_SDF_U8 and under FR_FILL_CONSISTENT.  fr_plan_describe must return exactly the string
 tests/golden/raster_plan_describe.json holds — minted from the library as it was before the plan rules left fr_api.hip —
-and a render with option overlap = 0 and = 2 must equal the CPU reference byte for byte."""
+and a render with option overlap = 0 and = 2 must equal the CPU reference byte for byte.
+Option kmax picks the CAP instance (raster_launches): a plan of two 20 x 20 coverage cells under kmax on both sides of 8, 16
+and 32, on the fast kernels and on the general one, must be described as the library described it while the launch
+functions still chose the instance (the golden file's "kmax<k>/cov4_<c>" strings), and must render the same bytes under
+every kmax."""
 import functools
 import json
 import os
@@ -85,4 +89,45 @@ def test_describe_is_the_parents_and_both_stream_layouts_render_the_reference(ct
             assert np.array_equal(got, ref), (name, overlap, text)
     finally:
         ctx.set_option("overlap", 1)                       # (the default; the library has no call that reads an option back)
+        dgs.close()
+
+
+KMAX = (1, 8, 9, 16, 17, 32, 128)
+KMAX_SHAPE = (24, 47)
+
+
+def kmax_jobs():
+    """two 20 x 20 cells, one of each 40-segment glyph"""
+    jobs = glyphs_and_jobs()[1][[0, 64]].copy()
+    jobs["w"], jobs["h"], jobs["out_x"], jobs["out_y"] = 20, 20, (1, 24), 2
+    return jobs
+
+
+def test_describe_under_every_kmax_is_the_parents_and_the_renders_are_one(ctx, oracle):
+    gs, jobs = glyphs_and_jobs()[0], kmax_jobs()
+    with open(GOLDEN) as f:
+        want = json.load(f)
+    ref = np.full(KMAX_SHAPE, SENT, np.uint8)
+    oracle.render_batch(gs, jobs, O.COVERAGE_U8, ref, 4, True)
+    assert (ref != SENT).any() and (ref[0] == SENT).all() and (ref[:, 0] == SENT).all()
+    dgs = fr.DeviceGlyphSet(ctx, gs)
+    try:
+        for cov4 in (1, 0):
+            ctx.set_option("cov4", cov4)
+            got = {}
+            for kmax in KMAX:
+                ctx.set_option("kmax", kmax)
+                plan = fr.Plan(dgs, jobs, fr.FR_COVERAGE_U8, 4, fr.FR_SAMPLE_CENTER, 0)
+                text, stats = plan.describe(), plan.stats()
+                plan.close()
+                assert text == want[f"kmax{kmax}/cov4_{cov4}"], (kmax, cov4)
+                assert stats == ({"jobs_cov4": 2, "jobs_general": 0} if cov4 else {"jobs_cov4": 0, "jobs_general": 2})
+                got[kmax] = np.full(KMAX_SHAPE, SENT, np.uint8)
+                rg.render_batch(dgs, jobs, fr.FR_COVERAGE_U8, got[kmax], 4, fr.FR_SAMPLE_CENTER, 0)
+            for kmax in KMAX:
+                assert np.array_equal(got[kmax], got[32]), (kmax, cov4)
+                assert np.array_equal(got[kmax], ref), (kmax, cov4)
+    finally:
+        ctx.set_option("kmax", 32)                         # (the defaults)
+        ctx.set_option("cov4", 1)
         dgs.close()

@@ -2,7 +2,8 @@
 fast_class, merge_small_classes, split_bands, the plan builder with its launch list, the single-glyph call's use of it
 and the two glyph bounds on synthetic number tables and prints one line per case.
 tests/golden/raster_plan_tables.json holds those lines as minted from the rules' text as it stood in fr_api.hip, moved
-but not yet restructured."""
+but not yet restructured; its name/ lines (the kernel instance of every launch, raster_launch_name) were minted when the
+launch list began to carry the instance."""
 import json
 import os
 import subprocess
@@ -40,3 +41,13 @@ def test_bounds_match_the_python_restatement():
         fields = dict(f.split("=") for f in text.split(" "))
         segs = np.array([int(v) for v in fields["segs"].split(",") if v], np.int64).reshape(-1, 3, 2)
         assert (int(fields["root"]), int(fields["ray"])) == (ic.root_bound(segs), ic.ray_bound(segs)), name
+
+
+def test_the_rules_name_exactly_the_expected_instances():
+    """the name/sweep/ lines — every value the rules can give each template argument, both fill rules — against
+    expected_instances of instance_cases.py, written from the template parameter products: none missing, none extra"""
+    named = [n for k, v in _lines().items() if k.startswith("name/sweep/") for n in v.split("; ") if n]
+    want = ic.expected_instances()
+    assert len(want) == len(set(want)) == 246
+    assert len(named) == len(set(named)), "a sweep line names an instance twice"
+    assert set(named) == set(want), (sorted(set(want) - set(named)), sorted(set(named) - set(want)))
