@@ -34,6 +34,8 @@ pub const FR_TEXT_BGRA: u32 = 4;
 pub const FR_TEXT_SRGB: u32 = 8;
 /// flag of fr_text_plan_create_rgba only (fr_raster.h): draw over the pixels already in the output
 pub const FR_TEXT_LOAD: u32 = 32;
+/// flag of the four upright and _ex text plan entry points (fr_raster.h): rasterise each distinct glyph image once per render
+pub const FR_TEXT_CACHE: u32 = 128;
 
 pub const RasterParams = extern struct {
     mode: i32,

@@ -11,6 +11,7 @@ FR_SAMPLE_CORNER, FR_SAMPLE_CENTER = 0, 1
 FR_FILL_CONSISTENT = 1           # crossing-rule flag of the _ex entry points (include/fr_raster.h)
 FR_TEXT_SRGB, FR_TEXT_BGRA = 8, 4  # flags of fr_text_plan_create_rgba only: linear-light blending, B G R A output
 FR_TEXT_LOAD = 32                  # fr_text_plan_create_rgba only: draw over the pixels already in the output
+FR_TEXT_CACHE = 128                # the upright and _ex text plans: each distinct glyph image made once per render, same bytes
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 

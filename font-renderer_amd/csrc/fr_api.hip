@@ -152,6 +152,13 @@ struct fr_plan {
     uint32_t *d_tlist = nullptr, *d_tglyphs = nullptr, *d_trec_count = nullptr;
     fr::Rec *d_trecs = nullptr;
     uint32_t n_tiles = 0, n_insts = 0, n_tglyphs = 0;
+    // FR_TEXT_CACHE with at least one mask cell: d_insts holds TextCachedInst, and a render fills the mask store from the
+    // cells' tiles between the prepare kernel and the composite (fr_text_cached.hip)
+    bool cached = false;
+    fr::TextMaskCell *d_mcells = nullptr;
+    fr::TextMaskTile *d_mtiles = nullptr;
+    uint16_t *d_masks = nullptr;
+    uint32_t n_mcells = 0, n_mtiles = 0;
 };
 
 template <class T> static void dfree(T *&p) { if (p) { (void)hipFree(p); p = nullptr; } }
@@ -228,11 +235,35 @@ static hipError_t text_args_launch(const fr_plan *plan, void *out_dev, size_t ou
 static hipError_t text_plan_launch(const fr_plan *plan, void *out_dev, size_t out_stride, uint32_t n_tiles, char *name = nullptr,
                                    size_t name_cap = 0)
 {
+    if (plan->cached) {
+        fr::TextCachedArgs a;
+        a.tiles = plan->d_tiles; a.runs = plan->d_runs; a.list = plan->d_tlist;
+        a.insts = static_cast<const fr::TextCachedInst *>(plan->d_insts);
+        a.recs = nullptr; a.rec_count = nullptr;
+        a.out = static_cast<uint8_t *>(out_dev);
+        a.out_stride = out_stride;
+        a.phase_center = plan->params.sample_phase == FR_SAMPLE_CENTER ? 1 : 0;
+        a.masks = plan->d_masks;
+        return fr::launch_text_cached(a, plan->params.samples_per_axis, plan->rgba, plan->blend, plan->srgb, plan->load, n_tiles,
+                                      plan->ctx->stream, name, name_cap);
+    }
     switch (plan->text_form) {
     case TEXT_AFFINE: return text_args_launch<fr::TextAffineArgs>(plan, out_dev, out_stride, n_tiles, name, name_cap);
     case TEXT_EX: return text_args_launch<fr::TextPlaceArgs>(plan, out_dev, out_stride, n_tiles, name, name_cap);
     default: return text_args_launch<fr::TextArgs>(plan, out_dev, out_stride, n_tiles, name, name_cap);
     }
+}
+
+// a cached plan's mask launch: glyph_mask_kernel over n_tiles mask tiles; n_tiles = 0: only names it
+static hipError_t text_mask_launch(const fr_plan *plan, uint32_t n_tiles, char *name = nullptr, size_t name_cap = 0)
+{
+    fr::TextMaskArgs a;
+    a.tiles = plan->d_mtiles; a.cells = plan->d_mcells;
+    a.recs = plan->d_trecs; a.rec_count = plan->d_trec_count;
+    a.masks = plan->d_masks;
+    a.phase_center = plan->params.sample_phase == FR_SAMPLE_CENTER ? 1 : 0;
+    return fr::launch_glyph_mask(a, plan->params.samples_per_axis, (plan->flags & FR_FILL_CONSISTENT) ? 1 : 0, n_tiles, plan->ctx->stream,
+                                 name, name_cap);
 }
 
 extern "C" {
@@ -462,6 +493,7 @@ void fr_plan_destroy(fr_plan *plan)
     dfree(plan->d_jobs); dfree(plan->d_job_seg); dfree(plan->d_large); dfree(plan->d_bits); dfree(plan->d_job_bits);
     dfree(plan->d_tiles); dfree(plan->d_runs); dfree(plan->d_insts); dfree(plan->d_tlist); dfree(plan->d_tglyphs);
     dfree(plan->d_trec_count); dfree(plan->d_trecs);
+    dfree(plan->d_mcells); dfree(plan->d_mtiles); dfree(plan->d_masks);
     if (plan->ev0) (void)hipEventDestroy(plan->ev0);
     if (plan->ev1) (void)hipEventDestroy(plan->ev1);
     if (plan->gexec) (void)hipGraphExecDestroy(plan->gexec);
@@ -469,7 +501,7 @@ void fr_plan_destroy(fr_plan *plan)
 }
 
 // also: the bits an entry point takes besides FR_FILL_CONSISTENT (fr_text_plan_create_rgba: FR_TEXT_SRGB, FR_TEXT_BGRA,
-// FR_TEXT_LOAD)
+// FR_TEXT_LOAD; the four upright and _ex text entry points: FR_TEXT_CACHE)
 static int check_flags(uint32_t flags, uint32_t also = 0u)
 {
     const uint32_t known = (uint32_t)FR_FILL_CONSISTENT | also;
@@ -580,8 +612,9 @@ int fr_glyphset_set_boxes(fr_glyphset *gs, const int16_t *boxes)
 
 // uploads the tables of text_plan_tables (fr_text_plan.hpp) and fills the text fields of a plan that its caller destroys on
 // failure
+// `cache`: the tables of text_cache_tables for a plan that renders through its mask cells (else NULL)
 template <class PLACE>
-static int text_plan_upload(const char *fn, fr_plan *p, const fr::TextPlanTables<PLACE> &t)
+static int text_plan_upload(const char *fn, fr_plan *p, const fr::TextPlanTables<PLACE> &t, const fr::TextCacheTables *cache)
 {
     fr_ctx *ctx = p->ctx;
     const fr_glyphset *gs = p->gs;
@@ -599,7 +632,16 @@ static int text_plan_upload(const char *fn, fr_plan *p, const fr::TextPlanTables
     };
     upload(p->d_tiles, t.tiles);
     upload(p->d_runs, t.runs);
-    upload(p->d_insts, t.insts);
+    if (cache) {
+        p->cached = true;
+        p->n_mcells = (uint32_t)cache->cells.size(); p->n_mtiles = (uint32_t)cache->tiles.size();
+        upload(p->d_insts, cache->insts);
+        upload(p->d_mcells, cache->cells);
+        upload(p->d_mtiles, cache->tiles);
+        if (e == hipSuccess) e = hipMalloc(&p->d_masks, (size_t)cache->elems * sizeof(uint16_t));
+    } else {
+        upload(p->d_insts, t.insts);
+    }
     upload(p->d_tlist, t.list);
     upload(p->d_tglyphs, t.glyphs);
     if (e == hipSuccess && p->n_tglyphs) e = hipMalloc(&p->d_trecs, 2 * (size_t)gs->n_seg * sizeof(fr::Rec));
@@ -628,7 +670,8 @@ static int text_plan_create(const char *fn, fr_ctx *ctx, const fr_glyphset *gs, 
 {
     if (!ctx || !gs || !out) return fail(FR_E_INVALID, "%s: NULL argument", fn);
     *out = nullptr;
-    if (const int frc = check_flags(flags, rgba ? FR_TEXT_SRGB | FR_TEXT_BGRA | FR_TEXT_LOAD : 0u)) return frc;
+    constexpr bool can_cache = !std::is_same<PLACE, fr_glyph_place_affine>::value;
+    if (const int frc = check_flags(flags, (rgba ? FR_TEXT_SRGB | FR_TEXT_BGRA | FR_TEXT_LOAD : 0u) | (can_cache ? FR_TEXT_CACHE : 0u))) return frc;
     if (gs->ctx != ctx) return fail(FR_E_INVALID, "glyph set belongs to another context");
     if (!params) return fail(FR_E_INVALID, "params is NULL");
     if (params->mode < FR_WINDING_I16 || params->mode > FR_SDF_U8) return fail(FR_E_INVALID, "unknown mode %d", params->mode);
@@ -653,6 +696,13 @@ static int text_plan_create(const char *fn, fr_ctx *ctx, const fr_glyphset *gs, 
     in.glyph_seg_start = gs->h_glyph_seg_start.data(); in.n_glyphs = gs->n_glyphs;
     fr::TextPlanTables<PLACE> t;
     if (const int rc = fr::text_plan_tables(in, places, t)) return rc;
+    // FR_TEXT_CACHE: the mask cells and the composite records (a plan whose placements are all clipped away has no cell
+    // and stays the plan it is without the flag); the 2^31-element limit answers here, before anything is allocated
+    fr::TextCacheTables cache;
+    if constexpr (can_cache) {
+        if (flags & FR_TEXT_CACHE)
+            if (const int rc = fr::text_cache_tables(in, places, t, cache)) return rc;
+    }
 
     fr_plan *p = new (std::nothrow) fr_plan;
     if (!p) return fail(FR_E_NOMEM, "%s: host allocation", fn);
@@ -660,7 +710,7 @@ static int text_plan_create(const char *fn, fr_ctx *ctx, const fr_glyphset *gs, 
     p->rgba = rgba;
     p->srgb = (flags & FR_TEXT_SRGB) != 0;
     p->load = (flags & FR_TEXT_LOAD) != 0;
-    if (const int rc = text_plan_upload(fn, p, t)) {
+    if (const int rc = text_plan_upload(fn, p, t, cache.cells.empty() ? nullptr : &cache)) {
         fr_plan_destroy(p);
         return rc;
     }
@@ -758,6 +808,10 @@ int fr_plan_describe(const fr_plan *plan, char *buf, size_t cap)
     if (plan->text) {
         if (plan->n_tglyphs) add(fill ? "fr::prepare_fill_kernel" : "fr::prepare_kernel", plan->n_tglyphs);
         name[0] = 0;
+        if (plan->cached) {
+            (void)text_mask_launch(plan, 0u, name, sizeof name);
+            add(name, plan->n_mcells);
+        }
         (void)text_plan_launch(plan, nullptr, 0, 0u, name, sizeof name);
         if (plan->n_tiles) add(name, plan->n_insts);
         return FR_OK;
@@ -803,7 +857,8 @@ static int plan_check(fr_plan *plan, void *out_dev, size_t out_stride, size_t ou
 }
 
 // one render of a text plan: the records of its glyphs from their points (plan-owned, so a plain plan's records are
-// never touched), then text_kernel over every tile of every run — two launches in stream order, nothing to fork
+// never touched), then text_kernel over every tile of every run — two launches in stream order, nothing to fork.
+// An FR_TEXT_CACHE plan fills its mask cells from the records in between: three launches in stream order
 static int text_launch(fr_plan *plan, void *out_dev, size_t out_stride)
 {
     if (plan->n_tiles == 0) return FR_OK;
@@ -815,6 +870,7 @@ static int text_launch(fr_plan *plan, void *out_dev, size_t out_stride)
                            plan->d_trecs, plan->d_trec_count, st, fill);
         HIP_TRY(hipGetLastError());
     }
+    if (plan->cached) HIP_TRY(text_mask_launch(plan, plan->n_mtiles));
     HIP_TRY(text_plan_launch(plan, out_dev, out_stride, plan->n_tiles));
     return FR_OK;
 }

@@ -30,4 +30,25 @@ template <class ARGS>
 hipError_t launch_text(const ARGS &a, int n, int fill, int rgba, int blend, int srgb, int load, uint32_t n_tiles, hipStream_t stream,
                        char *name = nullptr, size_t name_cap = 0);
 
+// ---- FR_TEXT_CACHE plans (fr_text_cached.hip) ---------------------------------------------------------------------------
+struct TextMaskArgs {      // what glyph_mask_kernel reads and writes
+    const TextMaskTile *tiles;
+    const TextMaskCell *cells;
+    const Rec *recs;
+    const uint32_t *rec_count;
+    uint16_t *masks;       // the mask store
+    int32_t phase_center;
+};
+struct TextCachedArgs : TextTables<TextCachedInst> {   // the text_cached_*_kernel instances (recs and rec_count are not read)
+    const uint16_t *masks;
+};
+
+// Fills every mask cell: glyph_mask_kernel<n, fill> over n_tiles mask tiles.  n_tiles = 0: only names the instance.
+hipError_t launch_glyph_mask(const TextMaskArgs &a, int n, int fill, uint32_t n_tiles, hipStream_t stream, char *name = nullptr,
+                             size_t name_cap = 0);
+// The composite of a cached plan over n_tiles run tiles; the parameters as launch_text's, without the fill rule (it acts
+// only where masks are made).  n_tiles = 0: only names the instance.
+hipError_t launch_text_cached(const TextCachedArgs &a, int n, int rgba, int blend, int srgb, int load, uint32_t n_tiles,
+                              hipStream_t stream, char *name = nullptr, size_t name_cap = 0);
+
 }  // namespace fr

@@ -1,0 +1,148 @@
+// fr_text_cached.hip — FR_TEXT_CACHE text plans (include/fr_raster.h, DESIGN.md sections 4.7 and 5): each distinct (glyph,
+// pen fraction, scale, slant) key of a plan is rasterised once per render into a mask cell, and every instance of the key
+// reads its masks from that cell.  An instance's n^2-bit mask at a pixel depends only on the key and on the pixel's offset
+// from the pen's whole-pixel part, so the bytes are those of the plan without the flag.
+//
+// glyph_mask_kernel: one workgroup of four waves per 64 x 16 tile of a mask cell, a wave on every fourth row, one cell
+// column per lane.  The cell is an instance in the TextInstEx layout whose image is the whole cell (fr_text_tables.hpp), and
+// the mask is the text of fr_text_mask_kernel.inc with PLACE = true, exactly as the cover body includes it; with fy = 0 and
+// slant 0 that arithmetic is the upright form's bit for bit (include/fr_raster.h), so the six instances N x FILL serve both
+// placement forms.  Every element of the cell is stored: 0 where the winding is zero.
+//
+// text_cached_*_kernel: the two row bodies of fr_text.hip — tile walk, row loop, instance loops, colour arithmetic, LOAD,
+// sRGB, stores — compiled here with FR_TEXT_MASK_CACHED, which replaces the evaluation of an instance's mask by one 2-byte
+// load from its key's cell, issued by the lanes inside the clipped cell only.  A preprocessor switch and a translation
+// unit of its own: the 162 instances of fr_text.hip and fr_text_affine.hip compile from the text they had.  The fill
+// rule acts only where masks are made, and one record (TextCachedInst) serves both placement forms, so these instances
+// carry neither FILL nor a form.
+#include "fr_text.hpp"
+#include "fr_text_colour.hpp"
+#include "fr_srgb.hpp"
+#include "fr_wave.hpp"
+
+#include <cstdio>
+#include <type_traits>
+
+namespace fr {
+
+#define FR_TEXT_GLOBAL __global__ __launch_bounds__(64 * TEXT_WAVES) void
+template <int N, int FILL>
+FR_TEXT_GLOBAL glyph_mask_kernel(TextMaskArgs a)
+{
+    constexpr bool PLACE = true;
+    const TextMaskTile tl = a.tiles[blockIdx.x];
+    const TextMaskCell *cl = a.cells + tl.cell;
+    const dependent_t<N, TextInstEx> in = cl->in;
+    [[maybe_unused]] const dependent_t<N, TextRun> rn{};                   // (named by the other form's branch of the mask text)
+    uint16_t *cell = a.masks + cl->base;
+    const int lane = (int)(threadIdx.x & 63u);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int X = (int)tl.x0 + lane;
+    float off[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) off[k] = sub_off(k, N, a.phase_center);
+    for (int yy = wave; yy < TEXT_TILE_H; yy += TEXT_WAVES) {
+        const int Y = (int)tl.y0 + yy;
+        if (Y >= in.y1) break;                                             // (x1 = cw, y1 = ch: the whole cell)
+        uint32_t m;
+#include "fr_text_mask_kernel.inc"
+        if (X < in.x1) cell[(uint32_t)Y * (uint32_t)in.x1 + (uint32_t)X] = (uint16_t)m;
+    }
+}
+
+#define FR_TEXT_MASK_CACHED 1
+template <int N>
+FR_TEXT_GLOBAL text_cached_kernel(TextCachedArgs a)
+{
+    using INST = TextCachedInst;
+#include "fr_text_cover_kernel.inc"
+}
+template <int N, int BLEND, bool SRGB, bool LOAD>
+__device__ __forceinline__ void cached_colour_rows(const TextCachedArgs &a)
+{
+    using INST = TextCachedInst;
+#include "fr_text_colour_kernel.inc"
+}
+template <int N, int BLEND>
+FR_TEXT_GLOBAL text_cached_rgba_kernel(TextCachedArgs a) { cached_colour_rows<N, BLEND, false, false>(a); }
+template <int N, int BLEND>
+FR_TEXT_GLOBAL text_cached_srgb_kernel(TextCachedArgs a) { cached_colour_rows<N, BLEND, true, false>(a); }
+template <int N, int BLEND>
+FR_TEXT_GLOBAL text_cached_rgba_load_kernel(TextCachedArgs a) { cached_colour_rows<N, BLEND, false, true>(a); }
+template <int N, int BLEND>
+FR_TEXT_GLOBAL text_cached_srgb_load_kernel(TextCachedArgs a) { cached_colour_rows<N, BLEND, true, true>(a); }
+#undef FR_TEXT_MASK_CACHED
+#undef FR_TEXT_GLOBAL
+
+namespace {
+
+struct Launch {
+    uint32_t n_tiles;
+    hipStream_t stream;
+    char *name;
+    size_t name_cap;
+};
+
+template <int N, int FILL>
+hipError_t mask_instance(const TextMaskArgs &a, const Launch &l)
+{
+    if (l.name) snprintf(l.name, l.name_cap, "fr::glyph_mask_kernel<%d, %d>", N, FILL);      // as rocprofv3 names the instance
+    if (!l.n_tiles) return hipSuccess;
+    hipLaunchKernelGGL((glyph_mask_kernel<N, FILL>), dim3(l.n_tiles), dim3(64 * TEXT_WAVES), 0, l.stream, a);
+    return hipGetLastError();
+}
+
+// FAM: 0 coverage (no BLEND), 1 rgba, 2 srgb, 3 rgba load, 4 srgb load
+template <int FAM, int BLEND, int N>
+hipError_t cached_instance(const TextCachedArgs &a, const Launch &l)
+{
+    constexpr const char *family[5] = {"", "rgba_", "srgb_", "rgba_load_", "srgb_load_"};
+    void (*kernel)(TextCachedArgs);
+    if constexpr (FAM == 0) kernel = text_cached_kernel<N>;
+    else if constexpr (FAM == 1) kernel = text_cached_rgba_kernel<N, BLEND>;
+    else if constexpr (FAM == 2) kernel = text_cached_srgb_kernel<N, BLEND>;
+    else if constexpr (FAM == 3) kernel = text_cached_rgba_load_kernel<N, BLEND>;
+    else kernel = text_cached_srgb_load_kernel<N, BLEND>;
+    if (l.name) {
+        if constexpr (FAM == 0) snprintf(l.name, l.name_cap, "fr::text_cached_kernel<%d>", N);
+        else snprintf(l.name, l.name_cap, "fr::text_cached_%skernel<%d, %d>", family[FAM], N, BLEND);
+    }
+    if (!l.n_tiles) return hipSuccess;
+    hipLaunchKernelGGL(kernel, dim3(l.n_tiles), dim3(64 * TEXT_WAVES), 0, l.stream, a);
+    return hipGetLastError();
+}
+
+template <int FAM, int BLEND>
+hipError_t cached_n(const TextCachedArgs &a, int n, const Launch &l)
+{
+    if (n == 4) return cached_instance<FAM, BLEND, 4>(a, l);
+    if (n == 2) return cached_instance<FAM, BLEND, 2>(a, l);
+    return cached_instance<FAM, BLEND, 1>(a, l);
+}
+
+template <int FAM>
+hipError_t cached_family(const TextCachedArgs &a, int n, int blend, const Launch &l)
+{
+    return blend ? cached_n<FAM, 1>(a, n, l) : cached_n<FAM, 0>(a, n, l);
+}
+
+}  // namespace
+
+hipError_t launch_glyph_mask(const TextMaskArgs &a, int n, int fill, uint32_t n_tiles, hipStream_t stream, char *name, size_t name_cap)
+{
+    const Launch l{n_tiles, stream, name, name_cap};
+    if (n == 4) return fill ? mask_instance<4, 1>(a, l) : mask_instance<4, 0>(a, l);
+    if (n == 2) return fill ? mask_instance<2, 1>(a, l) : mask_instance<2, 0>(a, l);
+    return fill ? mask_instance<1, 1>(a, l) : mask_instance<1, 0>(a, l);
+}
+
+hipError_t launch_text_cached(const TextCachedArgs &a, int n, int rgba, int blend, int srgb, int load, uint32_t n_tiles,
+                              hipStream_t stream, char *name, size_t name_cap)
+{
+    const Launch l{n_tiles, stream, name, name_cap};
+    if (!rgba) return cached_n<0, 0>(a, n, l);
+    if (load) return srgb ? cached_family<4>(a, n, blend, l) : cached_family<3>(a, n, blend, l);
+    return srgb ? cached_family<2>(a, n, blend, l) : cached_family<1>(a, n, blend, l);
+}
+
+}  // namespace fr

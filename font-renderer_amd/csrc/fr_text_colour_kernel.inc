@@ -1,5 +1,6 @@
 // fr_text_colour_kernel.inc — the rows of one tile as RGBA pixels: the body of colour_rows and of text_rgba_load_kernel
 // (fr_text.hip, which describes it), and of affine_colour_rows (fr_text_affine.hip).  Uses INST, N, FILL, BLEND, SRGB, LOAD, PLACE, a.
+// With FR_TEXT_MASK_CACHED defined (fr_text_cached.hip only) the masks are loaded from a.masks: see fr_text_cover_kernel.inc.
     constexpr uint32_t NN = (uint32_t)(N * N);
     constexpr uint32_t FULL = NN == 32u ? ~0u : (1u << NN) - 1u;
     constexpr uint32_t LG = N == 4 ? 4u : N == 2 ? 2u : 0u;              // log2(n^2)
@@ -38,11 +39,16 @@
                 if (Y < in.y0 || Y >= in.y1) continue;                   // (wave-uniform)
                 const bool inside = X >= in.x0 && X < in.x1;
                 uint32_t m;
+#ifdef FR_TEXT_MASK_CACHED
+                m = 0u;
+                if (inside) m = a.masks[in.base + (uint32_t)(Y - in.r0) * in.pitch + (uint32_t)(X - in.c0)];
+#else
                 if constexpr (std::is_same_v<INST, TextInstAffine>) {
 #include "fr_text_affine_mask_kernel.inc"
                 } else {
 #include "fr_text_mask_kernel.inc"
                 }
+#endif
                 if (inside) {
                     const uint32_t k = (uint32_t)__builtin_popcount(m & ~taken);
                     if constexpr (SRGB) {
@@ -82,11 +88,16 @@
                 if (Y < in.y0 || Y >= in.y1) continue;                   // (wave-uniform)
                 const bool inside = X >= in.x0 && X < in.x1;
                 uint32_t m;
+#ifdef FR_TEXT_MASK_CACHED
+                m = 0u;
+                if (inside) m = a.masks[in.base + (uint32_t)(Y - in.r0) * in.pitch + (uint32_t)(X - in.c0)];
+#else
                 if constexpr (std::is_same_v<INST, TextInstAffine>) {
 #include "fr_text_affine_mask_kernel.inc"
                 } else {
 #include "fr_text_mask_kernel.inc"
                 }
+#endif
                 const uint32_t hit = inside ? m : 0u;
                 const uint32_t A = in.rgba >> 24, ia = 255u - A, hiA = in.rgba & 0xff000000u;
                 if constexpr (SRGB) {

@@ -1,5 +1,7 @@
 // fr_text_cover_kernel.inc — the rows of one tile as coverage / mask bytes: the body of text_kernel and text_place_kernel
 // (fr_text.hip) and of text_affine_kernel (fr_text_affine.hip).  Uses INST, N, FILL, PLACE, a.  Text, not a function: see the note on the instances in fr_text.hip.
+// With FR_TEXT_MASK_CACHED defined (fr_text_cached.hip only: a preprocessor switch, so that the other units see the text they had)
+// the instance's mask is loaded from its key's cell in a.masks instead of being evaluated.
     const TextTile tl = a.tiles[blockIdx.x];
     const TextRun rn = a.runs[tl.run];
     const int lane = (int)(threadIdx.x & 63u);
@@ -17,11 +19,16 @@
             if (Y < in.y0 || Y >= in.y1) continue;                       // (wave-uniform)
             const bool inside = X >= in.x0 && X < in.x1;
             uint32_t m;
+#ifdef FR_TEXT_MASK_CACHED
+            m = 0u;
+            if (inside) m = a.masks[in.base + (uint32_t)(Y - in.r0) * in.pitch + (uint32_t)(X - in.c0)];
+#else
             if constexpr (std::is_same_v<INST, TextInstAffine>) {
 #include "fr_text_affine_mask_kernel.inc"
             } else {
 #include "fr_text_mask_kernel.inc"
             }
+#endif
             if (inside) mask |= m;
         }
         if (X < (int)rn.w) {                                               // every pixel of the run: 0 where no instance reaches

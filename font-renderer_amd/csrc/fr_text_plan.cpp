@@ -4,12 +4,16 @@
 // four small pieces, overloaded on the form and written next to each other below: pen_of (how the fields are read),
 // resolve (the form's own checks, and what the build keeps of them: the affine inverse), cell_of (the cell in pixels about the pen) and
 // finish (the tail of the instance record).  The order of the checks fixes which error a caller sees: it is part of
-// the ABI's behaviour and host/text_plan_selftest.cpp pins it.
+// the ABI's behaviour and host/text_plan_selftest.cpp pins it.  A second builder, text_cache_tables at the end, adds the
+// tables of an FR_TEXT_CACHE plan from the same pieces (host/text_cache_selftest.cpp).
 #include "fr_text_plan.hpp"
 #include "fr_srgb.hpp"
 
 #include <algorithm>
+#include <array>
 #include <cmath>
+#include <cstring>
+#include <map>
 #include <type_traits>
 #include <utility>
 
@@ -256,5 +260,76 @@ int text_plan_tables(const TextPlanIn &in, const PLACE *places, TextPlanTables<P
 template int text_plan_tables(const TextPlanIn &, const fr_glyph_place *, TextPlanTables<fr_glyph_place> &);
 template int text_plan_tables(const TextPlanIn &, const fr_glyph_place_ex *, TextPlanTables<fr_glyph_place_ex> &);
 template int text_plan_tables(const TextPlanIn &, const fr_glyph_place_affine *, TextPlanTables<fr_glyph_place_affine> &);
+
+// ---- FR_TEXT_CACHE (fr_text_plan.hpp) ---------------------------------------------------------------------------------
+namespace {
+
+uint32_t bits_of(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
+
+// what the key holds besides the glyph and the pen fractions; the plain form is the _ex form at the run's scale, upright
+struct Shape { float scale, slant; };
+Shape shape_of(const fr_glyph_place &, float run_scale) { return Shape{run_scale, 0.0f}; }
+Shape shape_of(const fr_glyph_place_ex &p, float run_scale) { return Shape{scale_of(p, run_scale), p.slant}; }
+
+}  // namespace
+
+// Walks the runs and placements exactly as text_plan_tables does, so that its k-th surviving placement is t.insts[k].
+template <class PLACE>
+int text_cache_tables(const TextPlanIn &in, const PLACE *places, const TextPlanTables<PLACE> &t, TextCacheTables &out)
+{
+    using Key = std::array<uint32_t, 5>;                   // glyph, fx64, fy64, bits of the scale, bits of the slant
+    std::map<Key, uint32_t> cell_of_key;
+    out.insts.reserve(t.insts.size());
+    uint64_t elems = 0;
+    for (uint32_t r = 0; r < in.n_runs; ++r) {
+        const fr_text_run &rn = in.runs[r];
+        if (!rn.w || !rn.h) continue;
+        for (uint32_t k = rn.first; k < rn.first + rn.count; ++k) {
+            const Pen pen = pen_of(places[k]);
+            const uint32_t g = pen.glyph;
+            if (in.glyph_seg_start[g + 1] == in.glyph_seg_start[g]) continue;
+            const Cell c = cell_of(places[k], in.boxes + 4 * (size_t)g, rn.scale);
+            const int64_t ix = pen.x64 >> 6, iy = pen.y64 >> 6;
+            const uint32_t fx64 = (uint32_t)pen.x64 & 63u, fy64 = (uint32_t)pen.y64 & 63u;
+            const int64_t cw = c.mxx - c.mnx + 1 + (fx64 ? 1 : 0), ch = c.mxy - c.mny + 1 + (fy64 ? 1 : 0);
+            const int64_t c0 = ix + c.mnx, r0 = iy - c.mxy;
+            if (std::max<int64_t>(c0, 0) >= std::min<int64_t>(c0 + cw, rn.w) || std::max<int64_t>(r0, 0) >= std::min<int64_t>(r0 + ch, rn.h))
+                continue;                                                                  // clipped away
+            const size_t id = out.insts.size();
+            if (id >= t.insts.size()) return set_error(FR_E_INVALID, "text cache: the tables are not those of these placements");
+            const auto &ti = t.insts[id];
+            const Shape sh = shape_of(places[k], rn.scale);
+            const Key key{g, fx64, fy64, bits_of(sh.scale), bits_of(sh.slant)};
+            auto it = cell_of_key.find(key);
+            if (it == cell_of_key.end()) {
+                if (elems + (uint64_t)(cw * ch) > TEXT_CACHE_MAX_ELEMS)
+                    return set_error(FR_E_UNSUPPORTED, "FR_TEXT_CACHE: the mask cells hold more than 2^31 elements; split the plan or drop the flag");
+                TextMaskCell mc{};
+                mc.in = TextInstEx{(int32_t)-c.mnx, (int32_t)c.mxy, 0, (int32_t)cw, 0, (int32_t)ch, g, ti.rec, fx64, 0u, {0, 0}, fy64, sh.scale, sh.slant, 0u};
+                mc.base = (uint32_t)elems;
+                elems += (uint64_t)(cw * ch);
+                it = cell_of_key.emplace(key, (uint32_t)out.cells.size()).first;
+                out.cells.push_back(mc);
+            }
+            const TextMaskCell &mc = out.cells[it->second];
+            out.insts.push_back(TextCachedInst{ti.x0, ti.x1, ti.y0, ti.y1, ti.rgba, {ti.pad[0], ti.pad[1]}, mc.base, (uint32_t)cw, (int32_t)c0, (int32_t)r0, 0u});
+        }
+    }
+    if (out.insts.size() != t.insts.size()) return set_error(FR_E_INVALID, "text cache: the tables are not those of these placements");
+    out.elems = elems;
+    uint64_t n_tiles = 0;
+    for (const TextMaskCell &mc : out.cells)
+        n_tiles += (uint64_t)((mc.in.x1 + TEXT_TILE_W - 1) / TEXT_TILE_W) * (uint64_t)((mc.in.y1 + TEXT_TILE_H - 1) / TEXT_TILE_H);
+    if (n_tiles > 0x7fffffffull) return set_error(FR_E_UNSUPPORTED, "FR_TEXT_CACHE: the mask cells need more than 2^31 workgroups; split the plan");
+    out.tiles.reserve((size_t)n_tiles);
+    for (uint32_t ci = 0; ci < out.cells.size(); ++ci)
+        for (int32_t y = 0; y < out.cells[ci].in.y1; y += TEXT_TILE_H)
+            for (int32_t x = 0; x < out.cells[ci].in.x1; x += TEXT_TILE_W)
+                out.tiles.push_back(TextMaskTile{ci, (uint32_t)x, (uint32_t)y, 0u});
+    return FR_OK;
+}
+
+template int text_cache_tables(const TextPlanIn &, const fr_glyph_place *, const TextPlanTables<fr_glyph_place> &, TextCacheTables &);
+template int text_cache_tables(const TextPlanIn &, const fr_glyph_place_ex *, const TextPlanTables<fr_glyph_place_ex> &, TextCacheTables &);
 
 }  // namespace fr

@@ -43,4 +43,21 @@ struct TextPlanTables {
 template <class PLACE>
 int text_plan_tables(const TextPlanIn &in, const PLACE *places, TextPlanTables<PLACE> &out);
 
+// ---- FR_TEXT_CACHE: one mask cell per key, filled once per render and read by every instance of the key ----------------
+struct TextCacheTables {
+    std::vector<TextMaskCell> cells;   // one per distinct key among the surviving instances, in order of first use
+    std::vector<TextMaskTile> tiles;   // every 64 x 16 tile of every cell, cell by cell
+    std::vector<TextCachedInst> insts; // one per instance of TextPlanTables::insts, in its order (the tiles' lists name both alike)
+    uint64_t elems = 0;                // the mask store: the sum of cw * ch over the cells, uint16_t each
+};
+
+constexpr uint64_t TEXT_CACHE_MAX_ELEMS = (uint64_t)1 << 31;
+
+// PLACE: fr_glyph_place (key: glyph, pen_x64 mod 64, the bits of the run's scale) or fr_glyph_place_ex (key: glyph, pen_x64
+// mod 64, pen_y64 mod 64, the bits of the effective scale and of the slant).  `in`, `places` and `t` are what
+// text_plan_tables took and returned.  FR_OK, or FR_E_UNSUPPORTED (message through fr::set_error) when the cells hold
+// more than TEXT_CACHE_MAX_ELEMS elements: decided before any tile is listed, so the caller has nothing to allocate.
+template <class PLACE>
+int text_cache_tables(const TextPlanIn &in, const PLACE *places, const TextPlanTables<PLACE> &t, TextCacheTables &out);
+
 }  // namespace fr

@@ -56,6 +56,28 @@ struct TextTile {      // one 64 x 16 tile of a run and its instance list list[l
     uint32_t run, x0, y0, lbeg, lend;
     uint32_t pad[3];
 };
+// FR_TEXT_CACHE plans (fr_text_plan.cpp: text_cache_tables; the kernels of fr_text_cached.hip)
+struct TextMaskCell {  // one key's mask cell: cw x ch elements of uint16_t, row-major with pitch cw, at store[base]
+    TextInstEx in;     // the key's placement as an instance whose image is the whole cell: ix = -min_x, iy = max_y, x0 = y0 = 0,
+                       // x1 = cw, y1 = ch, so that the mask at (X, Y) = (cell column, cell row) is the placement's own
+    uint32_t base;     // first element in the store
+    uint32_t pad[3];
+};
+struct TextMaskTile {  // one 64 x 16 tile of a mask cell
+    uint32_t cell, x0, y0, pad;
+};
+struct TextCachedInst {  // what a composite kernel reads of an instance: the clipped cell, the colour, and where its masks are
+    int32_t x0, x1;    // as TextInst
+    int32_t y0, y1;
+    uint32_t rgba;     // as TextInst::rgba
+    uint32_t pad[2];   // as TextInst::pad
+    uint32_t base;     // TextMaskCell::base of its key's cell
+    uint32_t pitch;    // cw
+    int32_t c0, r0;    // the unclipped cell's origin in the run's image: the mask of pixel (X, Y) is
+                       // store[base + (Y - r0) * pitch + (X - c0)]
+    uint32_t pad2;
+};
+static_assert(sizeof(TextMaskCell) == 80 && sizeof(TextMaskTile) == 16 && sizeof(TextCachedInst) == 48, "text tables");
 static_assert(sizeof(TextInstEx) == 64, "text tables");
 static_assert(sizeof(TextInstAffine) == 80, "text tables");
 static_assert(sizeof(TextInst) == 48 && sizeof(TextRun) == 32 && sizeof(TextTile) == 32, "text tables");

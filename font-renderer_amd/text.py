@@ -110,16 +110,19 @@ def _line(font: Font, text, font_size: int, slant: float = 0.0):
 
 
 def render_text(font: Font, text, font_size: int, *, samples_per_axis: int = 4, mode: int = L.FR_COVERAGE_U8,
-                phase: int = L.FR_SAMPLE_CENTER, flags: int = 0, slant: float = 0.0, ctx: Optional[Context] = None) -> Gray:
+                phase: int = L.FR_SAMPLE_CENTER, flags: int = 0, slant: float = 0.0, cache: bool = False,
+                ctx: Optional[Context] = None) -> Gray:
     """One line of text as one image: every glyph at its sub-pixel pen, overlapping glyphs unioned per sample.
     The image is the union of the instance cells: the pen origin at its left edge (moved right by whole pixels if a cell
     reaches left of it) and the baseline at row ceil(max y_max * scale).  slant: a point (x, y) of every outline is drawn
-    at (x + slant * y, y) (0.2: an oblique of about 11 degrees); the advances do not change."""
+    at (x + slant * y, y) (0.2: an oblique of about 11 degrees); the advances do not change.  cache: FR_TEXT_CACHE, the
+    same bytes with each distinct (glyph, pen fraction) rasterised once; it pays when characters repeat at equal
+    fractions and costs the mask store otherwise."""
     line = _line(font, text, font_size, _slant(slant))
     if line is None:
         return Gray.init(0, 0)
     ctx = ctx or default_context()
-    return _render_gray(ctx, *line, mode, samples_per_axis, phase, flags)
+    return _render_gray(ctx, *line, mode, samples_per_axis, phase, flags | (L.FR_TEXT_CACHE if cache else 0))
 
 
 def _render_gray(ctx: Context, gs, places, runs, width: int, height: int, mode: int, samples_per_axis: int, phase: int,
@@ -154,15 +157,15 @@ def _rgba(c) -> tuple:
 
 def render_text_rgba(font: Font, text, font_size: int, color=(225, 105, 180, 255), background=(0, 0, 0, 0), colors=None,
                      *, samples_per_axis: int = 4, phase: int = L.FR_SAMPLE_CENTER, flags: int = 0, srgb: bool = False,
-                     bgra: bool = False, slant: float = 0.0, ctx: Optional[Context] = None) -> RGBA:
+                     bgra: bool = False, slant: float = 0.0, cache: bool = False, ctx: Optional[Context] = None) -> RGBA:
     """One line of text as one RGBA image (fr_text_plan_create_rgba): every glyph blended per sample in order over
     `background`, in `color` or, if `colors` is given, in colors[k] for character k (e.g. to highlight a word).  The
     defaults are the reference's frame: pink text (shader.slang) on a transparent clear colour.  Sized as render_text.
     srgb: blend and resolve in linear light, as the reference's sRGB swapchain does (FR_TEXT_SRGB); bgra: the pixels'
-    bytes are B G R A (FR_TEXT_BGRA; the colours stay R G B A); slant as render_text."""
+    bytes are B G R A (FR_TEXT_BGRA; the colours stay R G B A); slant and cache as render_text."""
     slant = _slant(slant)
     ctx = ctx or default_context()
-    flags |= (L.FR_TEXT_SRGB if srgb else 0) | (L.FR_TEXT_BGRA if bgra else 0)
+    flags |= (L.FR_TEXT_SRGB if srgb else 0) | (L.FR_TEXT_BGRA if bgra else 0) | (L.FR_TEXT_CACHE if cache else 0)
     n_chars = len(text)
     if colors is not None and len(colors) != n_chars:
         raise ValueError(f"colors: {len(colors)} colours for {n_chars} characters")
@@ -196,7 +199,7 @@ def _render_rgba(ctx: Context, gs, places, runs, width: int, height: int, per_ch
 
 def draw_text_rgba(image: RGBA, font: Font, text, font_size: int, x: float, y: float, color=(225, 105, 180, 255), colors=None,
                    *, samples_per_axis: int = 4, phase: int = L.FR_SAMPLE_CENTER, flags: int = 0, srgb: bool = False,
-                   bgra: bool = False, slant: float = 0.0, ctx: Optional[Context] = None) -> RGBA:
+                   bgra: bool = False, slant: float = 0.0, cache: bool = False, ctx: Optional[Context] = None) -> RGBA:
     """One line of text drawn in place into `image` (FR_TEXT_LOAD): every sample starts at the pixel already there, and
     the glyphs are blended over it per sample in order, in `color` or colors[k] for character k.  x: the pen origin's
     image x in pixels (fractional x is kept to 1/64 pixel: pen_x64 = floor(64 x + 1/2)); y: the baseline's image y, kept
@@ -204,7 +207,7 @@ def draw_text_rgba(image: RGBA, font: Font, text, font_size: int, x: float, y: f
     line is one run covering the whole image, so glyphs are clipped at its edges.  The whole image is copied to the
     device and back; on the device only the 64 x 16 tiles that some glyph cell meets are read (and, where needed,
     written), and every pixel no glyph sample reaches comes back with its bytes unchanged.  srgb / bgra as
-    render_text_rgba: the image's bytes are sRGB / B G R A.  image.data must be a (height * width, 4) uint8 array
+    render_text_rgba: the image's bytes are sRGB / B G R A; cache as render_text.  image.data must be a (height * width, 4) uint8 array
     (ValueError otherwise).  Returns `image`."""
     import torch
 
@@ -218,7 +221,7 @@ def draw_text_rgba(image: RGBA, font: Font, text, font_size: int, x: float, y: f
     if not math.isfinite(float(y)):
         raise ValueError(f"y {y!r}: expected a finite value")
     ctx = ctx or default_context()
-    flags |= L.FR_TEXT_LOAD | (L.FR_TEXT_SRGB if srgb else 0) | (L.FR_TEXT_BGRA if bgra else 0)
+    flags |= L.FR_TEXT_LOAD | (L.FR_TEXT_SRGB if srgb else 0) | (L.FR_TEXT_BGRA if bgra else 0) | (L.FR_TEXT_CACHE if cache else 0)
     n_chars = len(text)
     if colors is not None and len(colors) != n_chars:
         raise ValueError(f"colors: {len(colors)} colours for {n_chars} characters")

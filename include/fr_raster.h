@@ -357,6 +357,39 @@ int fr_text_plan_create_rgba_ex(fr_ctx *ctx, const fr_glyphset *gs, const fr_gly
                                 const uint8_t *run_clear_rgba, uint32_t n_runs, const fr_raster_params *params,
                                 uint32_t flags, fr_plan **out);
 
+/* FR_TEXT_CACHE  (fr_text_plan_create, fr_text_plan_create_rgba, fr_text_plan_create_ex, fr_text_plan_create_rgba_ex)
+ *       rasterise each distinct glyph image of the plan once per render and let every placement that shows it read it,
+ *       as a text stack's glyph cache does.  The plan renders, byte for byte, what the same plan without the flag renders:
+ *       every mode, n, phase, flag combination, clipping case, the LOAD tile rule and "every pixel of the run is written".
+ *       Only the work differs.
+ *   Key: the placements that survive clipping are grouped by (glyph, pen_x64 mod 64, bits of the run's scale) for
+ *       fr_glyph_place, and by (glyph, pen_x64 mod 64, pen_y64 mod 64, bits of the effective scale, bits of the slant)
+ *       for fr_glyph_place_ex; floats compare as bit patterns (0.0 and -0.0 are two keys).  By the sample definitions
+ *       above, two placements of one key have identical n^2-bit sample masks at equal offsets from (ix, iy).
+ *   Mask cell: each key owns the placement's whole, unclipped cell (cw x ch as defined above) as cw * ch elements of
+ *       uint16_t, row-major with pitch cw: element (c, r) is the non-zero mask (bit j*n + i: sample (i, j)) of the pixel
+ *       at cell column c, row r.  The cells live in one plan-owned store on the device.
+ *   Render: "every render starts from the glyph points" stays: the prepare kernel as before, then one launch that fills
+ *       every mask cell from the records, then one composite launch over the plan's tiles, in stream order on the
+ *       context's stream; the composite is the cover / colour computation of the plan without the flag, with an
+ *       instance's mask loaded from its key's cell at (X - c0, Y - r0), (c0, r0) = (ix + min_x, iy - max_y) the unclipped
+ *       cell's origin.  The "graph" option captures the three launches.
+ *   Cost: the flag buys nothing when no two placements share a key (every glyph image is then still made once, and
+ *       stored and loaded besides), and it always costs the mask store: 2 bytes per element of every cell, allocated at
+ *       plan creation.  It pays when many placements share few keys: running text on whole-pixel pens, or a fixed set of
+ *       sub-pixel positions.
+ *   Limits: the cells of one plan may hold at most 2^31 elements in all: FR_E_UNSUPPORTED beyond, decided on the host
+ *       before anything is allocated; a device allocation failure is FR_E_NOMEM.  A plan whose placements are all clipped
+ *       away has no cell and is the plan without the flag.
+ *   Combines with FR_FILL_CONSISTENT and, on the RGBA entry points, with FR_TEXT_SRGB, FR_TEXT_BGRA and FR_TEXT_LOAD.  The
+ *   two _affine entry points and every other entry point that takes flags return FR_E_INVALID for it.  Bits 2, 16, 64 and
+ *   1 << 31 stay unassigned.
+ *   fr_plan_describe lists the prepare kernel with the glyph count, glyph_mask_kernel<n, fill> with the cell count, and
+ *   the composite with the instance count: text_cached_kernel<n>, or text_cached_rgba_kernel / text_cached_srgb_kernel /
+ *   text_cached_rgba_load_kernel / text_cached_srgb_load_kernel<n, blend> (the fill rule acts only where masks are made, and
+ *   one composite serves both placement forms).  fr_plan_pixels and fr_plan_stats are unchanged.                        */
+#define FR_TEXT_CACHE 128u
+
 /* ---- text placements with a 2 x 2 matrix: rotated, mirrored and sheared text (BUILD-DEFINED) ----
  * fr_text_plan_create_ex / fr_text_plan_create_rgba_ex with a matrix per placement: vertical axis titles, text along a
  * direction, a rotated view, mirrored text.  Runs, modes, n in {1, 2, 4}, both phases, the flags (FR_FILL_CONSISTENT; for

@@ -1,0 +1,411 @@
+"""FR_TEXT_CACHE text plans on the GPU (include/fr_raster.h): a plan with the flag must render, byte for byte, what the same
+plan without it renders, in every family (coverage / mask, RGBA, sRGB, LOAD, BGRA; fr_glyph_place and fr_glyph_place_ex).
+The expected image is always the same plan without the flag; for at least one case per family it is also the CPU twin of
+the definition (tests/text_ref.py and its siblings), and the block-glyph cases (tests/text_block_cases.py) are compared to
+their own exact expectations, so nothing rests on GPU kernels alone.  Outputs are sentinel-filled (or noise under LOAD)
+and the whole array is compared."""
+import re
+from contextlib import closing
+
+import numpy as np
+import pytest
+
+import font_renderer_amd as fr
+import text_block_cases as B
+import text_load_ref as tl
+import text_place_ref as tp
+import text_ref
+import text_rgba_ref as tr
+import text_srgb_ref as ts
+from fixtures import load_font
+from font_renderer_amd import render_glyph as rg
+
+pytestmark = pytest.mark.gpu
+SENT = 0x5b
+FILL, SRGB, BGRA, LOAD, CACHE = fr.FR_FILL_CONSISTENT, fr.FR_TEXT_SRGB, fr.FR_TEXT_BGRA, fr.FR_TEXT_LOAD, fr.FR_TEXT_CACHE
+TEXT = "minimum illumination"
+
+
+def _phase(center):
+    return fr.FR_SAMPLE_CENTER if center else fr.FR_SAMPLE_CORNER
+
+
+def _count(describe, kernel):
+    m = re.search(re.escape(kernel) + r" x(\d+)", describe)
+    assert m, (kernel, describe)
+    return int(m.group(1))
+
+
+def _gray(ctx, dgs, places, runs, shape, n=4, center=True, flags=0, mode=fr.FR_COVERAGE_U8, times=1):
+    """a coverage / mask plan into a sentinel-filled buffer -> (bytes, describe)"""
+    import torch
+    with closing(fr.TextPlan(dgs, places, runs, mode, n, _phase(center), flags)) as plan:
+        buf = torch.full(shape, SENT, dtype=torch.uint8, device="cuda:0")
+        torch.cuda.synchronize()
+        for _ in range(times):
+            plan.render(buf.data_ptr(), shape[1], shape[0])
+        ctx.sync()
+        desc = plan.describe()
+    return buf.cpu().numpy(), desc
+
+
+def _rgba(ctx, dgs, places, cols, runs, clears, dst, n=4, center=True, flags=0):
+    """an RGBA plan over a fresh device copy of dst ((rows, cols, 4) u8: sentinel, or noise under LOAD) -> (bytes, describe)"""
+    import torch
+    with closing(fr.TextPlanRGBA(dgs, places, cols, runs, clears, n, _phase(center), flags)) as plan:
+        buf = torch.from_numpy(np.ascontiguousarray(dst)).to("cuda:0")
+        torch.cuda.synchronize()
+        plan.render(buf.data_ptr(), dst.shape[1], dst.shape[0])
+        ctx.sync()
+        desc = plan.describe()
+    return buf.cpu().numpy(), desc
+
+
+def _both_gray(ctx, dgs, places, runs, shape, n, center, flags, mode=fr.FR_COVERAGE_U8):
+    """cached and plain renders of one plan; asserts the cached one's launches -> (cached bytes, plain bytes, describe)"""
+    got, desc = _gray(ctx, dgs, places, runs, shape, n, center, flags | CACHE, mode)
+    want, plain = _gray(ctx, dgs, places, runs, shape, n, center, flags, mode)
+    fill = 1 if flags & FILL else 0
+    assert f"fr::glyph_mask_kernel<{n}, {fill}> x" in desc and f"fr::text_cached_kernel<{n}> x" in desc, desc
+    assert "cached" not in plain and "glyph_mask" not in plain, plain
+    return got, want, desc
+
+
+# ---- 1. coverage and mask: a real line with repeated glyphs, keys shared across runs, clipping at every edge -----------------
+def _line_case(font):
+    """three runs of TEXT: sizes 16 (clipped on all four sides), 16 again (whole; the same pen fractions, so the same
+    keys) and 40 (clipped on all four sides, cells across the tile borders at column 64 and row 16)"""
+    lay = {size: font.layout(TEXT, size) for size in (16, 40)}
+    distinct = sorted({int(g) for gi, _, _ in lay.values() for g in gi})
+    gs, kept = font.glyphset(distinct, skip_unsupported=False)
+    local = {g: k for k, g in enumerate(kept)}
+    seg = gs.segments_per_glyph()
+    upm = np.float32(font.information.units_per_em)
+    s16, s40 = np.float32(16) / upm, np.float32(40) / upm
+    rows, runs = [], []
+
+    def add(size, scale, shift_px, pen_y, w, h, out_x, out_y):
+        gi, pen, _ = lay[size]
+        runs.append((len(rows), len(gi), w, h, out_x, out_y, scale))
+        rows.extend((local[int(g)], int(p) + 64 * shift_px, pen_y) for g, p in zip(gi, pen))
+
+    width = {size: int(lay[size][2]) // 64 + 2 for size in lay}
+    add(16, s16, -3, 11, width[16] - 9, 10, 1, 1)
+    add(16, s16, 2, 15, width[16] + 6, 20, 3, 13)
+    add(40, s40, -5, 28, 150, 24, 1, 35)
+    places, runs = rg.make_places(rows), rg.make_runs(runs)
+    shape = (61, max(width[16] + 10, 152))
+    # what the run sizes were chosen for
+    edges, straddle = set(), False
+    for r in (0, 2):
+        run = runs[r]
+        for k in range(int(run["first"]), int(run["first"]) + int(run["count"])):
+            g = int(places[k]["glyph"])
+            if not seg[g]:
+                continue
+            c0, r0, cw, ch = text_ref.cell(gs.boxes[g], run["scale"], int(places[k]["pen_x64"]), int(places[k]["pen_y"]))
+            edges |= {e for e, cut in (("left", c0 < 0 < c0 + cw), ("right", c0 < run["w"] < c0 + cw), ("top", r0 < 0 < r0 + ch),
+                                       ("bottom", r0 < run["h"] < r0 + ch)) if cut}
+            straddle |= bool(r == 2 and c0 < 64 < c0 + cw and r0 < 16 < r0 + ch and c0 >= 0)
+    assert edges == {"left", "right", "top", "bottom"} and straddle, (edges, straddle)
+    assert any(seg[g] == 0 for g in places["glyph"]), "the space has no segments"
+    return gs, places, runs, shape
+
+
+@pytest.fixture(scope="module", params=["DejaVuSans.ttf", "DejaVuSerif-Italic.ttf"])
+def line_case(request):
+    gs, places, runs, shape = _line_case(load_font(request.param, allow_hinted=True))
+    twin = text_ref.render_runs(gs, places, runs, np.full(shape, SENT, np.uint8), 4, True, False)
+    return gs, places, runs, shape, twin
+
+
+def test_lines_equal_the_plain_plan_and_the_twin(ctx, line_case):
+    gs, places, runs, shape, twin = line_case
+    sets = [(fr.FR_COVERAGE_U8, n, center, flags) for n in (1, 2, 4) for center in (False, True) for flags in (0, FILL)]
+    sets += [(fr.FR_MASK_NONZERO, 1, center, flags) for center in (False, True) for flags in (0, FILL)]
+    with closing(fr.DeviceGlyphSet(ctx, gs)) as dgs:
+        for mode, n, center, flags in sets:
+            got, want, desc = _both_gray(ctx, dgs, places, runs, shape, n, center, flags, mode)
+            assert np.array_equal(got, want), (mode, n, center, flags, np.argwhere(got != want)[:8].tolist())
+            assert (want != SENT).any() and (want == 255).any()
+            insts, cells = _count(desc, f"fr::text_cached_kernel<{n}>"), _count(desc, "fr::glyph_mask_kernel<%d, %d>" % (n, 1 if flags else 0))
+            assert 0 < cells < insts, desc                             # the case exercises sharing
+            if (mode, n, center, flags) == (fr.FR_COVERAGE_U8, 4, True, 0):
+                assert np.array_equal(got, twin)
+
+
+# ---- 2. one large cell: several mask tiles per cell -----------------------------------------------------------------------------
+def test_one_large_cell(ctx):
+    font = load_font("DejaVuSans.ttf", allow_hinted=True)
+    gs, _ = font.glyphset([font.glyph_index(ord("m"))], skip_unsupported=False)
+    scale = np.float32(86) / np.float32(font.information.units_per_em)
+    c0, r0, cw, ch = text_ref.cell(gs.boxes[0], scale, 0, 0)
+    assert 64 < cw < 128 and 32 < ch <= 64, (cw, ch)                   # about 70 x 50: 2 x 4 mask tiles
+    base = -r0 + 2
+    places = rg.make_places([(0, 64 * 3, base), (0, 64 * 60, base + 7), (0, 64 * 8 + 37, base + 3), (0, 64 * 90 + 37, base + 11)])
+    runs = rg.make_runs([(0, 2, 140, ch + 12, 1, 1, scale), (2, 2, 171, ch + 9, 3, ch + 15, scale)])
+    shape = (2 * ch + 27, 176)
+    with closing(fr.DeviceGlyphSet(ctx, gs)) as dgs:
+        for n, center, flags in [(4, True, 0), (2, False, FILL), (1, True, 0)]:
+            got, want, desc = _both_gray(ctx, dgs, places, runs, shape, n, center, flags)
+            assert np.array_equal(got, want), (n, center, flags)
+            assert _count(desc, f"fr::text_cached_kernel<{n}>") == 4 and "glyph_mask_kernel<%d, %d> x2;" % (n, 1 if flags else 0) in desc, desc
+        got, _, _ = _both_gray(ctx, dgs, places, runs, shape, 4, True, 0)
+        assert np.array_equal(got, text_ref.render_runs(gs, places, runs, np.full(shape, SENT, np.uint8), 4, True, False))
+
+
+# ---- 3. the _ex form: every key field separates, equal keys share ------------------------------------------------------------------
+def test_ex_keys(ctx):
+    font = load_font("DejaVuSerif-Italic.ttf")
+    gs, _ = font.glyphset([font.glyph_index(ord("g"))], skip_unsupported=False)
+    s = np.float32(30) / np.float32(font.information.units_per_em)
+    x, y = 64 * 6 + 8, 64 * 30 + 8
+    rows = [(0, x, y, s, 0.25), (0, x + 64 * 25, y + 64 * 2, s, 0.25),                 # the same key twice
+            (0, x + 64 * 50, y + 9 - 8, s, 0.25),                                       # fy64
+            (0, x + 64 * 75, y, np.float32(s * np.float32(1.25)), 0.25),                # scale
+            (0, x + 64 * 100, y, s, -0.25),                                             # slant
+            (0, x + 64 * 125 + 1, y, s, 0.25)]                                          # fx64
+    places = rg.make_places_ex(rows)
+    runs = rg.make_runs([(0, len(rows), 160, 44, 1, 1, s)])
+    shape = (46, 162)
+    with closing(fr.DeviceGlyphSet(ctx, gs)) as dgs:
+        for n, center, flags in [(4, True, 0), (2, False, FILL), (1, False, 0)]:
+            got, want, desc = _both_gray(ctx, dgs, places, runs, shape, n, center, flags)
+            assert np.array_equal(got, want), (n, center, flags)
+            assert "glyph_mask_kernel<%d, %d> x5; fr::text_cached_kernel<%d> x6" % (n, 1 if flags else 0, n) in desc, desc
+        got, _, _ = _both_gray(ctx, dgs, places, runs, shape, 4, True, FILL)
+        assert np.array_equal(got, tp.render_runs(gs, places, runs, np.full(shape, SENT, np.uint8), 4, True, True))
+        # scale 0 is the run's scale: the same key as naming it
+        places0 = places.copy()
+        places0["scale"][1] = 0.0
+        got0, desc0 = _gray(ctx, dgs, places0, runs, shape, 4, True, FILL | CACHE)
+        assert np.array_equal(got0, got) and "glyph_mask_kernel<4, 1> x5;" in desc0, desc0
+
+
+# ---- 4. RGBA: opaque and translucent, UNORM and sRGB, clear colour and LOAD, BGRA, overlaps in both orders -------------------------
+@pytest.fixture(scope="module")
+def colour_case():
+    """two runs of one italic word whose glyphs are packed so close that their ink overlaps, the second run with the
+    placements in reverse order; the runs are 200 pixels wide, so the tile at columns 128 .. 191 meets no instance"""
+    font = load_font("DejaVuSerif-Italic.ttf")
+    gi, pen, _ = font.layout("fjfjWf", 21)
+    gs, kept = font.glyphset(sorted({int(g) for g in gi}), skip_unsupported=False)
+    local = {g: k for k, g in enumerate(kept)}
+    scale = np.float32(21) / np.float32(font.information.units_per_em)
+    xs = 64 * 4 + 16 + 192 * np.arange(6)                               # 3 pixels apart, every fraction 16/64: three keys
+    fwd = [(local[int(g)], int(x), 20) for g, x in zip(gi, xs)]
+    places = rg.make_places(fwd + fwd[::-1])
+    runs = rg.make_runs([(0, 6, 200, 27, 1, 1, scale), (6, 6, 200, 27, 1, 29, scale)])
+    shape = (57, 202)
+    right = max(c[0] + c[2] for c in (text_ref.cell(gs.boxes[p["glyph"]], scale, int(p["pen_x64"]), 20) for p in places))
+    assert right <= 128
+    rng = np.random.default_rng(5)
+    opaque = rng.integers(0, 256, (12, 4)).astype(np.uint8)
+    opaque[:, 3] = 255
+    translucent = rng.integers(0, 256, (12, 4)).astype(np.uint8)
+    translucent[0, 3], translucent[7, 3] = 255, 0
+    clears = np.array([(10, 60, 90, 128), (255, 255, 240, 255)], np.uint8)
+    noise = rng.integers(0, 256, shape + (4,)).astype(np.uint8)
+    return gs, places, runs, shape, opaque, translucent, clears, noise
+
+
+def _rgba_name(n, flags, blend):
+    return "fr::text_cached_%s%skernel<%d, %d> x12" % ("srgb_" if flags & SRGB else "rgba_", "load_" if flags & LOAD else "", n, blend)
+
+
+@pytest.mark.parametrize("load", [0, LOAD], ids=["clear", "load"])
+@pytest.mark.parametrize("space", [0, SRGB], ids=["unorm", "srgb"])
+def test_rgba_equals_the_plain_plan_and_the_twin(ctx, colour_case, space, load):
+    gs, places, runs, shape, opaque, translucent, clears, noise = colour_case
+    dst = noise if load else np.full(shape + (4,), SENT, np.uint8)
+    with closing(fr.DeviceGlyphSet(ctx, gs)) as dgs:
+        for cols, blend in ((opaque, 0), (translucent, 1)):
+            for n, center, fill in [(4, True, 0), (2, False, FILL), (1, True, 0)]:
+                flags = space | load | fill
+                got, desc = _rgba(ctx, dgs, places, cols, runs, None if load else clears, dst, n, center, flags | CACHE)
+                want, plain = _rgba(ctx, dgs, places, cols, runs, None if load else clears, dst, n, center, flags)
+                assert _rgba_name(n, flags, blend) in desc and f"fr::glyph_mask_kernel<{n}, {1 if fill else 0}> x" in desc, desc
+                assert "cached" not in plain
+                assert np.array_equal(got, want), (space, load, blend, n, center, fill, np.argwhere(got != want)[:8].tolist())
+                assert not np.array_equal(got, dst)
+                if load:                                               # the tile no instance meets: neither read nor written
+                    for r in runs:
+                        sl = np.s_[r["out_y"]:r["out_y"] + r["h"], r["out_x"] + 128:r["out_x"] + 192]
+                        assert np.array_equal(got[sl], noise[sl])
+                if n == 2:                                             # the CPU twin of the definition, once per family and blend
+                    twin = tp.rgba_render_runs(gs, rg.make_places_ex([(int(p["glyph"]), int(p["pen_x64"]), 64 * int(p["pen_y"]), 0.0, 0.0) for p in places]),
+                                               cols, runs, clears, dst.copy(), n, center, bool(fill), bool(space), False, bool(load))
+                    assert np.array_equal(got, twin), (space, load, blend)
+        if not load:                                                   # the two orders of the placements differ where their ink overlaps
+            same = opaque[[0, 1, 2, 3, 4, 5, 5, 4, 3, 2, 1, 0]]        # each glyph in its colour in both runs
+            got, _ = _rgba(ctx, dgs, places, same, runs, clears[[0, 0]], dst, 4, True, space | CACHE)
+            a, b = (got[r["out_y"]:r["out_y"] + r["h"], r["out_x"]:r["out_x"] + r["w"]] for r in runs)
+            assert (a != b).any() and (a == b).any()
+
+
+def test_bgra_and_the_old_twins(ctx, colour_case):
+    """FR_TEXT_BGRA once per colour space, and the twins of the upright form itself (text_rgba_ref / text_srgb_ref /
+    text_load_ref), which the placement twin above does not go through for its blending order alone"""
+    gs, places, runs, shape, opaque, translucent, clears, noise = colour_case
+    sent = np.full(shape + (4,), SENT, np.uint8)
+    with closing(fr.DeviceGlyphSet(ctx, gs)) as dgs:
+        for flags, dst in ((BGRA, sent), (BGRA | SRGB | LOAD, noise)):
+            got, _ = _rgba(ctx, dgs, places, translucent, runs, None if flags & LOAD else clears, dst, 4, True, flags | CACHE)
+            want, _ = _rgba(ctx, dgs, places, translucent, runs, None if flags & LOAD else clears, dst, 4, True, flags)
+            assert np.array_equal(got, want), flags
+            swapped, _ = _rgba(ctx, dgs, places, translucent, runs, None if flags & LOAD else clears, dst, 4, True, (flags & ~BGRA) | CACHE)
+            assert not np.array_equal(got, swapped)
+        got, _ = _rgba(ctx, dgs, places, translucent, runs, clears, sent, 2, True, CACHE)
+        assert np.array_equal(got, tr.render_runs(gs, places, translucent, runs, clears, sent.copy(), 2, True, False))
+        got, _ = _rgba(ctx, dgs, places, opaque, runs, clears, sent, 2, False, CACHE | SRGB | FILL)
+        assert np.array_equal(got, ts.render_runs(gs, places, opaque, runs, clears, sent.copy(), 2, False, True))
+        got, _ = _rgba(ctx, dgs, places, translucent, runs, None, noise, 2, True, CACHE | LOAD | SRGB | BGRA)
+        assert np.array_equal(got, tl.render_runs(gs, places, translucent, runs, noise.copy(), 2, True, False, True, True))
+
+
+def test_rgba_ex_form(ctx, colour_case):
+    """the RGBA entry point of the _ex form, slanted and on a fractional baseline, against its plain plan"""
+    gs, places, runs, shape, opaque, translucent, clears, noise = colour_case
+    ex = rg.make_places_ex([(int(p["glyph"]), int(p["pen_x64"]), 64 * int(p["pen_y"]) + 24, 0.0, 0.2) for p in places])
+    with closing(fr.DeviceGlyphSet(ctx, gs)) as dgs:
+        for flags, dst, cl in ((0, np.full(shape + (4,), SENT, np.uint8), clears), (LOAD | SRGB, noise, None)):
+            got, desc = _rgba(ctx, dgs, ex, translucent, runs, cl, dst, 4, True, flags | CACHE)
+            want, plain = _rgba(ctx, dgs, ex, translucent, runs, cl, dst, 4, True, flags)
+            assert _rgba_name(4, flags, 1) in desc and "text_place_" in plain, (desc, plain)
+            assert np.array_equal(got, want), flags
+
+
+# ---- 5. exact block cases: integer geometry, compared to their own expectations --------------------------------------------------
+@pytest.mark.parametrize("ex", [False, True], ids=["place", "place_ex"])
+def test_block_rows_on_vertices_and_pen_fractions(ctx, ex):
+    cases = [((float(s), n, center), B.edge_row_case(s, n, center, ex), n, center) for s, n, center in B.GRIDS[:6]]
+    cases += [(("pen", n, center), case, n, center) for (n, center), case in B.pen_fraction_cases(ex).items()]
+    for tag, (glyphs, places, runs, shape), n, center in cases:
+        with closing(fr.DeviceGlyphSet(ctx, B.glyph_set(glyphs))) as dgs:
+            got, desc = _gray(ctx, dgs, places, runs, shape, n, center, FILL | CACHE)
+            assert f"fr::glyph_mask_kernel<{n}, 1> x" in desc and f"fr::text_cached_kernel<{n}> x" in desc, desc
+            want = B.render_runs(glyphs, places, runs, np.full(shape, B.SENT, np.uint8), n, center)
+            assert np.array_equal(got, want), (tag, np.argwhere(got != want)[:8].tolist())
+            assert (want == 255).any()
+
+
+@pytest.mark.parametrize("srgb", [False, True], ids=["unorm", "srgb"])
+@pytest.mark.parametrize("ex", [False, True], ids=["place", "place_ex"])
+def test_block_colour_cases(ctx, ex, srgb):
+    import torch
+    space = SRGB if srgb else 0
+    cases = [(B.opaque_overlap_case(n, ex, srgb, load), n, space | (LOAD if load else 0), 0) for n in (1, 2, 4) for load in (False, True)]
+    cases.append((B.blend_clear_case(2, ex, srgb), 2, space | FILL, 1))
+    for case, n, flags, blend in cases:
+        with closing(fr.DeviceGlyphSet(ctx, B.glyph_set(case.glyphs))) as dgs:
+            with closing(fr.TextPlanRGBA(dgs, case.places, case.rgba, case.runs, case.clears, n, fr.FR_SAMPLE_CENTER, flags | CACHE)) as plan:
+                buf = torch.from_numpy(np.ascontiguousarray(case.start)).to("cuda:0")
+                torch.cuda.synchronize()
+                plan.render(buf.data_ptr(), case.start.shape[1], case.start.shape[0])
+                ctx.sync()
+                desc = plan.describe()
+        assert "fr::text_cached_%s%skernel<%d, %d> x" % ("srgb_" if srgb else "rgba_", "load_" if flags & LOAD else "", n, blend) in desc, desc
+        got = buf.cpu().numpy()
+        assert np.array_equal(got, case.want.astype(np.uint8)), (n, flags, np.argwhere(got != case.want)[:8].tolist())
+
+
+# ---- 6. behaviour -------------------------------------------------------------------------------------------------------------------
+def test_repeat_graph_and_describe(ctx, line_case, colour_case):
+    gs, places, runs, shape, _ = line_case
+    with closing(fr.DeviceGlyphSet(ctx, gs)) as dgs:
+        once, desc = _gray(ctx, dgs, places, runs, shape, 4, True, CACHE)
+        twice, _ = _gray(ctx, dgs, places, runs, shape, 4, True, CACHE, times=2)
+        assert np.array_equal(once, twice)
+        try:
+            ctx.set_option("graph", 1)
+            graphed, _ = _gray(ctx, dgs, places, runs, shape, 4, True, CACHE, times=2)
+        finally:
+            ctx.set_option("graph", 0)
+        assert np.array_equal(graphed, once)
+        # prepare with the glyph count, the mask kernel with the cell count, the composite with the instance count, in this order
+        assert re.fullmatch(r"fr::prepare_kernel x(\d+); fr::glyph_mask_kernel<4, 0> x(\d+); fr::text_cached_kernel<4> x(\d+)", desc), desc
+        _, desc = _gray(ctx, dgs, places, runs, shape, 1, False, CACHE | FILL, fr.FR_MASK_NONZERO)
+        assert re.fullmatch(r"fr::prepare_fill_kernel x\d+; fr::glyph_mask_kernel<1, 1> x\d+; fr::text_cached_kernel<1> x\d+", desc), desc
+        with closing(fr.TextPlan(dgs, places, runs, fr.FR_COVERAGE_U8, 4, fr.FR_SAMPLE_CENTER, CACHE)) as plan:
+            with closing(fr.TextPlan(dgs, places, runs)) as plain:
+                assert plan.pixels == plain.pixels and plan.stats() == plain.stats()
+    gs, places, runs, shape, opaque, translucent, clears, noise = colour_case
+    with closing(fr.DeviceGlyphSet(ctx, gs)) as dgs:
+        for flags, cols, name in [(0, opaque, "rgba_kernel<4, 0>"), (SRGB, translucent, "srgb_kernel<4, 1>"), (LOAD, translucent, "rgba_load_kernel<4, 1>"),
+                                  (LOAD | SRGB | BGRA, opaque, "srgb_load_kernel<4, 0>")]:
+            with closing(fr.TextPlanRGBA(dgs, places, cols, runs, clears, 4, fr.FR_SAMPLE_CENTER, flags | CACHE)) as plan:
+                assert re.fullmatch(r"fr::prepare_kernel x\d+; fr::glyph_mask_kernel<4, 0> x\d+; fr::text_cached_" + re.escape(name) + " x12",
+                                    plan.describe()), plan.describe()
+
+
+def test_every_placement_clipped_away(ctx, colour_case):
+    gs, places, runs, shape, opaque, _, clears, noise = colour_case
+    away = places.copy()
+    away["pen_x64"] += 64 * 5000
+    with closing(fr.DeviceGlyphSet(ctx, gs)) as dgs:
+        got, desc = _gray(ctx, dgs, away, runs, shape, 4, True, CACHE)
+        want, plain = _gray(ctx, dgs, away, runs, shape, 4, True, 0)
+        assert desc == plain and np.array_equal(got, want)             # no cell: the plan it is without the flag
+        for r in runs:
+            assert not got[r["out_y"]:r["out_y"] + r["h"], r["out_x"]:r["out_x"] + r["w"]].any()
+        assert (got == SENT).any()
+        got, _ = _rgba(ctx, dgs, away, opaque, runs, clears, np.full(shape + (4,), SENT, np.uint8), 4, True, CACHE)
+        for k, r in enumerate(runs):
+            assert (got[r["out_y"]:r["out_y"] + r["h"], r["out_x"]:r["out_x"] + r["w"]] == clears[k]).all()
+        got, _ = _rgba(ctx, dgs, away, opaque, runs, None, noise, 4, True, CACHE | LOAD)
+        assert np.array_equal(got, noise)
+
+
+def test_where_the_flag_is_not_taken(ctx, colour_case):
+    gs, places, runs, shape, opaque, _, clears, _ = colour_case
+    aff = rg.make_places_affine([(int(p["glyph"]), int(p["pen_x64"]), 64 * int(p["pen_y"]), 0.01, 0.0, 0.0, 0.01) for p in places])
+    with closing(fr.DeviceGlyphSet(ctx, gs)) as dgs:
+        with pytest.raises(fr.FrError) as e:
+            fr.TextPlan(dgs, aff, runs, fr.FR_COVERAGE_U8, 4, fr.FR_SAMPLE_CENTER, CACHE)
+        assert e.value.code == -1
+        with pytest.raises(fr.FrError) as e:
+            fr.TextPlanRGBA(dgs, aff, opaque, runs, clears, 4, fr.FR_SAMPLE_CENTER, CACHE)
+        assert e.value.code == -1
+        jobs = rg.make_jobs([(0, 0, 20, 20, 20, 0, 0, 0.01)])
+        with pytest.raises(fr.FrError) as e:
+            fr.Plan(dgs, jobs, fr.FR_COVERAGE_U8, 4, fr.FR_SAMPLE_CENTER, CACHE)
+        assert e.value.code == -1
+        for bits in (2, 16, 64, 1 << 31):                              # the unassigned bits stay unassigned beside the flag
+            with pytest.raises(fr.FrError) as e:
+                fr.TextPlan(dgs, places, runs, fr.FR_COVERAGE_U8, 4, fr.FR_SAMPLE_CENTER, CACHE | bits)
+            assert e.value.code == -1, bits
+
+
+def test_store_cap_answers_before_allocating(ctx):
+    """two keys whose cells hold 40 001 x 40 001 elements each: FR_E_UNSUPPORTED from the host, nothing allocated"""
+    import torch
+    glyphs = [B.BlockGlyph("huge", [B.rect(0, 0, 32000, 32000)])]
+    places = rg.make_places([(0, 0, 50), (0, 1, 50)])
+    runs = rg.make_runs([(0, 2, 100, 100, 0, 0, 1.25)])
+    with closing(fr.DeviceGlyphSet(ctx, B.glyph_set(glyphs))) as dgs:
+        fr.TextPlan(dgs, places, runs, fr.FR_COVERAGE_U8, 4, fr.FR_SAMPLE_CENTER, 0).close()      # fine without the flag
+        torch.cuda.synchronize()
+        free0, _ = torch.cuda.mem_get_info()
+        with pytest.raises(fr.FrError) as e:
+            fr.TextPlan(dgs, places, runs, fr.FR_COVERAGE_U8, 4, fr.FR_SAMPLE_CENTER, CACHE)
+        assert e.value.code == -4 and "2^31" in str(e.value), e.value
+        assert torch.cuda.mem_get_info()[0] == free0
+        # one of the two cells alone is within the limit (40 001^2 < 2^31), so the limit is the sum's
+        assert 40001 * 40001 < 2 ** 31 < 2 * 40001 * 40001
+
+
+def test_python_helpers_take_cache(ctx):
+    font = load_font("DejaVuSerif-Italic.ttf")
+    plain = fr.render_text(font, TEXT, 19, ctx=ctx)
+    cached = fr.render_text(font, TEXT, 19, cache=True, ctx=ctx)
+    assert (cached.width, cached.height) == (plain.width, plain.height) and np.array_equal(cached.data, plain.data) and plain.data.any()
+    a = fr.render_text_rgba(font, TEXT, 19, srgb=True, slant=0.2, ctx=ctx)
+    b = fr.render_text_rgba(font, TEXT, 19, srgb=True, slant=0.2, cache=True, ctx=ctx)
+    assert np.array_equal(a.data, b.data) and a.data.any()
+    noise = np.random.default_rng(1).integers(0, 256, (40 * 150, 4)).astype(np.uint8)
+    ims = []
+    for cache in (False, True):
+        im = fr.RGBA.init(150, 40)
+        im.data[:] = noise
+        ims.append(fr.draw_text_rgba(im, font, TEXT, 19, 3.25, 27.5, cache=cache, ctx=ctx).data.copy())
+    assert np.array_equal(ims[0], ims[1]) and not np.array_equal(ims[0], noise)

@@ -37,13 +37,24 @@ degrees the runs are squares around a diagonal line: "run_mpixel" is reported pe
 The five are timed alternately in the same process, --repeats times over; figures as for --place.  --affine-only
 leaves the other configurations out.
 
+--cache prices FR_TEXT_CACHE (one mask cell per distinct (glyph, pen fraction, scale), filled once per render and read by
+every instance of the key: csrc/fr_text_cached.hip), printed as its own JSON lines ("case": "cache"), one per font and
+size, coverage plans: (a) the plain plan, (b) the same plan with the flag, timed alternately in the same process,
+--repeats times over; figures as for --place, so "a_min_ms" .. "a_max_ms" is the plain plan's own run-to-run spread.  (b)
+must render (a)'s bytes (checked).  Beside the times: instances and cells (from fr_plan_describe), the mask store's
+bytes (recomputed here from the cells), and as the kernel split "cells_only_ms": a plain plan that holds every key's
+placement exactly once, each in a run of its cell's size — the prepare kernel and the direct sum over every distinct
+glyph image once, which is the work of the cached plan's first two launches; the composite is what remains of (b).
+--cache-only leaves the other configurations out.
+
 --samples {1,2,4} (default 4) and --fill (FR_FILL_CONSISTENT) go to every plan, so the kernel instances named below as
 <4, 0, ...> become <samples, fill, ...>.  The text kernels live in csrc/fr_text.hip, those of the matrix form in
 csrc/fr_text_affine.hip.
 
     python tools/bench_text.py [--lines 4096] [--chars 64] [--steps 20] [--warmup 3] [--samples 4] [--fill]
                                [--rgba] [--srgb] [--load]
-                               [--place [--repeats 5] [--place-only]] [--affine [--affine-only]]"""
+                               [--place [--repeats 5] [--place-only]] [--affine [--affine-only]]
+                               [--cache [--cache-only]]"""
 import argparse
 import json
 import os
@@ -135,8 +146,11 @@ def main():
     ap.add_argument("--affine", action="store_true", help="also price the matrix form (fr_glyph_place_affine) at 0, 5, 45 and 90 "
                     "degrees against the _ex plan, alternating in the same run (--repeats)")
     ap.add_argument("--affine-only", action="store_true", help="--affine without the other configurations")
+    ap.add_argument("--cache", action="store_true", help="also price FR_TEXT_CACHE against the plain plan, alternating in the "
+                    "same run (--repeats)")
+    ap.add_argument("--cache-only", action="store_true", help="--cache without the other configurations")
     args = ap.parse_args()
-    if (args.place or args.affine) and args.repeats < 5:
+    if (args.place or args.affine or args.cache) and args.repeats < 5:
         ap.error("--repeats: at least 5")
     import torch
     ns, fill = args.samples, fr.FR_FILL_CONSISTENT if args.fill else 0
@@ -145,7 +159,9 @@ def main():
         place(ctx, args)
     if args.affine:
         affine(ctx, args)
-    for fi, name in enumerate([] if (args.place and args.place_only) or (args.affine and args.affine_only) else ["DejaVuSans.ttf", "DejaVuSerif-Italic.ttf"]):
+    if args.cache:
+        cache(ctx, args)
+    for fi, name in enumerate([] if (args.place and args.place_only) or (args.affine and args.affine_only) or (args.cache and args.cache_only) else ["DejaVuSans.ttf", "DejaVuSerif-Italic.ttf"]):
         font = load_font(name, allow_hinted=True)        # (DejaVuSans carries hinting instructions)
         for size in (16, 32):
             gs, places, runs, shape, jobs, jshape, lines = workload(font, args.lines, args.chars, size, seed=100 * fi + size)
@@ -261,6 +277,64 @@ def place(ctx, args):
                 del bufs
             dgs.close()
             print(json.dumps(out), flush=True)
+
+
+def cache(ctx, args):
+    """--cache: (a) the plain coverage plan, (b) the same with FR_TEXT_CACHE; alternated, --repeats times; and the plain plan
+    of every key placed once"""
+    import re
+    import torch
+    ns, fill = args.samples, fr.FR_FILL_CONSISTENT if args.fill else 0
+    med = lambda v: sorted(v)[len(v) // 2]
+    for fi, name in enumerate(["DejaVuSans.ttf", "DejaVuSerif-Italic.ttf"]):
+        font = load_font(name, allow_hinted=True)
+        for size in (16, 32):
+            gs, places, runs, shape, _, _, _ = workload(font, args.lines, args.chars, size, seed=100 * fi + size)
+            scale = runs[0]["scale"]
+            seg = gs.segments_per_glyph()
+            # every key once, each in a run of its own as large as its cell, shelf-packed
+            keys = sorted({(int(p["glyph"]), int(p["pen_x64"]) & 63) for p in places if seg[int(p["glyph"])]})
+            kplaces, kruns, x, y, shelf, store = [], [], 0, 0, 0, 0
+            for g, f in keys:
+                c0, r0, cw, ch = fr.instance_cell(gs.boxes[g], scale, f, 0)
+                store += 2 * cw * ch
+                if x + cw > 16384:
+                    x, y, shelf = 0, y + shelf, 0
+                kruns.append((len(kplaces), 1, cw, ch, x, y, scale))
+                kplaces.append((g, f - 64 * c0, -r0))
+                x, shelf = x + cw, max(shelf, ch)
+            kshape = (y + shelf, 16384)
+            dgs = fr.DeviceGlyphSet(ctx, gs)
+            make = lambda flags: fr.TextPlan(dgs, places, runs, fr.FR_COVERAGE_U8, ns, fr.FR_SAMPLE_CENTER, fill | flags)
+            plans = {"a": make(0), "b": make(fr.FR_TEXT_CACHE)}
+            bufs = {k: torch.zeros(shape, dtype=torch.uint8, device="cuda:0") for k in plans}
+            torch.cuda.synchronize()
+            ms = {k: [] for k in plans}
+            for _ in range(args.repeats):
+                for k, plan in plans.items():
+                    ms[k].append(timed(plan, bufs[k], shape, args.steps, args.warmup))
+            if not torch.equal(bufs["a"], bufs["b"]):
+                raise SystemExit(f"--cache: {name} {size}: the cached plan differs from the plain plan")
+            desc = plans["b"].describe()
+            n_cells = int(re.search(r"glyph_mask_kernel<\d, \d> x(\d+)", desc).group(1))
+            if n_cells != len(keys):
+                raise SystemExit(f"--cache: {name} {size}: {n_cells} cells for {len(keys)} keys")
+            kplan = fr.TextPlan(dgs, rg.make_places(kplaces), rg.make_runs(kruns), fr.FR_COVERAGE_U8, ns, fr.FR_SAMPLE_CENTER, fill)
+            kbuf = torch.zeros(kshape, dtype=torch.uint8, device="cuda:0")
+            torch.cuda.synchronize()
+            kms = timed(kplan, kbuf, kshape, args.steps, args.warmup)
+            a, b = med(ms["a"]), med(ms["b"])
+            print(json.dumps({
+                "case": "cache", "font": name, "font_size": size, "lines": args.lines, "chars": args.chars, "samples": ns * ns,
+                "instances": int(re.search(r"text_cached_kernel<\d> x(\d+)", desc).group(1)), "cells": n_cells, "mask_store_bytes": store,
+                "steps": args.steps, "repeats": args.repeats, "a_ms": round(a, 4), "a_min_ms": round(min(ms["a"]), 4),
+                "a_max_ms": round(max(ms["a"]), 4), "b_ms": round(b, 4), "b_min_ms": round(min(ms["b"]), 4), "b_max_ms": round(max(ms["b"]), 4),
+                "a_over_b": round(a / b, 2), "cells_only_ms": round(kms, 4), "b_minus_cells_only_ms": round(b - kms, 4),
+                "a_plan": plans["a"].describe(), "b_plan": desc, "cells_only_plan": kplan.describe()}), flush=True)
+            for plan in list(plans.values()) + [kplan]:
+                plan.close()
+            del bufs, kbuf
+            dgs.close()
 
 
 def rotated_runs(gs, places, runs, scale, angle_deg, width=16384):
