@@ -36,6 +36,8 @@ pub const FR_TEXT_SRGB: u32 = 8;
 pub const FR_TEXT_LOAD: u32 = 32;
 /// flag of the four upright and _ex text plan entry points (fr_raster.h): rasterise each distinct glyph image once per render
 pub const FR_TEXT_CACHE: u32 = 128;
+/// flag of the RGBA text plan entry points (fr_raster.h): source-over alpha, a premultiplied output
+pub const FR_TEXT_OVER: u32 = 256;
 
 pub const RasterParams = extern struct {
     mode: i32,
@@ -163,6 +165,8 @@ pub extern "c" fn fr_qoi_encode_rgba(rgba: [*]const u8, width: u32, height: u32,
 /// the sRGB conversions of FR_TEXT_SRGB plans: 8-bit sRGB -> 16-bit linear light, and back (rounded in the encoded domain)
 pub extern "c" fn fr_srgb_decode(in: [*]const u8, n: usize, out: [*]u16) c_int;
 pub extern "c" fn fr_srgb_encode(in: [*]const u16, n: usize, out: [*]u8) c_int;
+/// premultiplied -> straight alpha in place (the output of FR_TEXT_OVER plans); srgb != 0: in linear light
+pub extern "c" fn fr_rgba_unpremultiply(rgba: [*]u8, n_pixels: usize, srgb: c_int) c_int;
 // ---- self-tests of the two arithmetic shortcuts (device-side, exhaustive)
 pub extern "c" fn fr_selftest_division(d_lo: u32, d_hi: u32, mismatches: *u64, bad_divisor: ?*u32, bad_x_bits: ?*u32) c_int;
 pub extern "c" fn fr_selftest_sqrt(mismatches: *u64, bad_x_bits: ?*u32) c_int;

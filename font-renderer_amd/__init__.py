@@ -10,7 +10,7 @@ from .glyph import Box, Contour, FontInformation, Glyph, GlyphSet  # noqa: F401
 from .image import RGB, RGBA, Gray, GlyphDebug, Winding  # noqa: F401
 from ._lib import (  # noqa: F401
     FR_COVERAGE_U8, FR_FILL_CONSISTENT, FR_SDF_U8, FR_GRAY_DEBUG, FR_MASK_NONZERO, FR_SAMPLE_CENTER, FR_SAMPLE_CORNER,
-    FR_TEXT_BGRA, FR_TEXT_CACHE, FR_TEXT_LOAD, FR_TEXT_SRGB, FR_WINDING_I16, FrError, GlyphPlace, GlyphPlaceAffine, GlyphPlaceEx,
+    FR_TEXT_BGRA, FR_TEXT_CACHE, FR_TEXT_LOAD, FR_TEXT_OVER, FR_TEXT_SRGB, FR_WINDING_I16, FrError, GlyphPlace, GlyphPlaceAffine, GlyphPlaceEx,
     Job, TextRun, lib_path, load_library,
 )
 from .render_glyph import (  # noqa: F401

@@ -12,6 +12,7 @@ FR_FILL_CONSISTENT = 1           # crossing-rule flag of the _ex entry points (i
 FR_TEXT_SRGB, FR_TEXT_BGRA = 8, 4  # flags of fr_text_plan_create_rgba only: linear-light blending, B G R A output
 FR_TEXT_LOAD = 32                  # fr_text_plan_create_rgba only: draw over the pixels already in the output
 FR_TEXT_CACHE = 128                # the upright and _ex text plans: each distinct glyph image made once per render, same bytes
+FR_TEXT_OVER = 256                 # the RGBA text plans: source-over alpha (a premultiplied output) instead of alpha replaced
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -124,6 +125,7 @@ SYMBOLS = [
     ("fr_qoi_encode_rgba", C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("fr_srgb_decode", C.c_int, [_P, C.c_size_t, _P]),
     ("fr_srgb_encode", C.c_int, [_P, C.c_size_t, _P]),
+    ("fr_rgba_unpremultiply", C.c_int, [_P, C.c_size_t, C.c_int]),
     ("fr_selftest_sqrt", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     ("fr_selftest_division", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
 ]

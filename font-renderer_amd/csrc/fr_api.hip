@@ -144,7 +144,7 @@ struct fr_plan {
     bool rgba = false;                 // fr_text_plan_create_rgba: RGBA pixels, text_rgba_kernel
     bool srgb = false;                 // (rgba) FR_TEXT_SRGB: text_srgb_kernel
     bool load = false;                 // (rgba) FR_TEXT_LOAD: text_rgba_load_kernel / text_srgb_load_kernel, occupied tiles only
-    int blend = 0;                     // (rgba) 1 unless every placement colour is opaque
+    int blend = 0;                     // (rgba) 0: every placement colour is opaque; else 1, or 2 under FR_TEXT_OVER
     fr::TextTile *d_tiles = nullptr;
     fr::TextRun *d_runs = nullptr;
     TextForm text_form = TEXT_PLAIN;   // the placement form: which record d_insts holds and which kernels read it
@@ -500,8 +500,8 @@ void fr_plan_destroy(fr_plan *plan)
     delete plan;
 }
 
-// also: the bits an entry point takes besides FR_FILL_CONSISTENT (fr_text_plan_create_rgba: FR_TEXT_SRGB, FR_TEXT_BGRA,
-// FR_TEXT_LOAD; the four upright and _ex text entry points: FR_TEXT_CACHE)
+// also: the bits an entry point takes besides FR_FILL_CONSISTENT (the RGBA text entry points: FR_TEXT_SRGB, FR_TEXT_BGRA,
+// FR_TEXT_LOAD, FR_TEXT_OVER; the four upright and _ex text entry points: FR_TEXT_CACHE)
 static int check_flags(uint32_t flags, uint32_t also = 0u)
 {
     const uint32_t known = (uint32_t)FR_FILL_CONSISTENT | also;
@@ -659,8 +659,9 @@ static int text_plan_upload(const char *fn, fr_plan *p, const fr::TextPlanTables
 // then text_plan_upload.  PLACE is the placement form: fr_glyph_place (TextInst, the text_* kernels of fr_text.hip),
 // fr_glyph_place_ex (own scale, slant and sub-pixel baseline: TextInstEx, text_place_*) or fr_glyph_place_affine (a 2 x 2
 // matrix: TextInstAffine, the text_affine_* kernels of fr_text_affine.hip).  rgba: place_rgba / run_clear_rgba are the
-// colours (4 bytes each), the mode must be FR_COVERAGE_U8, the flags may add FR_TEXT_SRGB, FR_TEXT_BGRA and
-// FR_TEXT_LOAD (which ignores run_clear_rgba and launches only the tiles some instance meets).
+// colours (4 bytes each), the mode must be FR_COVERAGE_U8, the flags may add FR_TEXT_SRGB, FR_TEXT_BGRA,
+// FR_TEXT_LOAD (which ignores run_clear_rgba and launches only the tiles some instance meets) and FR_TEXT_OVER (source-over
+// alpha: blend = 2 when some placement colour is translucent).
 // (The parameter checks are not check_params: that one answers FR_E_INVALID with other words for n != 1 outside
 // coverage, and looks at n before the phase.)
 template <class PLACE>
@@ -671,7 +672,7 @@ static int text_plan_create(const char *fn, fr_ctx *ctx, const fr_glyphset *gs, 
     if (!ctx || !gs || !out) return fail(FR_E_INVALID, "%s: NULL argument", fn);
     *out = nullptr;
     constexpr bool can_cache = !std::is_same<PLACE, fr_glyph_place_affine>::value;
-    if (const int frc = check_flags(flags, (rgba ? FR_TEXT_SRGB | FR_TEXT_BGRA | FR_TEXT_LOAD : 0u) | (can_cache ? FR_TEXT_CACHE : 0u))) return frc;
+    if (const int frc = check_flags(flags, (rgba ? FR_TEXT_SRGB | FR_TEXT_BGRA | FR_TEXT_LOAD | FR_TEXT_OVER : 0u) | (can_cache ? FR_TEXT_CACHE : 0u))) return frc;
     if (gs->ctx != ctx) return fail(FR_E_INVALID, "glyph set belongs to another context");
     if (!params) return fail(FR_E_INVALID, "params is NULL");
     if (params->mode < FR_WINDING_I16 || params->mode > FR_SDF_U8) return fail(FR_E_INVALID, "unknown mode %d", params->mode);
@@ -774,6 +775,26 @@ int fr_srgb_encode(const uint16_t *in, size_t n, uint8_t *out)
     for (size_t i = 0; i < n; ++i) {
         const uint32_t L = in[i], k = fr::SRGB_K[L >> 4];
         out[i] = (uint8_t)((k & 0xffu) + ((L & 15u) >= (k >> 8) ? 1u : 0u));
+    }
+    return FR_OK;
+}
+
+// premultiplied -> straight alpha, in place (the output of FR_TEXT_OVER plans; include/fr_raster.h)
+int fr_rgba_unpremultiply(uint8_t *rgba, size_t n_pixels, int srgb)
+{
+    if (n_pixels && !rgba) return fail(FR_E_INVALID, "fr_rgba_unpremultiply: NULL argument");
+    for (size_t i = 0; i < n_pixels; ++i) {
+        uint8_t *p = rgba + 4 * i;
+        const uint32_t a = p[3];
+        if (a == 0u) { p[0] = p[1] = p[2] = 0; continue; }
+        for (int c = 0; c < 3; ++c) {
+            if (srgb) {
+                const uint32_t L = std::min<uint32_t>(65535u, (255u * fr::SRGB_D[p[c]] + a / 2u) / a), k = fr::SRGB_K[L >> 4];
+                p[c] = (uint8_t)((k & 0xffu) + ((L & 15u) >= (k >> 8) ? 1u : 0u));
+            } else {
+                p[c] = (uint8_t)std::min<uint32_t>(255u, (255u * p[c] + a / 2u) / a);
+            }
+        }
     }
     return FR_OK;
 }

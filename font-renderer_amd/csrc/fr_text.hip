@@ -33,7 +33,11 @@ namespace fr {
 // BLEND = 0: every placement colour is opaque, so a sample takes the colour of the last instance that covers it: the
 // instances are walked backwards and each adds the samples it takes first; the samples none takes add the start value.
 // BLEND = 1: n^2 RGBA8 sample states per lane, blended forwards in placement order (src*A + dst*(255 - A) for R G B,
-// alpha replaced by A).  Either way the pixel is (sum over the samples + n^2/2) div n^2 per channel.
+// alpha replaced by A).  BLEND = 2 (FR_TEXT_OVER with a translucent colour): BLEND = 1 with the alpha updated as a colour
+// channel whose source is 255, a' = (255*A + a*(255 - A) + 127) div 255: UNORM carries it in the high half of the G
+// channel's blend2 call, sRGB adds one div255_24 (alpha stays linear).  An if constexpr in the per-sample loop, so the
+// instances of BLEND 0 and 1 compile from the text they had.  Either way the pixel is (sum over the samples + n^2/2) div
+// n^2 per channel.
 // SRGB (FR_TEXT_SRGB): the colour channels are blended and resolved in 16-bit linear light, c' = E((D[C] * A + D[c] *
 // (255 - A) + 127) div 255) and E((sum of D[c] + n^2/2) div n^2), through the tables of fr_srgb.hpp, copied into LDS once
 // per workgroup; the host put the linear values of the placement and clear colours in TextInst::pad / TextRun::pad.

@@ -3,7 +3,7 @@
 // colour arithmetic, LOAD, sRGB and the stores are the two row bodies of fr_text.hip, unchanged; only the evaluation of an
 // instance's mask differs (fr_text_affine_mask_kernel.inc): a sample row's ray height is no longer the same in all 64
 // lanes, so every lane solves every record at its own height, and a wave-uniform cull skips the records whose height
-// range the row's samples cannot reach.  A translation unit of its own: the 54 instances compile beside the 108 of
+// range the row's samples cannot reach.  A translation unit of its own: the 78 instances compile beside the 156 of
 // fr_text.hip, and nothing here can move a register of those.
 #include "fr_text.hpp"
 #include "fr_text_colour.hpp"

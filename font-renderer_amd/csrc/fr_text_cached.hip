@@ -12,7 +12,7 @@
 // text_cached_*_kernel: the two row bodies of fr_text.hip — tile walk, row loop, instance loops, colour arithmetic, LOAD,
 // sRGB, stores — compiled here with FR_TEXT_MASK_CACHED, which replaces the evaluation of an instance's mask by one 2-byte
 // load from its key's cell, issued by the lanes inside the clipped cell only.  A preprocessor switch and a translation
-// unit of its own: the 162 instances of fr_text.hip and fr_text_affine.hip compile from the text they had.  The fill
+// unit of its own: the instances of fr_text.hip and fr_text_affine.hip (162 when the cache went in) compile from the text they had.  The fill
 // rule acts only where masks are made, and one record (TextCachedInst) serves both placement forms, so these instances
 // carry neither FILL nor a form.
 #include "fr_text.hpp"
@@ -123,6 +123,7 @@ hipError_t cached_n(const TextCachedArgs &a, int n, const Launch &l)
 template <int FAM>
 hipError_t cached_family(const TextCachedArgs &a, int n, int blend, const Launch &l)
 {
+    if (blend == 2) return cached_n<FAM, 2>(a, n, l);
     return blend ? cached_n<FAM, 1>(a, n, l) : cached_n<FAM, 0>(a, n, l);
 }
 

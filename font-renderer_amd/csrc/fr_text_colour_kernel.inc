@@ -102,6 +102,7 @@
                 const uint32_t A = in.rgba >> 24, ia = 255u - A, hiA = in.rgba & 0xff000000u;
                 if constexpr (SRGB) {
                     const uint32_t rA = (in.pad[0] & 0xffffu) * A + 127u, gA = (in.pad[0] >> 16) * A + 127u, bA = in.pad[1] * A + 127u;
+                    [[maybe_unused]] const uint32_t aA = 255u * A + 127u;                  // (BLEND = 2) alpha: the colour formula with C = 255, linear
 #pragma unroll
                     for (uint32_t k = 0; k < NN; ++k) {
                         if (hit >> k & 1u) {
@@ -109,15 +110,22 @@
                             const uint32_t r = srgb_encode(K, div255_24(rA + (uint32_t)D[sm & 0xffu] * ia));
                             const uint32_t g = srgb_encode(K, div255_24(gA + (uint32_t)D[(sm >> 8) & 0xffu] * ia));
                             const uint32_t b = srgb_encode(K, div255_24(bA + (uint32_t)D[(sm >> 16) & 0xffu] * ia));
-                            smp[k] = r | g << 8 | b << 16 | hiA;
+                            if constexpr (BLEND == 2) smp[k] = r | g << 8 | b << 16 | div255_24(aA + (sm >> 24) * ia) << 24;
+                            else smp[k] = r | g << 8 | b << 16 | hiA;
                         }
                     }
                 } else {
                     const uint32_t rbA = (in.rgba & M2) * A + 0x00800080u, gA = ((in.rgba >> 8) & 0xffu) * A + 128u;
+                    // (BLEND = 2) the sample's alpha rides the high half of the G call, its source 255: G | a << 16
+                    [[maybe_unused]] const uint32_t gaA = (((in.rgba >> 8) & 0xffu) | 255u << 16) * A + 0x00800080u;
 #pragma unroll
                     for (uint32_t k = 0; k < NN; ++k) {
-                        if (hit >> k & 1u)
-                            smp[k] = blend2(smp[k] & M2, rbA, ia) | (blend2((smp[k] >> 8) & 0xffu, gA, ia) << 8) | hiA;
+                        if constexpr (BLEND == 2) {
+                            if (hit >> k & 1u) smp[k] = blend2(smp[k] & M2, rbA, ia) | (blend2((smp[k] >> 8) & M2, gaA, ia) << 8);
+                        } else {
+                            if (hit >> k & 1u)
+                                smp[k] = blend2(smp[k] & M2, rbA, ia) | (blend2((smp[k] >> 8) & 0xffu, gA, ia) << 8) | hiA;
+                        }
                     }
                 }
             }

@@ -35,6 +35,9 @@ hipError_t launch_n(const ARGS &a, int n, const Launch &l)
 template <class ARGS, int FAM>
 hipError_t launch_family(const ARGS &a, int n, int fill, int blend, const Launch &l)
 {
+    if constexpr (FAM != 0) {                                              // (the coverage kernels have no BLEND)
+        if (blend == 2) return fill ? launch_n<ARGS, FAM, 1, 2>(a, n, l) : launch_n<ARGS, FAM, 0, 2>(a, n, l);
+    }
     if (blend) return fill ? launch_n<ARGS, FAM, 1, 1>(a, n, l) : launch_n<ARGS, FAM, 0, 1>(a, n, l);
     return fill ? launch_n<ARGS, FAM, 1, 0>(a, n, l) : launch_n<ARGS, FAM, 0, 0>(a, n, l);
 }

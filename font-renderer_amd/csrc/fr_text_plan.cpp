@@ -253,7 +253,7 @@ int text_plan_tables(const TextPlanIn &in, const PLACE *places, TextPlanTables<P
         if (used[g]) out.glyphs.push_back(g);
     out.pixels = pixels; out.need_cols = need_cols; out.need_rows = need_rows;
     for (uint32_t k = 0; rgba && k < n_places; ++k)
-        if (in.place_rgba[4 * (size_t)k + 3] != 255) { out.blend = 1; break; }
+        if (in.place_rgba[4 * (size_t)k + 3] != 255) { out.blend = (in.flags & FR_TEXT_OVER) ? 2 : 1; break; }
     return FR_OK;
 }
 

@@ -15,7 +15,7 @@ struct TextPlanIn {                    // everything the tables depend on beside
     const uint8_t *place_rgba;         // rgba: 4 bytes per placement
     const uint8_t *run_clear_rgba;     // rgba without FR_TEXT_LOAD: 4 bytes per run
     bool rgba;                         // an RGBA plan (the colours above are read); else coverage / mask bytes
-    uint32_t flags;                    // FR_TEXT_SRGB, FR_TEXT_BGRA, FR_TEXT_LOAD (other bits are not looked at)
+    uint32_t flags;                    // FR_TEXT_SRGB, FR_TEXT_BGRA, FR_TEXT_LOAD, FR_TEXT_OVER (other bits are not looked at)
     const int16_t *boxes;              // the glyph set's Glyph.box per glyph (x_min, y_min, x_max, y_max); NULL: never set
     const uint32_t *glyph_seg_start;   // its n_glyphs + 1 segment offsets
     uint32_t n_glyphs;
@@ -35,7 +35,7 @@ struct TextPlanTables {
     std::vector<uint32_t> list;        // the tiles' instance lists (TextTile::lbeg, lend), each in placement order
     std::vector<uint32_t> glyphs;      // the distinct glyphs of insts, ascending
     uint64_t pixels = 0, need_cols = 0, need_rows = 0;
-    int blend = 0;                     // (rgba) 1 unless every placement colour is opaque
+    int blend = 0;                     // (rgba) 0: every placement colour is opaque; else 1, or 2 under FR_TEXT_OVER
 };
 
 // PLACE: fr_glyph_place, fr_glyph_place_ex or fr_glyph_place_affine.  FR_OK, or the code include/fr_raster.h names with

@@ -185,6 +185,10 @@ inline Image::Gray renderAtlas(Context &ctx, const std::vector<Glyph> &glyphs, F
 // or of fr_glyph_place_affine placements (a 2 x 2 matrix per placement: rotated, mirrored and sheared text; the struct is
 // the C header's: uint32_t glyph, int32_t pen_x64, pen_y64, float m[4] = xx, xy, yx, yy) over a set of glyphs: coverage bytes, or RGBA pixels when place_rgba is given.  The plan renders into DEVICE memory
 // (fr_plan_render), which the host that owns the HIP stream allocates; this mirror owns the glyph set and the plan.
+// flags: the header's, passed through; with place_rgba FR_TEXT_OVER (256) makes the pixels premultiplied R G B A with
+// source-over alpha, which unpremultiply() below turns into straight alpha once they are back on the host.
+inline void unpremultiply(std::vector<uint8_t> &rgba, bool srgb = false) { check(fr_rgba_unpremultiply(rgba.data(), rgba.size() / 4, srgb ? 1 : 0)); }
+
 class PlacedText {
 public:
     PlacedText(Context &ctx, const std::vector<Glyph> &glyphs, const std::vector<fr_glyph_place_ex> &places,

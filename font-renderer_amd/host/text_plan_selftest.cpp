@@ -5,12 +5,16 @@
 // no tolerance, what the kernels rely on: every cell inside its run, every tile's list exactly the instances that meet
 // it and in placement order, no empty tile under FR_TEXT_LOAD, the glyph list sorted and exact.  Exit status 1 if a
 // property fails.  The one message without a case is "too many tile / instance pairs" (more than 2^32 of them).
+// With the argument "over" it runs the FR_TEXT_OVER cases instead (tests/test_text_over_ref.py): each RGBA case with and
+// without the flag, one line each ending in "blend <0|1|2>", the hash taken over everything but the blend value, and
+// checks that the flag changes nothing but that value: 2 in place of 1, 0 where every colour is opaque.
 #include "../csrc/fr_text_plan.hpp"
 
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -144,8 +148,10 @@ void properties(const std::string &id, const Case &c, const fr::TextPlanTables<P
     check(used == t.glyphs, id, "glyph list not sorted and exact");
 }
 
+struct Outcome { bool ok; uint64_t hash; int blend; };   // (over) of one form of a case: the hash leaves the blend value out
+
 template <class PLACE>
-void run_form(const Case &c, const char *form)
+Outcome run_form(const Case &c, const char *form, bool over = false)
 {
     const std::string id = std::string(c.name) + "/" + form;
     std::vector<PLACE> places;
@@ -166,14 +172,36 @@ void run_form(const Case &c, const char *form)
     const int rc = fr::text_plan_tables(in, c.null_places ? nullptr : places.data(), t);
     if (rc != FR_OK) {
         printf("%s error %d: %s\n", id.c_str(), rc, g_err);
-        return;
+        return Outcome{false, 0, 0};
     }
     properties(id, c, t);
     Fnv f;
     f.vec(t.runs); f.vec(t.tiles); f.vec(t.insts); f.vec(t.list); f.vec(t.glyphs);
-    f.u64(t.pixels); f.u64(t.need_cols); f.u64(t.need_rows); f.u64((uint64_t)t.blend);
+    f.u64(t.pixels); f.u64(t.need_cols); f.u64(t.need_rows);
+    if (over) {
+        printf("%s %016llx insts %zu blend %d\n", id.c_str(), (unsigned long long)f.h, t.insts.size(), t.blend);
+        return Outcome{true, f.h, t.blend};
+    }
+    f.u64((uint64_t)t.blend);
     printf("%s %016llx runs %zu tiles %zu insts %zu pairs %zu glyphs %zu\n", id.c_str(), (unsigned long long)f.h, t.runs.size(), t.tiles.size(),
            t.insts.size(), t.list.size(), t.glyphs.size());
+    return Outcome{true, f.h, t.blend};
+}
+
+// (over) the case as given, then the same with FR_TEXT_OVER under the name <case>_over: equal tables, blend 1 -> 2, 0 -> 0
+template <class PLACE>
+void run_over_form(const Case &c, const char *form)
+{
+    const Outcome plain = run_form<PLACE>(c, form, true);
+    Case o = c;
+    const std::string name = std::string(c.name) + "_over";
+    o.name = name.c_str();
+    o.flags |= FR_TEXT_OVER;
+    const Outcome with = run_form<PLACE>(o, form, true);
+    const std::string id = name + "/" + form;
+    check(plain.ok && with.ok, id, "an FR_TEXT_OVER case failed to build");
+    check(plain.hash == with.hash, id, "FR_TEXT_OVER changed a table");
+    check(with.blend == (plain.blend ? 2 : 0), id, "blend is not 2 for translucent colours and 0 for opaque ones under FR_TEXT_OVER");
 }
 
 void run_case(const Case &c)
@@ -195,8 +223,9 @@ std::vector<uint8_t> colours(size_t n, uint8_t alpha_of_second)
 
 }  // namespace
 
-int main()
+int main(int argc, char **argv)
 {
+    const bool over = argc > 1 && !strcmp(argv[1], "over");
     const float S = 0.5f;
     const std::vector<Place> three = {at(0, 5 * 64, 20 * 64), at(1, 20 * 64, 25 * 64), at(2, 10 * 64, 22 * 64)};
     auto R = [&](uint32_t count) { return std::vector<fr_text_run>{run(0, count, 40, 30, 3, 5, S)}; };   // one run of `count` placements
@@ -212,6 +241,21 @@ int main()
         for (size_t r = 0; clears && r < c.runs.size(); ++r)
             for (int k = 0; k < 4; ++k) c.clears.push_back((uint8_t)(10 * (k + 1) + r));
     };
+    if (over) {
+        rgba(add("translucent", ALL, one, three), 0u, 128);
+        rgba(add("opaque", ALL, one, three), 0u, 255);
+        rgba(add("alpha_zero_srgb_bgra", ALL, one, three), FR_TEXT_SRGB | FR_TEXT_BGRA, 0);
+        rgba(add("load_srgb", ALL, {run(0, 3, 200, 40, 7, 9, S)}, three), FR_TEXT_LOAD | FR_TEXT_SRGB, 3, false);
+        rgba(add("load_opaque", ALL, {run(0, 3, 200, 40, 0, 0, S)}, three), FR_TEXT_LOAD, 255, false);
+        // the translucent colour belongs to a placement that is clipped away: blend looks at every placement, as without the flag
+        rgba(add("translucent_clipped_away", ALL, R(3), {at(0, 5 * 64, 20 * 64), at(1, 1000 * 64, 25 * 64), at(2, 10 * 64, 22 * 64)}), 0u, 200);
+        for (const Case &c : cases) {
+            if (c.forms & PLAIN) run_over_form<fr_glyph_place>(c, "plain");
+            if (c.forms & EX) run_over_form<fr_glyph_place_ex>(c, "ex");
+            if (c.forms & AFFINE) run_over_form<fr_glyph_place_affine>(c, "affine");
+        }
+        return g_failed;
+    }
     add("coverage", ALL, one, three);
     rgba(add("rgba_translucent", ALL, one, three), 0u, 128);
     rgba(add("rgba_srgb_bgra", ALL, one, three), FR_TEXT_SRGB | FR_TEXT_BGRA, 255);

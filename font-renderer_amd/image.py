@@ -85,11 +85,24 @@ class RGB:                      # Image.zig:132-170
 class RGBA:                     # an RGBA text plan's image (fr_text_plan_create_rgba): the framebuffer's bytes
     width: int
     height: int
-    data: np.ndarray            # (height*width, 4) u8, R G B A, not premultiplied
+    data: np.ndarray            # (height*width, 4) u8, R G B A, not premultiplied (premultiplied from an over=True render)
 
     @staticmethod
     def init(width: int, height: int) -> "RGBA":
         return RGBA(width, height, np.zeros((width * height, 4), np.uint8))
+
+    def unpremultiply(self, srgb: bool = False) -> "RGBA":
+        """fr_rgba_unpremultiply, in place: the premultiplied image of an over=True render (FR_TEXT_OVER) as straight
+        alpha, which the RGBA QOI writer and image files expect.  srgb: the image was rendered with srgb=True, so the
+        division is in linear light.  A pixel of alpha 0 becomes (0, 0, 0, 0); one of alpha 255 is unchanged.  Returns self."""
+        from . import _lib as L
+        if not isinstance(self.data, np.ndarray) or self.data.dtype != np.uint8 or self.data.ndim != 2 or self.data.shape[1] != 4:
+            raise ValueError("RGBA.unpremultiply: data must be an (n, 4) uint8 array")
+        buf = np.ascontiguousarray(self.data)
+        L.check(L.load_library().fr_rgba_unpremultiply(L.ptr(buf), buf.shape[0], 1 if srgb else 0))
+        if buf is not self.data:
+            self.data[:] = buf
+        return self
 
     def getWidth(self) -> int:
         return self.width

@@ -157,15 +157,20 @@ def _rgba(c) -> tuple:
 
 def render_text_rgba(font: Font, text, font_size: int, color=(225, 105, 180, 255), background=(0, 0, 0, 0), colors=None,
                      *, samples_per_axis: int = 4, phase: int = L.FR_SAMPLE_CENTER, flags: int = 0, srgb: bool = False,
-                     bgra: bool = False, slant: float = 0.0, cache: bool = False, ctx: Optional[Context] = None) -> RGBA:
+                     bgra: bool = False, slant: float = 0.0, cache: bool = False, over: bool = False,
+                     ctx: Optional[Context] = None) -> RGBA:
     """One line of text as one RGBA image (fr_text_plan_create_rgba): every glyph blended per sample in order over
     `background`, in `color` or, if `colors` is given, in colors[k] for character k (e.g. to highlight a word).  The
     defaults are the reference's frame: pink text (shader.slang) on a transparent clear colour.  Sized as render_text.
     srgb: blend and resolve in linear light, as the reference's sRGB swapchain does (FR_TEXT_SRGB); bgra: the pixels'
-    bytes are B G R A (FR_TEXT_BGRA; the colours stay R G B A); slant and cache as render_text."""
+    bytes are B G R A (FR_TEXT_BGRA; the colours stay R G B A); slant and cache as render_text.  over: source-over
+    alpha (FR_TEXT_OVER): a covered sample's alpha becomes A + a (1 - A) instead of A, so the image is then premultiplied
+    (in linear light with srgb) and, over a transparent background, a layer that composites correctly over anything;
+    RGBA.unpremultiply turns it into straight alpha.  R, G and B are those of over=False."""
     slant = _slant(slant)
     ctx = ctx or default_context()
-    flags |= (L.FR_TEXT_SRGB if srgb else 0) | (L.FR_TEXT_BGRA if bgra else 0) | (L.FR_TEXT_CACHE if cache else 0)
+    flags |= ((L.FR_TEXT_SRGB if srgb else 0) | (L.FR_TEXT_BGRA if bgra else 0) | (L.FR_TEXT_CACHE if cache else 0)
+              | (L.FR_TEXT_OVER if over else 0))
     n_chars = len(text)
     if colors is not None and len(colors) != n_chars:
         raise ValueError(f"colors: {len(colors)} colours for {n_chars} characters")
@@ -199,7 +204,8 @@ def _render_rgba(ctx: Context, gs, places, runs, width: int, height: int, per_ch
 
 def draw_text_rgba(image: RGBA, font: Font, text, font_size: int, x: float, y: float, color=(225, 105, 180, 255), colors=None,
                    *, samples_per_axis: int = 4, phase: int = L.FR_SAMPLE_CENTER, flags: int = 0, srgb: bool = False,
-                   bgra: bool = False, slant: float = 0.0, cache: bool = False, ctx: Optional[Context] = None) -> RGBA:
+                   bgra: bool = False, slant: float = 0.0, cache: bool = False, over: bool = False,
+                   ctx: Optional[Context] = None) -> RGBA:
     """One line of text drawn in place into `image` (FR_TEXT_LOAD): every sample starts at the pixel already there, and
     the glyphs are blended over it per sample in order, in `color` or colors[k] for character k.  x: the pen origin's
     image x in pixels (fractional x is kept to 1/64 pixel: pen_x64 = floor(64 x + 1/2)); y: the baseline's image y, kept
@@ -208,7 +214,9 @@ def draw_text_rgba(image: RGBA, font: Font, text, font_size: int, x: float, y: f
     device and back; on the device only the 64 x 16 tiles that some glyph cell meets are read (and, where needed,
     written), and every pixel no glyph sample reaches comes back with its bytes unchanged.  srgb / bgra as
     render_text_rgba: the image's bytes are sRGB / B G R A; cache as render_text.  image.data must be a (height * width, 4) uint8 array
-    (ValueError otherwise).  Returns `image`."""
+    (ValueError otherwise).  over: source-over alpha (FR_TEXT_OVER): the image is then read and written as premultiplied
+    R G B A, and translucent text leaves the alpha of an opaque picture at 255 (with over=False every covered sample's
+    alpha becomes the colour's A).  Returns `image`."""
     import torch
 
     w, h, data = image.width, image.height, image.data
@@ -221,7 +229,8 @@ def draw_text_rgba(image: RGBA, font: Font, text, font_size: int, x: float, y: f
     if not math.isfinite(float(y)):
         raise ValueError(f"y {y!r}: expected a finite value")
     ctx = ctx or default_context()
-    flags |= L.FR_TEXT_LOAD | (L.FR_TEXT_SRGB if srgb else 0) | (L.FR_TEXT_BGRA if bgra else 0) | (L.FR_TEXT_CACHE if cache else 0)
+    flags |= (L.FR_TEXT_LOAD | (L.FR_TEXT_SRGB if srgb else 0) | (L.FR_TEXT_BGRA if bgra else 0) | (L.FR_TEXT_CACHE if cache else 0)
+              | (L.FR_TEXT_OVER if over else 0))
     n_chars = len(text)
     if colors is not None and len(colors) != n_chars:
         raise ValueError(f"colors: {len(colors)} colours for {n_chars} characters")
@@ -311,10 +320,11 @@ def render_spans(font: Font, spans, *, samples_per_axis: int = 4, mode: int = L.
 
 
 def render_spans_rgba(font: Font, spans, background=(0, 0, 0, 0), *, samples_per_axis: int = 4, phase: int = L.FR_SAMPLE_CENTER,
-                      flags: int = 0, srgb: bool = False, bgra: bool = False, ctx: Optional[Context] = None) -> RGBA:
+                      flags: int = 0, srgb: bool = False, bgra: bool = False, over: bool = False,
+                      ctx: Optional[Context] = None) -> RGBA:
     """render_spans as one RGBA image: every span's glyphs in its colour, blended per sample in order over `background`
-    (srgb / bgra as render_text_rgba)."""
-    flags |= (L.FR_TEXT_SRGB if srgb else 0) | (L.FR_TEXT_BGRA if bgra else 0)
+    (srgb / bgra / over as render_text_rgba: with over the image is premultiplied)."""
+    flags |= (L.FR_TEXT_SRGB if srgb else 0) | (L.FR_TEXT_BGRA if bgra else 0) | (L.FR_TEXT_OVER if over else 0)
     clear = _rgba(background)
     line = span_line(font, spans)
     if line is None:
@@ -422,10 +432,11 @@ def render_text_rotated(font: Font, text, font_size: int, angle_deg: float, x: f
 def render_text_rgba_rotated(font: Font, text, font_size: int, angle_deg: float, x: float, y: float, width: int, height: int,
                              color=(225, 105, 180, 255), background=(0, 0, 0, 0), colors=None, *, zoom: float = 1.0,
                              slant: float = 0.0, samples_per_axis: int = 4, phase: int = L.FR_SAMPLE_CENTER,
-                             flags: int = L.FR_FILL_CONSISTENT, srgb: bool = False, bgra: bool = False,
+                             flags: int = L.FR_FILL_CONSISTENT, srgb: bool = False, bgra: bool = False, over: bool = False,
                              ctx: Optional[Context] = None) -> RGBA:
-    """render_text_rotated as one RGBA image: colours, background, srgb and bgra as render_text_rgba"""
-    flags |= (L.FR_TEXT_SRGB if srgb else 0) | (L.FR_TEXT_BGRA if bgra else 0)
+    """render_text_rotated as one RGBA image: colours, background, srgb, bgra and over as render_text_rgba (with over the
+    image is premultiplied)"""
+    flags |= (L.FR_TEXT_SRGB if srgb else 0) | (L.FR_TEXT_BGRA if bgra else 0) | (L.FR_TEXT_OVER if over else 0)
     n_chars = len(text)
     if colors is not None and len(colors) != n_chars:
         raise ValueError(f"colors: {len(colors)} colours for {n_chars} characters")

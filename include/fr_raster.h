@@ -249,6 +249,7 @@ int fr_text_plan_create(fr_ctx *ctx, const fr_glyphset *gs, const fr_glyph_place
  * the order of overlapping placements matters.
  * The output element is 4 bytes, R G B A in memory, NOT premultiplied: the framebuffer's bytes.  With a (0,0,0,0) clear
  * colour and opaque text, RGB comes out premultiplied by the coverage, as in the reference's transparent window.
+ * (FR_TEXT_OVER, below, updates alpha by source-over instead of replacing it: the element is then premultiplied.)
  * Without FR_TEXT_SRGB, blending is on the stored 8-bit values, as on a UNORM framebuffer.
  * params->mode must be FR_COVERAGE_U8 with n in {1, 2, 4}, either phase (another mode or n: FR_E_UNSUPPORTED; an unknown
  * mode value stays FR_E_INVALID, as for fr_text_plan_create); FR_FILL_CONSISTENT
@@ -381,7 +382,8 @@ int fr_text_plan_create_rgba_ex(fr_ctx *ctx, const fr_glyphset *gs, const fr_gly
  *   Limits: the cells of one plan may hold at most 2^31 elements in all: FR_E_UNSUPPORTED beyond, decided on the host
  *       before anything is allocated; a device allocation failure is FR_E_NOMEM.  A plan whose placements are all clipped
  *       away has no cell and is the plan without the flag.
- *   Combines with FR_FILL_CONSISTENT and, on the RGBA entry points, with FR_TEXT_SRGB, FR_TEXT_BGRA and FR_TEXT_LOAD.  The
+ *   Combines with FR_FILL_CONSISTENT and, on the RGBA entry points, with FR_TEXT_SRGB, FR_TEXT_BGRA, FR_TEXT_LOAD and
+ *   FR_TEXT_OVER.  The
  *   two _affine entry points and every other entry point that takes flags return FR_E_INVALID for it.  Bits 2, 16, 64 and
  *   1 << 31 stay unassigned.
  *   fr_plan_describe lists the prepare kernel with the glyph count, glyph_mask_kernel<n, fill> with the cell count, and
@@ -389,6 +391,32 @@ int fr_text_plan_create_rgba_ex(fr_ctx *ctx, const fr_glyphset *gs, const fr_gly
  *   text_cached_rgba_load_kernel / text_cached_srgb_load_kernel<n, blend> (the fill rule acts only where masks are made, and
  *   one composite serves both placement forms).  fr_plan_pixels and fr_plan_stats are unchanged.                        */
 #define FR_TEXT_CACHE 128u
+
+/* FR_TEXT_OVER  (the RGBA text entry points: fr_text_plan_create_rgba, _rgba_ex, _rgba_affine) source-over alpha:
+ *       the alpha half of Porter-Duff "over" on a premultiplied target, Vulkan's alpha factors ONE, ONE_MINUS_SRC_ALPHA
+ *       in place of the reference's ONE, ZERO.
+ *   Everything of an RGBA text plan is unchanged except the alpha a covered sample receives: the start value (Q_r, or the
+ *       stored pixel under FR_TEXT_LOAD), the per-instance non-zero test, the placement order, the update of R, G and B
+ *       (UNORM and FR_TEXT_SRGB forms), the resolve, the cells, the clipping and the LOAD tile rule.  An instance with
+ *       C_k = (R, G, B, A) whose winding at the sample is non-zero updates the sample's alpha by
+ *           a' = (255 * A + a * (255 - A) + 127) div 255
+ *       the colour formula with C = 255 and the same exact rounding; alpha is stored linearly with or without
+ *       FR_TEXT_SRGB.  C * A + c * (255 - A) is premultiplied source-over when the destination is premultiplied, so the
+ *       output is read and written as PREMULTIPLIED R G B A (under FR_TEXT_SRGB: premultiplied in linear light);
+ *       fr_rgba_unpremultiply turns a finished layer into straight alpha.
+ *   Consequences:
+ *     1. R, G and B of every pixel equal those of the same plan without the flag, byte for byte; only alpha can differ.
+ *     2. If every placement colour has A = 255 the plan is the plan without the flag, byte for byte, and launches the
+ *        same kernel instance (blend = 0).
+ *     3. An instance with A = 0 leaves a sample entirely unchanged (without the flag it sets alpha to 0).
+ *     4. Under FR_TEXT_LOAD over pixels whose alpha is 255, every alpha stays 255.
+ *     5. Over a (0,0,0,0) clear, one instance (R, G, B, A) that covers k of the n^2 samples of a pixel gives alpha
+ *        (k * A + n^2/2) div n^2.
+ *   Combines with FR_FILL_CONSISTENT, FR_TEXT_SRGB, FR_TEXT_BGRA, FR_TEXT_LOAD and, where that flag is accepted,
+ *   FR_TEXT_CACHE; every other entry point that takes flags returns FR_E_INVALID for it.  Bits 2, 16, 64 and 1 << 31 stay
+ *   unassigned.  fr_plan_describe names the plan's kernel with blend = 2 (..._kernel<n, fill, 2>, text_cached_..._kernel<n,
+ *   2>) when the flag is set and some placement colour has A != 255.                                                    */
+#define FR_TEXT_OVER 256u
 
 /* ---- text placements with a 2 x 2 matrix: rotated, mirrored and sheared text (BUILD-DEFINED) ----
  * fr_text_plan_create_ex / fr_text_plan_create_rgba_ex with a matrix per placement: vertical axis titles, text along a
@@ -585,6 +613,15 @@ int fr_qoi_encode_rgba(const uint8_t *rgba, uint32_t width, uint32_t height, siz
  * n > 0 is FR_E_INVALID.                                                                                               */
 int fr_srgb_decode(const uint8_t *in, size_t n, uint16_t *out);
 int fr_srgb_encode(const uint16_t *in, size_t n, uint8_t *out);
+
+/* ---- premultiplied -> straight alpha (host side), for the output of FR_TEXT_OVER plans ---------------------------------
+ * In place, n_pixels elements of 4 bytes with alpha last (R G B A or B G R A alike).  Per pixel with alpha a:
+ *     a = 0:                   (0, 0, 0, 0)
+ *     otherwise, srgb = 0:     c = min(255, (255 * c + a div 2) div a)                       for the three colour bytes
+ *     otherwise, srgb != 0:    c = E(min(65535, (255 * D[c] + a div 2) div a))               (D, E: FR_TEXT_SRGB above)
+ * A pixel with a = 255 is unchanged in both spaces (E(D[v]) = v).  This is what the RGBA QOI writer and other
+ * straight-alpha file formats expect.  NULL with n_pixels > 0 is FR_E_INVALID.                                          */
+int fr_rgba_unpremultiply(uint8_t *rgba, size_t n_pixels, int srgb);
 
 /* ---- self-test: exhaustive device-side check of an arithmetic shortcut ----------
  * The render kernel computes t = num / d (render_glyph.zig:51,60-61; d an integer, |d| <= 2^17)

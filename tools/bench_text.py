@@ -47,6 +47,12 @@ placement exactly once, each in a run of its cell's size — the prepare kernel 
 glyph image once, which is the work of the cached plan's first two launches; the composite is what remains of (b).
 --cache-only leaves the other configurations out.
 
+--over prices FR_TEXT_OVER (source-over alpha: the colour kernels' third blend value, csrc/fr_text_colour_kernel.inc),
+printed as its own JSON lines ("case": "over"), one per font and size: the --rgba translucent colouring as (a) the plan
+without the flag (blend = 1) and (b) the plan with it (blend = 2), UNORM and sRGB, timed alternately in the same process,
+--repeats times over; figures as for --place, so "a_min_ms" .. "a_max_ms" is the flag-less plan's own run-to-run spread.
+(b) must render (a)'s R, G and B (checked).  --over-only leaves the other configurations out.
+
 --samples {1,2,4} (default 4) and --fill (FR_FILL_CONSISTENT) go to every plan, so the kernel instances named below as
 <4, 0, ...> become <samples, fill, ...>.  The text kernels live in csrc/fr_text.hip, those of the matrix form in
 csrc/fr_text_affine.hip.
@@ -54,7 +60,7 @@ csrc/fr_text_affine.hip.
     python tools/bench_text.py [--lines 4096] [--chars 64] [--steps 20] [--warmup 3] [--samples 4] [--fill]
                                [--rgba] [--srgb] [--load]
                                [--place [--repeats 5] [--place-only]] [--affine [--affine-only]]
-                               [--cache [--cache-only]]"""
+                               [--cache [--cache-only]] [--over [--over-only]]"""
 import argparse
 import json
 import os
@@ -149,8 +155,11 @@ def main():
     ap.add_argument("--cache", action="store_true", help="also price FR_TEXT_CACHE against the plain plan, alternating in the "
                     "same run (--repeats)")
     ap.add_argument("--cache-only", action="store_true", help="--cache without the other configurations")
+    ap.add_argument("--over", action="store_true", help="also price FR_TEXT_OVER against the plan without it, UNORM and sRGB, "
+                    "alternating in the same run (--repeats)")
+    ap.add_argument("--over-only", action="store_true", help="--over without the other configurations")
     args = ap.parse_args()
-    if (args.place or args.affine or args.cache) and args.repeats < 5:
+    if (args.place or args.affine or args.cache or args.over) and args.repeats < 5:
         ap.error("--repeats: at least 5")
     import torch
     ns, fill = args.samples, fr.FR_FILL_CONSISTENT if args.fill else 0
@@ -161,7 +170,11 @@ def main():
         affine(ctx, args)
     if args.cache:
         cache(ctx, args)
-    for fi, name in enumerate([] if (args.place and args.place_only) or (args.affine and args.affine_only) or (args.cache and args.cache_only) else ["DejaVuSans.ttf", "DejaVuSerif-Italic.ttf"]):
+    if args.over:
+        over(ctx, args)
+    only = ((args.place and args.place_only) or (args.affine and args.affine_only) or (args.cache and args.cache_only)
+            or (args.over and args.over_only))
+    for fi, name in enumerate([] if only else ["DejaVuSans.ttf", "DejaVuSerif-Italic.ttf"]):
         font = load_font(name, allow_hinted=True)        # (DejaVuSans carries hinting instructions)
         for size in (16, 32):
             gs, places, runs, shape, jobs, jshape, lines = workload(font, args.lines, args.chars, size, seed=100 * fi + size)
@@ -335,6 +348,45 @@ def cache(ctx, args):
                 plan.close()
             del bufs, kbuf
             dgs.close()
+
+
+def over(ctx, args):
+    """--over: the --rgba translucent colouring as (a) the plan without FR_TEXT_OVER, (b) the plan with it; UNORM and sRGB;
+    alternated, --repeats times"""
+    import torch
+    ns, fill = args.samples, fr.FR_FILL_CONSISTENT if args.fill else 0
+    med = lambda v: sorted(v)[len(v) // 2]
+    for fi, name in enumerate(["DejaVuSans.ttf", "DejaVuSerif-Italic.ttf"]):
+        font = load_font(name, allow_hinted=True)
+        for size in (16, 32):
+            gs, places, runs, shape, _, _, lines = workload(font, args.lines, args.chars, size, seed=100 * fi + size)
+            words = [(225, 105, 180, 255), (40, 200, 90, 255)]
+            cols = np.array([words[s[:k].count(" ") % 2] for s in lines for k in range(len(s))], np.uint8)
+            cols[:int(runs[0]["count"]), 3] = 160
+            clears = np.zeros((len(runs), 4), np.uint8)
+            dgs = fr.DeviceGlyphSet(ctx, gs)
+            out = {"case": "over", "font": name, "font_size": size, "lines": args.lines, "chars": args.chars, "samples": ns * ns,
+                   "instances": int(len(places)), "steps": args.steps, "repeats": args.repeats}
+            for kind, space in (("rgba", 0), ("srgb", fr.FR_TEXT_SRGB)):
+                make = lambda flags: fr.TextPlanRGBA(dgs, places, cols, runs, clears, ns, fr.FR_SAMPLE_CENTER, space | fill | flags)
+                plans = {"a": make(0), "b": make(fr.FR_TEXT_OVER)}
+                bufs = {k: torch.zeros(shape + (4,), dtype=torch.uint8, device="cuda:0") for k in plans}
+                torch.cuda.synchronize()
+                ms = {k: [] for k in plans}
+                for _ in range(args.repeats):
+                    for k, plan in plans.items():
+                        ms[k].append(timed(plan, bufs[k], shape, args.steps, args.warmup))
+                if not torch.equal(bufs["a"][..., :3], bufs["b"][..., :3]):
+                    raise SystemExit(f"--over: {name} {size} {kind}: R G B differ from the plan without the flag")
+                a, b = med(ms["a"]), med(ms["b"])
+                out.update({f"{kind}_a_ms": round(a, 4), f"{kind}_a_min_ms": round(min(ms["a"]), 4), f"{kind}_a_max_ms": round(max(ms["a"]), 4),
+                            f"{kind}_b_ms": round(b, 4), f"{kind}_b_min_ms": round(min(ms["b"]), 4), f"{kind}_b_max_ms": round(max(ms["b"]), 4),
+                            f"{kind}_b_over_a": round(b / a, 3), f"{kind}_a_plan": plans["a"].describe(), f"{kind}_b_plan": plans["b"].describe()})
+                for plan in plans.values():
+                    plan.close()
+                del bufs
+            dgs.close()
+            print(json.dumps(out), flush=True)
 
 
 def rotated_runs(gs, places, runs, scale, angle_deg, width=16384):
