@@ -170,6 +170,7 @@ pub extern "c" fn fr_rgba_unpremultiply(rgba: [*]u8, n_pixels: usize, srgb: c_in
 // ---- self-tests of the two arithmetic shortcuts (device-side, exhaustive)
 pub extern "c" fn fr_selftest_division(d_lo: u32, d_hi: u32, mismatches: *u64, bad_divisor: ?*u32, bad_x_bits: ?*u32) c_int;
 pub extern "c" fn fr_selftest_sqrt(mismatches: *u64, bad_x_bits: ?*u32) c_int;
+pub extern "c" fn fr_selftest_row_cuts(gs: *fr_glyphset, jobs: [*]const Job, n_jobs: u32, samples_per_axis: c_int, phase: c_int, pairs: *u64, mismatches: *u64, first_bad: ?*[3]u32) c_int;
 
 pub const Error = error{ RasterFailed, OutOfMemory };
 

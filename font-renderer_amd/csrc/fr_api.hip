@@ -25,6 +25,9 @@ namespace fr {
 // fill = 1: the FR_FILL_CONSISTENT instances (fr_records.hpp)
 void launch_prepare(const int16_t *, const uint32_t *, const uint32_t *, const uint32_t *, uint32_t, Rec *,
                     uint32_t *, hipStream_t, int fill = 0);
+void launch_cuts(const int16_t *, uint32_t, float4 *, hipStream_t);
+void launch_selftest_row_cuts(const Job *, uint32_t, uint32_t, const uint32_t *, const int16_t *, const float4 *, int, int,
+                              unsigned long long *, hipStream_t);
 hipError_t launch_render(const RenderArgs &, const RasterLaunch &, hipStream_t);
 uint32_t render_wg_waves();
 hipError_t launch_cov4(const RenderArgs &, const RasterLaunch &, hipStream_t);
@@ -83,6 +86,7 @@ struct fr_ctx {
     uint32_t lds_pad = 0;        // experiment knob: extra dynamic LDS bytes per workgroup (occupancy studies)
     uint32_t min_wgs = 2048;     // split a cell's bands over workgroups below this many workgroups
     uint32_t cov4 = 1;           // jobs take the fast kernels (cov4_kernel / win1_kernel) where they fit (fast_class); 0: all general
+    uint32_t row_cuts = 1;       // the fast kernels' set-up reads a row's class off the glyph set's row cuts; 0: evaluates the reference's acceptance
     uint32_t zero_copy = 0;      // fr_render_glyph: render small glyphs from / into pinned host memory directly (measured: no faster than two small copies; off)
     uint32_t sdf_cull = 1;       // FR_SDF_U8: drop segments that cannot change a tile / a pixel (exact; 0 = look at all, for tests)
     uint32_t overlap = 1;        // a plan's smaller launches run beside its largest one on a second stream: 0 never, 1 plans of >= 32 Mpixel, 2 always
@@ -105,7 +109,9 @@ struct fr_glyphset {
     int16_t *d_pts = nullptr, *d_seg_pts = nullptr;
     uint32_t *d_seg_p0 = nullptr, *d_seg_prev = nullptr, *d_glyph_seg_start = nullptr, *d_rec_count = nullptr;
     fr::Rec *d_recs = nullptr;
-    std::vector<uint32_t> h_glyph_seg_start;    // host copy: plans attach each job's segment range to it
+    float4 *d_seg_cut = nullptr;                // row cuts, one float4 per segment (fr_records.hpp): 16 B per segment.  Null in
+                                                // the glyph set fr_render_glyph dresses its arena as
+    std::vector<uint32_t> h_glyph_seg_start;   // host copy: plans attach each job's segment range to it
     std::vector<uint32_t> h_root_bound;         // per glyph: candidate roots the vertex rule cannot discard (>= live records)
     std::vector<uint32_t> h_ray_bound;          // per glyph: estimated maximum of the crossings of one horizontal ray
     std::vector<int16_t> h_box;                 // fr_glyphset_set_boxes: Glyph.box per glyph (x_min, y_min, x_max, y_max); empty until set
@@ -178,6 +184,7 @@ static fr::RenderArgs render_args(const fr_plan *plan, void *out_dev, size_t out
     a.pts = plan->gs->d_pts;
     a.seg_p0 = plan->gs->d_seg_p0;
     a.seg_pts = plan->gs->d_seg_pts;
+    a.seg_cut = plan->ctx->row_cuts ? plan->gs->d_seg_cut : nullptr;
     // fused: the render kernel builds the records of every glyph of <= 128 segments (<= 256 candidate roots)
     // in LDS itself — decided per job inside the kernel; larger glyphs are staged from HBM
     a.fused = plan->ctx->fuse_prepare ? 1u : 0u;
@@ -341,6 +348,7 @@ int fr_ctx_set_option(fr_ctx *ctx, const char *key, int64_t value)
     if (!strcmp(key, "fuse_prepare")) { ctx->fuse_prepare = value ? 1u : 0u; return FR_OK; }
     if (!strcmp(key, "lds_pad")) { ctx->lds_pad = (uint32_t)value; return FR_OK; }
     if (!strcmp(key, "cov4")) { ctx->cov4 = value ? 1u : 0u; return FR_OK; }
+    if (!strcmp(key, "row_cuts")) { ctx->row_cuts = value ? 1u : 0u; return FR_OK; }
     if (!strcmp(key, "sdf_cull")) { ctx->sdf_cull = value ? 1u : 0u; return FR_OK; }
     if (!strcmp(key, "overlap")) {
         if (value < 0 || value > 2) return fail(FR_E_INVALID, "overlap must be 0 (never), 1 (plans of >= 32 Mpixel) or 2 (always)");
@@ -363,7 +371,7 @@ void fr_glyphset_destroy(fr_glyphset *gs)
     (void)hipSetDevice(gs->ctx->device);
     (void)hipStreamSynchronize(gs->ctx->stream);
     dfree(gs->d_pts); dfree(gs->d_seg_pts); dfree(gs->d_seg_p0); dfree(gs->d_seg_prev); dfree(gs->d_glyph_seg_start);
-    dfree(gs->d_rec_count); dfree(gs->d_recs);
+    dfree(gs->d_rec_count); dfree(gs->d_recs); dfree(gs->d_seg_cut);
     delete gs;
 }
 
@@ -430,6 +438,7 @@ int fr_glyphset_create(fr_ctx *ctx, const int16_t *points_xy, const uint32_t *co
     GS_TRY(hipMalloc(&gs->d_glyph_seg_start, ((size_t)n_glyphs + 1) * 4));
     GS_TRY(hipMalloc(&gs->d_rec_count, ((size_t)n_glyphs + 1) * 4));
     GS_TRY(hipMalloc(&gs->d_recs, 2 * nseg1 * sizeof(fr::Rec)));
+    GS_TRY(hipMalloc(&gs->d_seg_cut, nseg1 * sizeof(float4)));
     hipStream_t st = ctx->stream;
     if (np) GS_TRY(hipMemcpyAsync(gs->d_pts, points_xy, np * 2 * sizeof(int16_t), hipMemcpyHostToDevice, st));
     std::vector<int16_t> seg_pts((size_t)gs->n_seg * 6);
@@ -446,6 +455,8 @@ int fr_glyphset_create(fr_ctx *ctx, const int16_t *points_xy, const uint32_t *co
     GS_TRY(hipMemsetAsync(gs->d_rec_count, 0, ((size_t)n_glyphs + 1) * 4, st));
     fr::launch_prepare(gs->d_pts, gs->d_seg_p0, gs->d_glyph_seg_start, nullptr, n_glyphs, gs->d_recs,
                        gs->d_rec_count, st);
+    GS_TRY(hipGetLastError());
+    fr::launch_cuts(gs->d_seg_pts, gs->n_seg, gs->d_seg_cut, st);     // the row cuts: once, they hold for every cell and scale
     GS_TRY(hipGetLastError());
     GS_TRY(hipStreamSynchronize(st));   // host vectors above die with this frame
 #undef GS_TRY
@@ -465,6 +476,68 @@ int fr_glyphset_stats(const fr_glyphset *gs, uint64_t *n_segments, uint64_t *n_r
         uint64_t t = 0;
         for (uint32_t g = 0; g < gs->n_glyphs; ++g) t += cnt[g];
         *n_records = t;
+    }
+    return FR_OK;
+}
+
+// what a job must satisfy for the kernels' arithmetic to be the reference's (a plan's jobs, and the cells
+// fr_selftest_row_cuts walks)
+static int check_job(const fr_glyphset *gs, const fr_job &jb, uint32_t j)
+{
+    if (jb.glyph >= gs->n_glyphs) return fail(FR_E_INVALID, "job %u: glyph %u of %u", j, jb.glyph, gs->n_glyphs);
+    if (!(jb.scale > 0.0f) || !std::isfinite(jb.scale)) return fail(FR_E_INVALID, "job %u: scale must be finite and > 0", j);
+    // keeps every ray height, quotient and FMA residual of div_by_int inside the normal range
+    // (the reference's own scale = u16 / u16 lies in [2^-16, 2^16])
+    if (jb.scale < 9.5367431640625e-07f || jb.scale > 1048576.0f)
+        return fail(FR_E_UNSUPPORTED, "job %u: scale outside [2^-20, 2^20]", j);
+    if (jb.w > 65535u || jb.h > 65535u) return fail(FR_E_UNSUPPORTED, "job %u: cell larger than 65535", j);
+    // sample coordinates must be exactly representable in binary32
+    if (jb.min_x < -(1 << 22) || (int64_t)jb.min_x + jb.w > (1 << 22) || jb.max_y > (1 << 22) ||
+        (int64_t)jb.max_y - jb.h < -(1 << 22))
+        return fail(FR_E_UNSUPPORTED, "job %u: pixel coordinates beyond +-2^22", j);
+    return FR_OK;
+}
+
+int fr_selftest_row_cuts(fr_glyphset *gs, const fr_job *jobs, uint32_t n_jobs, int samples_per_axis, int phase,
+                         uint64_t *pairs, uint64_t *mismatches, uint32_t *first_bad)
+{
+    if (!gs || !pairs || !mismatches) return fail(FR_E_INVALID, "fr_selftest_row_cuts: NULL argument");
+    if (n_jobs && !jobs) return fail(FR_E_INVALID, "jobs is NULL");
+    const int n = samples_per_axis;
+    if (n != 1 && n != 2 && n != 4) return fail(FR_E_UNSUPPORTED, "samples_per_axis %d not in {1,2,4}", n);
+    if (phase != FR_SAMPLE_CORNER && phase != FR_SAMPLE_CENTER) return fail(FR_E_INVALID, "unknown sample_phase %d", phase);
+    if (!gs->d_seg_cut) return fail(FR_E_INVALID, "fr_selftest_row_cuts: the glyph set has no row cuts");
+    uint32_t max_rows = 0;
+    for (uint32_t j = 0; j < n_jobs; ++j) {
+        if (const int jrc = check_job(gs, jobs[j], j)) return jrc;
+        max_rows = std::max(max_rows, jobs[j].h * (uint32_t)n);
+    }
+    *pairs = 0; *mismatches = 0;
+    if (first_bad) first_bad[0] = first_bad[1] = first_bad[2] = 0u;
+    if (n_jobs == 0 || max_rows == 0) return FR_OK;
+    HIP_TRY(hipSetDevice(gs->ctx->device));
+    hipStream_t st = gs->ctx->stream;
+    fr::Job *d_jobs = nullptr;
+    unsigned long long *d_res = nullptr;
+    unsigned long long res[3] = {0ull, 0ull, ~0ull};
+    hipError_t e = hipMalloc(&d_jobs, (size_t)n_jobs * sizeof(fr::Job));
+    if (e == hipSuccess) e = hipMalloc(&d_res, sizeof res);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_jobs, jobs, (size_t)n_jobs * sizeof(fr::Job), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_res, res, sizeof res, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        fr::launch_selftest_row_cuts(d_jobs, n_jobs, max_rows, gs->d_glyph_seg_start, gs->d_seg_pts, gs->d_seg_cut, n,
+                                     phase == FR_SAMPLE_CENTER ? 1 : 0, d_res, st);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(res, d_res, sizeof res, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    else (void)hipStreamSynchronize(st);                  // (the copies above read `jobs` and `res`)
+    dfree(d_jobs); dfree(d_res);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? FR_E_NOMEM : FR_E_HIP, "fr_selftest_row_cuts: %s", hipGetErrorString(e));
+    *pairs = res[0];
+    *mismatches = res[1];
+    if (first_bad && res[1]) {
+        first_bad[0] = (uint32_t)(res[2] >> 40); first_bad[1] = (uint32_t)((res[2] >> 20) & 0xfffffu); first_bad[2] = (uint32_t)(res[2] & 0xfffffu);
     }
     return FR_OK;
 }
@@ -560,18 +633,7 @@ int fr_plan_create_ex(fr_ctx *ctx, const fr_glyphset *gs, const fr_job *jobs, ui
     if (rc) return rc;
     if (n_jobs && !jobs) return fail(FR_E_INVALID, "jobs is NULL");
     for (uint32_t j = 0; j < n_jobs; ++j) {
-        const fr_job &jb = jobs[j];
-        if (jb.glyph >= gs->n_glyphs) return fail(FR_E_INVALID, "job %u: glyph %u of %u", j, jb.glyph, gs->n_glyphs);
-        if (!(jb.scale > 0.0f) || !std::isfinite(jb.scale)) return fail(FR_E_INVALID, "job %u: scale must be finite and > 0", j);
-        // keeps every ray height, quotient and FMA residual of div_by_int inside the normal range
-        // (the reference's own scale = u16 / u16 lies in [2^-16, 2^16])
-        if (jb.scale < 9.5367431640625e-07f || jb.scale > 1048576.0f)
-            return fail(FR_E_UNSUPPORTED, "job %u: scale outside [2^-20, 2^20]", j);
-        if (jb.w > 65535u || jb.h > 65535u) return fail(FR_E_UNSUPPORTED, "job %u: cell larger than 65535", j);
-        // sample coordinates must be exactly representable in binary32
-        if (jb.min_x < -(1 << 22) || (int64_t)jb.min_x + jb.w > (1 << 22) || jb.max_y > (1 << 22) ||
-            (int64_t)jb.max_y - jb.h < -(1 << 22))
-            return fail(FR_E_UNSUPPORTED, "job %u: pixel coordinates beyond +-2^22", j);
+        if (const int jrc = check_job(gs, jobs[j], j)) return jrc;
     }
     fr_plan *p = new (std::nothrow) fr_plan;
     if (!p) return fail(FR_E_NOMEM, "fr_plan_create: host allocation");

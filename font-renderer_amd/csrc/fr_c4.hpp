@@ -119,13 +119,24 @@ __device__ __forceinline__ void c4_fill_cx(float *s_cxp, uint32_t tid, int32_t m
     }
 }
 
+// the row cut (fr_records.hpp) of candidate c = 2 segment + root of the glyph whose first segment is seg0: one 8-byte
+// load beside the candidate's control points, not after them
+__device__ __forceinline__ Cut c4_load_cut(const RenderArgs &A, uint32_t seg0, uint32_t c)
+{
+    const float2 q = reinterpret_cast<const float2 *>(A.seg_cut)[2u * (size_t)seg0 + c];
+    Cut k;
+    k.lo = q.x; k.hi = q.y;
+    return k;
+}
+
 // Set-up for glyphs of <= 32 segments (<= 64 candidate roots: one per lane of ONE wave — ASCII-like glyphs), four
 // waves.  Settling a candidate's row range costs four evaluations of the reference's acceptance at the rows around
 // the two guessed ends; with the plain set-up wave 0 would do all of it while waves 1 - 3 (and the SIMDs they sit
 // on) wait.  Here every wave prepares the same 64 candidates and looks at ONE of the four rows (wave 0: ra - 1,
 // 1: ra, 2: re - 1, 3: re); wave 0 takes the guess when the four classes confirm it — exactly the condition under
 // which record_settle's walks would not move — and walks as before otherwise.  Same records, same order.
-template <uint32_t RCAP, int N, uint32_t NCOL, int FILL>
+// CUT = 1 (every set-up below): the class of a row is read off the candidate's row cut (A.seg_cut is not null, FILL = 0)
+template <uint32_t RCAP, int N, uint32_t NCOL, int FILL, int CUT>
 __device__ __forceinline__ uint32_t c4_setup_small(const RenderArgs &A, const Job &job, uint32_t seg0, uint32_t nseg, uint32_t x0s,
                                                    int phase, float *s_cxp, Rec40 *s_rec, uint32_t *s_wcnt, uint32_t *s_tmp, const float *cyt = nullptr)
 {
@@ -140,11 +151,15 @@ __device__ __forceinline__ uint32_t c4_setup_small(const RenderArgs &A, const Jo
     Piece pc;
     g.empty = true; g.ra = 1u; g.re = 0u;
     uint32_t cls = 3u;                                  // 3: no such row / not asked — the condition it stands for holds
+    Cut k;
+    k.lo = k.hi = 0.0f;
     if (have) {
-        record_prep<FILL>(A.seg_pts + 6u * (size_t)(seg0 + (lane >> 1)), lane & 1u, geo, r, g, &pc);
+        bool drop = false;
+        if constexpr (CUT != 0) { k = c4_load_cut(A, seg0, lane); drop = cut_misses(k, row_span(geo)); }
+        record_prep<FILL>(A.seg_pts + 6u * (size_t)(seg0 + (lane >> 1)), lane & 1u, geo, r, g, &pc, drop);
         if (!g.empty) {
             const uint32_t row = (wave == 0u) ? g.ra - 1u : (wave == 1u) ? g.ra : (wave == 2u) ? g.re - 1u : g.re;   // (ra - 1 wraps past the cell at ra = 0)
-            if (row < Hs && (wave != 2u || g.re > g.ra)) cls = (uint32_t)row_class<FILL>(r, pc, geo.cy(row));
+            if (row < Hs && (wave != 2u || g.re > g.ra)) cls = (uint32_t)row_class<FILL, CUT>(r, pc, geo.cy(row), &k);
         }
     }
     s_tmp[tid] = cls;
@@ -165,7 +180,7 @@ __device__ __forceinline__ uint32_t c4_setup_small(const RenderArgs &A, const Jo
                 // record_settle would leave (ra, re) alone iff: the row above ra is rejected from above (class 2), ra is
                 // not (class <= 1), re >= ra, the row before re is accepted (class >= 1), re is below the set (class 0)
                 const bool ok = (c0 >= 2u) && (c1 <= 1u || c1 == 3u) && re >= ra && (c2 >= 1u) && (c3 == 0u || c3 == 3u);
-                if (!ok) record_settle<FILL>(r, geo, ra, re, &pc);
+                if (!ok) record_settle<FILL, CUT>(r, geo, ra, re, &pc, &k);
             }
             live = ra < re;
             mine = c4_make_rec40<FILL>(r, ra, re);
@@ -187,7 +202,7 @@ __device__ __forceinline__ uint32_t c4_setup_small(const RenderArgs &A, const Jo
 // The same for 33 .. 64 segments (<= 128 candidate roots: one per lane of waves 0 and 1).  Thread c + 128 h looks at the
 // rows around the upper end (h = 0: ra - 1 and ra) or the lower end (h = 1: re - 1 and re) of candidate c; the owners
 // (h = 0) take the guess when all four classes confirm it and walk otherwise.
-template <uint32_t RCAP, int N, uint32_t NCOL, int FILL>
+template <uint32_t RCAP, int N, uint32_t NCOL, int FILL, int CUT>
 __device__ __forceinline__ uint32_t c4_setup_mid(const RenderArgs &A, const Job &job, uint32_t seg0, uint32_t nseg, uint32_t x0s,
                                                  int phase, float *s_cxp, Rec40 *s_rec, uint32_t *s_wcnt, uint32_t *s_tmp, const float *cyt = nullptr)
 {
@@ -203,12 +218,16 @@ __device__ __forceinline__ uint32_t c4_setup_mid(const RenderArgs &A, const Job 
     Piece pc;
     g.empty = true; g.ra = 1u; g.re = 0u;
     uint32_t cls0 = 3u, cls1 = 3u;                      // 3: no such row / not asked
+    Cut k;
+    k.lo = k.hi = 0.0f;
     if (have) {
-        record_prep<FILL>(A.seg_pts + 6u * (size_t)(seg0 + (c >> 1)), c & 1u, geo, r, g, &pc);
+        bool drop = false;
+        if constexpr (CUT != 0) { k = c4_load_cut(A, seg0, c); drop = cut_misses(k, row_span(geo)); }
+        record_prep<FILL>(A.seg_pts + 6u * (size_t)(seg0 + (c >> 1)), c & 1u, geo, r, g, &pc, drop);
         if (!g.empty) {
             const uint32_t end = h ? g.re : g.ra;       // rows end - 1 and end
-            if (end - 1u < Hs && (h == 0u || g.re > g.ra)) cls0 = (uint32_t)row_class<FILL>(r, pc, geo.cy(end - 1u));
-            if (end < Hs) cls1 = (uint32_t)row_class<FILL>(r, pc, geo.cy(end));
+            if (end - 1u < Hs && (h == 0u || g.re > g.ra)) cls0 = (uint32_t)row_class<FILL, CUT>(r, pc, geo.cy(end - 1u), &k);
+            if (end < Hs) cls1 = (uint32_t)row_class<FILL, CUT>(r, pc, geo.cy(end), &k);
         }
     }
     s_tmp[tid] = cls0 | (cls1 << 8);
@@ -226,7 +245,7 @@ __device__ __forceinline__ uint32_t c4_setup_mid(const RenderArgs &A, const Job 
             const uint32_t up = s_tmp[c], dn = s_tmp[128u + c];
             const uint32_t c0 = up & 0xffu, c1 = up >> 8, c2 = dn & 0xffu, c3 = dn >> 8;
             const bool ok = (c0 >= 2u) && (c1 <= 1u || c1 == 3u) && re >= ra && (c2 >= 1u) && (c3 == 0u || c3 == 3u);
-            if (!ok) record_settle<FILL>(r, geo, ra, re, &pc);
+            if (!ok) record_settle<FILL, CUT>(r, geo, ra, re, &pc, &k);
         }
         live = ra < re;
         mine = c4_make_rec40<FILL>(r, ra, re);
@@ -250,14 +269,14 @@ __device__ __forceinline__ uint32_t c4_setup_mid(const RenderArgs &A, const Job 
 // exact range of this cell's sample rows that accept each (fr_records.hpp), compacted into s_rec (<= RCAP kept), and
 // the padded table of the strip's exact sample abscissae.  Two workgroup barriers.  -> number of records.
 // N: samples per pixel axis (4: cov4_kernel, 1: win1_kernel); NCOL: sample columns of the strip.
-template <uint32_t NW, uint32_t RCAP, int N, uint32_t NCOL, int FILL = 0>
-__device__ __forceinline__ uint32_t c4_setup(const RenderArgs &A, const Job &job, uint32_t seg0, uint32_t nseg, uint32_t x0s,
-                                             int phase, float *s_cxp, Rec40 *s_rec, uint32_t *s_wcnt, uint32_t *s_tmp, const float *cyt = nullptr)
+template <uint32_t NW, uint32_t RCAP, int N, uint32_t NCOL, int FILL, int CUT>
+__device__ __forceinline__ uint32_t c4_setup_with(const RenderArgs &A, const Job &job, uint32_t seg0, uint32_t nseg, uint32_t x0s,
+                                                  int phase, float *s_cxp, Rec40 *s_rec, uint32_t *s_wcnt, uint32_t *s_tmp, const float *cyt)
 {
     if (NW == 4u && 2u * nseg <= 64u)                                        // (workgroup-uniform; s_tmp: 1 KB, free until the bands start)
-        return c4_setup_small<RCAP, N, NCOL, FILL>(A, job, seg0, nseg, x0s, phase, s_cxp, s_rec, s_wcnt, s_tmp, cyt);
+        return c4_setup_small<RCAP, N, NCOL, FILL, CUT>(A, job, seg0, nseg, x0s, phase, s_cxp, s_rec, s_wcnt, s_tmp, cyt);
     if (NW == 4u && 2u * nseg <= 128u)
-        return c4_setup_mid<RCAP, N, NCOL, FILL>(A, job, seg0, nseg, x0s, phase, s_cxp, s_rec, s_wcnt, s_tmp, cyt);
+        return c4_setup_mid<RCAP, N, NCOL, FILL, CUT>(A, job, seg0, nseg, x0s, phase, s_cxp, s_rec, s_wcnt, s_tmp, cyt);
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t Hs = job.h * (uint32_t)N;
     const ScaleDiv sdiv = scale_div(job.scale);
@@ -277,7 +296,13 @@ __device__ __forceinline__ uint32_t c4_setup(const RenderArgs &A, const Job &job
             Rec r;
             RowGeom geo;
             geo.max_y = job.max_y; geo.set_scale(sdiv); geo.rows = Hs; geo.n = N; geo.phase = phase; geo.cyt = cyt;
-            build_record_rows<FILL>(A.seg_pts + 6u * (size_t)(seg0 + (c >> 1)), c & 1u, geo, r);
+            if constexpr (CUT != 0) {
+                const Cut k = c4_load_cut(A, seg0, c);
+                const RowSpan span = row_span(geo);
+                build_record_rows<FILL, CUT>(A.seg_pts + 6u * (size_t)(seg0 + (c >> 1)), c & 1u, geo, r, &k, &span);
+            } else {
+                build_record_rows<FILL>(A.seg_pts + 6u * (size_t)(seg0 + (c >> 1)), c & 1u, geo, r);
+            }
             const uint32_t ra = __builtin_bit_cast(uint32_t, r.lo), re = __builtin_bit_cast(uint32_t, r.hi);
             live = ra < re;
             mine[it] = c4_make_rec40<FILL>(r, ra, re);
@@ -324,6 +349,23 @@ __device__ __forceinline__ uint32_t c4_setup(const RenderArgs &A, const Job &job
     rec_cnt = min(rec_cnt, RCAP);
     __syncthreads();
     return rec_cnt;
+}
+
+// the set-up with the glyph set's row cuts where the launch has them (A.seg_cut: the same for the whole grid), else without
+template <uint32_t NW, uint32_t RCAP, int N, uint32_t NCOL, int FILL = 0>
+__device__ __forceinline__ uint32_t c4_setup(const RenderArgs &A, const Job &job, uint32_t seg0, uint32_t nseg, uint32_t x0s,
+                                             int phase, float *s_cxp, Rec40 *s_rec, uint32_t *s_wcnt, uint32_t *s_tmp, const float *cyt = nullptr)
+{
+    // (FR_C4_ROW_CUTS: listing builds that hold one of the two paths alone — tools/trip_cost.py prices each; never shipped)
+#if !defined(FR_C4_ROW_CUTS) || FR_C4_ROW_CUTS == 1
+    if constexpr (FILL == 0) {
+#ifndef FR_C4_ROW_CUTS
+        if (A.seg_cut)
+#endif
+            return c4_setup_with<NW, RCAP, N, NCOL, 0, 1>(A, job, seg0, nseg, x0s, phase, s_cxp, s_rec, s_wcnt, s_tmp, cyt);
+    }
+#endif
+    return c4_setup_with<NW, RCAP, N, NCOL, FILL, 0>(A, job, seg0, nseg, x0s, phase, s_cxp, s_rec, s_wcnt, s_tmp, cyt);
 }
 
 }  // namespace fr

@@ -1,6 +1,7 @@
 // fr_prepare.hip — stand-alone per-glyph-set precompute of the root records (fr_records.hpp).
 // Used at glyph-set creation (the records serve the render kernel's over-full rows and the SDF sign) and, per render,
-// for glyphs too large for the render kernel's in-LDS record build.
+// for glyphs too large for the render kernel's in-LDS record build.  Also the glyph set's row cuts (cut_kernel), found
+// once at creation.
 #include "fr_records.hpp"
 
 namespace fr {
@@ -60,6 +61,32 @@ __global__ __launch_bounds__(64) void prepare_fill_kernel(const int16_t *__restr
                                                      uint32_t *__restrict__ glyph_rec_count)
 {
     prepare_body<1>(pts, seg_p0, glyph_seg_start, glyph_list, n_glyphs, out_recs, glyph_rec_count);
+}
+
+// The row cuts of a glyph set (fr_records.hpp): thread c = 2 segment + root builds the candidate's record as the fast
+// kernels' set-up does (record_prep, no cell) and bisects for its two cuts with classify_row.  A candidate that
+// record_prep discards without a probe gets the empty cut {+inf, -inf}; the set-up discards it by the same rule and
+// never reads the entry.  out: one float4 {lo0, hi0, lo1, hi1} per segment, written as two float2.
+__global__ __launch_bounds__(256) void cut_kernel(const int16_t *__restrict__ seg_pts, uint32_t n_cand, float2 *__restrict__ out)
+{
+    const uint32_t c = blockIdx.x * 256u + threadIdx.x;
+    if (c >= n_cand) return;
+    RowGeom G;                                     // (no cell: record_prep's row guesses are not used)
+    G.max_y = 0; G.scale = 1.0f; G.rows = 0u; G.n = 1; G.phase = 0;
+    Rec r;
+    RowGuess g;
+    record_prep<0>(seg_pts + 6u * (size_t)(c >> 1), c & 1u, G, r, g);
+    Cut k;
+    k.lo = __builtin_inff(); k.hi = -__builtin_inff();
+    if (!g.empty) k = find_cut(r);
+    out[c] = make_float2(k.lo, k.hi);
+}
+
+void launch_cuts(const int16_t *seg_pts, uint32_t n_seg, float4 *out, hipStream_t stream)
+{
+    if (n_seg == 0) return;
+    const uint32_t n_cand = 2u * n_seg;
+    hipLaunchKernelGGL(cut_kernel, dim3((uint32_t)(((uint64_t)n_cand + 255u) / 256u)), dim3(256), 0, stream, seg_pts, n_cand, reinterpret_cast<float2 *>(out));
 }
 
 void launch_prepare(const int16_t *pts, const uint32_t *seg_p0, const uint32_t *glyph_seg_start,

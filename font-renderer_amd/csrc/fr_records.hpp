@@ -224,11 +224,64 @@ __device__ __forceinline__ int classify_fill(const Piece &pc, float cy)
     const bool below = (pc.vend == 1u) ? !fill_at_or_above_vertex(pc, cy) : (cy < pc.ylo);
     return above ? 2 : (below ? 0 : 1);
 }
-// the class a record build walks with: the reference's acceptance (FILL = 0) or the piece's (FILL = 1)
-template <int FILL>
-__device__ __forceinline__ int row_class(const Rec &r, const Piece &pc, float cy)
+// ---------------------------------------------------------------------------------------------
+// Row cuts.  classify_row is a monotone step function 0 -> 1 -> 2 of cy (the header of this
+// file), so a candidate has two keys K1 <= K2 with class 0 below K1, 1 in [K1, K2) and 2 from K2 on.  They depend on the
+// segment's control points and the root only — not on cell, scale, sample grid or phase — and cut_kernel (fr_prepare.hip)
+// finds them once per glyph set by bisection with classify_row itself: a Cut is {key2f(K1), key2f(K2 - 1)}, and the
+// class of a ray height is the two compares of classify_cut.  K1 == K2 (never accepted) gives lo just above hi: still
+// a monotone class, 0 or 2 everywhere.
+//
+// The heights a render can form are 0 and 2^-23 <= |cy| < 2^43 (fr_device.hpp, ScaleDiv); sqrt_rn and div_by_int are
+// the correctly rounded operations only there.  The bisection runs over the keys of [-2^43, 2^43], and cut_height()
+// maps the heights below 2^-23 in magnitude onto the zero of their sign (a non-decreasing map, so
+// class(cut_height(cy)) is monotone over that whole range, and equal to class(cy) wherever a render looks).  Both ends
+// of a Cut are then normal numbers or a zero.
+//
+// +-0: delta = fl(fl(cy a) + c1) - c2 with c1 = p1y^2 >= +0, so fl(cy a) + c1 is the same binary32 for cy = -0 and
+// cy = +0; the linear t = (cy - p0y) / den is +-0 or the same non-zero number, and neither zero is < 0 or >= 1.  Hence
+// class(-0) == class(+0) for every record: no cut falls between the two zeros, and the compares of classify_cut are
+// plain float compares (under which -0 == +0) — they decide exactly as compares of the keys would.
+struct Cut {
+    float lo, hi;        // class 0 below lo, 2 above hi, 1 in [lo, hi]
+};
+__device__ __forceinline__ int classify_cut(const Cut &k, float cy)
 {
+    return cy > k.hi ? 2 : (cy < k.lo ? 0 : 1);
+}
+constexpr float CUT_HEIGHT_MIN = 1.1920929e-07f;         // 2^-23: the smallest non-zero |cy| of a render
+constexpr float CUT_HEIGHT_MAX = 8796093022208.0f;       // 2^43
+__device__ __forceinline__ float cut_height(float cy)
+{
+    return fabsf(cy) < CUT_HEIGHT_MIN ? __builtin_copysignf(0.0f, cy) : cy;
+}
+// the Cut of a candidate whose record is r: two bisections over the ordered keys, 2 x 32 evaluations of classify_row
+__device__ inline Cut find_cut(const Rec &r)
+{
+    const uint32_t kmin = f2key(-CUT_HEIGHT_MAX), kmax = f2key(CUT_HEIGHT_MAX);
+    auto first_at_least = [&](int T, uint32_t L) {        // smallest key in [L, kmax + 1] whose class is >= T
+        uint32_t H = kmax + 1u;
+        while (L < H) {
+            const uint32_t mid = L + ((H - L) >> 1);
+            if (classify_row(r, cut_height(key2f(mid))) >= T) H = mid; else L = mid + 1u;
+        }
+        return L;
+    };
+    const uint32_t K1 = first_at_least(1, kmin), K2 = first_at_least(2, K1);
+    Cut k;
+    k.lo = key2f(K1);
+    k.hi = key2f(K2 - 1u);
+    return k;
+}
+
+// the class a record build walks with: the reference's acceptance (FILL = 0) or the piece's (FILL = 1); CUT = 1: the
+// reference's acceptance read off the candidate's row cut
+template <int FILL, int CUT = 0>
+__device__ __forceinline__ int row_class(const Rec &r, const Piece &pc, float cy, const Cut *k = nullptr)
+{
+    static_assert(!(FILL != 0 && CUT != 0), "row cuts hold the reference's acceptance only");
     if constexpr (FILL != 0) return classify_fill(pc, cy);
+    else if constexpr (CUT != 0) return classify_cut(*k, cy);
     else return classify_row(r, cy);
 }
 
@@ -242,8 +295,9 @@ struct RowGuess {
     bool empty;          // the candidate is discarded without a probe (see above)
 };
 
+// `drop`: the caller already knows that no row of the cell accepts the candidate (its row cut misses the cell's heights)
 template <int FILL = 0>
-__device__ __forceinline__ void record_prep(const int16_t *p, uint32_t root, const RowGeom &G, Rec &r, RowGuess &g, Piece *pc = nullptr)
+__device__ __forceinline__ void record_prep(const int16_t *p, uint32_t root, const RowGeom &G, Rec &r, RowGuess &g, Piece *pc = nullptr, bool drop = false)
 {
     const float p0x = (float)p[0], p0y = (float)p[1];
     const float p1x = (float)p[2], p1y = (float)p[3];
@@ -304,6 +358,7 @@ __device__ __forceinline__ void record_prep(const int16_t *p, uint32_t root, con
             stop_incl = true;
         }
     }
+    empty = empty || drop;
     g.empty = empty;
     g.ra = 1u; g.re = 0u;
     if (!empty) {
@@ -320,11 +375,12 @@ __device__ __forceinline__ void record_prep(const int16_t *p, uint32_t root, con
 }
 
 // the exact ends from any starting guess: walk while the class of the row says so
-template <int FILL = 0>
-__device__ __forceinline__ void record_settle(const Rec &r, const RowGeom &G, uint32_t &ra, uint32_t &re, const Piece *pc = nullptr)
+template <int FILL = 0, int CUT = 0>
+__device__ __forceinline__ void record_settle(const Rec &r, const RowGeom &G, uint32_t &ra, uint32_t &re, const Piece *pc = nullptr, const Cut *k = nullptr)
 {
     auto classify_row = [&](const Rec &rr, float cy) {
         if constexpr (FILL != 0) return classify_fill(*pc, cy);
+        else if constexpr (CUT != 0) return classify_cut(*k, cy);
         else return fr::classify_row(rr, cy);
     };
     // (one trip each when the guess is right: keep the compiler from unrolling them)
@@ -339,14 +395,46 @@ __device__ __forceinline__ void record_settle(const Rec &r, const RowGeom &G, ui
     while (re < G.rows && classify_row(r, G.cy(re)) >= 1) ++re;
 }
 
-template <int FILL = 0>
-__device__ __forceinline__ void build_record_rows(const int16_t *p, uint32_t root, const RowGeom &G, Rec &r)
+// Bounds of the cell's ray heights: top >= cy(0), bot <= cy(rows - 1) — what a row cut is held against before any row is
+// looked at.  Exact when the division is a multiply (scale = 2^k).  Otherwise the quotients are taken with v_rcp_f32
+// (1 ulp) and one multiply instead of two IEEE divisions, and moved outwards by 2^-20 of their magnitude, eight times
+// the error of the two roundings: a bound that is too wide only keeps a candidate that the walks then settle as empty.
+struct RowSpan {
+    float top, bot;
+};
+__device__ __forceinline__ RowSpan row_span(const RowGeom &G)
+{
+    const uint32_t last = G.rows ? G.rows - 1u : 0u;
+    const float nt = (float)G.max_y - sub_off(0, G.n, G.phase);
+    const float nb = (float)(G.max_y - (int32_t)(last / (uint32_t)G.n)) - sub_off((int)(last % (uint32_t)G.n), G.n, G.phase);
+    RowSpan s;
+    if (G.pow2) {
+        s.top = nt * G.inv;
+        s.bot = nb * G.inv;
+    } else {
+        const float rs = __builtin_amdgcn_rcpf(G.scale);
+        const float t = nt * rs, b = nb * rs;
+        s.top = __builtin_fmaf(fabsf(t), 9.5367431640625e-07f, t);
+        s.bot = __builtin_fmaf(fabsf(b), -9.5367431640625e-07f, b);
+    }
+    return s;
+}
+// no row of the cell can have class 1: the cut is empty, lies wholly above the cell or wholly below it
+__device__ __forceinline__ bool cut_misses(const Cut &k, const RowSpan &s)
+{
+    return !(k.lo <= k.hi) || k.hi < s.bot || k.lo > s.top;
+}
+
+template <int FILL = 0, int CUT = 0>
+__device__ __forceinline__ void build_record_rows(const int16_t *p, uint32_t root, const RowGeom &G, Rec &r, const Cut *k = nullptr, const RowSpan *span = nullptr)
 {
     RowGuess g;
     Piece pc;
-    record_prep<FILL>(p, root, G, r, g, &pc);
+    bool drop = false;
+    if constexpr (CUT != 0) drop = cut_misses(*k, *span);
+    record_prep<FILL>(p, root, G, r, g, &pc, drop);
     uint32_t ra = g.ra, re = g.re;
-    if (!g.empty) record_settle<FILL>(r, G, ra, re, &pc);
+    if (!g.empty) record_settle<FILL, CUT>(r, G, ra, re, &pc, k);
     r.lo = __builtin_bit_cast(float, ra);
     r.hi = __builtin_bit_cast(float, re);
 }

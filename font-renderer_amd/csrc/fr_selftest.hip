@@ -10,7 +10,7 @@
 // correctly-rounded division).  Scaling x by 2^k is exact for q, r and q', so one binade
 // represents them all while every intermediate stays normal.
 #include "../../include/fr_raster.h"
-#include "fr_device.hpp"
+#include "fr_records.hpp"
 
 namespace fr {
 
@@ -82,6 +82,63 @@ __global__ __launch_bounds__(256) void selftest_sqrt_fast_kernel(uint32_t e_lo, 
         atomicAdd(mismatches, (unsigned long long)bad);
         first_bad[0] = bad_x;
     }
+}
+
+// The glyph set's row cuts (fr_records.hpp) against the expression they stand for, over the cells of `jobs`.
+// Block (j, chunk): job j, sample rows [64 chunk, 64 chunk + 64) of its cell; thread t takes candidates t, t + 256, ...
+// of the job's glyph that record_prep does not discard, and for each compares classify_cut with classify_row at every
+// row of the chunk.  Chunk 0 also settles each candidate's row range both ways from the same guess — and, as the
+// set-ups do, takes a cut that misses the cell's heights for an empty range — and compares the two.
+// res[0]: (candidate, row) pairs compared, res[1]: mismatches, res[2]: the smallest mismatch as
+// job << 40 | candidate << 20 | row (row 0xfffff: the settled ranges differ).
+__global__ __launch_bounds__(256) void selftest_row_cuts_kernel(const Job *__restrict__ jobs, const uint32_t *__restrict__ glyph_seg_start,
+                                                                const int16_t *__restrict__ seg_pts, const float4 *__restrict__ seg_cut,
+                                                                int n, int phase, unsigned long long *res)
+{
+    const uint32_t j = blockIdx.x, row0 = blockIdx.y * 64u;
+    const Job job = jobs[j];
+    const uint32_t rows = job.h * (uint32_t)n;
+    if (row0 >= rows) return;
+    const uint32_t row1 = min(row0 + 64u, rows);
+    const uint32_t seg0 = glyph_seg_start[job.glyph], n_cand = 2u * (glyph_seg_start[job.glyph + 1u] - seg0);
+    RowGeom geo;
+    geo.max_y = job.max_y; geo.set_scale(scale_div(job.scale)); geo.rows = rows; geo.n = n; geo.phase = phase;
+    const RowSpan span = row_span(geo);
+    unsigned long long pairs = 0ull, bad = 0ull, first = ~0ull;
+    for (uint32_t c = threadIdx.x; c < n_cand; c += 256u) {
+        Rec r;
+        RowGuess g;
+        record_prep<0>(seg_pts + 6u * (size_t)(seg0 + (c >> 1)), c & 1u, geo, r, g);
+        if (g.empty) continue;
+        const float2 q = reinterpret_cast<const float2 *>(seg_cut)[2u * (size_t)seg0 + c];
+        Cut k;
+        k.lo = q.x; k.hi = q.y;
+        const unsigned long long where = ((unsigned long long)j << 40) | ((unsigned long long)min(c, 0xfffffu) << 20);
+        for (uint32_t row = row0; row < row1; ++row) {
+            const float cy = geo.cy(row);
+            ++pairs;
+            if (classify_cut(k, cy) != classify_row(r, cy)) { ++bad; first = min(first, where | row); }
+        }
+        if (row0 == 0u) {
+            uint32_t ra0 = g.ra, re0 = g.re, ra1 = g.ra, re1 = g.re;
+            record_settle<0, 0>(r, geo, ra0, re0);
+            record_settle<0, 1>(r, geo, ra1, re1, nullptr, &k);
+            bool differ = ra0 != ra1 || re0 != re1;
+            if (cut_misses(k, span)) differ = differ || ra0 < re0;
+            if (differ) { ++bad; first = min(first, where | 0xfffffull); }
+        }
+    }
+    if (pairs) atomicAdd(&res[0], pairs);
+    if (bad) { atomicAdd(&res[1], bad); atomicMin(&res[2], first); }
+}
+
+// jobs: device memory.  max_rows: the largest h * n among them.  res: three zero-initialised (res[2]: all ones) words
+void launch_selftest_row_cuts(const Job *jobs, uint32_t n_jobs, uint32_t max_rows, const uint32_t *glyph_seg_start, const int16_t *seg_pts,
+                              const float4 *seg_cut, int n, int phase, unsigned long long *res, hipStream_t stream)
+{
+    if (n_jobs == 0 || max_rows == 0) return;
+    hipLaunchKernelGGL(selftest_row_cuts_kernel, dim3(n_jobs, (max_rows + 63u) / 64u), dim3(256), 0, stream, jobs, glyph_seg_start,
+                       seg_pts, seg_cut, n, phase, res);
 }
 
 }  // namespace fr

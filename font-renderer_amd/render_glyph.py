@@ -85,6 +85,17 @@ class DeviceGlyphSet:
         L.check(self.ctx._lib.fr_glyphset_stats(self._h, C.byref(a), C.byref(b)))
         return {"segments": a.value, "records": b.value}
 
+    def selftest_row_cuts(self, jobs: np.ndarray, samples_per_axis: int = 1, sample_phase: int = L.FR_SAMPLE_CORNER):
+        """fr_selftest_row_cuts over the cells of `jobs`: the set's row cuts against the acceptance expression at every
+        sample row -> (pairs compared, mismatches, (job, candidate, row) of the first mismatch)"""
+        assert jobs.dtype.itemsize == 32
+        jobs = np.ascontiguousarray(jobs)
+        pairs, bad = C.c_uint64(), C.c_uint64()
+        first = (C.c_uint32 * 3)()
+        L.check(self.ctx._lib.fr_selftest_row_cuts(self._h, L.ptr(jobs), len(jobs), samples_per_axis, sample_phase,
+                                                   C.byref(pairs), C.byref(bad), first))
+        return pairs.value, bad.value, tuple(first)
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             self.ctx._lib.fr_glyphset_destroy(self._h)

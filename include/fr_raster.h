@@ -123,7 +123,10 @@ int fr_ctx_sync(fr_ctx *ctx);
  * exact direct-sum fallback: rounded up to 8, 16 or 32; default 32), "strip_px" (column
  * strip width in pixels, multiple of 16, <= 256: wider cells are rendered strip by strip; the fast kernels use
  * the largest of 64 / 128 / 256 that does not exceed it),
- * "cov4" (0: every job takes the general kernel), "sdf_cull" (0: FR_SDF_U8 looks at every segment from
+ * "cov4" (0: every job takes the general kernel), "row_cuts" (default 1: the set-up of the fast kernels reads the
+ * class of a sample row off the glyph set's row cuts — two heights per candidate root, found once by
+ * fr_glyphset_create, 16 bytes per segment; 0: it evaluates the reference's acceptance expression at the row, as
+ * fr_render_glyph always does.  The pixels are the same either way: fr_selftest_row_cuts), "sdf_cull" (0: FR_SDF_U8 looks at every segment from
  * every pixel — the culls are exact, this is how the tests show it), "zero_copy" (1: fr_render_glyph renders small
  * glyphs straight from / into pinned host memory; measured no faster, off by default), "overlap" (a plan that needs several kernel launches forks the
  * smaller ones onto an internal second stream and joins them: 1 (default) for plans of >= 32 Mpixel — below that one
@@ -635,6 +638,15 @@ int fr_selftest_division(uint32_t d_lo, uint32_t d_hi, uint64_t *mismatches,
  * the general lowering; this compares it with the correctly rounded sqrt for every binary32 in
  * [2^-30, 2^66) on the device.  *mismatches must come back 0.                                  */
 int fr_selftest_sqrt(uint64_t *mismatches, uint32_t *bad_x_bits);
+/* The row cuts of a glyph set (option "row_cuts") stand for the reference's acceptance test of a candidate root at a
+ * ray height.  For every job, every candidate root of its glyph that the set-up does not discard from its control
+ * points alone, and EVERY sample row of the job's cell (h * samples_per_axis rows at sample phase `phase`), this
+ * compares on the device the class the cuts give with the class the acceptance expression gives, and once per job and
+ * candidate the row range the set-up settles either way.  *pairs: the (candidate, row) pairs compared; *mismatches must
+ * come back 0; first_bad (may be NULL, else three words): job, candidate (2 * segment of the glyph + root) and row of
+ * the smallest mismatch, row 0xfffff meaning the settled ranges.  Jobs are checked as fr_plan_create checks them.  */
+int fr_selftest_row_cuts(fr_glyphset *gs, const fr_job *jobs, uint32_t n_jobs, int samples_per_axis, int phase,
+                         uint64_t *pairs, uint64_t *mismatches, uint32_t *first_bad);
 
 #ifdef __cplusplus
 }

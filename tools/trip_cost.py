@@ -18,6 +18,9 @@ compiler's assembly and every vector instruction in them is classified by mnemon
           instructions per division: the sequence itself is 11) — blocks a job whose scale is a power of two branches
           around.  (A division by the scale is a v_div_fixup_f32 whose divisor is an SGPR: the scale is the only scalar
           divisor in the kernel.  Where the division sits inside a larger block, every job executes it.)
+          The shipped set-up holds two copies of each of its three forms: one reads a row's class off the glyph set's row
+          cuts, one evaluates the reference's acceptance (fr_records.hpp).  They are priced apart from two more listings,
+          compiled with -DFR_C4_ROW_CUTS=1 and =0, which hold one copy each.
 
 The counts are static: instructions in the text, not instructions executed.  The script reads only the mnemonics it
 classifies; labels, scalar instructions, LDS and memory instructions are counted as "other" and not priced."""
@@ -48,9 +51,9 @@ def makefile_flags():
     return flags.replace("$(ARCH)", arch).split()
 
 
-def compile_asm(path):
+def compile_asm(path, defs=()):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cmd = [hipcc] + makefile_flags() + ["-S", "--cuda-device-only", os.path.join(CSRC, "fr_cov4.hip"), "-o", path]
+    cmd = [hipcc] + makefile_flags() + list(defs) + ["-S", "--cuda-device-only", os.path.join(CSRC, "fr_cov4.hip"), "-o", path]
     subprocess.check_call(cmd, cwd=CSRC)
 
 
@@ -150,6 +153,19 @@ def is_scale_division(l):
     return bool(m) and m.group(1).startswith("s")
 
 
+def setup_paths(lines):
+    """-> (price of all set-up code, price of it without the blocks that only divide by the scale, divisions, of them aside)"""
+    last_barrier = max(i for i, l in enumerate(lines) if mnemonic(l) == "s_barrier")
+    setup = lines[:last_barrier + 1]
+    side, ndiv = [], sum(is_scale_division(l) for l in setup)
+    for _, _, body in blocks(setup):
+        n = sum(is_scale_division(l) for l in body)
+        if n and price(body)["valu"] <= 12 * n:
+            side += body
+    cs, ca = price(side), price(setup)
+    return ca, {k: ca[k] - cs[k] for k in ca}, ndiv, sum(is_scale_division(l) for l in side)
+
+
 def report(name, c, note=""):
     print(f"{name:<34} VALU {c['valu']:>5}   fast {c['fast']:>5}  normal {c['normal']:>5}  slow {c['slow']:>4}   "
           f"priced {c['ns']:>9.1f} ns{note}")
@@ -158,6 +174,8 @@ def report(name, c, note=""):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--asm", help="assembly of fr_cov4.hip made earlier; default: compile it now")
+    ap.add_argument("--asm-cuts", help="with --asm: assembly made with -DFR_C4_ROW_CUTS=1 (the set-up with row cuts alone)")
+    ap.add_argument("--asm-nocuts", help="with --asm: assembly made with -DFR_C4_ROW_CUTS=0 (the set-up that evaluates the acceptance alone)")
     ap.add_argument("--show", action="store_true", help="also print the trip's instructions with their classes")
     a = ap.parse_args()
     if a.asm:
@@ -180,19 +198,20 @@ def main():
               f"   (VALU per block: min {min(c['valu'] for c in tog)}, median {int(statistics.median(c['valu'] for c in tog))}, "
               f"max {max(c['valu'] for c in tog)})")
 
-    last_barrier = max(i for i, l in enumerate(lines) if mnemonic(l) == "s_barrier")
-    setup = lines[:last_barrier + 1]
-    report("set-up, all code", price(setup))
-    bl = blocks(setup)
-    side, ndiv = [], sum(is_scale_division(l) for l in setup)
-    for _, _, body in bl:
-        n = sum(is_scale_division(l) for l in body)
-        if n and price(body)["valu"] <= 12 * n:
-            side += body
-    cs, ca = price(side), price(setup)
-    path = {k: ca[k] - cs[k] for k in ca}
+    ca, path, ndiv, naside = setup_paths(lines)
+    report("set-up, all code", ca)
     report("set-up, power-of-two scale path", path,
-           f"   ({ndiv} divisions by the scale in the text, {sum(is_scale_division(l) for l in side)} of them in blocks of their own)")
+           f"   ({ndiv} divisions by the scale in the text, {naside} of them in blocks of their own)")
+    # the two ways a row's class is found, each from a listing build that holds it alone (FR_C4_ROW_CUTS, fr_c4.hpp)
+    if not a.asm or a.asm_cuts:
+        with tempfile.TemporaryDirectory() as d:
+            for name, val, given in (("acceptance evaluated", 0, a.asm_nocuts), ("row cuts", 1, a.asm_cuts)):
+                if not given:
+                    given = os.path.join(d, f"cov4_{val}.s")
+                    compile_asm(given, [f"-DFR_C4_ROW_CUTS={val}"])
+                ca1, path1, _, _ = setup_paths(kernel_lines(given))
+                report(f"set-up, {name}: all code", ca1)
+                report(f"set-up, {name}: 2^k scale", path1)
     if a.show:
         print("#\n# the trip:")
         for l in trip:
