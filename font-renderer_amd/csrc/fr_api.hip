@@ -117,13 +117,6 @@ struct fr_glyphset {
     std::vector<int16_t> h_box;                 // fr_glyphset_set_boxes: Glyph.box per glyph (x_min, y_min, x_max, y_max); empty until set
 };
 
-// the placement form of a text plan: fr_glyph_place (TextInst, the text_* kernels), fr_glyph_place_ex (TextInstEx,
-// text_place_*) or fr_glyph_place_affine (TextInstAffine, the text_affine_* kernels of fr_text_affine.hip)
-enum TextForm { TEXT_PLAIN, TEXT_EX, TEXT_AFFINE };
-static constexpr TextForm text_form_of(const fr_glyph_place *) { return TEXT_PLAIN; }
-static constexpr TextForm text_form_of(const fr_glyph_place_ex *) { return TEXT_EX; }
-static constexpr TextForm text_form_of(const fr_glyph_place_affine *) { return TEXT_AFFINE; }
-
 struct fr_plan {
     fr_ctx *ctx = nullptr;
     const fr_glyphset *gs = nullptr;
@@ -144,27 +137,20 @@ struct fr_plan {
     void *g_out = nullptr;
     size_t g_stride = 0, g_rows = 0;
     uint32_t g_epoch = 0;
-    // a text plan (fr_text_plan_create): its tables (fr_text.hpp), the distinct glyphs whose records prepare_kernel rebuilds
-    // into plan-owned memory before every render, and its counts
+    // a text plan (fr_text_plan_create): what its launches depend on (fr_text_plan.hpp), its tables (fr_text.hpp) and the
+    // distinct glyphs whose records prepare_kernel rebuilds into plan-owned memory before every render
     bool text = false;
-    bool rgba = false;                 // fr_text_plan_create_rgba: RGBA pixels, text_rgba_kernel
-    bool srgb = false;                 // (rgba) FR_TEXT_SRGB: text_srgb_kernel
-    bool load = false;                 // (rgba) FR_TEXT_LOAD: text_rgba_load_kernel / text_srgb_load_kernel, occupied tiles only
-    int blend = 0;                     // (rgba) 0: every placement colour is opaque; else 1, or 2 under FR_TEXT_OVER
+    fr::TextPlan tp;
     fr::TextTile *d_tiles = nullptr;
     fr::TextRun *d_runs = nullptr;
-    TextForm text_form = TEXT_PLAIN;   // the placement form: which record d_insts holds and which kernels read it
-    void *d_insts = nullptr;           // TextInst, TextInstEx or TextInstAffine
+    void *d_insts = nullptr;           // TextInst, TextInstEx or TextInstAffine (tp.form); tp.cached: TextCachedInst
     uint32_t *d_tlist = nullptr, *d_tglyphs = nullptr, *d_trec_count = nullptr;
     fr::Rec *d_trecs = nullptr;
-    uint32_t n_tiles = 0, n_insts = 0, n_tglyphs = 0;
-    // FR_TEXT_CACHE with at least one mask cell: d_insts holds TextCachedInst, and a render fills the mask store from the
-    // cells' tiles between the prepare kernel and the composite (fr_text_cached.hip)
-    bool cached = false;
+    // tp.cached: a render fills the mask store from the cells' tiles between the prepare kernel and the composite
+    // (fr_text_cached.hip)
     fr::TextMaskCell *d_mcells = nullptr;
     fr::TextMaskTile *d_mtiles = nullptr;
     uint16_t *d_masks = nullptr;
-    uint32_t n_mcells = 0, n_mtiles = 0;
 };
 
 template <class T> static void dfree(T *&p) { if (p) { (void)hipFree(p); p = nullptr; } }
@@ -220,57 +206,50 @@ static hipError_t launch_entry(const fr_plan *plan, fr::RenderArgs a, const fr::
     }
 }
 
-// launches the text kernel of a plan over n_tiles tiles for one placement form (ARGS: fr::TextArgs, fr::TextPlaceArgs or
-// fr::TextAffineArgs, over the plan's instance table of that form); n_tiles = 0: only names it, as rocprofv3 does, into
-// name[name_cap]
+// the TextTables part of what a text kernel reads, over the plan's instance table as the record type of ARGS
+// (fr::TextArgs, fr::TextPlaceArgs, fr::TextAffineArgs or fr::TextCachedArgs, whose kernels do not read the records)
 template <class ARGS>
-static hipError_t text_args_launch(const fr_plan *plan, void *out_dev, size_t out_stride, uint32_t n_tiles, char *name = nullptr,
-                                   size_t name_cap = 0)
+static ARGS text_args(const fr_plan *plan, void *out_dev, size_t out_stride)
 {
-    ARGS a;
+    ARGS a{};
     a.tiles = plan->d_tiles; a.runs = plan->d_runs; a.list = plan->d_tlist;
     a.insts = static_cast<decltype(a.insts)>(plan->d_insts);
     a.recs = plan->d_trecs; a.rec_count = plan->d_trec_count;
     a.out = static_cast<uint8_t *>(out_dev);
     a.out_stride = out_stride;
     a.phase_center = plan->params.sample_phase == FR_SAMPLE_CENTER ? 1 : 0;
-    return fr::launch_text(a, plan->params.samples_per_axis, (plan->flags & FR_FILL_CONSISTENT) ? 1 : 0, plan->rgba, plan->blend,
-                           plan->srgb, plan->load, n_tiles, plan->ctx->stream, name, name_cap);
+    return a;
 }
 
-// the same for the plan's own form: what a render launches (text_launch) and what fr_plan_describe names
-static hipError_t text_plan_launch(const fr_plan *plan, void *out_dev, size_t out_stride, uint32_t n_tiles, char *name = nullptr,
-                                   size_t name_cap = 0)
+// one entry of a text plan's launch list (fr_text_plan.hpp) on the context's stream
+static hipError_t text_launch_entry(const fr_plan *plan, const fr::TextLaunch &e, void *out_dev, size_t out_stride)
 {
-    if (plan->cached) {
-        fr::TextCachedArgs a;
-        a.tiles = plan->d_tiles; a.runs = plan->d_runs; a.list = plan->d_tlist;
-        a.insts = static_cast<const fr::TextCachedInst *>(plan->d_insts);
-        a.recs = nullptr; a.rec_count = nullptr;
-        a.out = static_cast<uint8_t *>(out_dev);
-        a.out_stride = out_stride;
-        a.phase_center = plan->params.sample_phase == FR_SAMPLE_CENTER ? 1 : 0;
+    const fr_glyphset *gs = plan->gs;
+    hipStream_t st = plan->ctx->stream;
+    switch (e.family) {
+    case fr::TL_PREPARE:
+        fr::launch_prepare(gs->d_pts, gs->d_seg_p0, gs->d_glyph_seg_start, plan->d_tglyphs, e.grid, plan->d_trecs, plan->d_trec_count, st, e.fill);
+        return hipGetLastError();
+    case fr::TL_MASK: {
+        fr::TextMaskArgs a;
+        a.tiles = plan->d_mtiles; a.cells = plan->d_mcells;
+        a.recs = plan->d_trecs; a.rec_count = plan->d_trec_count;
         a.masks = plan->d_masks;
-        return fr::launch_text_cached(a, plan->params.samples_per_axis, plan->rgba, plan->blend, plan->srgb, plan->load, n_tiles,
-                                      plan->ctx->stream, name, name_cap);
+        a.phase_center = plan->params.sample_phase == FR_SAMPLE_CENTER ? 1 : 0;
+        return fr::launch_glyph_mask(e, a, st);
     }
-    switch (plan->text_form) {
-    case TEXT_AFFINE: return text_args_launch<fr::TextAffineArgs>(plan, out_dev, out_stride, n_tiles, name, name_cap);
-    case TEXT_EX: return text_args_launch<fr::TextPlaceArgs>(plan, out_dev, out_stride, n_tiles, name, name_cap);
-    default: return text_args_launch<fr::TextArgs>(plan, out_dev, out_stride, n_tiles, name, name_cap);
+    case fr::TL_CACHED: {
+        fr::TextCachedArgs a = text_args<fr::TextCachedArgs>(plan, out_dev, out_stride);
+        a.masks = plan->d_masks;
+        return fr::launch_text_cached(e, a, st);
     }
-}
-
-// a cached plan's mask launch: glyph_mask_kernel over n_tiles mask tiles; n_tiles = 0: only names it
-static hipError_t text_mask_launch(const fr_plan *plan, uint32_t n_tiles, char *name = nullptr, size_t name_cap = 0)
-{
-    fr::TextMaskArgs a;
-    a.tiles = plan->d_mtiles; a.cells = plan->d_mcells;
-    a.recs = plan->d_trecs; a.rec_count = plan->d_trec_count;
-    a.masks = plan->d_masks;
-    a.phase_center = plan->params.sample_phase == FR_SAMPLE_CENTER ? 1 : 0;
-    return fr::launch_glyph_mask(a, plan->params.samples_per_axis, (plan->flags & FR_FILL_CONSISTENT) ? 1 : 0, n_tiles, plan->ctx->stream,
-                                 name, name_cap);
+    default:
+        switch (e.form) {
+        case fr::TEXT_AFFINE: return fr::launch_text(e, text_args<fr::TextAffineArgs>(plan, out_dev, out_stride), st);
+        case fr::TEXT_EX: return fr::launch_text(e, text_args<fr::TextPlaceArgs>(plan, out_dev, out_stride), st);
+        default: return fr::launch_text(e, text_args<fr::TextArgs>(plan, out_dev, out_stride), st);
+        }
+    }
 }
 
 extern "C" {
@@ -672,7 +651,7 @@ int fr_glyphset_set_boxes(fr_glyphset *gs, const int16_t *boxes)
 
 }  // extern "C"
 
-// uploads the tables of text_plan_tables (fr_text_plan.hpp) and fills the text fields of a plan that its caller destroys on
+// uploads the tables of text_plan_tables (fr_text_plan.hpp) for a plan whose tp is set and that its caller destroys on
 // failure
 // `cache`: the tables of text_cache_tables for a plan that renders through its mask cells (else NULL)
 template <class PLACE>
@@ -680,10 +659,8 @@ static int text_plan_upload(const char *fn, fr_plan *p, const fr::TextPlanTables
 {
     fr_ctx *ctx = p->ctx;
     const fr_glyphset *gs = p->gs;
-    p->text_form = text_form_of((const PLACE *)nullptr);
-    p->blend = t.blend;
     p->rp.pixels = t.pixels; p->rp.need_cols = t.need_cols; p->rp.need_rows = t.need_rows;
-    p->n_tiles = (uint32_t)t.tiles.size(); p->n_insts = (uint32_t)t.insts.size(); p->n_tglyphs = (uint32_t)t.glyphs.size();
+    const bool recs = p->tp.n_glyphs != 0;
     hipStream_t st = ctx->stream;
     hipError_t e = hipSetDevice(ctx->device);
     auto upload = [&](auto *&dst, const auto &v) {
@@ -695,8 +672,6 @@ static int text_plan_upload(const char *fn, fr_plan *p, const fr::TextPlanTables
     upload(p->d_tiles, t.tiles);
     upload(p->d_runs, t.runs);
     if (cache) {
-        p->cached = true;
-        p->n_mcells = (uint32_t)cache->cells.size(); p->n_mtiles = (uint32_t)cache->tiles.size();
         upload(p->d_insts, cache->insts);
         upload(p->d_mcells, cache->cells);
         upload(p->d_mtiles, cache->tiles);
@@ -706,9 +681,9 @@ static int text_plan_upload(const char *fn, fr_plan *p, const fr::TextPlanTables
     }
     upload(p->d_tlist, t.list);
     upload(p->d_tglyphs, t.glyphs);
-    if (e == hipSuccess && p->n_tglyphs) e = hipMalloc(&p->d_trecs, 2 * (size_t)gs->n_seg * sizeof(fr::Rec));
-    if (e == hipSuccess && p->n_tglyphs) e = hipMalloc(&p->d_trec_count, ((size_t)gs->n_glyphs + 1) * 4);
-    if (e == hipSuccess && p->n_tglyphs) e = hipMemsetAsync(p->d_trec_count, 0, ((size_t)gs->n_glyphs + 1) * 4, st);
+    if (e == hipSuccess && recs) e = hipMalloc(&p->d_trecs, 2 * (size_t)gs->n_seg * sizeof(fr::Rec));
+    if (e == hipSuccess && recs) e = hipMalloc(&p->d_trec_count, ((size_t)gs->n_glyphs + 1) * 4);
+    if (e == hipSuccess && recs) e = hipMemsetAsync(p->d_trec_count, 0, ((size_t)gs->n_glyphs + 1) * 4, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e == hipSuccess) e = hipEventCreate(&p->ev0);
     if (e == hipSuccess) e = hipEventCreate(&p->ev1);
@@ -769,11 +744,10 @@ static int text_plan_create(const char *fn, fr_ctx *ctx, const fr_glyphset *gs, 
 
     fr_plan *p = new (std::nothrow) fr_plan;
     if (!p) return fail(FR_E_NOMEM, "%s: host allocation", fn);
+    const fr::TextCacheTables *const cached = cache.cells.empty() ? nullptr : &cache;
     p->ctx = ctx; p->gs = gs; p->params = *params; p->flags = flags; p->text = true;
-    p->rgba = rgba;
-    p->srgb = (flags & FR_TEXT_SRGB) != 0;
-    p->load = (flags & FR_TEXT_LOAD) != 0;
-    if (const int rc = text_plan_upload(fn, p, t, cache.cells.empty() ? nullptr : &cache)) {
+    p->tp = fr::text_plan_of(in, *params, t, cached);
+    if (const int rc = text_plan_upload(fn, p, t, cached)) {
         fr_plan_destroy(p);
         return rc;
     }
@@ -868,7 +842,7 @@ int fr_plan_stats(const fr_plan *plan, uint32_t *n_jobs_cov4, uint32_t *n_jobs_g
     if (!plan) return fail(FR_E_INVALID, "fr_plan_stats: NULL");
     if (plan->text) {                  // every instance: text_kernel, a direct sum over the glyph's records (fr_text.hip)
         if (n_jobs_cov4) *n_jobs_cov4 = 0;
-        if (n_jobs_general) *n_jobs_general = plan->n_insts;
+        if (n_jobs_general) *n_jobs_general = plan->tp.n_insts;
         return FR_OK;
     }
     if (n_jobs_cov4) *n_jobs_cov4 = plan->rp.n_fast;
@@ -887,16 +861,13 @@ int fr_plan_describe(const fr_plan *plan, char *buf, size_t cap)
         if (k > 0) at = std::min(cap - 1, at + (size_t)k);
     };
     char name[96];
-    const int fill = (plan->flags & FR_FILL_CONSISTENT) ? 1 : 0;
-    if (plan->text) {
-        if (plan->n_tglyphs) add(fill ? "fr::prepare_fill_kernel" : "fr::prepare_kernel", plan->n_tglyphs);
-        name[0] = 0;
-        if (plan->cached) {
-            (void)text_mask_launch(plan, 0u, name, sizeof name);
-            add(name, plan->n_mcells);
+    if (plan->text) {                  // the list a render walks (text_launch)
+        fr::TextLaunchList L;
+        fr::text_launches(plan->tp, L);
+        for (uint32_t i = 0; i < L.n; ++i) {
+            fr::text_launch_name(L.l[i], name, sizeof name);
+            add(name, L.l[i].count);
         }
-        (void)text_plan_launch(plan, nullptr, 0, 0u, name, sizeof name);
-        if (plan->n_tiles) add(name, plan->n_insts);
         return FR_OK;
     }
     fr::RasterLaunchList L;
@@ -927,7 +898,7 @@ static int plan_check(fr_plan *plan, void *out_dev, size_t out_stride, size_t ou
     if (!plan) return fail(FR_E_INVALID, "plan is NULL");
     // (a FR_TEXT_LOAD plan whose instances are all clipped away launches no tile, but its runs still need the output the
     // same plan with a visible glyph would: it is checked as that plan is)
-    if (plan->rp.n_jobs == 0 && plan->n_tiles == 0 && !(plan->load && plan->rp.pixels)) return FR_OK;
+    if (plan->rp.n_jobs == 0 && plan->tp.n_tiles == 0 && !(plan->tp.load && plan->rp.pixels)) return FR_OK;
     if (!out_dev) return fail(FR_E_INVALID, "out is NULL");
     if (plan->rp.need_cols > out_stride || plan->rp.need_rows > out_rows)
         return fail(FR_E_INVALID, "jobs need %llu x %llu elements, output is %zu x %zu",
@@ -935,26 +906,21 @@ static int plan_check(fr_plan *plan, void *out_dev, size_t out_stride, size_t ou
     // (the fast kernels address the rows of a wave band by 32-bit offsets from the band's base: 32 rows of the pitch)
     if (out_stride > ((size_t)1 << 26))
         return fail(FR_E_INVALID, "row pitch of %zu elements: at most 2^26", out_stride);
-    if (plan->rgba && ((uintptr_t)out_dev & 3u)) return fail(FR_E_INVALID, "RGBA output %p is not 4-byte aligned", out_dev);
+    if (plan->tp.rgba && ((uintptr_t)out_dev & 3u)) return fail(FR_E_INVALID, "RGBA output %p is not 4-byte aligned", out_dev);
     return FR_OK;
 }
 
 // one render of a text plan: the records of its glyphs from their points (plan-owned, so a plain plan's records are
 // never touched), then text_kernel over every tile of every run — two launches in stream order, nothing to fork.
-// An FR_TEXT_CACHE plan fills its mask cells from the records in between: three launches in stream order
+// An FR_TEXT_CACHE plan fills its mask cells from the records in between: three launches in stream order.  The list is the
+// one fr_plan_describe prints (text_launches, fr_text_plan.hpp); a plan without tiles has an empty one
 static int text_launch(fr_plan *plan, void *out_dev, size_t out_stride)
 {
-    if (plan->n_tiles == 0) return FR_OK;
+    fr::TextLaunchList L;
+    fr::text_launches(plan->tp, L);
+    if (L.n == 0) return FR_OK;
     HIP_TRY(hipSetDevice(plan->ctx->device));
-    const int fill = (plan->flags & FR_FILL_CONSISTENT) ? 1 : 0;
-    hipStream_t st = plan->ctx->stream;
-    if (plan->n_tglyphs) {
-        fr::launch_prepare(plan->gs->d_pts, plan->gs->d_seg_p0, plan->gs->d_glyph_seg_start, plan->d_tglyphs, plan->n_tglyphs,
-                           plan->d_trecs, plan->d_trec_count, st, fill);
-        HIP_TRY(hipGetLastError());
-    }
-    if (plan->cached) HIP_TRY(text_mask_launch(plan, plan->n_mtiles));
-    HIP_TRY(text_plan_launch(plan, out_dev, out_stride, plan->n_tiles));
+    for (uint32_t i = 0; i < L.n; ++i) HIP_TRY(text_launch_entry(plan, L.l[i], out_dev, out_stride));
     return FR_OK;
 }
 
@@ -995,7 +961,7 @@ static int plan_launch_direct(fr_plan *plan, void *out_dev, size_t out_stride, s
 static int plan_launch(fr_plan *plan, void *out_dev, size_t out_stride, size_t out_rows)
 {
     if (const int rc = plan_check(plan, out_dev, out_stride, out_rows)) return rc;
-    if (plan->rp.n_jobs == 0 && plan->n_tiles == 0) return FR_OK;
+    if (plan->rp.n_jobs == 0 && plan->tp.n_tiles == 0) return FR_OK;
     fr_ctx *const ctx = plan->ctx;
     if (!ctx->graph) return plan_launch_direct(plan, out_dev, out_stride, out_rows);
     HIP_TRY(hipSetDevice(ctx->device));

@@ -24,7 +24,6 @@
 #include "fr_srgb.hpp"
 #include "fr_wave.hpp"
 
-#include <cstdio>
 #include <type_traits>
 
 namespace fr {
@@ -105,10 +104,7 @@ FR_TEXT_GLOBAL text_place_srgb_load_kernel(TextPlaceArgs a) { colour_rows<N, FIL
 
 namespace {
 
-template <class ARGS>
-constexpr const char *text_form() { return std::is_same_v<ARGS, TextPlaceArgs> ? "place_" : ""; }
-
-// FAM: 0 coverage (its kernels have no BLEND: launch_text passes 0), 1 rgba, 2 srgb, 3 rgba load, 4 srgb load
+// FAM (TextLaunch::colour): 0 coverage (its kernels have no BLEND), 1 rgba, 2 srgb, 3 rgba load, 4 srgb load
 template <class ARGS, int FAM, int FILL, int BLEND, int N>
 constexpr auto text_kernel_of() -> void (*)(ARGS)
 {
@@ -131,11 +127,15 @@ constexpr auto text_kernel_of() -> void (*)(ARGS)
     }
 }
 
-#include "fr_text_launch.inc"
-
 }  // namespace
 
-FR_TEXT_LAUNCH_FOR(TextArgs)
-FR_TEXT_LAUNCH_FOR(TextPlaceArgs)
+hipError_t launch_text(const TextLaunch &e, const TextArgs &a, hipStream_t stream)
+{
+    return launch_text_instance(e, a, stream, [](auto FAM, auto FILL, auto BLEND, auto N) { return text_kernel_of<TextArgs, FAM, FILL, BLEND, N>(); });
+}
+hipError_t launch_text(const TextLaunch &e, const TextPlaceArgs &a, hipStream_t stream)
+{
+    return launch_text_instance(e, a, stream, [](auto FAM, auto FILL, auto BLEND, auto N) { return text_kernel_of<TextPlaceArgs, FAM, FILL, BLEND, N>(); });
+}
 
 }  // namespace fr

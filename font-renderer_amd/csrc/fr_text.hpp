@@ -1,6 +1,7 @@
 // fr_text.hpp — what a text kernel reads (the tables of fr_text_tables.hpp, on the device) and how fr_api.hip launches it
 #pragma once
 #include "fr_device.hpp"
+#include "fr_text_plan.hpp"
 #include "fr_text_tables.hpp"
 
 namespace fr {
@@ -21,14 +22,30 @@ struct TextArgs : TextTables<TextInst> {};         // fr_glyph_place placements:
 struct TextPlaceArgs : TextTables<TextInstEx> {};  // fr_glyph_place_ex placements: the text_place_*_kernel instances
 struct TextAffineArgs : TextTables<TextInstAffine> {};  // fr_glyph_place_affine placements: the text_affine_*_kernel instances
 
-// Launches the instance of a plan: n in {1, 2, 4}; rgba = 0: coverage / mask bytes (text_kernel; blend, srgb and load are
-// then ignored); else blend = 0 when every placement colour of the plan is opaque (A = 255), srgb for FR_TEXT_SRGB plans
-// (blending and resolve in linear light), load for FR_TEXT_LOAD plans (the samples start at the output's pixels; n_tiles
-// then counts only the tiles with a non-empty instance list).  n_tiles = 0: only name the instance (as rocprofv3 names
-// it) into name[name_cap].  ARGS: TextArgs or TextPlaceArgs (fr_text.hip), or TextAffineArgs (fr_text_affine.hip).
+// The launch of a text plan's launch list (fr_text_plan.hpp) that runs a text kernel over e.grid tiles: e names the
+// instance (colour family, N, FILL, BLEND), the argument type says which form's.  TextArgs and TextPlaceArgs:
+// fr_text.hip; TextAffineArgs: fr_text_affine.hip.  hipErrorInvalidValue for arguments the kernels have no instance of.
+hipError_t launch_text(const TextLaunch &e, const TextArgs &a, hipStream_t stream);
+hipError_t launch_text(const TextLaunch &e, const TextPlaceArgs &a, hipStream_t stream);
+hipError_t launch_text(const TextLaunch &e, const TextAffineArgs &a, hipStream_t stream);
+
+// one workgroup of TEXT_WAVES waves per tile
 template <class ARGS>
-hipError_t launch_text(const ARGS &a, int n, int fill, int rgba, int blend, int srgb, int load, uint32_t n_tiles, hipStream_t stream,
-                       char *name = nullptr, size_t name_cap = 0);
+inline hipError_t launch_tiles(void (*kernel)(ARGS), uint32_t n_tiles, hipStream_t stream, const ARGS &a)
+{
+    hipLaunchKernelGGL(kernel, dim3(n_tiles), dim3(64 * TEXT_WAVES), 0, stream, a);
+    return hipGetLastError();
+}
+// the look-up of both units: of(FAM, FILL, BLEND, N) is the unit's kernel for ARGS (the coverage kernels have no BLEND)
+template <class ARGS, class OF>
+inline hipError_t launch_text_instance(const TextLaunch &e, const ARGS &a, hipStream_t stream, OF of)
+{
+    const int key[] = {e.colour, e.fill, e.blend, e.n};
+    return pick(key, [&](auto FAM, auto FILL, auto BLEND, auto N) {
+        if constexpr (decltype(FAM)::value == 0 && decltype(BLEND)::value != 0) return hipErrorInvalidValue;
+        else return launch_tiles<ARGS>(of(FAM, FILL, BLEND, N), e.grid, stream, a);
+    }, Among<0, 1, 2, 3, 4>{}, Among<0, 1>{}, Among<0, 1, 2>{}, Among<1, 2, 4>{});
+}
 
 // ---- FR_TEXT_CACHE plans (fr_text_cached.hip) ---------------------------------------------------------------------------
 struct TextMaskArgs {      // what glyph_mask_kernel reads and writes
@@ -43,12 +60,10 @@ struct TextCachedArgs : TextTables<TextCachedInst> {   // the text_cached_*_kern
     const uint16_t *masks;
 };
 
-// Fills every mask cell: glyph_mask_kernel<n, fill> over n_tiles mask tiles.  n_tiles = 0: only names the instance.
-hipError_t launch_glyph_mask(const TextMaskArgs &a, int n, int fill, uint32_t n_tiles, hipStream_t stream, char *name = nullptr,
-                             size_t name_cap = 0);
-// The composite of a cached plan over n_tiles run tiles; the parameters as launch_text's, without the fill rule (it acts
-// only where masks are made).  n_tiles = 0: only names the instance.
-hipError_t launch_text_cached(const TextCachedArgs &a, int n, int rgba, int blend, int srgb, int load, uint32_t n_tiles,
-                              hipStream_t stream, char *name = nullptr, size_t name_cap = 0);
+// Fills every mask cell: glyph_mask_kernel<e.n, e.fill> over e.grid mask tiles.
+hipError_t launch_glyph_mask(const TextLaunch &e, const TextMaskArgs &a, hipStream_t stream);
+// The composite of a cached plan over e.grid run tiles: the instance of (e.colour, e.n, e.blend); no fill rule (it acts
+// only where masks are made).
+hipError_t launch_text_cached(const TextLaunch &e, const TextCachedArgs &a, hipStream_t stream);
 
 }  // namespace fr

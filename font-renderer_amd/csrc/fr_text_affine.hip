@@ -10,7 +10,6 @@
 #include "fr_srgb.hpp"
 #include "fr_wave.hpp"
 
-#include <cstdio>
 #include <type_traits>
 
 namespace fr {
@@ -43,9 +42,6 @@ FR_TEXT_GLOBAL text_affine_srgb_load_kernel(TextAffineArgs a) { affine_colour_ro
 
 namespace {
 
-template <class ARGS>
-constexpr const char *text_form() { return "affine_"; }
-
 template <class ARGS, int FAM, int FILL, int BLEND, int N>
 constexpr auto text_kernel_of() -> void (*)(ARGS)
 {
@@ -56,10 +52,11 @@ constexpr auto text_kernel_of() -> void (*)(ARGS)
     else return text_affine_srgb_load_kernel<N, FILL, BLEND>;
 }
 
-#include "fr_text_launch.inc"
-
 }  // namespace
 
-FR_TEXT_LAUNCH_FOR(TextAffineArgs)
+hipError_t launch_text(const TextLaunch &e, const TextAffineArgs &a, hipStream_t stream)
+{
+    return launch_text_instance(e, a, stream, [](auto FAM, auto FILL, auto BLEND, auto N) { return text_kernel_of<TextAffineArgs, FAM, FILL, BLEND, N>(); });
+}
 
 }  // namespace fr

@@ -20,7 +20,6 @@
 #include "fr_srgb.hpp"
 #include "fr_wave.hpp"
 
-#include <cstdio>
 #include <type_traits>
 
 namespace fr {
@@ -76,74 +75,33 @@ FR_TEXT_GLOBAL text_cached_srgb_load_kernel(TextCachedArgs a) { cached_colour_ro
 
 namespace {
 
-struct Launch {
-    uint32_t n_tiles;
-    hipStream_t stream;
-    char *name;
-    size_t name_cap;
-};
-
-template <int N, int FILL>
-hipError_t mask_instance(const TextMaskArgs &a, const Launch &l)
-{
-    if (l.name) snprintf(l.name, l.name_cap, "fr::glyph_mask_kernel<%d, %d>", N, FILL);      // as rocprofv3 names the instance
-    if (!l.n_tiles) return hipSuccess;
-    hipLaunchKernelGGL((glyph_mask_kernel<N, FILL>), dim3(l.n_tiles), dim3(64 * TEXT_WAVES), 0, l.stream, a);
-    return hipGetLastError();
-}
-
-// FAM: 0 coverage (no BLEND), 1 rgba, 2 srgb, 3 rgba load, 4 srgb load
+// FAM (TextLaunch::colour): 0 coverage (no BLEND), 1 rgba, 2 srgb, 3 rgba load, 4 srgb load
 template <int FAM, int BLEND, int N>
-hipError_t cached_instance(const TextCachedArgs &a, const Launch &l)
+constexpr auto cached_kernel_of() -> void (*)(TextCachedArgs)
 {
-    constexpr const char *family[5] = {"", "rgba_", "srgb_", "rgba_load_", "srgb_load_"};
-    void (*kernel)(TextCachedArgs);
-    if constexpr (FAM == 0) kernel = text_cached_kernel<N>;
-    else if constexpr (FAM == 1) kernel = text_cached_rgba_kernel<N, BLEND>;
-    else if constexpr (FAM == 2) kernel = text_cached_srgb_kernel<N, BLEND>;
-    else if constexpr (FAM == 3) kernel = text_cached_rgba_load_kernel<N, BLEND>;
-    else kernel = text_cached_srgb_load_kernel<N, BLEND>;
-    if (l.name) {
-        if constexpr (FAM == 0) snprintf(l.name, l.name_cap, "fr::text_cached_kernel<%d>", N);
-        else snprintf(l.name, l.name_cap, "fr::text_cached_%skernel<%d, %d>", family[FAM], N, BLEND);
-    }
-    if (!l.n_tiles) return hipSuccess;
-    hipLaunchKernelGGL(kernel, dim3(l.n_tiles), dim3(64 * TEXT_WAVES), 0, l.stream, a);
-    return hipGetLastError();
-}
-
-template <int FAM, int BLEND>
-hipError_t cached_n(const TextCachedArgs &a, int n, const Launch &l)
-{
-    if (n == 4) return cached_instance<FAM, BLEND, 4>(a, l);
-    if (n == 2) return cached_instance<FAM, BLEND, 2>(a, l);
-    return cached_instance<FAM, BLEND, 1>(a, l);
-}
-
-template <int FAM>
-hipError_t cached_family(const TextCachedArgs &a, int n, int blend, const Launch &l)
-{
-    if (blend == 2) return cached_n<FAM, 2>(a, n, l);
-    return blend ? cached_n<FAM, 1>(a, n, l) : cached_n<FAM, 0>(a, n, l);
+    if constexpr (FAM == 0) return text_cached_kernel<N>;
+    else if constexpr (FAM == 1) return text_cached_rgba_kernel<N, BLEND>;
+    else if constexpr (FAM == 2) return text_cached_srgb_kernel<N, BLEND>;
+    else if constexpr (FAM == 3) return text_cached_rgba_load_kernel<N, BLEND>;
+    else return text_cached_srgb_load_kernel<N, BLEND>;
 }
 
 }  // namespace
 
-hipError_t launch_glyph_mask(const TextMaskArgs &a, int n, int fill, uint32_t n_tiles, hipStream_t stream, char *name, size_t name_cap)
+hipError_t launch_glyph_mask(const TextLaunch &e, const TextMaskArgs &a, hipStream_t stream)
 {
-    const Launch l{n_tiles, stream, name, name_cap};
-    if (n == 4) return fill ? mask_instance<4, 1>(a, l) : mask_instance<4, 0>(a, l);
-    if (n == 2) return fill ? mask_instance<2, 1>(a, l) : mask_instance<2, 0>(a, l);
-    return fill ? mask_instance<1, 1>(a, l) : mask_instance<1, 0>(a, l);
+    const int key[] = {e.n, e.fill};
+    return pick(key, [&](auto N, auto FILL) { return launch_tiles<TextMaskArgs>(glyph_mask_kernel<N, FILL>, e.grid, stream, a); },
+                Among<1, 2, 4>{}, Among<0, 1>{});
 }
 
-hipError_t launch_text_cached(const TextCachedArgs &a, int n, int rgba, int blend, int srgb, int load, uint32_t n_tiles,
-                              hipStream_t stream, char *name, size_t name_cap)
+hipError_t launch_text_cached(const TextLaunch &e, const TextCachedArgs &a, hipStream_t stream)
 {
-    const Launch l{n_tiles, stream, name, name_cap};
-    if (!rgba) return cached_n<0, 0>(a, n, l);
-    if (load) return srgb ? cached_family<4>(a, n, blend, l) : cached_family<3>(a, n, blend, l);
-    return srgb ? cached_family<2>(a, n, blend, l) : cached_family<1>(a, n, blend, l);
+    const int key[] = {e.colour, e.blend, e.n};
+    return pick(key, [&](auto FAM, auto BLEND, auto N) {
+        if constexpr (decltype(FAM)::value == 0 && decltype(BLEND)::value != 0) return hipErrorInvalidValue;
+        else return launch_tiles(cached_kernel_of<FAM, BLEND, N>(), e.grid, stream, a);
+    }, Among<0, 1, 2, 3, 4>{}, Among<0, 1, 2>{}, Among<1, 2, 4>{});
 }
 
 }  // namespace fr

@@ -4,14 +4,16 @@
 // four small pieces, overloaded on the form and written next to each other below: pen_of (how the fields are read),
 // resolve (the form's own checks, and what the build keeps of them: the affine inverse), cell_of (the cell in pixels about the pen) and
 // finish (the tail of the instance record).  The order of the checks fixes which error a caller sees: it is part of
-// the ABI's behaviour and host/text_plan_selftest.cpp pins it.  A second builder, text_cache_tables at the end, adds the
-// tables of an FR_TEXT_CACHE plan from the same pieces (host/text_cache_selftest.cpp).
+// the ABI's behaviour and host/text_plan_selftest.cpp pins it.  A second builder, text_cache_tables, adds the tables of an
+// FR_TEXT_CACHE plan from the same pieces (host/text_cache_selftest.cpp).  At the end: from a plan's flags and counts to the
+// launches of one render and their kernel names (text_plan_of, text_launches, text_launch_name).
 #include "fr_text_plan.hpp"
 #include "fr_srgb.hpp"
 
 #include <algorithm>
 #include <array>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <map>
 #include <type_traits>
@@ -331,5 +333,63 @@ int text_cache_tables(const TextPlanIn &in, const PLACE *places, const TextPlanT
 
 template int text_cache_tables(const TextPlanIn &, const fr_glyph_place *, const TextPlanTables<fr_glyph_place> &, TextCacheTables &);
 template int text_cache_tables(const TextPlanIn &, const fr_glyph_place_ex *, const TextPlanTables<fr_glyph_place_ex> &, TextCacheTables &);
+
+// ---- the launches of one render (fr_text_plan.hpp) --------------------------------------------------------------------
+template <class PLACE>
+TextPlan text_plan_of(const TextPlanIn &in, const fr_raster_params &params, const TextPlanTables<PLACE> &t, const TextCacheTables *cache)
+{
+    TextPlan p;
+    p.form = text_form_of((const PLACE *)nullptr);
+    p.rgba = in.rgba;
+    p.srgb = in.rgba && (in.flags & FR_TEXT_SRGB) != 0;
+    p.load = in.rgba && (in.flags & FR_TEXT_LOAD) != 0;
+    p.blend = t.blend;
+    p.fill = (in.flags & FR_FILL_CONSISTENT) ? 1 : 0;
+    p.samples = params.samples_per_axis;
+    p.n_tiles = (uint32_t)t.tiles.size(); p.n_insts = (uint32_t)t.insts.size(); p.n_glyphs = (uint32_t)t.glyphs.size();
+    if (cache) {
+        p.cached = true;
+        p.n_mcells = (uint32_t)cache->cells.size(); p.n_mtiles = (uint32_t)cache->tiles.size();
+    }
+    return p;
+}
+
+template TextPlan text_plan_of(const TextPlanIn &, const fr_raster_params &, const TextPlanTables<fr_glyph_place> &, const TextCacheTables *);
+template TextPlan text_plan_of(const TextPlanIn &, const fr_raster_params &, const TextPlanTables<fr_glyph_place_ex> &, const TextCacheTables *);
+template TextPlan text_plan_of(const TextPlanIn &, const fr_raster_params &, const TextPlanTables<fr_glyph_place_affine> &, const TextCacheTables *);
+
+// What a render launches and what fr_plan_describe prints are this one list.  The prepare and mask entries depend on their
+// own counts and the last entry on the tiles, yet a plan without tiles launches nothing at all: it has no surviving
+// instance (an instance meets at least one tile of its run, under FR_TEXT_LOAD too), hence no glyph to prepare and no mask
+// cell.  A plan with tiles and no instance (not FR_TEXT_LOAD) still launches its text kernel, which writes the clear value.
+void text_launches(const TextPlan &p, TextLaunchList &out)
+{
+    out.n = 0;
+    if (p.n_glyphs) out.l[out.n++] = TextLaunch{TL_PREPARE, p.form, 0, p.samples, p.fill, 0, p.n_glyphs, p.n_glyphs};
+    if (p.cached) out.l[out.n++] = TextLaunch{TL_MASK, p.form, 0, p.samples, p.fill, 0, p.n_mtiles, p.n_mcells};
+    if (!p.n_tiles) return;
+    const int colour = p.rgba ? 1 + (p.srgb ? 1 : 0) + (p.load ? 2 : 0) : 0;
+    out.l[out.n++] = TextLaunch{p.cached ? TL_CACHED : TL_TEXT, p.form, colour, p.samples, p.cached ? 0 : p.fill, p.rgba ? p.blend : 0,
+                                p.n_tiles, p.n_insts};
+}
+
+void text_launch_name(const TextLaunch &e, char *name, size_t cap)
+{
+    static const char *const form[3] = {"", "place_", "affine_"};
+    static const char *const colour[5] = {"", "rgba_", "srgb_", "rgba_load_", "srgb_load_"};
+    if (cap) name[0] = 0;
+    if (e.fill != 0 && e.fill != 1) return;
+    if (e.family == TL_PREPARE) { snprintf(name, cap, e.fill ? "fr::prepare_fill_kernel" : "fr::prepare_kernel"); return; }
+    if (e.n != 1 && e.n != 2 && e.n != 4) return;
+    if (e.family == TL_MASK) { snprintf(name, cap, "fr::glyph_mask_kernel<%d, %d>", e.n, e.fill); return; }
+    if (e.colour < 0 || e.colour > 4 || e.blend < 0 || e.blend > 2 || (e.colour == 0 && e.blend != 0)) return;
+    if (e.family == TL_CACHED) {
+        if (e.colour == 0) snprintf(name, cap, "fr::text_cached_kernel<%d>", e.n);
+        else snprintf(name, cap, "fr::text_cached_%skernel<%d, %d>", colour[e.colour], e.n, e.blend);
+    } else if (e.form <= TEXT_AFFINE) {
+        if (e.colour == 0) snprintf(name, cap, "fr::text_%skernel<%d, %d>", form[e.form], e.n, e.fill);
+        else snprintf(name, cap, "fr::text_%s%skernel<%d, %d, %d>", form[e.form], colour[e.colour], e.n, e.fill, e.blend);
+    }
+}
 
 }  // namespace fr

@@ -8,6 +8,10 @@
 // With the argument "over" it runs the FR_TEXT_OVER cases instead (tests/test_text_over_ref.py): each RGBA case with and
 // without the flag, one line each ending in "blend <0|1|2>", the hash taken over everything but the blend value, and
 // checks that the flag changes nothing but that value: 2 in place of 1, 0 where every colour is opaque.
+// With the argument "launches" it prints the launch list of a handful of plans (tests/test_text_launches.py): per form
+// "<case>/<form>/launches <n>" and per entry "<case>/<form>/launch<i> <family> <kernel name> grid <workgroups> count <what
+// fr_plan_describe prints>", then text_launch_name over a box of keys: one "name/..." line per key that has a kernel.
+// In every mode each plan's list is checked against what the render and the description rely on (launch_properties).
 #include "../csrc/fr_text_plan.hpp"
 
 #include <algorithm>
@@ -16,6 +20,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 static char g_err[512];
@@ -53,6 +58,7 @@ struct Case {
     std::vector<Place> places;
     std::vector<uint8_t> colours, clears;
     bool null_places = false, null_runs = false, no_boxes = false;
+    int samples = 4;                   // per axis (launches)
 };
 
 fr_text_run run(uint32_t first, uint32_t count, uint32_t w, uint32_t h, uint32_t x, uint32_t y, float s) { return fr_text_run{first, count, w, h, x, y, s}; }
@@ -148,10 +154,31 @@ void properties(const std::string &id, const Case &c, const fr::TextPlanTables<P
     check(used == t.glyphs, id, "glyph list not sorted and exact");
 }
 
+// what the render and fr_plan_describe rely on when they walk one list (text_launches, csrc/fr_text_plan.cpp): a plan without
+// tiles has no instance, no glyph and no mask cell, so its list is empty; any other list ends in the text kernel or the
+// composite over the plan's tiles; the entries come in stream order, each with a kernel name
+void launch_properties(const std::string &id, const fr::TextPlan &p, const fr::TextLaunchList &L)
+{
+    if (!p.n_tiles) check(!p.n_insts && !p.n_glyphs && !p.cached && !p.n_mcells && L.n == 0, id, "a plan without tiles has something to launch");
+    else check(L.n >= 1 && L.l[L.n - 1].family == (p.cached ? fr::TL_CACHED : fr::TL_TEXT) && L.l[L.n - 1].grid == p.n_tiles &&
+               L.l[L.n - 1].count == p.n_insts, id, "the list does not end in the plan's text kernel over its tiles");
+    check(L.n == (p.n_glyphs ? 1u : 0u) + (p.cached ? 1u : 0u) + (p.n_tiles ? 1u : 0u), id, "launch count");
+    check(!p.n_insts == !p.n_glyphs && (!p.cached || (p.n_mcells && p.n_mtiles >= p.n_mcells && p.n_glyphs)), id, "instances, glyphs and mask cells disagree");
+    for (uint32_t i = 0; i < L.n; ++i) {
+        char name[96];
+        fr::text_launch_name(L.l[i], name, sizeof name);
+        check(name[0] != 0 && L.l[i].grid != 0, id, "a launch without a kernel or without workgroups");
+        check(i == 0 || L.l[i - 1].family < L.l[i].family, id, "launches out of stream order");
+    }
+}
+
+const char *const FAMILY[4] = {"prepare", "mask", "text", "cached"};
+enum Mode { TABLES, OVER, LAUNCHES };
+
 struct Outcome { bool ok; uint64_t hash; int blend; };   // (over) of one form of a case: the hash leaves the blend value out
 
 template <class PLACE>
-Outcome run_form(const Case &c, const char *form, bool over = false)
+Outcome run_form(const Case &c, const char *form, Mode mode = TABLES)
 {
     const std::string id = std::string(c.name) + "/" + form;
     std::vector<PLACE> places;
@@ -175,10 +202,29 @@ Outcome run_form(const Case &c, const char *form, bool over = false)
         return Outcome{false, 0, 0};
     }
     properties(id, c, t);
+    // the launches: as fr_api.hip makes them, FR_TEXT_CACHE tables included where the form has them and some cell exists
+    fr::TextCacheTables cache;
+    if constexpr (!std::is_same<PLACE, fr_glyph_place_affine>::value) {
+        if (c.flags & FR_TEXT_CACHE) check(fr::text_cache_tables(in, places.data(), t, cache) == FR_OK, id, "text_cache_tables failed");
+    }
+    const fr_raster_params params{FR_COVERAGE_U8, c.samples, FR_SAMPLE_CENTER, 0};
+    const fr::TextPlan plan = fr::text_plan_of(in, params, t, cache.cells.empty() ? nullptr : &cache);
+    fr::TextLaunchList L;
+    fr::text_launches(plan, L);
+    launch_properties(id, plan, L);
+    if (mode == LAUNCHES) {
+        printf("%s/launches %u\n", id.c_str(), L.n);
+        for (uint32_t i = 0; i < L.n; ++i) {
+            char name[96];
+            fr::text_launch_name(L.l[i], name, sizeof name);
+            printf("%s/launch%u %s %s grid %u count %u\n", id.c_str(), i, FAMILY[L.l[i].family], name, L.l[i].grid, L.l[i].count);
+        }
+        return Outcome{true, 0, t.blend};
+    }
     Fnv f;
     f.vec(t.runs); f.vec(t.tiles); f.vec(t.insts); f.vec(t.list); f.vec(t.glyphs);
     f.u64(t.pixels); f.u64(t.need_cols); f.u64(t.need_rows);
-    if (over) {
+    if (mode == OVER) {
         printf("%s %016llx insts %zu blend %d\n", id.c_str(), (unsigned long long)f.h, t.insts.size(), t.blend);
         return Outcome{true, f.h, t.blend};
     }
@@ -192,23 +238,45 @@ Outcome run_form(const Case &c, const char *form, bool over = false)
 template <class PLACE>
 void run_over_form(const Case &c, const char *form)
 {
-    const Outcome plain = run_form<PLACE>(c, form, true);
+    const Outcome plain = run_form<PLACE>(c, form, OVER);
     Case o = c;
     const std::string name = std::string(c.name) + "_over";
     o.name = name.c_str();
     o.flags |= FR_TEXT_OVER;
-    const Outcome with = run_form<PLACE>(o, form, true);
+    const Outcome with = run_form<PLACE>(o, form, OVER);
     const std::string id = name + "/" + form;
     check(plain.ok && with.ok, id, "an FR_TEXT_OVER case failed to build");
     check(plain.hash == with.hash, id, "FR_TEXT_OVER changed a table");
     check(with.blend == (plain.blend ? 2 : 0), id, "blend is not 2 for translucent colours and 0 for opaque ones under FR_TEXT_OVER");
 }
 
-void run_case(const Case &c)
+void run_case(const Case &c, Mode mode = TABLES)
 {
-    if (c.forms & PLAIN) run_form<fr_glyph_place>(c, "plain");
-    if (c.forms & EX) run_form<fr_glyph_place_ex>(c, "ex");
-    if (c.forms & AFFINE) run_form<fr_glyph_place_affine>(c, "affine");
+    if (c.forms & PLAIN) run_form<fr_glyph_place>(c, "plain", mode);
+    if (c.forms & EX) run_form<fr_glyph_place_ex>(c, "ex", mode);
+    if (c.forms & AFFINE) run_form<fr_glyph_place_affine>(c, "affine", mode);
+}
+
+// (launches) text_launch_name over a box of keys around the valid ones: a line per key that gets a name, then the counts.
+// The composites have neither a form nor FILL and the mask kernels no form, colour or BLEND: those stay 0 in their keys
+void sweep_names()
+{
+    unsigned keys = 0, named = 0;
+    for (int family = fr::TL_MASK; family <= fr::TL_CACHED; ++family)
+        for (int form = 0; form <= (family == fr::TL_TEXT ? 3 : 0); ++form)
+            for (int colour = (family == fr::TL_MASK ? 0 : -1); colour <= (family == fr::TL_MASK ? 0 : 5); ++colour)
+                for (int n = 0; n <= 5; ++n)
+                    for (int fill = (family == fr::TL_CACHED ? 0 : -1); fill <= (family == fr::TL_CACHED ? 0 : 2); ++fill)
+                        for (int blend = (family == fr::TL_MASK ? 0 : -1); blend <= (family == fr::TL_MASK ? 0 : 3); ++blend) {
+                            const fr::TextLaunch e{(fr::TextFamily)family, (fr::TextForm)form, colour, n, fill, blend, 1u, 1u};
+                            char name[96];
+                            fr::text_launch_name(e, name, sizeof name);
+                            ++keys;
+                            if (!name[0]) continue;
+                            ++named;
+                            printf("name/%s/form%d/colour%d/n%d/fill%d/blend%d %s\n", FAMILY[family], form, colour, n, fill, blend, name);
+                        }
+    printf("name/swept keys %u named %u\n", keys, named);
 }
 
 std::vector<uint8_t> colours(size_t n, uint8_t alpha_of_second)
@@ -225,7 +293,7 @@ std::vector<uint8_t> colours(size_t n, uint8_t alpha_of_second)
 
 int main(int argc, char **argv)
 {
-    const bool over = argc > 1 && !strcmp(argv[1], "over");
+    const bool over = argc > 1 && !strcmp(argv[1], "over"), launches = argc > 1 && !strcmp(argv[1], "launches");
     const float S = 0.5f;
     const std::vector<Place> three = {at(0, 5 * 64, 20 * 64), at(1, 20 * 64, 25 * 64), at(2, 10 * 64, 22 * 64)};
     auto R = [&](uint32_t count) { return std::vector<fr_text_run>{run(0, count, 40, 30, 3, 5, S)}; };   // one run of `count` placements
@@ -254,6 +322,33 @@ int main(int argc, char **argv)
             if (c.forms & EX) run_over_form<fr_glyph_place_ex>(c, "ex");
             if (c.forms & AFFINE) run_over_form<fr_glyph_place_affine>(c, "affine");
         }
+        return g_failed;
+    }
+    if (launches) {
+        // cases of the other two lists with the flags and sample counts that choose an instance, and the three plans whose
+        // lists are short: all placements clipped away with and without FR_TEXT_LOAD, and no run at all
+        const std::vector<Place> away = {at(0, 1000 * 64, 20 * 64), at(2, 10 * 64, -400 * 64)};
+        add("coverage", ALL, one, three);
+        add("coverage_fill_n1", ALL, one, three).flags = FR_FILL_CONSISTENT;
+        cases.back().samples = 1;
+        add("coverage_cached", PLAIN | EX, one, three).flags = FR_TEXT_CACHE;
+        rgba(add("rgba_translucent_over_n2", ALL, one, three), FR_TEXT_OVER | FR_FILL_CONSISTENT, 128);
+        cases.back().samples = 2;
+        rgba(add("rgba_srgb_bgra", ALL, one, three), FR_TEXT_SRGB | FR_TEXT_BGRA, 255);
+        rgba(add("rgba_load", ALL, {run(0, 3, 200, 40, 0, 0, S)}, three), FR_TEXT_LOAD, 255, false);
+        rgba(add("rgba_load_srgb_translucent_cached", PLAIN | EX, {run(0, 3, 200, 40, 7, 9, S)}, three), FR_TEXT_LOAD | FR_TEXT_SRGB | FR_TEXT_CACHE | FR_FILL_CONSISTENT, 3, false);
+        rgba(add("two_runs_cached", PLAIN | EX, {run(0, 2, 40, 30, 0, 0, S), run(2, 3, 70, 20, 40, 0, S)},
+                 {at(0, 5 * 64, 20 * 64), at(1, 20 * 64, 25 * 64), at(2, 10 * 64, 12 * 64), at(4, 30 * 64, 18 * 64), at(1, 60 * 64, 15 * 64)}),
+             FR_TEXT_CACHE, 255);
+        rgba(add("affine_general", AFFINE, {run(0, 3, 130, 50, 0, 0, S)},
+                 {mat(4, 20 * 64 + 3, 45 * 64 + 60, 0.4f, 0.3f, -0.2f, 0.6f), mat(2, 90 * 64, 30 * 64, -0.7f, 0.45f, 0.15f, 0.9f), mat(1, 5 * 64, 5 * 64, 3.0f, -1.0f, 2.0f, 0.125f)}),
+             FR_TEXT_SRGB, 200);
+        rgba(add("load_all_clipped_away", ALL, R(2), away), FR_TEXT_LOAD, 128, false);
+        add("tiles_but_no_instance", ALL, R(2), away);
+        add("tiles_but_no_instance_cached", PLAIN | EX, R(2), away).flags = FR_TEXT_CACHE;
+        add("no_runs", ALL, {}, three);
+        for (const Case &c : cases) run_case(c, LAUNCHES);
+        sweep_names();
         return g_failed;
     }
     add("coverage", ALL, one, three);
