@@ -3,7 +3,7 @@
 // fr_render.hip (and therefore as the reference's glyphWindingAt per sample,
 // /root/reference/src/tools/render_glyph.zig:35-73, non-zero fill :29, box filter = the MSAA average
 // resolve of VulkanContext.zig:307-313); a plan takes this kernel for every job it fits (any width and height up to
-// 2048 sample rows, glyphs of <= 768 segments: fr_api.hip, fast_class) and the general kernel for the rest.
+// 2048 sample rows, glyphs of <= 768 segments: fast_class, fr_raster_plan.cpp) and the general kernel for the rest.
 // Which instance a launch gets and how it is named is settled on the host, without HIP, by raster_launches and
 // raster_launch_name (fr_raster_plan.cpp); launch_cov4 at the end of this file only looks the instance up.
 //

@@ -80,7 +80,7 @@ __device__ __forceinline__ float sqrt_fast(float x)
 }
 // x / scale for a job's `scale`, which is the same for a whole workgroup.  When scale = +-2^k the quotient is x with its
 // exponent moved by k: x * 2^-k is that very binary32, bit for bit, as long as neither 2^-k nor the product leaves the
-// normal range.  Taken only for 2^-20 <= |scale| <= 2^20 — the range fr_plan_create accepts (fr_api.hip) — and the
+// normal range.  Taken only for 2^-20 <= |scale| <= 2^20 — the range fr_plan_create accepts (check_job, fr_host_rules.cpp) — and the
 // dividends are 0 or sample coordinates, multiples of 1/8 with 1/8 <= |x| <= 2^22 + 1 (fr_plan_create bounds the cell), so
 // the product lies in [2^-23, 2^43): normal.  Zero keeps the sign the division gives it (sign x XOR sign scale).  The
 // decision is made from the bits of `scale` with scalar instructions (mantissa field 0, exponent field in 107 .. 147); the
@@ -119,7 +119,7 @@ struct Job {   // == fr_job (include/fr_raster.h)
     float scale;
 };
 
-// kernel arguments of render_kernel (fr_render.hip), filled by fr_api.hip
+// kernel arguments of render_kernel (fr_render.hip), filled by fr_api_plan.hip
 struct RenderArgs {
     const Job *jobs;
     const uint32_t *glyph_seg_start;   // record slice of glyph g starts at 2*glyph_seg_start[g]

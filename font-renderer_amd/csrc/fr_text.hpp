@@ -1,4 +1,4 @@
-// fr_text.hpp — what a text kernel reads (the tables of fr_text_tables.hpp, on the device) and how fr_api.hip launches it
+// fr_text.hpp — what a text kernel reads (the tables of fr_text_tables.hpp, on the device) and how fr_api_plan.hip launches it
 #pragma once
 #include "fr_device.hpp"
 #include "fr_text_plan.hpp"

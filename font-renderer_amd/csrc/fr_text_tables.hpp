@@ -1,4 +1,4 @@
-// fr_text_tables.hpp — the plain tables of a text plan: fr_text_plan.cpp builds them on the host (no HIP), fr_api.hip
+// fr_text_tables.hpp — the plain tables of a text plan: fr_text_plan.cpp builds them on the host (no HIP), fr_api_plan.hip
 // uploads them, the text kernels of fr_text.hip and fr_text_affine.hip read them (fr_text.hpp).  Needs only <cstdint>.
 #pragma once
 #include <cstdint>

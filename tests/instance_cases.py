@@ -172,7 +172,7 @@ def expected_instances():
     return names
 
 
-# instances no plan of the public API can reach: (name, the line of fr_api.hip that proves it).  None found.
+# instances no plan of the public API can reach: (name, the line of the C ABI units, csrc/fr_api_*.hip, that proves it).  None found.
 UNREACHABLE = []
 
 

@@ -298,11 +298,49 @@ def test_whole_font_at_renderglyph_sizes_properties(ctx, oracle):
     dgs.close()
 
 
+def _graph_steps(ctx, plan, dt, rows, W):
+    """`plan` under option "graph": the capture and first launch into A, two replays, another destination B, A again with
+    another pitch, and a render after a rejected fr_ctx_set_option — each == what the plain launches write.  Leaves
+    "graph" on; -> the plain launches' image"""
+    import torch
+
+    def fresh(pitch):
+        return torch.full((rows * pitch,), 0x5b, dtype=dt, device="cuda")
+    want, want_wide = fresh(W), fresh(W + 3)
+    ctx.set_option("graph", 0)
+    plan.render(want.data_ptr(), W, rows); plan.render(want_wide.data_ptr(), W + 3, rows); ctx.sync()
+    assert (want != 0x5b).any()
+    ctx.set_option("graph", 1)
+    a, b = fresh(W + 3), fresh(W)
+    n = rows * W
+    torch.cuda.synchronize()
+    plan.render(a.data_ptr(), W, rows); ctx.sync()                           # capture + first launch
+    assert torch.equal(a[:n], want)
+    a.fill_(0x5b); torch.cuda.synchronize()
+    plan.render(a.data_ptr(), W, rows); plan.render(a.data_ptr(), W, rows); ctx.sync()     # replays
+    assert torch.equal(a[:n], want)
+    plan.render(b.data_ptr(), W, rows); ctx.sync()                           # another destination: captured again
+    assert torch.equal(b, want)
+    a.fill_(0x5b); torch.cuda.synchronize()
+    plan.render(a.data_ptr(), W + 3, rows); ctx.sync()                       # the first one with another pitch: captured again
+    assert torch.equal(a, want_wide)
+    with pytest.raises(fr.FrError):
+        ctx.set_option("kmax", 0)                                            # rejected: nothing changes
+    a.fill_(0x5b); torch.cuda.synchronize()
+    plan.render(a.data_ptr(), W + 3, rows); ctx.sync()
+    assert torch.equal(a, want_wide)
+    return want.view(rows, W)
+
+
 def test_graph_replay_equals_plain_launches(ctx, oracle, ascii_set):
     """option "graph": a plan's launches (several classes, with and without the fork onto the second stream, the SDF's
     three kernels) captured into a hipGraph at the first render to a destination and replayed afterwards — every replay,
-    a second destination (re-capture) and a render after an option change == the plain launches, byte for byte."""
+    a second destination and another pitch (re-captures), a render after a rejected option and one after an option change
+    == the plain launches, byte for byte.  Then the same steps on the smallest plan that forks (one fast-kernel job and
+    one general-kernel job under overlap = 2) and on a three-placement text plan."""
     import torch
+    import text_instance_cases as T
+    from font_renderer_amd.synth import synth_glyph
     gs = ascii_set.gs
     W = 1021
     parts, y = [], 0
@@ -320,25 +358,27 @@ def test_graph_replay_equals_plain_launches(ctx, oracle, ascii_set):
             ctx.set_option("overlap", overlap)
             plan = fr.Plan(dgs, jobs, mode, n, fr.FR_SAMPLE_CENTER if center else fr.FR_SAMPLE_CORNER)
             assert plan.describe().count("fr::") >= 2, plan.describe()          # several launches per render
-            want = torch.full((y, W), 0x5b, dtype=dt, device="cuda")
-            ctx.set_option("graph", 0)
-            plan.render(want.data_ptr(), W, y); ctx.sync()
-            ctx.set_option("graph", 1)
-            a = torch.full((y, W), 0x5b, dtype=dt, device="cuda")
-            b = torch.full((y, W), 0x5b, dtype=dt, device="cuda")
-            torch.cuda.synchronize()
-            plan.render(a.data_ptr(), W, y); ctx.sync()                          # capture + first launch
-            assert torch.equal(a, want), mode
-            a.fill_(0x5b); torch.cuda.synchronize()
-            plan.render(a.data_ptr(), W, y); plan.render(a.data_ptr(), W, y); ctx.sync()     # replays
-            assert torch.equal(a, want), mode
-            plan.render(b.data_ptr(), W, y); ctx.sync()                          # another destination: captured again
-            assert torch.equal(b, want), mode
+            want = _graph_steps(ctx, plan, dt, y, W)
             ctx.set_option("overlap", 0)                                         # an option changed: captured again
-            a.fill_(0x5b); torch.cuda.synchronize()
+            a = torch.full((y, W), 0x5b, dtype=dt, device="cuda")
+            torch.cuda.synchronize()
             ms = plan.render_timed(a.data_ptr(), W, y)
             assert ms > 0 and torch.equal(a, want), mode
             plan.close()
+        dgs.close()
+        # one 64 x 64 cell on cov4_kernel beside one of a glyph of more than 768 segments on the general kernel
+        small = [Glyph(Box(*(int(v) for v in box)), [Contour(c) for c in cs]) for cs, box in (synth_glyph(0, 64), synth_glyph(1, 800))]
+        dgs = fr.DeviceGlyphSet(ctx, GlyphSet(small))
+        ctx.set_option("overlap", 2)
+        plan = fr.Plan(dgs, rg.make_jobs([(g, 0, 64, 64, 64, 5 + 70 * g, 3, 64.0 / 2048.0) for g in range(2)]), fr.FR_COVERAGE_U8, 4, fr.FR_SAMPLE_CENTER)
+        assert plan.stats() == {"jobs_cov4": 1, "jobs_general": 1}, plan.describe()
+        _graph_steps(ctx, plan, torch.uint8, 70, 141)
+        plan.close()
+        dgs.close()
+        dgs = fr.DeviceGlyphSet(ctx, T.glyph_set(ascii_set))
+        plan = fr.TextPlan(dgs, T.places_of(0), T.runs(), fr.FR_COVERAGE_U8, 4, fr.FR_SAMPLE_CORNER)
+        _graph_steps(ctx, plan, torch.uint8, T.SHAPE[0], T.SHAPE[1])
+        plan.close()
     finally:
         ctx.set_option("graph", 0)
         ctx.set_option("overlap", 1)

@@ -51,7 +51,7 @@ def test_one_case_per_instance():
 
 
 def test_unreachable_list():
-    """instances proven unreachable through the public API, each with the line of fr_api.hip that proves it: none"""
+    """instances proven unreachable through the public API, each with the line of the C ABI units (csrc/fr_api_*.hip) that proves it: none"""
     assert IC.UNREACHABLE == []
 
 
