@@ -38,6 +38,8 @@ pub const FR_TEXT_LOAD: u32 = 32;
 pub const FR_TEXT_CACHE: u32 = 128;
 /// flag of the RGBA text plan entry points (fr_raster.h): source-over alpha, a premultiplied output
 pub const FR_TEXT_OVER: u32 = 256;
+/// fr_layer_over's own flag space (fr_raster.h): composite in linear light
+pub const FR_LAYER_SRGB: u32 = 1;
 
 pub const RasterParams = extern struct {
     mode: i32,
@@ -83,6 +85,17 @@ pub const GlyphPlaceAffine = extern struct {
     pen_x64: i32,
     pen_y64: i32,
     m: [4]f32,
+};
+
+/// one rectangle of a layer and where it lands (fr_layer_over)
+pub const LayerBlit = extern struct {
+    src_x: u32,
+    src_y: u32,
+    w: u32,
+    h: u32,
+    dst_x: i32,
+    dst_y: i32,
+    opacity: u32,
 };
 
 pub const TextRun = extern struct {
@@ -167,6 +180,10 @@ pub extern "c" fn fr_srgb_decode(in: [*]const u8, n: usize, out: [*]u16) c_int;
 pub extern "c" fn fr_srgb_encode(in: [*]const u16, n: usize, out: [*]u8) c_int;
 /// premultiplied -> straight alpha in place (the output of FR_TEXT_OVER plans); srgb != 0: in linear light
 pub extern "c" fn fr_rgba_unpremultiply(rgba: [*]u8, n_pixels: usize, srgb: c_int) c_int;
+/// rectangles of a premultiplied layer over a premultiplied image, both in device memory, at whole-pixel offsets and an opacity
+pub extern "c" fn fr_layer_over(ctx: *Ctx, src_dev: *const anyopaque, src_stride_px: usize, src_rows: usize, dst_dev: *anyopaque, dst_stride_px: usize, dst_rows: usize, blits: ?[*]const LayerBlit, n_blits: u32, flags: u32) c_int;
+/// fr_rgba_unpremultiply on the device, over a w x h window of an image in rows of stride_px pixels
+pub extern "c" fn fr_layer_unpremultiply(ctx: *Ctx, rgba_dev: *anyopaque, stride_px: usize, w: u32, h: u32, srgb: c_int) c_int;
 // ---- self-tests of the two arithmetic shortcuts (device-side, exhaustive)
 pub extern "c" fn fr_selftest_division(d_lo: u32, d_hi: u32, mismatches: *u64, bad_divisor: ?*u32, bad_x_bits: ?*u32) c_int;
 pub extern "c" fn fr_selftest_sqrt(mismatches: *u64, bad_x_bits: ?*u32) c_int;

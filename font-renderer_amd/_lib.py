@@ -13,6 +13,7 @@ FR_TEXT_SRGB, FR_TEXT_BGRA = 8, 4  # flags of fr_text_plan_create_rgba only: lin
 FR_TEXT_LOAD = 32                  # fr_text_plan_create_rgba only: draw over the pixels already in the output
 FR_TEXT_CACHE = 128                # the upright and _ex text plans: each distinct glyph image made once per render, same bytes
 FR_TEXT_OVER = 256                 # the RGBA text plans: source-over alpha (a premultiplied output) instead of alpha replaced
+FR_LAYER_SRGB = 1                  # fr_layer_over's own flag space: composite in linear light
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -55,6 +56,11 @@ class GlyphPlaceAffine(C.Structure):  # == fr_glyph_place_affine
 class TextRun(C.Structure):      # == fr_text_run
     _fields_ = [("first", C.c_uint32), ("count", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32),
                 ("out_x", C.c_uint32), ("out_y", C.c_uint32), ("scale", C.c_float)]
+
+
+class LayerBlit(C.Structure):    # == fr_layer_blit
+    _fields_ = [("src_x", C.c_uint32), ("src_y", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32),
+                ("dst_x", C.c_int32), ("dst_y", C.c_int32), ("opacity", C.c_uint32)]
 
 
 # every symbol include/fr_raster.h declares: (name, restype, argtypes)
@@ -126,6 +132,8 @@ SYMBOLS = [
     ("fr_srgb_decode", C.c_int, [_P, C.c_size_t, _P]),
     ("fr_srgb_encode", C.c_int, [_P, C.c_size_t, _P]),
     ("fr_rgba_unpremultiply", C.c_int, [_P, C.c_size_t, C.c_int]),
+    ("fr_layer_over", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, _P, C.c_uint32, C.c_uint32]),
+    ("fr_layer_unpremultiply", C.c_int, [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.c_int]),
     ("fr_selftest_sqrt", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     ("fr_selftest_division", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("fr_selftest_row_cuts", C.c_int, [_P, _P, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),

@@ -84,6 +84,9 @@ void fr_ctx_destroy(fr_ctx *ctx)
     (void)hipStreamSynchronize(ctx->stream);
     ctx->arena.reset();
     if (ctx->stage) (void)hipHostFree(ctx->stage);
+    ctx->layer_tab.reset();
+    if (ctx->layer_stage) (void)hipHostFree(ctx->layer_stage);
+    if (ctx->layer_ev) (void)hipEventDestroy(ctx->layer_ev);
     if (ctx->aux) { (void)hipStreamSynchronize(ctx->aux); (void)hipStreamDestroy(ctx->aux); }
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
     if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);

@@ -1,0 +1,66 @@
+// fr_layer_plan.hpp — the host side of fr_layer_over and fr_layer_unpremultiply (include/fr_raster.h; DESIGN.md sections
+// 4.8 and 5): the argument checks, the clipping of the blits, their overlap check and the tile table the kernel walks.
+// Plain C++, no HIP: device pointers come in as integers.  host/layer_selftest.cpp runs all of it on the CPU.
+#pragma once
+#include "../../include/fr_raster.h"
+
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+namespace fr {
+
+// One workgroup of LAYER_WAVES waves takes one tile: a lane owns LAYER_LANE_PX consecutive pixels of a row (16 bytes), a
+// wave a row of 64 such groups, and walks LAYER_TILE_H / LAYER_WAVES rows.
+constexpr uint32_t LAYER_LANE_PX = 4, LAYER_TILE_W = 64 * LAYER_LANE_PX, LAYER_TILE_H = 16, LAYER_WAVES = 4;
+// a call may list at most this many tiles (2^34 pixels): FR_E_UNSUPPORTED beyond
+constexpr uint64_t LAYER_MAX_TILES = (uint64_t)1 << 22;
+// rows of either image beyond this: FR_E_UNSUPPORTED (a tile keeps its rows in 32 bits)
+constexpr size_t LAYER_MAX_ROWS = 0x7fffffffu;
+
+// LayerTile::ov above the opacity: the lane groups that lie wholly inside [x0, x1) move as one 16-byte access
+constexpr uint32_t LAYER_DST_VEC = 0x100u, LAYER_SRC_VEC = 0x200u;
+
+// A tile of one clipped blit, in destination pixels.  x is a multiple of LAYER_LANE_PX at or below the rectangle's left
+// edge, so that lane l's group starts at column x + 4 l; the pixels of the tile are [max(x, x0), min(x + LAYER_TILE_W, x1))
+// by [y, min(y + LAYER_TILE_H, y1)).  (sx, sy): the layer pixel that lands on (x, y); sx is below zero by up to three when
+// x < x0 and the blit reads the layer from column 0 (those pixels are outside the tile).
+struct LayerTile {
+    uint32_t x, y;
+    uint32_t x0, x1, y1;
+    int32_t sx;
+    uint32_t sy;
+    uint32_t ov;               // opacity | LAYER_DST_VEC | LAYER_SRC_VEC
+};
+static_assert(sizeof(LayerTile) == 32, "LayerTile is two dwordx4");
+
+struct LayerIn {
+    uintptr_t src, dst;        // the two device pointers
+    size_t src_stride, src_rows, dst_stride, dst_rows;
+    const fr_layer_blit *blits;
+    uint32_t n_blits;
+    uint32_t flags;
+};
+
+// a blit clipped to the destination: [x0, x1) x [y0, y1) there (empty: x0 == x1 == 0), from (sx, sy) of the layer
+struct LayerClip {
+    uint32_t x0, y0, x1, y1;
+    uint32_t sx, sy;
+};
+
+struct LayerTables {
+    std::vector<LayerClip> clips;      // one per blit, in the caller's order
+    std::vector<LayerTile> tiles;      // blit by blit, rows of tiles top to bottom, left to right; none for opacity 0
+    bool opacity = false;              // some blit that has tiles has an opacity below 255: the OPACITY = 1 instance
+    uint64_t pixels = 0;               // sum of the clipped rectangles' areas
+};
+
+// The checks of fr_layer_over in the order the header lists them, then clipping, the overlap check (the sweep down the rows
+// that text runs use) and the tiles.  FR_OK, or the code with its message left through fr::set_error; `out` is only
+// meaningful after FR_OK.
+int layer_tables(const LayerIn &in, LayerTables &out);
+
+// the checks of fr_layer_unpremultiply
+int layer_window_check(uintptr_t rgba, size_t stride_px, uint32_t w, uint32_t h);
+
+}  // namespace fr

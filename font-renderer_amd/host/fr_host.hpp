@@ -189,6 +189,25 @@ inline Image::Gray renderAtlas(Context &ctx, const std::vector<Glyph> &glyphs, F
 // source-over alpha, which unpremultiply() below turns into straight alpha once they are back on the host.
 inline void unpremultiply(std::vector<uint8_t> &rgba, bool srgb = false) { check(fr_rgba_unpremultiply(rgba.data(), rgba.size() / 4, srgb ? 1 : 0)); }
 
+// fr_layer_over: rectangles of a finished premultiplied layer (a FR_TEXT_OVER render over a (0, 0, 0, 0) clear colour) over
+// a premultiplied image, both in DEVICE memory the host owns, 4 bytes per pixel with alpha last; strides and rows count
+// pixels.  Asynchronous on the context's stream; `blits` may be reused at once.  srgb: FR_LAYER_SRGB (both images are
+// premultiplied in linear light).  A viewer renders the layer once and calls this per frame with the frame's offset.
+struct DeviceImage {
+    void *pixels;
+    size_t stride_px, rows;
+};
+inline void layer_over(Context &ctx, const DeviceImage &layer, const DeviceImage &image, const std::vector<fr_layer_blit> &blits, bool srgb = false)
+{
+    check(fr_layer_over(ctx.get(), layer.pixels, layer.stride_px, layer.rows, image.pixels, image.stride_px, image.rows, blits.data(),
+                        (uint32_t)blits.size(), srgb ? FR_LAYER_SRGB : 0u));
+}
+// fr_layer_unpremultiply: unpremultiply() above on the device, over the w x h window at the image's first pixel
+inline void layer_unpremultiply(Context &ctx, const DeviceImage &image, uint32_t w, uint32_t h, bool srgb = false)
+{
+    check(fr_layer_unpremultiply(ctx.get(), image.pixels, image.stride_px, w, h, srgb ? 1 : 0));
+}
+
 class PlacedText {
 public:
     PlacedText(Context &ctx, const std::vector<Glyph> &glyphs, const std::vector<fr_glyph_place_ex> &places,

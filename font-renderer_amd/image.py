@@ -91,17 +91,56 @@ class RGBA:                     # an RGBA text plan's image (fr_text_plan_create
     def init(width: int, height: int) -> "RGBA":
         return RGBA(width, height, np.zeros((width * height, 4), np.uint8))
 
-    def unpremultiply(self, srgb: bool = False) -> "RGBA":
+    def unpremultiply(self, srgb: bool = False, *, device: bool = False, ctx=None) -> "RGBA":
         """fr_rgba_unpremultiply, in place: the premultiplied image of an over=True render (FR_TEXT_OVER) as straight
         alpha, which the RGBA QOI writer and image files expect.  srgb: the image was rendered with srgb=True, so the
-        division is in linear light.  A pixel of alpha 0 becomes (0, 0, 0, 0); one of alpha 255 is unchanged.  Returns self."""
+        division is in linear light.  A pixel of alpha 0 becomes (0, 0, 0, 0); one of alpha 255 is unchanged.  Returns self.
+        device: the same bytes through fr_layer_unpremultiply on the GPU (the image is uploaded and copied back)."""
         from . import _lib as L
         if not isinstance(self.data, np.ndarray) or self.data.dtype != np.uint8 or self.data.ndim != 2 or self.data.shape[1] != 4:
             raise ValueError("RGBA.unpremultiply: data must be an (n, 4) uint8 array")
         buf = np.ascontiguousarray(self.data)
+        if device:
+            import torch
+
+            from . import render_glyph as rg
+            if buf.shape[0] != self.width * self.height:
+                raise ValueError(f"RGBA.unpremultiply: {buf.shape[0]} pixels for {self.width} x {self.height}")
+            ctx = ctx or rg.default_context()
+            dev = torch.from_numpy(buf).to(f"cuda:{ctx.device}")
+            torch.cuda.synchronize(ctx.device)
+            rg.layer_unpremultiply(ctx, dev.data_ptr(), self.width, self.width, self.height, srgb)
+            ctx.sync()
+            self.data[:] = dev.cpu().numpy()
+            return self
         L.check(L.load_library().fr_rgba_unpremultiply(L.ptr(buf), buf.shape[0], 1 if srgb else 0))
         if buf is not self.data:
             self.data[:] = buf
+        return self
+
+    def over(self, layer: "RGBA", x: int = 0, y: int = 0, opacity: int = 255, srgb: bool = False, ctx=None) -> "RGBA":
+        """fr_layer_over, in place: the premultiplied `layer` (an over=True render over a transparent background)
+        composited over this premultiplied image with its top-left pixel at (x, y), whole pixels, clipped at the image's
+        edges, at `opacity` in 0 .. 255.  srgb: both images are premultiplied in linear light (rendered with srgb=True).
+        Both images are uploaded, composited on the device and this one copied back, as draw_text_rgba does.  Returns self."""
+        import torch
+
+        from . import render_glyph as rg
+        for im, what in ((self, "image"), (layer, "layer")):
+            if (not isinstance(im.data, np.ndarray) or im.data.dtype != np.uint8 or im.data.shape != (im.width * im.height, 4)):
+                raise ValueError(f"RGBA.over: {what}.data must be a ({im.width * im.height}, 4) uint8 array")
+        if not 0 <= int(opacity) <= 255:
+            raise ValueError(f"opacity {opacity!r}: expected 0 .. 255")
+        if self.width == 0 or self.height == 0 or layer.width == 0 or layer.height == 0:
+            return self
+        ctx = ctx or rg.default_context()
+        dst = torch.from_numpy(np.ascontiguousarray(self.data)).to(f"cuda:{ctx.device}")
+        src = torch.from_numpy(np.ascontiguousarray(layer.data)).to(f"cuda:{ctx.device}")
+        torch.cuda.synchronize(ctx.device)
+        blits = rg.make_blits([(0, 0, layer.width, layer.height, int(x), int(y), int(opacity))])
+        rg.layer_over(ctx, src.data_ptr(), layer.width, layer.height, dst.data_ptr(), self.width, self.height, blits, srgb)
+        ctx.sync()
+        self.data[:] = dst.cpu().numpy()
         return self
 
     def getWidth(self) -> int:

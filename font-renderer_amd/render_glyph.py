@@ -261,6 +261,32 @@ class TextPlanRGBA(Plan):
         self.n_places, self.n_runs = len(places), len(runs)
 
 
+BLIT_DTYPE = np.dtype([("src_x", "<u4"), ("src_y", "<u4"), ("w", "<u4"), ("h", "<u4"), ("dst_x", "<i4"), ("dst_y", "<i4"),
+                       ("opacity", "<u4")])
+
+
+def make_blits(rows: Sequence) -> np.ndarray:
+    """rows of (src_x, src_y, w, h, dst_x, dst_y, opacity) -> fr_layer_blit array"""
+    return np.array([tuple(r) for r in rows], BLIT_DTYPE)
+
+
+def layer_over(ctx: Context, src_ptr: int, src_stride_px: int, src_rows: int, dst_ptr: int, dst_stride_px: int, dst_rows: int,
+               blits, srgb: bool = False, flags: int = 0) -> None:
+    """fr_layer_over: rectangles of the premultiplied layer at device address src_ptr composited over the premultiplied
+    image at dst_ptr (both 4 bytes per pixel, alpha last; strides and rows in pixels), asynchronous on the context's
+    stream.  blits: an fr_layer_blit array (make_blits) or None.  srgb: FR_LAYER_SRGB, composite in linear light."""
+    n = 0 if blits is None else len(blits)
+    b = None if blits is None else np.ascontiguousarray(blits, BLIT_DTYPE)
+    L.check(ctx._lib.fr_layer_over(ctx._h, C.c_void_p(src_ptr), src_stride_px, src_rows, C.c_void_p(dst_ptr), dst_stride_px,
+                                   dst_rows, None if b is None else L.ptr(b), n, flags | (L.FR_LAYER_SRGB if srgb else 0)))
+
+
+def layer_unpremultiply(ctx: Context, ptr: int, stride_px: int, w: int, h: int, srgb: bool = False) -> None:
+    """fr_layer_unpremultiply: the w x h window at device address ptr of an image with rows of stride_px pixels from
+    premultiplied to straight alpha, in place, asynchronous on the context's stream"""
+    L.check(ctx._lib.fr_layer_unpremultiply(ctx._h, C.c_void_p(ptr), stride_px, w, h, 1 if srgb else 0))
+
+
 def render_batch(dgs: DeviceGlyphSet, jobs: np.ndarray, mode: int, out: np.ndarray, samples_per_axis: int = 1,
                  sample_phase: int = L.FR_SAMPLE_CORNER, flags: int = 0) -> np.ndarray:
     """fr_render_batch into a HOST array `out` (2-D, u8 or i16 for FR_WINDING_I16)."""

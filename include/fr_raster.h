@@ -626,6 +626,68 @@ int fr_srgb_encode(const uint16_t *in, size_t n, uint8_t *out);
  * straight-alpha file formats expect.  NULL with n_pixels > 0 is FR_E_INVALID.                                          */
 int fr_rgba_unpremultiply(uint8_t *rgba, size_t n_pixels, int srgb);
 
+/* ---- compositing a finished layer (BUILD-DEFINED; DESIGN.md sections 4.8 and 5) ----------------------------------------
+ * An RGBA text plan with FR_TEXT_OVER over a (0, 0, 0, 0) clear colour renders a premultiplied layer.  fr_layer_over puts
+ * rectangles of such a layer over a premultiplied image on the device, at whole-pixel offsets and with an opacity: a
+ * viewer that drags or fades text renders the layer once and composites it per frame.
+ *   Both images are 4-byte elements with alpha last (R G B A or B G R A alike, provided the two agree), both
+ *   PREMULTIPLIED (with FR_LAYER_SRGB: in linear light, as FR_TEXT_SRGB | FR_TEXT_OVER plans write them).  src_dev: the
+ *   layer, src_rows rows of src_stride_px pixels; dst_dev: the image, dst_rows rows of dst_stride_px pixels.  An image's
+ *   width, for clipping, is its stride.
+ *   Definition: m(x, y) = (x * y + 127) div 255 (round to nearest; 255 is odd, so no ties occur).  For a layer pixel
+ *   (s_c, s_a), the destination pixel (d_c, d_a) under it, c over the three colour bytes, and the blit's opacity o:
+ *       a'    = m(s_a, o)
+ *       out_a = a' + m(d_a, 255 - a')                                  (both colour spaces; never exceeds 255)
+ *       out_c = min(255, m(s_c, o) + m(d_c, 255 - a'))                 (flags = 0: on the stored values, UNORM)
+ *       out_c = E(min(65535, (D[s_c] * o + 127) div 255 + (D[d_c] * (255 - a') + 127) div 255))       (FR_LAYER_SRGB; D and
+ *                                                                       E as defined at fr_text_plan_create_rgba)
+ *   Consequences:
+ *     1. A layer pixel (0, 0, 0, 0), or o = 0, leaves the destination pixel byte-identical in both spaces (m(x, 255) = x,
+ *        m(x, 0) = 0, E(D[v]) = v).
+ *     2. A layer pixel with s_a = 255 under o = 255 replaces the destination pixel.
+ *     3. A destination alpha of 255 stays 255.
+ *     4. A valid premultiplied UNORM layer pixel (s_c <= s_a) never reaches the clamp.
+ *     5. The layer of a plan with FR_TEXT_OVER, n = 1 and every placement alpha 255, rendered over the clear colour
+ *        (0, 0, 0, 0) and composited with o = 255 at (0, 0) onto a frame, equals the same plan rendered with FR_TEXT_LOAD
+ *        onto that frame, byte for byte, with and without FR_TEXT_SRGB (FR_LAYER_SRGB to match).  For translucent colours
+ *        or n > 1 the two routes round in two steps against one and differ in the last bit here and there: no equality is
+ *        promised.
+ *   Geometry: blit k copies the w x h rectangle at (src_x, src_y) of the layer so that its top-left pixel lands on
+ *     (dst_x, dst_y) of the image.  The rectangle must lie inside the layer (src_x + w <= src_stride_px, src_y + h <=
+ *     src_rows: FR_E_INVALID otherwise); its destination is clipped to [0, dst_stride_px) x [0, dst_rows), and a blit that
+ *     is clipped away entirely is valid.  After clipping, the destination rectangles of one call must not overlap each
+ *     other, and the byte ranges of the two images must not overlap (FR_E_INVALID).  Inside a clipped rectangle any pixel
+ *     may be read, and written back unchanged; outside every clipped rectangle no byte of the image is read or written; no
+ *     byte of the layer is ever written.
+ *   Validation: both pointers non-NULL and 4-byte aligned, both strides within the 2^26-element pitch limit of
+ *     fr_plan_render, blits non-NULL when n_blits > 0, every opacity <= 255, no unknown flag bit (FR_E_INVALID each);
+ *     n_blits = 0 is valid and launches nothing.  FR_E_UNSUPPORTED: an image of 2^31 rows or more, or a call whose clipped
+ *     rectangles need more than 2^22 tiles of 256 x 16 pixels.
+ *   Execution: one launch of layer_over_kernel<srgb, opacity> (opacity = 0 when every blit that draws has o = 255) for
+ *     all blits of the call, behind a small kernel that brings the call's tile table into device memory; asynchronous on
+ *     the context's stream, in stream order after earlier renders as fr_plan_render is; the caller may reuse `blits` as
+ *     soon as the call returns.
+ * FR_LAYER_SRGB is the flag space of fr_layer_over alone: no other entry point knows it, and fr_layer_over knows none of
+ * the FR_TEXT_ / FR_FILL_ flags.                                                                                          */
+#define FR_LAYER_SRGB 1u
+
+typedef struct fr_layer_blit {
+    uint32_t src_x, src_y;     /* top-left of the rectangle in the layer, pixels                 */
+    uint32_t w, h;             /* its size; 0 x anything is valid and does nothing               */
+    int32_t  dst_x, dst_y;     /* where that top-left lands in the destination; may be negative  */
+    uint32_t opacity;          /* o in 0 .. 255 (above: FR_E_INVALID); 255 = the layer as it is  */
+} fr_layer_blit;
+
+int fr_layer_over(fr_ctx *ctx, const void *src_dev, size_t src_stride_px, size_t src_rows,
+                  void *dst_dev, size_t dst_stride_px, size_t dst_rows,
+                  const fr_layer_blit *blits, uint32_t n_blits, uint32_t flags);
+
+/* fr_rgba_unpremultiply on the device: the same three cases, in place, over the w x h window at rgba_dev of an image with
+ * rows of stride_px pixels; byte for byte what the host function makes of the same pixels, and no byte outside the window
+ * is read or written.  Asynchronous on the context's stream.  FR_E_INVALID: NULL or a pointer that is not 4-byte aligned,
+ * w > stride_px, stride_px beyond 2^26.                                                                                   */
+int fr_layer_unpremultiply(fr_ctx *ctx, void *rgba_dev, size_t stride_px, uint32_t w, uint32_t h, int srgb);
+
 /* ---- self-test: exhaustive device-side check of an arithmetic shortcut ----------
  * The render kernel computes t = num / d (render_glyph.zig:51,60-61; d an integer, |d| <= 2^17)
  * as a reciprocal multiply + FMA correction.  This compares that sequence with IEEE division
