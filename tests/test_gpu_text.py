@@ -1,63 +1,20 @@
 """Text runs on the GPU (fr_text_plan_create, include/fr_raster.h): byte for byte against the CPU twin of the definition
-(tests/text_ref.py) or, for whole-pixel single instances, against fr_render_batch of the equivalent job.  Outputs are
+(tests/text_twin.py) or, for whole-pixel single instances, against fr_render_batch of the equivalent job.  Outputs are
 sentinel-filled device buffers: bytes outside every run must keep the sentinel."""
 import numpy as np
 import pytest
 
 import font_renderer_amd as fr
-import text_ref
+import text_gpu as G
+import text_twin as tw
 from fixtures import load_font
 from font_renderer_amd import render_glyph as rg
 from font_renderer_amd.glyph import GlyphSet
 from font_renderer_amd.synth import synth_glyphset
+from text_gpu import FILL
 
 pytestmark = pytest.mark.gpu
 SENT = 0x5b
-FILL = fr.FR_FILL_CONSISTENT
-
-
-def _phase(center):
-    return fr.FR_SAMPLE_CENTER if center else fr.FR_SAMPLE_CORNER
-
-
-def _render(ctx, dgs, places, runs, shape, mode=fr.FR_COVERAGE_U8, n=4, center=True, flags=0, plan_out=None):
-    import torch
-    plan = fr.TextPlan(dgs, places, runs, mode, n, _phase(center), flags)
-    buf = torch.full(shape, SENT, dtype=torch.uint8, device="cuda:0")
-    torch.cuda.synchronize()
-    plan.render(buf.data_ptr(), shape[1], shape[0])
-    ctx.sync()
-    if plan_out is not None:
-        plan_out.update(stats=plan.stats(), describe=plan.describe(), pixels=plan.pixels)
-    plan.close()
-    return buf.cpu().numpy()
-
-
-def _twin(gs, places, runs, shape, n=4, center=True, fill=False, which=None):
-    return text_ref.render_runs(gs, places, runs, np.full(shape, SENT, np.uint8), n, center, fill, which)
-
-
-def _lines(font, strings, size, pad=0):
-    """one run per string, stacked: the run is the union of the string's instance cells (pen origin at its left edge,
-    whole pixels moved right if a cell reaches left of it), `pad` pixels of sentinel between runs"""
-    lay = [font.layout(s, size) for s in strings]
-    distinct = sorted({int(g) for gi, _, _ in lay for g in gi})
-    gs, kept = font.glyphset(distinct, skip_unsupported=False)
-    local = {g: k for k, g in enumerate(kept)}
-    scale = np.float32(size) / np.float32(font.information.units_per_em)
-    seg = gs.segments_per_glyph()
-    places, runs, y, W = [], [], pad, 0
-    for gi, pen, _ in lay:
-        cells = [text_ref.cell(gs.boxes[local[int(g)]], scale, int(p), 0) for g, p in zip(gi, pen) if seg[local[int(g)]]]
-        left, top = min(c[0] for c in cells), min(c[1] for c in cells)
-        shift = max(-left, 0)
-        w = max(c[0] + c[2] for c in cells) + shift
-        h = max(c[1] + c[3] for c in cells) - top
-        runs.append((len(places), len(gi), w, h, pad, y, scale))
-        places += [(local[int(g)], int(p) + 64 * shift, -top) for g, p in zip(gi, pen)]
-        y += h + pad
-        W = max(W, w + 2 * pad)
-    return gs, rg.make_places(places), rg.make_runs(runs), (y, W)
 
 
 # ---- 1. one whole-pixel instance is the ordinary job ----------------------------------------------------------------
@@ -67,7 +24,7 @@ def test_one_instance_equals_the_job(ctx, ascii_set, font_size):
     cells = []
     for g in range(len(ascii_set)):
         scale = np.float32(font_size) / np.float32(int(ascii_set.g_upm[g]))
-        c0, r0, w, h = text_ref.cell(gs.boxes[g], scale, 0, 0)
+        c0, r0, w, h = tw.plain_cell(gs.boxes[g], scale, 0, 0)
         cells.append((c0, -r0, w, h, scale))
     CW, CH, cols = max(c[2] for c in cells) + 3, max(c[3] for c in cells) + 3, 24
     shape = (CH * ((len(cells) + cols - 1) // cols), CW * cols)
@@ -78,9 +35,9 @@ def test_one_instance_equals_the_job(ctx, ascii_set, font_size):
     for mode, n in [(fr.FR_MASK_NONZERO, 1), (fr.FR_COVERAGE_U8, 1), (fr.FR_COVERAGE_U8, 2), (fr.FR_COVERAGE_U8, 4)]:
         for center in (False, True):
             for flags in (0, FILL):
-                got = _render(ctx, dgs, places, runs, shape, mode, n, center, flags)
+                got = G.render_gray(ctx, dgs, places, runs, shape, mode, n, center, flags)
                 want = np.full(shape, SENT, np.uint8)
-                rg.render_batch(dgs, jobs, mode, want, n, _phase(center), flags)
+                rg.render_batch(dgs, jobs, mode, want, n, G.phase(center), flags)
                 assert np.array_equal(got, want), (font_size, mode, n, center, flags)
     dgs.close()
 
@@ -92,12 +49,12 @@ STRINGS = ["ffi fj Tf ff", "Tjfyfgf jjj", "Wavy /// fff", "ƒ∫ fî T,"]
 @pytest.mark.parametrize("font_size,n,center", [(16, 4, True), (23, 2, False), (40, 1, True), (11, 4, False)])
 def test_overlapping_strings_equal_the_twin(ctx, font_size, n, center):
     font = load_font("DejaVuSerif-Italic.ttf")
-    gs, places, runs, shape = _lines(font, STRINGS, font_size, pad=2)
+    gs, places, runs, shape = tw.lines(font, STRINGS, font_size, pad=2)
     assert any(p % 64 for p in places["pen_x64"]), "the pens must have fractional parts"
     dgs = fr.DeviceGlyphSet(ctx, gs)
     for flags in (0, FILL):
-        got = _render(ctx, dgs, places, runs, shape, fr.FR_COVERAGE_U8, n, center, flags)
-        assert np.array_equal(got, _twin(gs, places, runs, shape, n, center, flags == FILL)), (font_size, n, flags)
+        got = G.render_gray(ctx, dgs, places, runs, shape, fr.FR_COVERAGE_U8, n, center, flags)
+        assert np.array_equal(got, G.twin_gray("plain", gs, places, runs, shape, n, center, flags == FILL)), (font_size, n, flags)
     dgs.close()
     # instances of different glyphs share pixels, and the union is not the max of the separate coverages
     overlaps, differs = 0, 0
@@ -107,10 +64,10 @@ def test_overlapping_strings_equal_the_twin(ctx, font_size, n, center):
         for k in range(int(run["first"]), int(run["first"]) + int(run["count"])):
             one = run.copy()
             one["first"], one["count"] = k, 1
-            sep.append(text_ref.render_run(gs, places, one, n, center))
+            sep.append(tw.render_run("plain", gs, places, one, n, center))
         cov = np.stack(sep)
         overlaps += int(((cov > 0).sum(0) > 1).sum())
-        differs += int((cov.max(0) != text_ref.render_run(gs, places, run, n, center)).sum())
+        differs += int((cov.max(0) != tw.render_run("plain", gs, places, run, n, center)).sum())
     assert overlaps > 0
     if n > 1:
         assert differs > 0
@@ -120,9 +77,9 @@ def test_render_text_matches_the_twin(ctx):
     font = load_font("DejaVuSerif-Italic.ttf")
     for text, size in [("Tffj fix", 27), ("jump", 9)]:
         im = fr.render_text(font, text, size, ctx=ctx)
-        gs, places, runs, shape = _lines(font, [text], size)
+        gs, places, runs, shape = tw.lines(font, [text], size)
         assert (im.height, im.width) == shape
-        assert np.array_equal(im.as_2d(), text_ref.render_run(gs, places, runs[0], 4, True))
+        assert np.array_equal(im.as_2d(), tw.render_run("plain", gs, places, runs[0], 4, True))
 
 
 # ---- 3. every sub-pixel pen ------------------------------------------------------------------------------------------
@@ -141,8 +98,8 @@ def test_every_pen_fraction(ctx):
     shape = (16 * (H + 1), 16 * (W + 1))
     dgs = fr.DeviceGlyphSet(ctx, gs)
     for n, center in [(4, True), (1, False), (2, True)]:
-        got = _render(ctx, dgs, places, runs, shape, fr.FR_COVERAGE_U8, n, center)
-        assert np.array_equal(got, _twin(gs, places, runs, shape, n, center)), (n, center)
+        got = G.render_gray(ctx, dgs, places, runs, shape, fr.FR_COVERAGE_U8, n, center)
+        assert np.array_equal(got, G.twin_gray("plain", gs, places, runs, shape, n, center)), (n, center)
         for k in range(0, len(rows), 2):
             a = got[runs[k]["out_y"]:runs[k]["out_y"] + H, runs[k]["out_x"]:runs[k]["out_x"] + W]
             b = got[runs[k + 1]["out_y"]:runs[k + 1]["out_y"] + H, runs[k + 1]["out_x"]:runs[k + 1]["out_x"] + W]
@@ -171,8 +128,8 @@ def test_borders_and_clipping(ctx):
     places, runs = rg.make_places(rows), rg.make_runs(runs)
     shape = (2 + 5 * (H + 3) + 14, 8 * (W + 4) + 9)
     dgs = fr.DeviceGlyphSet(ctx, gs)
-    got = _render(ctx, dgs, places, runs, shape)
-    want = _twin(gs, places, runs, shape)
+    got = G.render_gray(ctx, dgs, places, runs, shape)
+    want = G.twin_gray("plain", gs, places, runs, shape)
     assert np.array_equal(got, want)
     inside = np.zeros(shape, bool)
     for r in runs:
@@ -182,7 +139,7 @@ def test_borders_and_clipping(ctx):
     assert not got[last["out_y"]:last["out_y"] + last["h"], last["out_x"]:last["out_x"] + last["w"]].any()
     # run pixels outside every cell are 0: the four-glyph run, right of its cells
     r4 = runs[-2]
-    right = max(c[0] + c[2] for c in (text_ref.cell(gs.boxes[int(p["glyph"])], scale, int(p["pen_x64"]), 24) for p in places[-4:]))
+    right = max(c[0] + c[2] for c in (tw.plain_cell(gs.boxes[int(p["glyph"])], scale, int(p["pen_x64"]), 24) for p in places[-4:]))
     assert right < int(r4["w"])
     assert not got[r4["out_y"]:r4["out_y"] + r4["h"], r4["out_x"] + right:r4["out_x"] + r4["w"]].any()
     dgs.close()
@@ -195,9 +152,9 @@ def test_large_glyph_and_tall_cell(ctx):
     tall, _ = font.glyphset([font.glyph_index(ord("l")), font.glyph_index(ord("|"))], skip_unsupported=False)
     gs = GlyphSet([big.glyph(0), tall.glyph(0), tall.glyph(1)])
     s_big = np.float32(0.05)
-    c0, r0, w0, h0 = text_ref.cell(gs.boxes[0], s_big, 0, 0)
+    c0, r0, w0, h0 = tw.plain_cell(gs.boxes[0], s_big, 0, 0)
     s_tall = np.float32(700) / np.float32(2048)                          # 'l' at 700: > 512 rows, > 2048 sample rows at n = 4
-    c1, r1, w1, h1 = text_ref.cell(gs.boxes[1], s_tall, 0, 0)
+    c1, r1, w1, h1 = tw.plain_cell(gs.boxes[1], s_tall, 0, 0)
     assert 4 * h1 > 2048
     places = rg.make_places([(0, -64 * c0 + 37, -r0), (0, -64 * c0 + 64 * 9 + 5, -r0 + 4),
                              (1, -64 * c1 + 21, -r1), (2, -64 * c1 + 64 * 30 + 50, -r1)])
@@ -205,14 +162,14 @@ def test_large_glyph_and_tall_cell(ctx):
     shape = (max(h0 + 5, h1 + 1) + 1, w0 + 13 + 121)
     dgs = fr.DeviceGlyphSet(ctx, gs)
     info = {}
-    got = _render(ctx, dgs, places, runs, shape, fr.FR_COVERAGE_U8, 4, True, plan_out=info)
+    got = G.render_gray(ctx, dgs, places, runs, shape, fr.FR_COVERAGE_U8, 4, True, info=info)
     assert info["stats"] == {"jobs_cov4": 0, "jobs_general": 4}, info
     assert info["pixels"] == sum(int(r["w"]) * int(r["h"]) for r in runs)
     assert "fr::text_kernel<4, 0>" in info["describe"], info
-    assert np.array_equal(got, _twin(gs, places, runs, shape, 4, True))
-    got = _render(ctx, dgs, places, runs, shape, fr.FR_COVERAGE_U8, 2, False, FILL, plan_out=info)
+    assert np.array_equal(got, G.twin_gray("plain", gs, places, runs, shape, 4, True))
+    got = G.render_gray(ctx, dgs, places, runs, shape, fr.FR_COVERAGE_U8, 2, False, FILL, info=info)
     assert "fr::text_kernel<2, 1>" in info["describe"], info
-    assert np.array_equal(got, _twin(gs, places, runs, shape, 2, False, True))
+    assert np.array_equal(got, G.twin_gray("plain", gs, places, runs, shape, 2, False, True))
     dgs.close()
 
 
@@ -222,7 +179,7 @@ def test_many_runs_graph_and_overlap(ctx):
     rng = np.random.default_rng(2024)
     alphabet = np.array(list("abcdefghijklmnopqrstuvwxyzABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789ffjT.,;!?"))
     strings = ["".join(rng.choice(alphabet, int(rng.integers(3, 24)))) for _ in range(2500)]
-    gs, places, runs, (H, W) = _lines(font, strings, 14, pad=1)
+    gs, places, runs, (H, W) = tw.lines(font, strings, 14, pad=1)
     # two columns of runs, so the output is not one tall strip
     half = len(runs) // 2
     y_off = int(runs[half]["out_y"]) - 1
@@ -230,9 +187,9 @@ def test_many_runs_graph_and_overlap(ctx):
     runs["out_y"][half:] -= y_off
     shape = (max(H - y_off, int(runs["out_y"][half - 1] + runs["h"][half - 1] + 1)), 2 * W)
     dgs = fr.DeviceGlyphSet(ctx, gs)
-    base = _render(ctx, dgs, places, runs, shape)
+    base = G.render_gray(ctx, dgs, places, runs, shape)
     which = sorted(rng.choice(len(runs), 40, replace=False).tolist())
-    want = _twin(gs, places, runs, shape, which=which)
+    want = G.twin_gray("plain", gs, places, runs, shape, which=which)
     for r in which:
         run = runs[r]
         sl = np.s_[run["out_y"]:run["out_y"] + run["h"], run["out_x"]:run["out_x"] + run["w"]]
@@ -240,10 +197,10 @@ def test_many_runs_graph_and_overlap(ctx):
     try:
         ctx.set_option("graph", 1)
         for _ in range(2):
-            assert np.array_equal(_render(ctx, dgs, places, runs, shape), base)
+            assert np.array_equal(G.render_gray(ctx, dgs, places, runs, shape), base)
         ctx.set_option("graph", 0)
         ctx.set_option("overlap", 2)
-        assert np.array_equal(_render(ctx, dgs, places, runs, shape), base)
+        assert np.array_equal(G.render_gray(ctx, dgs, places, runs, shape), base)
     finally:
         ctx.set_option("graph", 0)
         ctx.set_option("overlap", 1)

@@ -1,7 +1,7 @@
 """Text plans of fr_glyph_place_affine placements on the GPU (fr_text_plan_create_affine / fr_text_plan_create_rgba_affine,
 include/fr_raster.h): byte for byte against the fr_glyph_place_ex plans where the matrix is upright with a power-of-two
 scale, against exact block-glyph images (tests/text_affine_cases.py), and against the CPU twin of the definition
-(tests/text_affine_ref.py) everywhere else.  Outputs are sentinel-filled (or, for FR_TEXT_LOAD, noise-filled) device
+(tests/text_twin.py) everywhere else.  Outputs are sentinel-filled (or, for FR_TEXT_LOAD, noise-filled) device
 buffers a few pixels larger than the runs: bytes outside every run must keep what they held.  Every comparison is
 np.array_equal over the whole array: the feature has no tolerance."""
 import math
@@ -12,69 +12,22 @@ import pytest
 
 import font_renderer_amd as fr
 import text_affine_cases as ac
-import text_affine_ref as ta
 import text_block_cases as bc
-import text_rgba_ref as tr
+import text_gpu as G
+import text_twin as tw
 from fixtures import load_font
 from font_renderer_amd import render_glyph as rg
 from font_renderer_amd import text as T
+from text_gpu import BGRA, FILL, LOAD, SRGB
 
 pytestmark = pytest.mark.gpu
 SENT = 0x5b
-FILL, SRGB, BGRA, LOAD = fr.FR_FILL_CONSISTENT, fr.FR_TEXT_SRGB, fr.FR_TEXT_BGRA, fr.FR_TEXT_LOAD
 GRIDS = [(4, True), (4, False), (2, True), (2, False), (1, True), (1, False)]
 FAMILIES = [("rgba_", 0), ("srgb_", SRGB), ("rgba_load_", LOAD), ("srgb_load_", SRGB | LOAD)]
 
 
-def _phase(center):
-    return fr.FR_SAMPLE_CENTER if center else fr.FR_SAMPLE_CORNER
-
-
-def _render(ctx, dgs, places, runs, shape, mode=fr.FR_COVERAGE_U8, n=4, center=True, flags=0, info=None):
-    """a coverage / mask plan of any placement form into a sentinel-filled buffer"""
-    import torch
-    with closing(fr.TextPlan(dgs, places, runs, mode, n, _phase(center), flags)) as plan:
-        buf = torch.full(shape, SENT, dtype=torch.uint8, device="cuda:0")
-        torch.cuda.synchronize()
-        plan.render(buf.data_ptr(), shape[1], shape[0])
-        ctx.sync()
-        if info is not None:
-            info.update(describe=plan.describe(), pixels=plan.pixels)
-    return buf.cpu().numpy()
-
-
-def _render_rgba(ctx, dgs, places, cols, runs, clears, dst, n=4, center=True, flags=0, info=None):
-    """an RGBA plan of any placement form over a device copy of dst ((rows, cols, 4) u8: sentinel, or noise for LOAD)"""
-    import torch
-    with closing(fr.TextPlanRGBA(dgs, places, cols, runs, clears, n, _phase(center), flags)) as plan:
-        buf = torch.from_numpy(np.ascontiguousarray(dst)).to("cuda:0")
-        torch.cuda.synchronize()
-        plan.render(buf.data_ptr(), dst.shape[1], dst.shape[0])
-        ctx.sync()
-        if info is not None:
-            info.update(describe=plan.describe(), pixels=plan.pixels)
-    return buf.cpu().numpy()
-
-
 def _start(shape, load, seed):
-    if load:
-        return np.random.default_rng(seed).integers(0, 256, shape + (4,)).astype(np.uint8)
-    return np.full(shape + (4,), SENT, np.uint8)
-
-
-def _colours(n, seed, opaque):
-    c = np.random.default_rng(seed).integers(0, 256, (n, 4)).astype(np.uint8)
-    if opaque:
-        c[:, 3] = 255
-    else:
-        c[::3, 3] = 255                                                   # a mix: opaque, translucent, and one clear glyph
-        c[1 % n, 3] = 0
-    return c
-
-
-def _twin_rgba(gs, places, cols, runs, clears, dst, n, center, flags):
-    return ta.rgba_render_runs(gs, places, cols, runs, clears, dst.copy(), n, center, bool(flags & FILL), bool(flags & SRGB),
-                               bool(flags & BGRA), bool(flags & LOAD))
+    return G.noise(shape, seed) if load else G.sent4(shape, SENT)
 
 
 # ---- 1. the _ex equivalence on the device (consequence 1) ----------------------------------------------------------------
@@ -82,30 +35,30 @@ def _twin_rgba(gs, places, cols, runs, clears, dst, n, center, flags):
                                                 (1 / 32, 64, 0.2, "gf ∫î")])
 def test_upright_power_of_two_matrices_equal_the_ex_plans(ctx, s, font_size, k, text):
     font = load_font("DejaVuSerif-Italic.ttf")
-    gs, places, runs, shape = tr.lines(font, [text], font_size, pad=3)
+    gs, places, runs, shape = tw.lines(font, [text], font_size, pad=3)
     rng = np.random.default_rng(font_size)
     ex = rg.make_places_ex([(int(p["glyph"]), int(p["pen_x64"]), 64 * int(p["pen_y"]) + int(rng.integers(1, 64)), s, k) for p in places])
-    af = ta.from_ex(ex, runs)
-    clears = _colours(len(runs), 5, False)
+    af = tw.from_ex(ex, runs)
+    clears = G.colours(len(runs), 5, False)
     with closing(fr.DeviceGlyphSet(ctx, gs)) as dgs:
         for fill in (0, FILL):
             for n, center in ((1, False), (2, True), (4, True)):
                 old, new = {}, {}
-                a = _render(ctx, dgs, ex, runs, shape, fr.FR_COVERAGE_U8, n, center, fill, old)
-                b = _render(ctx, dgs, af, runs, shape, fr.FR_COVERAGE_U8, n, center, fill, new)
+                a = G.render_gray(ctx, dgs, ex, runs, shape, fr.FR_COVERAGE_U8, n, center, fill, info=old)
+                b = G.render_gray(ctx, dgs, af, runs, shape, fr.FR_COVERAGE_U8, n, center, fill, info=new)
                 assert np.array_equal(a, b) and (a != SENT).any() and (a == SENT).any(), ("coverage", n, fill)
                 assert "fr::text_place_kernel<" in old["describe"] and "fr::text_affine_kernel<" in new["describe"], (old, new)
                 assert old["pixels"] == new["pixels"]
-            a = _render(ctx, dgs, ex, runs, shape, fr.FR_MASK_NONZERO, 1, True, fill)
-            b = _render(ctx, dgs, af, runs, shape, fr.FR_MASK_NONZERO, 1, True, fill)
+            a = G.render_gray(ctx, dgs, ex, runs, shape, fr.FR_MASK_NONZERO, 1, True, fill)
+            b = G.render_gray(ctx, dgs, af, runs, shape, fr.FR_MASK_NONZERO, 1, True, fill)
             assert np.array_equal(a, b), ("mask", fill)
             n = 4 if fill else 2
             for opaque in (True, False):
-                cols = _colours(len(places), font_size + opaque, opaque)
+                cols = G.colours(len(places), font_size + opaque, opaque)
                 for flags in (0, SRGB, LOAD, SRGB | LOAD, BGRA):
                     dst = _start(shape, flags & LOAD, font_size)
-                    a = _render_rgba(ctx, dgs, ex, cols, runs, None if flags & LOAD else clears, dst, n, True, flags | fill)
-                    b = _render_rgba(ctx, dgs, af, cols, runs, None if flags & LOAD else clears, dst, n, True, flags | fill)
+                    a = G.render_rgba(ctx, dgs, ex, cols, runs, None if flags & LOAD else clears, dst, n, True, flags | fill)
+                    b = G.render_rgba(ctx, dgs, af, cols, runs, None if flags & LOAD else clears, dst, n, True, flags | fill)
                     assert np.array_equal(a, b) and not np.array_equal(a, dst), ("rgba", opaque, flags, fill)
 
 
@@ -115,7 +68,7 @@ def test_block_glyph_images_are_exact(ctx, n, center):
     glyphs, places, runs, shape = ac.block_case(n, center)
     want = ac.render_runs(glyphs, places, runs, np.full(shape, SENT, np.uint8), n, center)
     with closing(fr.DeviceGlyphSet(ctx, bc.glyph_set(glyphs))) as dgs:
-        got = _render(ctx, dgs, places, runs, shape, fr.FR_COVERAGE_U8, n, center, FILL)
+        got = G.render_gray(ctx, dgs, places, runs, shape, fr.FR_COVERAGE_U8, n, center, FILL)
     assert np.array_equal(got, want), np.argwhere(got != want)[:8]
     assert (want[2:146, 3:219] == 0).any() and (want[2:146, 3:219] == 255).any() and (want[5:12, 225:234] != 0).any()
 
@@ -145,23 +98,23 @@ def test_rotated_real_font_strings_match_the_twin(ctx, case):
     gs, places, runs, shape = _rotated(font_name, size, angle, mirror)
     m = places["m"][0].astype(np.float64)
     assert (m[0] * m[3] - m[1] * m[2] < 0) == mirror
-    clears = _colours(1, 9, False)
+    clears = G.colours(1, 9, False)
     with closing(fr.DeviceGlyphSet(ctx, gs)) as dgs:
         for fill in (0, FILL):
             for n, center in ((4, True), (1, False)):
-                got = _render(ctx, dgs, places, runs, shape, fr.FR_COVERAGE_U8, n, center, fill)
-                want = ta.render_runs(gs, places, runs, np.full(shape, SENT, np.uint8), n, center, bool(fill))
+                got = G.render_gray(ctx, dgs, places, runs, shape, fr.FR_COVERAGE_U8, n, center, fill)
+                want = G.twin_gray("affine", gs, places, runs, shape, n, center, bool(fill))
                 assert np.array_equal(got, want), ("coverage", n, fill, np.argwhere(got != want)[:8])
                 inner = want[2:98, 3:163]
                 assert (inner > 0).sum() > 40 * (size // 14) and (inner == 0).sum() > inner.size // 2
         for j, (_, fam) in enumerate(FAMILIES):                           # each colour family once per case; over the cases each
             n, center = ((4, True), (1, False))[(case + j) % 2]           # meets n = 4 and n = 1, both fills, opaque and not
             fill = FILL if (case + j // 2) % 2 else 0
-            cols = _colours(len(places), 10 * case + j, opaque=(case + j) % 3 == 0)
+            cols = G.colours(len(places), 10 * case + j, opaque=(case + j) % 3 == 0)
             flags = fam | fill | (BGRA if (case + j) % 4 == 3 else 0)
             dst = _start(shape, fam & LOAD, case)
-            got = _render_rgba(ctx, dgs, places, cols, runs, None if fam & LOAD else clears, dst, n, center, flags)
-            want = _twin_rgba(gs, places, cols, runs, clears, dst, n, center, flags)
+            got = G.render_rgba(ctx, dgs, places, cols, runs, None if fam & LOAD else clears, dst, n, center, flags)
+            want = G.twin_rgba("affine", gs, places, cols, runs, clears, dst, n, center, flags)
             assert np.array_equal(got, want), ("colour", j, n, fill, np.argwhere(got != want)[:8])
             assert not np.array_equal(got, dst)
 
@@ -194,17 +147,17 @@ def test_every_affine_instance_by_name(ctx, three, family, n, fill, blend):
     info = {}
     prep = "fr::prepare_fill_kernel x3; " if fill else "fr::prepare_kernel x3; "
     if blend is None:
-        got = _render(ctx, dgs, places, runs, shape, fr.FR_COVERAGE_U8, n, center, FILL if fill else 0, info)
-        want = ta.render_runs(gs, places, runs, np.full(shape, SENT, np.uint8), n, center, bool(fill))
+        got = G.render_gray(ctx, dgs, places, runs, shape, fr.FR_COVERAGE_U8, n, center, FILL if fill else 0, info=info)
+        want = G.twin_gray("affine", gs, places, runs, shape, n, center, bool(fill))
         assert info["describe"] == prep + "fr::text_affine_kernel<%d, %d> x3" % (n, fill), info
     else:
         fam = dict(FAMILIES)[family]
         flags = fam | (FILL if fill else 0)
-        cols = _colours(3, 7, opaque=not blend)
-        clears = _colours(1, 11, False)
+        cols = G.colours(3, 7, opaque=not blend)
+        clears = G.colours(1, 11, False)
         dst = _start(shape, fam & LOAD, n)
-        got = _render_rgba(ctx, dgs, places, cols, runs, None if fam & LOAD else clears, dst, n, center, flags, info)
-        want = _twin_rgba(gs, places, cols, runs, clears, dst, n, center, flags)
+        got = G.render_rgba(ctx, dgs, places, cols, runs, None if fam & LOAD else clears, dst, n, center, flags, info=info)
+        want = G.twin_rgba("affine", gs, places, cols, runs, clears, dst, n, center, flags)
         assert info["describe"] == prep + "fr::text_affine_%skernel<%d, %d, %d> x3" % (family, n, fill, blend), info
         assert not np.array_equal(got, dst)
     assert np.array_equal(got, want), np.argwhere(got != want)[:8]
@@ -251,15 +204,15 @@ def test_validation_and_fully_clipped_plans(ctx, three):
     away = places.copy()
     away["pen_x64"] += 64 * 5000
     info = {}
-    got = _render(ctx, dgs, away, runs, shape, fr.FR_COVERAGE_U8, 4, True, FILL, info)
+    got = G.render_gray(ctx, dgs, away, runs, shape, fr.FR_COVERAGE_U8, 4, True, FILL, info=info)
     want = np.full(shape, SENT, np.uint8)
     want[1:41, 2:98] = 0
     assert np.array_equal(got, want) and info["describe"] == "fr::text_affine_kernel<4, 1> x0"
     clears = np.array([[9, 8, 7, 6]], np.uint8)
-    got = _render_rgba(ctx, dgs, away, _colours(3, 1, False), runs, clears, _start(shape, False, 0), 2, True, SRGB)
+    got = G.render_rgba(ctx, dgs, away, G.colours(3, 1, False), runs, clears, _start(shape, False, 0), 2, True, SRGB)
     want = _start(shape, False, 0)
     want[1:41, 2:98] = clears[0]
     assert np.array_equal(got, want)
     dst = _start(shape, True, 3)                                                                    # LOAD: nothing is launched
-    got = _render_rgba(ctx, dgs, away, _colours(3, 1, False), runs, None, dst, 2, True, LOAD)
+    got = G.render_rgba(ctx, dgs, away, G.colours(3, 1, False), runs, None, dst, 2, True, LOAD)
     assert np.array_equal(got, dst)

@@ -10,29 +10,12 @@ import pytest
 
 import font_renderer_amd as fr
 import text_block_cases as B
-import text_place_ref as tp
-import text_ref
+import text_gpu as G
 from font_renderer_amd import render_glyph as rg
+from text_gpu import FILL
 
 pytestmark = pytest.mark.gpu
 SENT = B.SENT
-FILL = fr.FR_FILL_CONSISTENT
-
-
-def _phase(center):
-    return fr.FR_SAMPLE_CENTER if center else fr.FR_SAMPLE_CORNER
-
-
-def _render(ctx, dgs, places, runs, shape, n, center, flags, mode=fr.FR_COVERAGE_U8):
-    """a coverage / mask plan of either placement form into a sentinel-filled buffer -> (bytes, describe)"""
-    import torch
-    with closing(fr.TextPlan(dgs, places, runs, mode, n, _phase(center), flags)) as plan:
-        buf = torch.full(shape, SENT, dtype=torch.uint8, device="cuda:0")
-        torch.cuda.synchronize()
-        plan.render(buf.data_ptr(), shape[1], shape[0])
-        ctx.sync()
-        desc = plan.describe()
-    return buf.cpu().numpy(), desc
 
 
 def _check_text(ctx, glyphs, places, runs, shape, n, center, tag):
@@ -42,18 +25,19 @@ def _check_text(ctx, glyphs, places, runs, shape, n, center, tag):
     kernel = "fr::text_%skernel<%d, %%d>" % ("place_" if ex else "", n)
     assert runs["out_x"].min() % 2 == 1 and runs["out_y"].min() % 2 == 1
     with closing(fr.DeviceGlyphSet(ctx, gs)) as dgs:
-        got, desc = _render(ctx, dgs, places, runs, shape, n, center, FILL)
-        assert kernel % 1 in desc, (tag, desc)
+        info = {}
+        got = G.render_gray(ctx, dgs, places, runs, shape, fr.FR_COVERAGE_U8, n, center, FILL, sent=SENT, info=info)
+        assert kernel % 1 in info["describe"], (tag, info)
         want = B.render_runs(glyphs, places, runs, np.full(shape, SENT, np.uint8), n, center)
         assert np.array_equal(got, want), (tag, "fill", np.argwhere(got != want)[:8].tolist())
         assert (want != SENT).any() and (want == 255).any()
-        got, desc = _render(ctx, dgs, places, runs, shape, n, center, 0)
-        assert kernel % 0 in desc, (tag, desc)
-        twin = (tp if ex else text_ref).render_runs(gs, places, runs, np.full(shape, SENT, np.uint8), n, center, False)
+        got = G.render_gray(ctx, dgs, places, runs, shape, fr.FR_COVERAGE_U8, n, center, 0, sent=SENT, info=info)
+        assert kernel % 0 in info["describe"], (tag, info)
+        twin = G.twin_gray("ex" if ex else "plain", gs, places, runs, shape, n, center, False, sent=SENT)
         assert np.array_equal(got, twin), (tag, "reference rule", np.argwhere(got != twin)[:8].tolist())
         if n == 1:                                             # FR_MASK_NONZERO is the same kernel instance and the same bytes
-            mask, desc = _render(ctx, dgs, places, runs, shape, 1, center, FILL, fr.FR_MASK_NONZERO)
-            assert kernel % 1 in desc and np.array_equal(mask, want), tag
+            mask = G.render_gray(ctx, dgs, places, runs, shape, fr.FR_MASK_NONZERO, 1, center, FILL, sent=SENT, info=info)
+            assert kernel % 1 in info["describe"] and np.array_equal(mask, want), tag
         return want, twin
 
 
@@ -106,10 +90,10 @@ def _exact_jobs(glyphs, jobs, shape, n, center, mode):
 
 
 def _render_jobs(ctx, dgs, jobs, mode, shape, n, center, flags):
-    with closing(fr.Plan(dgs, jobs, mode, n, _phase(center), flags)) as plan:
+    with closing(fr.Plan(dgs, jobs, mode, n, G.phase(center), flags)) as plan:
         desc = plan.describe()
     out = np.full(shape, SENT, np.int16 if mode == fr.FR_WINDING_I16 else np.uint8)
-    rg.render_batch(dgs, jobs, mode, out, n, _phase(center), flags)
+    rg.render_batch(dgs, jobs, mode, out, n, G.phase(center), flags)
     return out, desc
 
 

@@ -1,7 +1,7 @@
 """FR_TEXT_CACHE text plans on the GPU (include/fr_raster.h): a plan with the flag must render, byte for byte, what the same
 plan without it renders, in every family (coverage / mask, RGBA, sRGB, LOAD, BGRA; fr_glyph_place and fr_glyph_place_ex).
 The expected image is always the same plan without the flag; for at least one case per family it is also the CPU twin of
-the definition (tests/text_ref.py and its siblings), and the block-glyph cases (tests/text_block_cases.py) are compared to
+the definition (tests/text_twin.py), and the block-glyph cases (tests/text_block_cases.py) are compared to
 their own exact expectations, so nothing rests on GPU kernels alone.  Outputs are sentinel-filled (or noise under LOAD)
 and the whole array is compared."""
 import re
@@ -12,59 +12,23 @@ import pytest
 
 import font_renderer_amd as fr
 import text_block_cases as B
-import text_load_ref as tl
-import text_place_ref as tp
-import text_ref
-import text_rgba_ref as tr
-import text_srgb_ref as ts
+import text_gpu as G
+import text_twin as tw
 from fixtures import load_font
 from font_renderer_amd import render_glyph as rg
+from text_gpu import BGRA, CACHE, FILL, LOAD, SRGB
 
 pytestmark = pytest.mark.gpu
 SENT = 0x5b
-FILL, SRGB, BGRA, LOAD, CACHE = fr.FR_FILL_CONSISTENT, fr.FR_TEXT_SRGB, fr.FR_TEXT_BGRA, fr.FR_TEXT_LOAD, fr.FR_TEXT_CACHE
 TEXT = "minimum illumination"
-
-
-def _phase(center):
-    return fr.FR_SAMPLE_CENTER if center else fr.FR_SAMPLE_CORNER
-
-
-def _count(describe, kernel):
-    m = re.search(re.escape(kernel) + r" x(\d+)", describe)
-    assert m, (kernel, describe)
-    return int(m.group(1))
-
-
-def _gray(ctx, dgs, places, runs, shape, n=4, center=True, flags=0, mode=fr.FR_COVERAGE_U8, times=1):
-    """a coverage / mask plan into a sentinel-filled buffer -> (bytes, describe)"""
-    import torch
-    with closing(fr.TextPlan(dgs, places, runs, mode, n, _phase(center), flags)) as plan:
-        buf = torch.full(shape, SENT, dtype=torch.uint8, device="cuda:0")
-        torch.cuda.synchronize()
-        for _ in range(times):
-            plan.render(buf.data_ptr(), shape[1], shape[0])
-        ctx.sync()
-        desc = plan.describe()
-    return buf.cpu().numpy(), desc
-
-
-def _rgba(ctx, dgs, places, cols, runs, clears, dst, n=4, center=True, flags=0):
-    """an RGBA plan over a fresh device copy of dst ((rows, cols, 4) u8: sentinel, or noise under LOAD) -> (bytes, describe)"""
-    import torch
-    with closing(fr.TextPlanRGBA(dgs, places, cols, runs, clears, n, _phase(center), flags)) as plan:
-        buf = torch.from_numpy(np.ascontiguousarray(dst)).to("cuda:0")
-        torch.cuda.synchronize()
-        plan.render(buf.data_ptr(), dst.shape[1], dst.shape[0])
-        ctx.sync()
-        desc = plan.describe()
-    return buf.cpu().numpy(), desc
 
 
 def _both_gray(ctx, dgs, places, runs, shape, n, center, flags, mode=fr.FR_COVERAGE_U8):
     """cached and plain renders of one plan; asserts the cached one's launches -> (cached bytes, plain bytes, describe)"""
-    got, desc = _gray(ctx, dgs, places, runs, shape, n, center, flags | CACHE, mode)
-    want, plain = _gray(ctx, dgs, places, runs, shape, n, center, flags, mode)
+    info, plain_info = {}, {}
+    got = G.render_gray(ctx, dgs, places, runs, shape, mode, n, center, flags | CACHE, info=info)
+    want = G.render_gray(ctx, dgs, places, runs, shape, mode, n, center, flags, info=plain_info)
+    desc, plain = info["describe"], plain_info["describe"]
     fill = 1 if flags & FILL else 0
     assert f"fr::glyph_mask_kernel<{n}, {fill}> x" in desc and f"fr::text_cached_kernel<{n}> x" in desc, desc
     assert "cached" not in plain and "glyph_mask" not in plain, plain
@@ -103,7 +67,7 @@ def _line_case(font):
             g = int(places[k]["glyph"])
             if not seg[g]:
                 continue
-            c0, r0, cw, ch = text_ref.cell(gs.boxes[g], run["scale"], int(places[k]["pen_x64"]), int(places[k]["pen_y"]))
+            c0, r0, cw, ch = tw.plain_cell(gs.boxes[g], run["scale"], int(places[k]["pen_x64"]), int(places[k]["pen_y"]))
             edges |= {e for e, cut in (("left", c0 < 0 < c0 + cw), ("right", c0 < run["w"] < c0 + cw), ("top", r0 < 0 < r0 + ch),
                                        ("bottom", r0 < run["h"] < r0 + ch)) if cut}
             straddle |= bool(r == 2 and c0 < 64 < c0 + cw and r0 < 16 < r0 + ch and c0 >= 0)
@@ -115,7 +79,7 @@ def _line_case(font):
 @pytest.fixture(scope="module", params=["DejaVuSans.ttf", "DejaVuSerif-Italic.ttf"])
 def line_case(request):
     gs, places, runs, shape = _line_case(load_font(request.param, allow_hinted=True))
-    twin = text_ref.render_runs(gs, places, runs, np.full(shape, SENT, np.uint8), 4, True, False)
+    twin = G.twin_gray("plain", gs, places, runs, shape, 4, True, False)
     return gs, places, runs, shape, twin
 
 
@@ -128,7 +92,7 @@ def test_lines_equal_the_plain_plan_and_the_twin(ctx, line_case):
             got, want, desc = _both_gray(ctx, dgs, places, runs, shape, n, center, flags, mode)
             assert np.array_equal(got, want), (mode, n, center, flags, np.argwhere(got != want)[:8].tolist())
             assert (want != SENT).any() and (want == 255).any()
-            insts, cells = _count(desc, f"fr::text_cached_kernel<{n}>"), _count(desc, "fr::glyph_mask_kernel<%d, %d>" % (n, 1 if flags else 0))
+            insts, cells = G.count(desc, f"fr::text_cached_kernel<{n}>"), G.count(desc, "fr::glyph_mask_kernel<%d, %d>" % (n, 1 if flags else 0))
             assert 0 < cells < insts, desc                             # the case exercises sharing
             if (mode, n, center, flags) == (fr.FR_COVERAGE_U8, 4, True, 0):
                 assert np.array_equal(got, twin)
@@ -139,7 +103,7 @@ def test_one_large_cell(ctx):
     font = load_font("DejaVuSans.ttf", allow_hinted=True)
     gs, _ = font.glyphset([font.glyph_index(ord("m"))], skip_unsupported=False)
     scale = np.float32(86) / np.float32(font.information.units_per_em)
-    c0, r0, cw, ch = text_ref.cell(gs.boxes[0], scale, 0, 0)
+    c0, r0, cw, ch = tw.plain_cell(gs.boxes[0], scale, 0, 0)
     assert 64 < cw < 128 and 32 < ch <= 64, (cw, ch)                   # about 70 x 50: 2 x 4 mask tiles
     base = -r0 + 2
     places = rg.make_places([(0, 64 * 3, base), (0, 64 * 60, base + 7), (0, 64 * 8 + 37, base + 3), (0, 64 * 90 + 37, base + 11)])
@@ -149,9 +113,9 @@ def test_one_large_cell(ctx):
         for n, center, flags in [(4, True, 0), (2, False, FILL), (1, True, 0)]:
             got, want, desc = _both_gray(ctx, dgs, places, runs, shape, n, center, flags)
             assert np.array_equal(got, want), (n, center, flags)
-            assert _count(desc, f"fr::text_cached_kernel<{n}>") == 4 and "glyph_mask_kernel<%d, %d> x2;" % (n, 1 if flags else 0) in desc, desc
+            assert G.count(desc, f"fr::text_cached_kernel<{n}>") == 4 and "glyph_mask_kernel<%d, %d> x2;" % (n, 1 if flags else 0) in desc, desc
         got, _, _ = _both_gray(ctx, dgs, places, runs, shape, 4, True, 0)
-        assert np.array_equal(got, text_ref.render_runs(gs, places, runs, np.full(shape, SENT, np.uint8), 4, True, False))
+        assert np.array_equal(got, G.twin_gray("plain", gs, places, runs, shape, 4, True, False))
 
 
 # ---- 3. the _ex form: every key field separates, equal keys share ------------------------------------------------------------------
@@ -174,12 +138,13 @@ def test_ex_keys(ctx):
             assert np.array_equal(got, want), (n, center, flags)
             assert "glyph_mask_kernel<%d, %d> x5; fr::text_cached_kernel<%d> x6" % (n, 1 if flags else 0, n) in desc, desc
         got, _, _ = _both_gray(ctx, dgs, places, runs, shape, 4, True, FILL)
-        assert np.array_equal(got, tp.render_runs(gs, places, runs, np.full(shape, SENT, np.uint8), 4, True, True))
+        assert np.array_equal(got, G.twin_gray("ex", gs, places, runs, shape, 4, True, True))
         # scale 0 is the run's scale: the same key as naming it
         places0 = places.copy()
         places0["scale"][1] = 0.0
-        got0, desc0 = _gray(ctx, dgs, places0, runs, shape, 4, True, FILL | CACHE)
-        assert np.array_equal(got0, got) and "glyph_mask_kernel<4, 1> x5;" in desc0, desc0
+        info = {}
+        got0 = G.render_gray(ctx, dgs, places0, runs, shape, fr.FR_COVERAGE_U8, 4, True, FILL | CACHE, info=info)
+        assert np.array_equal(got0, got) and "glyph_mask_kernel<4, 1> x5;" in info["describe"], info
 
 
 # ---- 4. RGBA: opaque and translucent, UNORM and sRGB, clear colour and LOAD, BGRA, overlaps in both orders -------------------------
@@ -197,7 +162,7 @@ def colour_case():
     places = rg.make_places(fwd + fwd[::-1])
     runs = rg.make_runs([(0, 6, 200, 27, 1, 1, scale), (6, 6, 200, 27, 1, 29, scale)])
     shape = (57, 202)
-    right = max(c[0] + c[2] for c in (text_ref.cell(gs.boxes[p["glyph"]], scale, int(p["pen_x64"]), 20) for p in places))
+    right = max(c[0] + c[2] for c in (tw.plain_cell(gs.boxes[p["glyph"]], scale, int(p["pen_x64"]), 20) for p in places))
     assert right <= 128
     rng = np.random.default_rng(5)
     opaque = rng.integers(0, 256, (12, 4)).astype(np.uint8)
@@ -209,10 +174,6 @@ def colour_case():
     return gs, places, runs, shape, opaque, translucent, clears, noise
 
 
-def _rgba_name(n, flags, blend):
-    return "fr::text_cached_%s%skernel<%d, %d> x12" % ("srgb_" if flags & SRGB else "rgba_", "load_" if flags & LOAD else "", n, blend)
-
-
 @pytest.mark.parametrize("load", [0, LOAD], ids=["clear", "load"])
 @pytest.mark.parametrize("space", [0, SRGB], ids=["unorm", "srgb"])
 def test_rgba_equals_the_plain_plan_and_the_twin(ctx, colour_case, space, load):
@@ -222,10 +183,12 @@ def test_rgba_equals_the_plain_plan_and_the_twin(ctx, colour_case, space, load):
         for cols, blend in ((opaque, 0), (translucent, 1)):
             for n, center, fill in [(4, True, 0), (2, False, FILL), (1, True, 0)]:
                 flags = space | load | fill
-                got, desc = _rgba(ctx, dgs, places, cols, runs, None if load else clears, dst, n, center, flags | CACHE)
-                want, plain = _rgba(ctx, dgs, places, cols, runs, None if load else clears, dst, n, center, flags)
-                assert _rgba_name(n, flags, blend) in desc and f"fr::glyph_mask_kernel<{n}, {1 if fill else 0}> x" in desc, desc
-                assert "cached" not in plain
+                info, plain = {}, {}
+                got = G.render_rgba(ctx, dgs, places, cols, runs, None if load else clears, dst, n, center, flags | CACHE, info=info)
+                want = G.render_rgba(ctx, dgs, places, cols, runs, None if load else clears, dst, n, center, flags, info=plain)
+                desc = info["describe"]
+                assert G.cached_kernel_name(flags, n, blend) + "12" in desc and f"fr::glyph_mask_kernel<{n}, {1 if fill else 0}> x" in desc, desc
+                assert "cached" not in plain["describe"]
                 assert np.array_equal(got, want), (space, load, blend, n, center, fill, np.argwhere(got != want)[:8].tolist())
                 assert not np.array_equal(got, dst)
                 if load:                                               # the tile no instance meets: neither read nor written
@@ -233,34 +196,33 @@ def test_rgba_equals_the_plain_plan_and_the_twin(ctx, colour_case, space, load):
                         sl = np.s_[r["out_y"]:r["out_y"] + r["h"], r["out_x"] + 128:r["out_x"] + 192]
                         assert np.array_equal(got[sl], noise[sl])
                 if n == 2:                                             # the CPU twin of the definition, once per family and blend
-                    twin = tp.rgba_render_runs(gs, rg.make_places_ex([(int(p["glyph"]), int(p["pen_x64"]), 64 * int(p["pen_y"]), 0.0, 0.0) for p in places]),
-                                               cols, runs, clears, dst.copy(), n, center, bool(fill), bool(space), False, bool(load))
+                    twin = G.twin_rgba("ex", gs, G.degenerate(places), cols, runs, clears, dst, n, center, flags)
                     assert np.array_equal(got, twin), (space, load, blend)
         if not load:                                                   # the two orders of the placements differ where their ink overlaps
             same = opaque[[0, 1, 2, 3, 4, 5, 5, 4, 3, 2, 1, 0]]        # each glyph in its colour in both runs
-            got, _ = _rgba(ctx, dgs, places, same, runs, clears[[0, 0]], dst, 4, True, space | CACHE)
+            got = G.render_rgba(ctx, dgs, places, same, runs, clears[[0, 0]], dst, 4, True, space | CACHE)
             a, b = (got[r["out_y"]:r["out_y"] + r["h"], r["out_x"]:r["out_x"] + r["w"]] for r in runs)
             assert (a != b).any() and (a == b).any()
 
 
 def test_bgra_and_the_old_twins(ctx, colour_case):
-    """FR_TEXT_BGRA once per colour space, and the twins of the upright form itself (text_rgba_ref / text_srgb_ref /
-    text_load_ref), which the placement twin above does not go through for its blending order alone"""
+    """FR_TEXT_BGRA once per colour space, and the twin of the upright form itself, UNORM, sRGB and LOAD, which the
+    placement twin above does not go through"""
     gs, places, runs, shape, opaque, translucent, clears, noise = colour_case
     sent = np.full(shape + (4,), SENT, np.uint8)
     with closing(fr.DeviceGlyphSet(ctx, gs)) as dgs:
         for flags, dst in ((BGRA, sent), (BGRA | SRGB | LOAD, noise)):
-            got, _ = _rgba(ctx, dgs, places, translucent, runs, None if flags & LOAD else clears, dst, 4, True, flags | CACHE)
-            want, _ = _rgba(ctx, dgs, places, translucent, runs, None if flags & LOAD else clears, dst, 4, True, flags)
+            got = G.render_rgba(ctx, dgs, places, translucent, runs, None if flags & LOAD else clears, dst, 4, True, flags | CACHE)
+            want = G.render_rgba(ctx, dgs, places, translucent, runs, None if flags & LOAD else clears, dst, 4, True, flags)
             assert np.array_equal(got, want), flags
-            swapped, _ = _rgba(ctx, dgs, places, translucent, runs, None if flags & LOAD else clears, dst, 4, True, (flags & ~BGRA) | CACHE)
+            swapped = G.render_rgba(ctx, dgs, places, translucent, runs, None if flags & LOAD else clears, dst, 4, True, (flags & ~BGRA) | CACHE)
             assert not np.array_equal(got, swapped)
-        got, _ = _rgba(ctx, dgs, places, translucent, runs, clears, sent, 2, True, CACHE)
-        assert np.array_equal(got, tr.render_runs(gs, places, translucent, runs, clears, sent.copy(), 2, True, False))
-        got, _ = _rgba(ctx, dgs, places, opaque, runs, clears, sent, 2, False, CACHE | SRGB | FILL)
-        assert np.array_equal(got, ts.render_runs(gs, places, opaque, runs, clears, sent.copy(), 2, False, True))
-        got, _ = _rgba(ctx, dgs, places, translucent, runs, None, noise, 2, True, CACHE | LOAD | SRGB | BGRA)
-        assert np.array_equal(got, tl.render_runs(gs, places, translucent, runs, noise.copy(), 2, True, False, True, True))
+        got = G.render_rgba(ctx, dgs, places, translucent, runs, clears, sent, 2, True, CACHE)
+        assert np.array_equal(got, G.twin_rgba("plain", gs, places, translucent, runs, clears, sent, 2, True, 0))
+        got = G.render_rgba(ctx, dgs, places, opaque, runs, clears, sent, 2, False, CACHE | SRGB | FILL)
+        assert np.array_equal(got, G.twin_rgba("plain", gs, places, opaque, runs, clears, sent, 2, False, SRGB | FILL))
+        got = G.render_rgba(ctx, dgs, places, translucent, runs, None, noise, 2, True, CACHE | LOAD | SRGB | BGRA)
+        assert np.array_equal(got, G.twin_rgba("plain", gs, places, translucent, runs, None, noise, 2, True, LOAD | SRGB | BGRA))
 
 
 def test_rgba_ex_form(ctx, colour_case):
@@ -269,9 +231,10 @@ def test_rgba_ex_form(ctx, colour_case):
     ex = rg.make_places_ex([(int(p["glyph"]), int(p["pen_x64"]), 64 * int(p["pen_y"]) + 24, 0.0, 0.2) for p in places])
     with closing(fr.DeviceGlyphSet(ctx, gs)) as dgs:
         for flags, dst, cl in ((0, np.full(shape + (4,), SENT, np.uint8), clears), (LOAD | SRGB, noise, None)):
-            got, desc = _rgba(ctx, dgs, ex, translucent, runs, cl, dst, 4, True, flags | CACHE)
-            want, plain = _rgba(ctx, dgs, ex, translucent, runs, cl, dst, 4, True, flags)
-            assert _rgba_name(4, flags, 1) in desc and "text_place_" in plain, (desc, plain)
+            info, plain = {}, {}
+            got = G.render_rgba(ctx, dgs, ex, translucent, runs, cl, dst, 4, True, flags | CACHE, info=info)
+            want = G.render_rgba(ctx, dgs, ex, translucent, runs, cl, dst, 4, True, flags, info=plain)
+            assert G.cached_kernel_name(flags, 4, 1) + "12" in info["describe"] and "text_place_" in plain["describe"], (info, plain)
             assert np.array_equal(got, want), flags
 
 
@@ -282,7 +245,9 @@ def test_block_rows_on_vertices_and_pen_fractions(ctx, ex):
     cases += [(("pen", n, center), case, n, center) for (n, center), case in B.pen_fraction_cases(ex).items()]
     for tag, (glyphs, places, runs, shape), n, center in cases:
         with closing(fr.DeviceGlyphSet(ctx, B.glyph_set(glyphs))) as dgs:
-            got, desc = _gray(ctx, dgs, places, runs, shape, n, center, FILL | CACHE)
+            info = {}
+            got = G.render_gray(ctx, dgs, places, runs, shape, fr.FR_COVERAGE_U8, n, center, FILL | CACHE, info=info)
+            desc = info["describe"]
             assert f"fr::glyph_mask_kernel<{n}, 1> x" in desc and f"fr::text_cached_kernel<{n}> x" in desc, desc
             want = B.render_runs(glyphs, places, runs, np.full(shape, B.SENT, np.uint8), n, center)
             assert np.array_equal(got, want), (tag, np.argwhere(got != want)[:8].tolist())
@@ -313,18 +278,21 @@ def test_block_colour_cases(ctx, ex, srgb):
 def test_repeat_graph_and_describe(ctx, line_case, colour_case):
     gs, places, runs, shape, _ = line_case
     with closing(fr.DeviceGlyphSet(ctx, gs)) as dgs:
-        once, desc = _gray(ctx, dgs, places, runs, shape, 4, True, CACHE)
-        twice, _ = _gray(ctx, dgs, places, runs, shape, 4, True, CACHE, times=2)
+        info = {}
+        once = G.render_gray(ctx, dgs, places, runs, shape, fr.FR_COVERAGE_U8, 4, True, CACHE, info=info)
+        desc = info["describe"]
+        twice = G.render_gray(ctx, dgs, places, runs, shape, fr.FR_COVERAGE_U8, 4, True, CACHE, times=2)
         assert np.array_equal(once, twice)
         try:
             ctx.set_option("graph", 1)
-            graphed, _ = _gray(ctx, dgs, places, runs, shape, 4, True, CACHE, times=2)
+            graphed = G.render_gray(ctx, dgs, places, runs, shape, fr.FR_COVERAGE_U8, 4, True, CACHE, times=2)
         finally:
             ctx.set_option("graph", 0)
         assert np.array_equal(graphed, once)
         # prepare with the glyph count, the mask kernel with the cell count, the composite with the instance count, in this order
         assert re.fullmatch(r"fr::prepare_kernel x(\d+); fr::glyph_mask_kernel<4, 0> x(\d+); fr::text_cached_kernel<4> x(\d+)", desc), desc
-        _, desc = _gray(ctx, dgs, places, runs, shape, 1, False, CACHE | FILL, fr.FR_MASK_NONZERO)
+        G.render_gray(ctx, dgs, places, runs, shape, fr.FR_MASK_NONZERO, 1, False, CACHE | FILL, info=info)
+        desc = info["describe"]
         assert re.fullmatch(r"fr::prepare_fill_kernel x\d+; fr::glyph_mask_kernel<1, 1> x\d+; fr::text_cached_kernel<1> x\d+", desc), desc
         with closing(fr.TextPlan(dgs, places, runs, fr.FR_COVERAGE_U8, 4, fr.FR_SAMPLE_CENTER, CACHE)) as plan:
             with closing(fr.TextPlan(dgs, places, runs)) as plain:
@@ -343,16 +311,17 @@ def test_every_placement_clipped_away(ctx, colour_case):
     away = places.copy()
     away["pen_x64"] += 64 * 5000
     with closing(fr.DeviceGlyphSet(ctx, gs)) as dgs:
-        got, desc = _gray(ctx, dgs, away, runs, shape, 4, True, CACHE)
-        want, plain = _gray(ctx, dgs, away, runs, shape, 4, True, 0)
-        assert desc == plain and np.array_equal(got, want)             # no cell: the plan it is without the flag
+        info, plain = {}, {}
+        got = G.render_gray(ctx, dgs, away, runs, shape, fr.FR_COVERAGE_U8, 4, True, CACHE, info=info)
+        want = G.render_gray(ctx, dgs, away, runs, shape, fr.FR_COVERAGE_U8, 4, True, 0, info=plain)
+        assert info["describe"] == plain["describe"] and np.array_equal(got, want)             # no cell: the plan it is without the flag
         for r in runs:
             assert not got[r["out_y"]:r["out_y"] + r["h"], r["out_x"]:r["out_x"] + r["w"]].any()
         assert (got == SENT).any()
-        got, _ = _rgba(ctx, dgs, away, opaque, runs, clears, np.full(shape + (4,), SENT, np.uint8), 4, True, CACHE)
+        got = G.render_rgba(ctx, dgs, away, opaque, runs, clears, np.full(shape + (4,), SENT, np.uint8), 4, True, CACHE)
         for k, r in enumerate(runs):
             assert (got[r["out_y"]:r["out_y"] + r["h"], r["out_x"]:r["out_x"] + r["w"]] == clears[k]).all()
-        got, _ = _rgba(ctx, dgs, away, opaque, runs, None, noise, 4, True, CACHE | LOAD)
+        got = G.render_rgba(ctx, dgs, away, opaque, runs, None, noise, 4, True, CACHE | LOAD)
         assert np.array_equal(got, noise)
 
 

@@ -11,9 +11,10 @@ import pytest
 
 import font_renderer_amd as fr
 import text_block_cases as B
+import text_gpu as G
+from text_gpu import BGRA, FILL, LOAD, SRGB
 
 pytestmark = pytest.mark.gpu
-FILL, SRGB, BGRA, LOAD = fr.FR_FILL_CONSISTENT, fr.FR_TEXT_SRGB, fr.FR_TEXT_BGRA, fr.FR_TEXT_LOAD
 FORMS = [False, True]                                          # fr_glyph_place, fr_glyph_place_ex
 
 
@@ -24,16 +25,10 @@ def _name(ex, srgb, load, n, fill, blend):
 
 def _run(ctx, case, n, flags, name):
     """render the case over a device copy of its start buffer, assert the kernel instance, compare every byte"""
-    import torch
+    info = {}
     with closing(fr.DeviceGlyphSet(ctx, B.glyph_set(case.glyphs))) as dgs:
-        with closing(fr.TextPlanRGBA(dgs, case.places, case.rgba, case.runs, case.clears, n, fr.FR_SAMPLE_CENTER, flags)) as plan:
-            buf = torch.from_numpy(np.ascontiguousarray(case.start)).to("cuda:0")
-            torch.cuda.synchronize()
-            plan.render(buf.data_ptr(), case.start.shape[1], case.start.shape[0])
-            ctx.sync()
-            desc = plan.describe()
-    assert name in desc, (name, desc)
-    got = buf.cpu().numpy()
+        got = G.render_rgba(ctx, dgs, case.places, case.rgba, case.runs, case.clears, case.start, n, True, flags, info=info)
+    assert name in info["describe"], (name, info)
     if not np.array_equal(got, case.want):
         bad = np.argwhere((got != case.want).any(axis=-1))
         y, x = bad[0]

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import font_renderer_amd as fr
+import text_gpu as G
 import text_instance_cases as T
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -30,28 +31,21 @@ def _golden(name):
         return json.load(f)
 
 
-def _render(ctx, dgs, k):
+def _describe_and_hash(ctx, dgs, k):
     """the key's plan over its start buffer -> (describe, SHA-256 of the whole buffer)"""
-    import torch
     places, runs, flags = T.places_of(k.form), T.runs(), T.flags_of(k)
     start = T.start_buffer(k)
+    info = {}
     if k.fam == 0:
-        plan = fr.TextPlan(dgs, places, runs, fr.FR_COVERAGE_U8, k.n, fr.FR_SAMPLE_CORNER, flags)
+        got = G.render_gray(ctx, dgs, places, runs, T.SHAPE, fr.FR_COVERAGE_U8, k.n, False, flags, sent=T.SENT, info=info)
     else:
         cols = T.TRANSLUCENT if k.blend else T.OPAQUE
-        plan = fr.TextPlanRGBA(dgs, places, cols, runs, None if k.fam in (3, 4) else T.CLEAR, k.n, fr.FR_SAMPLE_CORNER, flags)
-    with closing(plan):
-        buf = torch.from_numpy(start).to("cuda:0")
-        torch.cuda.synchronize()
-        plan.render(buf.data_ptr(), T.SHAPE[1], T.SHAPE[0])
-        ctx.sync()
-        desc = plan.describe()
-    got = buf.cpu().numpy()
+        got = G.render_rgba(ctx, dgs, places, cols, runs, None if k.fam in (3, 4) else T.CLEAR, start, k.n, False, flags, info=info)
     border = np.ones(T.SHAPE, bool)
     border[T.RUN[5]:T.RUN[5] + T.RUN[3], T.RUN[4]:T.RUN[4] + T.RUN[2]] = False
     assert np.array_equal(got[border], start[border]), (T.key_id(k), "a byte outside the run changed")
     assert not np.array_equal(got, start), T.key_id(k)
-    return desc, hashlib.sha256(got.tobytes()).hexdigest()
+    return info["describe"], hashlib.sha256(got.tobytes()).hexdigest()
 
 
 def _record(got):
@@ -80,7 +74,7 @@ def test_every_instance_of_the_group(ctx, ascii_set, group):
     with closing(fr.DeviceGlyphSet(ctx, T.glyph_set(ascii_set))) as dgs:
         for k in GROUPS[group]:
             assert T.kernel_name(k) in names and (not k.cached or T.mask_name(k) in names), T.key_id(k)
-            desc, sha = _render(ctx, dgs, k)
+            desc, sha = _describe_and_hash(ctx, dgs, k)
             assert desc == T.describe_of(k), (T.key_id(k), desc)
             got[T.key_id(k)] = sha
     if MINT:

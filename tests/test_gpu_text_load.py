@@ -1,5 +1,5 @@
 """FR_TEXT_LOAD text plans on the GPU (fr_text_plan_create_rgba with FR_TEXT_LOAD, include/fr_raster.h): drawn over
-random-noise destinations, byte for byte against the CPU twin of the definition (tests/text_load_ref.py), and the
+random-noise destinations, byte for byte against the CPU twin of the definition (tests/text_twin.py), and the
 consequences the definition states: untouched pixels keep their bytes, a uniform destination gives the clear-colour plan,
 and a second render composites over the first."""
 import ctypes as C
@@ -9,62 +9,17 @@ import numpy as np
 import pytest
 
 import font_renderer_amd as fr
-import text_load_ref as tl
-import text_ref
-import text_rgba_ref as tr
+import text_gpu as G
+import text_twin as tw
 from fixtures import load_font
 from font_renderer_amd import render_glyph as rg
 from font_renderer_amd.glyph import GlyphSet
 from font_renderer_amd.synth import synth_glyphset
+from text_gpu import BGRA, FILL, LOAD, SRGB, italic  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-FILL, SRGB, BGRA, LOAD = fr.FR_FILL_CONSISTENT, fr.FR_TEXT_SRGB, fr.FR_TEXT_BGRA, fr.FR_TEXT_LOAD
 PINK, RED, BLUE = (225, 105, 180, 255), (230, 20, 10, 255), (20, 40, 250, 255)
 CONFIGS = [(4, True, 0), (4, False, FILL), (2, True, FILL), (2, False, 0), (1, True, 0), (1, False, FILL)]
-
-
-def _phase(center):
-    return fr.FR_SAMPLE_CENTER if center else fr.FR_SAMPLE_CORNER
-
-
-def _noise(shape, seed):
-    return np.random.default_rng(seed).integers(0, 256, shape + (4,)).astype(np.uint8)
-
-
-def _render(ctx, dgs, places, cols, runs, dst, n=4, center=True, flags=LOAD, clears=None, plan_out=None, times=1):
-    """the plan rendered `times` times over a device copy of dst -> the output (host)"""
-    import torch
-    plan = fr.TextPlanRGBA(dgs, places, cols, runs, clears, n, _phase(center), flags)
-    buf = torch.from_numpy(np.ascontiguousarray(dst)).to("cuda:0")
-    torch.cuda.synchronize()
-    for _ in range(times):
-        plan.render(buf.data_ptr(), dst.shape[1], dst.shape[0])
-    ctx.sync()
-    if plan_out is not None:
-        plan_out.update(stats=plan.stats(), describe=plan.describe(), pixels=plan.pixels)
-    plan.close()
-    return buf.cpu().numpy()
-
-
-def _twin(gs, places, cols, runs, dst, n=4, center=True, flags=LOAD, which=None):
-    return tl.render_runs(gs, places, cols, runs, dst.copy(), n, center, bool(flags & FILL), bool(flags & SRGB),
-                          bool(flags & BGRA), which)
-
-
-def _kernel(n, flags, blend):
-    return f"fr::text_{'srgb' if flags & SRGB else 'rgba'}_load_kernel<{n}, {1 if flags & FILL else 0}, {blend}> x"
-
-
-ITALIC = ["ffi fj Tf ff", "Tjfyfgf jjj", "WoWfj"]
-
-
-@pytest.fixture(scope="module")
-def italic():
-    font = load_font("DejaVuSerif-Italic.ttf")
-    gs, places, runs, shape = tr.lines(font, ITALIC, 21, pad=2)
-    k0 = int(runs[2]["first"])                                  # a run of glyphs packed so close that their ink overlaps
-    places["pen_x64"][k0:k0 + 5] = places["pen_x64"][k0] + np.array([0, 213, 410, 641, 817])
-    return gs, places, runs, shape
 
 
 # ---- 1. overlapping instances over noise: UNORM and sRGB, opaque (BLEND = 0) and translucent (BLEND = 1), BGRA ---------
@@ -75,16 +30,16 @@ def test_overlapping_pairs_over_noise_equal_the_twin(ctx, italic, n, center, fil
     translucent = np.random.default_rng(n * 10 + fill).integers(0, 256, (len(places), 4)).astype(np.uint8)
     translucent[::5, 3] = 0
     translucent[1::5, 3] = 255
-    dst = _noise(shape, n + 7 * fill)
+    dst = G.noise(shape, n + 7 * fill)
     info = {}
     with closing(fr.DeviceGlyphSet(ctx, gs)) as dgs:
         for cols, blend in ((two, 0), (translucent, 1)):
             for space in (0, SRGB):
                 for order in (0, BGRA):
                     flags = LOAD | fill | space | order
-                    got = _render(ctx, dgs, places, cols, runs, dst, n, center, flags, plan_out=info)
-                    assert _kernel(n, flags, blend) in info["describe"], info
-                    assert np.array_equal(got, _twin(gs, places, cols, runs, dst, n, center, flags)), (n, center, flags)
+                    got = G.render_rgba(ctx, dgs, places, cols, runs, None, dst, n, center, flags, info=info)
+                    assert G.kernel_name("plain", flags, n, blend) in info["describe"], info
+                    assert np.array_equal(got, G.twin_rgba("plain", gs, places, cols, runs, None, dst, n, center, flags)), (n, center, flags)
                     assert not np.array_equal(got, dst)
 
 
@@ -102,11 +57,11 @@ def test_every_pen_fraction(ctx):
     places = rg.make_places(rows)
     runs = rg.make_runs([(k, 2, W, H, (k // 2 % 16) * (W + 1), (k // 32) * (H + 1), scale) for k in range(0, len(rows), 2)])
     cols = np.array([(200, 30, 60, 255 if k % 2 == 0 else 140) for k in range(len(rows))], np.uint8)
-    dst = _noise((8 * (H + 1), 16 * (W + 1)), 64)
+    dst = G.noise((8 * (H + 1), 16 * (W + 1)), 64)
     with closing(fr.DeviceGlyphSet(ctx, gs)) as dgs:
         for n, center, flags in [(4, True, LOAD), (1, False, LOAD | SRGB | BGRA), (2, True, LOAD | SRGB | FILL)]:
-            got = _render(ctx, dgs, places, cols, runs, dst, n, center, flags)
-            assert np.array_equal(got, _twin(gs, places, cols, runs, dst, n, center, flags)), (n, center, flags)
+            got = G.render_rgba(ctx, dgs, places, cols, runs, None, dst, n, center, flags)
+            assert np.array_equal(got, G.twin_rgba("plain", gs, places, cols, runs, None, dst, n, center, flags)), (n, center, flags)
 
 
 # ---- 3. clipping at all four edges; runs whose glyphs are all clipped away, and empty runs, touch nothing -----------------
@@ -132,21 +87,21 @@ def test_clipping_and_untouched_pixels(ctx):
     places, runs = rg.make_places(rows), rg.make_runs(runs)
     shape = (2 + 5 * (H + 3) + 14, 8 * (W + 4) + 9)
     rng = np.random.default_rng(6)
-    dst = _noise(shape, 11)
+    dst = G.noise(shape, 11)
     info = {}
     variants = ((np.array([PINK] * len(rows), np.uint8), LOAD), (rng.integers(0, 256, (len(rows), 4)).astype(np.uint8), LOAD | SRGB),
                 (rng.integers(0, 256, (len(rows), 4)).astype(np.uint8), LOAD | SRGB | BGRA | FILL))
     with closing(fr.DeviceGlyphSet(ctx, gs)) as dgs:
         for cols, flags in variants:
-            got = _render(ctx, dgs, places, cols, runs, dst, flags=flags, plan_out=info)
-            assert np.array_equal(got, _twin(gs, places, cols, runs, dst, flags=flags)), flags
+            got = G.render_rgba(ctx, dgs, places, cols, runs, None, dst, flags=flags, info=info)
+            assert np.array_equal(got, G.twin_rgba("plain", gs, places, cols, runs, None, dst, flags=flags)), flags
             assert info["pixels"] == sum(int(r["w"]) * int(r["h"]) for r in runs)
             # pixels outside every clipped cell (outside the runs too) keep their bytes
             cells = np.zeros(shape, bool)
             for r in runs:
                 for kk in range(int(r["first"]), int(r["first"]) + int(r["count"])):
                     pl = places[kk]
-                    c0, r0, cw, ch = text_ref.cell(gs.boxes[int(pl["glyph"])], r["scale"], int(pl["pen_x64"]), int(pl["pen_y"]))
+                    c0, r0, cw, ch = tw.plain_cell(gs.boxes[int(pl["glyph"])], r["scale"], int(pl["pen_x64"]), int(pl["pen_y"]))
                     x0, x1 = max(c0, 0), min(c0 + cw, int(r["w"]))
                     y0, y1 = max(r0, 0), min(r0 + ch, int(r["h"]))
                     if x0 < x1 and y0 < y1:
@@ -155,7 +110,7 @@ def test_clipping_and_untouched_pixels(ctx):
             assert (got[cells] != dst[cells]).any()
         # a plan of only the empty run and the all-clipped run launches nothing and leaves the buffer as it is
         only = rg.make_runs([tuple(runs[i]) for i in (len(runs) - 2, len(runs) - 1)])
-        got = _render(ctx, dgs, places, cols, only, dst, flags=LOAD, plan_out=info)
+        got = G.render_rgba(ctx, dgs, places, cols, only, None, dst, flags=LOAD, info=info)
         assert info["describe"] == "" and np.array_equal(got, dst), info
         # ... but checks its output as the same plan with a visible glyph does: NULL, too narrow, too short, misaligned
         need_x = max(int(r["out_x"]) + int(r["w"]) for r in only)
@@ -179,22 +134,22 @@ def test_large_glyph_and_tall_cell(ctx):
     tall, _ = font.glyphset([font.glyph_index(ord("l")), font.glyph_index(ord("|"))], skip_unsupported=False)
     gs = GlyphSet([big.glyph(0), tall.glyph(0), tall.glyph(1)])
     s_big = np.float32(0.05)
-    c0, r0, w0, h0 = text_ref.cell(gs.boxes[0], s_big, 0, 0)
+    c0, r0, w0, h0 = tw.plain_cell(gs.boxes[0], s_big, 0, 0)
     s_tall = np.float32(700) / np.float32(2048)                          # > 2048 sample rows at n = 4
-    c1, r1, w1, h1 = text_ref.cell(gs.boxes[1], s_tall, 0, 0)
+    c1, r1, w1, h1 = tw.plain_cell(gs.boxes[1], s_tall, 0, 0)
     assert 4 * h1 > 2048
     places = rg.make_places([(0, -64 * c0 + 37, -r0), (0, -64 * c0 + 64 * 9 + 5, -r0 + 4),
                              (1, -64 * c1 + 21, -r1), (2, -64 * c1 + 64 * 30 + 50, -r1)])
     runs = rg.make_runs([(0, 2, w0 + 12, h0 + 5, 0, 0, s_big), (2, 2, 120, h1 + 1, w0 + 13, 0, s_tall)])
-    dst = _noise((max(h0 + 5, h1 + 1) + 1, w0 + 13 + 121), 4)
+    dst = G.noise((max(h0 + 5, h1 + 1) + 1, w0 + 13 + 121), 4)
     cols = np.array([RED, (0, 255, 0, 100), BLUE, (255, 255, 0, 0)], np.uint8)
     info = {}
     with closing(fr.DeviceGlyphSet(ctx, gs)) as dgs:
         for n, center, flags in ((4, True, LOAD | SRGB), (2, False, LOAD | FILL | BGRA)):
-            got = _render(ctx, dgs, places, cols, runs, dst, n, center, flags, plan_out=info)
+            got = G.render_rgba(ctx, dgs, places, cols, runs, None, dst, n, center, flags, info=info)
             assert info["stats"] == {"jobs_cov4": 0, "jobs_general": 4}, info
-            assert _kernel(n, flags, 1) in info["describe"], info
-            assert np.array_equal(got, _twin(gs, places, cols, runs, dst, n, center, flags)), flags
+            assert G.kernel_name("plain", flags, n, 1) in info["describe"], info
+            assert np.array_equal(got, G.twin_rgba("plain", gs, places, cols, runs, None, dst, n, center, flags)), flags
 
 
 # ---- 5. consequences: a uniform destination is the clear-colour plan; two renders are the twin applied twice -------------
@@ -203,22 +158,22 @@ def test_uniform_destination_and_two_renders(ctx, italic, space):
     gs, places, runs, shape = italic
     cols = np.random.default_rng(3).integers(0, 256, (len(places), 4)).astype(np.uint8)
     clears = [(0, 0, 0, 0), (255, 255, 240, 255), (10, 60, 90, 128)]
-    base = _noise(shape, 21)
+    base = G.noise(shape, 21)
     with closing(fr.DeviceGlyphSet(ctx, gs)) as dgs:
         for n, center, fill in CONFIGS[:3]:
             for order in (0, BGRA):
                 flags = space | fill | order
-                plain = _render(ctx, dgs, places, cols, runs, base, n, center, flags, clears=clears)
+                plain = G.render_rgba(ctx, dgs, places, cols, runs, clears, base, n, center, flags)
                 d = base.copy()                                  # Q_r in every pixel of run r, in the stored byte order
                 for r, run in enumerate(runs):
                     d[run["out_y"]:run["out_y"] + run["h"], run["out_x"]:run["out_x"] + run["w"]] = \
                         np.array(clears[r], np.uint8)[[2, 1, 0, 3] if order else [0, 1, 2, 3]]
-                got = _render(ctx, dgs, places, cols, runs, d, n, center, flags | LOAD)
+                got = G.render_rgba(ctx, dgs, places, cols, runs, None, d, n, center, flags | LOAD)
                 assert np.array_equal(got, plain), (n, center, flags)
-        noise = _noise(shape, 22)
-        twice = _render(ctx, dgs, places, cols, runs, noise, 4, True, LOAD | space, times=2)
-        once = _twin(gs, places, cols, runs, noise, 4, True, LOAD | space)
-        assert np.array_equal(twice, _twin(gs, places, cols, runs, once, 4, True, LOAD | space))
+        noise = G.noise(shape, 22)
+        twice = G.render_rgba(ctx, dgs, places, cols, runs, None, noise, 4, True, LOAD | space, times=2)
+        once = G.twin_rgba("plain", gs, places, cols, runs, None, noise, 4, True, LOAD | space)
+        assert np.array_equal(twice, G.twin_rgba("plain", gs, places, cols, runs, None, once, 4, True, LOAD | space))
         assert not np.array_equal(twice, once)
 
 
@@ -229,13 +184,13 @@ def test_many_runs_and_graph(ctx):
     rng = np.random.default_rng(2026)
     alphabet = np.array(list("abcdefghijklmnopqrstuvwxyzABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789ffjT.,;!? "))
     strings = ["".join(rng.choice(alphabet, int(rng.integers(3, 24)))) for _ in range(1500)]
-    gs, places, runs, shape = tr.lines(font, strings, 14, pad=1)
+    gs, places, runs, shape = tw.lines(font, strings, 14, pad=1)
     cols = np.array([PINK if s[:k].count(" ") % 2 == 0 else (40, 200, 90, 255) for s in strings for k in range(len(s))], np.uint8)
     cols[len(cols) // 2:, 3] = 150
     which = sorted(rng.choice(len(runs), 30, replace=False).tolist()) + [len(runs) - 1]
     with closing(fr.DeviceGlyphSet(ctx, gs)) as dgs:
-        a, b = _noise(shape, 1), _noise(shape, 2)
-        want = {k: _twin(gs, places, cols, runs, d, 4, True, LOAD | SRGB, which=which) for k, d in (("a", a), ("b", b))}
+        a, b = G.noise(shape, 1), G.noise(shape, 2)
+        want = {k: G.twin_rgba("plain", gs, places, cols, runs, None, d, 4, True, LOAD | SRGB, which=which) for k, d in (("a", a), ("b", b))}
         plan = fr.TextPlanRGBA(dgs, places, cols, runs, None, 4, fr.FR_SAMPLE_CENTER, LOAD | SRGB)
         try:
             ctx.set_option("graph", 1)
@@ -256,7 +211,7 @@ def test_many_runs_and_graph(ctx):
                 run = runs[r]
                 sl = np.s_[run["out_y"]:run["out_y"] + run["h"], run["out_x"]:run["out_x"] + run["w"]]
                 assert np.array_equal(got[k][sl], want[k][sl]), (k, r)
-        assert np.array_equal(got["a"], _render(ctx, dgs, places, cols, runs, a, 4, True, LOAD | SRGB))
+        assert np.array_equal(got["a"], G.render_rgba(ctx, dgs, places, cols, runs, None, a, 4, True, LOAD | SRGB))
 
 
 # ---- 7. validation and describe strings -----------------------------------------------------------------------------------
@@ -329,7 +284,7 @@ def _draw_twin(font, text, size, img, x, y, cols, n=4, center=True, srgb=False, 
     places = rg.make_places([(local[int(g)], x64 + int(p), y) for g, p in zip(gi, pen)])
     scale = np.float32(size) / np.float32(font.information.units_per_em)
     run = rg.make_runs([(0, len(places), img.shape[1], img.shape[0], 0, 0, scale)])[0]
-    return tl.render_run(gs, places, np.asarray(cols, np.uint8), run, img, n, center, False, srgb, bgr)
+    return tw.rgba_render_run("plain", gs, places, np.asarray(cols, np.uint8), run, None, img, n, center, False, srgb, bgr)
 
 
 def test_draw_text_rgba(ctx):
@@ -337,7 +292,7 @@ def test_draw_text_rgba(ctx):
     text = "Tffj a red word"
     hl = [(255, 0, 0, 255) if 6 <= k < 9 else (0, 0, 0, 160) for k in range(len(text))]
     for k, (x, y) in enumerate([(-20.3, 40), (90.71875, 40), (30.5, 9), (30.0, 70), (2.015625, 33)]):   # off each edge
-        base = _noise((60, 150), 30 + k)
+        base = G.noise((60, 150), 30 + k)
         im = fr.RGBA(150, 60, base.reshape(-1, 4).copy())
         assert fr.draw_text_rgba(im, font, text, 27, x, y, colors=hl, ctx=ctx) is im
         assert np.array_equal(im.as_3d(), _draw_twin(font, text, 27, base, x, y, hl)), (x, y)
@@ -345,7 +300,7 @@ def test_draw_text_rgba(ctx):
         im = fr.RGBA(150, 60, base.reshape(-1, 4).copy())
         fr.draw_text_rgba(im, font, text, 27, x, y, samples_per_axis=2, phase=fr.FR_SAMPLE_CORNER, srgb=True, bgra=True, ctx=ctx)
         assert np.array_equal(im.as_3d(), _draw_twin(font, text, 27, base, x, y, [PINK] * len(text), 2, False, True, True))
-    im = fr.RGBA(150, 60, _noise((60, 150), 3).reshape(-1, 4))
+    im = fr.RGBA(150, 60, G.noise((60, 150), 3).reshape(-1, 4))
     before = im.data.copy()
     fr.draw_text_rgba(im, font, "", 27, 5, 30, ctx=ctx)                             # nothing to draw
     fr.draw_text_rgba(im, font, "Tf", 27, 400, 30, ctx=ctx)                          # all of it outside the image
@@ -355,7 +310,7 @@ def test_draw_text_rgba(ctx):
 
 def test_draw_text_rgba_on_a_large_frame(ctx):
     font = load_font("DejaVuSans.ttf", allow_hinted=True)
-    base = _noise((2160, 3840), 99)
+    base = G.noise((2160, 3840), 99)
     im = fr.RGBA(3840, 2160, base.reshape(-1, 4).copy())
     text = "Caption on a 3840 x 2160 frame"
     fr.draw_text_rgba(im, font, text, 32, 1700.25, 2000, color=(255, 255, 255, 220), ctx=ctx)

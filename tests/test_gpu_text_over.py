@@ -1,6 +1,6 @@
 """FR_TEXT_OVER text plans on the GPU (include/fr_raster.h): source-over alpha in every RGBA kernel family, placement form
 and the mask cache.  The expected image never comes from the code under test: it is the twin assembled by
-tests/text_over_ref.py from the twins of the plan without the flag, the exact cases of tests/text_over_cases.py, or the
+tests/text_twin.py from the twins of the plan without the flag, the exact cases of tests/text_over_cases.py, or the
 definition in integers; the plan without the flag on the GPU is a second witness for R, G, B.  Outputs are
 sentinel-filled (or noise under LOAD) and the whole array is compared."""
 import math
@@ -12,46 +12,17 @@ import pytest
 
 import font_renderer_amd as fr
 import text_block_cases as B
+import text_gpu as G
 import text_over_cases as OC
-import text_over_ref as tov
+import text_twin as tw
 from fixtures import load_font
 from font_renderer_amd import _lib as L
 from font_renderer_amd import render_glyph as rg
+from text_gpu import BGRA, CACHE, FILL, LOAD, OVER, SRGB
 
 pytestmark = pytest.mark.gpu
 SENT = 0x5b
-FILL, SRGB, BGRA, LOAD, CACHE, OVER = (fr.FR_FILL_CONSISTENT, fr.FR_TEXT_SRGB, fr.FR_TEXT_BGRA, fr.FR_TEXT_LOAD, fr.FR_TEXT_CACHE,
-                                       fr.FR_TEXT_OVER)
 GRIDS = [(4, True, 0), (2, False, FILL), (1, True, 0)]                  # (n, centre phase, fill)
-FORM_NAME = {"plain": "", "ex": "place_", "affine": "affine_"}
-
-
-def _phase(center):
-    return fr.FR_SAMPLE_CENTER if center else fr.FR_SAMPLE_CORNER
-
-
-def _rgba(ctx, dgs, places, cols, runs, clears, dst, n=4, center=True, flags=0, times=1, info=None):
-    """an RGBA plan over a fresh device copy of dst ((rows, cols, 4) u8: sentinel, or noise under LOAD) -> (bytes, describe)"""
-    import torch
-    with closing(fr.TextPlanRGBA(dgs, places, cols, runs, clears, n, _phase(center), flags)) as plan:
-        buf = torch.from_numpy(np.ascontiguousarray(dst)).to("cuda:0")
-        torch.cuda.synchronize()
-        for _ in range(times):
-            plan.render(buf.data_ptr(), dst.shape[1], dst.shape[0])
-        ctx.sync()
-        desc = plan.describe()
-        if info is not None:
-            info.update(pixels=plan.pixels, stats=plan.stats())
-    return buf.cpu().numpy(), desc
-
-
-def _kernel(form, flags, n, blend):
-    return "fr::text_%s%s%skernel<%d, %d, %d> x" % (FORM_NAME[form], "srgb_" if flags & SRGB else "rgba_", "load_" if flags & LOAD else "",
-                                                     n, 1 if flags & FILL else 0, blend)
-
-
-def _cached_kernel(flags, n, blend):
-    return "fr::text_cached_%s%skernel<%d, %d> x" % ("srgb_" if flags & SRGB else "rgba_", "load_" if flags & LOAD else "", n, blend)
 
 
 @pytest.fixture(scope="module")
@@ -94,15 +65,15 @@ def _twin(case, form, n, center, fill, space, load, bgra):
     key = (form, n, center, fill, space, load, bgra)
     if key not in _TWINS:
         start = case["noise"] if load else case["sent"]
-        img = tov.render_runs(form, case["gs"], case["places"][form], case["translucent"], case["runs"], None if load else case["clears"],
-                              start, n, center, bool(fill), bool(space), bool(bgra), bool(load))
+        img = G.twin_rgba(form, case["gs"], case["places"][form], case["translucent"], case["runs"], None if load else case["clears"],
+                          start, n, center, fill | space | load | bgra | OVER)
         img.setflags(write=False)
         _TWINS[key] = img
     return _TWINS[key]
 
 
 # ---- 1. families: every space x start x placement form, three grids -------------------------------------------------------------
-@pytest.mark.parametrize("form", tov.FORMS)
+@pytest.mark.parametrize("form", tw.FORMS)
 @pytest.mark.parametrize("load", [0, LOAD], ids=["clear", "load"])
 @pytest.mark.parametrize("space", [0, SRGB], ids=["unorm", "srgb"])
 def test_families_equal_the_assembled_twin(ctx, colour_case, space, load, form):
@@ -112,12 +83,13 @@ def test_families_equal_the_assembled_twin(ctx, colour_case, space, load, form):
     with closing(fr.DeviceGlyphSet(ctx, case["gs"])) as dgs:
         for n, center, fill in GRIDS:
             flags = space | load | fill
-            got, desc = _rgba(ctx, dgs, places, cols, runs, clears, dst, n, center, flags | OVER)
-            assert _kernel(form, flags, n, 2) in desc, desc
+            info = {}
+            got = G.render_rgba(ctx, dgs, places, cols, runs, clears, dst, n, center, flags | OVER, info=info)
+            assert G.kernel_name(form, flags, n, 2) in info["describe"], info
             want = _twin(case, form, n, center, fill, space, load, 0)
             assert np.array_equal(got, want), (space, load, form, n, np.argwhere(got != want)[:8].tolist())
-            plain, pdesc = _rgba(ctx, dgs, places, cols, runs, clears, dst, n, center, flags)
-            assert _kernel(form, flags, n, 1) in pdesc, pdesc
+            plain = G.render_rgba(ctx, dgs, places, cols, runs, clears, dst, n, center, flags, info=info)
+            assert G.kernel_name(form, flags, n, 1) in info["describe"], info
             assert np.array_equal(got[..., :3], plain[..., :3]) and (got[..., 3] != plain[..., 3]).any()
             assert not np.array_equal(got, dst)
 
@@ -129,11 +101,12 @@ def test_bgra_once_per_space(ctx, colour_case, space):
         for form, load in (("plain", 0), ("ex", LOAD)):
             clears, dst = (None, case["noise"]) if load else (case["clears"], case["sent"])
             flags = space | load | BGRA
-            got, desc = _rgba(ctx, dgs, case["places"][form], case["translucent"], case["runs"], clears, dst, 4, True, flags | OVER)
-            assert _kernel(form, flags, 4, 2) in desc, desc
+            info = {}
+            got = G.render_rgba(ctx, dgs, case["places"][form], case["translucent"], case["runs"], clears, dst, 4, True, flags | OVER, info=info)
+            assert G.kernel_name(form, flags, 4, 2) in info["describe"], info
             want = _twin(case, form, 4, True, 0, space, load, BGRA)
             assert np.array_equal(got, want), (space, form, np.argwhere(got != want)[:8].tolist())
-            swapped, _ = _rgba(ctx, dgs, case["places"][form], case["translucent"], case["runs"], clears, dst, 4, True, (flags & ~BGRA) | OVER)
+            swapped = G.render_rgba(ctx, dgs, case["places"][form], case["translucent"], case["runs"], clears, dst, 4, True, (flags & ~BGRA) | OVER)
             assert not np.array_equal(got, swapped) and np.array_equal(got[..., 3], swapped[..., 3])
 
 
@@ -148,10 +121,12 @@ def test_cache_equals_the_plan_without_it(ctx, colour_case, space, load, form):
     with closing(fr.DeviceGlyphSet(ctx, case["gs"])) as dgs:
         for n, center, fill in GRIDS:
             flags = space | load | fill | OVER
-            got, desc = _rgba(ctx, dgs, places, cols, runs, clears, dst, n, center, flags | CACHE)
-            assert _cached_kernel(flags, n, 2) + "12" in desc and f"fr::glyph_mask_kernel<{n}, {1 if fill else 0}> x" in desc, desc
-            want, plain = _rgba(ctx, dgs, places, cols, runs, clears, dst, n, center, flags)
-            assert "cached" not in plain
+            info, plain = {}, {}
+            got = G.render_rgba(ctx, dgs, places, cols, runs, clears, dst, n, center, flags | CACHE, info=info)
+            desc = info["describe"]
+            assert G.cached_kernel_name(flags, n, 2) + "12" in desc and f"fr::glyph_mask_kernel<{n}, {1 if fill else 0}> x" in desc, desc
+            want = G.render_rgba(ctx, dgs, places, cols, runs, clears, dst, n, center, flags, info=plain)
+            assert "cached" not in plain["describe"]
             assert np.array_equal(got, want), (space, load, form, n)
             assert np.array_equal(got, _twin(case, form, n, center, fill, space, load, 0))
 
@@ -166,21 +141,24 @@ def test_cache_stays_invalid_for_affine(ctx, colour_case):
 
 
 # ---- 3. opaque colours: the plan without the flag ------------------------------------------------------------------------------------
-@pytest.mark.parametrize("form", tov.FORMS)
+@pytest.mark.parametrize("form", tw.FORMS)
 def test_opaque_is_untouched(ctx, colour_case, form):
     case = colour_case
     places, cols, runs = case["places"][form], case["opaque"], case["runs"]
     with closing(fr.DeviceGlyphSet(ctx, case["gs"])) as dgs:
         for flags in (0, SRGB, LOAD, SRGB | LOAD):
             clears, dst = (None, case["noise"]) if flags & LOAD else (case["clears"], case["sent"])
-            got, desc = _rgba(ctx, dgs, places, cols, runs, clears, dst, 4, True, flags | OVER)
-            want, plain = _rgba(ctx, dgs, places, cols, runs, clears, dst, 4, True, flags)
-            assert desc == plain and _kernel(form, flags, 4, 0) in desc, (desc, plain)
+            info, plain_info = {}, {}
+            got = G.render_rgba(ctx, dgs, places, cols, runs, clears, dst, 4, True, flags | OVER, info=info)
+            want = G.render_rgba(ctx, dgs, places, cols, runs, clears, dst, 4, True, flags, info=plain_info)
+            desc, plain = info["describe"], plain_info["describe"]
+            assert desc == plain and G.kernel_name(form, flags, 4, 0) in desc, (desc, plain)
             assert np.array_equal(got, want) and not np.array_equal(got, dst)
         if form != "affine":
-            got, desc = _rgba(ctx, dgs, places, cols, runs, case["clears"], case["sent"], 2, False, CACHE | OVER | FILL)
-            want, plain = _rgba(ctx, dgs, places, cols, runs, case["clears"], case["sent"], 2, False, CACHE | FILL)
-            assert desc == plain and _cached_kernel(0, 2, 0) in desc and np.array_equal(got, want)
+            got = G.render_rgba(ctx, dgs, places, cols, runs, case["clears"], case["sent"], 2, False, CACHE | OVER | FILL, info=info)
+            want = G.render_rgba(ctx, dgs, places, cols, runs, case["clears"], case["sent"], 2, False, CACHE | FILL, info=plain_info)
+            desc, plain = info["describe"], plain_info["describe"]
+            assert desc == plain and G.cached_kernel_name(0, 2, 0) in desc and np.array_equal(got, want)
 
 
 # ---- 4. every (a, A) on the device ---------------------------------------------------------------------------------------------------
@@ -189,9 +167,10 @@ def test_every_alpha_pair(ctx, srgb):
     case = OC.every_alpha_pair_case(srgb)
     flags = LOAD | FILL | (SRGB if srgb else 0)
     with closing(fr.DeviceGlyphSet(ctx, B.glyph_set(case.glyphs))) as dgs:
-        got, desc = _rgba(ctx, dgs, case.places, case.rgba, case.runs, None, case.start, 1, True, flags | OVER)
-        plain, _ = _rgba(ctx, dgs, case.places, case.rgba, case.runs, None, case.start, 1, True, flags)
-    assert _kernel("plain", flags, 1, 2) + "256" in desc, desc
+        info = {}
+        got = G.render_rgba(ctx, dgs, case.places, case.rgba, case.runs, None, case.start, 1, True, flags | OVER, info=info)
+        plain = G.render_rgba(ctx, dgs, case.places, case.rgba, case.runs, None, case.start, 1, True, flags)
+    assert G.kernel_name("plain", flags, 1, 2) + "256" in info["describe"], info
     bad = np.argwhere(got[..., 3] != case.want_alpha)
     assert not len(bad), (len(bad), bad[:8].tolist())
     assert np.array_equal(got[..., :3], plain[..., :3])
@@ -207,12 +186,13 @@ def test_exact_partial_coverage(ctx, n, ex, srgb):
     case = OC.partial_cover_case(n, ex, srgb)
     flags = (SRGB if srgb else 0) | FILL
     with closing(fr.DeviceGlyphSet(ctx, B.glyph_set(case.glyphs))) as dgs:
-        got, desc = _rgba(ctx, dgs, case.places, case.rgba, case.runs, case.clears, case.start, n, True, flags | OVER)
-        assert _kernel("ex" if ex else "plain", flags, n, 2) in desc, desc
+        info = {}
+        got = G.render_rgba(ctx, dgs, case.places, case.rgba, case.runs, case.clears, case.start, n, True, flags | OVER, info=info)
+        assert G.kernel_name("ex" if ex else "plain", flags, n, 2) in info["describe"], info
         assert np.array_equal(got, case.want), (n, ex, srgb, np.argwhere(got != case.want)[:8].tolist())
         if not ex:
-            cached, desc = _rgba(ctx, dgs, case.places, case.rgba, case.runs, case.clears, case.start, n, True, flags | OVER | CACHE)
-            assert _cached_kernel(flags, n, 2) in desc and np.array_equal(cached, case.want)
+            cached = G.render_rgba(ctx, dgs, case.places, case.rgba, case.runs, case.clears, case.start, n, True, flags | OVER | CACHE, info=info)
+            assert G.cached_kernel_name(flags, n, 2) in info["describe"] and np.array_equal(cached, case.want)
 
 
 # ---- 6. an opaque picture stays opaque ----------------------------------------------------------------------------------------------
@@ -248,7 +228,7 @@ def test_opaque_background_stays_opaque(ctx, srgb):
 def test_where_the_flag_is_not_taken(ctx, colour_case):
     case = colour_case
     with closing(fr.DeviceGlyphSet(ctx, case["gs"])) as dgs:
-        for form in tov.FORMS:
+        for form in tw.FORMS:
             with pytest.raises(fr.FrError) as e:
                 fr.TextPlan(dgs, case["places"][form], case["runs"], fr.FR_COVERAGE_U8, 4, fr.FR_SAMPLE_CENTER, OVER)
             assert e.value.code == -1, form
@@ -275,21 +255,21 @@ def test_repeat_graph_pixels_and_stats(ctx, colour_case):
     places, cols, runs = case["places"]["plain"], case["translucent"], case["runs"]
     with closing(fr.DeviceGlyphSet(ctx, case["gs"])) as dgs:
         info, plain_info = {}, {}
-        once, _ = _rgba(ctx, dgs, places, cols, runs, case["clears"], case["sent"], 4, True, OVER, info=info)
-        twice, _ = _rgba(ctx, dgs, places, cols, runs, case["clears"], case["sent"], 4, True, OVER, times=2)
+        once = G.render_rgba(ctx, dgs, places, cols, runs, case["clears"], case["sent"], 4, True, OVER, info=info)
+        twice = G.render_rgba(ctx, dgs, places, cols, runs, case["clears"], case["sent"], 4, True, OVER, times=2)
         assert np.array_equal(once, twice)                            # a clear colour: idempotent
-        _rgba(ctx, dgs, places, cols, runs, case["clears"], case["sent"], 4, True, 0, info=plain_info)
-        assert info == plain_info and info["pixels"] == 2 * 200 * 27
-        one, _ = _rgba(ctx, dgs, places, cols, runs, None, case["noise"], 4, True, OVER | LOAD)
-        two, _ = _rgba(ctx, dgs, places, cols, runs, None, case["noise"], 4, True, OVER | LOAD, times=2)
-        again, _ = _rgba(ctx, dgs, places, cols, runs, None, one, 4, True, OVER | LOAD)
+        G.render_rgba(ctx, dgs, places, cols, runs, case["clears"], case["sent"], 4, True, 0, info=plain_info)
+        assert all(info[k] == plain_info[k] for k in ("pixels", "stats")) and info["pixels"] == 2 * 200 * 27
+        one = G.render_rgba(ctx, dgs, places, cols, runs, None, case["noise"], 4, True, OVER | LOAD)
+        two = G.render_rgba(ctx, dgs, places, cols, runs, None, case["noise"], 4, True, OVER | LOAD, times=2)
+        again = G.render_rgba(ctx, dgs, places, cols, runs, None, one, 4, True, OVER | LOAD)
         assert np.array_equal(two, again) and not np.array_equal(two, one)          # LOAD: the second render composites over the first
         a0, a1, a2 = (v[..., 3].astype(np.int64) for v in (case["noise"], one, two))
         assert (a1 >= a0).all() and (a2 >= a1).all() and (a2 > a1).any()           # alpha rises monotonically
         try:
             ctx.set_option("graph", 1)
-            graphed, _ = _rgba(ctx, dgs, places, cols, runs, case["clears"], case["sent"], 4, True, OVER, times=2)
-            graphed_cache, _ = _rgba(ctx, dgs, places, cols, runs, case["clears"], case["sent"], 4, True, OVER | CACHE, times=2)
+            graphed = G.render_rgba(ctx, dgs, places, cols, runs, case["clears"], case["sent"], 4, True, OVER, times=2)
+            graphed_cache = G.render_rgba(ctx, dgs, places, cols, runs, case["clears"], case["sent"], 4, True, OVER | CACHE, times=2)
         finally:
             ctx.set_option("graph", 0)
         assert np.array_equal(graphed, once) and np.array_equal(graphed_cache, once)

@@ -1,135 +1,62 @@
 """Text plans of fr_glyph_place_ex placements on the GPU (fr_text_plan_create_ex / fr_text_plan_create_rgba_ex,
 include/fr_raster.h): byte for byte against the old entry points where the parameters are degenerate, and against the
-CPU twin of the definition (tests/text_place_ref.py) everywhere else.  Outputs are sentinel-filled (or, for
+CPU twin of the definition (tests/text_twin.py) everywhere else.  Outputs are sentinel-filled (or, for
 FR_TEXT_LOAD, noise-filled) device buffers: bytes outside every run must keep what they held.  Every comparison is
 np.array_equal: the feature has no tolerance."""
 import ctypes as C
-import re
 from contextlib import closing
 
 import numpy as np
 import pytest
 
 import font_renderer_amd as fr
-import text_place_ref as tp
-import text_ref
-import text_rgba_ref as tr
+import text_gpu as G
+import text_twin as tw
 from fixtures import load_font
 from font_renderer_amd import render_glyph as rg
 from font_renderer_amd import text as T
 from font_renderer_amd.glyph import GlyphSet
 from font_renderer_amd.synth import synth_glyphset
+from text_gpu import BGRA, FILL, LOAD, SRGB
 
 pytestmark = pytest.mark.gpu
 SENT = 0x5b
-FILL, SRGB, BGRA, LOAD = fr.FR_FILL_CONSISTENT, fr.FR_TEXT_SRGB, fr.FR_TEXT_BGRA, fr.FR_TEXT_LOAD
 STRINGS = ["ffi fj Tf ff", "Tjfyfgf jjj", "Wavy /// fff", "ƒ∫ fî T,"]           # tests/test_gpu_text.py's STRINGS
 SLANTS = [-1.0, -0.36, -0.2, 0.0, 0.2, 0.36397, 1.0, 4.0]
 CONFIGS = [(4, True, 0), (4, False, FILL), (2, True, FILL), (2, False, 0), (1, True, 0), (1, False, FILL),
            (4, True, FILL), (4, False, 0), (2, True, 0), (2, False, FILL), (1, True, FILL), (1, False, 0)]
 
 
-def _phase(center):
-    return fr.FR_SAMPLE_CENTER if center else fr.FR_SAMPLE_CORNER
-
-
-def _noise(shape, seed):
-    return np.random.default_rng(seed).integers(0, 256, shape + (4,)).astype(np.uint8)
-
-
-def _info(plan, plan_out):
-    if plan_out is not None:
-        plan_out.update(stats=plan.stats(), describe=plan.describe(), pixels=plan.pixels)
-
-
-def _render(ctx, dgs, places, runs, shape, mode=fr.FR_COVERAGE_U8, n=4, center=True, flags=0, plan_out=None):
-    """a coverage / mask plan of either placement form into a sentinel-filled buffer"""
-    import torch
-    with closing(fr.TextPlan(dgs, places, runs, mode, n, _phase(center), flags)) as plan:
-        buf = torch.full(shape, SENT, dtype=torch.uint8, device="cuda:0")
-        torch.cuda.synchronize()
-        plan.render(buf.data_ptr(), shape[1], shape[0])
-        ctx.sync()
-        _info(plan, plan_out)
-    return buf.cpu().numpy()
-
-
-def _render_rgba(ctx, dgs, places, cols, runs, clears, dst, n=4, center=True, flags=0, plan_out=None):
-    """an RGBA plan of either placement form over a device copy of dst ((rows, cols, 4) u8: sentinel, or noise for LOAD)"""
-    import torch
-    with closing(fr.TextPlanRGBA(dgs, places, cols, runs, clears, n, _phase(center), flags)) as plan:
-        buf = torch.from_numpy(np.ascontiguousarray(dst)).to("cuda:0")
-        torch.cuda.synchronize()
-        plan.render(buf.data_ptr(), dst.shape[1], dst.shape[0])
-        ctx.sync()
-        _info(plan, plan_out)
-    return buf.cpu().numpy()
-
-
-def _sent4(shape):
-    return np.full(shape + (4,), SENT, np.uint8)
-
-
-def _twin(gs, places, runs, shape, n=4, center=True, fill=False):
-    return tp.render_runs(gs, places, runs, np.full(shape, SENT, np.uint8), n, center, fill)
-
-
-def _twin_rgba(gs, places, cols, runs, clears, dst, n=4, center=True, flags=0):
-    return tp.rgba_render_runs(gs, places, cols, runs, clears, dst.copy(), n, center, bool(flags & FILL), bool(flags & SRGB),
-                               bool(flags & BGRA), bool(flags & LOAD))
-
-
-def _degenerate(places, scale=0.0):
-    return rg.make_places_ex([(int(p["glyph"]), int(p["pen_x64"]), 64 * int(p["pen_y"]), scale, 0.0) for p in places])
-
-
-def _colours(n, seed, opaque):
-    c = np.random.default_rng(seed).integers(0, 256, (n, 4)).astype(np.uint8)
-    if opaque:
-        c[:, 3] = 255
-    else:
-        c[::3, 3] = 255                                                   # a mix: opaque, translucent, and one clear glyph
-        c[1, 3] = 0
-    return c
-
-
-def _count(describe, kernel):
-    """the count fr_plan_describe reports for `kernel`"""
-    m = re.search(re.escape(kernel) + r" x(\d+)", describe)
-    assert m, (kernel, describe)
-    return int(m.group(1))
-
-
 # ---- 1. old and new entry points agree -----------------------------------------------------------------------------------
 @pytest.mark.parametrize("font_size,n,center", [(16, 4, True), (23, 2, False), (40, 1, True), (11, 4, False)])
 def test_degenerate_placements_equal_the_old_entry_points(ctx, font_size, n, center):
     font = load_font("DejaVuSerif-Italic.ttf")
-    gs, places, runs, shape = tr.lines(font, STRINGS, font_size, pad=2)
+    gs, places, runs, shape = tw.lines(font, STRINGS, font_size, pad=2)
     assert any(p % 64 for p in places["pen_x64"])
-    clears = _colours(len(runs), 5, False)
+    clears = G.colours(len(runs), 5, False)
     with closing(fr.DeviceGlyphSet(ctx, gs)) as dgs:
-        for ex in (_degenerate(places), _degenerate(places, float(runs[0]["scale"]))):
+        for ex in (G.degenerate(places), G.degenerate(places, float(runs[0]["scale"]))):
             for fill in (0, FILL):
                 old, new = {}, {}
-                a = _render(ctx, dgs, places, runs, shape, fr.FR_COVERAGE_U8, n, center, fill, old)
-                b = _render(ctx, dgs, ex, runs, shape, fr.FR_COVERAGE_U8, n, center, fill, new)
+                a = G.render_gray(ctx, dgs, places, runs, shape, fr.FR_COVERAGE_U8, n, center, fill, info=old)
+                b = G.render_gray(ctx, dgs, ex, runs, shape, fr.FR_COVERAGE_U8, n, center, fill, info=new)
                 assert np.array_equal(a, b) and (a != SENT).any(), ("coverage", fill)
                 assert "fr::text_kernel<" in old["describe"] and "fr::text_place_kernel<" in new["describe"], (old, new)
                 assert old["stats"] == new["stats"] and old["pixels"] == new["pixels"]
                 if n == 1:
-                    a = _render(ctx, dgs, places, runs, shape, fr.FR_MASK_NONZERO, 1, center, fill)
-                    b = _render(ctx, dgs, ex, runs, shape, fr.FR_MASK_NONZERO, 1, center, fill)
+                    a = G.render_gray(ctx, dgs, places, runs, shape, fr.FR_MASK_NONZERO, 1, center, fill)
+                    b = G.render_gray(ctx, dgs, ex, runs, shape, fr.FR_MASK_NONZERO, 1, center, fill)
                     assert np.array_equal(a, b), ("mask", fill)
                 for opaque in (True, False):
-                    cols = _colours(len(places), font_size + opaque, opaque)
+                    cols = G.colours(len(places), font_size + opaque, opaque)
                     for flags in (0, SRGB, BGRA, SRGB | BGRA):
-                        a = _render_rgba(ctx, dgs, places, cols, runs, clears, _sent4(shape), n, center, flags | fill)
-                        b = _render_rgba(ctx, dgs, ex, cols, runs, clears, _sent4(shape), n, center, flags | fill)
+                        a = G.render_rgba(ctx, dgs, places, cols, runs, clears, G.sent4(shape, SENT), n, center, flags | fill)
+                        b = G.render_rgba(ctx, dgs, ex, cols, runs, clears, G.sent4(shape, SENT), n, center, flags | fill)
                         assert np.array_equal(a, b), ("rgba", opaque, flags, fill)
-                    dst = _noise(shape, font_size)
+                    dst = G.noise(shape, font_size)
                     for flags in (LOAD, LOAD | SRGB, LOAD | BGRA):
-                        a = _render_rgba(ctx, dgs, places, cols, runs, None, dst, n, center, flags | fill)
-                        b = _render_rgba(ctx, dgs, ex, cols, runs, None, dst, n, center, flags | fill)
+                        a = G.render_rgba(ctx, dgs, places, cols, runs, None, dst, n, center, flags | fill)
+                        b = G.render_rgba(ctx, dgs, ex, cols, runs, None, dst, n, center, flags | fill)
                         assert np.array_equal(a, b) and not np.array_equal(a, dst), ("load", opaque, flags, fill)
 
 
@@ -138,7 +65,7 @@ def _random_lines(seed, size):
     """the strings' lines with every placement given its own baseline fraction, scale (a quarter to four times the run's)
     and slant; the runs grow by a margin so that the moved glyphs mostly stay inside, and some are clipped"""
     font = load_font("DejaVuSerif-Italic.ttf")
-    gs, places, runs, shape = tr.lines(font, STRINGS, size, pad=2)
+    gs, places, runs, shape = tw.lines(font, STRINGS, size, pad=2)
     rng = np.random.default_rng(seed)
     rows = []
     for k, p in enumerate(places):
@@ -169,31 +96,31 @@ def test_random_placements_equal_the_twin(ctx, seed, size):
     with closing(fr.DeviceGlyphSet(ctx, gs)) as dgs:
         for n, center, fill in CONFIGS:
             info = {}
-            got = _render(ctx, dgs, places, runs, shape, fr.FR_COVERAGE_U8, n, center, fill, info)
+            got = G.render_gray(ctx, dgs, places, runs, shape, fr.FR_COVERAGE_U8, n, center, fill, info=info)
             assert f"fr::text_place_kernel<{n}, {1 if fill else 0}>" in info["describe"], info
-            assert np.array_equal(got, _twin(gs, places, runs, shape, n, center, bool(fill))), (n, center, fill)
-        got = _render(ctx, dgs, places, runs, shape, fr.FR_MASK_NONZERO, 1, True, 0)
-        assert np.array_equal(got, _twin(gs, places, runs, shape, 1, True, False))
+            assert np.array_equal(got, G.twin_gray("ex", gs, places, runs, shape, n, center, bool(fill))), (n, center, fill)
+        got = G.render_gray(ctx, dgs, places, runs, shape, fr.FR_MASK_NONZERO, 1, True, 0)
+        assert np.array_equal(got, G.twin_gray("ex", gs, places, runs, shape, 1, True, False))
 
 
 @pytest.mark.parametrize("seed,size", [(3, 21)])
 def test_random_placements_rgba_equal_the_twin(ctx, seed, size):
     gs, places, runs, shape = _random_lines(seed, size)
-    clears = _colours(len(runs), 9, False)
-    dst = _noise(shape, seed)
+    clears = G.colours(len(runs), 9, False)
+    dst = G.noise(shape, seed)
     with closing(fr.DeviceGlyphSet(ctx, gs)) as dgs:
         for opaque in (True, False):
-            cols = _colours(len(places), seed + opaque, opaque)
+            cols = G.colours(len(places), seed + opaque, opaque)
             for k, (n, center, fill) in enumerate(CONFIGS):
                 for flags in ((0, SRGB | BGRA, LOAD, LOAD | SRGB) if k % 2 == 0 else (SRGB, BGRA, LOAD | BGRA, LOAD | SRGB | BGRA)):
                     flags |= fill
                     info = {}
-                    start = dst if flags & LOAD else _sent4(shape)
-                    got = _render_rgba(ctx, dgs, places, cols, runs, None if flags & LOAD else clears, start, n, center, flags, info)
+                    start = dst if flags & LOAD else G.sent4(shape, SENT)
+                    got = G.render_rgba(ctx, dgs, places, cols, runs, None if flags & LOAD else clears, start, n, center, flags, info=info)
                     name = "fr::text_place_%s%skernel<%d, %d, %d>" % ("srgb_" if flags & SRGB else "rgba_", "load_" if flags & LOAD else "",
                                                                       n, 1 if fill else 0, 0 if opaque else 1)
                     assert name in info["describe"], (name, info)
-                    assert np.array_equal(got, _twin_rgba(gs, places, cols, runs, clears, start, n, center, flags)), (opaque, n, center, flags)
+                    assert np.array_equal(got, G.twin_rgba("ex", gs, places, cols, runs, clears, start, n, center, flags)), (opaque, n, center, flags)
 
 
 # ---- 3. clipping -------------------------------------------------------------------------------------------------------
@@ -204,7 +131,7 @@ def _clip_case(ascii_set):
     g = ascii_set.find("Serif", "f")
     s = np.float32(30) / np.float32(int(ascii_set.g_upm[g]))
     k = 0.36397
-    c0, r0, cw, ch = tp.cell(gs.boxes[g], s, k, 0, 0)                   # whole-pixel pen: cw x ch; fractional: one more
+    c0, r0, cw, ch = tw.ex_cell(gs.boxes[g], s, k, 0, 0)                   # whole-pixel pen: cw x ch; fractional: one more
     W, H = cw + 6, ch + 6
     px, py = -64 * c0, -64 * r0                                          # the pen that puts the cell at the run's (0, 0)
     pens = [(px - 64 * (cw // 2), py + 64 * 3), (px + 64 * (W - cw // 2), py + 64 * 3),      # over the left, the right,
@@ -220,7 +147,7 @@ def _clip_case(ascii_set):
     shape = (1 + 3 * (H + 2) + 2 * H + 2, max(3 * (W + 3) + 4, 2 + W + 3 + 150 + 2))
     places, runs = rg.make_places_ex(rows), rg.make_runs(runs)
     for i, want in [(4, (W - cw, 2, cw + 1, ch)), (5, (2, H - ch, cw, ch + 1)), (6, (W - cw, H - ch, cw + 1, ch + 1))]:
-        assert tp.cell(gs.boxes[g], s, k, *pens[i]) == want
+        assert tw.ex_cell(gs.boxes[g], s, k, *pens[i]) == want
     return gs, places, runs, shape
 
 
@@ -229,27 +156,27 @@ def test_clipping(ctx, ascii_set):
     outside = np.ones(shape, bool)
     for r in runs:
         outside[int(r["out_y"]):int(r["out_y"]) + int(r["h"]), int(r["out_x"]):int(r["out_x"]) + int(r["w"])] = False
-    cols = _colours(len(places), 11, False)
-    clears = _colours(len(runs), 12, False)
+    cols = G.colours(len(places), 11, False)
+    clears = G.colours(len(runs), 12, False)
     with closing(fr.DeviceGlyphSet(ctx, gs)) as dgs:
         for n, center, fill in CONFIGS[:6]:
             info = {}
-            got = _render(ctx, dgs, places, runs, shape, fr.FR_COVERAGE_U8, n, center, fill, info)
-            want = _twin(gs, places, runs, shape, n, center, bool(fill))
+            got = G.render_gray(ctx, dgs, places, runs, shape, fr.FR_COVERAGE_U8, n, center, fill, info=info)
+            want = G.twin_gray("ex", gs, places, runs, shape, n, center, bool(fill))
             assert np.array_equal(got, want), (n, center, fill)
             assert (got[outside] == SENT).all() and not (got[~outside] == SENT).all()
             for i in (7, 8, 9):                                          # outside / no instance: every pixel written, as 0
                 r = runs[i]
                 assert not got[int(r["out_y"]):int(r["out_y"]) + int(r["h"]), int(r["out_x"]):int(r["out_x"]) + int(r["w"])].any()
             # 7 visible instances in their own runs; in the wide, taller run those and the one that was below its own
-            assert sum(len(tp.instance_hits(gs, places, r, 1)) for r in runs) == 15
+            assert sum(len(tw.instance_hits("ex", gs, places, r, 1)) for r in runs) == 15
             assert info["stats"]["jobs_general"] == 15 and info["pixels"] == sum(int(r["w"]) * int(r["h"]) for r in runs), info
-            got = _render_rgba(ctx, dgs, places, cols, runs, clears, _sent4(shape), n, center, fill | (SRGB if n == 2 else 0))
-            assert np.array_equal(got, _twin_rgba(gs, places, cols, runs, clears, _sent4(shape), n, center, fill | (SRGB if n == 2 else 0)))
+            got = G.render_rgba(ctx, dgs, places, cols, runs, clears, G.sent4(shape, SENT), n, center, fill | (SRGB if n == 2 else 0))
+            assert np.array_equal(got, G.twin_rgba("ex", gs, places, cols, runs, clears, G.sent4(shape, SENT), n, center, fill | (SRGB if n == 2 else 0)))
             assert (got[outside] == SENT).all()
         # a plan of only the empty run renders nothing
         only = rg.make_runs([tuple(runs[9])])
-        assert (_render(ctx, dgs, places, only, shape)[outside] == SENT).all()
+        assert (G.render_gray(ctx, dgs, places, only, shape)[outside] == SENT).all()
 
 
 def test_load_launches_only_the_tiles_under_a_cell(ctx, ascii_set):
@@ -265,26 +192,26 @@ def test_load_launches_only_the_tiles_under_a_cell(ctx, ascii_set):
             (g, 64 * 650 + 5, 64 * 40, np.float32(s / 2), 4.0), (g, 64 * 699, 64 * 199 + 32, 0.0, 0.0), (g, 64 * 900, 64 * 100, 0.0, 0.0)]
     places = rg.make_places_ex(rows)
     shape = (205, 706)
-    met = tp.met_tiles(gs, places, big)
+    met = tw.met_tiles("ex", gs, places, big)
     assert 4 <= len(met) < 11 * 13 // 2                                  # of the run's 11 x 13 tiles
     untouched = np.ones(shape, bool)
     for _, ty, tx in met:
         untouched[2 + 16 * ty:2 + min(16 * ty + 16, 200), 3 + 64 * tx:3 + min(64 * tx + 64, 700)] = False
-    dst = _noise(shape, 77)
+    dst = G.noise(shape, 77)
     with closing(fr.DeviceGlyphSet(ctx, gs)) as dgs:
         for opaque in (True, False):
-            cols = _colours(len(places), 21, opaque)
+            cols = G.colours(len(places), 21, opaque)
             for n, center, flags in ((4, True, LOAD), (2, False, LOAD | SRGB | FILL), (1, True, LOAD | BGRA)):
                 info = {}
-                got = _render_rgba(ctx, dgs, places, cols, big, None, dst, n, center, flags, info)
-                assert np.array_equal(got, _twin_rgba(gs, places, cols, big, None, dst, n, center, flags)), (opaque, n, flags)
+                got = G.render_rgba(ctx, dgs, places, cols, big, None, dst, n, center, flags, info=info)
+                assert np.array_equal(got, G.twin_rgba("ex", gs, places, cols, big, None, dst, n, center, flags)), (opaque, n, flags)
                 assert np.array_equal(got[untouched], dst[untouched]) and not np.array_equal(got, dst)
                 name = "fr::text_place_%sload_kernel<%d, %d, %d>" % ("srgb_" if flags & SRGB else "rgba_", n, 1 if flags & FILL else 0, 0 if opaque else 1)
-                assert _count(info["describe"], name) == 4 == info["stats"]["jobs_general"], info     # the fifth is clipped away
+                assert G.count(info["describe"], name) == 4 == info["stats"]["jobs_general"], info     # the fifth is clipped away
         # all instances clipped away: nothing is launched, the buffer stays as it is
         gone = rg.make_places_ex([(g, 64 * 900, 64 * 100, 0.0, 0.2)])
         info = {}
-        got = _render_rgba(ctx, dgs, gone, _colours(1, 1, True), rg.make_runs([(0, 1, 700, 200, 3, 2, s)]), None, dst, 4, True, LOAD, info)
+        got = G.render_rgba(ctx, dgs, gone, G.colours(1, 1, True), rg.make_runs([(0, 1, 700, 200, 3, 2, s)]), None, dst, 4, True, LOAD, info=info)
         assert info["describe"] == "" and np.array_equal(got, dst), info
 
 
@@ -295,9 +222,9 @@ def test_large_glyph_and_tall_cell(ctx):
     tall, _ = font.glyphset([font.glyph_index(ord("l")), font.glyph_index(ord("|"))], skip_unsupported=False)
     gs = GlyphSet([big.glyph(0), tall.glyph(0), tall.glyph(1)])
     s_big = np.float32(0.05)
-    c0, r0, w0, h0 = tp.cell(gs.boxes[0], s_big, 0.2, 0, 0)
+    c0, r0, w0, h0 = tw.ex_cell(gs.boxes[0], s_big, 0.2, 0, 0)
     s_tall = np.float32(700) / np.float32(2048)                          # 'l' at 700: > 512 rows, > 2048 sample rows at n = 4
-    c1, r1, w1, h1 = tp.cell(gs.boxes[1], s_tall, -0.2, 0, 0)
+    c1, r1, w1, h1 = tw.ex_cell(gs.boxes[1], s_tall, -0.2, 0, 0)
     assert 4 * h1 > 2048 and h1 > 512
     places = rg.make_places_ex([(0, -64 * c0 + 37, -64 * r0 + 11, 0.0, 0.2), (0, -64 * c0 + 64 * 9 + 5, -64 * r0 + 64 * 4 + 50, np.float32(0.04), -0.36),
                                 (1, -64 * c1 + 21, -64 * r1 + 33, 0.0, -0.2), (2, -64 * c1 + 64 * 30 + 50, -64 * r1, 0.0, 0.2)])
@@ -305,14 +232,14 @@ def test_large_glyph_and_tall_cell(ctx):
     shape = (max(h0 + 6, h1 + 2) + 1, w0 + 13 + w1 + 61)
     with closing(fr.DeviceGlyphSet(ctx, gs)) as dgs:
         info = {}
-        got = _render(ctx, dgs, places, runs, shape, fr.FR_COVERAGE_U8, 4, True, plan_out=info)
+        got = G.render_gray(ctx, dgs, places, runs, shape, fr.FR_COVERAGE_U8, 4, True, info=info)
         assert info["stats"] == {"jobs_cov4": 0, "jobs_general": 4}, info
         assert info["pixels"] == sum(int(r["w"]) * int(r["h"]) for r in runs)
         assert "fr::text_place_kernel<4, 0>" in info["describe"], info
-        assert np.array_equal(got, _twin(gs, places, runs, shape, 4, True))
-        got = _render(ctx, dgs, places, runs, shape, fr.FR_COVERAGE_U8, 2, False, FILL, plan_out=info)
+        assert np.array_equal(got, G.twin_gray("ex", gs, places, runs, shape, 4, True))
+        got = G.render_gray(ctx, dgs, places, runs, shape, fr.FR_COVERAGE_U8, 2, False, FILL, info=info)
         assert "fr::text_place_kernel<2, 1>" in info["describe"], info
-        assert np.array_equal(got, _twin(gs, places, runs, shape, 2, False, True))
+        assert np.array_equal(got, G.twin_gray("ex", gs, places, runs, shape, 2, False, True))
 
 
 # ---- 5. the Python surface ---------------------------------------------------------------------------------------------
@@ -324,12 +251,12 @@ def test_render_spans_equals_the_twin(ctx):
     assert len(runs) == 1 and len(set(places["scale"].tolist())) == 3
     im = fr.render_spans(font, spans, ctx=ctx)
     assert (im.width, im.height) == (w, h)
-    assert np.array_equal(im.as_2d(), tp.render_run(gs, places, runs[0], 4, True))
+    assert np.array_equal(im.as_2d(), tw.render_run("ex", gs, places, runs[0], 4, True))
     im = fr.render_spans(font, spans, samples_per_axis=2, phase=fr.FR_SAMPLE_CORNER, flags=FILL, ctx=ctx)
-    assert np.array_equal(im.as_2d(), tp.render_run(gs, places, runs[0], 2, False, True))
+    assert np.array_equal(im.as_2d(), tw.render_run("ex", gs, places, runs[0], 2, False, True))
     for srgb in (False, True):
         im = fr.render_spans_rgba(font, spans, (250, 250, 240, 255), srgb=srgb, ctx=ctx)
-        want = tp.rgba_render_run(gs, places, np.array(cols, np.uint8), runs[0], (250, 250, 240, 255), None, 4, True, False, srgb)
+        want = tw.rgba_render_run("ex", gs, places, np.array(cols, np.uint8), runs[0], (250, 250, 240, 255), None, 4, True, False, srgb)
         assert np.array_equal(im.as_3d(), want), srgb
 
 
@@ -340,15 +267,15 @@ def test_render_text_slant_equals_the_twin(ctx):
         assert places.dtype == rg.PLACE_EX_DTYPE
         im = fr.render_text(font, text, size, slant=slant, ctx=ctx)
         assert (im.width, im.height) == (w, h)
-        assert np.array_equal(im.as_2d(), tp.render_run(gs, places, runs[0], 4, True))
+        assert np.array_equal(im.as_2d(), tw.render_run("ex", gs, places, runs[0], 4, True))
         up = fr.render_text(font, text, size, ctx=ctx)
         assert not np.array_equal(up.as_2d(), im.as_2d()) if (up.width, up.height) == (w, h) else True
         rgba = fr.render_text_rgba(font, text, size, (10, 200, 30, 180), (255, 255, 255, 255), slant=slant, ctx=ctx)
-        want = tp.rgba_render_run(gs, places, np.array([(10, 200, 30, 180)] * len(text), np.uint8), runs[0], (255, 255, 255, 255), None, 4, True)
+        want = tw.rgba_render_run("ex", gs, places, np.array([(10, 200, 30, 180)] * len(text), np.uint8), runs[0], (255, 255, 255, 255), None, 4, True)
         assert np.array_equal(rgba.as_3d(), want)
     # the default is today's call: the old entry point's bytes
-    gs, places, runs, shape = tr.lines(font, ["Tffj fix"], 27)
-    assert np.array_equal(fr.render_text(font, "Tffj fix", 27, slant=0.0, ctx=ctx).as_2d(), text_ref.render_run(gs, places, runs[0], 4, True))
+    gs, places, runs, shape = tw.lines(font, ["Tffj fix"], 27)
+    assert np.array_equal(fr.render_text(font, "Tffj fix", 27, slant=0.0, ctx=ctx).as_2d(), tw.render_run("plain", gs, places, runs[0], 4, True))
 
 
 def _draw_twin(font, text, size, img, x, y, cols, slant=0.0, n=4, center=True, srgb=False):
@@ -359,14 +286,14 @@ def _draw_twin(font, text, size, img, x, y, cols, slant=0.0, n=4, center=True, s
     places = rg.make_places_ex([(local[int(g)], x64 + int(p), y64, 0.0, slant) for g, p in zip(gi, pen)])
     scale = np.float32(size) / np.float32(font.information.units_per_em)
     run = rg.make_runs([(0, len(places), img.shape[1], img.shape[0], 0, 0, scale)])[0]
-    return tp.rgba_render_run(gs, places, np.asarray(cols, np.uint8), run, None, img, n, center, False, srgb)
+    return tw.rgba_render_run("ex", gs, places, np.asarray(cols, np.uint8), run, None, img, n, center, False, srgb)
 
 
 def test_draw_text_rgba_fractional_baseline(ctx):
     font = load_font("DejaVuSerif-Italic.ttf")
     text = "Tffj a red word"
     hl = [(255, 0, 0, 255) if 6 <= k < 9 else (0, 0, 0, 160) for k in range(len(text))]
-    base = _noise((60, 150), 31)
+    base = G.noise((60, 150), 31)
 
     def draw(y, **kw):
         im = fr.RGBA(150, 60, base.reshape(-1, 4).copy())
@@ -385,7 +312,7 @@ def test_draw_text_rgba_fractional_baseline(ctx):
     places = rg.make_places([(local[int(g)], 129 + int(p), 10) for g, p in zip(gi, pen)])
     runs = rg.make_runs([(0, len(places), 150, 60, 0, 0, np.float32(27) / np.float32(font.information.units_per_em))])
     with closing(fr.DeviceGlyphSet(ctx, gs)) as dgs:
-        old = _render_rgba(ctx, dgs, places, np.array(hl, np.uint8), runs, None, base, 4, True, LOAD)
+        old = G.render_rgba(ctx, dgs, places, np.array(hl, np.uint8), runs, None, base, 4, True, LOAD)
     assert np.array_equal(draw(10.0), old) and np.array_equal(draw(10), old)
     assert np.array_equal(old, _draw_twin(font, text, 27, base, 2.015625, 10, hl))
 
@@ -398,7 +325,7 @@ def test_render_text_view_equals_the_twin(ctx):
         gs, places, runs = T.view_line(font, text, 24, zoom, ox, oy, 260, 70)
         im = fr.render_text_view(font, text, 24, zoom, ox, oy, 260, 70, ctx=ctx)
         assert (im.width, im.height) == (260, 70)
-        assert np.array_equal(im.as_2d(), tp.render_run(gs, places, runs[0], 4, True)), (zoom, ox, oy)
+        assert np.array_equal(im.as_2d(), tw.render_run("ex", gs, places, runs[0], 4, True)), (zoom, ox, oy)
         assert im.as_2d().any()
         frames.append(im.as_2d().copy())
     assert not np.array_equal(frames[0], frames[1])

@@ -1,5 +1,5 @@
 """RGBA text plans on the GPU (fr_text_plan_create_rgba, include/fr_raster.h): byte for byte against the CPU twin of the
-definition (tests/text_rgba_ref.py), and against the coverage of a plain text plan for white on transparent.  Outputs
+definition (tests/text_twin.py), and against the coverage of a plain text plan for white on transparent.  Outputs
 are device buffers filled with a 4-byte sentinel: pixels outside every run must keep it, pixels inside are all written."""
 import ctypes as C
 import io
@@ -9,69 +9,23 @@ import numpy as np
 import pytest
 
 import font_renderer_amd as fr
-import text_ref
-import text_rgba_ref as tr
+import text_gpu as G
+import text_twin as tw
 from fixtures import load_font
 from font_renderer_amd import render_glyph as rg
 from font_renderer_amd.glyph import GlyphSet
 from font_renderer_amd.synth import synth_glyphset
+from text_gpu import FILL, italic  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 SENT = np.array([0x5b, 0xa7, 0x13, 0xc4], np.uint8)
-FILL = fr.FR_FILL_CONSISTENT
 PINK, RED, BLUE = (225, 105, 180, 255), (230, 20, 10, 255), (20, 40, 250, 255)
 CONFIGS = [(4, True, 0), (4, False, FILL), (2, True, FILL), (2, False, 0), (1, True, 0), (1, False, FILL)]
-
-
-def _phase(center):
-    return fr.FR_SAMPLE_CENTER if center else fr.FR_SAMPLE_CORNER
-
-
-def _render(ctx, dgs, places, cols, runs, clears, shape, n=4, center=True, flags=0, plan_out=None):
-    import torch
-    plan = fr.TextPlanRGBA(dgs, places, cols, runs, clears, n, _phase(center), flags)
-    buf = torch.from_numpy(np.tile(SENT, shape + (1,))).to("cuda:0")
-    torch.cuda.synchronize()
-    plan.render(buf.data_ptr(), shape[1], shape[0])
-    ctx.sync()
-    if plan_out is not None:
-        plan_out.update(stats=plan.stats(), describe=plan.describe(), pixels=plan.pixels)
-    plan.close()
-    return buf.cpu().numpy()
-
-
-def _twin(gs, places, cols, runs, clears, shape, n=4, center=True, fill=False, which=None):
-    return tr.render_runs(gs, places, cols, runs, clears, np.tile(SENT, shape + (1,)), n, center, fill, which)
-
-
-def _inside(runs, shape):
-    m = np.zeros(shape, bool)
-    for r in runs:
-        m[r["out_y"]:r["out_y"] + r["h"], r["out_x"]:r["out_x"] + r["w"]] = True
-    return m
-
-
-def _check_borders(got, runs):
-    inside = _inside(runs, got.shape[:2])
-    is_sent = (got == SENT).all(axis=2)
-    assert is_sent[~inside].all() and not is_sent[inside].any()
 
 
 def _alternating(strings, a, b):
     """per-word colours of the runs' characters (one placement each): a for the even words of a string, b for the odd"""
     return np.array([a if s[:k].count(" ") % 2 == 0 else b for s in strings for k in range(len(s))], np.uint8)
-
-
-ITALIC = ["ffi fj Tf ff", "Tjfyfgf jjj", "WoWfj"]
-
-
-@pytest.fixture(scope="module")
-def italic():
-    font = load_font("DejaVuSerif-Italic.ttf")
-    gs, places, runs, shape = tr.lines(font, ITALIC, 21, pad=2)
-    k0 = int(runs[2]["first"])                                  # a run of glyphs packed so close that their ink overlaps
-    places["pen_x64"][k0:k0 + 5] = places["pen_x64"][k0] + np.array([0, 213, 410, 641, 817])
-    return gs, places, runs, shape
 
 
 # ---- 1. overlapping instances: opaque (BLEND = 0) and translucent (BLEND = 1) colours on the same placements ----------
@@ -96,10 +50,10 @@ def test_overlapping_pairs_equal_the_twin(ctx, italic, n, center, flags):
     for name, pl, cols, blend in [("opaque", places, two, 0), ("opaque swapped", places[perm], two[perm], 0),
                                   ("translucent", places, translucent, 1),
                                   ("translucent swapped", places[perm], translucent[perm], 1)]:
-        got = _render(ctx, dgs, pl, cols, runs, clears, shape, n, center, flags, plan_out=info)
+        got = G.render_rgba(ctx, dgs, pl, cols, runs, clears, G.sent4(shape, SENT), n, center, flags, info=info)
         assert f"fr::text_rgba_kernel<{n}, {1 if flags else 0}, {blend}> x" in info["describe"], (name, info)
-        assert np.array_equal(got, _twin(gs, pl, cols, runs, clears, shape, n, center, flags == FILL)), (name, n, center, flags)
-        _check_borders(got, runs)
+        assert np.array_equal(got, G.twin_rgba("plain", gs, pl, cols, runs, clears, G.sent4(shape, SENT), n, center, flags)), (name, n, center, flags)
+        G.check_borders(got, runs, SENT)
         outs[name] = got
     assert not np.array_equal(outs["opaque"], outs["opaque swapped"])
     assert not np.array_equal(outs["translucent"], outs["translucent swapped"])
@@ -122,19 +76,19 @@ def test_white_on_transparent_is_the_text_plan_coverage(ctx, name):
     font = load_font(name, allow_hinted=True)
     whole = "".join(chr(c) for c in range(0x21, 0x7f)) + "".join(chr(c) for c in range(0xa1, 0x180))
     whole = "".join(c for c in whole if font.glyph_index(ord(c)) and _loads(font, c))
-    gs, places, runs, shape = tr.lines(font, [whole[:120], whole[120:]], 18, pad=1)
+    gs, places, runs, shape = tw.lines(font, [whole[:120], whole[120:]], 18, pad=1)
     dgs = fr.DeviceGlyphSet(ctx, gs)
     white = np.full((len(places), 4), 255, np.uint8)
     for n, center, flags in CONFIGS:
-        got = _render(ctx, dgs, places, white, runs, [(0, 0, 0, 0)] * len(runs), shape, n, center, flags)
-        plan = fr.TextPlan(dgs, places, runs, fr.FR_COVERAGE_U8, n, _phase(center), flags)
+        got = G.render_rgba(ctx, dgs, places, white, runs, [(0, 0, 0, 0)] * len(runs), G.sent4(shape, SENT), n, center, flags)
+        plan = fr.TextPlan(dgs, places, runs, fr.FR_COVERAGE_U8, n, G.phase(center), flags)
         cov = torch.full(shape, 0x5b, dtype=torch.uint8, device="cuda:0")
         torch.cuda.synchronize()
         plan.render(cov.data_ptr(), shape[1], shape[0])
         ctx.sync()
         plan.close()
         cov = cov.cpu().numpy()
-        inside = _inside(runs, shape)
+        inside = G.inside(runs, shape)
         for ch in range(4):
             assert np.array_equal(got[..., ch][inside], cov[inside]), (name, n, center, flags, ch)
         assert (cov[inside] > 0).sum() > 1000
@@ -159,9 +113,9 @@ def test_every_pen_fraction(ctx):
     shape = (8 * (H + 1), 16 * (W + 1))
     dgs = fr.DeviceGlyphSet(ctx, gs)
     for n, center in [(4, True), (1, False), (2, True)]:
-        got = _render(ctx, dgs, places, cols, runs, clears, shape, n, center)
-        assert np.array_equal(got, _twin(gs, places, cols, runs, clears, shape, n, center)), (n, center)
-        _check_borders(got, runs)
+        got = G.render_rgba(ctx, dgs, places, cols, runs, clears, G.sent4(shape, SENT), n, center)
+        assert np.array_equal(got, G.twin_rgba("plain", gs, places, cols, runs, clears, G.sent4(shape, SENT), n, center)), (n, center)
+        G.check_borders(got, runs, SENT)
     dgs.close()
 
 
@@ -188,9 +142,9 @@ def test_borders_clipping_and_clear_colours(ctx):
     shape = (2 + 5 * (H + 3) + 14, 8 * (W + 4) + 9)
     dgs = fr.DeviceGlyphSet(ctx, gs)
     for cols in (np.array([PINK] * len(rows), np.uint8), rng.integers(0, 256, (len(rows), 4)).astype(np.uint8)):
-        got = _render(ctx, dgs, places, cols, runs, clears, shape)
-        assert np.array_equal(got, _twin(gs, places, cols, runs, clears, shape))
-        _check_borders(got, runs)
+        got = G.render_rgba(ctx, dgs, places, cols, runs, clears, G.sent4(shape, SENT))
+        assert np.array_equal(got, G.twin_rgba("plain", gs, places, cols, runs, clears, G.sent4(shape, SENT)))
+        G.check_borders(got, runs, SENT)
         last = runs[-1]
         assert (got[last["out_y"]:last["out_y"] + last["h"], last["out_x"]:last["out_x"] + last["w"]] == clears[-1]).all()
     dgs.close()
@@ -203,9 +157,9 @@ def test_large_glyph_and_tall_cell(ctx):
     tall, _ = font.glyphset([font.glyph_index(ord("l")), font.glyph_index(ord("|"))], skip_unsupported=False)
     gs = GlyphSet([big.glyph(0), tall.glyph(0), tall.glyph(1)])
     s_big = np.float32(0.05)
-    c0, r0, w0, h0 = text_ref.cell(gs.boxes[0], s_big, 0, 0)
+    c0, r0, w0, h0 = tw.plain_cell(gs.boxes[0], s_big, 0, 0)
     s_tall = np.float32(700) / np.float32(2048)                          # > 2048 sample rows at n = 4
-    c1, r1, w1, h1 = text_ref.cell(gs.boxes[1], s_tall, 0, 0)
+    c1, r1, w1, h1 = tw.plain_cell(gs.boxes[1], s_tall, 0, 0)
     assert 4 * h1 > 2048
     places = rg.make_places([(0, -64 * c0 + 37, -r0), (0, -64 * c0 + 64 * 9 + 5, -r0 + 4),
                              (1, -64 * c1 + 21, -r1), (2, -64 * c1 + 64 * 30 + 50, -r1)])
@@ -215,14 +169,14 @@ def test_large_glyph_and_tall_cell(ctx):
     clears = [(0, 0, 0, 0), (255, 255, 255, 255)]
     dgs = fr.DeviceGlyphSet(ctx, gs)
     info = {}
-    got = _render(ctx, dgs, places, cols, runs, clears, shape, 4, True, plan_out=info)
+    got = G.render_rgba(ctx, dgs, places, cols, runs, clears, G.sent4(shape, SENT), 4, True, info=info)
     assert info["stats"] == {"jobs_cov4": 0, "jobs_general": 4}, info
     assert info["pixels"] == sum(int(r["w"]) * int(r["h"]) for r in runs)
     assert "fr::text_rgba_kernel<4, 0, 1> x" in info["describe"], info
-    assert np.array_equal(got, _twin(gs, places, cols, runs, clears, shape, 4, True))
-    got = _render(ctx, dgs, places, cols, runs, clears, shape, 2, False, FILL, plan_out=info)
+    assert np.array_equal(got, G.twin_rgba("plain", gs, places, cols, runs, clears, G.sent4(shape, SENT), 4, True))
+    got = G.render_rgba(ctx, dgs, places, cols, runs, clears, G.sent4(shape, SENT), 2, False, FILL, info=info)
     assert "fr::text_rgba_kernel<2, 1, 1> x" in info["describe"], info
-    assert np.array_equal(got, _twin(gs, places, cols, runs, clears, shape, 2, False, True))
+    assert np.array_equal(got, G.twin_rgba("plain", gs, places, cols, runs, clears, G.sent4(shape, SENT), 2, False, FILL))
     dgs.close()
 
 
@@ -232,7 +186,7 @@ def test_many_runs_graph_and_overlap(ctx):
     rng = np.random.default_rng(2025)
     alphabet = np.array(list("abcdefghijklmnopqrstuvwxyzABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789ffjT.,;!? "))
     strings = ["".join(rng.choice(alphabet, int(rng.integers(3, 24)))) for _ in range(2500)]
-    gs, places, runs, (H, W) = tr.lines(font, strings, 14, pad=1)
+    gs, places, runs, (H, W) = tw.lines(font, strings, 14, pad=1)
     half = len(runs) // 2
     y_off = int(runs[half]["out_y"]) - 1
     runs["out_x"][half:] += W
@@ -242,10 +196,10 @@ def test_many_runs_graph_and_overlap(ctx):
     cols[len(cols) // 2:, 3] = 150                                    # translucent in the second half
     clears = [(0, 0, 0, 0) if r % 2 else (250, 250, 250, 255) for r in range(len(runs))]
     dgs = fr.DeviceGlyphSet(ctx, gs)
-    base = _render(ctx, dgs, places, cols, runs, clears, shape)
-    _check_borders(base, runs)
+    base = G.render_rgba(ctx, dgs, places, cols, runs, clears, G.sent4(shape, SENT))
+    G.check_borders(base, runs, SENT)
     which = sorted(rng.choice(len(runs), 40, replace=False).tolist()) + [half - 1, half, len(runs) - 1]
-    want = _twin(gs, places, cols, runs, clears, shape, which=which)
+    want = G.twin_rgba("plain", gs, places, cols, runs, clears, G.sent4(shape, SENT), which=which)
     for r in which:
         run = runs[r]
         sl = np.s_[run["out_y"]:run["out_y"] + run["h"], run["out_x"]:run["out_x"] + run["w"]]
@@ -253,11 +207,11 @@ def test_many_runs_graph_and_overlap(ctx):
     try:
         ctx.set_option("graph", 1)
         for _ in range(3):
-            assert np.array_equal(_render(ctx, dgs, places, cols, runs, clears, shape), base)
+            assert np.array_equal(G.render_rgba(ctx, dgs, places, cols, runs, clears, G.sent4(shape, SENT)), base)
         ctx.set_option("graph", 0)
         for ov in (0, 2):
             ctx.set_option("overlap", ov)
-            assert np.array_equal(_render(ctx, dgs, places, cols, runs, clears, shape), base)
+            assert np.array_equal(G.render_rgba(ctx, dgs, places, cols, runs, clears, G.sent4(shape, SENT)), base)
     finally:
         ctx.set_option("graph", 0)
         ctx.set_option("overlap", 1)
@@ -347,10 +301,10 @@ def test_render_text_rgba_saves_as_qoi(ctx):
     font = load_font("DejaVuSerif-Italic.ttf")
     text = "Tffj a red word"
     im = fr.render_text_rgba(font, text, 27, ctx=ctx)
-    gs, places, runs, shape = tr.lines(font, [text], 27)
+    gs, places, runs, shape = tw.lines(font, [text], 27)
     assert (im.height, im.width) == shape
     cols = np.array([(225, 105, 180, 255)] * len(text), np.uint8)
-    assert np.array_equal(im.as_3d(), tr.render_run(gs, places, cols, runs[0], (0, 0, 0, 0), 4, True))
+    assert np.array_equal(im.as_3d(), tw.rgba_render_run("plain", gs, places, cols, runs[0], (0, 0, 0, 0), None, 4, True))
     # RGB premultiplied by the coverage: white on transparent would be the coverage byte in every channel
     cov = fr.render_text(font, text, 27, ctx=ctx).as_2d()
     assert np.array_equal(im.as_3d()[..., 3], cov)
@@ -360,6 +314,6 @@ def test_render_text_rgba_saves_as_qoi(ctx):
     hl = [(255, 0, 0, 255) if 6 <= k < 9 else (0, 0, 0, 255) for k in range(len(text))]
     im2 = fr.render_text_rgba(font, text, 27, background=(255, 255, 255, 255), colors=hl, samples_per_axis=2,
                               phase=fr.FR_SAMPLE_CORNER, ctx=ctx)
-    want = tr.render_run(gs, places, np.array(hl, np.uint8), runs[0], (255, 255, 255, 255), 2, False)
+    want = tw.rgba_render_run("plain", gs, places, np.array(hl, np.uint8), runs[0], (255, 255, 255, 255), None, 2, False)
     assert np.array_equal(im2.as_3d(), want)
     assert (im2.as_3d()[..., 3] == 255).all() and (im2.as_3d()[..., 0] > im2.as_3d()[..., 1]).any()

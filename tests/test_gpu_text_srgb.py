@@ -1,5 +1,5 @@
 """sRGB text plans on the GPU (fr_text_plan_create_rgba with FR_TEXT_SRGB / FR_TEXT_BGRA, include/fr_raster.h): byte for
-byte against the CPU twin of the definition (tests/text_srgb_ref.py).  Outputs are device buffers filled with a 4-byte
+byte against the CPU twin of the definition (tests/text_twin.py).  Outputs are device buffers filled with a 4-byte
 sentinel: pixels outside every run must keep it, pixels inside are all written."""
 import ctypes as C
 from contextlib import closing
@@ -8,78 +8,26 @@ import numpy as np
 import pytest
 
 import font_renderer_amd as fr
-import text_ref
-import text_rgba_ref as tr
-import text_srgb_ref as ts
+import text_gpu as G
+import text_twin as tw
 from fixtures import load_font
 from font_renderer_amd import render_glyph as rg
 from font_renderer_amd.glyph import GlyphSet
 from font_renderer_amd.synth import synth_glyphset
+from text_gpu import BGRA, FILL, SRGB, italic  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 SENT = np.array([0x5b, 0xa7, 0x13, 0xc4], np.uint8)
-FILL, SRGB, BGRA = fr.FR_FILL_CONSISTENT, fr.FR_TEXT_SRGB, fr.FR_TEXT_BGRA
 PINK, RED, BLUE = (225, 105, 180, 255), (230, 20, 10, 255), (20, 40, 250, 255)
 CONFIGS = [(4, True, 0), (4, False, FILL), (2, True, FILL), (2, False, 0), (1, True, 0), (1, False, FILL)]
-
-
-def _phase(center):
-    return fr.FR_SAMPLE_CENTER if center else fr.FR_SAMPLE_CORNER
-
-
-def _render(ctx, dgs, places, cols, runs, clears, shape, n=4, center=True, flags=SRGB, plan_out=None):
-    import torch
-    plan = fr.TextPlanRGBA(dgs, places, cols, runs, clears, n, _phase(center), flags)
-    buf = torch.from_numpy(np.tile(SENT, shape + (1,))).to("cuda:0")
-    torch.cuda.synchronize()
-    plan.render(buf.data_ptr(), shape[1], shape[0])
-    ctx.sync()
-    if plan_out is not None:
-        plan_out.update(stats=plan.stats(), describe=plan.describe(), pixels=plan.pixels)
-    plan.close()
-    return buf.cpu().numpy()
-
-
-def _twin(gs, places, cols, runs, clears, shape, n=4, center=True, flags=SRGB, which=None):
-    out = np.tile(SENT, shape + (1,))
-    if flags & SRGB:
-        return ts.render_runs(gs, places, cols, runs, clears, out, n, center, bool(flags & FILL), which, bool(flags & BGRA))
-    if flags & BGRA:                  # the UNORM plan's B G R A: R and B swapped in every colour
-        cols, clears = np.asarray(cols)[:, [2, 1, 0, 3]], np.asarray(clears)[:, [2, 1, 0, 3]]
-    return tr.render_runs(gs, places, cols, runs, clears, out, n, center, bool(flags & FILL), which)
-
-
-def _inside(runs, shape):
-    m = np.zeros(shape, bool)
-    for r in runs:
-        m[r["out_y"]:r["out_y"] + r["h"], r["out_x"]:r["out_x"] + r["w"]] = True
-    return m
-
-
-def _check_borders(got, runs):
-    inside = _inside(runs, got.shape[:2])
-    is_sent = (got == SENT).all(axis=2)
-    assert is_sent[~inside].all() and not is_sent[inside].any()
 
 
 def _swapped(img, runs):
     """the pixels of the runs with bytes 0 and 2 swapped (R G B A <-> B G R A); the sentinel outside them as it is"""
     out = img.copy()
-    inside = _inside(runs, img.shape[:2])
+    inside = G.inside(runs, img.shape[:2])
     out[inside] = img[inside][:, [2, 1, 0, 3]]
     return out
-
-
-ITALIC = ["ffi fj Tf ff", "Tjfyfgf jjj", "WoWfj"]
-
-
-@pytest.fixture(scope="module")
-def italic():
-    font = load_font("DejaVuSerif-Italic.ttf")
-    gs, places, runs, shape = tr.lines(font, ITALIC, 21, pad=2)
-    k0 = int(runs[2]["first"])                                  # a run of glyphs packed so close that their ink overlaps
-    places["pen_x64"][k0:k0 + 5] = places["pen_x64"][k0] + np.array([0, 213, 410, 641, 817])
-    return gs, places, runs, shape
 
 
 # ---- 1. overlapping instances: opaque (BLEND = 0) and translucent (BLEND = 1), RGBA and BGRA ------------------------------
@@ -109,20 +57,20 @@ def _overlapping_pairs(ctx, dgs, gs, places, runs, shape, n, center, fill, perm,
                                   ("translucent swapped", places[perm], translucent[perm], 1)]:
         for order in (0, BGRA):
             flags = SRGB | fill | order
-            got = _render(ctx, dgs, pl, cols, runs, clears, shape, n, center, flags, plan_out=info)
+            got = G.render_rgba(ctx, dgs, pl, cols, runs, clears, G.sent4(shape, SENT), n, center, flags, info=info)
             assert f"fr::text_srgb_kernel<{n}, {1 if fill else 0}, {blend}> x" in info["describe"], (name, info)
-            assert np.array_equal(got, _twin(gs, pl, cols, runs, clears, shape, n, center, flags)), (name, n, center, flags)
-            _check_borders(got, runs)
+            assert np.array_equal(got, G.twin_rgba("plain", gs, pl, cols, runs, clears, G.sent4(shape, SENT), n, center, flags)), (name, n, center, flags)
+            G.check_borders(got, runs, SENT)
             outs[name, order] = got
         assert np.array_equal(outs[name, BGRA], _swapped(outs[name, 0], runs))
     assert not np.array_equal(outs["opaque", 0], outs["opaque swapped", 0])
     assert not np.array_equal(outs["translucent", 0], outs["translucent swapped", 0])
     # against the UNORM plan: the alpha channel is the same; RGB differs at the edges (and for n = 1 opaque, nowhere)
-    unorm = _render(ctx, dgs, places, translucent, runs, clears, shape, n, center, fill)
+    unorm = G.render_rgba(ctx, dgs, places, translucent, runs, clears, G.sent4(shape, SENT), n, center, fill)
     assert np.array_equal(unorm[..., 3], outs["translucent", 0][..., 3])
     assert not np.array_equal(unorm, outs["translucent", 0])
-    unorm = _render(ctx, dgs, places, two, runs, clears, shape, n, center, fill | BGRA)
-    assert np.array_equal(unorm, _twin(gs, places, two, runs, clears, shape, n, center, fill | BGRA))
+    unorm = G.render_rgba(ctx, dgs, places, two, runs, clears, G.sent4(shape, SENT), n, center, fill | BGRA)
+    assert np.array_equal(unorm, G.twin_rgba("plain", gs, places, two, runs, clears, G.sent4(shape, SENT), n, center, fill | BGRA))
     assert np.array_equal(unorm, outs["opaque", BGRA]) == (n == 1)
 
 
@@ -144,9 +92,9 @@ def test_every_pen_fraction(ctx):
     shape = (8 * (H + 1), 16 * (W + 1))
     with closing(fr.DeviceGlyphSet(ctx, gs)) as dgs:
         for n, center, flags in [(4, True, SRGB), (1, False, SRGB | BGRA), (2, True, SRGB | FILL)]:
-            got = _render(ctx, dgs, places, cols, runs, clears, shape, n, center, flags)
-            assert np.array_equal(got, _twin(gs, places, cols, runs, clears, shape, n, center, flags)), (n, center, flags)
-            _check_borders(got, runs)
+            got = G.render_rgba(ctx, dgs, places, cols, runs, clears, G.sent4(shape, SENT), n, center, flags)
+            assert np.array_equal(got, G.twin_rgba("plain", gs, places, cols, runs, clears, G.sent4(shape, SENT), n, center, flags)), (n, center, flags)
+            G.check_borders(got, runs, SENT)
 
 
 # ---- 3. clipping at run borders, several runs with different clear colours --------------------------------------------
@@ -174,9 +122,9 @@ def test_borders_clipping_and_clear_colours(ctx):
                 (rng.integers(0, 256, (len(rows), 4)).astype(np.uint8), SRGB | BGRA | FILL))
     with closing(fr.DeviceGlyphSet(ctx, gs)) as dgs:
         for cols, flags in variants:
-            got = _render(ctx, dgs, places, cols, runs, clears, shape, flags=flags)
-            assert np.array_equal(got, _twin(gs, places, cols, runs, clears, shape, flags=flags)), flags
-            _check_borders(got, runs)
+            got = G.render_rgba(ctx, dgs, places, cols, runs, clears, G.sent4(shape, SENT), flags=flags)
+            assert np.array_equal(got, G.twin_rgba("plain", gs, places, cols, runs, clears, G.sent4(shape, SENT), flags=flags)), flags
+            G.check_borders(got, runs, SENT)
             last = runs[-1]
             want = np.array(clears[-1], np.uint8)[[2, 1, 0, 3] if flags & BGRA else [0, 1, 2, 3]]
             assert (got[last["out_y"]:last["out_y"] + last["h"], last["out_x"]:last["out_x"] + last["w"]] == want).all()
@@ -189,9 +137,9 @@ def test_large_glyph_and_tall_cell(ctx):
     tall, _ = font.glyphset([font.glyph_index(ord("l")), font.glyph_index(ord("|"))], skip_unsupported=False)
     gs = GlyphSet([big.glyph(0), tall.glyph(0), tall.glyph(1)])
     s_big = np.float32(0.05)
-    c0, r0, w0, h0 = text_ref.cell(gs.boxes[0], s_big, 0, 0)
+    c0, r0, w0, h0 = tw.plain_cell(gs.boxes[0], s_big, 0, 0)
     s_tall = np.float32(700) / np.float32(2048)                          # > 2048 sample rows at n = 4
-    c1, r1, w1, h1 = text_ref.cell(gs.boxes[1], s_tall, 0, 0)
+    c1, r1, w1, h1 = tw.plain_cell(gs.boxes[1], s_tall, 0, 0)
     assert 4 * h1 > 2048
     places = rg.make_places([(0, -64 * c0 + 37, -r0), (0, -64 * c0 + 64 * 9 + 5, -r0 + 4),
                              (1, -64 * c1 + 21, -r1), (2, -64 * c1 + 64 * 30 + 50, -r1)])
@@ -201,14 +149,14 @@ def test_large_glyph_and_tall_cell(ctx):
     clears = [(0, 0, 0, 0), (255, 255, 255, 255)]
     info = {}
     with closing(fr.DeviceGlyphSet(ctx, gs)) as dgs:
-        got = _render(ctx, dgs, places, cols, runs, clears, shape, 4, True, SRGB, plan_out=info)
+        got = G.render_rgba(ctx, dgs, places, cols, runs, clears, G.sent4(shape, SENT), 4, True, SRGB, info=info)
         assert info["stats"] == {"jobs_cov4": 0, "jobs_general": 4}, info
         assert info["pixels"] == sum(int(r["w"]) * int(r["h"]) for r in runs)
         assert "fr::text_srgb_kernel<4, 0, 1> x" in info["describe"], info
-        assert np.array_equal(got, _twin(gs, places, cols, runs, clears, shape, 4, True, SRGB))
-        got = _render(ctx, dgs, places, cols, runs, clears, shape, 2, False, SRGB | FILL | BGRA, plan_out=info)
+        assert np.array_equal(got, G.twin_rgba("plain", gs, places, cols, runs, clears, G.sent4(shape, SENT), 4, True, SRGB))
+        got = G.render_rgba(ctx, dgs, places, cols, runs, clears, G.sent4(shape, SENT), 2, False, SRGB | FILL | BGRA, info=info)
         assert "fr::text_srgb_kernel<2, 1, 1> x" in info["describe"], info
-        assert np.array_equal(got, _twin(gs, places, cols, runs, clears, shape, 2, False, SRGB | FILL | BGRA))
+        assert np.array_equal(got, G.twin_rgba("plain", gs, places, cols, runs, clears, G.sent4(shape, SENT), 2, False, SRGB | FILL | BGRA))
 
 
 # ---- 5. thousands of runs, and the graph / overlap options ---------------------------------------------------------------
@@ -217,7 +165,7 @@ def test_many_runs_graph_and_overlap(ctx):
     rng = np.random.default_rng(2026)
     alphabet = np.array(list("abcdefghijklmnopqrstuvwxyzABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789ffjT.,;!? "))
     strings = ["".join(rng.choice(alphabet, int(rng.integers(3, 24)))) for _ in range(2500)]
-    gs, places, runs, (H, W) = tr.lines(font, strings, 14, pad=1)
+    gs, places, runs, (H, W) = tw.lines(font, strings, 14, pad=1)
     half = len(runs) // 2
     y_off = int(runs[half]["out_y"]) - 1
     runs["out_x"][half:] += W
@@ -231,10 +179,10 @@ def test_many_runs_graph_and_overlap(ctx):
 
 
 def _many_runs(ctx, dgs, gs, places, cols, runs, clears, shape, half, rng):
-    base = _render(ctx, dgs, places, cols, runs, clears, shape)
-    _check_borders(base, runs)
+    base = G.render_rgba(ctx, dgs, places, cols, runs, clears, G.sent4(shape, SENT), flags=SRGB)
+    G.check_borders(base, runs, SENT)
     which = sorted(rng.choice(len(runs), 40, replace=False).tolist()) + [half - 1, half, len(runs) - 1]
-    want = _twin(gs, places, cols, runs, clears, shape, which=which)
+    want = G.twin_rgba("plain", gs, places, cols, runs, clears, G.sent4(shape, SENT), flags=SRGB, which=which)
     for r in which:
         run = runs[r]
         sl = np.s_[run["out_y"]:run["out_y"] + run["h"], run["out_x"]:run["out_x"] + run["w"]]
@@ -242,12 +190,12 @@ def _many_runs(ctx, dgs, gs, places, cols, runs, clears, shape, half, rng):
     try:
         ctx.set_option("graph", 1)
         for _ in range(3):
-            assert np.array_equal(_render(ctx, dgs, places, cols, runs, clears, shape), base)
-        assert np.array_equal(_render(ctx, dgs, places, cols, runs, clears, shape, flags=SRGB | BGRA), _swapped(base, runs))
+            assert np.array_equal(G.render_rgba(ctx, dgs, places, cols, runs, clears, G.sent4(shape, SENT), flags=SRGB), base)
+        assert np.array_equal(G.render_rgba(ctx, dgs, places, cols, runs, clears, G.sent4(shape, SENT), flags=SRGB | BGRA), _swapped(base, runs))
         ctx.set_option("graph", 0)
         for ov in (0, 2):
             ctx.set_option("overlap", ov)
-            assert np.array_equal(_render(ctx, dgs, places, cols, runs, clears, shape), base)
+            assert np.array_equal(G.render_rgba(ctx, dgs, places, cols, runs, clears, G.sent4(shape, SENT), flags=SRGB), base)
     finally:
         ctx.set_option("graph", 0)
         ctx.set_option("overlap", 1)
@@ -315,17 +263,17 @@ def _describe_and_validate(ctx, lib, dgs, gs, places, runs, cols, clears):
 def test_render_text_rgba_srgb(ctx):
     font = load_font("DejaVuSerif-Italic.ttf")
     text = "Tffj a red word"
-    gs, places, runs, shape = tr.lines(font, [text], 27)
+    gs, places, runs, shape = tw.lines(font, [text], 27)
     cols = np.array([(225, 105, 180, 255)] * len(text), np.uint8)
     im = fr.render_text_rgba(font, text, 27, srgb=True, ctx=ctx)
     assert (im.height, im.width) == shape
-    assert np.array_equal(im.as_3d(), ts.render_run(gs, places, cols, runs[0], (0, 0, 0, 0), 4, True))
+    assert np.array_equal(im.as_3d(), tw.rgba_render_run("plain", gs, places, cols, runs[0], (0, 0, 0, 0), None, 4, True, srgb=True))
     plain = fr.render_text_rgba(font, text, 27, ctx=ctx).as_3d()
     assert np.array_equal(im.as_3d()[..., 3], plain[..., 3]) and not np.array_equal(im.as_3d(), plain)
     hl = [(255, 0, 0, 255) if 6 <= k < 9 else (0, 0, 0, 160) for k in range(len(text))]
     im2 = fr.render_text_rgba(font, text, 27, background=(255, 255, 255, 255), colors=hl, samples_per_axis=2,
                               phase=fr.FR_SAMPLE_CORNER, srgb=True, bgra=True, ctx=ctx)
-    want = ts.render_run(gs, places, np.array(hl, np.uint8), runs[0], (255, 255, 255, 255), 2, False, bgr=True)
+    want = tw.rgba_render_run("plain", gs, places, np.array(hl, np.uint8), runs[0], (255, 255, 255, 255), None, 2, False, srgb=True, bgr=True)
     assert np.array_equal(im2.as_3d(), want)
     im3 = fr.render_text_rgba(font, text, 27, bgra=True, ctx=ctx)
     assert np.array_equal(im3.as_3d(), plain[..., [2, 1, 0, 3]])

@@ -1,4 +1,4 @@
-"""CPU suite for the twin of fr_glyph_place_affine text plans (tests/text_affine_ref.py) and for the Python layout that
+"""CPU suite for the twin of fr_glyph_place_affine text plans (tests/text_twin.py) and for the Python layout that
 feeds them (font_renderer_amd/text.py), no GPU: (a) the upright, power-of-two case is fr_glyph_place_ex bit for bit;
 (b) on block glyphs under exact maps the twin equals the winding decided with Fractions; (c) the cell holds the glyph;
 (d) rotated_line's pens and matrices."""
@@ -9,10 +9,8 @@ import numpy as np
 import pytest
 
 import text_affine_cases as ac
-import text_affine_ref as ta
 import text_block_cases as bc
-import text_place_ref as tp
-import text_rgba_ref
+import text_twin as tw
 from fixtures import load_font
 from font_renderer_amd import render_glyph as rg
 from font_renderer_amd import text as T
@@ -24,7 +22,7 @@ GRIDS = [(4, True), (4, False), (2, True), (2, False), (1, True), (1, False)]
 def _ex_lines(font_name, font_size, s, k, seed):
     """the strings as fr_glyph_place_ex runs at scale s and slant k, every pen with its own fractions in both axes"""
     font = load_font(font_name, allow_hinted=True)
-    gs, places, runs, _ = text_rgba_ref.lines(font, STRINGS, font_size, pad=3)
+    gs, places, runs, _ = tw.lines(font, STRINGS, font_size, pad=3)
     rng = np.random.default_rng(seed)
     ex = rg.make_places_ex([(int(p["glyph"]), int(p["pen_x64"]), 64 * int(p["pen_y"]) + int(rng.integers(0, 64)), s, k) for p in places])
     return gs, ex, runs
@@ -36,23 +34,23 @@ def _ex_lines(font_name, font_size, s, k, seed):
 def test_upright_power_of_two_equals_the_ex_twin(s, font_size, k):
     n, center = ((4, True), (2, False), (1, True))[int(round(math.log2(s * 64)))]
     gs, ex, runs = _ex_lines("DejaVuSerif-Italic.ttf" if k else "DejaVuSans.ttf", font_size, s, k, font_size)
-    af = ta.from_ex(ex, runs)
+    af = tw.from_ex(ex, runs)
     assert af["m"][0, 1] == np.float32(s) * np.float32(k) and af["m"][0, 2] == 0
     rng = np.random.default_rng(3)
     colours = rng.integers(0, 256, (len(ex), 4)).astype(np.uint8)
     clear = rng.integers(0, 256, 4).astype(np.uint8)
     for r in range(len(runs)):
         for idx in range(int(runs[r]["first"]), int(runs[r]["first"]) + int(runs[r]["count"])):
-            g, px, py, ps, pk = tp.place_params(ex[idx], runs[r])
-            assert ta.cell(gs.boxes[g], af[idx]["m"], px, py) == tp.cell(gs.boxes[g], ps, pk, px, py), idx
+            g, px, py, ps, pk = tw.ex_place_params(ex[idx], runs[r])
+            assert tw.affine_cell(gs.boxes[g], af[idx]["m"], px, py) == tw.ex_cell(gs.boxes[g], ps, pk, px, py), idx
         for fill in (False, True):
-            want = tp.run_samples(gs, ex, runs[r], n, center, fill)
+            want = tw.coverage_samples("ex", gs, ex, runs[r], n, center, fill)
             assert want.any()
-            assert np.array_equal(ta.run_samples(gs, af, runs[r], n, center, fill), want), (r, fill)
-            assert np.array_equal(ta.rgba_run_samples(gs, af, colours, runs[r], clear, None, n, center, fill),
-                                  tp.rgba_run_samples(gs, ex, colours, runs[r], clear, None, n, center, fill)), (r, fill)
-    assert np.array_equal(ta.rgba_render_run(gs, af, colours, runs[1], clear, None, n, center, True, srgb=True, bgr=True),
-                          tp.rgba_render_run(gs, ex, colours, runs[1], clear, None, n, center, True, srgb=True, bgr=True))
+            assert np.array_equal(tw.coverage_samples("affine", gs, af, runs[r], n, center, fill), want), (r, fill)
+            assert np.array_equal(tw.rgba_samples("affine", gs, af, colours, runs[r], clear, None, n, center, fill),
+                                  tw.rgba_samples("ex", gs, ex, colours, runs[r], clear, None, n, center, fill)), (r, fill)
+    assert np.array_equal(tw.rgba_render_run("affine", gs, af, colours, runs[1], clear, None, n, center, True, srgb=True, bgr=True),
+                          tw.rgba_render_run("ex", gs, ex, colours, runs[1], clear, None, n, center, True, srgb=True, bgr=True))
 
 
 def test_inverse_is_binary64_as_defined():
@@ -61,9 +59,9 @@ def test_inverse_is_binary64_as_defined():
     xx, xy, yx, yy = (float(v) for v in m)
     det = xx * yy - xy * yx                                # (Python floats: binary64, one rounding per operation)
     want = tuple(np.float32(v) for v in (yy / det, -xy / det, -yx / det, xx / det))
-    assert ta.inverse(m) == want
-    assert ta.inverse((0.5, 0.0, 0.0, 0.5)) == (2.0, 0.0, 0.0, 2.0)
-    assert ta.inverse((0.0, -0.25, 0.25, 0.0)) == (0.0, 4.0, -4.0, 0.0)      # a quarter turn: consequence 3
+    assert tw.inverse(m) == want
+    assert tw.inverse((0.5, 0.0, 0.0, 0.5)) == (2.0, 0.0, 0.0, 2.0)
+    assert tw.inverse((0.0, -0.25, 0.25, 0.0)) == (0.0, 4.0, -4.0, 0.0)      # a quarter turn: consequence 3
 
 
 # ---- (b) block glyphs under the eight exact maps: the twin against Fractions ------------------------------------------------
@@ -75,11 +73,11 @@ def test_twin_equals_the_exact_winding_on_block_glyphs(n, center):
     assert {(int(p["pen_x64"]) % 64, int(p["pen_y64"]) % 64) for p in places} == {(0, 0), (37, 0), (0, 37), (37, 37)}
     for run in runs:
         exact = ac.instance_hits(glyphs, places, run, n, center)          # (asserts the margin condition, sample by sample)
-        twin = ta.instance_hits(gs, places, run, n, center, fill=True)
+        twin = tw.instance_hits("affine", gs, places, run, n, center, fill=True)
         assert [e[:3] for e in exact] == [t[:3] for t in twin]
         for (idx, y0, x0, hit, cx, cy), (_, _, _, thit) in zip(exact, twin):
-            g, px, py, m = ta.place_params(places[idx])
-            fcx, fcy = ta.sample_coords(m, px, py, x0, x0 + len(cx[0]) // n, y0, y0 + len(cx) // n, n, center)
+            g, px, py, m = tw.affine_place_params(places[idx])
+            fcx, fcy = tw.affine_sample_coords(m, px, py, x0, x0 + len(cx[0]) // n, y0, y0 + len(cx) // n, n, center)
             assert np.array_equal(fcx.astype(np.float64), np.array(cx, np.float64)), idx   # every (cx, cy) is the exact value
             assert np.array_equal(fcy.astype(np.float64), np.array(cy, np.float64)), idx
             assert np.array_equal(thit, hit), (idx, n, center)
@@ -88,7 +86,7 @@ def test_twin_equals_the_exact_winding_on_block_glyphs(n, center):
 
 def test_block_case_reaches_tile_borders_and_clips_on_four_sides():
     glyphs, places, runs, shape = ac.block_case(4, True)
-    met = ta.met_tiles(bc.glyph_set(glyphs), places, runs)
+    met = tw.met_tiles("affine", bc.glyph_set(glyphs), places, runs)
     assert {(2, 0, 0), (2, 0, 1), (2, 1, 0), (2, 1, 1)} <= met and len({t for t in met if t[0] == 0}) >= 20
     cells = [ac.cell(glyphs[int(p["glyph"])].box, ac.place_of(p)[3], int(p["pen_x64"]), int(p["pen_y64"])) for p in places[:24]]
     assert any(c0 < 64 < c0 + cw or c0 < 128 < c0 + cw for c0, _, cw, _ in cells)          # a cell across a 64-column border
@@ -128,7 +126,7 @@ def _rotated(font_name, size, angle, slant=0.0, mirror=False):
 def test_widening_the_cell_changes_nothing_on_rotated_lines(angle, font_name, size):
     gs, places, runs = _rotated(font_name, size, angle, slant=0.2 if angle == 33 else 0.0)
     n = 2
-    inner = ta.instance_hits(gs, places, runs[0], n, True, fill=True)
+    inner = tw.instance_hits("affine", gs, places, runs[0], n, True, fill=True)
     for idx in range(len(places)):
         if not gs.segments_per_glyph()[int(places[idx]["glyph"])]:
             continue
@@ -137,7 +135,7 @@ def test_widening_the_cell_changes_nothing_on_rotated_lines(angle, font_name, si
         pl = places.copy()
         pl["pen_x64"] += 64 * 300                                       # far from every edge of a huge run: nothing is clipped
         pl["pen_y64"] += 64 * 300
-        (_, y0, x0, hit), = ta.instance_hits(gs, pl, one, n, True, fill=True, widen=1)
+        (_, y0, x0, hit), = tw.instance_hits("affine", gs, pl, one, n, True, fill=True, widen=1)
         ring = hit.copy()
         ring[n:-n, n:-n] = False
         assert not ring.any() and hit.any(), idx
@@ -178,10 +176,10 @@ def test_rotated_line_at_zero_degrees_is_view_line(slant):
     (_, vp, vr), (_, rp, rr) = view, rot
     assert np.array_equal(vp["glyph"], rp["glyph"]) and np.array_equal(vp["pen_x64"], rp["pen_x64"])
     assert np.array_equal(vp["pen_y64"], rp["pen_y64"])
-    assert np.array_equal(ta.from_ex(vp, vr)["m"], rp["m"])
+    assert np.array_equal(tw.from_ex(vp, vr)["m"], rp["m"])
     assert T.rotated_line(font, "", size, 0.0, 0, 0, 10, 10) is None and T.rotated_line(font, "a", size, 0.0, 0, 0, 0, 10) is None
     with pytest.raises(ValueError):
         T.rotated_line(font, "a", size, float("nan"), 0, 0, 10, 10)
     box = font.glyphset([int(font.layout("T", size)[0][0])], skip_unsupported=False)[0].boxes[0]
-    assert T.instance_cell_affine(box, rp["m"][0], 37, 64 * 9 + 5) == ta.cell(box, rp["m"][0], 37, 64 * 9 + 5)
+    assert T.instance_cell_affine(box, rp["m"][0], 37, 64 * 9 + 5) == tw.affine_cell(box, rp["m"][0], 37, 64 * 9 + 5)
     assert T.instance_cell_affine(box, (1 / 64, 0.0, 0.0, 1 / 64), 37, 64 * 9 + 5) == T.instance_cell_ex(box, 1 / 64, 0.0, 37, 64 * 9 + 5)

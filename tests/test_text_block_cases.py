@@ -10,11 +10,7 @@ import fill_rule_ref as FR
 import oracle_lib as O
 import ref_numpy
 import text_block_cases as B
-import text_load_ref as tl
-import text_place_ref as tp
-import text_ref
-import text_rgba_ref as tr
-import text_srgb_ref as ts
+import text_twin as tw
 
 F = np.float32
 
@@ -108,7 +104,7 @@ def _same_samples(glyphs, places, runs, n, center, ex):
     lit = 0
     for run in runs:
         exact = B.run_hits(glyphs, places, run, n, center)
-        twin = (tp if ex else text_ref).run_samples(gs, places, run, n, center, True)
+        twin = tw.coverage_samples("ex" if ex else "plain", gs, places, run, n, center, True)
         assert exact.shape == twin.shape and np.array_equal(exact, twin), (n, center, ex, int(run["first"]))
         lit += int(exact.sum())
     assert B.cells_hold_the_glyphs(glyphs, places, runs, n, center)
@@ -163,7 +159,7 @@ def test_tile_case_is_what_it_claims():
             for tx in range(max(c0, 0) // 64, (min(c0 + cw, 200) - 1) // 64 + 1):
                 lists.setdefault((ty, tx), []).append(k)
     assert len(lists[(2, 0)]) >= 40 and len(lists) >= 10        # one tile lists 40 placements; 10 of the 12 tiles are met
-    assert tp.met_tiles(gs, places, runs[:1]) == {(0, ty, tx) for ty, tx in lists}
+    assert tw.met_tiles("ex", gs, places, runs[:1]) == {(0, ty, tx) for ty, tx in lists}
     assert int(runs[1]["w"]) < 64 and int(runs[1]["out_x"]) % 4 != 0
     # the pen at 55 + 32/64 has a cell of 10 columns: 55 .. 63 and the extra column 64, in the next tile
     assert 4 in lists[(1, 0)] and 4 in lists[(1, 1)] and 5 in lists[(2, 1)] and 5 in lists[(2, 2)]
@@ -192,7 +188,7 @@ def test_reference_rule_twin_equals_the_oracle_on_the_job_cells(oracle):
         gs = B.glyph_set(glyphs)
         assert len(jobs) >= 7
         for j in jobs:
-            pts, cs = text_ref.glyph_arrays(gs, int(j["glyph"]))
+            pts, cs = tw.glyph_arrays(gs, int(j["glyph"]))
             cell = (int(j["min_x"]), int(j["max_y"]), int(j["w"]), int(j["h"]), j["scale"])
             cx, cy = FR.sample_axes(*cell, n, center)
             wd = ref_numpy.winding_at(pts, cs, cx[None, :], cy[:, None])
@@ -204,7 +200,7 @@ def test_reference_rule_twin_equals_the_oracle_on_the_job_cells(oracle):
         # and the consistent rule: exact == twin on the same cells
         exact = B.job_windings(glyphs, jobs, shape, n, center)
         for j in jobs:
-            pts, cs = text_ref.glyph_arrays(gs, int(j["glyph"]))
+            pts, cs = tw.glyph_arrays(gs, int(j["glyph"]))
             cx, cy = FR.sample_axes(int(j["min_x"]), int(j["max_y"]), int(j["w"]), int(j["h"]), j["scale"], n, center)
             oy, ox = int(j["out_y"]) * n, int(j["out_x"]) * n
             assert np.array_equal(FR.winding_fill(pts, cs, cx[None, :], cy[:, None]), exact[oy:oy + len(cy), ox:ox + len(cx)])
@@ -216,15 +212,15 @@ def test_colour_formulas_are_the_definitions():
     rng = np.random.default_rng(5)
     dst = rng.integers(0, 256, (500, 4)).astype(np.int64)
     for col in [(0, 255, 17, 0), (200, 3, 99, 255), (5, 6, 7, 128), (255, 255, 255, 1)]:
-        for mod, fn in ((tr, B.blend_rgba), (ts, B.blend_srgb)):
-            assert np.array_equal(mod.blend(dst, col)[:, :3], fn(np.array(col[:3]), dst[:, :3], col[3]))
+        for blend, fn in ((tw.blend, B.blend_rgba), (tw.srgb_blend, B.blend_srgb)):
+            assert np.array_equal(blend(dst, col)[:, :3], fn(np.array(col[:3]), dst[:, :3], col[3]))
     v = np.arange(256)
-    assert np.array_equal(ts.E[ts.D[v]], v)                     # an untouched sRGB sample resolves to itself
+    assert np.array_equal(tw.E[tw.D[v]], v)                     # an untouched sRGB sample resolves to itself
     for n in (1, 2, 4):
         smp = rng.integers(0, 256, (n, 7 * n, 4)).astype(np.int64)
         parts = [(1, smp.reshape(1, n, 7, n, 4)[0, a, :, b]) for a in range(n) for b in range(n)]
-        assert np.array_equal(tr.resolve(smp, n)[0], B.mix_rgba(parts, n))
-        assert np.array_equal(ts.resolve(smp, n)[0, :, :3], B.mix_srgb([(k, p[:, :3]) for k, p in parts], n))
+        assert np.array_equal(tw.resolve(smp, n)[0], B.mix_rgba(parts, n))
+        assert np.array_equal(tw.srgb_resolve(smp, n)[0, :, :3], B.mix_srgb([(k, p[:, :3]) for k, p in parts], n))
 
 
 def _twin_rows(case, n, srgb, load, count, h):
@@ -234,11 +230,7 @@ def _twin_rows(case, n, srgb, load, count, h):
     run = np.array([(0, count, int(r["w"]), h, 1, 1, r["scale"])], B.rg.RUN_DTYPE)
     ex = "pen_y64" in case.places.dtype.names
     out = case.start[:h + 2].copy()
-    if ex:
-        got = tp.rgba_render_runs(gs, case.places, case.rgba, run, case.clears, out, n, True, False, srgb, False, load)
-    else:
-        got = tl.render_runs(gs, case.places, case.rgba, run, out, n, True, False, srgb) if load else \
-            (ts if srgb else tr).render_runs(gs, case.places, case.rgba, run, case.clears, out, n, True)
+    got = tw.rgba_render_runs("ex" if ex else "plain", gs, case.places, case.rgba, run, case.clears, out, n, True, False, srgb, False, load)
     return got[1:h + 1], case.want[1:h + 1]
 
 
@@ -257,10 +249,7 @@ def test_colour_cases_equal_the_definition_twins_on_their_first_rows(n, ex, srgb
         gs = B.glyph_set(case.glyphs)
         which = [0, 1, 100, 255]
         out = case.start.copy()
-        if ex:
-            tp.rgba_render_runs(gs, case.places, case.rgba, case.runs, case.clears, out, n, True, False, srgb, False, False, which)
-        else:
-            (ts if srgb else tr).render_runs(gs, case.places, case.rgba, case.runs, case.clears, out, n, True, False, which)
+        tw.rgba_render_runs("ex" if ex else "plain", gs, case.places, case.rgba, case.runs, case.clears, out, n, True, False, srgb, False, False, which)
         for r in which:
             assert np.array_equal(out[1 + r], case.want[1 + r]), (build.__name__, r)
 
@@ -272,7 +261,7 @@ def test_the_enumerations_reach_what_they_claim():
     seen = np.zeros(1 << 24, bool)
     seen[(C << 16) | (c << 8) | A] = True
     assert seen.all()
-    L = (ts.D[C] * A + ts.D[c] * (255 - A) + 127) // 255
+    L = (tw.D[C] * A + tw.D[c] * (255 - A) + 127) // 255
     assert len(np.unique(L)) >= 65502 and len(np.unique(L >> 4)) == 4096      # the linear values, the entries of SRGB_K
     assert (case.want[1:-1, 1:-1, 3] == case.A[..., 0]).all()
     bg = B.blend_load_case(4, False, False, bgra=True)
@@ -288,7 +277,7 @@ def test_the_enumerations_reach_what_they_claim():
         k, C, c = (np.broadcast_to(v, case.c.shape).reshape(-1) for v in (case.k, case.C, case.c))
         assert len(np.unique((k << 16) | (C << 8) | c)) == (n * n + 1) * 65536
         if n == 4:
-            L = (k * ts.D[C] + (16 - k) * ts.D[c] + 8) >> 4
+            L = (k * tw.D[C] + (16 - k) * tw.D[c] + 8) >> 4
             assert len(np.unique(L)) >= 60846 and len(np.unique(L >> 4)) >= 4080
         case = B.opaque_clear_case(n, False, False)
         assert len(np.unique(case.C[..., 0] * 256 + case.c[..., 0])) == 65536

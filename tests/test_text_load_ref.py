@@ -1,7 +1,6 @@
 """FR_TEXT_LOAD on the CPU: the flag's value in the header, the Python binding and the Zig binding, and the CPU twin
-(tests/text_load_ref.py) against the consequences the definition states (include/fr_raster.h): untouched pixels come
-back byte-identical, and a uniform destination gives the clear-colour plans' twins (tests/text_rgba_ref.py,
-tests/text_srgb_ref.py)."""
+(tests/text_twin.py) against the consequences the definition states (include/fr_raster.h): untouched pixels come
+back byte-identical, and a uniform destination gives the clear-colour plans' twins."""
 import os
 import re
 
@@ -9,9 +8,7 @@ import numpy as np
 import pytest
 
 import font_renderer_amd as fr
-import text_load_ref as tl
-import text_rgba_ref as tr
-import text_srgb_ref as ts
+import text_twin as tw
 from font_renderer_amd import _lib
 from fixtures import load_font
 
@@ -30,13 +27,13 @@ def test_flag_value_everywhere():
 
 def test_decode_then_encode_is_the_identity():
     """consequence 1 for sRGB: E(D[v]) = v for all 256 values"""
-    assert np.array_equal(ts.encode(ts.D), np.arange(256))
+    assert np.array_equal(tw.srgb_encode(tw.D), np.arange(256))
 
 
 @pytest.fixture(scope="module")
 def italic():
     font = load_font("DejaVuSerif-Italic.ttf")
-    gs, places, runs, shape = tr.lines(font, ["ffi fj Tf", "Wavy /// fff", "WoWfj"], 19, pad=1)
+    gs, places, runs, shape = tw.lines(font, ["ffi fj Tf", "Wavy /// fff", "WoWfj"], 19, pad=1)
     k0 = int(runs[2]["first"])                                  # glyphs packed so close that their ink overlaps
     places["pen_x64"][k0:k0 + 5] = places["pen_x64"][k0] + np.array([0, 203, 390, 611, 777])
     return gs, places, runs, shape
@@ -56,16 +53,15 @@ def test_uniform_destination_is_the_clear_colour_plan(italic, srgb, n, center, f
     """consequence 2: a destination holding Q_r in every pixel of run r gives the plan without FR_TEXT_LOAD"""
     gs, places, runs, _ = italic
     cols = _colours(len(places), 3 + n, opaque)
-    ref = ts if srgb else tr
     for r, run in enumerate(runs):
         q = tuple(int(v) for v in np.random.default_rng(r).integers(0, 256, 4))
         dst = np.empty((int(run["h"]), int(run["w"]), 4), np.uint8)
         dst[:] = q
-        got = tl.render_run(gs, places, cols, run, dst, n, center, fill, srgb)
-        assert np.array_equal(got, ref.render_run(gs, places, cols, run, q, n, center, fill)), (r, srgb, n)
+        got = tw.rgba_render_run("plain", gs, places, cols, run, None, dst, n, center, fill, srgb)
+        assert np.array_equal(got, tw.rgba_render_run("plain", gs, places, cols, run, q, None, n, center, fill, srgb)), (r, srgb, n)
         if srgb:                           # FR_TEXT_BGRA: the same, read and written as B G R A
-            got = tl.render_run(gs, places, cols, run, ts.bgra(dst), n, center, fill, srgb, bgr=True)
-            assert np.array_equal(got, ts.render_run(gs, places, cols, run, q, n, center, fill, bgr=True))
+            got = tw.rgba_render_run("plain", gs, places, cols, run, None, tw.bgra(dst), n, center, fill, srgb, bgr=True)
+            assert np.array_equal(got, tw.rgba_render_run("plain", gs, places, cols, run, q, None, n, center, fill, True, bgr=True))
 
 
 @pytest.mark.parametrize("srgb", [False, True])
@@ -80,11 +76,11 @@ def test_untouched_pixels_are_identical(italic, srgb, n):
         h, w = int(run["h"]), int(run["w"])
         dst = rng.integers(0, 256, (h, w, 4)).astype(np.uint8)
         lit = np.zeros((h * n, w * n), bool)
-        for k, y0, x0, hit in tr.instance_hits(gs, places, run, n, True):
+        for k, y0, x0, hit in tw.instance_hits("plain", gs, places, run, n, True):
             lit[y0 * n:y0 * n + hit.shape[0], x0 * n:x0 * n + hit.shape[1]] |= hit
         lit = lit.reshape(h, n, w, n).any(axis=(1, 3))
         for bgr in (False, True):
-            got = tl.render_run(gs, places, cols, run, dst, n, True, False, srgb, bgr)
+            got = tw.rgba_render_run("plain", gs, places, cols, run, None, dst, n, True, False, srgb, bgr)
             assert np.array_equal(got[~lit], dst[~lit]), (srgb, n, bgr)
             changed += int((got[lit] != dst[lit]).any(axis=1).sum())
     assert changed > 0
@@ -96,8 +92,8 @@ def test_second_render_composites_over_the_first(italic):
     cols = _colours(len(places), 9, opaque=False)
     cols[:, 3] = 120
     out = np.random.default_rng(5).integers(0, 256, shape + (4,)).astype(np.uint8)
-    once = tl.render_runs(gs, places, cols, runs, out.copy(), 4, True)
-    twice = tl.render_runs(gs, places, cols, runs, once.copy(), 4, True)
+    once = tw.rgba_render_runs("plain", gs, places, cols, runs, None, out.copy(), 4, True, load=True)
+    twice = tw.rgba_render_runs("plain", gs, places, cols, runs, None, once.copy(), 4, True, load=True)
     assert not np.array_equal(once, twice)
 
 

@@ -1,5 +1,5 @@
 """FR_TEXT_OVER on the CPU (include/fr_raster.h): the flag's value in the header and its mirrors, the alpha formula against
-rationals, the consequences the header states on the assembled twin (tests/text_over_ref.py), the exact cases'
+rationals, the consequences the header states on the assembled twin (tests/text_twin.py), the exact cases'
 own expectations (tests/text_over_cases.py), the blend = 2 lines of host/text_plan_selftest, and fr_rgba_unpremultiply
 for every (c, a)."""
 import os
@@ -13,9 +13,7 @@ import pytest
 import font_renderer_amd as fr
 import text_block_cases as B
 import text_over_cases as OC
-import text_over_ref as tov
-import text_rgba_ref as tr
-import text_srgb_ref as ts
+import text_twin as tw
 from font_renderer_amd import _lib
 from fixtures import load_font
 
@@ -41,13 +39,13 @@ def test_alpha_formula_is_round_half_up_of_source_over():
             exact = Fraction(255 * A + a * (255 - A), 255)
             assert (exact * 2).denominator != 2 or exact.denominator == 1
             want = (2 * exact.numerator + exact.denominator) // (2 * exact.denominator)          # floor(exact + 1/2)
-            assert tov.alpha_over(a, A) == want, (a, A)
+            assert tw.alpha_over(a, A) == want, (a, A)
     a, A = np.meshgrid(np.arange(256, dtype=np.int64), np.arange(256, dtype=np.int64), indexing="ij")
-    want = tov.alpha_over(a, A)
+    want = tw.alpha_over(a, A)
     assert want.min() == 0 and want.max() == 255 and (want >= np.maximum(a, A) - 0).all()        # over never lowers alpha
     for Ak in (0, 1, 127, 128, 254, 255):
         dst = np.repeat(np.arange(256, dtype=np.int64)[:, None], 4, axis=1)
-        assert np.array_equal(tr.blend(dst, (255, 255, 255, Ak))[:, 0], want[:, Ak])
+        assert np.array_equal(tw.blend(dst, (255, 255, 255, Ak))[:, 0], want[:, Ak])
     # what the UNORM kernel computes: x = 255 A + a (255 - A) <= 65025 lies in blend2's proven domain
     assert (255 * A + a * (255 - A)).max() == 65025
 
@@ -56,7 +54,7 @@ def test_alpha_formula_is_round_half_up_of_source_over():
 def word():
     """one short italic string whose glyphs overlap, as one run with a margin"""
     font = load_font("DejaVuSerif-Italic.ttf")
-    gs, places, runs, shape = tr.lines(font, ["fjW"], 17, pad=1)
+    gs, places, runs, shape = tw.lines(font, ["fjW"], 17, pad=1)
     places["pen_x64"][:3] = places["pen_x64"][0] + np.array([0, 150, 330])
     return gs, places, runs, shape
 
@@ -70,36 +68,36 @@ CLEAR = np.array([(10, 60, 90, 128)], np.uint8)
 def test_consequences_on_the_assembled_twin(word, srgb, n, center, fill):
     gs, places, runs, shape = word
     sent = np.full(shape + (4,), 0x5b, np.uint8)
-    got = tov.render_runs("plain", gs, places, COLS, runs, CLEAR, sent, n, center, fill, srgb)
-    plain = tov.plain_twin("plain", gs, places, COLS, runs, CLEAR, sent.copy(), n, center, fill, srgb, False, False)
+    got = tw.over_render_runs("plain", gs, places, COLS, runs, CLEAR, sent, n, center, fill, srgb)
+    plain = tw.rgba_render_runs("plain", gs, places, COLS, runs, CLEAR, sent.copy(), n, center, fill, srgb, False, False)
     assert np.array_equal(got[..., :3], plain[..., :3]) and (got[..., 3] != plain[..., 3]).any()      # 1
     # 2: every A = 255 is the plan without the flag
     opaque = COLS.copy()
     opaque[:, 3] = 255
-    assert np.array_equal(tov.render_runs("plain", gs, places, opaque, runs, CLEAR, sent, n, center, fill, srgb),
-                          tov.plain_twin("plain", gs, places, opaque, runs, CLEAR, sent.copy(), n, center, fill, srgb, False, False))
+    assert np.array_equal(tw.over_render_runs("plain", gs, places, opaque, runs, CLEAR, sent, n, center, fill, srgb),
+                          tw.rgba_render_runs("plain", gs, places, opaque, runs, CLEAR, sent.copy(), n, center, fill, srgb, False, False))
     # 3: an instance with A = 0 leaves every sample unchanged: the plan without that placement (its glyph has no other)
     zero = COLS.copy()
     zero[1, 3] = 0
     without = np.array(runs).copy()
     two = np.array(places)[[0, 2]]
     without["count"] = 2
-    assert np.array_equal(tov.render_runs("plain", gs, places, zero, runs, CLEAR, sent, n, center, fill, srgb),
-                          tov.render_runs("plain", gs, two, zero[[0, 2]], without, CLEAR, sent, n, center, fill, srgb))
-    replaced = tov.plain_twin("plain", gs, places, zero, runs, CLEAR, sent.copy(), n, center, fill, srgb, False, False)
+    assert np.array_equal(tw.over_render_runs("plain", gs, places, zero, runs, CLEAR, sent, n, center, fill, srgb),
+                          tw.over_render_runs("plain", gs, two, zero[[0, 2]], without, CLEAR, sent, n, center, fill, srgb))
+    replaced = tw.rgba_render_runs("plain", gs, places, zero, runs, CLEAR, sent.copy(), n, center, fill, srgb, False, False)
     assert (replaced[..., 3] == 0).any() or n > 1                       # (without the flag A = 0 sets alpha to 0)
     # 4: under LOAD over alpha 255 every alpha stays 255
     noise = np.random.default_rng(n).integers(0, 256, shape + (4,)).astype(np.uint8)
     noise[..., 3] = 255
-    over = tov.render_runs("plain", gs, places, COLS, runs, None, noise, n, center, fill, srgb, False, True)
+    over = tw.over_render_runs("plain", gs, places, COLS, runs, None, noise, n, center, fill, srgb, False, True)
     assert (over[..., 3] == 255).all() and not np.array_equal(over, noise)
-    holes = tov.plain_twin("plain", gs, places, COLS, runs, None, noise.copy(), n, center, fill, srgb, False, True)
+    holes = tw.rgba_render_runs("plain", gs, places, COLS, runs, None, noise.copy(), n, center, fill, srgb, False, True)
     assert (holes[..., 3] != 255).any() and np.array_equal(holes[..., :3], over[..., :3])
     # 5: one instance (R, G, B, A) over (0, 0, 0, 0): alpha = (k A + n^2/2) div n^2 for the k samples it lights
     run1 = np.array(runs).copy()
     run1["count"] = 1
-    one = tov.render_runs("plain", gs, places, COLS, run1, np.zeros((1, 4), np.uint8), sent, n, center, fill, srgb)
-    (_, y0, x0, hit), = tr.instance_hits(gs, places, run1[0], n, center, fill)
+    one = tw.over_render_runs("plain", gs, places, COLS, run1, np.zeros((1, 4), np.uint8), sent, n, center, fill, srgb)
+    (_, y0, x0, hit), = tw.instance_hits("plain", gs, places, run1[0], n, center, fill)
     k = np.zeros((int(run1[0]["h"]), int(run1[0]["w"])), np.int64)
     k[y0:y0 + hit.shape[0] // n, x0:x0 + hit.shape[1] // n] = hit.reshape(hit.shape[0] // n, n, hit.shape[1] // n, n).sum(axis=(1, 3))
     oy, ox = int(run1[0]["out_y"]), int(run1[0]["out_x"])
@@ -111,18 +109,17 @@ def test_consequences_on_the_assembled_twin(word, srgb, n, center, fill):
 def test_the_other_forms_assemble_alike(word, form):
     """with slant 0 and whole baselines the _ex twin, and with m = {s, 0, 0, s} at a power-of-two size the affine twin, give
     the upright form's image: the assembly goes through each form's own twin"""
-    import text_affine_ref as ta
     from font_renderer_amd import render_glyph as rg
     gs, places, runs, shape = word
     sent = np.full(shape + (4,), 0x5b, np.uint8)
     ex = rg.make_places_ex([(int(p["glyph"]), int(p["pen_x64"]), 64 * int(p["pen_y"]), 0.0, 0.0) for p in places])
-    want = tov.render_runs("plain", gs, places, COLS, runs, CLEAR, sent, 2, True, True, True)
-    assert np.array_equal(tov.render_runs("ex", gs, ex, COLS, runs, CLEAR, sent, 2, True, True, True), want)
+    want = tw.over_render_runs("plain", gs, places, COLS, runs, CLEAR, sent, 2, True, True, True)
+    assert np.array_equal(tw.over_render_runs("ex", gs, ex, COLS, runs, CLEAR, sent, 2, True, True, True), want)
     if form == "affine":
         p2 = np.array(runs).copy()
         p2["scale"] = np.float32(2.0 ** -7)
-        want = tov.render_runs("ex", gs, ex, COLS, p2, CLEAR, sent, 2, True, True, False)
-        assert np.array_equal(tov.render_runs("affine", gs, ta.from_ex(ex, p2), COLS, p2, CLEAR, sent, 2, True, True, False), want)
+        want = tw.over_render_runs("ex", gs, ex, COLS, p2, CLEAR, sent, 2, True, True, False)
+        assert np.array_equal(tw.over_render_runs("affine", gs, tw.from_ex(ex, p2), COLS, p2, CLEAR, sent, 2, True, True, False), want)
 
 
 @pytest.mark.parametrize("srgb", [False, True])
@@ -172,7 +169,7 @@ def _unpremultiply_want(c, a, srgb):
         return 0
     if not srgb:
         return min(255, (255 * c + a // 2) // a)
-    return int(ts.E[min(65535, (255 * int(ts.D[c]) + a // 2) // a)])
+    return int(tw.E[min(65535, (255 * int(tw.D[c]) + a // 2) // a)])
 
 
 @pytest.mark.parametrize("srgb", [False, True])

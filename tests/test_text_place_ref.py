@@ -1,25 +1,18 @@
-"""CPU suite for the twin of fr_glyph_place_ex text plans (tests/text_place_ref.py) and for the Python layout that feeds
+"""CPU suite for the twin of fr_glyph_place_ex text plans (tests/text_twin.py) and for the Python layout that feeds
 them (font_renderer_amd/text.py), no GPU: the two consequences of the definition (include/fr_raster.h) — degenerate
 parameters are fr_glyph_place bit for bit, a +64 shift of pen_y64 is a one-row shift —, that the slanted cell holds the
 glyph, the span layout, and the validation of the new Python arguments."""
 import numpy as np
 import pytest
 
-import text_place_ref as tp
-import text_ref
-import text_rgba_ref
-import text_srgb_ref
+import text_twin as tw
 from fixtures import load_font
 from font_renderer_amd import render_glyph as rg
 from font_renderer_amd import text as T
+from text_gpu import degenerate
 
 STRINGS = ["ffi fj Tf ff", "Tjfyfgf jjj", "Wavy /// fff", "ƒ∫ fî T,"]
 SLANTS = [-1.0, -0.36, -0.2, 0.0, 0.2, 0.36397, 1.0, 4.0]          # those of tests/test_gpu_text_place.py's twin test
-
-
-def degenerate(places, scale=0.0):
-    """fr_glyph_place rows as fr_glyph_place_ex: pen_y64 = 64 pen_y, scale 0 (or the given one), slant 0"""
-    return rg.make_places_ex([(int(p["glyph"]), int(p["pen_x64"]), 64 * int(p["pen_y"]), scale, 0.0) for p in places])
 
 
 def _random_instances(ascii_set, rng, count):
@@ -33,7 +26,7 @@ def _random_instances(ascii_set, rng, count):
             continue
         scale = np.float32(int(rng.integers(12, 49))) / np.float32(int(ascii_set.g_upm[g]))
         pen_x64 = int(rng.integers(0, 64))
-        c0, r0, w, h = text_ref.cell(gs.boxes[g], scale, pen_x64, 0)
+        c0, r0, w, h = tw.plain_cell(gs.boxes[g], scale, pen_x64, 0)
         runs.append((len(rows), 1, w + 2, h + 2, 0, 0, scale))
         rows.append((g, pen_x64 - 64 * c0 + 64, -r0 + 1))
     return rg.make_places(rows), rg.make_runs(runs)
@@ -47,32 +40,32 @@ def test_degenerate_equals_text_ref_on_the_ascii_set(ascii_set, n, center, fill)
     rng = np.random.default_rng(1000 + 10 * n + 2 * center + fill)
     places, runs = _random_instances(ascii_set, rng, 12)
     for r in range(len(runs)):
-        want = text_ref.run_samples(ascii_set.gs, places, runs[r], n, center, fill)
+        want = tw.coverage_samples("plain", ascii_set.gs, places, runs[r], n, center, fill)
         for scale in (0.0, float(runs[r]["scale"])):
-            got = tp.run_samples(ascii_set.gs, degenerate(places, scale), runs[r], n, center, fill)
+            got = tw.coverage_samples("ex", ascii_set.gs, degenerate(places, scale), runs[r], n, center, fill)
             assert np.array_equal(got, want), (r, n, center, fill, scale)
         k = int(runs[r]["first"])
-        assert (tp.cell(ascii_set.gs.boxes[int(places[k]["glyph"])], runs[r]["scale"], 0.0, int(places[k]["pen_x64"]), 64 * int(places[k]["pen_y"]))
-                == text_ref.cell(ascii_set.gs.boxes[int(places[k]["glyph"])], runs[r]["scale"], int(places[k]["pen_x64"]), int(places[k]["pen_y"])))
+        assert (tw.ex_cell(ascii_set.gs.boxes[int(places[k]["glyph"])], runs[r]["scale"], 0.0, int(places[k]["pen_x64"]), 64 * int(places[k]["pen_y"]))
+                == tw.plain_cell(ascii_set.gs.boxes[int(places[k]["glyph"])], runs[r]["scale"], int(places[k]["pen_x64"]), int(places[k]["pen_y"])))
 
 
 @pytest.mark.parametrize("font_size,n,center", [(16, 4, True), (23, 2, False), (40, 1, True), (11, 4, False)])
 def test_degenerate_equals_the_twins_on_italic_strings(font_size, n, center):
     font = load_font("DejaVuSerif-Italic.ttf")
-    gs, places, runs, _ = text_rgba_ref.lines(font, STRINGS, font_size, pad=2)
+    gs, places, runs, _ = tw.lines(font, STRINGS, font_size, pad=2)
     ex = degenerate(places)
     rng = np.random.default_rng(font_size)
     colours = rng.integers(0, 256, (len(places), 4)).astype(np.uint8)
     clear = rng.integers(0, 256, 4).astype(np.uint8)
     for fill in (False, True):
         for r in range(len(runs)):
-            assert np.array_equal(tp.run_samples(gs, ex, runs[r], n, center, fill),
-                                  text_ref.run_samples(gs, places, runs[r], n, center, fill)), (r, fill)
-            assert np.array_equal(tp.rgba_run_samples(gs, ex, colours, runs[r], clear, None, n, center, fill),
-                                  text_rgba_ref.run_samples(gs, places, colours, runs[r], clear, n, center, fill)), (r, fill)
+            assert np.array_equal(tw.coverage_samples("ex", gs, ex, runs[r], n, center, fill),
+                                  tw.coverage_samples("plain", gs, places, runs[r], n, center, fill)), (r, fill)
+            assert np.array_equal(tw.rgba_samples("ex", gs, ex, colours, runs[r], clear, None, n, center, fill),
+                                  tw.rgba_samples("plain", gs, places, colours, runs[r], clear, None, n, center, fill)), (r, fill)
     r = 1
-    assert np.array_equal(tp.rgba_render_run(gs, ex, colours, runs[r], clear, None, n, center, False, srgb=True, bgr=True),
-                          text_srgb_ref.render_run(gs, places, colours, runs[r], clear, n, center, False, bgr=True))
+    assert np.array_equal(tw.rgba_render_run("ex", gs, ex, colours, runs[r], clear, None, n, center, False, srgb=True, bgr=True),
+                          tw.rgba_render_run("plain", gs, places, colours, runs[r], clear, None, n, center, False, srgb=True, bgr=True))
 
 
 # ---- consequence 2: pen_y64 + 64 is the same image one row down --------------------------------------------------------
@@ -86,9 +79,9 @@ def test_a_64_shift_of_pen_y64_is_one_row(ascii_set, fill):
         scale = np.float32(int(rng.integers(12, 49))) / np.float32(int(ascii_set.g_upm[g]))
         slant = float(rng.choice(SLANTS))
         pen_x64 = int(rng.integers(0, 64))
-        c0, r0, w, h = tp.cell(gs.boxes[g], scale, slant, pen_x64, fy64)
+        c0, r0, w, h = tw.ex_cell(gs.boxes[g], scale, slant, pen_x64, fy64)
         run = rg.make_runs([(0, 1, w + 2, h + 3, 0, 0, np.float32(1.0))])[0]
-        at = lambda y64: tp.run_samples(gs, rg.make_places_ex([(g, pen_x64 - 64 * c0 + 64, y64, scale, slant)]), run, n, center, fill)
+        at = lambda y64: tw.coverage_samples("ex", gs, rg.make_places_ex([(g, pen_x64 - 64 * c0 + 64, y64, scale, slant)]), run, n, center, fill)
         base, down = at(fy64 - 64 * r0 + 64), at(fy64 - 64 * r0 + 128)
         assert base.any()
         assert np.array_equal(down[n:], base[:-n]) and not down[:n].any(), (fy64, n, center, slant)
@@ -99,10 +92,10 @@ def test_fractional_baseline_moves_the_samples(ascii_set):
     gs = ascii_set.gs
     g = ascii_set.find("Serif", "f")
     scale = np.float32(40) / np.float32(int(ascii_set.g_upm[g]))
-    c0, r0, w, h = tp.cell(gs.boxes[g], scale, 0.0, 0, 0)
-    assert tp.cell(gs.boxes[g], scale, 0.0, 0, 32)[3] == h + 1
+    c0, r0, w, h = tw.ex_cell(gs.boxes[g], scale, 0.0, 0, 0)
+    assert tw.ex_cell(gs.boxes[g], scale, 0.0, 0, 32)[3] == h + 1
     run = rg.make_runs([(0, 1, w, h + 2, 0, 0, scale)])[0]
-    img = [tp.render_run(gs, rg.make_places_ex([(g, -64 * c0, -64 * r0 + d, 0.0, 0.0)]), run, 4, True) for d in (0, 32, 64)]
+    img = [tw.render_run("ex", gs, rg.make_places_ex([(g, -64 * c0, -64 * r0 + d, 0.0, 0.0)]), run, 4, True) for d in (0, 32, 64)]
     assert not np.array_equal(img[1], img[0]) and not np.array_equal(img[1], img[2])
     assert np.array_equal(img[2][1:], img[0][:-1])
 
@@ -123,11 +116,11 @@ def test_the_slanted_cell_holds_the_glyph(ascii_set, slant):
             continue
         scale = np.float32(int(rng.integers(16, 49))) / np.float32(int(ascii_set.g_upm[g]))
         pen_x64, fy64 = int(rng.integers(0, 64)), int(rng.integers(0, 64))
-        c0, r0, w, h = tp.cell(gs.boxes[g], scale, slant, pen_x64, fy64)
+        c0, r0, w, h = tw.ex_cell(gs.boxes[g], scale, slant, pen_x64, fy64)
         run = rg.make_runs([(0, 1, w + 8, h + 2, 0, 0, scale)])[0]
         places = rg.make_places_ex([(g, pen_x64 - 64 * c0 + 64 * 4, fy64 - 64 * r0 + 64, 0.0, slant)])
-        tight = tp.run_samples(gs, places, run, 4, True, True)
-        wide = tp.run_samples(gs, places, run, 4, True, True, widen=2)
+        tight = tw.coverage_samples("ex", gs, places, run, 4, True, True)
+        wide = tw.coverage_samples("ex", gs, places, run, 4, True, True, widen=2)
         assert tight.any()
         assert np.array_equal(tight, wide), (g, slant, float(scale))
         done += 1
@@ -138,8 +131,8 @@ def test_slant_moves_the_top_of_a_stem_to_the_right(ascii_set):
     g = ascii_set.find("STIX", "l")
     scale = np.float32(48) / np.float32(int(ascii_set.g_upm[g]))
     run = rg.make_runs([(0, 1, 80, 64, 0, 0, scale)])[0]
-    up = tp.render_run(gs, rg.make_places_ex([(g, 64 * 10, 64 * 50, 0.0, 0.0)]), run, 4, True)
-    ob = tp.render_run(gs, rg.make_places_ex([(g, 64 * 10, 64 * 50, 0.0, 0.5)]), run, 4, True)
+    up = tw.render_run("ex", gs, rg.make_places_ex([(g, 64 * 10, 64 * 50, 0.0, 0.0)]), run, 4, True)
+    ob = tw.render_run("ex", gs, rg.make_places_ex([(g, 64 * 10, 64 * 50, 0.0, 0.5)]), run, 4, True)
     cols = lambda im, row: np.nonzero(im[row])[0]
     top = min(np.nonzero(up.any(1))[0])
     assert top == min(np.nonzero(ob.any(1))[0])                      # the shear keeps every height
@@ -189,7 +182,7 @@ def test_span_size_slant_and_rise_reach_the_placements():
     assert min(c[0] for c in cells) >= 0 and max(c[0] + c[2] for c in cells) == w
     for p in places:                                                   # the twin's cell is the package's
         args = (gs.boxes[int(p["glyph"])], p["scale"], p["slant"], int(p["pen_x64"]), int(p["pen_y64"]))
-        assert T.instance_cell_ex(*args) == tp.cell(*args)
+        assert T.instance_cell_ex(*args) == tw.ex_cell(*args)
 
 
 def test_view_line_places_the_zoomed_line():

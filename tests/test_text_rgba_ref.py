@@ -1,4 +1,4 @@
-"""Pins the CPU twin of RGBA text plans (tests/text_rgba_ref.py) to the consequences the definition states
+"""Pins the CPU twin of RGBA text plans (tests/text_twin.py) to the consequences the definition states
 (include/fr_raster.h), checks the kernel's divide-by-255 shortcut over its whole domain, and decodes the 4-channel QOI
 writer with Pillow."""
 import io
@@ -6,8 +6,7 @@ import io
 import numpy as np
 import pytest
 
-import text_ref
-import text_rgba_ref as tr
+import text_twin as tw
 from fixtures import load_font
 
 STRINGS = ["ffi fj Tf", "Wavy /// fff"]
@@ -17,7 +16,7 @@ STRINGS = ["ffi fj Tf", "Wavy /// fff"]
 def italic():
     """two lines of real text, and a third run of glyphs packed so close that their ink overlaps"""
     font = load_font("DejaVuSerif-Italic.ttf")
-    gs, places, runs, shape = tr.lines(font, STRINGS + ["WoWfj"], 19, pad=1)
+    gs, places, runs, shape = tw.lines(font, STRINGS + ["WoWfj"], 19, pad=1)
     k0 = int(runs[2]["first"])
     places["pen_x64"][k0:k0 + 5] = places["pen_x64"][k0] + np.array([0, 203, 390, 611, 777])
     return gs, places, runs, shape
@@ -36,8 +35,8 @@ def test_white_on_transparent_is_the_coverage(italic, n, center, fill):
     gs, places, runs, _ = italic
     white = np.full((len(places), 4), 255, np.uint8)
     for run in runs:
-        got = tr.render_run(gs, places, white, run, (0, 0, 0, 0), n, center, fill)
-        want = text_ref.render_run(gs, places, run, n, center, fill)
+        got = tw.rgba_render_run("plain", gs, places, white, run, (0, 0, 0, 0), None, n, center, fill)
+        want = tw.render_run("plain", gs, places, run, n, center, fill)
         for ch in range(4):
             assert np.array_equal(got[..., ch], want), (n, center, fill, ch)
 
@@ -53,14 +52,14 @@ def test_opaque_colours_last_instance_wins(italic):
         # argmax formulation: the index of the last instance that covers each sample, or -1
         last = np.full((h * n, w * n), -1, np.int64)
         overlap = np.zeros((h * n, w * n), np.int64)
-        for k, y0, x0, hit in tr.instance_hits(gs, places, run, n, True):
+        for k, y0, x0, hit in tw.instance_hits("plain", gs, places, run, n, True):
             sl = np.s_[y0 * n:y0 * n + hit.shape[0], x0 * n:x0 * n + hit.shape[1]]
             last[sl] = np.where(hit, k, last[sl])
             overlap[sl] += hit
         overlaps += int((overlap > 1).sum())
         table = np.vstack([cols.astype(np.int64), clear[None, :]])     # index -1: the clear colour
-        want = tr.resolve(table[last], n)
-        assert np.array_equal(tr.render_run(gs, places, cols, run, clear, n, True), want)
+        want = tw.resolve(table[last], n)
+        assert np.array_equal(tw.rgba_render_run("plain", gs, places, cols, run, clear, None, n, True), want)
     assert overlaps > 0
 
 
@@ -71,8 +70,8 @@ def test_alpha_zero_keeps_rgb_and_clears_alpha(italic):
     cols = np.zeros((len(places), 4), np.uint8)
     cols[:, :3] = _colors(len(places), 3)[:, :3]                     # any RGB: with A = 0 it must not show
     for run in runs:
-        got = tr.render_run(gs, places, cols, run, clear, n, True)
-        k = text_ref.run_samples(gs, places, run, n, True).reshape(int(run["h"]), n, int(run["w"]), n).sum(axis=(1, 3))
+        got = tw.rgba_render_run("plain", gs, places, cols, run, clear, None, n, True)
+        k = tw.coverage_samples("plain", gs, places, run, n, True).reshape(int(run["h"]), n, int(run["w"]), n).sum(axis=(1, 3))
         for ch in range(3):
             assert (got[..., ch] == clear[ch]).all()
         assert np.array_equal(got[..., 3], ((200 * (n * n - k) + n * n // 2) // (n * n)).astype(np.uint8))
@@ -87,15 +86,15 @@ def test_order_matters(italic):
     red, blue = (255, 0, 0, 255), (0, 0, 255, 160)
     cols = np.zeros((len(places), 4), np.uint8)
     cols[k0], cols[k0 + 1] = red, blue
-    a = tr.render_run(gs, places, cols, run, (0, 0, 0, 0), 4, True)
+    a = tw.rgba_render_run("plain", gs, places, cols, run, (0, 0, 0, 0), None, 4, True)
     sw = places.copy()
     sw[k0], sw[k0 + 1] = places[k0 + 1], places[k0]
     cols_sw = cols.copy()
     cols_sw[k0], cols_sw[k0 + 1] = cols[k0 + 1], cols[k0]
-    b = tr.render_run(gs, sw, cols_sw, run, (0, 0, 0, 0), 4, True)
+    b = tw.rgba_render_run("plain", gs, sw, cols_sw, run, (0, 0, 0, 0), None, 4, True)
     assert not np.array_equal(a, b)
     # ... and only where the two instances overlap
-    hits = {k: (y0, x0, hit) for k, y0, x0, hit in tr.instance_hits(gs, places, run, 4, True)}
+    hits = {k: (y0, x0, hit) for k, y0, x0, hit in tw.instance_hits("plain", gs, places, run, 4, True)}
     cover = []
     for k in (k0, k0 + 1):
         y0, x0, hit = hits[k]

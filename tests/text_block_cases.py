@@ -1,7 +1,7 @@
 """Block glyphs: tiny synthetic outlines in even integer font units, rendered at power-of-two scales so that every
 sample coordinate is exact in binary32, and their expected images from integer geometry alone.
 
-Nothing here imports a float twin (ref_numpy, fill_rule_ref, text_ref, ...): everything that decides a pixel is a Python
+Nothing here calls a float twin (ref_numpy, fill_rule_ref, text_twin, ...): everything that decides a pixel is a Python
 int or a fractions.Fraction; numpy only holds the arrays.  Three parts:
 
   * outlines: edge_glyphs() (piece ends, extrema and horizontal edges on sample rows) and cover(k, W, n) (exactly k of
@@ -10,7 +10,7 @@ int or a fractions.Fraction; numpy only holds the arrays.  Three parts:
     with exact rationals, and the sample maps and cells of fr_glyph_place, fr_glyph_place_ex and fr_job copied from
     that header with Fractions;
   * colour expectations: the header's integer formulas (straight RGBA), and for FR_TEXT_SRGB the tables D / E that
-    tests/text_srgb_ref.py builds from the IEC decode in binary64 (definitions, not kernel restatements).
+    tests/text_twin.py builds from the IEC decode in binary64 (definitions, not kernel restatements).
 
 Conditions the generators assert, in exact arithmetic, for every sample of every case:
   * every sample coordinate (cx, cy, and for a slanted placement t and k * cy) is a binary32 value: a multiple of 2^-12
@@ -419,7 +419,7 @@ def blend_rgba(C, c, A):
 
 def blend_srgb(C, c, A):
     """E((D[C] A + D[c] (255 - A) + 127) div 255)"""
-    import text_srgb_ref as ts
+    import text_twin as ts
     C, c, A = (np.asarray(v, np.int64) for v in (C, c, A))
     return ts.E[(ts.D[C] * A + ts.D[c] * (255 - A) + 127) // 255]
 
@@ -432,7 +432,7 @@ def mix_rgba(parts, n):
 
 def mix_srgb(parts, n):
     """E((sum of D over the samples + n^2 / 2) div n^2)"""
-    import text_srgb_ref as ts
+    import text_twin as ts
     tot = sum(np.asarray(k, np.int64) * ts.D[np.asarray(v, np.int64)] for k, v in parts)
     return ts.E[(tot + n * n // 2) // (n * n)]
 

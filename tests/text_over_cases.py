@@ -5,7 +5,7 @@ import numpy as np
 
 import text_block_cases as B
 from font_renderer_amd import render_glyph as rg
-from text_over_ref import alpha_over
+from text_twin import alpha_over
 
 
 def _apply(srgb, state, colour):
