@@ -98,6 +98,24 @@ pub const LayerBlit = extern struct {
     opacity: u32,
 };
 
+/// the parameters of fr_layer_shadow: the layer's window, the destination rectangle, the offset, the stages and the colour
+pub const LayerShadowParams = extern struct {
+    src_x: u32,
+    src_y: u32,
+    w: u32,
+    h: u32,
+    dst_x: u32,
+    dst_y: u32,
+    dst_w: u32,
+    dst_h: u32,
+    dx: i32,
+    dy: i32,
+    spread: u32,
+    blur_radius: u32,
+    blur_passes: u32,
+    rgba: [4]u8,
+};
+
 pub const TextRun = extern struct {
     first: u32,
     count: u32,
@@ -184,6 +202,8 @@ pub extern "c" fn fr_rgba_unpremultiply(rgba: [*]u8, n_pixels: usize, srgb: c_in
 pub extern "c" fn fr_layer_over(ctx: *Ctx, src_dev: *const anyopaque, src_stride_px: usize, src_rows: usize, dst_dev: *anyopaque, dst_stride_px: usize, dst_rows: usize, blits: ?[*]const LayerBlit, n_blits: u32, flags: u32) c_int;
 /// fr_rgba_unpremultiply on the device, over a w x h window of an image in rows of stride_px pixels
 pub extern "c" fn fr_layer_unpremultiply(ctx: *Ctx, rgba_dev: *anyopaque, stride_px: usize, w: u32, h: u32, srgb: c_int) c_int;
+/// the alpha of a layer's window, spread, box-blurred, moved and tinted: a premultiplied layer written over a rectangle of the destination
+pub extern "c" fn fr_layer_shadow(ctx: *Ctx, src_dev: *const anyopaque, src_stride_px: usize, src_rows: usize, dst_dev: *anyopaque, dst_stride_px: usize, dst_rows: usize, shadow: *const LayerShadowParams, flags: u32) c_int;
 // ---- self-tests of the two arithmetic shortcuts (device-side, exhaustive)
 pub extern "c" fn fr_selftest_division(d_lo: u32, d_hi: u32, mismatches: *u64, bad_divisor: ?*u32, bad_x_bits: ?*u32) c_int;
 pub extern "c" fn fr_selftest_sqrt(mismatches: *u64, bad_x_bits: ?*u32) c_int;

@@ -11,10 +11,10 @@ from .image import RGB, RGBA, Gray, GlyphDebug, Winding  # noqa: F401
 from ._lib import (  # noqa: F401
     FR_COVERAGE_U8, FR_FILL_CONSISTENT, FR_SDF_U8, FR_GRAY_DEBUG, FR_MASK_NONZERO, FR_SAMPLE_CENTER, FR_SAMPLE_CORNER,
     FR_LAYER_SRGB, FR_TEXT_BGRA, FR_TEXT_CACHE, FR_TEXT_LOAD, FR_TEXT_OVER, FR_TEXT_SRGB, FR_WINDING_I16, FrError, GlyphPlace, GlyphPlaceAffine, GlyphPlaceEx,
-    Job, LayerBlit, TextRun, lib_path, load_library,
+    Job, LayerBlit, LayerShadowParams, TextRun, lib_path, load_library,
 )
 from .render_glyph import (  # noqa: F401
-    Context, GlyphInfo, Plan, TextPlan, TextPlanRGBA, DeviceGlyphSet, layer_over, layer_unpremultiply, make_blits, make_places, make_places_affine,
+    Context, GlyphInfo, Plan, TextPlan, TextPlanRGBA, DeviceGlyphSet, layer_over, layer_shadow, layer_unpremultiply, make_blits, make_places, make_places_affine,
     make_places_ex, make_runs, renderGlyph, render_glyph_dims,
     windingInGlyph, winding_lattice, exact_lattice, exact_coverage, glyph_debug_render, build_id, srgb_to_linear16,
     linear16_to_srgb,

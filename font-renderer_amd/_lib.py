@@ -13,7 +13,7 @@ FR_TEXT_SRGB, FR_TEXT_BGRA = 8, 4  # flags of fr_text_plan_create_rgba only: lin
 FR_TEXT_LOAD = 32                  # fr_text_plan_create_rgba only: draw over the pixels already in the output
 FR_TEXT_CACHE = 128                # the upright and _ex text plans: each distinct glyph image made once per render, same bytes
 FR_TEXT_OVER = 256                 # the RGBA text plans: source-over alpha (a premultiplied output) instead of alpha replaced
-FR_LAYER_SRGB = 1                  # fr_layer_over's own flag space: composite in linear light
+FR_LAYER_SRGB = 1                  # the flag space of fr_layer_over and fr_layer_shadow: work in linear light
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -61,6 +61,13 @@ class TextRun(C.Structure):      # == fr_text_run
 class LayerBlit(C.Structure):    # == fr_layer_blit
     _fields_ = [("src_x", C.c_uint32), ("src_y", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32),
                 ("dst_x", C.c_int32), ("dst_y", C.c_int32), ("opacity", C.c_uint32)]
+
+
+class LayerShadowParams(C.Structure):    # == fr_layer_shadow_params
+    _fields_ = [("src_x", C.c_uint32), ("src_y", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32),
+                ("dst_x", C.c_uint32), ("dst_y", C.c_uint32), ("dst_w", C.c_uint32), ("dst_h", C.c_uint32),
+                ("dx", C.c_int32), ("dy", C.c_int32), ("spread", C.c_uint32), ("blur_radius", C.c_uint32),
+                ("blur_passes", C.c_uint32), ("rgba", C.c_uint8 * 4)]
 
 
 # every symbol include/fr_raster.h declares: (name, restype, argtypes)
@@ -134,6 +141,7 @@ SYMBOLS = [
     ("fr_rgba_unpremultiply", C.c_int, [_P, C.c_size_t, C.c_int]),
     ("fr_layer_over", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, _P, C.c_uint32, C.c_uint32]),
     ("fr_layer_unpremultiply", C.c_int, [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.c_int]),
+    ("fr_layer_shadow", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.POINTER(LayerShadowParams), C.c_uint32]),
     ("fr_selftest_sqrt", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     ("fr_selftest_division", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("fr_selftest_row_cuts", C.c_int, [_P, _P, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),

@@ -1,7 +1,9 @@
-// fr_api_layer.hip — C ABI (include/fr_raster.h): fr_layer_over and fr_layer_unpremultiply.  The checks, the clipping and
-// the tile table are fr_layer_plan.cpp's; this unit stages the table and launches the kernels of fr_layer.hip.
+// fr_api_layer.hip — C ABI (include/fr_raster.h): fr_layer_over, fr_layer_unpremultiply and fr_layer_shadow.  The checks, the
+// clipping and the tile table are fr_layer_plan.cpp's, the shadow's stages fr_layer_shadow_plan.cpp's; this unit stages the
+// table, keeps the shadow's planes and launches the kernels of fr_layer.hip and fr_layer_shadow.hip.
 #include "fr_internal.hpp"
 #include "fr_layer.hpp"
+#include "fr_layer_shadow.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -22,6 +24,25 @@ static int layer_table_room(fr_ctx *ctx, size_t n)
     ctx->layer_tab.alloc(e, cap * sizeof(fr::LayerTile));
     if (e != hipSuccess) return hip_fail(e, "hipMalloc(&ctx->layer_tab, cap)");
     ctx->layer_cap = cap;
+    return FR_OK;
+}
+
+// Room for need[i] bytes in plane i of the context.  A stage in flight may still use an earlier plane, so growing waits for
+// the stream, once, as the tile table does; a plane that cannot grow stays as it was.
+static int shadow_plane_room(fr_ctx *ctx, const uint64_t need[2])
+{
+    if (need[0] <= ctx->shadow_cap[0] && need[1] <= ctx->shadow_cap[1]) return FR_OK;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (int i = 0; i < 2; ++i) {
+        if (need[i] <= ctx->shadow_cap[i]) continue;
+        const size_t cap = (size_t)(need[i] + need[i] / 4);
+        hipError_t e = hipSuccess;
+        DevBuf<unsigned char> grown;
+        grown.alloc(e, cap);
+        if (e != hipSuccess) return hip_fail(e, "hipMalloc(&ctx->shadow_plane, cap)");
+        ctx->shadow_plane[i] = std::move(grown);
+        ctx->shadow_cap[i] = cap;
+    }
     return FR_OK;
 }
 
@@ -60,6 +81,77 @@ int fr_layer_unpremultiply(fr_ctx *ctx, void *rgba_dev, size_t stride_px, uint32
     if (!w || !h) return FR_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(fr::launch_layer_unpremultiply(srgb != 0, static_cast<uint32_t *>(rgba_dev), stride_px, w, h, ctx->stream));
+    return FR_OK;
+}
+
+int fr_layer_shadow(fr_ctx *ctx, const void *src_dev, size_t src_stride_px, size_t src_rows, void *dst_dev, size_t dst_stride_px,
+                    size_t dst_rows, const fr_layer_shadow_params *shadow, uint32_t flags)
+{
+    if (!ctx) return fail(FR_E_INVALID, "fr_layer_shadow: ctx is NULL");
+    fr::ShadowPlan p;
+    try {
+        const fr::ShadowIn in{(uintptr_t)src_dev, (uintptr_t)dst_dev, src_stride_px, src_rows, dst_stride_px, dst_rows, shadow, flags};
+        if (const int rc = fr::shadow_plan(in, p)) return rc;
+    } catch (const std::bad_alloc &) {
+        return fail(FR_E_NOMEM, "fr_layer_shadow: host allocation");
+    }
+    if (p.nothing) return FR_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (const int rc = shadow_plane_room(ctx, p.plane_bytes)) return rc;
+    const fr_layer_shadow_params &s = *shadow;
+    const size_t n = p.stages.size();
+    // the input of the stage at hand: the window of the layer, then the plane of the stage before
+    fr::ShadowArgs a{};
+    a.in = src_dev;                                             // (an input without extent is never loaded from)
+    if (!p.zeros) {
+        a.in = static_cast<const uint32_t *>(src_dev) + ((uint64_t)s.src_y * src_stride_px + s.src_x);
+        a.in_w = s.w;
+        a.in_h = s.h;
+    }
+    a.in_pitch = src_stride_px;
+    fr::ShadowRect in_rect{0, 0, 0, 0};                         // its first pixel in window coordinates
+    for (size_t k = 0; k < std::max<size_t>(n, 1); ++k) {
+        const bool last = k + 1 >= n;
+        fr::ShadowOp op = fr::SHADOW_OP_NONE;
+        if (n) {
+            const fr::ShadowStage &st = p.stages[k];
+            op = st.kind == fr::SHADOW_SPREAD ? fr::SHADOW_OP_MAX : fr::SHADOW_OP_BOX;
+            a.radius = st.radius;
+            a.recip_m = st.recip.m;
+            a.recip_shift = st.recip.shift;
+            a.half_w = (2 * st.radius + 1) * (2 * st.radius + 1) / 2;
+        }
+        if (last) {                                            // the whole destination rectangle, tinted
+            uint32_t *first = static_cast<uint32_t *>(dst_dev) + ((uint64_t)s.dst_y * dst_stride_px + s.dst_x);
+            a.out = first;
+            a.out_pitch = dst_stride_px;
+            a.out_w = s.dst_w;
+            a.out_h = s.dst_h;
+            a.off_x = p.want.x0 - in_rect.x0;
+            a.off_y = p.want.y0 - in_rect.y0;
+            a.vec = dst_stride_px % 4 == 0;
+            a.lead = a.vec ? (uint32_t)(((uintptr_t)first >> 2) & 3u) : 0u;
+            a.rgba = (uint32_t)s.rgba[0] | (uint32_t)s.rgba[1] << 8 | (uint32_t)s.rgba[2] << 16 | (uint32_t)s.rgba[3] << 24;
+            a.srgb = flags & FR_LAYER_SRGB;
+        } else {
+            const fr::ShadowStage &st = p.stages[k];
+            a.out = ctx->shadow_plane[k & 1].get();
+            a.out_pitch = st.pitch;
+            a.out_w = (uint32_t)st.out.w();
+            a.out_h = (uint32_t)st.out.h();
+            a.off_x = st.out.x0 - in_rect.x0;
+            a.off_y = st.out.y0 - in_rect.y0;
+        }
+        HIP_TRY(fr::launch_layer_shadow(k == 0, op, last, a, ctx->stream));
+        if (!last) {
+            const fr::ShadowStage &st = p.stages[k];
+            a.in = a.out;
+            a.in_pitch = st.pitch;
+            a.in_w = a.out_w;
+            a.in_h = a.out_h;
+            in_rect = st.out;
+        }
+    }
     return FR_OK;
 }
 

@@ -60,6 +60,9 @@ struct fr_ctx {
     fr::LayerTile *layer_stage = nullptr;
     size_t layer_cap = 0;
     hipEvent_t layer_ev = nullptr;
+    // the two intermediate planes of fr_layer_shadow, one byte per pixel, grown on demand
+    DevBuf<unsigned char> shadow_plane[2];
+    size_t shadow_cap[2] = {0, 0};
 };
 
 // what kernels read of a glyph set

@@ -207,6 +207,14 @@ inline void layer_unpremultiply(Context &ctx, const DeviceImage &image, uint32_t
 {
     check(fr_layer_unpremultiply(ctx.get(), image.pixels, image.stride_px, w, h, srgb ? 1 : 0));
 }
+// fr_layer_shadow: the alpha of a window of the layer, spread, box-blurred, moved by whole pixels and tinted, written as a
+// premultiplied R G B A layer over every pixel of the rectangle of `image` that `shadow` names.  Composite the result with
+// layer_over, then the text over it.  Asynchronous on the context's stream; `shadow` may be reused at once.
+inline void layer_shadow(Context &ctx, const DeviceImage &layer, const DeviceImage &image, const fr_layer_shadow_params &shadow, bool srgb = false)
+{
+    check(fr_layer_shadow(ctx.get(), layer.pixels, layer.stride_px, layer.rows, image.pixels, image.stride_px, image.rows, &shadow,
+                          srgb ? FR_LAYER_SRGB : 0u));
+}
 
 class PlacedText {
 public:

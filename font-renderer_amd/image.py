@@ -143,6 +143,37 @@ class RGBA:                     # an RGBA text plan's image (fr_text_plan_create
         self.data[:] = dst.cpu().numpy()
         return self
 
+    def shadow(self, offset=(0, 0), spread: int = 0, blur_radius: int = 0, blur_passes: int = 0, rgba=(0, 0, 0, 255),
+               pad: int = None, srgb: bool = False, ctx=None) -> "RGBA":
+        """fr_layer_shadow of this premultiplied layer as a new premultiplied layer, `pad` pixels larger on every side
+        (default: the reach spread + blur_passes * blur_radius, which holds the whole shadow at offset (0, 0)); pixel
+        (pad, pad) of the result lies under pixel (0, 0) of this layer moved by `offset`.  Composite it with over(...,
+        x - pad, y - pad), then this layer at (x, y).  The layer is uploaded and the shadow copied back."""
+        import torch
+
+        from . import render_glyph as rg
+        if not isinstance(self.data, np.ndarray) or self.data.dtype != np.uint8 or self.data.shape != (self.width * self.height, 4):
+            raise ValueError(f"RGBA.shadow: data must be a ({self.width * self.height}, 4) uint8 array")
+        reach = int(spread) + (int(blur_passes) * int(blur_radius) if blur_radius and blur_passes else 0)
+        pad = reach if pad is None else int(pad)
+        if pad < 0:
+            raise ValueError(f"pad {pad!r}: expected at least 0")
+        out = RGBA.init(self.width + 2 * pad, self.height + 2 * pad)
+        if out.width == 0 or out.height == 0:
+            return out
+        ctx = ctx or rg.default_context()
+        src = torch.from_numpy(np.ascontiguousarray(self.data).reshape(-1)).to(f"cuda:{ctx.device}")
+        if src.numel() == 0:
+            src = torch.zeros(4, dtype=torch.uint8, device=f"cuda:{ctx.device}")
+        dst = torch.empty((out.width * out.height, 4), dtype=torch.uint8, device=f"cuda:{ctx.device}")
+        torch.cuda.synchronize(ctx.device)
+        rg.layer_shadow(ctx, src.data_ptr(), self.width, self.height, dst.data_ptr(), out.width, out.height,
+                        (0, 0, self.width, self.height), (0, 0, out.width, out.height), (int(offset[0]) + pad, int(offset[1]) + pad),
+                        spread, blur_radius, blur_passes, rgba, srgb)
+        ctx.sync()
+        out.data[:] = dst.cpu().numpy()
+        return out
+
     def getWidth(self) -> int:
         return self.width
 

@@ -287,6 +287,23 @@ def layer_unpremultiply(ctx: Context, ptr: int, stride_px: int, w: int, h: int, 
     L.check(ctx._lib.fr_layer_unpremultiply(ctx._h, C.c_void_p(ptr), stride_px, w, h, 1 if srgb else 0))
 
 
+def layer_shadow(ctx: Context, src_ptr: int, src_stride_px: int, src_rows: int, dst_ptr: int, dst_stride_px: int, dst_rows: int,
+                 window, rect, offset=(0, 0), spread: int = 0, blur_radius: int = 0, blur_passes: int = 0,
+                 rgba=(0, 0, 0, 255), srgb: bool = False, flags: int = 0) -> None:
+    """fr_layer_shadow: the alpha of the window (src_x, src_y, w, h) of the premultiplied layer at device address src_ptr,
+    spread by a square maximum of radius `spread`, blurred by `blur_passes` box passes of radius `blur_radius`, moved by
+    offset = (dx, dy) whole pixels and tinted with the straight colour rgba, written as a premultiplied R G B A layer over
+    every pixel of rect = (dst_x, dst_y, dst_w, dst_h) of the image at dst_ptr (strides and rows in pixels); asynchronous
+    on the context's stream.  srgb: FR_LAYER_SRGB, the colour bytes as an srgb=True render writes them.  window or rect
+    None passes a NULL parameter block (refused)."""
+    p = None
+    if window is not None and rect is not None:
+        p = L.LayerShadowParams(*[int(v) for v in window], *[int(v) for v in rect], int(offset[0]), int(offset[1]), int(spread),
+                                int(blur_radius), int(blur_passes), (C.c_uint8 * 4)(*[int(v) for v in rgba]))
+    L.check(ctx._lib.fr_layer_shadow(ctx._h, C.c_void_p(src_ptr), src_stride_px, src_rows, C.c_void_p(dst_ptr), dst_stride_px, dst_rows,
+                                     None if p is None else C.byref(p), flags | (L.FR_LAYER_SRGB if srgb else 0)))
+
+
 def render_batch(dgs: DeviceGlyphSet, jobs: np.ndarray, mode: int, out: np.ndarray, samples_per_axis: int = 1,
                  sample_phase: int = L.FR_SAMPLE_CORNER, flags: int = 0) -> np.ndarray:
     """fr_render_batch into a HOST array `out` (2-D, u8 or i16 for FR_WINDING_I16)."""

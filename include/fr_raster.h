@@ -667,8 +667,8 @@ int fr_rgba_unpremultiply(uint8_t *rgba, size_t n_pixels, int srgb);
  *     all blits of the call, behind a small kernel that brings the call's tile table into device memory; asynchronous on
  *     the context's stream, in stream order after earlier renders as fr_plan_render is; the caller may reuse `blits` as
  *     soon as the call returns.
- * FR_LAYER_SRGB is the flag space of fr_layer_over alone: no other entry point knows it, and fr_layer_over knows none of
- * the FR_TEXT_ / FR_FILL_ flags.                                                                                          */
+ * FR_LAYER_SRGB is the flag space of fr_layer_over and fr_layer_shadow: no other entry point knows it, and these two know
+ * none of the FR_TEXT_ / FR_FILL_ flags.                                                                                        */
 #define FR_LAYER_SRGB 1u
 
 typedef struct fr_layer_blit {
@@ -687,6 +687,64 @@ int fr_layer_over(fr_ctx *ctx, const void *src_dev, size_t src_stride_px, size_t
  * is read or written.  Asynchronous on the context's stream.  FR_E_INVALID: NULL or a pointer that is not 4-byte aligned,
  * w > stride_px, stride_px beyond 2^26.                                                                                   */
 int fr_layer_unpremultiply(fr_ctx *ctx, void *rgba_dev, size_t stride_px, uint32_t w, uint32_t h, int srgb);
+
+/* ---- the shadow of a finished layer (BUILD-DEFINED; DESIGN.md sections 4.9 and 5) ----------------------------------------
+ * fr_layer_shadow makes a drop shadow, a glow or an outline of a layer: the layer's alpha, spread by a square maximum,
+ * blurred by up to three box passes, moved by whole pixels and tinted with one colour.  The result is itself a
+ * premultiplied layer (R G B A, alpha last), so the caller composites it with fr_layer_over, then the text over it.
+ *   All arithmetic is in integers; m, D and E are as defined above.
+ *   Source alpha: A0(u, v) is the alpha byte of layer pixel (src_x + u, src_y + v) for 0 <= u < w, 0 <= v < h, and 0
+ *     everywhere else on the integer plane.  No layer byte outside the window is read, and only alpha is read.
+ *   Spread: A1(u, v) = max of A0(u + i, v + j) over |i| <= s, |j| <= s.
+ *   Blur: with W = (2 r + 1)^2, for k = 1 .. p:
+ *       A_{k+1}(u, v) = (sum of A_k(u + i, v + j) over |i| <= r, |j| <= r  +  W div 2) div W
+ *     Each two-dimensional pass rounds once to 8 bits; the sum is exact, so any evaluation order gives the same bytes.
+ *     r = 0 or p = 0 skips the stage.
+ *   Tint: for pixel (X, Y) of the destination rectangle, 0 <= X < dst_w, 0 <= Y < dst_h:
+ *       alpha = A_last(X - dx, Y - dy),  a = m(alpha, rgba[3])
+ *       stored = (m(R, a), m(G, a), m(B, a), a)                                              (flags = 0)
+ *       stored = (E((D[R] * a + 127) div 255), E((D[G] * a + 127) div 255), E((D[B] * a + 127) div 255), a)   (FR_LAYER_SRGB)
+ *     The sRGB form is what an FR_TEXT_SRGB | FR_TEXT_OVER plan writes for one fully covered sample of colour (C, a) over
+ *     a (0, 0, 0, 0) clear.  Byte order is R G B A; a caller with B G R A layers swaps rgba[0] and rgba[2].
+ *   Writes: every pixel of the destination rectangle is written and none of it is read.  No byte of the destination
+ *     outside the rectangle is read or written.  No layer byte is written.
+ *   Consequences:
+ *     1. With s = 0, no blur, dx = dy = 0 and colour (255, 255, 255, 255) the output is (alpha, alpha, alpha, alpha) of the
+ *        layer.
+ *     2. A stage leaves a constant neighbourhood unchanged: (v W + W div 2) div W = v.  Text-interior alpha 255 stays 255.
+ *     3. alpha is non-zero only within Chebyshev distance R = s + p r of a window pixel with non-zero alpha.  A rectangle
+ *        padded by R holds the whole shadow; a rectangle out of reach is all (0, 0, 0, 0).
+ *     4. Adding 1 to dx or dy moves the image by exactly one column or row.
+ *     5. The definition is symmetric in the axes: a transposed window with dx and dy swapped gives the transposed image.
+ *     6. One pixel of alpha 255 with p = 1 gives (255 + W div 2) div W on exactly the (2 r + 1)^2 square around it.
+ *   Validation, in this order.  FR_E_INVALID: NULL ctx; an unknown flag bit; a NULL or not 4-byte aligned image pointer,
+ *     or a stride beyond 2^26 (the layer, then the destination).  FR_E_UNSUPPORTED: an image of 2^31 rows or more.
+ *     FR_E_INVALID: NULL `shadow`; a window of non-zero area that is not inside the layer (src_x + w <= src_stride_px,
+ *     src_y + h <= src_rows); a rectangle of non-zero area that is not inside dst_stride_px x dst_rows; s > 8, r > 32 or
+ *     p > 3; overlapping byte ranges of the two images.  FR_E_UNSUPPORTED: a rectangle of more than 2^22 tiles of 64 x 64
+ *     pixels, counted as ceil((dst_w + 3) / 64) * ceil(dst_h / 64) (fr_layer_over's limit of 2^34 pixels); a call whose two
+ *     intermediate planes (one byte per pixel each) would exceed 2^30 bytes together.
+ *     w, h, dst_w or dst_h of 0 is valid: dst_w = 0 or dst_h = 0 writes nothing, a window of zero area writes zeros over
+ *     the rectangle.  Any int32 dx or dy is valid.
+ *   Execution: one kernel per stage (the last one fused with the tint; a single kernel when there is no stage),
+ *     asynchronous on the context's stream, in stream order with renders and composites.  The intermediate planes belong
+ *     to the context and grow on demand; growing waits for the stream.  The caller may reuse `shadow` as soon as the call
+ *     returns.
+ * The parameters' type is fr_layer_shadow_params: C keeps typedef names and functions in one name space.                  */
+typedef struct fr_layer_shadow_params {
+    uint32_t src_x, src_y, w, h;          /* the window of the layer whose alpha casts the shadow      */
+    uint32_t dst_x, dst_y, dst_w, dst_h;  /* the rectangle of the destination that receives it         */
+    int32_t  dx, dy;                      /* destination pixel (X, Y) of the rectangle shows window
+                                             coordinate (X - dx, Y - dy)                               */
+    uint32_t spread;                      /* s in 0 .. 8                                               */
+    uint32_t blur_radius;                 /* r in 0 .. 32                                              */
+    uint32_t blur_passes;                 /* p in 0 .. 3; r = 0 or p = 0 means no blur                 */
+    uint8_t  rgba[4];                     /* the shadow's colour, straight R G B A                     */
+} fr_layer_shadow_params;
+
+int fr_layer_shadow(fr_ctx *ctx, const void *src_dev, size_t src_stride_px, size_t src_rows,
+                    void *dst_dev, size_t dst_stride_px, size_t dst_rows,
+                    const fr_layer_shadow_params *shadow, uint32_t flags);   /* 0 or FR_LAYER_SRGB */
 
 /* ---- self-test: exhaustive device-side check of an arithmetic shortcut ----------
  * The render kernel computes t = num / d (render_glyph.zig:51,60-61; d an integer, |d| <= 2^17)
