@@ -38,7 +38,7 @@ pub const FR_TEXT_LOAD: u32 = 32;
 pub const FR_TEXT_CACHE: u32 = 128;
 /// flag of the RGBA text plan entry points (fr_raster.h): source-over alpha, a premultiplied output
 pub const FR_TEXT_OVER: u32 = 256;
-/// fr_layer_over's own flag space (fr_raster.h): composite in linear light
+/// the flag space of fr_layer_over, fr_layer_shadow and fr_layer_rects (fr_raster.h): composite in linear light
 pub const FR_LAYER_SRGB: u32 = 1;
 
 pub const RasterParams = extern struct {
@@ -116,6 +116,32 @@ pub const LayerShadowParams = extern struct {
     rgba: [4]u8,
 };
 
+/// one anti-aliased rectangle of fr_layer_rects: edges in 1/64 pixel of the destination, y down, and a straight colour
+pub const LayerRect = extern struct {
+    x0: i32,
+    y0: i32,
+    x1: i32,
+    y1: i32,
+    rgba: [4]u8,
+};
+
+/// fr_font_line_metrics: hhea, post and OS/2 in font units, y up; present bit 0: post, bit 1: OS/2
+pub const FontLine = extern struct {
+    ascender: i16,
+    descender: i16,
+    line_gap: i16,
+    underline_position: i16,
+    underline_thickness: i16,
+    strikeout_size: i16,
+    strikeout_position: i16,
+    present: u16,
+};
+
+/// the kinds of fr_text_decoration
+pub const FR_DECOR_UNDERLINE: u32 = 0;
+pub const FR_DECOR_STRIKEOUT: u32 = 1;
+pub const FR_DECOR_LINE_BOX: u32 = 2;
+
 pub const TextRun = extern struct {
     first: u32,
     count: u32,
@@ -185,6 +211,9 @@ pub extern "c" fn fr_font_info(font: *const fr_font, units_per_em: ?*u16, num_gl
 pub extern "c" fn fr_font_char_to_glyph(font: *const fr_font, codepoint: u32, glyph_index: *u16) c_int;
 pub extern "c" fn fr_font_glyph_advance(font: *const fr_font, glyph_index: u16, advance_width: *i16) c_int;
 pub extern "c" fn fr_text_layout(font: *const fr_font, codepoints: [*]const u32, n: u32, font_size: u16, glyph_index_out: [*]u16, pen_x64_out: [*]i32, end_pen_x64: ?*i32) c_int;
+/// where a line's decorations belong: the font's line metrics, and a decoration's rows below the baseline in 1/64 pixel
+pub extern "c" fn fr_font_line_metrics(font: *const fr_font, out: *FontLine) c_int;
+pub extern "c" fn fr_text_decoration(font: *const fr_font, font_size: u16, kind: u32, top_y64: *i32, bottom_y64: *i32) c_int;
 pub extern "c" fn fr_font_glyph_measure(font: *fr_font, glyph_index: u16, n_contours: *u32, n_points: *u32, box: *[4]i16) c_int;
 pub extern "c" fn fr_font_glyph_fill(font: *fr_font, glyph_index: u16, points_xy: [*]i16, contour_start: [*]u32) c_int;
 // ---- QOI writer (host side; byte-compatible with tools/qoi.zig, which the Zig host keeps)
@@ -204,6 +233,8 @@ pub extern "c" fn fr_layer_over(ctx: *Ctx, src_dev: *const anyopaque, src_stride
 pub extern "c" fn fr_layer_unpremultiply(ctx: *Ctx, rgba_dev: *anyopaque, stride_px: usize, w: u32, h: u32, srgb: c_int) c_int;
 /// the alpha of a layer's window, spread, box-blurred, moved and tinted: a premultiplied layer written over a rectangle of the destination
 pub extern "c" fn fr_layer_shadow(ctx: *Ctx, src_dev: *const anyopaque, src_stride_px: usize, src_rows: usize, dst_dev: *anyopaque, dst_stride_px: usize, dst_rows: usize, shadow: *const LayerShadowParams, flags: u32) c_int;
+/// anti-aliased rectangles, each in one straight colour, composited in order over a premultiplied image in device memory
+pub extern "c" fn fr_layer_rects(ctx: *Ctx, dst_dev: *anyopaque, dst_stride_px: usize, dst_rows: usize, rects: ?[*]const LayerRect, n_rects: u32, flags: u32) c_int;
 // ---- self-tests of the two arithmetic shortcuts (device-side, exhaustive)
 pub extern "c" fn fr_selftest_division(d_lo: u32, d_hi: u32, mismatches: *u64, bad_divisor: ?*u32, bad_x_bits: ?*u32) c_int;
 pub extern "c" fn fr_selftest_sqrt(mismatches: *u64, bad_x_bits: ?*u32) c_int;

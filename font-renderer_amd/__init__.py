@@ -9,18 +9,18 @@ the shared library and raises if it (or a GPU) is missing.
 from .glyph import Box, Contour, FontInformation, Glyph, GlyphSet  # noqa: F401
 from .image import RGB, RGBA, Gray, GlyphDebug, Winding  # noqa: F401
 from ._lib import (  # noqa: F401
-    FR_COVERAGE_U8, FR_FILL_CONSISTENT, FR_SDF_U8, FR_GRAY_DEBUG, FR_MASK_NONZERO, FR_SAMPLE_CENTER, FR_SAMPLE_CORNER,
+    FR_COVERAGE_U8, FR_DECOR_LINE_BOX, FR_DECOR_STRIKEOUT, FR_DECOR_UNDERLINE, FR_FILL_CONSISTENT, FR_SDF_U8, FR_GRAY_DEBUG, FR_MASK_NONZERO, FR_SAMPLE_CENTER, FR_SAMPLE_CORNER,
     FR_LAYER_SRGB, FR_TEXT_BGRA, FR_TEXT_CACHE, FR_TEXT_LOAD, FR_TEXT_OVER, FR_TEXT_SRGB, FR_WINDING_I16, FrError, GlyphPlace, GlyphPlaceAffine, GlyphPlaceEx,
-    Job, LayerBlit, LayerShadowParams, TextRun, lib_path, load_library,
+    FontLine, Job, LayerBlit, LayerRect, LayerShadowParams, TextRun, lib_path, load_library,
 )
 from .render_glyph import (  # noqa: F401
-    Context, GlyphInfo, Plan, TextPlan, TextPlanRGBA, DeviceGlyphSet, layer_over, layer_shadow, layer_unpremultiply, make_blits, make_places, make_places_affine,
+    Context, GlyphInfo, Plan, TextPlan, TextPlanRGBA, DeviceGlyphSet, layer_over, layer_rects, layer_shadow, layer_unpremultiply, make_blits, make_rects, make_places, make_places_affine,
     make_places_ex, make_runs, renderGlyph, render_glyph_dims,
     windingInGlyph, winding_lattice, exact_lattice, exact_coverage, glyph_debug_render, build_id, srgb_to_linear16,
     linear16_to_srgb,
 )
 from .font import Font  # noqa: F401
 from .text import (  # noqa: F401
-    draw_text_rgba, instance_cell, instance_cell_affine, instance_cell_ex, render_spans, render_spans_rgba, render_text,
+    decoration_rects, draw_text_rgba, instance_cell, instance_cell_affine, instance_cell_ex, render_spans, render_spans_rgba, render_text,
     render_text_rgba, render_text_rgba_rotated, render_text_rotated, render_text_view, rotated_line, span_line, view_line,
 )

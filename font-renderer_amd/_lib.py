@@ -13,7 +13,8 @@ FR_TEXT_SRGB, FR_TEXT_BGRA = 8, 4  # flags of fr_text_plan_create_rgba only: lin
 FR_TEXT_LOAD = 32                  # fr_text_plan_create_rgba only: draw over the pixels already in the output
 FR_TEXT_CACHE = 128                # the upright and _ex text plans: each distinct glyph image made once per render, same bytes
 FR_TEXT_OVER = 256                 # the RGBA text plans: source-over alpha (a premultiplied output) instead of alpha replaced
-FR_LAYER_SRGB = 1                  # the flag space of fr_layer_over and fr_layer_shadow: work in linear light
+FR_LAYER_SRGB = 1                  # the flag space of fr_layer_over, fr_layer_shadow and fr_layer_rects: work in linear light
+FR_DECOR_UNDERLINE, FR_DECOR_STRIKEOUT, FR_DECOR_LINE_BOX = 0, 1, 2    # the kinds of fr_text_decoration
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -68,6 +69,16 @@ class LayerShadowParams(C.Structure):    # == fr_layer_shadow_params
                 ("dst_x", C.c_uint32), ("dst_y", C.c_uint32), ("dst_w", C.c_uint32), ("dst_h", C.c_uint32),
                 ("dx", C.c_int32), ("dy", C.c_int32), ("spread", C.c_uint32), ("blur_radius", C.c_uint32),
                 ("blur_passes", C.c_uint32), ("rgba", C.c_uint8 * 4)]
+
+
+class LayerRect(C.Structure):    # == fr_layer_rect
+    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32), ("rgba", C.c_uint8 * 4)]
+
+
+class FontLine(C.Structure):     # == fr_font_line
+    _fields_ = [("ascender", C.c_int16), ("descender", C.c_int16), ("line_gap", C.c_int16),
+                ("underline_position", C.c_int16), ("underline_thickness", C.c_int16),
+                ("strikeout_size", C.c_int16), ("strikeout_position", C.c_int16), ("present", C.c_uint16)]
 
 
 # every symbol include/fr_raster.h declares: (name, restype, argtypes)
@@ -130,6 +141,8 @@ SYMBOLS = [
     ("fr_font_char_to_glyph", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint16)]),
     ("fr_font_glyph_advance", C.c_int, [_P, C.c_uint16, C.POINTER(C.c_int16)]),
     ("fr_text_layout", C.c_int, [_P, _P, C.c_uint32, C.c_uint16, _P, _P, C.POINTER(C.c_int32)]),
+    ("fr_font_line_metrics", C.c_int, [_P, C.POINTER(FontLine)]),
+    ("fr_text_decoration", C.c_int, [_P, C.c_uint16, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("fr_font_glyph_measure", C.c_int, [_P, C.c_uint16, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _P]),
     ("fr_font_glyph_fill", C.c_int, [_P, C.c_uint16, _P, _P]),
     ("fr_qoi_bound", C.c_size_t, [C.c_uint32, C.c_uint32]),
@@ -142,6 +155,7 @@ SYMBOLS = [
     ("fr_layer_over", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, _P, C.c_uint32, C.c_uint32]),
     ("fr_layer_unpremultiply", C.c_int, [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.c_int]),
     ("fr_layer_shadow", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.POINTER(LayerShadowParams), C.c_uint32]),
+    ("fr_layer_rects", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_uint32, C.c_uint32]),
     ("fr_selftest_sqrt", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     ("fr_selftest_division", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("fr_selftest_row_cuts", C.c_int, [_P, _P, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),

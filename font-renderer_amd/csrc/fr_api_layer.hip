@@ -1,16 +1,18 @@
-// fr_api_layer.hip — C ABI (include/fr_raster.h): fr_layer_over, fr_layer_unpremultiply and fr_layer_shadow.  The checks, the
-// clipping and the tile table are fr_layer_plan.cpp's, the shadow's stages fr_layer_shadow_plan.cpp's; this unit stages the
-// table, keeps the shadow's planes and launches the kernels of fr_layer.hip and fr_layer_shadow.hip.
+// fr_api_layer.hip — C ABI (include/fr_raster.h): fr_layer_over, fr_layer_unpremultiply, fr_layer_shadow and fr_layer_rects.
+// The checks, the clipping and the tile table are fr_layer_plan.cpp's, the shadow's stages fr_layer_shadow_plan.cpp's, the
+// rectangles' tables fr_layer_rects_plan.cpp's; this unit stages the tables, keeps the shadow's planes and launches the
+// kernels of fr_layer.hip, fr_layer_shadow.hip and fr_layer_rects.hip.
 #include "fr_internal.hpp"
 #include "fr_layer.hpp"
+#include "fr_layer_rects.hpp"
 #include "fr_layer_shadow.hpp"
 
 #include <algorithm>
 #include <cstring>
 #include <new>
 
-// Room for n tiles in the context's table: pinned staging on the host, which the device reads, and its DevBuf on the
-// device, grown on demand.  The earlier table may still be read by a composite in flight, so growing waits for the stream.
+// Room for n units of 16 bytes in the context's tables: pinned staging on the host, which the device reads, and its DevBuf on
+// the device, grown on demand.  The earlier tables may still be read by a kernel in flight, so growing waits for the stream.
 static int layer_table_room(fr_ctx *ctx, size_t n)
 {
     if (n <= ctx->layer_cap) return FR_OK;
@@ -18,12 +20,29 @@ static int layer_table_room(fr_ctx *ctx, size_t n)
     if (ctx->layer_stage) { (void)hipHostFree(ctx->layer_stage); ctx->layer_stage = nullptr; }
     ctx->layer_tab.reset();
     ctx->layer_cap = 0;
-    const size_t cap = std::max<size_t>(n + n / 2, 1024);
-    hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&ctx->layer_stage), cap * sizeof(fr::LayerTile), hipHostMallocDefault);
+    const size_t cap = std::max<size_t>(n + n / 2, 2048);
+    hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&ctx->layer_stage), cap * sizeof(uint4), hipHostMallocDefault);
     if (e != hipSuccess) { ctx->layer_stage = nullptr; return hip_fail(e, "hipHostMalloc(&ctx->layer_stage, cap)"); }
-    ctx->layer_tab.alloc(e, cap * sizeof(fr::LayerTile));
+    ctx->layer_tab.alloc(e, cap * sizeof(uint4));
     if (e != hipSuccess) return hip_fail(e, "hipMalloc(&ctx->layer_tab, cap)");
     ctx->layer_cap = cap;
+    return FR_OK;
+}
+
+// The tables of one call, `units` units of 16 bytes that `fill` writes into the staging, brought into the context's device
+// copy in stream order; -> that copy in *table.  A kernel launched on the stream after this reads the call's own tables
+// even while an earlier call's kernels are still in flight.
+template <class FILL>
+static int layer_tables_to_device(fr_ctx *ctx, size_t units, const uint4 **table, FILL fill)
+{
+    // the tables of the call before this one have left the staging (layer_table_kernel reads it in stream order)
+    if (ctx->layer_ev) HIP_TRY(hipEventSynchronize(ctx->layer_ev));
+    else HIP_TRY(hipEventCreateWithFlags(&ctx->layer_ev, hipEventDisableTiming));
+    if (const int rc = layer_table_room(ctx, units)) return rc;
+    fill(ctx->layer_stage);
+    HIP_TRY(fr::launch_layer_table(ctx->layer_stage, ctx->layer_tab.get(), (uint32_t)units, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->layer_ev, ctx->stream));
+    *table = ctx->layer_tab.get();
     return FR_OK;
 }
 
@@ -62,14 +81,10 @@ int fr_layer_over(fr_ctx *ctx, const void *src_dev, size_t src_stride_px, size_t
     const size_t n = t.tiles.size();
     if (!n) return FR_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    // the table of the call before this one has left the staging (layer_table_kernel reads it in stream order)
-    if (ctx->layer_ev) HIP_TRY(hipEventSynchronize(ctx->layer_ev));
-    else HIP_TRY(hipEventCreateWithFlags(&ctx->layer_ev, hipEventDisableTiming));
-    if (const int rc = layer_table_room(ctx, n)) return rc;
-    memcpy(ctx->layer_stage, t.tiles.data(), n * sizeof(fr::LayerTile));
-    HIP_TRY(fr::launch_layer_table(ctx->layer_stage, ctx->layer_tab.get(), (uint32_t)n, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->layer_ev, ctx->stream));
-    const fr::LayerArgs a{ctx->layer_tab.get(), static_cast<const uint32_t *>(src_dev), static_cast<uint32_t *>(dst_dev), src_stride_px, dst_stride_px};
+    static_assert(sizeof(fr::LayerTile) == 2 * sizeof(uint4), "a tile is two units of the staging");
+    const uint4 *tab = nullptr;
+    if (const int rc = layer_tables_to_device(ctx, 2 * n, &tab, [&](uint4 *to) { memcpy(to, t.tiles.data(), n * sizeof(fr::LayerTile)); })) return rc;
+    const fr::LayerArgs a{reinterpret_cast<const fr::LayerTile *>(tab), static_cast<const uint32_t *>(src_dev), static_cast<uint32_t *>(dst_dev), src_stride_px, dst_stride_px};
     HIP_TRY(fr::launch_layer_over((flags & FR_LAYER_SRGB) != 0, t.opacity, (uint32_t)n, a, ctx->stream));
     return FR_OK;
 }
@@ -152,6 +167,35 @@ int fr_layer_shadow(fr_ctx *ctx, const void *src_dev, size_t src_stride_px, size
             in_rect = st.out;
         }
     }
+    return FR_OK;
+}
+
+int fr_layer_rects(fr_ctx *ctx, void *dst_dev, size_t dst_stride_px, size_t dst_rows, const fr_layer_rect *rects, uint32_t n_rects,
+                   uint32_t flags)
+{
+    if (!ctx) return fail(FR_E_INVALID, "fr_layer_rects: ctx is NULL");
+    fr::RectsTables t;
+    try {
+        const fr::RectsIn in{(uintptr_t)dst_dev, dst_stride_px, dst_rows, rects, n_rects, flags};
+        if (const int rc = fr::layer_rects_tables(in, t)) return rc;
+    } catch (const std::bad_alloc &) {
+        return fail(FR_E_NOMEM, "fr_layer_rects: host allocation");
+    }
+    const size_t n = t.tiles.size();
+    if (!n) return FR_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    // the three tables back to back, each from a 16-byte boundary: tiles (one unit each), the list, the records (two each)
+    const size_t list_at = n, recs_at = list_at + (t.list.size() + 3) / 4, units = recs_at + 2 * t.recs.size();
+    const uint4 *tab = nullptr;
+    if (const int rc = layer_tables_to_device(ctx, units, &tab, [&](uint4 *to) {
+            memcpy(to, t.tiles.data(), n * sizeof(fr::RectTile));
+            to[recs_at - 1] = make_uint4(0u, 0u, 0u, 0u);       // (the list's last unit may be part-filled)
+            memcpy(to + list_at, t.list.data(), t.list.size() * sizeof(uint32_t));
+            memcpy(to + recs_at, t.recs.data(), t.recs.size() * sizeof(fr::RectRec));
+        })) return rc;
+    const fr::RectsArgs a{reinterpret_cast<const fr::RectTile *>(tab), reinterpret_cast<const uint32_t *>(tab + list_at),
+                          reinterpret_cast<const fr::RectRec *>(tab + recs_at), static_cast<uint32_t *>(dst_dev), dst_stride_px, t.dst_vec ? 1u : 0u};
+    HIP_TRY(fr::launch_layer_rects((flags & FR_LAYER_SRGB) != 0, (uint32_t)n, a, ctx->stream));
     return FR_OK;
 }
 

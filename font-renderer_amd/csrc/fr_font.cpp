@@ -45,6 +45,7 @@ struct fr_font {
     size_t pos_loca = 0, pos_glyf = 0, pos_cmap_sub = 0, pos_hmtx = 0;
     uint16_t num_long_hor_metrics = 0;
     int cmap_format = 0;
+    fr_font_line line{};            // hhea, post and OS/2 as fr_font_line_metrics hands them out
     std::vector<GlyphData> glyphs;
     size_t composite_depth = 0;     // load_composite frames currently on the stack
 
@@ -336,9 +337,12 @@ int fr_font_open(const void *data, size_t len, uint32_t flags, fr_font **out)
     const uint16_t n_tables = f->u16(4);                                             // OffsetSubtable, Font.zig:38
     if (!f->has(12, 16u * n_tables)) return bail(set_error(FR_E_INVALID, "truncated table directory"));
     size_t head = 0, maxp = 0, cmap = 0, loca = 0, glyf = 0, hhea = 0, hmtx = 0;
+    size_t post = 0, os2 = 0;                              // optional: kept only when the fields read below are all there
     for (uint16_t t = 0; t < n_tables; ++t) {
         const size_t e = 12 + 16u * t;
         const uint32_t tg = f->u32(e), off = f->u32(e + 8);
+        if (tg == tag("post") && f->u32(e + 12) >= 12 && f->has(off, 12)) post = off;
+        if (tg == tag("OS/2") && f->u32(e + 12) >= 30 && f->has(off, 30)) os2 = off;
         if (tg == tag("head")) head = off;
         else if (tg == tag("maxp")) maxp = off;
         else if (tg == tag("cmap")) cmap = off;
@@ -359,6 +363,19 @@ int fr_font_open(const void *data, size_t len, uint32_t flags, fr_font **out)
     if (!f->has(hhea, 36)) return bail(set_error(FR_E_INVALID, "truncated hhea"));
     f->num_long_hor_metrics = f->u16(hhea + 34);
     f->pos_hmtx = hmtx;
+    f->line.ascender = f->i16(hhea + 4);
+    f->line.descender = f->i16(hhea + 6);
+    f->line.line_gap = f->i16(hhea + 8);
+    if (post) {
+        f->line.underline_position = f->i16(post + 8);
+        f->line.underline_thickness = f->i16(post + 10);
+        f->line.present |= 1u;
+    }
+    if (os2) {
+        f->line.strikeout_size = f->i16(os2 + 26);
+        f->line.strikeout_position = f->i16(os2 + 28);
+        f->line.present |= 2u;
+    }
     f->glyphs.resize(f->num_glyphs);
     // cmap: Font.zig:87-121
     if (!f->has(cmap, 4)) return bail(set_error(FR_E_INVALID, "truncated cmap"));
@@ -476,6 +493,45 @@ int fr_text_layout(const fr_font *font, const uint32_t *codepoints, uint32_t n, 
         e += adv;
     }
     if (end_pen_x64) return pen(e, end_pen_x64);
+    return FR_OK;
+}
+
+int fr_font_line_metrics(const fr_font *font, fr_font_line *out)
+{
+    if (!font || !out) return set_error(FR_E_INVALID, "fr_font_line_metrics: NULL argument");
+    *out = font->line;
+    return FR_OK;
+}
+
+// Offsets from the baseline in 1/64 pixel, y down, rounded as fr_text_layout rounds a pen: R(v) = floor((128 * font_size * v
+// + upm) / (2 * upm)).  |128 * font_size * v| < 2^38: plain int64.
+int fr_text_decoration(const fr_font *font, uint16_t font_size, uint32_t kind, int32_t *top_y64, int32_t *bottom_y64)
+{
+    if (!font || !top_y64 || !bottom_y64) return set_error(FR_E_INVALID, "fr_text_decoration: NULL argument");
+    if (kind > FR_DECOR_LINE_BOX) return set_error(FR_E_INVALID, "fr_text_decoration: unknown kind %u", kind);
+    const int64_t upm = font->units_per_em;
+    if (upm <= 0) return set_error(FR_E_INVALID, "fr_text_decoration: units_per_em is 0");
+    auto R = [&](int64_t v) {
+        const int64_t num = 128 * (int64_t)font_size * v + upm, den = 2 * upm;
+        return num / den - ((num % den != 0 && num < 0) ? 1 : 0);                         // floor division
+    };
+    const fr_font_line &l = font->line;
+    int64_t top, bottom;
+    if (kind == FR_DECOR_LINE_BOX) {
+        top = -R(l.ascender);
+        bottom = -R(l.descender);
+    } else {
+        const bool under = kind == FR_DECOR_UNDERLINE;
+        if (!(l.present & (under ? 1u : 2u)))
+            return set_error(FR_E_UNSUPPORTED, "fr_text_decoration: the font has no %s table", under ? "post" : "OS/2");
+        top = -R(under ? l.underline_position : l.strikeout_position);
+        const int64_t t = R(under ? l.underline_thickness : l.strikeout_size);
+        bottom = top + (t > 1 ? t : 1);
+    }
+    if (top < INT32_MIN || top > INT32_MAX || bottom < INT32_MIN || bottom > INT32_MAX)
+        return set_error(FR_E_INVALID, "fr_text_decoration: offset beyond int32 (1/64 pixel)");
+    *top_y64 = (int32_t)top;
+    *bottom_y64 = (int32_t)bottom;
     return FR_OK;
 }
 

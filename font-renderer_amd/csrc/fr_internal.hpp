@@ -17,7 +17,6 @@ struct TextTile;                       // fr_text_tables.hpp
 struct TextRun;
 struct TextMaskCell;
 struct TextMaskTile;
-struct LayerTile;                      // fr_layer_plan.hpp
 }  // namespace fr
 
 // leaves the message for fr_last_error (this thread's) -> code
@@ -53,11 +52,11 @@ struct fr_ctx {
     size_t arena_cap = 0;
     unsigned char *stage = nullptr;     // pinned host memory: [upload block | image coming back]
     size_t stage_cap = 0;
-    // the tile table of fr_layer_over (fr_api_layer.hip): pinned host staging and the device copy the kernel reads, room for
-    // layer_cap tiles each, grown on demand; layer_ev: the last copy out of the staging (layer_table_kernel), which the next
-    // call waits for
-    DevBuf<fr::LayerTile> layer_tab;
-    fr::LayerTile *layer_stage = nullptr;
+    // the tables of one fr_layer_over or fr_layer_rects call (fr_api_layer.hip): pinned host staging and the device copy the
+    // kernel reads, room for layer_cap units of 16 bytes each, grown on demand; layer_ev: the last copy out of the staging
+    // (layer_table_kernel), which the next call waits for
+    DevBuf<uint4> layer_tab;
+    uint4 *layer_stage = nullptr;
     size_t layer_cap = 0;
     hipEvent_t layer_ev = nullptr;
     // the two intermediate planes of fr_layer_shadow, one byte per pixel, grown on demand

@@ -13,8 +13,8 @@ struct LayerArgs {             // what layer_over_kernel reads and writes
     uint64_t src_stride, dst_stride;   // pixels
 };
 
-// n_tiles tiles from `staged` (pinned host memory the device can read) into `table` (device memory), by a kernel
-hipError_t launch_layer_table(const LayerTile *staged, LayerTile *table, uint32_t n_tiles, hipStream_t stream);
+// n units of 16 bytes from `staged` (pinned host memory the device can read) into `table` (device memory), by a kernel
+hipError_t launch_layer_table(const uint4 *staged, uint4 *table, uint32_t n, hipStream_t stream);
 // layer_over_kernel<srgb, opacity> over n_tiles tiles, one workgroup each
 hipError_t launch_layer_over(bool srgb, bool opacity, uint32_t n_tiles, const LayerArgs &a, hipStream_t stream);
 // layer_unpremultiply_kernel<srgb> over the w x h window at rgba (w, h > 0)

@@ -5,22 +5,12 @@
 
 namespace fr {
 
-int set_error(int code, const char *fmt, ...);         // the context unit (the self-test has its own)
-
-static int check_image(const char *what, uintptr_t p, size_t stride)
-{
-    if (!p) return set_error(FR_E_INVALID, "%s is NULL", what);
-    if (p & 3u) return set_error(FR_E_INVALID, "%s %p is not 4-byte aligned", what, (void *)p);
-    if (stride > ((size_t)1 << 26)) return set_error(FR_E_INVALID, "%s: row pitch of %zu elements: at most 2^26", what, stride);
-    return FR_OK;
-}
-
 int layer_tables(const LayerIn &in, LayerTables &out)
 {
     out = LayerTables{};
     if (in.flags & ~(uint32_t)FR_LAYER_SRGB) return set_error(FR_E_INVALID, "unknown flag bits 0x%x", in.flags & ~(uint32_t)FR_LAYER_SRGB);
-    if (const int rc = check_image("src", in.src, in.src_stride)) return rc;
-    if (const int rc = check_image("dst", in.dst, in.dst_stride)) return rc;
+    if (const int rc = layer_image_check("src", in.src, in.src_stride)) return rc;
+    if (const int rc = layer_image_check("dst", in.dst, in.dst_stride)) return rc;
     if (in.src_rows > LAYER_MAX_ROWS || in.dst_rows > LAYER_MAX_ROWS) return set_error(FR_E_UNSUPPORTED, "an image of more than 2^31 - 1 rows");
     if (in.n_blits && !in.blits) return set_error(FR_E_INVALID, "blits is NULL");
     // the two images' bytes (stride <= 2^26, rows < 2^31: no overflow)
@@ -84,7 +74,7 @@ int layer_tables(const LayerIn &in, LayerTables &out)
 
 int layer_window_check(uintptr_t rgba, size_t stride_px, uint32_t w, uint32_t h)
 {
-    if (const int rc = check_image("rgba", rgba, stride_px)) return rc;
+    if (const int rc = layer_image_check("rgba", rgba, stride_px)) return rc;
     if (w > stride_px) return set_error(FR_E_INVALID, "a window of %u pixels in rows of %zu", w, stride_px);
     if ((uint64_t)((w + LAYER_TILE_W - 1) / LAYER_TILE_W) * (((uint64_t)h + LAYER_TILE_H - 1) / LAYER_TILE_H) > LAYER_MAX_TILES)
         return set_error(FR_E_UNSUPPORTED, "the window needs more than 2^22 tiles; split the call");

@@ -60,6 +60,17 @@ struct LayerTables {
 // meaningful after FR_OK.
 int layer_tables(const LayerIn &in, LayerTables &out);
 
+int set_error(int code, const char *fmt, ...);         // the context unit (the self-tests have their own)
+
+// an image of the layer calls: a non-NULL, 4-byte aligned pointer and a row pitch within fr_plan_render's limit
+inline int layer_image_check(const char *what, uintptr_t p, size_t stride)
+{
+    if (!p) return set_error(FR_E_INVALID, "%s is NULL", what);
+    if (p & 3u) return set_error(FR_E_INVALID, "%s %p is not 4-byte aligned", what, (void *)p);
+    if (stride > ((size_t)1 << 26)) return set_error(FR_E_INVALID, "%s: row pitch of %zu elements: at most 2^26", what, stride);
+    return FR_OK;
+}
+
 // the checks of fr_layer_unpremultiply
 int layer_window_check(uintptr_t rgba, size_t stride_px, uint32_t w, uint32_t h);
 

@@ -1,0 +1,53 @@
+// fr_layer_px.hpp — source-over of one premultiplied pixel, for the kernels that composite onto an image: layer_over_kernel
+// (fr_layer.hip) and layer_rects_kernel (fr_layer_rects.hip).  The arithmetic is that of the text plans' colour body
+// (fr_text_colour.hpp), per pixel instead of per sample.
+#pragma once
+#include "fr_text_colour.hpp"
+
+namespace fr {
+
+inline constexpr uint32_t M2 = 0x00ff00ffu, HALF2 = 0x00800080u;
+
+// m(x, y) = (x * y + 127) div 255 on the two channels of c2 at once: blend2 with a colour term of zero
+__device__ __forceinline__ uint32_t m2(uint32_t c2, uint32_t y) { return blend2(c2, HALF2, y); }
+
+// the two 16-bit halves of v, each at most 510, clamped to 255
+__device__ __forceinline__ uint32_t clamp2(uint32_t v)
+{
+    return min(v & 0xffffu, 255u) | (min(v >> 16, 255u) << 16);
+}
+
+// a' = m(s_a, o) of the layer pixel s
+template <int OPACITY>
+__device__ __forceinline__ uint32_t alpha_of(uint32_t s, uint32_t o)
+{
+    return OPACITY ? m2(s >> 24, o) : s >> 24;
+}
+
+// The definition of fr_layer_over for one pixel: s over d at opacity o.  s == 0 gives d (consequence 1), and with
+// a' == 255 no bit of d reaches the result, so the caller may pass anything for a destination it did not load.
+template <int SRGB, int OPACITY>
+__device__ __forceinline__ uint32_t over_px(uint32_t s, uint32_t d, uint32_t o, const uint16_t *D, const uint16_t *K)
+{
+    uint32_t s1a = (s >> 8) & M2;                              // channel 1 and alpha
+    if (OPACITY) s1a = m2(s1a, o);
+    const uint32_t ia = 255u - (s1a >> 16);
+    const uint32_t r1a = s1a + m2((d >> 8) & M2, ia);          // alpha: a' + m(d_a, 255 - a') <= 255
+    if constexpr (!SRGB) {
+        uint32_t s02 = s & M2;
+        if (OPACITY) s02 = m2(s02, o);
+        return clamp2(s02 + m2(d & M2, ia)) | (clamp2(r1a) << 8);
+    } else {
+        uint32_t out = 0u;                                     // a shift register: a channel enters at the top byte
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            uint32_t S = D[(s >> (8 * c)) & 0xffu];
+            if (OPACITY) S = div255_24(S * o + 127u);
+            const uint32_t L = min(65535u, S + div255_24((uint32_t)D[(d >> (8 * c)) & 0xffu] * ia + 127u));
+            out = (out >> 8) | (srgb_encode(K, L) << 24);
+        }
+        return (out >> 8) | (r1a & 0x00ff0000u) << 8;          // alpha is stored linearly
+    }
+}
+
+}  // namespace fr

@@ -63,7 +63,22 @@ class Font:
         L.check(self._lib.fr_text_layout(self._h, L.ptr(cps), len(cps), font_size, L.ptr(gi), L.ptr(pen), C.byref(end)))
         return gi[:len(cps)], pen[:len(cps)], end.value
 
-    def getGlyph(self, char: int):                                     # Font.zig:161-169 -> struct {Glyph, i16}
+    def line_metrics(self) -> dict:
+        """fr_font_line_metrics: hhea's ascender, descender and line_gap, post's underline_position (the top of the line)
+        and underline_thickness, OS/2's strikeout_size and strikeout_position, in font units, y up; `present`: bit 0 post,
+        bit 1 OS/2 (an absent table's values are 0)"""
+        m = L.FontLine()
+        L.check(self._lib.fr_font_line_metrics(self._h, C.byref(m)))
+        return {name: getattr(m, name) for name, _ in L.FontLine._fields_}
+
+    def decoration(self, font_size: int, kind: int):
+        """fr_text_decoration: (top, bottom) of the underline (FR_DECOR_UNDERLINE), the strike-out (FR_DECOR_STRIKEOUT) or
+        the line box (FR_DECOR_LINE_BOX) at font_size, as offsets from the baseline in 1/64 pixel, y down"""
+        top, bottom = C.c_int32(), C.c_int32()
+        L.check(self._lib.fr_text_decoration(self._h, font_size, kind, C.byref(top), C.byref(bottom)))
+        return top.value, bottom.value
+
+    def getGlyph(self, char: int):                                   # Font.zig:161-169 -> struct {Glyph, i16}
         gi = self.glyph_index(char)
         return self.glyph_by_index(gi), self.advance_width(gi)
 

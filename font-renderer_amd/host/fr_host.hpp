@@ -215,6 +215,13 @@ inline void layer_shadow(Context &ctx, const DeviceImage &layer, const DeviceIma
     check(fr_layer_shadow(ctx.get(), layer.pixels, layer.stride_px, layer.rows, image.pixels, image.stride_px, image.rows, &shadow,
                           srgb ? FR_LAYER_SRGB : 0u));
 }
+// fr_layer_rects: anti-aliased rectangles (edges in 1/64 pixel, one straight colour each) composited in order over the
+// premultiplied `image`: underlines, strike-outs, highlights, carets, panels.  They may overlap.  Asynchronous on the
+// context's stream; `rects` may be reused at once.
+inline void layer_rects(Context &ctx, const DeviceImage &image, const std::vector<fr_layer_rect> &rects, bool srgb = false)
+{
+    check(fr_layer_rects(ctx.get(), image.pixels, image.stride_px, image.rows, rects.data(), (uint32_t)rects.size(), srgb ? FR_LAYER_SRGB : 0u));
+}
 
 class PlacedText {
 public:

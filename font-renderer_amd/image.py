@@ -143,6 +143,37 @@ class RGBA:                     # an RGBA text plan's image (fr_text_plan_create
         self.data[:] = dst.cpu().numpy()
         return self
 
+    def fill_rects(self, rects, srgb: bool = False, ctx=None) -> "RGBA":
+        """fr_layer_rects, in place: rects of (x0, y0, x1, y1, (R, G, B, A)) in float pixels, y down, each edge kept to 1/64
+        pixel as floor(64 v + 1/2), filled with anti-aliased edges in their straight colours, in order, over this
+        premultiplied image.  srgb: the image is premultiplied in linear light.  The image is uploaded, drawn into on the
+        device and copied back.  Returns self."""
+        import math
+
+        import torch
+
+        from . import render_glyph as rg
+        if not isinstance(self.data, np.ndarray) or self.data.dtype != np.uint8 or self.data.shape != (self.width * self.height, 4):
+            raise ValueError(f"RGBA.fill_rects: data must be a ({self.width * self.height}, 4) uint8 array")
+        rows = []
+        for x0, y0, x1, y1, colour in rects:
+            edges = [math.floor(64.0 * float(v) + 0.5) for v in (x0, y0, x1, y1)]
+            if not all(-2 ** 31 <= e < 2 ** 31 for e in edges):
+                raise ValueError(f"rectangle {(x0, y0, x1, y1)!r}: an edge beyond int32 in 1/64 pixel")
+            colour = tuple(int(v) for v in colour)
+            if len(colour) != 4 or not all(0 <= v <= 255 for v in colour):
+                raise ValueError(f"colour {colour}: expected 4 values in [0, 255]")
+            rows.append((*edges, colour))
+        if not rows or self.width == 0 or self.height == 0:
+            return self
+        ctx = ctx or rg.default_context()
+        dst = torch.from_numpy(np.ascontiguousarray(self.data)).to(f"cuda:{ctx.device}")
+        torch.cuda.synchronize(ctx.device)
+        rg.layer_rects(ctx, dst.data_ptr(), self.width, self.height, rg.make_rects(rows), srgb)
+        ctx.sync()
+        self.data[:] = dst.cpu().numpy()
+        return self
+
     def shadow(self, offset=(0, 0), spread: int = 0, blur_radius: int = 0, blur_passes: int = 0, rgba=(0, 0, 0, 255),
                pad: int = None, srgb: bool = False, ctx=None) -> "RGBA":
         """fr_layer_shadow of this premultiplied layer as a new premultiplied layer, `pad` pixels larger on every side

@@ -281,6 +281,24 @@ def layer_over(ctx: Context, src_ptr: int, src_stride_px: int, src_rows: int, ds
                                    dst_rows, None if b is None else L.ptr(b), n, flags | (L.FR_LAYER_SRGB if srgb else 0)))
 
 
+RECT_DTYPE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("rgba", "u1", (4,))])
+
+
+def make_rects(rows: Sequence) -> np.ndarray:
+    """rows of (x0, y0, x1, y1, (R, G, B, A)), the edges in 1/64 pixel -> fr_layer_rect array"""
+    return np.array([(int(r[0]), int(r[1]), int(r[2]), int(r[3]), tuple(int(v) for v in r[4])) for r in rows], RECT_DTYPE)
+
+
+def layer_rects(ctx: Context, dst_ptr: int, dst_stride_px: int, dst_rows: int, rects, srgb: bool = False, flags: int = 0) -> None:
+    """fr_layer_rects: anti-aliased rectangles, each in one straight colour, composited in order over the premultiplied
+    image at device address dst_ptr (4 bytes per pixel, alpha last; stride and rows in pixels), asynchronous on the
+    context's stream.  rects: an fr_layer_rect array (make_rects) or None.  srgb: FR_LAYER_SRGB, composite in linear light."""
+    n = 0 if rects is None else len(rects)
+    r = None if rects is None else np.ascontiguousarray(rects, RECT_DTYPE)
+    L.check(ctx._lib.fr_layer_rects(ctx._h, C.c_void_p(dst_ptr), dst_stride_px, dst_rows, None if r is None else L.ptr(r), n,
+                                    flags | (L.FR_LAYER_SRGB if srgb else 0)))
+
+
 def layer_unpremultiply(ctx: Context, ptr: int, stride_px: int, w: int, h: int, srgb: bool = False) -> None:
     """fr_layer_unpremultiply: the w x h window at device address ptr of an image with rows of stride_px pixels from
     premultiplied to straight alpha, in place, asynchronous on the context's stream"""

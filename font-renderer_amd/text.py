@@ -264,6 +264,27 @@ def draw_text_rgba(image: RGBA, font: Font, text, font_size: int, x: float, y: f
     return image
 
 
+def decoration_rects(font: Font, text, font_size: int, x: float, y: float, underline=None, strikeout=None, highlight=None):
+    """The rectangles that decorate the line draw_text_rgba(image, font, text, font_size, x, y) draws, for RGBA.fill_rects /
+    fr_layer_rects: rows of (x0, y0, x1, y1, (R, G, B, A)) in pixels, every edge an exact multiple of 1/64 (fill_rects
+    takes them as they are, make_rects takes 64 times the edges), in drawing order: the highlight (the line box, ascender to descender), the underline, the strike-out, each for
+    the colour given and left out for None.  x spans from the pen origin x64 = floor(64 x + 1/2) to x64 + the end pen; y
+    is pen_y64 = floor(64 y + 1/2) plus the offsets of Font.decoration.  A highlight goes down before the text, the
+    lines after it."""
+    if not math.isfinite(float(x)) or not math.isfinite(float(y)):
+        raise ValueError(f"x {x!r}, y {y!r}: expected finite values")
+    _, _, end = font.layout(text, font_size)
+    x64 = math.floor(64.0 * float(x) + 0.5)
+    y64 = math.floor(64.0 * float(y) + 0.5)
+    rows = []
+    for colour, kind in ((highlight, L.FR_DECOR_LINE_BOX), (underline, L.FR_DECOR_UNDERLINE), (strikeout, L.FR_DECOR_STRIKEOUT)):
+        if colour is None:
+            continue
+        top, bottom = font.decoration(font_size, kind)
+        rows.append((x64 / 64.0, (y64 + top) / 64.0, (x64 + end) / 64.0, (y64 + bottom) / 64.0, _rgba(colour)))
+    return rows
+
+
 def span_line(font: Font, spans):
     """Spans (text, font_size, slant, rise, colour) laid out as one line on a common baseline by chaining fr_text_layout:
     each span starts at the previous span's end pen (1/64 pixel where the size changes); rise: pixels above the baseline, kept to 1/64

@@ -599,6 +599,32 @@ int fr_font_glyph_fill(fr_font *font, uint16_t glyph_index, int16_t *points_xy, 
 int fr_text_layout(const fr_font *font, const uint32_t *codepoints, uint32_t n, uint16_t font_size,
                    uint16_t *glyph_index_out, int32_t *pen_x64_out, int32_t *end_pen_x64);
 
+/* Where a line's decorations belong (host only; BUILD-DEFINED: the reference reads none of these tables).  All values are
+ * in font units, y up, as the font stores them: hhea's ascender, descender and lineGap; post's underlinePosition (the TOP of
+ * the underline) and underlineThickness; OS/2's yStrikeoutSize and yStrikeoutPosition (the top of the stroke).  A font
+ * without a post or OS/2 table, or with one too short to hold these fields, opens as before: its bit of `present` is clear
+ * and its values are 0.                                                                                                  */
+typedef struct fr_font_line {
+    int16_t ascender, descender, line_gap;              /* hhea */
+    int16_t underline_position, underline_thickness;    /* post; 0 when absent */
+    int16_t strikeout_size, strikeout_position;         /* OS/2; 0 when absent */
+    uint16_t present;                                   /* bit 0: post, bit 1: OS/2 */
+} fr_font_line;
+int fr_font_line_metrics(const fr_font *font, fr_font_line *out);
+
+/* The rows of a decoration at font_size, as offsets from the baseline in 1/64 pixel, y DOWN (add them to a placement's
+ * pen_y64), rounded as fr_text_layout rounds a pen: R(v) = floor((128 * font_size * v + upm) / (2 * upm)), exact, with a
+ * true floor for negative v.
+ *     FR_DECOR_UNDERLINE:  top = -R(underline_position),  bottom = top + max(1, R(underline_thickness))
+ *     FR_DECOR_STRIKEOUT:  top = -R(strikeout_position),  bottom = top + max(1, R(strikeout_size))
+ *     FR_DECOR_LINE_BOX:   top = -R(ascender),            bottom = -R(descender)
+ * [top, bottom) x the line's pen span, as an fr_layer_rect, is the underline, the stroke or the box a highlight fills.
+ * FR_E_UNSUPPORTED when the table the kind needs is absent; FR_E_INVALID for an unknown kind or a NULL argument.          */
+#define FR_DECOR_UNDERLINE 0u
+#define FR_DECOR_STRIKEOUT 1u
+#define FR_DECOR_LINE_BOX  2u
+int fr_text_decoration(const fr_font *font, uint16_t font_size, uint32_t kind, int32_t *top_y64, int32_t *bottom_y64);
+
 /* ---- QOI writer (host side), byte-compatible with tools/qoi.zig:25-88 saveRGB -----------
  * RGB-only stream, op order RUN -> INDEX -> DIFF -> LUMA -> RGB, run cap 62, BE header, 8-byte
  * trailer.  fr_qoi_encode_gray feeds an Image.Gray (or an atlas page) through getRGBLinear =
@@ -667,7 +693,7 @@ int fr_rgba_unpremultiply(uint8_t *rgba, size_t n_pixels, int srgb);
  *     all blits of the call, behind a small kernel that brings the call's tile table into device memory; asynchronous on
  *     the context's stream, in stream order after earlier renders as fr_plan_render is; the caller may reuse `blits` as
  *     soon as the call returns.
- * FR_LAYER_SRGB is the flag space of fr_layer_over and fr_layer_shadow: no other entry point knows it, and these two know
+ * FR_LAYER_SRGB is the flag space of fr_layer_over, fr_layer_shadow and fr_layer_rects: no other entry point knows it, and these know
  * none of the FR_TEXT_ / FR_FILL_ flags.                                                                                        */
 #define FR_LAYER_SRGB 1u
 
@@ -745,6 +771,56 @@ typedef struct fr_layer_shadow_params {
 int fr_layer_shadow(fr_ctx *ctx, const void *src_dev, size_t src_stride_px, size_t src_rows,
                     void *dst_dev, size_t dst_stride_px, size_t dst_rows,
                     const fr_layer_shadow_params *shadow, uint32_t flags);   /* 0 or FR_LAYER_SRGB */
+
+/* ---- anti-aliased rectangles over an image (BUILD-DEFINED; DESIGN.md sections 4.10 and 5) ----------------------------------
+ * fr_layer_rects fills axis-aligned rectangles with sub-pixel edges, each in one straight colour, over a premultiplied
+ * image on the device: underlines, strike-outs, selections behind text, carets, panels.  fr_text_decoration gives the rows
+ * of the first three.
+ *   The destination is what fr_layer_over's is: dst_rows rows of dst_stride_px elements of 4 bytes, alpha last,
+ *   PREMULTIPLIED (with FR_LAYER_SRGB: in linear light); its width, for clipping, is its stride.  m, D and E as above.
+ *   Coverage is the exact area of the rectangle inside the pixel.  For pixel column X and row Y:
+ *       cx = max(0, min(x1, 64 (X + 1)) - max(x0, 64 X))         (0 .. 64; cy likewise from y0, y1 and Y)
+ *       k  = (255 * cx * cy + 2048) div 4096                     (0 .. 255)
+ *   Source: a = m(k, rgba[3]).  A pixel with a = 0 is left byte-identical.
+ *   Composite, for colour byte C of the rectangle over the destination pixel (d_c, d_a):
+ *       out_a = a + m(d_a, 255 - a)
+ *       out_c = min(255, m(C, a) + m(d_c, 255 - a))                                                   (flags = 0)
+ *       out_c = E(min(65535, (D[C] * a + 127) div 255 + (D[d_c] * (255 - a) + 127) div 255))          (FR_LAYER_SRGB)
+ *     m(C, a) <= a, so the clamp is never reached on a valid premultiplied destination (d_c <= d_a).  Byte order is
+ *     R G B A; a caller with B G R A images swaps rgba[0] and rgba[2].
+ *   Order: rectangles MAY overlap (fr_layer_over's blits may not): rectangle j is composited over the result of rectangles
+ *     0 .. j - 1, per pixel.
+ *   Consequences:
+ *     1. A pixel-aligned rectangle with rgba[3] = 255 replaces its pixels with (R, G, B, 255) in both spaces.
+ *     2. With flags = 0 the result equals a route through the other two calls: a layer whose alpha plane is k(X, Y),
+ *        tinted by fr_layer_shadow with no stage and colour rgba, composited by fr_layer_over at o = 255, byte for byte.
+ *     3. That is not promised with FR_LAYER_SRGB: the shadow stores an encoded 8-bit colour and so rounds once more; this
+ *        call blends the colour's 16-bit linear value directly.
+ *     4. Moving all four edges of a rectangle by 64 moves its image by exactly one pixel.
+ *     5. The definition is symmetric in the axes.
+ *     6. Outside the outward-rounded, clipped bounding box of every rectangle no byte of the image is read or written;
+ *        inside one, a pixel may be read and written back unchanged.
+ *   Not promised: two rectangles that split a pixel between them do not add up to full coverage (coverages are
+ *     composited, not summed); and a rectangle is not the bytes a text plan makes of a block glyph with the same edges
+ *     (text counts samples, this is area).
+ *   Validation, in this order.  FR_E_INVALID: NULL ctx; an unknown flag bit; a NULL or not 4-byte aligned dst_dev; a stride
+ *     beyond 2^26.  FR_E_UNSUPPORTED: 2^31 rows or more.  FR_E_INVALID: NULL `rects` with n_rects > 0.  FR_E_UNSUPPORTED:
+ *     rectangles that meet more than 2^22 tiles of 256 x 16 pixels (tiles on the image's grid, each counted once), then more
+ *     than 2^24 (tile, rectangle) pairs.  FR_E_NOMEM: a host allocation failed.
+ *     Every value of the four int32 edges is valid (the arithmetic is in int64), x1 <= x0 or y1 <= y0 included; edges of
+ *     int32 in 1/64 pixel cannot reach columns or rows beyond 2^25, so wider images are only drawn into up to there.
+ *     n_rects = 0 launches nothing; nor does a call whose rectangles are all empty, clipped away or fully transparent.
+ *   Execution: one launch of layer_rects_kernel<srgb> for all rectangles of the call, one workgroup per tile that some
+ *     rectangle meets, behind the small kernel that brings the call's tables into device memory; every pixel is loaded at
+ *     most once and stored at most once however many rectangles cover it.  Asynchronous on the context's stream, in stream
+ *     order with renders, composites and shadows; the caller may reuse `rects` as soon as the call returns.               */
+typedef struct fr_layer_rect {
+    int32_t x0, y0, x1, y1;   /* edges in 1/64 pixel of the destination, y down; x1 <= x0 or y1 <= y0: valid, draws nothing */
+    uint8_t rgba[4];          /* straight R G B A */
+} fr_layer_rect;
+
+int fr_layer_rects(fr_ctx *ctx, void *dst_dev, size_t dst_stride_px, size_t dst_rows,
+                   const fr_layer_rect *rects, uint32_t n_rects, uint32_t flags);   /* 0 or FR_LAYER_SRGB */
 
 /* ---- self-test: exhaustive device-side check of an arithmetic shortcut ----------
  * The render kernel computes t = num / d (render_glyph.zig:51,60-61; d an integer, |d| <= 2^17)
