@@ -5,36 +5,16 @@
 // their bytes.  tools/mint_host_rules.py makes the same calls on a built library through ctypes: the case tables
 // here and there are the same, line for line.
 #include "../csrc/fr_host_rules.hpp"
+#include "selftest.hpp"
 
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
 
-static char g_msg[512];
-namespace fr {
-int set_error(int code, const char *f, ...)
-{
-    va_list ap;
-    va_start(ap, f);
-    vsnprintf(g_msg, sizeof g_msg, f, ap);
-    va_end(ap);
-    return code;
-}
-}  // namespace fr
+using namespace selftest;
 
 namespace {
-
-std::string fmt(const char *f, ...)
-{
-    char b[512];
-    va_list ap;
-    va_start(ap, f);
-    vsnprintf(b, sizeof b, f, ap);
-    va_end(ap);
-    return b;
-}
 
 std::string hash(const void *v, size_t bytes)
 {
@@ -45,7 +25,7 @@ std::string hash(const void *v, size_t bytes)
 
 void line(const std::string &name, int rc, const std::string &fields)
 {
-    printf("%s rc=%d %s\n", name.c_str(), rc, rc ? fmt("err=%s", g_msg).c_str() : fields.c_str());
+    printf("%s rc=%d %s\n", name.c_str(), rc, rc ? fmt("err=%s", last_error()).c_str() : fields.c_str());
 }
 
 std::string job_text(const fr_job &j)

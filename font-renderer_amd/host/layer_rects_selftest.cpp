@@ -8,24 +8,14 @@
 // properties (the tiles distinct, on the grid and in order; every list ascending; a record in a tile's list exactly when
 // its bounding box meets the tile) and fails with the case and the property on stderr.
 #include "../csrc/fr_layer_rects_plan.hpp"
+#include "selftest.hpp"
 
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
 #include <vector>
 
-static char g_msg[512];
-namespace fr {
-int set_error(int code, const char *f, ...)
-{
-    va_list ap;
-    va_start(ap, f);
-    vsnprintf(g_msg, sizeof g_msg, f, ap);
-    va_end(ap);
-    return code;
-}
-}  // namespace fr
+using namespace selftest;
 
 namespace {
 
@@ -99,31 +89,6 @@ std::vector<Case> cases()
     return c;
 }
 
-std::string join(const std::vector<std::string> &v)
-{
-    std::string s;
-    for (size_t i = 0; i < v.size(); ++i) s += (i ? ";" : "") + v[i];
-    return s.empty() ? "-" : s;
-}
-
-std::string fmt(const char *f, ...)
-{
-    char b[256];
-    va_list ap;
-    va_start(ap, f);
-    vsnprintf(b, sizeof b, f, ap);
-    va_end(ap);
-    return b;
-}
-
-int g_failed = 0;
-void require(bool ok, const std::string &name, const char *what)
-{
-    if (ok) return;
-    fprintf(stderr, "%s: %s\n", name.c_str(), what);
-    g_failed = 1;
-}
-
 // the properties the kernel relies on
 void check_tables(const Case &cs, const fr::RectsTables &t)
 {
@@ -164,14 +129,14 @@ int main()
     for (const Case &cs : cases()) {
         const fr::RectsIn in{cs.dst, cs.ds, cs.dr, cs.null_rects ? nullptr : cs.rects.data(), (uint32_t)cs.rects.size(), cs.flags};
         fr::RectsTables t;
-        g_msg[0] = 0;
+        clear_error();
         const int rc = fr::layer_rects_tables(in, t);
         std::vector<std::string> rl, cl, tl, ll;
         for (const fr_layer_rect &r : cs.rects) rl.push_back(fmt("%d,%d,%d,%d,%u,%u,%u,%u", r.x0, r.y0, r.x1, r.y1, r.rgba[0], r.rgba[1], r.rgba[2], r.rgba[3]));
         printf("%s rc=%d in=%llu,%zu,%zu,%u rects=%s%s | ", cs.name.c_str(), rc, (unsigned long long)cs.dst, cs.ds, cs.dr, cs.flags, join(rl).c_str(),
                cs.null_rects ? " null" : "");
         if (rc) {
-            printf("err=%s\n", g_msg);
+            printf("err=%s\n", last_error());
             continue;
         }
         for (const fr::RectRec &c : t.recs) cl.push_back(fmt("%u,%u,%u,%u,%u,%u", c.x0, c.y0, c.x1, c.y1, c.rgba, c.index));
@@ -180,5 +145,5 @@ int main()
         printf("vec=%d recs=%s tiles=%s list=%s\n", t.dst_vec ? 1 : 0, join(cl).c_str(), join(tl).c_str(), join(ll).c_str());
         check_tables(cs, t);
     }
-    return g_failed;
+    return exit_status();
 }

@@ -8,24 +8,14 @@
 // (every pixel of a clipped rectangle in exactly one tile, no tile pixel outside it, the vector flags only where the
 // addresses are 16-byte aligned) and fails with the case and the property on stderr.
 #include "../csrc/fr_layer_plan.hpp"
+#include "selftest.hpp"
 
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
 #include <vector>
 
-static char g_msg[512];
-namespace fr {
-int set_error(int code, const char *f, ...)
-{
-    va_list ap;
-    va_start(ap, f);
-    vsnprintf(g_msg, sizeof g_msg, f, ap);
-    va_end(ap);
-    return code;
-}
-}  // namespace fr
+using namespace selftest;
 
 namespace {
 
@@ -89,31 +79,6 @@ std::vector<Case> cases()
     return c;
 }
 
-std::string join(const std::vector<std::string> &v)
-{
-    std::string s;
-    for (size_t i = 0; i < v.size(); ++i) s += (i ? ";" : "") + v[i];
-    return s.empty() ? "-" : s;
-}
-
-std::string fmt(const char *f, ...)
-{
-    char b[256];
-    va_list ap;
-    va_start(ap, f);
-    vsnprintf(b, sizeof b, f, ap);
-    va_end(ap);
-    return b;
-}
-
-int g_failed = 0;
-void require(bool ok, const std::string &name, const char *what)
-{
-    if (ok) return;
-    fprintf(stderr, "%s: %s\n", name.c_str(), what);
-    g_failed = 1;
-}
-
 // the properties the kernel relies on, for small images: a count per destination pixel
 void check_tables(const Case &cs, const fr::LayerTables &t)
 {
@@ -151,14 +116,14 @@ int main()
     for (const Case &cs : cases()) {
         const fr::LayerIn in{cs.src, cs.dst, cs.ss, cs.sr, cs.ds, cs.dr, cs.null_blits ? nullptr : cs.blits.data(), (uint32_t)cs.blits.size(), cs.flags};
         fr::LayerTables t;
-        g_msg[0] = 0;
+        clear_error();
         const int rc = fr::layer_tables(in, t);
         std::vector<std::string> bl, cl, tl;
         for (const fr_layer_blit &b : cs.blits) bl.push_back(fmt("%u,%u,%u,%u,%d,%d,%u", b.src_x, b.src_y, b.w, b.h, b.dst_x, b.dst_y, b.opacity));
         printf("%s rc=%d in=%llu,%llu,%zu,%zu,%zu,%zu,%u blits=%s%s | ", cs.name.c_str(), rc, (unsigned long long)cs.src, (unsigned long long)cs.dst, cs.ss, cs.sr,
                cs.ds, cs.dr, cs.flags, join(bl).c_str(), cs.null_blits ? " null" : "");
         if (rc) {
-            printf("err=%s\n", g_msg);
+            printf("err=%s\n", last_error());
             continue;
         }
         for (const fr::LayerClip &c : t.clips) cl.push_back(fmt("%u,%u,%u,%u,%u,%u", c.x0, c.y0, c.x1, c.y1, c.sx, c.sy));
@@ -173,9 +138,9 @@ int main()
         {"window/pitch_over", DST, ((size_t)1 << 26) + 1, 10, 10}, {"window/too_many_tiles", DST, (size_t)1 << 26, 1u << 26, 1u << 10},
     };
     for (const auto &w : W) {
-        g_msg[0] = 0;
+        clear_error();
         const int rc = fr::layer_window_check(w.p, w.stride, w.w, w.h);
-        printf("%s rc=%d in=%llu,%zu,%u,%u | %s%s\n", w.name, rc, (unsigned long long)w.p, w.stride, w.w, w.h, rc ? "err=" : "ok", rc ? g_msg : "");
+        printf("%s rc=%d in=%llu,%zu,%u,%u | %s%s\n", w.name, rc, (unsigned long long)w.p, w.stride, w.w, w.h, rc ? "err=" : "ok", rc ? last_error() : "");
     }
-    return g_failed;
+    return exit_status();
 }

@@ -10,24 +10,14 @@
 // (every stage's rectangle inside its input's rectangle grown by the radius, a plane large enough for it) and fails with the
 // case and the property on stderr.
 #include "../csrc/fr_layer_shadow_plan.hpp"
+#include "selftest.hpp"
 
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
 #include <vector>
 
-static char g_msg[512];
-namespace fr {
-int set_error(int code, const char *f, ...)
-{
-    va_list ap;
-    va_start(ap, f);
-    vsnprintf(g_msg, sizeof g_msg, f, ap);
-    va_end(ap);
-    return code;
-}
-}  // namespace fr
+using namespace selftest;
 
 namespace {
 
@@ -125,24 +115,6 @@ std::vector<Case> cases()
     return c;
 }
 
-std::string fmt(const char *f, ...)
-{
-    char b[256];
-    va_list ap;
-    va_start(ap, f);
-    vsnprintf(b, sizeof b, f, ap);
-    va_end(ap);
-    return b;
-}
-
-int g_failed = 0;
-void require(bool ok, const std::string &name, const char *what)
-{
-    if (ok) return;
-    fprintf(stderr, "%s: %s\n", name.c_str(), what);
-    g_failed = 1;
-}
-
 bool inside(const fr::ShadowRect &a, const fr::ShadowRect &b) { return a.x0 >= b.x0 && a.y0 >= b.y0 && a.x1 <= b.x1 && a.y1 <= b.y1; }
 
 // what the kernels rely on
@@ -175,7 +147,7 @@ int main()
     for (const Case &cs : cases()) {
         const fr::ShadowIn in{cs.src, cs.dst, cs.ss, cs.sr, cs.ds, cs.dr, cs.null_shadow ? nullptr : &cs.p, cs.flags};
         fr::ShadowPlan p;
-        g_msg[0] = 0;
+        clear_error();
         const int rc = fr::shadow_plan(in, p);
         const fr_layer_shadow_params &s = cs.p;
         printf("%s rc=%d in=%llu,%llu,%zu,%zu,%zu,%zu,%u shadow=%s | ", cs.name.c_str(), rc, (unsigned long long)cs.src, (unsigned long long)cs.dst, cs.ss,
@@ -184,7 +156,7 @@ int main()
                               : fmt("%u,%u,%u,%u,%u,%u,%u,%u,%d,%d,%u,%u,%u", s.src_x, s.src_y, s.w, s.h, s.dst_x, s.dst_y, s.dst_w, s.dst_h, s.dx, s.dy, s.spread,
                                     s.blur_radius, s.blur_passes).c_str());
         if (rc) {
-            printf("err=%s\n", g_msg);
+            printf("err=%s\n", last_error());
             continue;
         }
         std::string st;
@@ -200,5 +172,5 @@ int main()
         const fr::ShadowRecip q = fr::shadow_recip(r);
         printf("recip/%u m=%u shift=%u\n", r, q.m, q.shift);
     }
-    return g_failed;
+    return exit_status();
 }

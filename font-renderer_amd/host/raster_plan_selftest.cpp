@@ -5,15 +5,13 @@
 // which tests/test_raster_plan_tables.py compares with tests/golden/raster_plan_tables.json.  Job orders and tables of
 // more than 16 entries are printed as an FNV-1a 64 hash.
 #include "../csrc/fr_raster_plan.hpp"
+#include "selftest.hpp"
 
-#include <cstdarg>
 #include <cstdio>
 #include <string>
 #include <vector>
 
-namespace fr {
-int set_error(int code, const char *, ...) { return code; }
-}  // namespace fr
+using namespace selftest;
 
 namespace {
 
@@ -22,16 +20,6 @@ struct G { uint32_t nseg, root, ray; };
 const G GLYPHS[] = {{10, 20, 4}, {200, 200, 10}, {300, 400, 10}, {700, 900, 10}, {800, 900, 10}, {129, 100, 4}, {0, 0, 0}, {129, 2000, 4}};
 
 const fr::RasterOpts DEFAULTS = {256u, 1u, 1u, 2048u, 1u, 4u, 4u, 32u};   // the context's defaults; both kernels: 4 waves
-
-std::string fmt(const char *f, ...)
-{
-    char b[512];
-    va_list ap;
-    va_start(ap, f);
-    vsnprintf(b, sizeof b, f, ap);
-    va_end(ap);
-    return b;
-}
 
 std::string hash(const void *v, size_t n, size_t size)
 {

@@ -14,26 +14,16 @@
 //   - beyond 2^31 elements the builder answers FR_E_UNSUPPORTED and has listed no tile.
 // Exit status 1 if a property fails.
 #include "../csrc/fr_text_plan.hpp"
+#include "selftest.hpp"
 
 #include <algorithm>
 #include <array>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
 
-static char g_err[512];
-namespace fr {
-int set_error(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return code;
-}
-}  // namespace fr
+using namespace selftest;
 
 namespace {
 
@@ -67,14 +57,6 @@ struct Fnv {
     template <class T> void vec(const std::vector<T> &v) { u64(v.size()); bytes(v.data(), v.size() * sizeof(T)); }
 };
 
-int g_failed = 0;
-void check(bool ok, const std::string &where, const char *what)
-{
-    if (ok) return;
-    fprintf(stderr, "PROPERTY FAILED %s: %s\n", where.c_str(), what);
-    g_failed = 1;
-}
-
 uint32_t bits_of(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
 using Key = std::array<uint32_t, 5>;
 
@@ -88,7 +70,7 @@ template <class PLACE>
 void properties(const std::string &id, const fr::TextPlanTables<PLACE> &t, const fr::TextCacheTables &c)
 {
     const size_t ni = t.insts.size(), nc = c.cells.size();
-    check(c.insts.size() == ni, id, "one composite record per instance");
+    require(c.insts.size() == ni, id, "one composite record per instance");
     if (c.insts.size() != ni) return;
     // the cells: unique keys, extents back to back from 0 to elems
     std::vector<Key> keys;
@@ -96,16 +78,16 @@ void properties(const std::string &id, const fr::TextPlanTables<PLACE> &t, const
     for (const fr::TextMaskCell &mc : c.cells) {
         const fr::TextInstEx &in = mc.in;
         keys.push_back(Key{in.glyph, in.fx64, in.fy64, bits_of(in.scale), bits_of(in.slant)});
-        check(in.x0 == 0 && in.y0 == 0 && in.x1 > 0 && in.y1 > 0 && in.x1 <= 65535 && in.y1 <= 65535, id, "cell extent");
-        check(mc.base == at, id, "cell extents are not disjoint and back to back");
+        require(in.x0 == 0 && in.y0 == 0 && in.x1 > 0 && in.y1 > 0 && in.x1 <= 65535 && in.y1 <= 65535, id, "cell extent");
+        require(mc.base == at, id, "cell extents are not disjoint and back to back");
         at += (uint64_t)in.x1 * (uint64_t)in.y1;
-        check(in.rec == 2u * SEG_START[in.glyph], id, "cell's first record");
+        require(in.rec == 2u * SEG_START[in.glyph], id, "cell's first record");
     }
-    check(at == c.elems && c.elems <= fr::TEXT_CACHE_MAX_ELEMS, id, "the extents' sum is not the reported total");
+    require(at == c.elems && c.elems <= fr::TEXT_CACHE_MAX_ELEMS, id, "the extents' sum is not the reported total");
     {
         std::vector<Key> s = keys;
         std::sort(s.begin(), s.end());
-        check(std::adjacent_find(s.begin(), s.end()) == s.end(), id, "two cells share a key");
+        require(std::adjacent_find(s.begin(), s.end()) == s.end(), id, "two cells share a key");
     }
     // each instance's run, from the tiles that list it
     std::vector<int64_t> inst_run(ni, -1);
@@ -115,49 +97,49 @@ void properties(const std::string &id, const fr::TextPlanTables<PLACE> &t, const
     for (size_t i = 0; i < ni; ++i) {
         const auto &in = t.insts[i];
         const fr::TextCachedInst &ci = c.insts[i];
-        check(inst_run[i] >= 0, id, "instance in no tile's list");
+        require(inst_run[i] >= 0, id, "instance in no tile's list");
         if (inst_run[i] < 0) continue;
         const Key want = key_of(in, t.runs[(size_t)inst_run[i]]);
         const size_t cell = (size_t)(std::find(keys.begin(), keys.end(), want) - keys.begin());
-        check(cell < nc, id, "no cell has the instance's key");
+        require(cell < nc, id, "no cell has the instance's key");
         if (cell >= nc) continue;
         cell_used[cell] = 1;
         const fr::TextMaskCell &mc = c.cells[cell];
         const uint64_t lo = mc.base, hi = lo + (uint64_t)mc.in.x1 * (uint64_t)mc.in.y1;
-        check(ci.base == mc.base && ci.pitch == (uint32_t)mc.in.x1, id, "instance does not read the cell of its own key");
-        check(ci.x0 == in.x0 && ci.x1 == in.x1 && ci.y0 == in.y0 && ci.y1 == in.y1 && ci.rgba == in.rgba && ci.pad[0] == in.pad[0] && ci.pad[1] == in.pad[1],
-              id, "composite record differs from the instance");
+        require(ci.base == mc.base && ci.pitch == (uint32_t)mc.in.x1, id, "instance does not read the cell of its own key");
+        require(ci.x0 == in.x0 && ci.x1 == in.x1 && ci.y0 == in.y0 && ci.y1 == in.y1 && ci.rgba == in.rgba && ci.pad[0] == in.pad[0] && ci.pad[1] == in.pad[1],
+                id, "composite record differs from the instance");
         // the unclipped cell's origin: column 0 at ix + min_x, row 0 at iy - max_y (the cell holds ix = -min_x, iy = max_y)
-        check(ci.c0 == in.ix - mc.in.ix && ci.r0 == iy_of(in) - mc.in.iy, id, "cell origin");
+        require(ci.c0 == in.ix - mc.in.ix && ci.r0 == iy_of(in) - mc.in.iy, id, "cell origin");
         for (int32_t Y = ci.y0; Y < ci.y1; ++Y)
             for (int32_t X = ci.x0; X < ci.x1; ++X) {
                 const uint32_t addr = ci.base + (uint32_t)(Y - ci.r0) * ci.pitch + (uint32_t)(X - ci.c0);     // as the kernel computes it
                 const int64_t dc = (int64_t)X - ci.c0, dr = (int64_t)Y - ci.r0;
                 const bool ok = dc >= 0 && dc < mc.in.x1 && dr >= 0 && dr < mc.in.y1 && addr >= lo && addr < hi &&
                                 (uint64_t)addr == lo + (uint64_t)dr * (uint64_t)mc.in.x1 + (uint64_t)dc;
-                if (!ok) { check(false, id, "a composite read lies outside the instance's cell"); Y = ci.y1 - 1; break; }
+                if (!ok) { require(false, id, "a composite read lies outside the instance's cell"); Y = ci.y1 - 1; break; }
             }
     }
-    for (size_t k = 0; k < nc; ++k) check(cell_used[k] != 0, id, "a cell no instance reads");
+    for (size_t k = 0; k < nc; ++k) require(cell_used[k] != 0, id, "a cell no instance reads");
     // the mask tiles: every element of every cell once, by the stores glyph_mask_kernel makes
     std::vector<std::vector<uint8_t>> seen(nc);
     for (size_t k = 0; k < nc; ++k) seen[k].assign((size_t)c.cells[k].in.x1 * (size_t)c.cells[k].in.y1, 0);
     for (const fr::TextMaskTile &tl : c.tiles) {
-        check(tl.cell < nc, id, "tile names no cell");
+        require(tl.cell < nc, id, "tile names no cell");
         if (tl.cell >= nc) continue;
         const fr::TextInstEx &in = c.cells[tl.cell].in;
-        check(tl.x0 % fr::TEXT_TILE_W == 0 && tl.y0 % fr::TEXT_TILE_H == 0 && (int64_t)tl.x0 < in.x1 && (int64_t)tl.y0 < in.y1, id, "tile origin");
+        require(tl.x0 % fr::TEXT_TILE_W == 0 && tl.y0 % fr::TEXT_TILE_H == 0 && (int64_t)tl.x0 < in.x1 && (int64_t)tl.y0 < in.y1, id, "tile origin");
         for (int yy = 0; yy < fr::TEXT_TILE_H; ++yy)
             for (int lane = 0; lane < fr::TEXT_TILE_W; ++lane) {
                 const int X = (int)tl.x0 + lane, Y = (int)tl.y0 + yy;
                 if (Y >= in.y1 || X >= in.x1) continue;                    // (the kernel's two guards)
                 const uint32_t e = (uint32_t)Y * (uint32_t)in.x1 + (uint32_t)X;
-                check(e < seen[tl.cell].size(), id, "a mask store lies outside its cell");
+                require(e < seen[tl.cell].size(), id, "a mask store lies outside its cell");
                 if (e < seen[tl.cell].size()) ++seen[tl.cell][e];
             }
     }
     for (size_t k = 0; k < nc; ++k)
-        check(std::all_of(seen[k].begin(), seen[k].end(), [](uint8_t v) { return v == 1; }), id, "the mask tiles do not cover a cell exactly once");
+        require(std::all_of(seen[k].begin(), seen[k].end(), [](uint8_t v) { return v == 1; }), id, "the mask tiles do not cover a cell exactly once");
 }
 
 template <class PLACE>
@@ -180,15 +162,15 @@ void run_form(const Case &c, const char *form)
     in.glyph_seg_start = SEG_START;
     in.n_glyphs = 6;
     fr::TextPlanTables<PLACE> t;
-    g_err[0] = 0;
+    clear_error();
     int rc = fr::text_plan_tables(in, places.data(), t);
     fr::TextCacheTables ct;
     if (rc == FR_OK) {
         rc = fr::text_cache_tables(in, places.data(), t, ct);
-        if (rc != FR_OK) check(ct.tiles.empty(), id, "tiles listed although the builder failed");
+        if (rc != FR_OK) require(ct.tiles.empty(), id, "tiles listed although the builder failed");
     }
     if (rc != FR_OK) {
-        printf("%s error %d: %s\n", id.c_str(), rc, g_err);
+        printf("%s error %d: %s\n", id.c_str(), rc, last_error());
         return;
     }
     properties(id, t, ct);
@@ -243,5 +225,5 @@ int main()
     // the store's limit: two keys whose cells hold 40001 x 40001 elements each; one such cell alone is within it
     add("err_store_cap", BOTH, {run(0, 2, 100, 100, 0, 0, 1.25f)}, {at(5, 0, 50 * 64), at(5, 1, 50 * 64)});
     for (const Case &c : cases) run_case(c);
-    return g_failed;
+    return exit_status();
 }

@@ -13,27 +13,17 @@
 // fr_plan_describe prints>", then text_launch_name over a box of keys: one "name/..." line per key that has a kernel.
 // In every mode each plan's list is checked against what the render and the description rely on (launch_properties).
 #include "../csrc/fr_text_plan.hpp"
+#include "selftest.hpp"
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <string>
 #include <type_traits>
 #include <vector>
 
-static char g_err[512];
-namespace fr {
-int set_error(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return code;
-}
-}  // namespace fr
+using namespace selftest;
 
 namespace {
 
@@ -85,14 +75,6 @@ struct Fnv {
     template <class T> void vec(const std::vector<T> &v) { u64(v.size()); bytes(v.data(), v.size() * sizeof(T)); }
 };
 
-int g_failed = 0;
-void check(bool ok, const std::string &where, const char *what)
-{
-    if (ok) return;
-    fprintf(stderr, "PROPERTY FAILED %s: %s\n", where.c_str(), what);
-    g_failed = 1;
-}
-
 template <class PLACE>
 void properties(const std::string &id, const Case &c, const fr::TextPlanTables<PLACE> &t)
 {
@@ -102,28 +84,28 @@ void properties(const std::string &id, const Case &c, const fr::TextPlanTables<P
     std::vector<int64_t> inst_run(ni, -1);
     uint32_t at = 0;
     for (const auto &tl : t.tiles) {
-        check(tl.lbeg == at && tl.lend >= tl.lbeg && tl.lend <= t.list.size(), id, "tile lists do not partition the list");
+        require(tl.lbeg == at && tl.lend >= tl.lbeg && tl.lend <= t.list.size(), id, "tile lists do not partition the list");
         at = tl.lend;
-        check(!load || tl.lend > tl.lbeg, id, "empty tile listed under FR_TEXT_LOAD");
+        require(!load || tl.lend > tl.lbeg, id, "empty tile listed under FR_TEXT_LOAD");
         for (uint32_t k = tl.lbeg; k < tl.lend && k < t.list.size(); ++k) {
             const uint32_t i = t.list[k];
-            check(i < ni, id, "list names no instance");
+            require(i < ni, id, "list names no instance");
             if (i >= ni) continue;
-            check(k == tl.lbeg || t.list[k - 1] < i, id, "a tile's list is not in placement order");
-            check(inst_run[i] < 0 || inst_run[i] == (int64_t)tl.run, id, "instance listed by two runs");
+            require(k == tl.lbeg || t.list[k - 1] < i, id, "a tile's list is not in placement order");
+            require(inst_run[i] < 0 || inst_run[i] == (int64_t)tl.run, id, "instance listed by two runs");
             inst_run[i] = tl.run;
         }
     }
-    check(at == t.list.size(), id, "list longer than the tiles' ranges");
-    check(t.runs.size() == c.runs.size(), id, "run count");
+    require(at == t.list.size(), id, "list longer than the tiles' ranges");
+    require(t.runs.size() == c.runs.size(), id, "run count");
     for (size_t i = 0; i < ni; ++i) {
         const auto &in = t.insts[i];
-        check(inst_run[i] >= 0, id, "instance in no tile's list");
+        require(inst_run[i] >= 0, id, "instance in no tile's list");
         if (inst_run[i] < 0) continue;
-        check(i == 0 || inst_run[i - 1] <= inst_run[i], id, "instances not in run order");
+        require(i == 0 || inst_run[i - 1] <= inst_run[i], id, "instances not in run order");
         const fr::TextRun &r = t.runs[(size_t)inst_run[i]];
-        check(0 <= in.x0 && in.x0 < in.x1 && in.x1 <= (int64_t)r.w && 0 <= in.y0 && in.y0 < in.y1 && in.y1 <= (int64_t)r.h, id,
-              "instance cell not inside its run");
+        require(0 <= in.x0 && in.x0 < in.x1 && in.x1 <= (int64_t)r.w && 0 <= in.y0 && in.y0 < in.y1 && in.y1 <= (int64_t)r.h, id,
+                "instance cell not inside its run");
     }
     // every tile of every run, in order: listed (without LOAD always), and its list is exactly the run's instances that meet it
     size_t k = 0;
@@ -139,19 +121,19 @@ void properties(const std::string &id, const Case &c, const fr::TextPlanTables<P
                 }
                 const bool here = k < t.tiles.size() && t.tiles[k].run == r && t.tiles[k].x0 == x0 && t.tiles[k].y0 == y0;
                 if (!here) {
-                    check(load && want.empty(), id, "a tile is missing");
+                    require(load && want.empty(), id, "a tile is missing");
                     continue;
                 }
                 const auto &tl = t.tiles[k++];
                 const std::vector<uint32_t> got(t.list.begin() + tl.lbeg, t.list.begin() + std::min<size_t>(tl.lend, t.list.size()));
-                check(got == want, id, "a tile's list is not the instances whose cell meets it");
+                require(got == want, id, "a tile's list is not the instances whose cell meets it");
             }
-    check(k == t.tiles.size(), id, "tiles that belong to no run");
+    require(k == t.tiles.size(), id, "tiles that belong to no run");
     std::vector<uint32_t> used;
     for (const auto &in : t.insts) used.push_back(in.glyph);
     std::sort(used.begin(), used.end());
     used.erase(std::unique(used.begin(), used.end()), used.end());
-    check(used == t.glyphs, id, "glyph list not sorted and exact");
+    require(used == t.glyphs, id, "glyph list not sorted and exact");
 }
 
 // what the render and fr_plan_describe rely on when they walk one list (text_launches, csrc/fr_text_plan.cpp): a plan without
@@ -159,16 +141,16 @@ void properties(const std::string &id, const Case &c, const fr::TextPlanTables<P
 // composite over the plan's tiles; the entries come in stream order, each with a kernel name
 void launch_properties(const std::string &id, const fr::TextPlan &p, const fr::TextLaunchList &L)
 {
-    if (!p.n_tiles) check(!p.n_insts && !p.n_glyphs && !p.cached && !p.n_mcells && L.n == 0, id, "a plan without tiles has something to launch");
-    else check(L.n >= 1 && L.l[L.n - 1].family == (p.cached ? fr::TL_CACHED : fr::TL_TEXT) && L.l[L.n - 1].grid == p.n_tiles &&
-               L.l[L.n - 1].count == p.n_insts, id, "the list does not end in the plan's text kernel over its tiles");
-    check(L.n == (p.n_glyphs ? 1u : 0u) + (p.cached ? 1u : 0u) + (p.n_tiles ? 1u : 0u), id, "launch count");
-    check(!p.n_insts == !p.n_glyphs && (!p.cached || (p.n_mcells && p.n_mtiles >= p.n_mcells && p.n_glyphs)), id, "instances, glyphs and mask cells disagree");
+    if (!p.n_tiles) require(!p.n_insts && !p.n_glyphs && !p.cached && !p.n_mcells && L.n == 0, id, "a plan without tiles has something to launch");
+    else require(L.n >= 1 && L.l[L.n - 1].family == (p.cached ? fr::TL_CACHED : fr::TL_TEXT) && L.l[L.n - 1].grid == p.n_tiles &&
+                 L.l[L.n - 1].count == p.n_insts, id, "the list does not end in the plan's text kernel over its tiles");
+    require(L.n == (p.n_glyphs ? 1u : 0u) + (p.cached ? 1u : 0u) + (p.n_tiles ? 1u : 0u), id, "launch count");
+    require(!p.n_insts == !p.n_glyphs && (!p.cached || (p.n_mcells && p.n_mtiles >= p.n_mcells && p.n_glyphs)), id, "instances, glyphs and mask cells disagree");
     for (uint32_t i = 0; i < L.n; ++i) {
         char name[96];
         fr::text_launch_name(L.l[i], name, sizeof name);
-        check(name[0] != 0 && L.l[i].grid != 0, id, "a launch without a kernel or without workgroups");
-        check(i == 0 || L.l[i - 1].family < L.l[i].family, id, "launches out of stream order");
+        require(name[0] != 0 && L.l[i].grid != 0, id, "a launch without a kernel or without workgroups");
+        require(i == 0 || L.l[i - 1].family < L.l[i].family, id, "launches out of stream order");
     }
 }
 
@@ -195,17 +177,17 @@ Outcome run_form(const Case &c, const char *form, Mode mode = TABLES)
     in.glyph_seg_start = SEG_START;
     in.n_glyphs = 6;
     fr::TextPlanTables<PLACE> t;
-    g_err[0] = 0;
+    clear_error();
     const int rc = fr::text_plan_tables(in, c.null_places ? nullptr : places.data(), t);
     if (rc != FR_OK) {
-        printf("%s error %d: %s\n", id.c_str(), rc, g_err);
+        printf("%s error %d: %s\n", id.c_str(), rc, last_error());
         return Outcome{false, 0, 0};
     }
     properties(id, c, t);
     // the launches: as fr_api.hip makes them, FR_TEXT_CACHE tables included where the form has them and some cell exists
     fr::TextCacheTables cache;
     if constexpr (!std::is_same<PLACE, fr_glyph_place_affine>::value) {
-        if (c.flags & FR_TEXT_CACHE) check(fr::text_cache_tables(in, places.data(), t, cache) == FR_OK, id, "text_cache_tables failed");
+        if (c.flags & FR_TEXT_CACHE) require(fr::text_cache_tables(in, places.data(), t, cache) == FR_OK, id, "text_cache_tables failed");
     }
     const fr_raster_params params{FR_COVERAGE_U8, c.samples, FR_SAMPLE_CENTER, 0};
     const fr::TextPlan plan = fr::text_plan_of(in, params, t, cache.cells.empty() ? nullptr : &cache);
@@ -245,9 +227,9 @@ void run_over_form(const Case &c, const char *form)
     o.flags |= FR_TEXT_OVER;
     const Outcome with = run_form<PLACE>(o, form, OVER);
     const std::string id = name + "/" + form;
-    check(plain.ok && with.ok, id, "an FR_TEXT_OVER case failed to build");
-    check(plain.hash == with.hash, id, "FR_TEXT_OVER changed a table");
-    check(with.blend == (plain.blend ? 2 : 0), id, "blend is not 2 for translucent colours and 0 for opaque ones under FR_TEXT_OVER");
+    require(plain.ok && with.ok, id, "an FR_TEXT_OVER case failed to build");
+    require(plain.hash == with.hash, id, "FR_TEXT_OVER changed a table");
+    require(with.blend == (plain.blend ? 2 : 0), id, "blend is not 2 for translucent colours and 0 for opaque ones under FR_TEXT_OVER");
 }
 
 void run_case(const Case &c, Mode mode = TABLES)
@@ -322,7 +304,7 @@ int main(int argc, char **argv)
             if (c.forms & EX) run_over_form<fr_glyph_place_ex>(c, "ex");
             if (c.forms & AFFINE) run_over_form<fr_glyph_place_affine>(c, "affine");
         }
-        return g_failed;
+        return exit_status();
     }
     if (launches) {
         // cases of the other two lists with the flags and sample counts that choose an instance, and the three plans whose
@@ -349,7 +331,7 @@ int main(int argc, char **argv)
         add("no_runs", ALL, {}, three);
         for (const Case &c : cases) run_case(c, LAUNCHES);
         sweep_names();
-        return g_failed;
+        return exit_status();
     }
     add("coverage", ALL, one, three);
     rgba(add("rgba_translucent", ALL, one, three), 0u, 128);
@@ -409,5 +391,5 @@ int main(int argc, char **argv)
     add("err_order_pen_before_matrix", EX | AFFINE, R(1), {Place{0, 0x7fffffff, 0, -1.0f, 0.0f, {1, 2, 2, 4}}});
 
     for (const Case &c : cases) run_case(c);
-    return g_failed;
+    return exit_status();
 }

@@ -11,40 +11,19 @@ import layer_ref as lr
 from fixtures import load_font
 from font_renderer_amd import _lib as L
 from font_renderer_amd import render_glyph as rg
+from layer_gpu import SENT, Guarded, premultiplied
 
 pytestmark = pytest.mark.gpu
-SENT = 0x5b
 OPACITIES = (0, 1, 2, 127, 128, 129, 253, 254, 255)
 DEST_C = (0, 1, 127, 254, 255)
-GUARD = 3                              # rows of sentinel before and after every destination
 
 
 def _over(ctx, layer, image, blits, srgb=False, src_skip=0, dst_skip=0):
-    """fr_layer_over of `layer` (rows, stride, 4) over a device copy of `image` -> (image after, with its guard rows checked;
-    the layer after).  src_skip / dst_skip: pixels the device arrays are moved by, to leave the 16-byte grid."""
-    import torch
-    guard = np.full((GUARD, image.shape[1], 4), SENT, np.uint8)
-    flat = np.concatenate([np.full((dst_skip, 4), SENT, np.uint8), guard.reshape(-1, 4), image.reshape(-1, 4), guard.reshape(-1, 4)])
-    dst = torch.from_numpy(flat).to("cuda:0")
-    src = torch.from_numpy(np.concatenate([np.zeros((src_skip, 4), np.uint8), layer.reshape(-1, 4)])).to("cuda:0")
-    torch.cuda.synchronize()
-    first = dst_skip + guard.shape[0] * guard.shape[1]
-    rg.layer_over(ctx, src.data_ptr() + 4 * src_skip, layer.shape[1], layer.shape[0], dst.data_ptr() + 4 * first, image.shape[1],
-                  image.shape[0], blits, srgb)
-    ctx.sync()
-    got = dst.cpu().numpy()
-    n = image.shape[0] * image.shape[1]
-    assert (got[:first] == SENT).all() and (got[first + n:] == SENT).all(), "bytes written outside the destination's rows"
-    return got[first:first + n].reshape(image.shape), src.cpu().numpy()[src_skip:].reshape(layer.shape)
-
-
-def _premultiplied(rng, shape):
-    """random valid premultiplied pixels (colour <= alpha) with a share of (0, 0, 0, 0) and of opaque ones"""
-    a = rng.integers(0, 256, shape + (1,))
-    kind = rng.integers(0, 4, shape + (1,))
-    a = np.where(kind == 0, 0, np.where(kind == 1, 255, a))
-    c = rng.integers(0, 256, shape + (3,)) * a // 255
-    return np.concatenate([c, a], -1).astype(np.uint8)
+    """fr_layer_over of `layer` (rows, stride, 4) over a guarded device copy of `image` -> (image after, the layer after).
+    src_skip / dst_skip: pixels the device arrays are moved by, to leave the 16-byte grid."""
+    d = Guarded(image, layer, dst_skip, src_skip)
+    rg.layer_over(ctx, d.src, layer.shape[1], layer.shape[0], d.dst, image.shape[1], image.shape[0], blits, srgb)
+    return d.result(ctx), d.layer_after
 
 
 @pytest.fixture(scope="module")
@@ -111,8 +90,8 @@ GEOMETRY = {
 def small():
     """the 97 x 41 layer in rows of 97 pixels, and the same pixels in rows of 100 (three more columns of other pixels)"""
     rng = np.random.default_rng(7)
-    layer = _premultiplied(rng, (41, 97))
-    return layer, np.concatenate([layer, _premultiplied(rng, (41, 3))], 1)
+    layer = premultiplied(rng, (41, 97))
+    return layer, np.concatenate([layer, premultiplied(rng, (41, 3))], 1)
 
 
 @pytest.mark.parametrize("srgb", [False, True], ids=["unorm", "srgb"])
@@ -195,7 +174,7 @@ def test_unpremultiply_is_the_host_function(ctx, srgb):
     # a 97 x 41 window at (3, 2) of a 50-row image in rows of 131
     rng = np.random.default_rng(11)
     image = np.full((50, 131, 4), SENT, np.uint8)
-    image[2:43, 3:100] = _premultiplied(rng, (41, 97))
+    image[2:43, 3:100] = premultiplied(rng, (41, 97))
     win = np.ascontiguousarray(image[2:43, 3:100]).reshape(-1, 4)
     want = image.copy()
     want[2:43, 3:100] = fr.RGBA(97, 41, win).unpremultiply(srgb).data.reshape(41, 97, 4)
@@ -208,7 +187,7 @@ def test_unpremultiply_is_the_host_function(ctx, srgb):
 
 def test_rgba_over_method(ctx, small):
     layer = fr.RGBA(97, 41, small[0].reshape(-1, 4).copy())
-    frame = fr.RGBA(120, 45, _premultiplied(np.random.default_rng(5), (45, 120)).reshape(-1, 4))
+    frame = fr.RGBA(120, 45, premultiplied(np.random.default_rng(5), (45, 120)).reshape(-1, 4))
     before = frame.data.reshape(45, 120, 4).copy()
     assert frame.over(layer, x=-4, y=9, opacity=77, srgb=True, ctx=ctx) is frame
     assert np.array_equal(frame.as_3d(), lr.composite(small[0], before, [(0, 0, 97, 41, -4, 9, 77)], True))

@@ -12,42 +12,23 @@ import layer_rects_ref as rr
 from fixtures import load_font
 from font_renderer_amd import _lib as L
 from font_renderer_amd import render_glyph as rg
+from layer_gpu import SENT, Guarded, premultiplied
 
 pytestmark = pytest.mark.gpu
-SENT = 0x5b
-GUARD = 3                              # rows of sentinel before and after every destination
 MAXI, MINI = 2 ** 31 - 1, -2 ** 31
 
 
 def _rects(ctx, image, rows, srgb=False, dst_skip=0):
-    """fr_layer_rects of `rows` (edges in 1/64 pixel) over a device copy of `image` (rows, stride, 4) -> the image after, with
-    its guard rows checked.  dst_skip: pixels the device array is moved by, to leave the 16-byte grid."""
-    import torch
-    guard = np.full((GUARD * image.shape[1], 4), SENT, np.uint8)
-    flat = np.concatenate([np.full((dst_skip, 4), SENT, np.uint8), guard, image.reshape(-1, 4), guard])
-    dst = torch.from_numpy(flat).to("cuda:0")
-    torch.cuda.synchronize()
-    first = dst_skip + guard.shape[0]
-    rg.layer_rects(ctx, dst.data_ptr() + 4 * first, image.shape[1], image.shape[0], None if rows is None else rg.make_rects(rows), srgb)
-    ctx.sync()
-    got = dst.cpu().numpy()
-    n = image.shape[0] * image.shape[1]
-    assert (got[:first] == SENT).all() and (got[first + n:] == SENT).all(), "bytes written outside the destination's rows"
-    return got[first:first + n].reshape(image.shape)
-
-
-def _premultiplied(rng, shape):
-    """random valid premultiplied pixels (colour <= alpha) with a share of (0, 0, 0, 0) and of opaque ones"""
-    a = rng.integers(0, 256, shape + (1,))
-    kind = rng.integers(0, 4, shape + (1,))
-    a = np.where(kind == 0, 0, np.where(kind == 1, 255, a))
-    c = rng.integers(0, 256, shape + (3,)) * a // 255
-    return np.concatenate([c, a], -1).astype(np.uint8)
+    """fr_layer_rects of `rows` (edges in 1/64 pixel) over a guarded device copy of `image` (rows, stride, 4) -> the image
+    after.  dst_skip: pixels the device array is moved by, to leave the 16-byte grid."""
+    d = Guarded(image, dst_skip=dst_skip)
+    rg.layer_rects(ctx, d.dst, image.shape[1], image.shape[0], None if rows is None else rg.make_rects(rows), srgb)
+    return d.result(ctx)
 
 
 @pytest.fixture(scope="module")
 def noise():
-    return _premultiplied(np.random.default_rng(31), (130, 130))
+    return premultiplied(np.random.default_rng(31), (130, 130))
 
 
 @pytest.mark.parametrize("srgb", [False, True], ids=["unorm", "srgb"])

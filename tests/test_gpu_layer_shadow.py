@@ -13,62 +13,32 @@ import text_gpu as tg
 from fixtures import load_font
 from font_renderer_amd import _lib as L
 from font_renderer_amd import render_glyph as rg
+from layer_gpu import SENT, Guarded, premultiplied
 
 pytestmark = pytest.mark.gpu
-SENT = 0x5b
-GUARD = 3                              # rows of sentinel before and after every destination
 
 
-class Dev:
+def _dev(layer, dst_shape, src_skip=0, dst_skip=0):
     """a layer and a sentinel-filled destination on the device, each optionally moved off the 16-byte grid"""
+    return Guarded(np.full(dst_shape + (4,), SENT, np.uint8), layer, dst_skip, src_skip)
 
-    def __init__(self, layer, dst_shape, src_skip=0, dst_skip=0, image=None):
-        import torch
-        self.layer, self.src_skip, self.dst_skip = layer, src_skip, dst_skip
-        self.image = np.full(dst_shape + (4,), SENT, np.uint8) if image is None else image
-        rows, stride = self.image.shape[:2]
-        guard = np.full((GUARD * stride, 4), SENT, np.uint8)
-        self.first = dst_skip + GUARD * stride
-        self.flat = np.concatenate([np.full((dst_skip, 4), SENT, np.uint8), guard, self.image.reshape(-1, 4), guard])
-        self.dst = torch.from_numpy(self.flat).to("cuda:0")
-        self.src = torch.from_numpy(np.concatenate([np.zeros((src_skip, 4), np.uint8), layer.reshape(-1, 4)])).to("cuda:0")
-        torch.cuda.synchronize()
 
-    def shadow(self, ctx, window, rect, offset, s, r, p, rgba, srgb=False, flags=0):
-        rg.layer_shadow(ctx, self.src.data_ptr() + 4 * self.src_skip, self.layer.shape[1], self.layer.shape[0],
-                        self.dst.data_ptr() + 4 * self.first, self.image.shape[1], self.image.shape[0], window, rect, offset, s, r, p, rgba, srgb,
-                        flags)
-
-    def result(self, ctx):
-        """the image after, with its guard rows and the layer checked"""
-        ctx.sync()
-        got = self.dst.cpu().numpy()
-        n = self.image.shape[0] * self.image.shape[1]
-        assert (got[:self.first] == SENT).all() and (got[self.first + n:] == SENT).all(), "bytes written outside the destination's rows"
-        assert np.array_equal(self.src.cpu().numpy()[self.src_skip:].reshape(self.layer.shape), self.layer), "the layer was written"
-        return got[self.first:self.first + n].reshape(self.image.shape)
+def _shadow(ctx, d, window, rect, offset, s, r, p, rgba, srgb=False, flags=0):
+    rg.layer_shadow(ctx, d.src, d.layer.shape[1], d.layer.shape[0], d.dst, d.image.shape[1], d.image.shape[0], window, rect, offset, s, r, p, rgba, srgb,
+                    flags)
 
 
 def _run(ctx, layer, dst_shape, window, rect, offset, s, r, p, rgba, srgb=False, src_skip=0, dst_skip=0):
     """one call on fresh buffers -> (got, want)"""
-    d = Dev(layer, dst_shape, src_skip, dst_skip)
-    d.shadow(ctx, window, rect, offset, s, r, p, rgba, srgb)
+    d = _dev(layer, dst_shape, src_skip, dst_skip)
+    _shadow(ctx, d, window, rect, offset, s, r, p, rgba, srgb)
     return d.result(ctx), sr.shadow(layer, d.image, window, rect, offset, s, r, p, rgba, srgb)
-
-
-def _premultiplied(rng, shape):
-    """random valid premultiplied pixels (colour <= alpha) with a share of (0, 0, 0, 0) and of opaque ones"""
-    a = rng.integers(0, 256, shape + (1,))
-    kind = rng.integers(0, 4, shape + (1,))
-    a = np.where(kind == 0, 0, np.where(kind == 1, 255, a))
-    c = rng.integers(0, 256, shape + (3,)) * a // 255
-    return np.concatenate([c, a], -1).astype(np.uint8)
 
 
 @pytest.fixture(scope="module")
 def layers():
     rng = np.random.default_rng(17)
-    return {"small": _premultiplied(rng, (41, 97)), "wide": _premultiplied(rng, (70, 300))}
+    return {"small": premultiplied(rng, (41, 97)), "wide": premultiplied(rng, (70, 300))}
 
 
 # ---- impulses ----------------------------------------------------------------------------------------------------------
@@ -149,12 +119,12 @@ def test_rectangle_widths(ctx, layers, dst_w, dst_x):
 
 def test_zero_sizes(ctx, layers):
     """dst_w or dst_h of 0 writes nothing; a window without area writes zeros over the rectangle"""
-    d = Dev(layers["small"], (50, 132))
-    d.shadow(ctx, (0, 0, 97, 41), (7, 7, 0, 30), (0, 0), 1, 3, 3, (1, 2, 3, 255))
-    d.shadow(ctx, (0, 0, 97, 41), (1000, 1000, 30, 0), (0, 0), 1, 3, 3, (1, 2, 3, 255))
+    d = _dev(layers["small"], (50, 132))
+    _shadow(ctx, d, (0, 0, 97, 41), (7, 7, 0, 30), (0, 0), 1, 3, 3, (1, 2, 3, 255))
+    _shadow(ctx, d, (0, 0, 97, 41), (1000, 1000, 30, 0), (0, 0), 1, 3, 3, (1, 2, 3, 255))
     assert np.array_equal(d.result(ctx), d.image)
-    d.shadow(ctx, (500, 500, 0, 41), (7, 8, 90, 30), (0, 0), 1, 3, 3, (1, 2, 3, 255))
-    d.shadow(ctx, (0, 0, 97, 0), (100, 40, 31, 9), (0, 0), 0, 0, 0, (1, 2, 3, 255))
+    _shadow(ctx, d, (500, 500, 0, 41), (7, 8, 90, 30), (0, 0), 1, 3, 3, (1, 2, 3, 255))
+    _shadow(ctx, d, (0, 0, 97, 0), (100, 40, 31, 9), (0, 0), 0, 0, 0, (1, 2, 3, 255))
     want = d.image.copy()
     want[8:38, 7:97] = 0
     want[40:49, 100:131] = 0
@@ -192,10 +162,10 @@ def test_tint_over_its_domain(ctx, srgb):
     layer[..., :3] = 77
     colours = [((3 * A) % 256, (255 - A) % 256, (A * 7 + 1) % 256, A) for A in range(256)]
     colours += [(k, (k + 86) % 256, (k + 172) % 256, 255) for k in range(86)]
-    d = Dev(layer, (4 * len(colours), 256))
+    d = _dev(layer, (4 * len(colours), 256))
     want = d.image.copy()
     for i, c in enumerate(colours):
-        d.shadow(ctx, (0, 0, 256, 4), (0, 4 * i, 256, 4), (0, 0), 0, 0, 0, c, srgb)
+        _shadow(ctx, d, (0, 0, 256, 4), (0, 4 * i, 256, 4), (0, 0), 0, 0, 0, c, srgb)
         want = sr.shadow(layer, want, (0, 0, 256, 4), (0, 4 * i, 256, 4), (0, 0), 0, 0, 0, c, srgb)
     got = d.result(ctx)
     assert np.array_equal(got, want), np.argwhere(got != want)[:4]
@@ -250,8 +220,8 @@ def test_rgba_shadow_method(ctx, layers):
 
 # ---- validation through the ABI --------------------------------------------------------------------------------------------
 def test_refusals_leave_the_destination_untouched(ctx, layers):
-    d = Dev(layers["small"], (50, 132))
-    S, D = d.src.data_ptr(), d.dst.data_ptr() + 4 * d.first
+    d = _dev(layers["small"], (50, 132))
+    S, D = d.src, d.dst
     win, rect = (0, 0, 97, 41), (0, 0, 100, 50)
 
     def call(s=S, ss=97, srows=41, dp=D, ds=132, dr=50, window=win, rc=rect, stages=(1, 3, 3), flags=0):

@@ -7,21 +7,15 @@ restated here on their own."""
 import json
 import os
 import re
-import subprocess
+
+import host_selftest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "font-renderer_amd", "csrc")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "host_rules.json")
-_cache = {}
 
 
 def _lines():
-    if not _cache:
-        subprocess.check_call(["make", "-C", CSRC, "../host/host_rules_selftest"], stdout=subprocess.DEVNULL)
-        run = subprocess.run([os.path.join(ROOT, "font-renderer_amd", "host", "host_rules_selftest")], capture_output=True, text=True)
-        assert run.returncode == 0, run.stderr
-        _cache.update(line.split(" ", 1) for line in run.stdout.splitlines())
-    return _cache
+    return host_selftest.named("host_rules_selftest")
 
 
 def test_host_rules_match_golden():

@@ -3,27 +3,14 @@ case, the inputs and what the builder made of them: the records, the tiles and t
 is compared with a restatement of the checks, the clipping and the binning written here from include/fr_raster.h and the
 comments of fr_layer_rects_plan.hpp, computed from the inputs the line itself names; the program checks the properties of
 its tables on its own and fails if one does not hold."""
-import os
-import subprocess
-
+import host_selftest
 import layer_rects_ref as rr
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "font-renderer_amd", "csrc")
 TILE_W, TILE_H, MAX_EDGE, MAX_TILES, MAX_PAIRS = 256, 16, 2 ** 31 - 1, 1 << 22, 1 << 24
-_cache = {}
 
 
 def _lines():
-    if not _cache:
-        subprocess.check_call(["make", "-C", CSRC, "../host/layer_rects_selftest"], stdout=subprocess.DEVNULL)
-        run = subprocess.run([os.path.join(ROOT, "font-renderer_amd", "host", "layer_rects_selftest")], capture_output=True, text=True)
-        assert run.returncode == 0, run.stderr          # a property failed: stderr names the case and the property
-        for line in run.stdout.splitlines():
-            name, rest = line.split(" ", 1)
-            head, tail = rest.split(" | ", 1)
-            _cache[name] = (dict(f.split("=", 1) for f in head.split(" ") if "=" in f), "null" in head.split(" "), tail)
-    return _cache
+    return host_selftest.cases("layer_rects_selftest")
 
 
 def _rows(text):

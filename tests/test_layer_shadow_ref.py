@@ -1,17 +1,12 @@
 """The numpy twin of fr_layer_shadow (tests/layer_shadow_ref.py) held to a brute-force loop over the header's definition,
 to the header's six consequences, and the reciprocal constants of the box division (csrc/fr_layer_shadow_plan.cpp, printed
 by host/layer_shadow_selftest) to every numerator they can meet.  No GPU."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import host_selftest
 import layer_ref as lr
 import layer_shadow_ref as sr
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "font-renderer_amd", "csrc")
 
 
 def _brute(a0, s, r, p):
@@ -141,11 +136,8 @@ def test_tint_is_the_text_plans_sample():
 def test_reciprocal_constants_are_exact():
     """the kernel divides by W = (2 r + 1)^2 as (n * m) >> (32 + shift) with the constants shadow_recip() hands it: every
     numerator 0 .. 255 W + W div 2 of every radius 1 .. 32"""
-    subprocess.check_call(["make", "-C", CSRC, "../host/layer_shadow_selftest"], stdout=subprocess.DEVNULL)
-    run = subprocess.run([os.path.join(ROOT, "font-renderer_amd", "host", "layer_shadow_selftest")], capture_output=True, text=True)
-    assert run.returncode == 0, run.stderr
     seen = {}
-    for line in run.stdout.splitlines():
+    for line in host_selftest.lines("layer_shadow_selftest"):
         if line.startswith("recip/"):
             name, m, shift = line.split(" ")
             seen[int(name.split("/")[1])] = (int(m.split("=")[1]), int(shift.split("=")[1]))

@@ -3,27 +3,18 @@ case, the inputs and what the planner made of them: the stage list with every st
 reciprocal of the box division, or the refusal.  Every line is compared with a restatement of the checks and the rectangles
 written here from include/fr_raster.h, computed from the inputs the line itself names; the program checks on its own that
 every stage's rectangle lies inside its input's rectangle grown by the radius and fails if not."""
-import os
-import subprocess
+import host_selftest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "font-renderer_amd", "csrc")
 TILE = 64
-_cache = {}
 
 
 def _lines():
-    if not _cache:
-        subprocess.check_call(["make", "-C", CSRC, "../host/layer_shadow_selftest"], stdout=subprocess.DEVNULL)
-        run = subprocess.run([os.path.join(ROOT, "font-renderer_amd", "host", "layer_shadow_selftest")], capture_output=True, text=True)
-        assert run.returncode == 0, run.stderr          # a property failed: stderr names the case and the property
-        for line in run.stdout.splitlines():
-            if line.startswith("recip/"):
-                continue
-            name, rest = line.split(" ", 1)
+    out = {}
+    for name, rest in host_selftest.named("layer_shadow_selftest").items():
+        if not name.startswith("recip/"):
             head, tail = rest.split(" | ", 1)
-            _cache[name] = (dict(f.split("=", 1) for f in head.split(" ")), tail)
-    return _cache
+            out[name] = (dict(f.split("=", 1) for f in head.split(" ")), tail)
+    return out
 
 
 def _cut(a, b):

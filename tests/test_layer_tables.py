@@ -3,29 +3,16 @@ and what the builder made of them: the clipped rectangles and the tile table, or
 a restatement of the clipping, the overlap rule and the tiling written here from include/fr_raster.h and the comments of
 fr_layer_plan.hpp, computed from the inputs the line itself names; the program checks the coverage properties of its
 tables on its own and fails if one does not hold."""
-import os
-import subprocess
-
 import pytest
 
+import host_selftest
 import layer_ref as lr
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "font-renderer_amd", "csrc")
 TILE_W, TILE_H, LANE_PX, DST_VEC, SRC_VEC = 256, 16, 4, 0x100, 0x200
-_cache = {}
 
 
 def _lines():
-    if not _cache:
-        subprocess.check_call(["make", "-C", CSRC, "../host/layer_selftest"], stdout=subprocess.DEVNULL)
-        run = subprocess.run([os.path.join(ROOT, "font-renderer_amd", "host", "layer_selftest")], capture_output=True, text=True)
-        assert run.returncode == 0, run.stderr          # a property failed: stderr names the case and the property
-        for line in run.stdout.splitlines():
-            name, rest = line.split(" ", 1)
-            head, tail = rest.split(" | ", 1)
-            _cache[name] = (dict(f.split("=", 1) for f in head.split(" ") if "=" in f), "null" in head.split(" "), tail)
-    return _cache
+    return host_selftest.cases("layer_selftest")
 
 
 def _rows(text):

@@ -6,22 +6,18 @@ but not yet restructured; its name/ lines (the kernel instance of every launch, 
 launch list began to carry the instance."""
 import json
 import os
-import subprocess
 
 import numpy as np
 
+import host_selftest
 import instance_cases as ic
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "font-renderer_amd", "csrc")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "raster_plan_tables.json")
 
 
 def _lines():
-    subprocess.check_call(["make", "-C", CSRC, "../host/raster_plan_selftest"], stdout=subprocess.DEVNULL)
-    run = subprocess.run([os.path.join(ROOT, "font-renderer_amd", "host", "raster_plan_selftest")], capture_output=True, text=True)
-    assert run.returncode == 0, run.stderr
-    return dict(line.split(" ", 1) for line in run.stdout.splitlines())
+    return host_selftest.named("raster_plan_selftest")
 
 
 def test_raster_plan_tables_match_golden():

@@ -8,18 +8,15 @@ the flag's value in the Python and Zig mirrors of the header."""
 import json
 import os
 import re
-import subprocess
+
+import host_selftest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "font-renderer_amd", "csrc")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "text_cache_tables.json")
 
 
 def _lines():
-    subprocess.check_call(["make", "-C", CSRC, "../host/text_cache_selftest"], stdout=subprocess.DEVNULL)
-    run = subprocess.run([os.path.join(ROOT, "font-renderer_amd", "host", "text_cache_selftest")], capture_output=True, text=True)
-    assert run.returncode == 0, run.stderr          # a property failed: stderr names the case and the property
-    return dict(line.split(" ", 1) for line in run.stdout.splitlines())
+    return host_selftest.named("text_cache_selftest")
 
 
 def test_text_cache_tables_match_golden():

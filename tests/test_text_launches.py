@@ -7,18 +7,15 @@ text units' device code as they stood before the launch list carried the instanc
 argument list: the names rocprofv3 shows."""
 import json
 import os
-import subprocess
+
+import host_selftest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "font-renderer_amd", "csrc")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 
 def _lines():
-    subprocess.check_call(["make", "-C", CSRC, "../host/text_plan_selftest"], stdout=subprocess.DEVNULL)
-    run = subprocess.run([os.path.join(ROOT, "font-renderer_amd", "host", "text_plan_selftest"), "launches"], capture_output=True, text=True)
-    assert run.returncode == 0, run.stderr          # a property failed: stderr names the case and the property
-    return dict(line.split(" ", 1) for line in run.stdout.splitlines())
+    return host_selftest.named("text_plan_selftest", "launches")
 
 
 def _golden(name):

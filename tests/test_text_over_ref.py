@@ -4,13 +4,13 @@ own expectations (tests/text_over_cases.py), the blend = 2 lines of host/text_pl
 for every (c, a)."""
 import os
 import re
-import subprocess
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
 import font_renderer_amd as fr
+import host_selftest
 import text_block_cases as B
 import text_over_cases as OC
 import text_twin as tw
@@ -18,7 +18,6 @@ from font_renderer_amd import _lib
 from fixtures import load_font
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "font-renderer_amd", "csrc")
 
 
 def test_flag_in_the_mirrors_of_the_header():
@@ -144,16 +143,9 @@ def test_partial_cover_case_is_what_it_says(n, srgb):
     assert len(np.unique(case.want[..., 3])) > 32
 
 
-def _selftest_over():
-    subprocess.check_call(["make", "-C", CSRC, "../host/text_plan_selftest"], stdout=subprocess.DEVNULL)
-    run = subprocess.run([os.path.join(ROOT, "font-renderer_amd", "host", "text_plan_selftest"), "over"], capture_output=True, text=True)
-    assert run.returncode == 0, run.stderr          # a property failed: stderr names the case and the property
-    return dict(line.split(" ", 1) for line in run.stdout.splitlines())
-
-
 def test_selftest_blend_lines():
     """host/text_plan_selftest over: FR_TEXT_OVER changes no table, and blend is 2 for translucent colours, 0 for opaque"""
-    got = _selftest_over()
+    got = host_selftest.named("text_plan_selftest", "over")
     assert len(got) == 36
     field = {k: re.fullmatch(r"([0-9a-f]{16}) insts (\d+) blend ([012])", v).groups() for k, v in got.items()}
     for name, translucent in (("translucent", True), ("opaque", False), ("alpha_zero_srgb_bgra", True), ("load_srgb", True),

@@ -6,18 +6,15 @@ tests/golden/text_plan_tables.json holds those lines as minted from the builder'
 import json
 import os
 import re
-import subprocess
+
+import host_selftest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "font-renderer_amd", "csrc")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "text_plan_tables.json")
 
 
 def test_text_plan_tables_match_golden():
-    subprocess.check_call(["make", "-C", CSRC, "../host/text_plan_selftest"], stdout=subprocess.DEVNULL)
-    run = subprocess.run([os.path.join(ROOT, "font-renderer_amd", "host", "text_plan_selftest")], capture_output=True, text=True)
-    assert run.returncode == 0, run.stderr          # a property failed: stderr names the case and the property
-    got = dict(line.split(" ", 1) for line in run.stdout.splitlines())
+    got = host_selftest.named("text_plan_selftest")
     with open(GOLDEN) as f:
         want = json.load(f)
     assert list(got) == list(want), "the cases differ from the golden file's"
