@@ -13,14 +13,16 @@ from ._lib import (  # noqa: F401
     FR_LAYER_SRGB, FR_TEXT_BGRA, FR_TEXT_CACHE, FR_TEXT_LOAD, FR_TEXT_OVER, FR_TEXT_SRGB, FR_WINDING_I16, FrError, GlyphPlace, GlyphPlaceAffine, GlyphPlaceEx,
     FontLine, Job, LayerBlit, LayerRect, LayerShadowParams, TextRun, lib_path, load_library,
 )
+from .device import Context  # noqa: F401
+from .layer import layer_over, layer_rects, layer_shadow, layer_unpremultiply, make_blits, make_rects  # noqa: F401
 from .render_glyph import (  # noqa: F401
-    Context, GlyphInfo, Plan, TextPlan, TextPlanRGBA, DeviceGlyphSet, layer_over, layer_rects, layer_shadow, layer_unpremultiply, make_blits, make_rects, make_places, make_places_affine,
-    make_places_ex, make_runs, renderGlyph, render_glyph_dims,
+    GlyphInfo, Plan, TextPlan, TextPlanRGBA, DeviceGlyphSet, make_places, make_places_affine, make_places_ex, make_runs, renderGlyph,
+    render_glyph_dims,
     windingInGlyph, winding_lattice, exact_lattice, exact_coverage, glyph_debug_render, build_id, srgb_to_linear16,
     linear16_to_srgb,
 )
 from .font import Font  # noqa: F401
 from .text import (  # noqa: F401
-    decoration_rects, draw_text_rgba, instance_cell, instance_cell_affine, instance_cell_ex, render_spans, render_spans_rgba, render_text,
+    decoration_rects, draw_text_rgba, instance_cell, instance_cell_affine, instance_cell_ex, placed_line, render_spans, render_spans_rgba, render_text,
     render_text_rgba, render_text_rgba_rotated, render_text_rotated, render_text_view, rotated_line, span_line, view_line,
 )

@@ -11,18 +11,17 @@ from typing import Iterable, List, Optional
 import numpy as np
 
 from . import _lib as L
+from .device import Handle
 from .glyph import Box, Contour, FontInformation, Glyph, GlyphSet
 
 FR_FONT_ALLOW_HINTED = 1
 
 
-class Font:
+class Font(Handle):
     def __init__(self, data: bytes, allow_hinted: bool = False):
         self._lib = L.load_library()
-        h = C.c_void_p()
         buf = (C.c_ubyte * len(data)).from_buffer_copy(data)
-        L.check(self._lib.fr_font_open(buf, len(data), FR_FONT_ALLOW_HINTED if allow_hinted else 0, C.byref(h)))
-        self._h = h
+        self._open(self._lib.fr_font_close, self._lib.fr_font_open, buf, len(data), FR_FONT_ALLOW_HINTED if allow_hinted else 0)
         upm, ng, y0 = C.c_uint16(), C.c_uint16(), C.c_int()
         L.check(self._lib.fr_font_info(self._h, C.byref(upm), C.byref(ng), C.byref(y0)))
         self.information = FontInformation(upm.value, bool(y0.value))
@@ -96,14 +95,3 @@ class Font:
                 if not skip_unsupported:
                     raise
         return GlyphSet(glyphs), kept
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.fr_font_close(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

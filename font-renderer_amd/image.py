@@ -2,9 +2,41 @@
 Row-major `data[y*width + x]`; getRGBLinear reproduces the reference's colour maps."""
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 
 import numpy as np
+
+from . import _lib as L
+from .device import default_context, round_trip
+from .glyph import GlyphSet
+from .layer import layer_over, layer_rects, layer_shadow, layer_unpremultiply, make_blits, make_rects
+
+
+def q64(v) -> int:
+    """a pixel coordinate kept to 1/64 pixel, half up"""
+    return math.floor(64.0 * float(v) + 0.5)
+
+
+def colour_rgba(c, alpha_optional: bool = True) -> tuple:
+    """an (R, G, B, A) colour, or (R, G, B) where the alpha is optional -> (R, G, B, A), A = 255 when omitted"""
+    c = tuple(int(v) for v in c)
+    if alpha_optional and len(c) == 3:
+        c += (255,)
+    if len(c) != 4 or not all(0 <= v <= 255 for v in c):
+        raise ValueError(f"colour {c}: expected {'3 or 4' if alpha_optional else '4'} values in [0, 255]")
+    return c
+
+
+def rgba_pixels(image, what: str, sized: bool = True) -> np.ndarray:
+    """the pixels of an RGBA image as a C-contiguous array; ValueError unless image.data is an (n, 4) uint8 array, with
+    n = width * height when `sized`.  what: the caller's name for the image, for the message."""
+    d, n = image.data, image.width * image.height
+    if (not isinstance(d, np.ndarray) or d.dtype != np.uint8 or d.ndim != 2 or d.shape[1] != 4 or (sized and d.shape[0] != n)):
+        raise ValueError(f"{what}: data must be a ({n if sized else 'n'}, 4) uint8 array"
+                         + (f" for {image.width} x {image.height} pixels" if sized else "")
+                         + f", got {getattr(d, 'shape', None)} {getattr(d, 'dtype', type(d).__name__)}")
+    return np.ascontiguousarray(d)
 
 
 @dataclass
@@ -96,22 +128,10 @@ class RGBA:                     # an RGBA text plan's image (fr_text_plan_create
         alpha, which the RGBA QOI writer and image files expect.  srgb: the image was rendered with srgb=True, so the
         division is in linear light.  A pixel of alpha 0 becomes (0, 0, 0, 0); one of alpha 255 is unchanged.  Returns self.
         device: the same bytes through fr_layer_unpremultiply on the GPU (the image is uploaded and copied back)."""
-        from . import _lib as L
-        if not isinstance(self.data, np.ndarray) or self.data.dtype != np.uint8 or self.data.ndim != 2 or self.data.shape[1] != 4:
-            raise ValueError("RGBA.unpremultiply: data must be an (n, 4) uint8 array")
-        buf = np.ascontiguousarray(self.data)
+        buf = rgba_pixels(self, "RGBA.unpremultiply", sized=device)
         if device:
-            import torch
-
-            from . import render_glyph as rg
-            if buf.shape[0] != self.width * self.height:
-                raise ValueError(f"RGBA.unpremultiply: {buf.shape[0]} pixels for {self.width} x {self.height}")
-            ctx = ctx or rg.default_context()
-            dev = torch.from_numpy(buf).to(f"cuda:{ctx.device}")
-            torch.cuda.synchronize(ctx.device)
-            rg.layer_unpremultiply(ctx, dev.data_ptr(), self.width, self.width, self.height, srgb)
-            ctx.sync()
-            self.data[:] = dev.cpu().numpy()
+            ctx = ctx or default_context()
+            self.data[:] = round_trip(ctx, lambda p: layer_unpremultiply(ctx, p, self.width, self.width, self.height, srgb), buf)
             return self
         L.check(L.load_library().fr_rgba_unpremultiply(L.ptr(buf), buf.shape[0], 1 if srgb else 0))
         if buf is not self.data:
@@ -123,24 +143,15 @@ class RGBA:                     # an RGBA text plan's image (fr_text_plan_create
         composited over this premultiplied image with its top-left pixel at (x, y), whole pixels, clipped at the image's
         edges, at `opacity` in 0 .. 255.  srgb: both images are premultiplied in linear light (rendered with srgb=True).
         Both images are uploaded, composited on the device and this one copied back, as draw_text_rgba does.  Returns self."""
-        import torch
-
-        from . import render_glyph as rg
-        for im, what in ((self, "image"), (layer, "layer")):
-            if (not isinstance(im.data, np.ndarray) or im.data.dtype != np.uint8 or im.data.shape != (im.width * im.height, 4)):
-                raise ValueError(f"RGBA.over: {what}.data must be a ({im.width * im.height}, 4) uint8 array")
+        dst, src = rgba_pixels(self, "RGBA.over: image"), rgba_pixels(layer, "RGBA.over: layer")
         if not 0 <= int(opacity) <= 255:
             raise ValueError(f"opacity {opacity!r}: expected 0 .. 255")
         if self.width == 0 or self.height == 0 or layer.width == 0 or layer.height == 0:
             return self
-        ctx = ctx or rg.default_context()
-        dst = torch.from_numpy(np.ascontiguousarray(self.data)).to(f"cuda:{ctx.device}")
-        src = torch.from_numpy(np.ascontiguousarray(layer.data)).to(f"cuda:{ctx.device}")
-        torch.cuda.synchronize(ctx.device)
-        blits = rg.make_blits([(0, 0, layer.width, layer.height, int(x), int(y), int(opacity))])
-        rg.layer_over(ctx, src.data_ptr(), layer.width, layer.height, dst.data_ptr(), self.width, self.height, blits, srgb)
-        ctx.sync()
-        self.data[:] = dst.cpu().numpy()
+        ctx = ctx or default_context()
+        blits = make_blits([(0, 0, layer.width, layer.height, int(x), int(y), int(opacity))])
+        self.data[:] = round_trip(ctx, lambda d, s: layer_over(ctx, s, layer.width, layer.height, d, self.width, self.height,
+                                                               blits, srgb), dst, src)
         return self
 
     def fill_rects(self, rects, srgb: bool = False, ctx=None) -> "RGBA":
@@ -148,30 +159,18 @@ class RGBA:                     # an RGBA text plan's image (fr_text_plan_create
         pixel as floor(64 v + 1/2), filled with anti-aliased edges in their straight colours, in order, over this
         premultiplied image.  srgb: the image is premultiplied in linear light.  The image is uploaded, drawn into on the
         device and copied back.  Returns self."""
-        import math
-
-        import torch
-
-        from . import render_glyph as rg
-        if not isinstance(self.data, np.ndarray) or self.data.dtype != np.uint8 or self.data.shape != (self.width * self.height, 4):
-            raise ValueError(f"RGBA.fill_rects: data must be a ({self.width * self.height}, 4) uint8 array")
+        dst = rgba_pixels(self, "RGBA.fill_rects")
         rows = []
         for x0, y0, x1, y1, colour in rects:
-            edges = [math.floor(64.0 * float(v) + 0.5) for v in (x0, y0, x1, y1)]
+            edges = [q64(v) for v in (x0, y0, x1, y1)]
             if not all(-2 ** 31 <= e < 2 ** 31 for e in edges):
                 raise ValueError(f"rectangle {(x0, y0, x1, y1)!r}: an edge beyond int32 in 1/64 pixel")
-            colour = tuple(int(v) for v in colour)
-            if len(colour) != 4 or not all(0 <= v <= 255 for v in colour):
-                raise ValueError(f"colour {colour}: expected 4 values in [0, 255]")
-            rows.append((*edges, colour))
+            rows.append((*edges, colour_rgba(colour, alpha_optional=False)))
         if not rows or self.width == 0 or self.height == 0:
             return self
-        ctx = ctx or rg.default_context()
-        dst = torch.from_numpy(np.ascontiguousarray(self.data)).to(f"cuda:{ctx.device}")
-        torch.cuda.synchronize(ctx.device)
-        rg.layer_rects(ctx, dst.data_ptr(), self.width, self.height, rg.make_rects(rows), srgb)
-        ctx.sync()
-        self.data[:] = dst.cpu().numpy()
+        ctx = ctx or default_context()
+        table = make_rects(rows)
+        self.data[:] = round_trip(ctx, lambda d: layer_rects(ctx, d, self.width, self.height, table, srgb), dst)
         return self
 
     def shadow(self, offset=(0, 0), spread: int = 0, blur_radius: int = 0, blur_passes: int = 0, rgba=(0, 0, 0, 255),
@@ -180,11 +179,7 @@ class RGBA:                     # an RGBA text plan's image (fr_text_plan_create
         (default: the reach spread + blur_passes * blur_radius, which holds the whole shadow at offset (0, 0)); pixel
         (pad, pad) of the result lies under pixel (0, 0) of this layer moved by `offset`.  Composite it with over(...,
         x - pad, y - pad), then this layer at (x, y).  The layer is uploaded and the shadow copied back."""
-        import torch
-
-        from . import render_glyph as rg
-        if not isinstance(self.data, np.ndarray) or self.data.dtype != np.uint8 or self.data.shape != (self.width * self.height, 4):
-            raise ValueError(f"RGBA.shadow: data must be a ({self.width * self.height}, 4) uint8 array")
+        src = rgba_pixels(self, "RGBA.shadow").reshape(-1)
         reach = int(spread) + (int(blur_passes) * int(blur_radius) if blur_radius and blur_passes else 0)
         pad = reach if pad is None else int(pad)
         if pad < 0:
@@ -192,17 +187,12 @@ class RGBA:                     # an RGBA text plan's image (fr_text_plan_create
         out = RGBA.init(self.width + 2 * pad, self.height + 2 * pad)
         if out.width == 0 or out.height == 0:
             return out
-        ctx = ctx or rg.default_context()
-        src = torch.from_numpy(np.ascontiguousarray(self.data).reshape(-1)).to(f"cuda:{ctx.device}")
-        if src.numel() == 0:
-            src = torch.zeros(4, dtype=torch.uint8, device=f"cuda:{ctx.device}")
-        dst = torch.empty((out.width * out.height, 4), dtype=torch.uint8, device=f"cuda:{ctx.device}")
-        torch.cuda.synchronize(ctx.device)
-        rg.layer_shadow(ctx, src.data_ptr(), self.width, self.height, dst.data_ptr(), out.width, out.height,
-                        (0, 0, self.width, self.height), (0, 0, out.width, out.height), (int(offset[0]) + pad, int(offset[1]) + pad),
-                        spread, blur_radius, blur_passes, rgba, srgb)
-        ctx.sync()
-        out.data[:] = dst.cpu().numpy()
+        ctx = ctx or default_context()
+        if src.size == 0:
+            src = np.zeros(4, np.uint8)                     # an empty layer still needs an address
+        out.data[:] = round_trip(ctx, lambda s, d: layer_shadow(
+            ctx, s, self.width, self.height, d, out.width, out.height, (0, 0, self.width, self.height), (0, 0, out.width, out.height),
+            (int(offset[0]) + pad, int(offset[1]) + pad), spread, blur_radius, blur_passes, rgba, srgb), src, out.data.shape, back=1)
         return out
 
     def getWidth(self) -> int:
@@ -227,5 +217,11 @@ class GlyphDebug:               # Image.zig:173-241
 
     @staticmethod
     def render(glyph, winding_scale: int, *, ctx=None) -> "GlyphDebug":       # Image.zig:220
-        from . import render_glyph as rg
-        return GlyphDebug(rg.glyph_debug_render(glyph, winding_scale, ctx=ctx), winding_scale)
+        ctx = ctx or default_context()
+        gs = GlyphSet([glyph])
+        box = glyph.box.as_array()
+        W, H = int(box[2]) - int(box[0]) + 3, int(box[3]) - int(box[1]) + 3
+        out = np.zeros((H * W, 3), np.uint8)
+        L.check(ctx._lib.fr_glyph_debug_render(ctx._h, L.ptr(gs.points_xy), L.ptr(gs.contour_start), len(gs.contour_start) - 1,
+                                               L.ptr(box), winding_scale, L.ptr(out)))
+        return GlyphDebug(RGB(W, H, out), winding_scale)

@@ -1,0 +1,76 @@
+"""The layer calls of the C ABI (fr_layer_*, include/fr_raster.h) on device addresses, and the builders of their tables.
+All of them are asynchronous on the context's stream; RGBA.over / fill_rects / shadow / unpremultiply (image.py) wrap them
+for host images."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Sequence
+
+import numpy as np
+
+from . import _lib as L
+from .device import Context
+
+BLIT_DTYPE = np.dtype(L.LayerBlit)
+RECT_DTYPE = np.dtype(L.LayerRect)
+
+
+def make_blits(rows: Sequence) -> np.ndarray:
+    """rows of (src_x, src_y, w, h, dst_x, dst_y, opacity) -> fr_layer_blit array"""
+    return np.array([tuple(r) for r in rows], BLIT_DTYPE)
+
+
+def make_rects(rows: Sequence) -> np.ndarray:
+    """rows of (x0, y0, x1, y1, (R, G, B, A)), the edges in 1/64 pixel -> fr_layer_rect array"""
+    return np.array([(int(r[0]), int(r[1]), int(r[2]), int(r[3]), tuple(int(v) for v in r[4])) for r in rows], RECT_DTYPE)
+
+
+def _table(rows, dtype):
+    """an optional table -> (C-contiguous array or None, row count)"""
+    return (None, 0) if rows is None else (np.ascontiguousarray(rows, dtype), len(rows))
+
+
+def _flags(flags: int, srgb: bool) -> int:
+    return flags | (L.FR_LAYER_SRGB if srgb else 0)
+
+
+def layer_over(ctx: Context, src_ptr: int, src_stride_px: int, src_rows: int, dst_ptr: int, dst_stride_px: int, dst_rows: int,
+               blits, srgb: bool = False, flags: int = 0) -> None:
+    """fr_layer_over: rectangles of the premultiplied layer at device address src_ptr composited over the premultiplied
+    image at dst_ptr (both 4 bytes per pixel, alpha last; strides and rows in pixels), asynchronous on the context's
+    stream.  blits: an fr_layer_blit array (make_blits) or None.  srgb: FR_LAYER_SRGB, composite in linear light."""
+    b, n = _table(blits, BLIT_DTYPE)
+    L.check(ctx._lib.fr_layer_over(ctx._h, C.c_void_p(src_ptr), src_stride_px, src_rows, C.c_void_p(dst_ptr), dst_stride_px,
+                                   dst_rows, None if b is None else L.ptr(b), n, _flags(flags, srgb)))
+
+
+def layer_rects(ctx: Context, dst_ptr: int, dst_stride_px: int, dst_rows: int, rects, srgb: bool = False, flags: int = 0) -> None:
+    """fr_layer_rects: anti-aliased rectangles, each in one straight colour, composited in order over the premultiplied
+    image at device address dst_ptr (4 bytes per pixel, alpha last; stride and rows in pixels), asynchronous on the
+    context's stream.  rects: an fr_layer_rect array (make_rects) or None.  srgb: FR_LAYER_SRGB, composite in linear light."""
+    r, n = _table(rects, RECT_DTYPE)
+    L.check(ctx._lib.fr_layer_rects(ctx._h, C.c_void_p(dst_ptr), dst_stride_px, dst_rows, None if r is None else L.ptr(r), n,
+                                    _flags(flags, srgb)))
+
+
+def layer_unpremultiply(ctx: Context, ptr: int, stride_px: int, w: int, h: int, srgb: bool = False) -> None:
+    """fr_layer_unpremultiply: the w x h window at device address ptr of an image with rows of stride_px pixels from
+    premultiplied to straight alpha, in place, asynchronous on the context's stream"""
+    L.check(ctx._lib.fr_layer_unpremultiply(ctx._h, C.c_void_p(ptr), stride_px, w, h, 1 if srgb else 0))
+
+
+def layer_shadow(ctx: Context, src_ptr: int, src_stride_px: int, src_rows: int, dst_ptr: int, dst_stride_px: int, dst_rows: int,
+                 window, rect, offset=(0, 0), spread: int = 0, blur_radius: int = 0, blur_passes: int = 0,
+                 rgba=(0, 0, 0, 255), srgb: bool = False, flags: int = 0) -> None:
+    """fr_layer_shadow: the alpha of the window (src_x, src_y, w, h) of the premultiplied layer at device address src_ptr,
+    spread by a square maximum of radius `spread`, blurred by `blur_passes` box passes of radius `blur_radius`, moved by
+    offset = (dx, dy) whole pixels and tinted with the straight colour rgba, written as a premultiplied R G B A layer over
+    every pixel of rect = (dst_x, dst_y, dst_w, dst_h) of the image at dst_ptr (strides and rows in pixels); asynchronous
+    on the context's stream.  srgb: FR_LAYER_SRGB, the colour bytes as an srgb=True render writes them.  window or rect
+    None passes a NULL parameter block (refused)."""
+    p = None
+    if window is not None and rect is not None:
+        p = L.LayerShadowParams(*[int(v) for v in window], *[int(v) for v in rect], int(offset[0]), int(offset[1]), int(spread),
+                                int(blur_radius), int(blur_passes), (C.c_uint8 * 4)(*[int(v) for v in rgba]))
+    L.check(ctx._lib.fr_layer_shadow(ctx._h, C.c_void_p(src_ptr), src_stride_px, src_rows, C.c_void_p(dst_ptr), dst_stride_px, dst_rows,
+                                     None if p is None else C.byref(p), _flags(flags, srgb)))

@@ -11,8 +11,13 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib as L
+from .device import Context, Handle, default_context
 from .glyph import FontInformation, Glyph, GlyphSet
-from .image import RGB, Gray, Winding
+from .image import RGB, GlyphDebug, Gray, Winding
+# Kept names, not a second home: the layer calls are defined in layer.py only.  They were public attributes of this
+# module, and code outside this tree's current tests and tools (the suite of the commit before layer.py existed among
+# it) calls render_glyph.layer_* and render_glyph.make_blits / make_rects; dropping the names breaks those callers.
+from .layer import BLIT_DTYPE, RECT_DTYPE, layer_over, layer_rects, layer_shadow, layer_unpremultiply, make_blits, make_rects  # noqa: F401
 
 
 def _flat(glyph: Glyph):
@@ -20,60 +25,13 @@ def _flat(glyph: Glyph):
     return gs.points_xy, gs.contour_start, len(gs.contour_start) - 1
 
 
-class Context:
-    """fr_ctx.  stream: a hipStream_t handle (int) to launch on, e.g.
-    torch.cuda.current_stream().cuda_stream, or None for a private stream."""
-
-    def __init__(self, device: int = 0, stream: Optional[int] = None):
-        self._lib = L.load_library()
-        h = C.c_void_p()
-        L.check(self._lib.fr_ctx_create(device, C.c_void_p(stream) if stream else None, C.byref(h)))
-        self._h = h
-        self.device = device
-
-    def set_option(self, key: str, value: int) -> None:
-        L.check(self._lib.fr_ctx_set_option(self._h, key.encode(), value))
-
-    def sync(self) -> None:
-        L.check(self._lib.fr_ctx_sync(self._h))
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.fr_ctx_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-_default_ctx: Optional[Context] = None
-
-
-def default_context() -> Context:
-    global _default_ctx
-    if _default_ctx is None:
-        _default_ctx = Context(0)
-    return _default_ctx
-
-
-class DeviceGlyphSet:
+class DeviceGlyphSet(Handle):
     """fr_glyphset: points in HBM + root records (precompute kernel run at creation)."""
 
     def __init__(self, ctx: Context, gs: GlyphSet):
         self.ctx, self.host = ctx, gs
-        h = C.c_void_p()
-        L.check(ctx._lib.fr_glyphset_create(ctx._h, L.ptr(gs.points_xy), L.ptr(gs.contour_start), gs.n_contours,
-                                            L.ptr(gs.glyph_start), len(gs), C.byref(h)))
-        self._h = h
+        self._open(ctx._lib.fr_glyphset_destroy, ctx._lib.fr_glyphset_create, ctx._h, L.ptr(gs.points_xy),
+                   L.ptr(gs.contour_start), gs.n_contours, L.ptr(gs.glyph_start), len(gs))
         boxes = np.ascontiguousarray(gs.boxes, np.int16)               # Glyph.box: what text plans size their cells from
         L.check(ctx._lib.fr_glyphset_set_boxes(self._h, L.ptr(boxes)))
 
@@ -96,42 +54,39 @@ class DeviceGlyphSet:
                                                    C.byref(pairs), C.byref(bad), first))
         return pairs.value, bad.value, tuple(first)
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self.ctx._lib.fr_glyphset_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+# the tables of the C ABI as numpy sees them: derived from the ctypes structures of _lib, which mirror include/fr_raster.h
+JOB_DTYPE = np.dtype(L.Job)
+PLACE_DTYPE = np.dtype(L.GlyphPlace)
+PLACE_EX_DTYPE = np.dtype(L.GlyphPlaceEx)
+PLACE_AFFINE_DTYPE = np.dtype(L.GlyphPlaceAffine)
+RUN_DTYPE = np.dtype(L.TextRun)
 
 
 def make_jobs(rows: Sequence) -> np.ndarray:
     """rows of (glyph, min_x, max_y, w, h, out_x, out_y, scale) -> fr_job array"""
-    dt = np.dtype([("glyph", "<u4"), ("min_x", "<i4"), ("max_y", "<i4"), ("w", "<u4"), ("h", "<u4"),
-                   ("out_x", "<u4"), ("out_y", "<u4"), ("scale", "<f4")])
-    a = np.zeros(len(rows), dt)
+    a = np.zeros(len(rows), JOB_DTYPE)
     for i, r in enumerate(rows):
         a[i] = tuple(r)
     return a
 
 
-class Plan:
+class Plan(Handle):
     """fr_plan: a job table resident on the device.  flags: FR_FILL_CONSISTENT or 0 (the reference's crossing rule)."""
 
     def __init__(self, dgs: DeviceGlyphSet, jobs: np.ndarray, mode: int, samples_per_axis: int = 1,
                  sample_phase: int = L.FR_SAMPLE_CORNER, flags: int = 0):
         assert jobs.dtype.itemsize == 32
+        jobs = np.ascontiguousarray(jobs)
+        self._create(dgs, mode, samples_per_axis, sample_phase, flags, "fr_plan_create_ex", L.ptr(jobs), len(jobs))
+        self.n_jobs = len(jobs)
+
+    def _create(self, dgs: DeviceGlyphSet, mode: int, samples_per_axis: int, sample_phase: int, flags: int, entry: str, *table):
+        """what every plan is made by: entry(ctx, glyph set, *table, &params, flags, &plan)"""
         self.ctx, self.dgs, self.mode = dgs.ctx, dgs, mode
         self.params = L.RasterParams(mode, samples_per_axis, sample_phase, 0)
-        jobs = np.ascontiguousarray(jobs)
-        h = C.c_void_p()
-        L.check(self.ctx._lib.fr_plan_create_ex(self.ctx._h, dgs._h, L.ptr(jobs), len(jobs), C.byref(self.params), flags,
-                                                C.byref(h)))
-        self._h = h
-        self.n_jobs = len(jobs)
+        lib = self.ctx._lib
+        self._open(lib.fr_plan_destroy, getattr(lib, entry), self.ctx._h, dgs._h, *table, C.byref(self.params), flags)
 
     @property
     def pixels(self) -> int:
@@ -157,24 +112,6 @@ class Plan:
         ms = C.c_float()
         L.check(self.ctx._lib.fr_plan_render_timed(self._h, C.c_void_p(out_dev_ptr), out_stride, out_rows, C.byref(ms)))
         return ms.value
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self.ctx._lib.fr_plan_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-PLACE_DTYPE = np.dtype([("glyph", "<u4"), ("pen_x64", "<i4"), ("pen_y", "<i4")])
-PLACE_EX_DTYPE = np.dtype([("glyph", "<u4"), ("pen_x64", "<i4"), ("pen_y64", "<i4"), ("scale", "<f4"), ("slant", "<f4")])
-PLACE_AFFINE_DTYPE = np.dtype([("glyph", "<u4"), ("pen_x64", "<i4"), ("pen_y64", "<i4"), ("m", "<f4", (4,))])
-RUN_DTYPE = np.dtype([("first", "<u4"), ("count", "<u4"), ("w", "<u4"), ("h", "<u4"), ("out_x", "<u4"), ("out_y", "<u4"),
-                      ("scale", "<f4")])
 
 
 def make_places(rows: Sequence) -> np.ndarray:
@@ -220,12 +157,8 @@ class TextPlan(Plan):
                  samples_per_axis: int = 4, sample_phase: int = L.FR_SAMPLE_CENTER, flags: int = 0):
         places, ex = _places(places)
         runs = np.ascontiguousarray(runs, RUN_DTYPE)
-        self.ctx, self.dgs, self.mode = dgs.ctx, dgs, mode
-        self.params = L.RasterParams(mode, samples_per_axis, sample_phase, 0)
-        h = C.c_void_p()
-        create = getattr(self.ctx._lib, "fr_text_plan_create" + ex)
-        L.check(create(self.ctx._h, dgs._h, L.ptr(places), len(places), L.ptr(runs), len(runs), C.byref(self.params), flags, C.byref(h)))
-        self._h = h
+        self._create(dgs, mode, samples_per_axis, sample_phase, flags, "fr_text_plan_create" + ex,
+                     L.ptr(places), len(places), L.ptr(runs), len(runs))
         self.n_places, self.n_runs = len(places), len(runs)
 
 
@@ -251,75 +184,9 @@ class TextPlanRGBA(Plan):
         runs = np.ascontiguousarray(runs, RUN_DTYPE)
         pc = _colors(place_rgba, len(places), "place_rgba")
         rc = None if run_clear_rgba is None else _colors(run_clear_rgba, len(runs), "run_clear_rgba")     # (None: NULL)
-        self.ctx, self.dgs, self.mode = dgs.ctx, dgs, L.FR_COVERAGE_U8
-        self.params = L.RasterParams(L.FR_COVERAGE_U8, samples_per_axis, sample_phase, 0)
-        h = C.c_void_p()
-        create = getattr(self.ctx._lib, "fr_text_plan_create_rgba" + ex)
-        L.check(create(self.ctx._h, dgs._h, L.ptr(places), L.ptr(pc), len(places), L.ptr(runs), None if rc is None else L.ptr(rc),
-                       len(runs), C.byref(self.params), flags, C.byref(h)))
-        self._h = h
+        self._create(dgs, L.FR_COVERAGE_U8, samples_per_axis, sample_phase, flags, "fr_text_plan_create_rgba" + ex,
+                     L.ptr(places), L.ptr(pc), len(places), L.ptr(runs), None if rc is None else L.ptr(rc), len(runs))
         self.n_places, self.n_runs = len(places), len(runs)
-
-
-BLIT_DTYPE = np.dtype([("src_x", "<u4"), ("src_y", "<u4"), ("w", "<u4"), ("h", "<u4"), ("dst_x", "<i4"), ("dst_y", "<i4"),
-                       ("opacity", "<u4")])
-
-
-def make_blits(rows: Sequence) -> np.ndarray:
-    """rows of (src_x, src_y, w, h, dst_x, dst_y, opacity) -> fr_layer_blit array"""
-    return np.array([tuple(r) for r in rows], BLIT_DTYPE)
-
-
-def layer_over(ctx: Context, src_ptr: int, src_stride_px: int, src_rows: int, dst_ptr: int, dst_stride_px: int, dst_rows: int,
-               blits, srgb: bool = False, flags: int = 0) -> None:
-    """fr_layer_over: rectangles of the premultiplied layer at device address src_ptr composited over the premultiplied
-    image at dst_ptr (both 4 bytes per pixel, alpha last; strides and rows in pixels), asynchronous on the context's
-    stream.  blits: an fr_layer_blit array (make_blits) or None.  srgb: FR_LAYER_SRGB, composite in linear light."""
-    n = 0 if blits is None else len(blits)
-    b = None if blits is None else np.ascontiguousarray(blits, BLIT_DTYPE)
-    L.check(ctx._lib.fr_layer_over(ctx._h, C.c_void_p(src_ptr), src_stride_px, src_rows, C.c_void_p(dst_ptr), dst_stride_px,
-                                   dst_rows, None if b is None else L.ptr(b), n, flags | (L.FR_LAYER_SRGB if srgb else 0)))
-
-
-RECT_DTYPE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("rgba", "u1", (4,))])
-
-
-def make_rects(rows: Sequence) -> np.ndarray:
-    """rows of (x0, y0, x1, y1, (R, G, B, A)), the edges in 1/64 pixel -> fr_layer_rect array"""
-    return np.array([(int(r[0]), int(r[1]), int(r[2]), int(r[3]), tuple(int(v) for v in r[4])) for r in rows], RECT_DTYPE)
-
-
-def layer_rects(ctx: Context, dst_ptr: int, dst_stride_px: int, dst_rows: int, rects, srgb: bool = False, flags: int = 0) -> None:
-    """fr_layer_rects: anti-aliased rectangles, each in one straight colour, composited in order over the premultiplied
-    image at device address dst_ptr (4 bytes per pixel, alpha last; stride and rows in pixels), asynchronous on the
-    context's stream.  rects: an fr_layer_rect array (make_rects) or None.  srgb: FR_LAYER_SRGB, composite in linear light."""
-    n = 0 if rects is None else len(rects)
-    r = None if rects is None else np.ascontiguousarray(rects, RECT_DTYPE)
-    L.check(ctx._lib.fr_layer_rects(ctx._h, C.c_void_p(dst_ptr), dst_stride_px, dst_rows, None if r is None else L.ptr(r), n,
-                                    flags | (L.FR_LAYER_SRGB if srgb else 0)))
-
-
-def layer_unpremultiply(ctx: Context, ptr: int, stride_px: int, w: int, h: int, srgb: bool = False) -> None:
-    """fr_layer_unpremultiply: the w x h window at device address ptr of an image with rows of stride_px pixels from
-    premultiplied to straight alpha, in place, asynchronous on the context's stream"""
-    L.check(ctx._lib.fr_layer_unpremultiply(ctx._h, C.c_void_p(ptr), stride_px, w, h, 1 if srgb else 0))
-
-
-def layer_shadow(ctx: Context, src_ptr: int, src_stride_px: int, src_rows: int, dst_ptr: int, dst_stride_px: int, dst_rows: int,
-                 window, rect, offset=(0, 0), spread: int = 0, blur_radius: int = 0, blur_passes: int = 0,
-                 rgba=(0, 0, 0, 255), srgb: bool = False, flags: int = 0) -> None:
-    """fr_layer_shadow: the alpha of the window (src_x, src_y, w, h) of the premultiplied layer at device address src_ptr,
-    spread by a square maximum of radius `spread`, blurred by `blur_passes` box passes of radius `blur_radius`, moved by
-    offset = (dx, dy) whole pixels and tinted with the straight colour rgba, written as a premultiplied R G B A layer over
-    every pixel of rect = (dst_x, dst_y, dst_w, dst_h) of the image at dst_ptr (strides and rows in pixels); asynchronous
-    on the context's stream.  srgb: FR_LAYER_SRGB, the colour bytes as an srgb=True render writes them.  window or rect
-    None passes a NULL parameter block (refused)."""
-    p = None
-    if window is not None and rect is not None:
-        p = L.LayerShadowParams(*[int(v) for v in window], *[int(v) for v in rect], int(offset[0]), int(offset[1]), int(spread),
-                                int(blur_radius), int(blur_passes), (C.c_uint8 * 4)(*[int(v) for v in rgba]))
-    L.check(ctx._lib.fr_layer_shadow(ctx._h, C.c_void_p(src_ptr), src_stride_px, src_rows, C.c_void_p(dst_ptr), dst_stride_px, dst_rows,
-                                     None if p is None else C.byref(p), flags | (L.FR_LAYER_SRGB if srgb else 0)))
 
 
 def render_batch(dgs: DeviceGlyphSet, jobs: np.ndarray, mode: int, out: np.ndarray, samples_per_axis: int = 1,
@@ -459,13 +326,7 @@ def exact_coverage(glyph: Glyph, K: int, x0: int, y0: int, w_px: int, h_px: int,
 def glyph_debug_render(glyph: Glyph, winding_scale: int, *, ctx: Optional[Context] = None) -> RGB:
     """Image.GlyphDebug.render (Image.zig:220-240) through fr_glyph_debug_render: the exact-integer lattice
     coloured by setWindingLinear (:192-200) with the glyph's points marked (:202-218)"""
-    ctx = ctx or default_context()
-    pts, cs, nc = _flat(glyph)
-    box = glyph.box.as_array()
-    W, H = int(box[2]) - int(box[0]) + 3, int(box[3]) - int(box[1]) + 3
-    out = np.zeros((H * W, 3), np.uint8)
-    L.check(ctx._lib.fr_glyph_debug_render(ctx._h, L.ptr(pts), L.ptr(cs), nc, L.ptr(box), winding_scale, L.ptr(out)))
-    return RGB(W, H, out)
+    return GlyphDebug.render(glyph, winding_scale, ctx=ctx).rgb
 
 
 def build_id() -> str:

@@ -8,15 +8,16 @@ and the pen positions."""
 from __future__ import annotations
 
 import math
+from contextlib import closing
 from typing import Optional
 
 import numpy as np
 
 from . import _lib as L
+from .device import Context, default_context, round_trip
 from .font import Font
-from .image import RGBA, Gray
-from .render_glyph import (Context, DeviceGlyphSet, TextPlan, TextPlanRGBA, default_context, make_places, make_places_affine,
-                           make_places_ex, make_runs)
+from .image import RGBA, Gray, colour_rgba, q64, rgba_pixels
+from .render_glyph import DeviceGlyphSet, TextPlan, TextPlanRGBA, make_places, make_places_affine, make_places_ex, make_runs
 
 
 def instance_cell(box, scale: float, pen_x64: int, pen_y: int):
@@ -32,7 +33,8 @@ def instance_cell(box, scale: float, pen_x64: int, pen_y: int):
 
 def instance_cell_ex(box, scale: float, slant: float, pen_x64: int, pen_y64: int):
     """instance_cell for an fr_glyph_place_ex (include/fr_raster.h): the grid of the box sheared by `slant`, one column /
-    row wider when the pen's x / y has a fractional part (binary32, one rounding per operation)"""
+    row wider when the pen's x / y has a fractional part (binary32, one rounding per operation).  At slant 0 and a
+    whole pen_y64 = 64 * pen_y it is instance_cell's (x + 0 * y == x in binary32)."""
     f = np.float32
     s, k = f(scale), f(slant)
     x_min, y_min, x_max, y_max = (f(int(v)) for v in box)
@@ -58,6 +60,8 @@ def instance_cell_affine(box, m, pen_x64: int, pen_y64: int):
             mx_y - mn_y + 1 + ((pen_y64 & 63) != 0))
 
 
+# ---- the small rules, each written once
+
 def _slant(slant) -> float:
     k = float(slant)
     if not math.isfinite(k) or abs(k) > 4.0:
@@ -65,10 +69,64 @@ def _slant(slant) -> float:
     return k
 
 
-def _fit(gs, rows):
+def _zoom(zoom) -> float:
+    zoom = float(zoom)
+    if not (math.isfinite(zoom) and zoom > 0.0):
+        raise ValueError(f"zoom {zoom!r}: expected a finite value > 0")
+    return zoom
+
+
+def _frame(width, height) -> None:
+    """the size of an image that clips a line"""
+    if not (isinstance(width, (int, np.integer)) and isinstance(height, (int, np.integer)) and 0 <= width <= 65535
+            and 0 <= height <= 65535):
+        raise ValueError(f"width {width!r} and height {height!r} must be integers in [0, 65535]")
+
+
+def _flags(flags: int, srgb: bool = False, bgra: bool = False, cache: bool = False, over: bool = False) -> int:
+    """the flag word of a text plan from the keyword arguments of the render functions"""
+    return (flags | (L.FR_TEXT_SRGB if srgb else 0) | (L.FR_TEXT_BGRA if bgra else 0) | (L.FR_TEXT_CACHE if cache else 0)
+            | (L.FR_TEXT_OVER if over else 0))
+
+
+def _per_char(text, color, colors) -> list:
+    """the colour of every character: colors[k], or `color` for all of them"""
+    if colors is None:
+        return [colour_rgba(color)] * len(text)
+    if len(colors) != len(text):
+        raise ValueError(f"colors: {len(colors)} colours for {len(text)} characters")
+    return [colour_rgba(c) for c in colors]
+
+
+def _scale(font: Font, font_size, zoom: float = 1.0) -> np.float32:
+    """f32(f32(font_size) * f32(zoom)) / f32(units_per_em)"""
+    return np.float32(font_size) * np.float32(zoom) / np.float32(font.information.units_per_em)
+
+
+# ---- layout
+
+def _glyphs(font: Font, glyph_indices):
+    """the glyph set of the distinct glyphs of a line -> (glyph set, every entry's index in the set)"""
+    gs, kept = font.glyphset(sorted({int(g) for g in glyph_indices}), skip_unsupported=False)
+    local = {g: k for k, g in enumerate(kept)}
+    return gs, [local[int(g)] for g in glyph_indices]
+
+
+def _layout(font: Font, text, font_size: int, clipped_away: bool = False):
+    """font.layout and the line's glyph set -> (glyph set, glyph k's index in the set, glyph k's pen_x64, end pen), or None
+    for an empty text, and after the layout's own checks for an image that has no pixels (clipped_away)"""
+    gi, pen, end = font.layout(text, font_size)
+    if clipped_away or len(gi) == 0:
+        return None
+    return _glyphs(font, gi) + ([int(p) for p in pen], end)
+
+
+def _fit(gs, rows, upright: bool = False):
     """rows of (local glyph, pen_x64, pen_y64, scale, slant) around the pen origin (0, 0) -> one run whose image is the
-    union of the instance cells, as _line sizes it: (places, runs, width, height), or None when nothing is drawn.  The
-    pens move by whole pixels only."""
+    union of the instance cells: (places, runs, width, height), or None when nothing is drawn.  The pen origin is at the
+    image's left edge, moved right by whole pixels if a cell reaches left of it (the fractional pens stay as laid out),
+    and the baseline at row -top = ceil(max y_max * scale).  upright: the rows have slant 0 and whole pen_y64, and the
+    places are fr_glyph_place rows, which select the text_* kernels, instead of fr_glyph_place_ex rows."""
     seg = gs.segments_per_glyph()
     cells = [instance_cell_ex(gs.boxes[g], s, k, x, y) for g, x, y, s, k in rows if seg[g] > 0]
     if not cells:
@@ -78,35 +136,50 @@ def _fit(gs, rows):
     top = min(c[1] for c in cells)
     width = max(c[0] + c[2] for c in cells) + shift
     height = max(c[1] + c[3] for c in cells) - top
-    places = make_places_ex([(g, x + 64 * shift, y - 64 * top, s, k) for g, x, y, s, k in rows])
+    if upright:
+        places = make_places([(g, x + 64 * shift, (y >> 6) - top) for g, x, y, _, _ in rows])
+    else:
+        places = make_places_ex([(g, x + 64 * shift, y - 64 * top, s, k) for g, x, y, s, k in rows])
     runs = make_runs([(0, len(places), width, height, 0, 0, rows[0][3])])
     return places, runs, width, height
 
 
 def _line(font: Font, text, font_size: int, slant: float = 0.0):
-    """one line laid out as one run: (glyph set, places, runs, width, height), or None when nothing is drawn.  The image
-    is the union of the instance cells: the pen origin at its left edge (moved right by whole pixels if a cell reaches
-    left of it) and the baseline at row ceil(max y_max * scale)."""
-    gi, pen, _ = font.layout(text, font_size)
-    distinct = sorted(set(int(g) for g in gi))
-    gs, kept = font.glyphset(distinct, skip_unsupported=False)
-    local = {g: k for k, g in enumerate(kept)}
-    scale = np.float32(font_size) / np.float32(font.information.units_per_em)
-    if slant != 0.0:                                       # oblique: the placement form, cells of the sheared boxes
-        fit = _fit(gs, [(local[int(g)], int(p), 0, scale, slant) for g, p in zip(gi, pen)])
-        return None if fit is None else (gs,) + fit
-    cells = [instance_cell(gs.boxes[local[int(g)]], scale, int(p), 0) for g, p in zip(gi, pen)
-             if gs.segments_per_glyph()[local[int(g)]] > 0]
-    if not cells:
+    """one line laid out as one run: (glyph set, places, runs, width, height), or None when nothing is drawn; sized by
+    _fit.  An oblique line is in the placement form, cells of the sheared boxes."""
+    laid = _layout(font, text, font_size)
+    if laid is None:
         return None
-    left = min(c[0] for c in cells)
-    shift = -left if left < 0 else 0                       # whole pixels: the fractional pens stay as laid out
-    top = min(c[1] for c in cells)                         # the baseline row is -top = ceil(max y_max * scale)
-    width = max(c[0] + c[2] for c in cells) + shift
-    height = max(c[1] + c[3] for c in cells) - top
-    places = make_places([(local[int(g)], int(p) + 64 * shift, -top) for g, p in zip(gi, pen)])
-    runs = make_runs([(0, len(places), width, height, 0, 0, scale)])
-    return gs, places, runs, width, height
+    gs, local, pens, _ = laid
+    scale = _scale(font, font_size)
+    fit = _fit(gs, [(g, p, 0, scale, slant) for g, p in zip(local, pens)], upright=slant == 0.0)
+    return None if fit is None else (gs,) + fit
+
+
+# ---- rendering
+
+def _render(ctx: Optional[Context], line, width: int, height: int, samples_per_axis: int, phase: int, flags: int,
+            mode: int = L.FR_COVERAGE_U8, colours=None, clear=None, image: Optional[RGBA] = None):
+    """line = (glyph set, places, runs) of any placement form through one plan, rendered once into width x height pixels
+    -> Gray from a TextPlan in `mode`, or with per-placement `colours` RGBA from a TextPlanRGBA: over the colour `clear`, or
+    with `image` over that image's pixels (FR_TEXT_LOAD in flags), which are replaced"""
+    ctx = ctx or default_context()
+    gs, places, runs = line
+    if image is not None:
+        target = image.data                                 # uploaded and drawn over
+    else:
+        target = (height * width,) if colours is None else (height * width, 4)    # a shape: allocated on the device
+    with closing(DeviceGlyphSet(ctx, gs)) as dgs:
+        if colours is None:
+            plan = TextPlan(dgs, places, runs, mode, samples_per_axis, phase, flags)
+        else:
+            plan = TextPlanRGBA(dgs, places, colours, runs, None if clear is None else [clear], samples_per_axis, phase, flags)
+        with closing(plan):
+            out = round_trip(ctx, lambda p: plan.render(p, width, height), target)
+    if image is not None:
+        image.data[:] = out
+        return image
+    return Gray(width, height, out) if colours is None else RGBA(width, height, out)
 
 
 def render_text(font: Font, text, font_size: int, *, samples_per_axis: int = 4, mode: int = L.FR_COVERAGE_U8,
@@ -121,38 +194,7 @@ def render_text(font: Font, text, font_size: int, *, samples_per_axis: int = 4, 
     line = _line(font, text, font_size, _slant(slant))
     if line is None:
         return Gray.init(0, 0)
-    ctx = ctx or default_context()
-    return _render_gray(ctx, *line, mode, samples_per_axis, phase, flags | (L.FR_TEXT_CACHE if cache else 0))
-
-
-def _render_gray(ctx: Context, gs, places, runs, width: int, height: int, mode: int, samples_per_axis: int, phase: int,
-                 flags: int) -> Gray:
-    """one text plan of either placement form, rendered into a width x height image"""
-    import torch
-
-    dgs = DeviceGlyphSet(ctx, gs)
-    plan = TextPlan(dgs, places, runs, mode, samples_per_axis, phase, flags)
-    try:
-        buf = torch.empty((height, width), dtype=torch.uint8, device=f"cuda:{ctx.device}")
-        torch.cuda.synchronize(ctx.device)
-        plan.render(buf.data_ptr(), width, height)
-        ctx.sync()
-        im = Gray.init(width, height)
-        im.data[:] = buf.cpu().numpy().reshape(-1)
-    finally:
-        plan.close()
-        dgs.close()
-    return im
-
-
-def _rgba(c) -> tuple:
-    """an (R, G, B) or (R, G, B, A) colour -> (R, G, B, A), A = 255 when omitted"""
-    c = tuple(int(v) for v in c)
-    if len(c) == 3:
-        c += (255,)
-    if len(c) != 4 or not all(0 <= v <= 255 for v in c):
-        raise ValueError(f"colour {c}: expected 3 or 4 values in [0, 255]")
-    return c
+    return _render(ctx, line[:3], *line[3:], samples_per_axis, phase, _flags(flags, cache=cache), mode)
 
 
 def render_text_rgba(font: Font, text, font_size: int, color=(225, 105, 180, 255), background=(0, 0, 0, 0), colors=None,
@@ -169,37 +211,32 @@ def render_text_rgba(font: Font, text, font_size: int, color=(225, 105, 180, 255
     RGBA.unpremultiply turns it into straight alpha.  R, G and B are those of over=False."""
     slant = _slant(slant)
     ctx = ctx or default_context()
-    flags |= ((L.FR_TEXT_SRGB if srgb else 0) | (L.FR_TEXT_BGRA if bgra else 0) | (L.FR_TEXT_CACHE if cache else 0)
-              | (L.FR_TEXT_OVER if over else 0))
-    n_chars = len(text)
-    if colors is not None and len(colors) != n_chars:
-        raise ValueError(f"colors: {len(colors)} colours for {n_chars} characters")
-    per_char = [_rgba(c) for c in colors] if colors is not None else [_rgba(color)] * n_chars
-    clear = _rgba(background)
+    per_char, clear = _per_char(text, color, colors), colour_rgba(background)
     line = _line(font, text, font_size, slant)
     if line is None:
         return RGBA.init(0, 0)
-    return _render_rgba(ctx, *line, per_char, clear, samples_per_axis, phase, flags)
+    return _render(ctx, line[:3], *line[3:], samples_per_axis, phase, _flags(flags, srgb, bgra, cache, over), colours=per_char,
+                   clear=clear)
 
 
-def _render_rgba(ctx: Context, gs, places, runs, width: int, height: int, per_char, clear, samples_per_axis: int, phase: int,
-                 flags: int) -> RGBA:
-    """one RGBA text plan of either placement form, rendered into a width x height image"""
-    import torch
-
-    dgs = DeviceGlyphSet(ctx, gs)
-    plan = TextPlanRGBA(dgs, places, per_char, runs, [clear], samples_per_axis, phase, flags)
-    try:
-        buf = torch.empty((height, width, 4), dtype=torch.uint8, device=f"cuda:{ctx.device}")
-        torch.cuda.synchronize(ctx.device)
-        plan.render(buf.data_ptr(), width, height)
-        ctx.sync()
-        im = RGBA.init(width, height)
-        im.data[:] = buf.cpu().numpy().reshape(-1, 4)
-    finally:
-        plan.close()
-        dgs.close()
-    return im
+def placed_line(font: Font, text, font_size: int, x: float, y: float, width: int, height: int, slant: float = 0.0):
+    """The line draw_text_rgba draws: laid out at `font_size` with the pen origin at image x and the baseline at image y,
+    both kept to 1/64 pixel (floor(64 v + 1/2)).  -> (glyph set, places, runs): one run of width x height pixels that
+    clips the line, or None for an empty text or image.  The places are fr_glyph_place rows for an upright line on a
+    whole pixel row (slant == 0 and pen_y64 a multiple of 64) and fr_glyph_place_ex rows otherwise."""
+    slant = _slant(slant)
+    if not math.isfinite(float(y)):
+        raise ValueError(f"y {y!r}: expected a finite value")
+    laid = _layout(font, text, font_size, width == 0 or height == 0)
+    if laid is None:
+        return None
+    gs, local, pens, _ = laid
+    x64, y64 = q64(x), q64(y)
+    if slant == 0.0 and y64 % 64 == 0:
+        places = make_places([(g, x64 + p, y64 // 64) for g, p in zip(local, pens)])
+    else:
+        places = make_places_ex([(g, x64 + p, y64, 0.0, slant) for g, p in zip(local, pens)])
+    return gs, places, make_runs([(0, len(places), int(width), int(height), 0, 0, _scale(font, font_size))])
 
 
 def draw_text_rgba(image: RGBA, font: Font, text, font_size: int, x: float, y: float, color=(225, 105, 180, 255), colors=None,
@@ -210,58 +247,29 @@ def draw_text_rgba(image: RGBA, font: Font, text, font_size: int, x: float, y: f
     the glyphs are blended over it per sample in order, in `color` or colors[k] for character k.  x: the pen origin's
     image x in pixels (fractional x is kept to 1/64 pixel: pen_x64 = floor(64 x + 1/2)); y: the baseline's image y, kept
     to 1/64 pixel likewise (pen_y64 = floor(64 y + 1/2); an integral y is that row); slant as render_text.  The
-    line is one run covering the whole image, so glyphs are clipped at its edges.  The whole image is copied to the
+    line is one run covering the whole image (placed_line), so glyphs are clipped at its edges.  The whole image is copied to the
     device and back; on the device only the 64 x 16 tiles that some glyph cell meets are read (and, where needed,
     written), and every pixel no glyph sample reaches comes back with its bytes unchanged.  srgb / bgra as
     render_text_rgba: the image's bytes are sRGB / B G R A; cache as render_text.  image.data must be a (height * width, 4) uint8 array
     (ValueError otherwise).  over: source-over alpha (FR_TEXT_OVER): the image is then read and written as premultiplied
     R G B A, and translucent text leaves the alpha of an opaque picture at 255 (with over=False every covered sample's
     alpha becomes the colour's A).  Returns `image`."""
-    import torch
-
-    w, h, data = image.width, image.height, image.data
+    w, h = image.width, image.height
     if not (isinstance(w, (int, np.integer)) and isinstance(h, (int, np.integer)) and w >= 0 and h >= 0):
         raise ValueError(f"image: width {w!r} and height {h!r} must be non-negative integers")
-    if not isinstance(data, np.ndarray) or data.dtype != np.uint8 or data.shape != (h * w, 4):
-        raise ValueError(f"image.data: expected a ({h * w}, 4) uint8 array for {w} x {h} pixels, got "
-                         f"{getattr(data, 'shape', None)} {getattr(data, 'dtype', type(data).__name__)}")
+    rgba_pixels(image, "draw_text_rgba: image")
     slant = _slant(slant)
     if not math.isfinite(float(y)):
         raise ValueError(f"y {y!r}: expected a finite value")
     ctx = ctx or default_context()
-    flags |= (L.FR_TEXT_LOAD | (L.FR_TEXT_SRGB if srgb else 0) | (L.FR_TEXT_BGRA if bgra else 0) | (L.FR_TEXT_CACHE if cache else 0)
-              | (L.FR_TEXT_OVER if over else 0))
-    n_chars = len(text)
-    if colors is not None and len(colors) != n_chars:
-        raise ValueError(f"colors: {len(colors)} colours for {n_chars} characters")
-    per_char = [_rgba(c) for c in colors] if colors is not None else [_rgba(color)] * n_chars
-    if n_chars == 0 or image.width == 0 or image.height == 0:
+    per_char = _per_char(text, color, colors)
+    if len(text) == 0 or w == 0 or h == 0:
         return image
-    gi, pen, _ = font.layout(text, font_size)
-    gs, kept = font.glyphset(sorted(set(int(g) for g in gi)), skip_unsupported=False)
-    local = {g: k for k, g in enumerate(kept)}
-    scale = np.float32(font_size) / np.float32(font.information.units_per_em)
-    x64 = math.floor(64.0 * float(x) + 0.5)
-    y64 = math.floor(64.0 * float(y) + 0.5)
-    if slant == 0.0 and y64 % 64 == 0:
-        places = make_places([(local[int(g)], x64 + int(p), y64 // 64) for g, p in zip(gi, pen)])
-    else:
-        places = make_places_ex([(local[int(g)], x64 + int(p), y64, 0.0, slant) for g, p in zip(gi, pen)])
-    runs = make_runs([(0, len(places), image.width, image.height, 0, 0, scale)])
-    dgs = DeviceGlyphSet(ctx, gs)
-    try:
-        plan = TextPlanRGBA(dgs, places, per_char, runs, None, samples_per_axis, phase, flags)
-        try:
-            buf = torch.from_numpy(np.ascontiguousarray(image.data)).to(f"cuda:{ctx.device}")
-            torch.cuda.synchronize(ctx.device)
-            plan.render(buf.data_ptr(), image.width, image.height)
-            ctx.sync()
-            image.data[:] = buf.cpu().numpy()
-        finally:
-            plan.close()
-    finally:
-        dgs.close()
-    return image
+    line = placed_line(font, text, font_size, x, y, w, h, slant)
+    if line is None:
+        return image
+    return _render(ctx, line, w, h, samples_per_axis, phase, _flags(flags | L.FR_TEXT_LOAD, srgb, bgra, cache, over),
+                   colours=per_char, image=image)
 
 
 def decoration_rects(font: Font, text, font_size: int, x: float, y: float, underline=None, strikeout=None, highlight=None):
@@ -274,14 +282,13 @@ def decoration_rects(font: Font, text, font_size: int, x: float, y: float, under
     if not math.isfinite(float(x)) or not math.isfinite(float(y)):
         raise ValueError(f"x {x!r}, y {y!r}: expected finite values")
     _, _, end = font.layout(text, font_size)
-    x64 = math.floor(64.0 * float(x) + 0.5)
-    y64 = math.floor(64.0 * float(y) + 0.5)
+    x64, y64 = q64(x), q64(y)
     rows = []
     for colour, kind in ((highlight, L.FR_DECOR_LINE_BOX), (underline, L.FR_DECOR_UNDERLINE), (strikeout, L.FR_DECOR_STRIKEOUT)):
         if colour is None:
             continue
         top, bottom = font.decoration(font_size, kind)
-        rows.append((x64 / 64.0, (y64 + top) / 64.0, (x64 + end) / 64.0, (y64 + bottom) / 64.0, _rgba(colour)))
+        rows.append((x64 / 64.0, (y64 + top) / 64.0, (x64 + end) / 64.0, (y64 + bottom) / 64.0, colour_rgba(colour)))
     return rows
 
 
@@ -292,7 +299,6 @@ def span_line(font: Font, spans):
     f32(units_per_em) and slant.  -> (glyph set, fr_glyph_place_ex places, runs, width, height, per-character colours),
     or None when nothing is drawn.  One run; the image is the union of the instance cells, as for render_text."""
     spans = [tuple(sp) for sp in spans]
-    upm = np.float32(font.information.units_per_em)
     for sp in spans:
         if len(sp) != 5:
             raise ValueError(f"span {sp!r}: expected (text, font_size, slant, rise, colour)")
@@ -301,31 +307,28 @@ def span_line(font: Font, spans):
             raise ValueError(f"span font_size {size!r}: expected an integer in [1, 65535]")
         if not math.isfinite(float(rise)):
             raise ValueError(f"span rise {rise!r}: expected a finite value")
-        _slant(slant), _rgba(colour)
+        _slant(slant), colour_rgba(colour)
     # consecutive spans of one size are one fr_text_layout call (the pen walks on unrounded, as inside one string, so
     # spans of a single size give exactly that string's pens); where the size changes the next call starts at the end pen
-    laid, start, k = [], 0, 0
+    glyphs, rows, colours, start, k = [], [], [], 0, 0
     while k < len(spans):
         m = k
         while m < len(spans) and spans[m][1] == spans[k][1]:
             m += 1
         texts = [[ord(c) for c in sp[0]] if isinstance(sp[0], str) else [int(c) for c in sp[0]] for sp in spans[k:m]]
         gi, pen, end = font.layout([c for t in texts for c in t], int(spans[k][1]))
+        glyphs += list(gi)
         at = 0
         for t, (_, size, slant, rise, colour) in zip(texts, spans[k:m]):
-            laid.append((gi[at:at + len(t)], pen[at:at + len(t)] + start, np.float32(size) / upm, _slant(slant),
-                         -math.floor(64.0 * float(rise) + 0.5), _rgba(colour)))
+            rows += [(int(p) + start, -q64(rise), _scale(font, size), _slant(slant)) for p in pen[at:at + len(t)]]
+            colours += [colour_rgba(colour)] * len(t)
             at += len(t)
         start += end
         k = m
-    distinct = sorted({int(g) for gi, *_ in laid for g in gi})
-    if not distinct:
+    if not glyphs:
         return None
-    gs, kept = font.glyphset(distinct, skip_unsupported=False)
-    local = {g: k for k, g in enumerate(kept)}
-    rows = [(local[int(g)], int(p), y64, s, k) for gi, pen, s, k, y64, _ in laid for g, p in zip(gi, pen)]
-    colours = [c for gi, _, _, _, _, c in laid for _ in gi]
-    fit = _fit(gs, rows)
+    gs, local = _glyphs(font, glyphs)
+    fit = _fit(gs, [(g,) + row for g, row in zip(local, rows)])
     return None if fit is None else (gs,) + fit + (colours,)
 
 
@@ -336,8 +339,7 @@ def render_spans(font: Font, spans, *, samples_per_axis: int = 4, mode: int = L.
     line = span_line(font, spans)
     if line is None:
         return Gray.init(0, 0)
-    ctx = ctx or default_context()
-    return _render_gray(ctx, *line[:5], mode, samples_per_axis, phase, flags)
+    return _render(ctx, line[:3], *line[3:5], samples_per_axis, phase, flags, mode)
 
 
 def render_spans_rgba(font: Font, spans, background=(0, 0, 0, 0), *, samples_per_axis: int = 4, phase: int = L.FR_SAMPLE_CENTER,
@@ -345,13 +347,12 @@ def render_spans_rgba(font: Font, spans, background=(0, 0, 0, 0), *, samples_per
                       ctx: Optional[Context] = None) -> RGBA:
     """render_spans as one RGBA image: every span's glyphs in its colour, blended per sample in order over `background`
     (srgb / bgra / over as render_text_rgba: with over the image is premultiplied)."""
-    flags |= (L.FR_TEXT_SRGB if srgb else 0) | (L.FR_TEXT_BGRA if bgra else 0) | (L.FR_TEXT_OVER if over else 0)
-    clear = _rgba(background)
+    clear = colour_rgba(background)
     line = span_line(font, spans)
     if line is None:
         return RGBA.init(0, 0)
-    ctx = ctx or default_context()
-    return _render_rgba(ctx, *line[:5], line[5], clear, samples_per_axis, phase, flags)
+    return _render(ctx, line[:3], *line[3:5], samples_per_axis, phase, _flags(flags, srgb, bgra, over=over), colours=line[5],
+                   clear=clear)
 
 
 def view_line(font: Font, text, font_size: int, zoom: float, offset_x: float, offset_y: float, width: int, height: int,
@@ -361,26 +362,18 @@ def view_line(font: Font, text, font_size: int, zoom: float, offset_x: float, of
     origin is at x = offset_x + zoom * pen_k and the baseline at y = offset_y, both kept to 1/64 pixel (floor(64 v +
     1/2)); the scale is f32(f32(font_size) * f32(zoom)) / f32(units_per_em).  -> (glyph set, fr_glyph_place_ex places,
     runs): one run of width x height pixels that clips the line, or None for an empty text or image."""
-    zoom = float(zoom)
-    if not (math.isfinite(zoom) and zoom > 0.0):
-        raise ValueError(f"zoom {zoom!r}: expected a finite value > 0")
+    zoom = _zoom(zoom)
     if not (math.isfinite(float(offset_x)) and math.isfinite(float(offset_y))):
         raise ValueError("offset_x / offset_y: expected finite values")
-    if not (isinstance(width, (int, np.integer)) and isinstance(height, (int, np.integer)) and 0 <= width <= 65535
-            and 0 <= height <= 65535):
-        raise ValueError(f"width {width!r} and height {height!r} must be integers in [0, 65535]")
+    _frame(width, height)
     slant = _slant(slant)
-    gi, pen, _ = font.layout(text, font_size)
-    if len(gi) == 0 or width == 0 or height == 0:
+    laid = _layout(font, text, font_size, width == 0 or height == 0)
+    if laid is None:
         return None
-    gs, kept = font.glyphset(sorted(set(int(g) for g in gi)), skip_unsupported=False)
-    local = {g: k for k, g in enumerate(kept)}
-    scale = np.float32(np.float32(font_size) * np.float32(zoom)) / np.float32(font.information.units_per_em)
-    y64 = math.floor(64.0 * float(offset_y) + 0.5)
-    places = make_places_ex([(local[int(g)], math.floor(64.0 * float(offset_x) + zoom * int(p) + 0.5), y64, 0.0, slant)
-                             for g, p in zip(gi, pen)])
-    runs = make_runs([(0, len(places), int(width), int(height), 0, 0, scale)])
-    return gs, places, runs
+    gs, local, pens, _ = laid
+    y64 = q64(offset_y)
+    places = make_places_ex([(g, math.floor(64.0 * float(offset_x) + zoom * p + 0.5), y64, 0.0, slant) for g, p in zip(local, pens)])
+    return gs, places, make_runs([(0, len(places), int(width), int(height), 0, 0, _scale(font, font_size, zoom))])
 
 
 def render_text_view(font: Font, text, font_size: int, zoom: float, offset_x: float, offset_y: float, width: int, height: int,
@@ -392,8 +385,7 @@ def render_text_view(font: Font, text, font_size: int, zoom: float, offset_x: fl
     line = view_line(font, text, font_size, zoom, offset_x, offset_y, width, height, slant)
     if line is None:
         return Gray.init(int(width), int(height))
-    ctx = ctx or default_context()
-    return _render_gray(ctx, *line, int(width), int(height), mode, samples_per_axis, phase, flags)
+    return _render(ctx, line, int(width), int(height), samples_per_axis, phase, flags, mode)
 
 
 def _cos_sin(angle_deg: float):
@@ -414,27 +406,21 @@ def rotated_line(font: Font, text, font_size: int, angle_deg: float, x: float, y
     binary32.  At the quarter turns cos and sin are exactly 0 and +-1, so those matrices are exact.  -> (glyph set,
     fr_glyph_place_affine places, runs): one run of width x height pixels that clips the line, or None for an empty text
     or image."""
-    zoom = float(zoom)
-    if not (math.isfinite(zoom) and zoom > 0.0):
-        raise ValueError(f"zoom {zoom!r}: expected a finite value > 0")
+    zoom = _zoom(zoom)
     if not (math.isfinite(float(x)) and math.isfinite(float(y)) and math.isfinite(float(angle_deg))):
         raise ValueError("x / y / angle_deg: expected finite values")
-    if not (isinstance(width, (int, np.integer)) and isinstance(height, (int, np.integer)) and 0 <= width <= 65535
-            and 0 <= height <= 65535):
-        raise ValueError(f"width {width!r} and height {height!r} must be integers in [0, 65535]")
+    _frame(width, height)
     k = _slant(slant)
-    gi, pen, _ = font.layout(text, font_size)
-    if len(gi) == 0 or width == 0 or height == 0:
+    laid = _layout(font, text, font_size, width == 0 or height == 0)
+    if laid is None:
         return None
-    gs, kept = font.glyphset(sorted(set(int(g) for g in gi)), skip_unsupported=False)
-    local = {g: i for i, g in enumerate(kept)}
+    gs, local, pens, _ = laid
     c, sn = _cos_sin(angle_deg)
     s = float(font_size) * zoom / float(font.information.units_per_em)
     m = (s * c, s * (c * k - sn), s * sn, s * (sn * k + c))
-    places = make_places_affine([(local[int(g)], math.floor(64.0 * (float(x) + c * zoom * int(p) / 64.0) + 0.5),
-                                  math.floor(64.0 * (float(y) - sn * zoom * int(p) / 64.0) + 0.5)) + m for g, p in zip(gi, pen)])
-    runs = make_runs([(0, len(places), int(width), int(height), 0, 0, 1.0)])
-    return gs, places, runs
+    places = make_places_affine([(g, q64(float(x) + c * zoom * p / 64.0), q64(float(y) - sn * zoom * p / 64.0)) + m
+                                 for g, p in zip(local, pens)])
+    return gs, places, make_runs([(0, len(places), int(width), int(height), 0, 0, 1.0)])
 
 
 def render_text_rotated(font: Font, text, font_size: int, angle_deg: float, x: float, y: float, width: int, height: int, *,
@@ -446,8 +432,7 @@ def render_text_rotated(font: Font, text, font_size: int, angle_deg: float, x: f
     line = rotated_line(font, text, font_size, angle_deg, x, y, width, height, zoom, slant)
     if line is None:
         return Gray.init(int(width), int(height))
-    ctx = ctx or default_context()
-    return _render_gray(ctx, *line, int(width), int(height), mode, samples_per_axis, phase, flags)
+    return _render(ctx, line, int(width), int(height), samples_per_axis, phase, flags, mode)
 
 
 def render_text_rgba_rotated(font: Font, text, font_size: int, angle_deg: float, x: float, y: float, width: int, height: int,
@@ -457,16 +442,11 @@ def render_text_rgba_rotated(font: Font, text, font_size: int, angle_deg: float,
                              ctx: Optional[Context] = None) -> RGBA:
     """render_text_rotated as one RGBA image: colours, background, srgb, bgra and over as render_text_rgba (with over the
     image is premultiplied)"""
-    flags |= (L.FR_TEXT_SRGB if srgb else 0) | (L.FR_TEXT_BGRA if bgra else 0) | (L.FR_TEXT_OVER if over else 0)
-    n_chars = len(text)
-    if colors is not None and len(colors) != n_chars:
-        raise ValueError(f"colors: {len(colors)} colours for {n_chars} characters")
-    per_char = [_rgba(c) for c in colors] if colors is not None else [_rgba(color)] * n_chars
-    clear = _rgba(background)
+    per_char, clear = _per_char(text, color, colors), colour_rgba(background)
     line = rotated_line(font, text, font_size, angle_deg, x, y, width, height, zoom, slant)
     if line is None:
         im = RGBA.init(int(width), int(height))
         im.data[:] = clear
         return im
-    ctx = ctx or default_context()
-    return _render_rgba(ctx, *line, int(width), int(height), per_char, clear, samples_per_axis, phase, flags)
+    return _render(ctx, line, int(width), int(height), samples_per_axis, phase, _flags(flags, srgb, bgra, over=over),
+                   colours=per_char, clear=clear)

@@ -37,6 +37,20 @@ def test_job_struct_layout():
     raw = _lib.Job.from_buffer_copy(j.tobytes())
     assert (raw.glyph, raw.min_x, raw.max_y, raw.w, raw.h, raw.out_x, raw.out_y, raw.scale) == (3, -5, 7, 16, 32, 48, 64, 0.5)
 
+    def back(struct, table, size):
+        """the one row of `table` read field by field through the ctypes structure (arrays as tuples)"""
+        assert table.shape == (1,) and table.dtype.itemsize == C.sizeof(struct) == size
+        raw = struct.from_buffer_copy(table.tobytes())
+        vals = [getattr(raw, name) for name, _ in struct._fields_]
+        return tuple(v if isinstance(v, (int, float)) else tuple(v) for v in vals)
+
+    assert back(_lib.GlyphPlace, fr.make_places([(7, -130, -9)]), 12) == (7, -130, -9)
+    assert back(_lib.GlyphPlaceEx, fr.make_places_ex([(7, -130, 77, 0.25, -0.5)]), 20) == (7, -130, 77, 0.25, -0.5)
+    assert back(_lib.GlyphPlaceAffine, fr.make_places_affine([(7, -130, 77, 0.5, -0.25, 2.0, 4.0)]), 28) == (7, -130, 77, (0.5, -0.25, 2.0, 4.0))
+    assert back(_lib.TextRun, fr.make_runs([(1, 2, 300, 40, 5, 6, 0.125)]), 28) == (1, 2, 300, 40, 5, 6, 0.125)
+    assert back(_lib.LayerBlit, fr.make_blits([(1, 2, 30, 40, -5, -6, 200)]), 28) == (1, 2, 30, 40, -5, -6, 200)
+    assert back(_lib.LayerRect, fr.make_rects([(-64, 32, 640, 1280, (9, 8, 7, 250))]), 20) == (-64, 32, 640, 1280, (9, 8, 7, 250))
+
 
 def test_render_glyph_dims_matches_oracle(oracle, ascii_set):
     """fr_render_glyph_dims is host arithmetic (render_glyph.zig:13-19): no GPU needed"""

@@ -10,7 +10,6 @@ import font_renderer_amd as fr
 import layer_ref as lr
 from fixtures import load_font
 from font_renderer_amd import _lib as L
-from font_renderer_amd import render_glyph as rg
 from layer_gpu import SENT, Guarded, premultiplied
 
 pytestmark = pytest.mark.gpu
@@ -22,7 +21,7 @@ def _over(ctx, layer, image, blits, srgb=False, src_skip=0, dst_skip=0):
     """fr_layer_over of `layer` (rows, stride, 4) over a guarded device copy of `image` -> (image after, the layer after).
     src_skip / dst_skip: pixels the device arrays are moved by, to leave the 16-byte grid."""
     d = Guarded(image, layer, dst_skip, src_skip)
-    rg.layer_over(ctx, d.src, layer.shape[1], layer.shape[0], d.dst, image.shape[1], image.shape[0], blits, srgb)
+    fr.layer_over(ctx, d.src, layer.shape[1], layer.shape[0], d.dst, image.shape[1], image.shape[0], blits, srgb)
     return d.result(ctx), d.layer_after
 
 
@@ -46,7 +45,7 @@ def domain():
 def test_every_triple_at_full_opacity(ctx, domain, srgb):
     """the OPACITY = 0 instance over the whole domain of its arithmetic, the clamp included (s_c > s_a occurs)"""
     layer, image = domain
-    got, layer_after = _over(ctx, layer, image, rg.make_blits([(0, 0, layer.shape[1], 256, 0, 0, 255)]), srgb)
+    got, layer_after = _over(ctx, layer, image, fr.make_blits([(0, 0, layer.shape[1], 256, 0, 0, 255)]), srgb)
     want = lr.over(layer, image, 255, srgb)
     assert np.array_equal(got, want), np.argwhere(got != want)[:4]
     assert np.array_equal(layer_after, layer)
@@ -64,7 +63,7 @@ def test_every_source_pixel_at_the_edge_opacities(ctx, srgb):
     image[..., 3] = np.arange(image.shape[1])[None, :] % 256
     for k, d in enumerate(DEST_C):
         image[:, 256 * k:256 * (k + 1), :3] = d
-    blits = rg.make_blits([(0, 0, 256, 256, 256 * k, 256 * j, o) for j, o in enumerate(OPACITIES) for k in range(len(DEST_C))])
+    blits = fr.make_blits([(0, 0, 256, 256, 256 * k, 256 * j, o) for j, o in enumerate(OPACITIES) for k in range(len(DEST_C))])
     got, layer_after = _over(ctx, layer, image, blits, srgb)
     want = lr.composite(layer, image, blits.tolist(), srgb)
     assert np.array_equal(got[..., 3], want[..., 3]), "alpha"
@@ -104,7 +103,7 @@ def test_geometry(ctx, small, case, stride, wide, src_skip, dst_skip, srgb):
     and its column matches the destination's modulo 4"""
     layer = small[wide]
     image = np.full((50, stride, 4), SENT, np.uint8)
-    blits = rg.make_blits(GEOMETRY[case])
+    blits = fr.make_blits(GEOMETRY[case])
     got, layer_after = _over(ctx, layer, image, blits, srgb, src_skip, dst_skip)
     want = lr.composite(layer, image, GEOMETRY[case], srgb)
     assert np.array_equal(got, want), (case, np.argwhere(got != want)[:4])
@@ -117,8 +116,8 @@ def test_translation(ctx, small, dx, dy):
     layer = small[0]
     image = np.zeros((60, 132, 4), np.uint8)
     image[:] = (40, 90, 20, 200)
-    at0, _ = _over(ctx, layer, image, rg.make_blits([(0, 0, 97, 41, 0, 0, 200)]))
-    moved, _ = _over(ctx, layer, image, rg.make_blits([(0, 0, 97, 41, dx, dy, 200)]))
+    at0, _ = _over(ctx, layer, image, fr.make_blits([(0, 0, 97, 41, 0, 0, 200)]))
+    moved, _ = _over(ctx, layer, image, fr.make_blits([(0, 0, 97, 41, dx, dy, 200)]))
     want = image.copy()
     want[dy:dy + 41, dx:dx + 97] = at0[:41, :97]
     assert np.array_equal(moved, want)
@@ -152,7 +151,7 @@ def test_a_text_layer_over_a_frame_is_the_load_render(ctx, flags):
     finally:
         dgs.close()
     assert out["layer"][..., 3].max() == 255 and (out["layer"][..., 3] == 0).any()
-    got, _ = _over(ctx, out["layer"], frame, rg.make_blits([(0, 0, w, h, 0, 0, 255)]), bool(flags & fr.FR_TEXT_SRGB))
+    got, _ = _over(ctx, out["layer"], frame, fr.make_blits([(0, 0, w, h, 0, 0, 255)]), bool(flags & fr.FR_TEXT_SRGB))
     assert np.array_equal(got, out["load"]), np.argwhere(got != out["load"])[:4]
     assert not np.array_equal(got, frame)
 
@@ -167,7 +166,7 @@ def test_unpremultiply_is_the_host_function(ctx, srgb):
     want = fr.RGBA(256, 256, px.reshape(-1, 4).copy()).unpremultiply(srgb).data.reshape(px.shape)
     buf = torch.from_numpy(px.copy()).to("cuda:0")
     torch.cuda.synchronize()
-    rg.layer_unpremultiply(ctx, buf.data_ptr(), 256, 256, 256, srgb)
+    fr.layer_unpremultiply(ctx, buf.data_ptr(), 256, 256, 256, srgb)
     ctx.sync()
     assert np.array_equal(buf.cpu().numpy(), want)
     assert np.array_equal(fr.RGBA(256, 256, px.reshape(-1, 4).copy()).unpremultiply(srgb, device=True, ctx=ctx).data.reshape(px.shape), want)
@@ -180,7 +179,7 @@ def test_unpremultiply_is_the_host_function(ctx, srgb):
     want[2:43, 3:100] = fr.RGBA(97, 41, win).unpremultiply(srgb).data.reshape(41, 97, 4)
     buf = torch.from_numpy(image.copy()).to("cuda:0")
     torch.cuda.synchronize()
-    rg.layer_unpremultiply(ctx, buf.data_ptr() + 4 * (2 * 131 + 3), 131, 97, 41, srgb)
+    fr.layer_unpremultiply(ctx, buf.data_ptr() + 4 * (2 * 131 + 3), 131, 97, 41, srgb)
     ctx.sync()
     assert np.array_equal(buf.cpu().numpy(), want)
 
@@ -219,20 +218,20 @@ def test_refusals_leave_the_destination_untouched(ctx, small):
     }
     for what, (code, (s, ss, sr, d, ds, dr, rows)) in cases.items():
         with pytest.raises(fr.FrError) as e:
-            rg.layer_over(ctx, s, ss, sr, d, ds, dr, rg.make_blits(rows))
+            fr.layer_over(ctx, s, ss, sr, d, ds, dr, fr.make_blits(rows))
         assert e.value.code == code, (what, str(e.value))
     for flags in (2, fr.FR_TEXT_SRGB, fr.FR_TEXT_OVER, 1 << 31):
         with pytest.raises(fr.FrError) as e:
-            rg.layer_over(ctx, S, 97, 41, D, 132, 50, rg.make_blits(ok), flags=flags)
+            fr.layer_over(ctx, S, 97, 41, D, 132, 50, fr.make_blits(ok), flags=flags)
         assert e.value.code == -1, flags
     with pytest.raises(fr.FrError) as e:                               # NULL blits with a count
         L.check(L.load_library().fr_layer_over(ctx._h, S, 97, 41, D, 132, 50, None, 1, 0))
     assert e.value.code == -1
-    rg.layer_over(ctx, S, 97, 41, D, 132, 50, None)                    # n_blits = 0: valid, launches nothing
-    rg.layer_over(ctx, S, 97, 41, D, 132, 50, rg.make_blits([(500, 500, 0, 3, 0, 0, 255)]))      # 0 x anything: valid
+    fr.layer_over(ctx, S, 97, 41, D, 132, 50, None)                    # n_blits = 0: valid, launches nothing
+    fr.layer_over(ctx, S, 97, 41, D, 132, 50, fr.make_blits([(500, 500, 0, 3, 0, 0, 255)]))      # 0 x anything: valid
     for w, h, stride, off, code in ((133, 1, 132, 0, -1), (10, 10, 132, 2, -1), (10, 10, (1 << 26) + 1, 0, -1)):
         with pytest.raises(fr.FrError) as e:
-            rg.layer_unpremultiply(ctx, D + off, stride, w, h)
+            fr.layer_unpremultiply(ctx, D + off, stride, w, h)
         assert e.value.code == code
     ctx.sync()
     assert np.array_equal(dst.cpu().numpy(), image) and np.array_equal(src.cpu().numpy(), layer)

@@ -11,7 +11,6 @@ import layer_ref as lr
 import layer_rects_ref as rr
 from fixtures import load_font
 from font_renderer_amd import _lib as L
-from font_renderer_amd import render_glyph as rg
 from layer_gpu import SENT, Guarded, premultiplied
 
 pytestmark = pytest.mark.gpu
@@ -22,7 +21,7 @@ def _rects(ctx, image, rows, srgb=False, dst_skip=0):
     """fr_layer_rects of `rows` (edges in 1/64 pixel) over a guarded device copy of `image` (rows, stride, 4) -> the image
     after.  dst_skip: pixels the device array is moved by, to leave the 16-byte grid."""
     d = Guarded(image, dst_skip=dst_skip)
-    rg.layer_rects(ctx, d.dst, image.shape[1], image.shape[0], None if rows is None else rg.make_rects(rows), srgb)
+    fr.layer_rects(ctx, d.dst, image.shape[1], image.shape[0], None if rows is None else fr.make_rects(rows), srgb)
     return d.result(ctx)
 
 
@@ -171,8 +170,8 @@ def test_consequence_2_on_the_device(ctx, noise, rect):
     tinted = torch.zeros((h, w, 4), dtype=torch.uint8, device="cuda:0")
     dst = torch.from_numpy(image.copy()).to("cuda:0")
     torch.cuda.synchronize()
-    rg.layer_shadow(ctx, src.data_ptr(), w, h, tinted.data_ptr(), w, h, (0, 0, w, h), (0, 0, w, h), (0, 0), 0, 0, 0, rect[4])
-    rg.layer_over(ctx, tinted.data_ptr(), w, h, dst.data_ptr(), w, h, rg.make_blits([(0, 0, w, h, 0, 0, 255)]))
+    fr.layer_shadow(ctx, src.data_ptr(), w, h, tinted.data_ptr(), w, h, (0, 0, w, h), (0, 0, w, h), (0, 0), 0, 0, 0, rect[4])
+    fr.layer_over(ctx, tinted.data_ptr(), w, h, dst.data_ptr(), w, h, fr.make_blits([(0, 0, w, h, 0, 0, 255)]))
     ctx.sync()
     got = _rects(ctx, image, [rect])
     assert np.array_equal(got, dst.cpu().numpy()) and not np.array_equal(got, image)
@@ -196,15 +195,15 @@ def test_consequence_1_and_refusals(ctx, noise):
         assert np.array_equal(got, want)
     dst = torch.from_numpy(image.copy()).to("cuda:0")
     torch.cuda.synchronize()
-    D, ok = dst.data_ptr(), rg.make_rects([(0, 0, 640, 640, (1, 2, 3, 255))])
+    D, ok = dst.data_ptr(), fr.make_rects([(0, 0, 640, 640, (1, 2, 3, 255))])
     for what, code, args in (("dst NULL", -1, (0, 128, 50)), ("dst not 4-byte aligned", -1, (D + 2, 128, 49)), ("pitch beyond 2^26", -1, (D, (1 << 26) + 1, 0)),
                              ("2^31 rows", -4, (D, 0, 1 << 31))):
         with pytest.raises(fr.FrError) as e:
-            rg.layer_rects(ctx, *args, ok)
+            fr.layer_rects(ctx, *args, ok)
         assert e.value.code == code, what
     for flags in (2, fr.FR_TEXT_SRGB, fr.FR_TEXT_OVER, 1 << 31):
         with pytest.raises(fr.FrError) as e:
-            rg.layer_rects(ctx, D, 128, 50, ok, flags=flags)
+            fr.layer_rects(ctx, D, 128, 50, ok, flags=flags)
         assert e.value.code == -1, flags
     lib = L.load_library()
     assert lib.fr_layer_rects(ctx._h, D, 128, 50, None, 1, 0) == -1 and lib.fr_layer_rects(None, D, 128, 50, L.ptr(ok), 1, 0) == -1

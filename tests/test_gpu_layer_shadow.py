@@ -12,7 +12,6 @@ import layer_shadow_ref as sr
 import text_gpu as tg
 from fixtures import load_font
 from font_renderer_amd import _lib as L
-from font_renderer_amd import render_glyph as rg
 from layer_gpu import SENT, Guarded, premultiplied
 
 pytestmark = pytest.mark.gpu
@@ -24,7 +23,7 @@ def _dev(layer, dst_shape, src_skip=0, dst_skip=0):
 
 
 def _shadow(ctx, d, window, rect, offset, s, r, p, rgba, srgb=False, flags=0):
-    rg.layer_shadow(ctx, d.src, d.layer.shape[1], d.layer.shape[0], d.dst, d.image.shape[1], d.image.shape[0], window, rect, offset, s, r, p, rgba, srgb,
+    fr.layer_shadow(ctx, d.src, d.layer.shape[1], d.layer.shape[0], d.dst, d.image.shape[1], d.image.shape[0], window, rect, offset, s, r, p, rgba, srgb,
                     flags)
 
 
@@ -199,9 +198,9 @@ def test_text_with_its_shadow_over_a_frame(ctx, srgb):
     dev_shadow = torch.full((H, W, 4), SENT, dtype=torch.uint8, device="cuda:0")
     dev_frame = torch.from_numpy(frame.copy()).to("cuda:0")
     torch.cuda.synchronize()
-    rg.layer_shadow(ctx, dev_layer.data_ptr(), w, h, dev_shadow.data_ptr(), W, H, (0, 0, w, h), (0, 0, W, H), (tx + 2, ty + 3), 1, 3, 3, colour, srgb)
-    rg.layer_over(ctx, dev_shadow.data_ptr(), W, H, dev_frame.data_ptr(), W, H, rg.make_blits([(0, 0, W, H, 0, 0, 255)]), srgb)
-    rg.layer_over(ctx, dev_layer.data_ptr(), w, h, dev_frame.data_ptr(), W, H, rg.make_blits([(0, 0, w, h, tx, ty, 255)]), srgb)
+    fr.layer_shadow(ctx, dev_layer.data_ptr(), w, h, dev_shadow.data_ptr(), W, H, (0, 0, w, h), (0, 0, W, H), (tx + 2, ty + 3), 1, 3, 3, colour, srgb)
+    fr.layer_over(ctx, dev_shadow.data_ptr(), W, H, dev_frame.data_ptr(), W, H, fr.make_blits([(0, 0, W, H, 0, 0, 255)]), srgb)
+    fr.layer_over(ctx, dev_layer.data_ptr(), w, h, dev_frame.data_ptr(), W, H, fr.make_blits([(0, 0, w, h, tx, ty, 255)]), srgb)
     ctx.sync()
     shadow = sr.shadow_rect(layer, (0, 0, w, h), (W, H), (tx + 2, ty + 3), 1, 3, 3, colour, srgb)
     assert np.array_equal(dev_shadow.cpu().numpy(), shadow)
@@ -225,7 +224,7 @@ def test_refusals_leave_the_destination_untouched(ctx, layers):
     win, rect = (0, 0, 97, 41), (0, 0, 100, 50)
 
     def call(s=S, ss=97, srows=41, dp=D, ds=132, dr=50, window=win, rc=rect, stages=(1, 3, 3), flags=0):
-        rg.layer_shadow(ctx, s, ss, srows, dp, ds, dr, window, rc, (0, 0), *stages, (1, 2, 3, 255), False, flags)
+        fr.layer_shadow(ctx, s, ss, srows, dp, ds, dr, window, rc, (0, 0), *stages, (1, 2, 3, 255), False, flags)
 
     cases = {
         "src NULL": (-1, "src", dict(s=0)),

@@ -29,7 +29,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")]
 
 import font_renderer_amd as fr  # noqa: E402
-from font_renderer_amd import render_glyph as rg  # noqa: E402
 from bench_text import workload  # noqa: E402
 from fixtures import load_font  # noqa: E402
 
@@ -105,8 +104,8 @@ def frame_case(ctx, stream, args, W, H):
         for c in configs:
             name, srgb, o, off = c
             lay = layers[name]
-            blits = rg.make_blits([(off, 0, W, H, 0, 0, o)])
-            res[c].append(time_calls(ctx, stream, args.calls, lambda k: rg.layer_over(ctx, lay.data_ptr(), W + 4, H, frame.data_ptr(), W, H, blits, srgb)))
+            blits = fr.make_blits([(off, 0, W, H, 0, 0, o)])
+            res[c].append(time_calls(ctx, stream, args.calls, lambda k: fr.layer_over(ctx, lay.data_ptr(), W + 4, H, frame.data_ptr(), W, H, blits, srgb)))
     for c in configs:
         name, srgb, o, off = c
         ms, lo, hi = stats([r[0] for r in res[c][1:]])
@@ -134,7 +133,7 @@ def text_case(ctx, stream, args):
                 torch.cuda.synchronize()
 
                 def composite(k):
-                    rg.layer_over(ctx, layer.data_ptr(), W, H, frame.data_ptr(), W, H, rg.make_blits([(0, 0, W, H, k % 7, k % 5, 255)]), srgb)
+                    fr.layer_over(ctx, layer.data_ptr(), W, H, frame.data_ptr(), W, H, fr.make_blits([(0, 0, W, H, k % 7, k % 5, 255)]), srgb)
 
                 rer, lay, comp, host = [], [], [], []
                 for r in range(args.repeats + 1):

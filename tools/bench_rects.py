@@ -24,7 +24,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")]
 
 import font_renderer_amd as fr  # noqa: E402
-from font_renderer_amd import render_glyph as rg  # noqa: E402
 from bench_layer import stats, time_calls  # noqa: E402
 from bench_text import workload  # noqa: E402
 from fixtures import load_font  # noqa: E402
@@ -56,13 +55,13 @@ def fill_case(ctx, stream, hip, args, W, H):
     solid[255][:] = torch.tensor([200, 60, 250, 255], dtype=torch.uint8, device="cuda:0")
     solid[128][:] = torch.tensor([100, 30, 125, 128], dtype=torch.uint8, device="cuda:0")          # (200, 60, 250) premultiplied by 128
     torch.cuda.synchronize()
-    blit = rg.make_blits([(0, 0, W, H, 0, 0, 255)])
+    blit = fr.make_blits([(0, 0, W, H, 0, 0, 255)])
     routes = {}
     for srgb in (False, True):
         for A in (255, 128):
-            rect = rg.make_rects([(0, 0, 64 * W, 64 * H, (200, 60, 250, A))])
-            routes[("rects", srgb, A)] = (lambda k, rect=rect, srgb=srgb: rg.layer_rects(ctx, frame.data_ptr(), W, H, rect, srgb), 4 if A == 255 else 8)
-            routes[("over", srgb, A)] = (lambda k, lay=solid[A], srgb=srgb: rg.layer_over(ctx, lay.data_ptr(), W, H, frame.data_ptr(), W, H, blit, srgb),
+            rect = fr.make_rects([(0, 0, 64 * W, 64 * H, (200, 60, 250, A))])
+            routes[("rects", srgb, A)] = (lambda k, rect=rect, srgb=srgb: fr.layer_rects(ctx, frame.data_ptr(), W, H, rect, srgb), 4 if A == 255 else 8)
+            routes[("over", srgb, A)] = (lambda k, lay=solid[A], srgb=srgb: fr.layer_over(ctx, lay.data_ptr(), W, H, frame.data_ptr(), W, H, blit, srgb),
                                          8 if A == 255 else 12)
     routes[("memset", False, 255)] = (lambda k: hip.hipMemsetD32Async(frame.data_ptr(), 0x7f3cfac8, W * H, stream.cuda_stream), 4)
     res = {r: [] for r in routes}
@@ -94,7 +93,7 @@ def lines_case(ctx, stream, args):
         boxes.append((0, 0, w, y1 - y0, 0, y0, 255))
         u0 = (base + under[0]) // 64
         lines.append((0, 0, w, max(1, (under[1] - under[0] + 32) // 64), 0, u0, 255))
-    rects, boxes, lines = rg.make_rects(rects), rg.make_blits(boxes), rg.make_blits(lines)
+    rects, boxes, lines = fr.make_rects(rects), fr.make_blits(boxes), fr.make_blits(lines)
     frame = torch.empty((H, W, 4), dtype=torch.uint8, device="cuda:0").random_(0, 256, generator=torch.Generator("cuda:0").manual_seed(9))
     frame[..., 3] = 255
     lh = int(max(b[3] for b in boxes.tolist()))
@@ -106,10 +105,10 @@ def lines_case(ctx, stream, args):
     px = sum(int(b[2]) * int(b[3]) for b in boxes.tolist()) + sum(int(b[2]) * int(b[3]) for b in lines.tolist())
 
     def over(k):
-        rg.layer_over(ctx, solid_box.data_ptr(), W, lh, frame.data_ptr(), W, H, boxes)
-        rg.layer_over(ctx, solid_line.data_ptr(), W, lh, frame.data_ptr(), W, H, lines)
+        fr.layer_over(ctx, solid_box.data_ptr(), W, lh, frame.data_ptr(), W, H, boxes)
+        fr.layer_over(ctx, solid_line.data_ptr(), W, lh, frame.data_ptr(), W, H, lines)
 
-    routes = {"rects": lambda k: rg.layer_rects(ctx, frame.data_ptr(), W, H, rects), "over": over}
+    routes = {"rects": lambda k: fr.layer_rects(ctx, frame.data_ptr(), W, H, rects), "over": over}
     res = {r: [] for r in routes}
     for _ in range(args.repeats + 1):
         for r, fn in routes.items():

@@ -24,7 +24,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")]
 
 import font_renderer_amd as fr  # noqa: E402
-from font_renderer_amd import render_glyph as rg  # noqa: E402
 from bench_layer import render_layer, stats, time_calls  # noqa: E402
 from bench_text import workload  # noqa: E402
 from fixtures import load_font  # noqa: E402
@@ -54,7 +53,7 @@ def frame_case(ctx, stream, args, W, H):
     out = torch.empty((H, W, 4), dtype=torch.uint8, device="cuda:0")
     frame = torch.empty((H, W, 4), dtype=torch.uint8, device="cuda:0").random_(0, 256, generator=torch.Generator("cuda:0").manual_seed(W))
     plane = layer[..., 3].to(torch.float16).reshape(1, 1, H, W).contiguous()
-    blits = rg.make_blits([(0, 0, W, H, 0, 0, 255)])
+    blits = fr.make_blits([(0, 0, W, H, 0, 0, 255)])
     torch.cuda.synchronize()
     sets = SETS + [(0, 32, 3), (0, 4, 1)]
     configs = [(st, srgb) for st in sets for srgb in (False, True)]
@@ -63,7 +62,7 @@ def frame_case(ctx, stream, args, W, H):
 
     def shadow(st, srgb):
         s, r, p = st
-        return lambda k: rg.layer_shadow(ctx, layer.data_ptr(), W, H, out.data_ptr(), W, H, (0, 0, W, H), (0, 0, W, H), (3, 4), s, r, p, COLOUR, srgb)
+        return lambda k: fr.layer_shadow(ctx, layer.data_ptr(), W, H, out.data_ptr(), W, H, (0, 0, W, H), (0, 0, W, H), (3, 4), s, r, p, COLOUR, srgb)
 
     def pooled(st):
         _, r, p = st
@@ -77,7 +76,7 @@ def frame_case(ctx, stream, args, W, H):
     with torch.cuda.stream(stream):
         for _ in range(args.repeats + 1):                               # the first round warms up
             for srgb in (False, True):
-                over[srgb].append(time_calls(ctx, stream, args.calls, lambda k: rg.layer_over(ctx, layer.data_ptr(), W, H, frame.data_ptr(), W, H, blits, srgb))[0])
+                over[srgb].append(time_calls(ctx, stream, args.calls, lambda k: fr.layer_over(ctx, layer.data_ptr(), W, H, frame.data_ptr(), W, H, blits, srgb))[0])
             for st in sets:
                 if st[1] and st[2]:
                     pool[st].append(time_calls(ctx, stream, args.calls, pooled(st))[0])
