@@ -239,6 +239,7 @@ pub extern "c" fn fr_layer_rects(ctx: *Ctx, dst_dev: *anyopaque, dst_stride_px: 
 pub extern "c" fn fr_selftest_division(d_lo: u32, d_hi: u32, mismatches: *u64, bad_divisor: ?*u32, bad_x_bits: ?*u32) c_int;
 pub extern "c" fn fr_selftest_sqrt(mismatches: *u64, bad_x_bits: ?*u32) c_int;
 pub extern "c" fn fr_selftest_row_cuts(gs: *fr_glyphset, jobs: [*]const Job, n_jobs: u32, samples_per_axis: c_int, phase: c_int, pairs: *u64, mismatches: *u64, first_bad: ?*[3]u32) c_int;
+pub extern "c" fn fr_selftest_cand_records(gs: *fr_glyphset, live: *u64, mismatches: *u64, first_bad: ?*[2]u32, glyph_live: ?[*]u32) c_int;
 
 pub const Error = error{ RasterFailed, OutOfMemory };
 

@@ -12,6 +12,8 @@ namespace fr {
 void launch_prepare(const int16_t *, const uint32_t *, const uint32_t *, const uint32_t *, uint32_t, Rec *,
                     uint32_t *, hipStream_t, int fill = 0);
 void launch_cuts(const int16_t *, uint32_t, float4 *, hipStream_t);
+void launch_cands(const int16_t *, const uint32_t *, const float4 *, uint32_t, uint4 *, hipStream_t);
+void launch_selftest_cand_records(const uint32_t *, const int16_t *, const uint4 *, uint32_t, unsigned long long *, uint32_t *, hipStream_t);
 void launch_selftest_row_cuts(const Job *, uint32_t, uint32_t, const uint32_t *, const int16_t *, const float4 *, int, int,
                               unsigned long long *, hipStream_t);
 uint32_t cov4_max_segments();
@@ -122,6 +124,7 @@ int fr_ctx_set_option(fr_ctx *ctx, const char *key, int64_t value)
         {"lds_pad", &fr_ctx::lds_pad, true, 0, 0xffffffffll, 1, nullptr},           // (taken modulo 2^32)
         {"cov4", &fr_ctx::cov4, true, 0, 0, 1, nullptr},
         {"row_cuts", &fr_ctx::row_cuts, true, 0, 0, 1, nullptr},
+        {"cand_records", &fr_ctx::cand_records, true, 0, 0, 1, nullptr},
         {"sdf_cull", &fr_ctx::sdf_cull, true, 0, 0, 1, nullptr},
         {"overlap", &fr_ctx::overlap, true, 0, 2, 1, "overlap must be 0 (never), 1 (plans of >= 32 Mpixel) or 2 (always)"},
         {"zero_copy", &fr_ctx::zero_copy, false, 0, 0, 1, nullptr},
@@ -204,6 +207,7 @@ int fr_glyphset_create(fr_ctx *ctx, const int16_t *points_xy, const uint32_t *co
     gs->rec_count.alloc(e, ng1 * 4);
     gs->recs.alloc(e, 2 * nseg1 * sizeof(fr::Rec));
     gs->seg_cut.alloc(e, nseg1 * sizeof(float4));
+    gs->seg_cand.alloc(e, nseg1 * 6 * sizeof(uint4));
     if (e == hipSuccess && np) e = hipMemcpyAsync(gs->pts.get(), points_xy, np * 2 * sizeof(int16_t), hipMemcpyHostToDevice, st);
     if (e == hipSuccess && gs->n_seg) e = hipMemcpyAsync(gs->seg_pts.get(), seg_pts.data(), (size_t)gs->n_seg * 12, hipMemcpyHostToDevice, st);
     if (e == hipSuccess && gs->n_seg) e = hipMemcpyAsync(gs->seg_p0.get(), seg_p0.data(), (size_t)gs->n_seg * 4, hipMemcpyHostToDevice, st);
@@ -217,6 +221,11 @@ int fr_glyphset_create(fr_ctx *ctx, const int16_t *points_xy, const uint32_t *co
     }
     if (e == hipSuccess) {
         fr::launch_cuts(gs->seg_pts.get(), gs->n_seg, gs->seg_cut.get(), st);     // the row cuts: once, they hold for every cell and scale
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
+        // the candidate table, from the cuts: once, it holds for every cell and scale
+        fr::launch_cands(gs->seg_pts.get(), gs->glyph_seg_start.get(), gs->seg_cut.get(), n_glyphs, gs->seg_cand.get(), st);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);   // host vectors above die with this frame
@@ -295,6 +304,40 @@ int fr_selftest_row_cuts(fr_glyphset *gs, const fr_job *jobs, uint32_t n_jobs, i
     if (first_bad && res[1]) {
         first_bad[0] = (uint32_t)(res[2] >> 40); first_bad[1] = (uint32_t)((res[2] >> 20) & 0xfffffu); first_bad[2] = (uint32_t)(res[2] & 0xfffffu);
     }
+    return FR_OK;
+}
+
+int fr_selftest_cand_records(fr_glyphset *gs, uint64_t *live, uint64_t *mismatches, uint32_t *first_bad, uint32_t *glyph_live)
+{
+    if (!gs || !live || !mismatches) return fail(FR_E_INVALID, "fr_selftest_cand_records: NULL argument");
+    if (!gs->seg_cand.get()) return fail(FR_E_INVALID, "fr_selftest_cand_records: the glyph set has no candidate table");
+    *live = 0; *mismatches = 0;
+    if (first_bad) first_bad[0] = first_bad[1] = 0u;
+    if (gs->n_glyphs == 0) return FR_OK;
+    HIP_TRY(hipSetDevice(gs->ctx->device));
+    hipStream_t st = gs->ctx->stream;
+    DevBuf<unsigned long long> d_res;
+    DevBuf<uint32_t> d_live;
+    unsigned long long res[3] = {0ull, 0ull, ~0ull};
+    std::vector<uint32_t> h_live(gs->n_glyphs, 0u);
+    hipError_t e = hipSuccess;
+    d_res.alloc(e, sizeof res);
+    d_live.alloc(e, (size_t)gs->n_glyphs * 4);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_res.get(), res, sizeof res, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        fr::launch_selftest_cand_records(gs->glyph_seg_start.get(), gs->seg_pts.get(), gs->seg_cand.get(), gs->n_glyphs, d_res.get(),
+                                         d_live.get(), st);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(res, d_res.get(), sizeof res, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(h_live.data(), d_live.get(), (size_t)gs->n_glyphs * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    else (void)hipStreamSynchronize(st);                  // (the copies above read and write `res` and `h_live`)
+    if (e != hipSuccess) return hip_fail(e, "fr_selftest_cand_records");
+    *live = res[0];
+    *mismatches = res[1];
+    if (first_bad && res[1]) { first_bad[0] = (uint32_t)(res[2] >> 32); first_bad[1] = (uint32_t)res[2]; }
+    if (glyph_live) memcpy(glyph_live, h_live.data(), (size_t)gs->n_glyphs * 4);
     return FR_OK;
 }
 

@@ -38,6 +38,7 @@ static fr::RenderArgs render_args(const fr_ctx *ctx, const GlyphView &g, const f
     a.seg_p0 = g.seg_p0;
     a.seg_pts = g.seg_pts;
     a.seg_cut = ctx->row_cuts ? g.seg_cut : nullptr;
+    a.seg_cand = (ctx->row_cuts && ctx->cand_records) ? g.seg_cand : nullptr;
     // fused: the render kernel builds the records of every glyph of <= 128 segments (<= 256 candidate roots)
     // in LDS itself — decided per job inside the kernel; larger glyphs are staged from HBM
     a.fused = ctx->fuse_prepare ? 1u : 0u;

@@ -67,6 +67,19 @@ struct __attribute__((aligned(8))) Rec40 {
                     // the crossing's step code is (dy > 0) ? zb : cb   (2: +1, 0: -1; :55, :68)
 };
 
+// One slot of a glyph set's candidate table (cand_kernel, fr_prepare.hip): a candidate root's record
+// as the set-up would build it — every field depends on the segment's control points and the root alone — with the range
+// bits of `fr` clear, and its row cut.  48 bytes, three 16-byte loads.  A glyph's slice [2 seg0, 2 seg0 + 2 nseg) holds its
+// live candidates (record_prep does not discard them, and their cut is not empty) in record order — quadratic first,
+// linear last, each group in candidate order — and then dead slots: all zero, the empty cut {+inf, -inf}.  A live record
+// divides by `a`, so a == 0 in the first 16 bytes marks a dead slot.
+struct __attribute__((aligned(16))) Cand {
+    Rec40 rec;
+    Cut cut;
+};
+static_assert(sizeof(Cand) == 48, "three 16-byte loads per candidate");
+__device__ __forceinline__ bool c4_cand_dead(const Cand &e) { return e.rec.a == 0.0f; }
+
 // select on a wave mask held in SGPRs — the VOP3 form, whose cost does not depend on what wrote the mask
 // (a VOP2 v_cndmask reading a VCC that is not fresh costs 3-5 vector instructions: profiles/r02/issue_model3.txt)
 __device__ __forceinline__ uint32_t c4_sel(unsigned long long m, uint32_t if_set, uint32_t if_clear)
@@ -129,6 +142,31 @@ __device__ __forceinline__ Cut c4_load_cut(const RenderArgs &A, uint32_t seg0, u
     return k;
 }
 
+// Slot c of the glyph's slice of the candidate table, and the row range guessed from its cut: the first row at or below
+// `hi` and the first row below `lo`, where the class changes in exact arithmetic.  As record_prep's, the guess only decides
+// how many rows record_settle looks at.  A dead slot has the empty cut, which misses every cell.
+__device__ __forceinline__ Cand c4_load_cand(const RenderArgs &A, uint32_t seg0, uint32_t c)
+{
+    return reinterpret_cast<const Cand *>(A.seg_cand)[2u * (size_t)seg0 + c];
+}
+__device__ __forceinline__ void c4_cand_guess(const Cut &k, const RowGeom &G, RowGuess &g)
+{
+    g.empty = cut_misses(k, row_span(G));
+    g.ra = 1u; g.re = 0u;
+    if (!g.empty) {
+        const float top = (float)G.rows;
+        g.ra = (uint32_t)fminf(fmaxf(__builtin_ceilf(G.row_of(k.hi)), 0.0f), top);
+        g.re = (uint32_t)fminf(fmaxf(__builtin_floorf(G.row_of(k.lo)) + 1.0f, 0.0f), top);
+    }
+}
+// the settled candidate: the table's record with its row range in the low bits of `fr`
+__device__ __forceinline__ Rec40 c4_cand_rec40(const Rec40 &m, uint32_t ra, uint32_t re)
+{
+    Rec40 o = m;
+    o.fr |= ra | (re << 12);
+    return o;
+}
+
 // Set-up for glyphs of <= 32 segments (<= 64 candidate roots: one per lane of ONE wave — ASCII-like glyphs), four
 // waves.  Settling a candidate's row range costs four evaluations of the reference's acceptance at the rows around
 // the two guessed ends; with the plain set-up wave 0 would do all of it while waves 1 - 3 (and the SIMDs they sit
@@ -136,6 +174,9 @@ __device__ __forceinline__ Cut c4_load_cut(const RenderArgs &A, uint32_t seg0, u
 // 1: ra, 2: re - 1, 3: re); wave 0 takes the guess when the four classes confirm it — exactly the condition under
 // which record_settle's walks would not move — and walks as before otherwise.  Same records, same order.
 // CUT = 1 (every set-up below): the class of a row is read off the candidate's row cut (A.seg_cut is not null, FILL = 0)
+// CUT = 2: the same, and lane c takes slot c of the glyph's candidate table (A.seg_cand is not null, FILL = 0) instead of
+// building candidate c: the slots are in record order already, so one ballot places the records, and a wave whose slots
+// are all dead has nothing to do between the barriers
 template <uint32_t RCAP, int N, uint32_t NCOL, int FILL, int CUT>
 __device__ __forceinline__ uint32_t c4_setup_small(const RenderArgs &A, const Job &job, uint32_t seg0, uint32_t nseg, uint32_t x0s,
                                                    int phase, float *s_cxp, Rec40 *s_rec, uint32_t *s_wcnt, uint32_t *s_tmp, const float *cyt = nullptr)
@@ -153,10 +194,18 @@ __device__ __forceinline__ uint32_t c4_setup_small(const RenderArgs &A, const Jo
     uint32_t cls = 3u;                                  // 3: no such row / not asked — the condition it stands for holds
     Cut k;
     k.lo = k.hi = 0.0f;
+    Rec40 tab;                                          // CUT = 2: the table's record of slot `lane`
+    tab.fr = 0u;
     if (have) {
-        bool drop = false;
-        if constexpr (CUT != 0) { k = c4_load_cut(A, seg0, lane); drop = cut_misses(k, row_span(geo)); }
-        record_prep<FILL>(A.seg_pts + 6u * (size_t)(seg0 + (lane >> 1)), lane & 1u, geo, r, g, &pc, drop);
+        if constexpr (CUT == 2) {
+            const Cand e = c4_load_cand(A, seg0, lane);
+            tab = e.rec; k = e.cut;
+            c4_cand_guess(k, geo, g);
+        } else {
+            bool drop = false;
+            if constexpr (CUT != 0) { k = c4_load_cut(A, seg0, lane); drop = cut_misses(k, row_span(geo)); }
+            record_prep<FILL>(A.seg_pts + 6u * (size_t)(seg0 + (lane >> 1)), lane & 1u, geo, r, g, &pc, drop);
+        }
         if (!g.empty) {
             const uint32_t row = (wave == 0u) ? g.ra - 1u : (wave == 1u) ? g.ra : (wave == 2u) ? g.re - 1u : g.re;   // (ra - 1 wraps past the cell at ra = 0)
             if (row < Hs && (wave != 2u || g.re > g.ra)) cls = (uint32_t)row_class<FILL, CUT>(r, pc, geo.cy(row), &k);
@@ -183,11 +232,12 @@ __device__ __forceinline__ uint32_t c4_setup_small(const RenderArgs &A, const Jo
                 if (!ok) record_settle<FILL, CUT>(r, geo, ra, re, &pc, &k);
             }
             live = ra < re;
-            mine = c4_make_rec40<FILL>(r, ra, re);
+            if constexpr (CUT == 2) mine = c4_cand_rec40(tab, ra, re);
+            else mine = c4_make_rec40<FILL>(r, ra, re);
         }
-        // quadratic records first, linear ones last (as c4_setup)
-        const bool linr = live && (int32_t)mine.fr < 0;
-        const unsigned long long lm = __ballot(live && !linr), ll = __ballot(linr), below = (1ull << lane) - 1ull;
+        // quadratic records first, linear ones last (as c4_setup); the candidate table's slots are in that order already
+        const bool linr = CUT != 2 && live && (int32_t)mine.fr < 0;
+        const unsigned long long lm = __ballot(live && !linr), ll = (CUT == 2) ? 0ull : __ballot(linr), below = (1ull << lane) - 1ull;
         const uint32_t n_quad = (uint32_t)__popcll(lm);
         uint32_t pos = RCAP;
         if ((lm >> lane) & 1ull) pos = (uint32_t)__popcll(lm & below);
@@ -220,10 +270,18 @@ __device__ __forceinline__ uint32_t c4_setup_mid(const RenderArgs &A, const Job 
     uint32_t cls0 = 3u, cls1 = 3u;                      // 3: no such row / not asked
     Cut k;
     k.lo = k.hi = 0.0f;
+    Rec40 tab;                                          // CUT = 2: the table's record of slot c
+    tab.fr = 0u;
     if (have) {
-        bool drop = false;
-        if constexpr (CUT != 0) { k = c4_load_cut(A, seg0, c); drop = cut_misses(k, row_span(geo)); }
-        record_prep<FILL>(A.seg_pts + 6u * (size_t)(seg0 + (c >> 1)), c & 1u, geo, r, g, &pc, drop);
+        if constexpr (CUT == 2) {
+            const Cand e = c4_load_cand(A, seg0, c);
+            tab = e.rec; k = e.cut;
+            c4_cand_guess(k, geo, g);
+        } else {
+            bool drop = false;
+            if constexpr (CUT != 0) { k = c4_load_cut(A, seg0, c); drop = cut_misses(k, row_span(geo)); }
+            record_prep<FILL>(A.seg_pts + 6u * (size_t)(seg0 + (c >> 1)), c & 1u, geo, r, g, &pc, drop);
+        }
         if (!g.empty) {
             const uint32_t end = h ? g.re : g.ra;       // rows end - 1 and end
             if (end - 1u < Hs && (h == 0u || g.re > g.ra)) cls0 = (uint32_t)row_class<FILL, CUT>(r, pc, geo.cy(end - 1u), &k);
@@ -248,11 +306,13 @@ __device__ __forceinline__ uint32_t c4_setup_mid(const RenderArgs &A, const Job 
             if (!ok) record_settle<FILL, CUT>(r, geo, ra, re, &pc, &k);
         }
         live = ra < re;
-        mine = c4_make_rec40<FILL>(r, ra, re);
+        if constexpr (CUT == 2) mine = c4_cand_rec40(tab, ra, re);
+        else mine = c4_make_rec40<FILL>(r, ra, re);
     }
-    // quadratic records first, linear ones last (as c4_setup): waves 0 and 1 hold them
-    const bool linr = live && (int32_t)mine.fr < 0;
-    const unsigned long long lm = __ballot(live && !linr), ll = __ballot(linr), below = (1ull << lane) - 1ull;
+    // quadratic records first, linear ones last (as c4_setup): waves 0 and 1 hold them; the candidate table's slots are in
+    // that order already
+    const bool linr = CUT != 2 && live && (int32_t)mine.fr < 0;
+    const unsigned long long lm = __ballot(live && !linr), ll = (CUT == 2) ? 0ull : __ballot(linr), below = (1ull << lane) - 1ull;
     if (lane == 0u && wave < 2u) { s_wcnt[wave] = (uint32_t)__popcll(lm); s_wcnt[2u + wave] = (uint32_t)__popcll(ll); }
     __syncthreads();
     const uint32_t q0 = s_wcnt[0], q1 = s_wcnt[1], l0 = s_wcnt[2], l1 = s_wcnt[3];
@@ -292,6 +352,28 @@ __device__ __forceinline__ uint32_t c4_setup_with(const RenderArgs &A, const Job
         lm[it] = 0ull; ll[it] = 0ull;
         mine[it].fr = 0u;
         if (it > 0 && it * 64u * NW >= 2u * nseg) continue;                 // workgroup-uniform: no second candidate
+        if constexpr (CUT == 2) {
+            if (c < 2u * nseg) {
+                const Cand e = c4_load_cand(A, seg0, c);
+                // (a wave whose slots are all dead — the fourth of a 128-segment glyph, with at most 192 live candidates —
+                // skips the block: the compiler branches on an empty execution mask)
+                if (!c4_cand_dead(e)) {
+                    RowGeom geo;
+                    geo.max_y = job.max_y; geo.set_scale(sdiv); geo.rows = Hs; geo.n = N; geo.phase = phase; geo.cyt = cyt;
+                    RowGuess g;
+                    c4_cand_guess(e.cut, geo, g);
+                    uint32_t ra = g.ra, re = g.re;
+                    Rec none;                                                    // (record_settle reads the cut alone)
+                    if (!g.empty) record_settle<0, 1>(none, geo, ra, re, nullptr, &e.cut);
+                    live = ra < re;
+                    mine[it] = c4_cand_rec40(e.rec, ra, re);
+                }
+            }
+            // the slots are in record order: one ballot
+            lm[it] = __ballot(live);
+            if (lane == 0) s_wcnt[it * NW + wave] = (uint32_t)__popcll(lm[it]);
+            continue;
+        }
         if (c < 2u * nseg) {
             Rec r;
             RowGeom geo;
@@ -328,7 +410,7 @@ __device__ __forceinline__ uint32_t c4_setup_with(const RenderArgs &A, const Job
 #pragma unroll
         for (uint32_t q = 0; q < CPT * NW; ++q) {
             if (q >= NW && q / NW * 64u * NW >= 2u * nseg) continue;        // (never written)
-            const uint32_t cq = s_wcnt[q], cl = s_wcnt[CPT * NW + q];
+            const uint32_t cq = s_wcnt[q], cl = (CUT == 2) ? 0u : s_wcnt[CPT * NW + q];
 #pragma unroll
             for (uint32_t it = 0; it < CPT; ++it) {
                 base_q[it] += (q < it * NW + wave) ? cq : 0u;
@@ -351,12 +433,21 @@ __device__ __forceinline__ uint32_t c4_setup_with(const RenderArgs &A, const Job
     return rec_cnt;
 }
 
-// the set-up with the glyph set's row cuts where the launch has them (A.seg_cut: the same for the whole grid), else without
+// the set-up from the glyph set's candidate table where the launch has it (A.seg_cand), else with its row cuts where the
+// launch has them (A.seg_cut), else without: the same for the whole grid
 template <uint32_t NW, uint32_t RCAP, int N, uint32_t NCOL, int FILL = 0>
 __device__ __forceinline__ uint32_t c4_setup(const RenderArgs &A, const Job &job, uint32_t seg0, uint32_t nseg, uint32_t x0s,
                                              int phase, float *s_cxp, Rec40 *s_rec, uint32_t *s_wcnt, uint32_t *s_tmp, const float *cyt = nullptr)
 {
-    // (FR_C4_ROW_CUTS: listing builds that hold one of the two paths alone — tools/trip_cost.py prices each; never shipped)
+    // (FR_C4_ROW_CUTS: listing builds that hold one of the three paths alone — tools/trip_cost.py prices each; never shipped)
+#if !defined(FR_C4_ROW_CUTS) || FR_C4_ROW_CUTS == 2
+    if constexpr (FILL == 0) {
+#ifndef FR_C4_ROW_CUTS
+        if (A.seg_cand)
+#endif
+            return c4_setup_with<NW, RCAP, N, NCOL, 0, 2>(A, job, seg0, nseg, x0s, phase, s_cxp, s_rec, s_wcnt, s_tmp, cyt);
+    }
+#endif
 #if !defined(FR_C4_ROW_CUTS) || FR_C4_ROW_CUTS == 1
     if constexpr (FILL == 0) {
 #ifndef FR_C4_ROW_CUTS

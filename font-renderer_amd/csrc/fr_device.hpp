@@ -133,6 +133,9 @@ struct RenderArgs {
     const float4 *seg_cut;             // per segment {lo, hi} of its t+ and of its t- candidate: the glyph set's row cuts
                                        // (fr_records.hpp).  May be null: the fast kernels' set-up then evaluates the
                                        // reference's acceptance itself
+    const uint4 *seg_cand;             // the glyph set's candidate table (Cand, fr_c4.hpp): three uint4 per candidate root, a
+                                       // glyph's live candidates first, in record order.  May be null: the fast kernels'
+                                       // set-up then builds every candidate from seg_pts (and seg_cut)
     const uint32_t *job_bits;          // win1_kernel's sign-bit mode / sdf_kernel: first word of each job's bit plane, or
                                        // 0xffffffff for a job whose sign is the byte the general kernel left in the output
     const uint32_t *bits;              // sdf_kernel: the bit planes (win1_kernel's sign-bit mode writes them through `out`)

@@ -38,6 +38,7 @@ struct fr_ctx {
     uint32_t min_wgs = 2048;     // split a cell's bands over workgroups below this many workgroups
     uint32_t cov4 = 1;           // jobs take the fast kernels (cov4_kernel / win1_kernel) where they fit (fast_class); 0: all general
     uint32_t row_cuts = 1;       // the fast kernels' set-up reads a row's class off the glyph set's row cuts; 0: evaluates the reference's acceptance
+    uint32_t cand_records = 1;   // with row_cuts: the fast kernels' set-up reads each candidate's record from the glyph set's candidate table; 0: builds it from the control points
     uint32_t zero_copy = 0;      // fr_render_glyph: render small glyphs from / into pinned host memory directly (measured: no faster than two small copies; off)
     uint32_t sdf_cull = 1;       // FR_SDF_U8: drop segments that cannot change a tile / a pixel (exact; 0 = look at all, for tests)
     uint32_t overlap = 1;        // a plan's smaller launches run beside its largest one on a second stream: 0 never, 1 plans of >= 32 Mpixel, 2 always
@@ -71,6 +72,7 @@ struct GlyphView {
     fr::Rec *recs;                     // written by prepare_kernel
     uint32_t *rec_count;
     const float4 *seg_cut;             // may be null (RenderArgs::seg_cut)
+    const uint4 *seg_cand;             // may be null (RenderArgs::seg_cand)
     uint32_t n_glyphs, max_seg_per_glyph;
 };
 
@@ -82,6 +84,7 @@ struct fr_glyphset {
     DevBuf<uint32_t> seg_p0, seg_prev, glyph_seg_start, rec_count;
     DevBuf<fr::Rec> recs;
     DevBuf<float4> seg_cut;                     // row cuts, one float4 per segment (fr_records.hpp): 16 B per segment
+    DevBuf<uint4> seg_cand;                     // candidate table, two Cand per segment (fr_c4.hpp): 96 B per segment
     std::vector<uint32_t> h_glyph_seg_start;   // host copy: plans attach each job's segment range to it
     std::vector<uint32_t> h_root_bound;         // per glyph: candidate roots the vertex rule cannot discard (>= live records)
     std::vector<uint32_t> h_ray_bound;          // per glyph: estimated maximum of the crossings of one horizontal ray
@@ -89,7 +92,7 @@ struct fr_glyphset {
 
     GlyphView view() const
     {
-        return GlyphView{pts.get(), seg_pts.get(), seg_p0.get(), glyph_seg_start.get(), recs.get(), rec_count.get(), seg_cut.get(), n_glyphs, max_seg_per_glyph};
+        return GlyphView{pts.get(), seg_pts.get(), seg_p0.get(), glyph_seg_start.get(), recs.get(), rec_count.get(), seg_cut.get(), seg_cand.get(), n_glyphs, max_seg_per_glyph};
     }
     ~fr_glyphset();                             // waits for the context's stream before the tables go
 };

@@ -10,7 +10,7 @@
 // correctly-rounded division).  Scaling x by 2^k is exact for q, r and q', so one binade
 // represents them all while every intermediate stays normal.
 #include "../../include/fr_raster.h"
-#include "fr_records.hpp"
+#include "fr_c4.hpp"
 
 namespace fr {
 
@@ -139,6 +139,78 @@ void launch_selftest_row_cuts(const Job *jobs, uint32_t n_jobs, uint32_t max_row
     if (n_jobs == 0 || max_rows == 0) return;
     hipLaunchKernelGGL(selftest_row_cuts_kernel, dim3(n_jobs, (max_rows + 63u) / 64u), dim3(256), 0, stream, jobs, glyph_seg_start,
                        seg_pts, seg_cut, n, phase, res);
+}
+
+// The glyph set's candidate table (Cand, fr_c4.hpp) against what it stands for.  One wave per glyph: lane l rebuilds
+// candidates l, l + 64, ... from the control points (record_prep, then find_cut — not the stored cuts), and the wave
+// works out where each live one belongs: quadratic first, linear last, each group in candidate order.  The slot there
+// must hold the rebuilt record and cut bit for bit (all twelve words), and every slot behind the live ones must be a
+// dead one: a == 0 and the empty cut.  That is the live count, the order, every field and the dead marks at once.
+// res[0]: live candidates, res[1]: mismatching slots, res[2]: the smallest mismatch as glyph << 32 | slot;
+// glyph_live[g]: the live candidates of glyph g as rebuilt.
+__global__ __launch_bounds__(64) void selftest_cand_records_kernel(const uint32_t *__restrict__ glyph_seg_start, const int16_t *__restrict__ seg_pts,
+                                                                   const Cand *__restrict__ tab, uint32_t n_glyphs, unsigned long long *res,
+                                                                   uint32_t *__restrict__ glyph_live)
+{
+    const uint32_t gl = blockIdx.x, lane = threadIdx.x;
+    if (gl >= n_glyphs) return;
+    const uint32_t s0 = glyph_seg_start[gl], n_cand = 2u * (glyph_seg_start[gl + 1u] - s0);
+    const size_t base = 2u * (size_t)s0;
+    RowGeom G;                                     // (no cell: record_prep's row guesses are not used)
+    G.max_y = 0; G.scale = 1.0f; G.rows = 0u; G.n = 1; G.phase = 0;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    // walk 0 counts the live quadratic candidates, walk 1 compares
+    uint32_t n_quad = 0u, at_q = 0u, at_l = 0u;
+    unsigned long long bad = 0ull, first = ~0ull;
+    for (int walk = 0; walk < 2; ++walk) {
+        for (uint32_t c0 = 0u; c0 < n_cand; c0 += 64u) {
+            const uint32_t c = c0 + lane;
+            bool live = false, lin = false;
+            Cand want;
+            if (c < n_cand) {
+                Rec r;
+                RowGuess g;
+                record_prep<0>(seg_pts + 6u * (size_t)(s0 + (c >> 1)), c & 1u, G, r, g);
+                if (!g.empty) {
+                    want.cut = find_cut(r);
+                    live = want.cut.lo <= want.cut.hi;
+                    lin = (int32_t)r.flags < 0;
+                    want.rec = c4_make_rec40<0>(r, 0u, 0u);
+                }
+            }
+            const unsigned long long mq = __ballot(live && !lin), ml = __ballot(live && lin);
+            if (walk == 0) { n_quad += (uint32_t)__popcll(mq); continue; }
+            if (live) {
+                const uint32_t slot = lin ? n_quad + at_l + (uint32_t)__popcll(ml & below) : at_q + (uint32_t)__popcll(mq & below);
+                const Cand got = tab[base + slot];
+                uint32_t w[12], v[12];
+                __builtin_memcpy(w, &want, 48);
+                __builtin_memcpy(v, &got, 48);
+                bool same = true;
+#pragma unroll
+                for (int i = 0; i < 12; ++i) same = same && w[i] == v[i];
+                if (!same) { ++bad; first = min(first, ((unsigned long long)gl << 32) | slot); }
+            }
+            at_q += (uint32_t)__popcll(mq);
+            at_l += (uint32_t)__popcll(ml);
+        }
+    }
+    const uint32_t n_live = n_quad + at_l;
+    for (uint32_t slot = n_live + lane; slot < n_cand; slot += 64u) {
+        const Cand got = tab[base + slot];
+        if (!(c4_cand_dead(got) && !(got.cut.lo <= got.cut.hi))) { ++bad; first = min(first, ((unsigned long long)gl << 32) | slot); }
+    }
+    if (lane == 0u) { glyph_live[gl] = n_live; atomicAdd(&res[0], (unsigned long long)n_live); }
+    if (bad) { atomicAdd(&res[1], bad); atomicMin(&res[2], first); }
+}
+
+// res: three words, zero-initialised but res[2] all ones; glyph_live: n_glyphs words
+void launch_selftest_cand_records(const uint32_t *glyph_seg_start, const int16_t *seg_pts, const uint4 *tab, uint32_t n_glyphs,
+                                  unsigned long long *res, uint32_t *glyph_live, hipStream_t stream)
+{
+    if (n_glyphs == 0) return;
+    hipLaunchKernelGGL(selftest_cand_records_kernel, dim3(n_glyphs), dim3(64), 0, stream, glyph_seg_start, seg_pts,
+                       reinterpret_cast<const Cand *>(tab), n_glyphs, res, glyph_live);
 }
 
 }  // namespace fr

@@ -54,6 +54,15 @@ class DeviceGlyphSet(Handle):
                                                    C.byref(pairs), C.byref(bad), first))
         return pairs.value, bad.value, tuple(first)
 
+    def selftest_cand_records(self):
+        """fr_selftest_cand_records: the set's candidate table against records and cuts rebuilt from the control points
+        -> (live candidates, mismatching slots, (glyph, slot) of the first mismatch, live candidates per glyph)"""
+        live, bad = C.c_uint64(), C.c_uint64()
+        first = (C.c_uint32 * 2)()
+        per_glyph = np.zeros(max(len(self.host), 1), np.uint32)
+        L.check(self.ctx._lib.fr_selftest_cand_records(self._h, C.byref(live), C.byref(bad), first, L.ptr(per_glyph)))
+        return live.value, bad.value, tuple(first), per_glyph[:len(self.host)]
+
 
 # the tables of the C ABI as numpy sees them: derived from the ctypes structures of _lib, which mirror include/fr_raster.h
 JOB_DTYPE = np.dtype(L.Job)

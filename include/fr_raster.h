@@ -126,7 +126,11 @@ int fr_ctx_sync(fr_ctx *ctx);
  * "cov4" (0: every job takes the general kernel), "row_cuts" (default 1: the set-up of the fast kernels reads the
  * class of a sample row off the glyph set's row cuts — two heights per candidate root, found once by
  * fr_glyphset_create, 16 bytes per segment; 0: it evaluates the reference's acceptance expression at the row, as
- * fr_render_glyph always does.  The pixels are the same either way: fr_selftest_row_cuts), "sdf_cull" (0: FR_SDF_U8 looks at every segment from
+ * fr_render_glyph always does.  The pixels are the same either way: fr_selftest_row_cuts), "cand_records" (default 1, and only
+ * with "row_cuts": that set-up also reads each candidate root's record — the coefficients, the reciprocal, the step codes,
+ * its cut — ready-made from the glyph set's candidate table, built once by fr_glyphset_create, 96 bytes per segment,
+ * live candidates first and in record order; 0: it builds every candidate from the segment's control points.  The same
+ * records either way: fr_selftest_cand_records), "sdf_cull" (0: FR_SDF_U8 looks at every segment from
  * every pixel — the culls are exact, this is how the tests show it), "zero_copy" (1: fr_render_glyph renders small
  * glyphs straight from / into pinned host memory; measured no faster, off by default), "overlap" (a plan that needs several kernel launches forks the
  * smaller ones onto an internal second stream and joins them: 1 (default) for plans of >= 32 Mpixel — below that one
@@ -843,6 +847,14 @@ int fr_selftest_sqrt(uint64_t *mismatches, uint32_t *bad_x_bits);
  * the smallest mismatch, row 0xfffff meaning the settled ranges.  Jobs are checked as fr_plan_create checks them.  */
 int fr_selftest_row_cuts(fr_glyphset *gs, const fr_job *jobs, uint32_t n_jobs, int samples_per_axis, int phase,
                          uint64_t *pairs, uint64_t *mismatches, uint32_t *first_bad);
+/* The candidate table of a glyph set (option "cand_records") holds, per glyph, the records of its live candidate roots —
+ * those the set-up does not discard from the control points alone and whose row cut is not empty — quadratic first,
+ * linear last, each group in candidate order, and dead slots behind them.  For every glyph of the set this rebuilds each
+ * candidate's record and cut on the device from the control points and compares with the table: the live count, the
+ * order, every field bit for bit, and the dead slots' mark.  *live: the live candidates of the whole set; *mismatches
+ * (slots that differ) must come back 0; first_bad (may be NULL, else two words): glyph and slot within the glyph of the
+ * smallest mismatch; glyph_live (may be NULL, else one word per glyph): each glyph's live candidates as rebuilt.  */
+int fr_selftest_cand_records(fr_glyphset *gs, uint64_t *live, uint64_t *mismatches, uint32_t *first_bad, uint32_t *glyph_live);
 
 #ifdef __cplusplus
 }

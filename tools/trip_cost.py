@@ -18,9 +18,10 @@ compiler's assembly and every vector instruction in them is classified by mnemon
           instructions per division: the sequence itself is 11) — blocks a job whose scale is a power of two branches
           around.  (A division by the scale is a v_div_fixup_f32 whose divisor is an SGPR: the scale is the only scalar
           divisor in the kernel.  Where the division sits inside a larger block, every job executes it.)
-          The shipped set-up holds two copies of each of its three forms: one reads a row's class off the glyph set's row
-          cuts, one evaluates the reference's acceptance (fr_records.hpp).  They are priced apart from two more listings,
-          compiled with -DFR_C4_ROW_CUTS=1 and =0, which hold one copy each.
+          The shipped set-up holds three copies of each of its three forms: one reads ready-made candidate records from the
+          glyph set's table, one builds them and reads a row's class off the glyph set's row cuts, one evaluates the
+          reference's acceptance (fr_c4.hpp, fr_records.hpp).  They are priced apart from three more listings, compiled
+          with -DFR_C4_ROW_CUTS=2, =1 and =0, which hold one copy each.
 
 The counts are static: instructions in the text, not instructions executed.  The script reads only the mnemonics it
 classifies; labels, scalar instructions, LDS and memory instructions are counted as "other" and not priced."""
@@ -176,6 +177,7 @@ def main():
     ap.add_argument("--asm", help="assembly of fr_cov4.hip made earlier; default: compile it now")
     ap.add_argument("--asm-cuts", help="with --asm: assembly made with -DFR_C4_ROW_CUTS=1 (the set-up with row cuts alone)")
     ap.add_argument("--asm-nocuts", help="with --asm: assembly made with -DFR_C4_ROW_CUTS=0 (the set-up that evaluates the acceptance alone)")
+    ap.add_argument("--asm-cands", help="with --asm: assembly made with -DFR_C4_ROW_CUTS=2 (the set-up from the candidate table alone)")
     ap.add_argument("--show", action="store_true", help="also print the trip's instructions with their classes")
     a = ap.parse_args()
     if a.asm:
@@ -202,10 +204,10 @@ def main():
     report("set-up, all code", ca)
     report("set-up, power-of-two scale path", path,
            f"   ({ndiv} divisions by the scale in the text, {naside} of them in blocks of their own)")
-    # the two ways a row's class is found, each from a listing build that holds it alone (FR_C4_ROW_CUTS, fr_c4.hpp)
+    # the three ways a set-up gets its records, each from a listing build that holds it alone (FR_C4_ROW_CUTS, fr_c4.hpp)
     if not a.asm or a.asm_cuts:
         with tempfile.TemporaryDirectory() as d:
-            for name, val, given in (("acceptance evaluated", 0, a.asm_nocuts), ("row cuts", 1, a.asm_cuts)):
+            for name, val, given in (("acceptance evaluated", 0, a.asm_nocuts), ("row cuts", 1, a.asm_cuts), ("candidate table", 2, a.asm_cands)):
                 if not given:
                     given = os.path.join(d, f"cov4_{val}.s")
                     compile_asm(given, [f"-DFR_C4_ROW_CUTS={val}"])
