@@ -38,8 +38,15 @@ pub const FR_TEXT_LOAD: u32 = 32;
 pub const FR_TEXT_CACHE: u32 = 128;
 /// flag of the RGBA text plan entry points (fr_raster.h): source-over alpha, a premultiplied output
 pub const FR_TEXT_OVER: u32 = 256;
-/// the flag space of fr_layer_over, fr_layer_shadow and fr_layer_rects (fr_raster.h): composite in linear light
+/// the flag space of fr_layer_over, fr_layer_shadow, fr_layer_rects and fr_layer_paint (fr_raster.h): composite in linear light
 pub const FR_LAYER_SRGB: u32 = 1;
+/// LayerPaintParams.kind and .spread (fr_raster.h: fr_layer_paint)
+pub const FR_GRADIENT_LINEAR: u32 = 0;
+pub const FR_GRADIENT_RADIAL: u32 = 1;
+pub const FR_SPREAD_PAD: u32 = 0;
+pub const FR_SPREAD_REPEAT: u32 = 1;
+pub const FR_SPREAD_REFLECT: u32 = 2;
+pub const FR_GRADIENT_MAX_STOPS = 8;
 
 pub const RasterParams = extern struct {
     mode: i32,
@@ -123,6 +130,31 @@ pub const LayerRect = extern struct {
     x1: i32,
     y1: i32,
     rgba: [4]u8,
+};
+
+/// one colour stop of a gradient (fr_layer_paint): offset in 0 .. 65536, not below the stop before it, and a straight colour
+pub const GradientStop = extern struct {
+    offset: u32,
+    rgba: [4]u8,
+};
+
+/// the parameters of fr_layer_paint: the layer's window, where it lands, and the gradient (geometry in 1/64 pixel of the
+/// destination, y down; linear: (x0, y0) to (x1, y1); radial: centre (x0, y0), radius x1, y1 = 0)
+pub const LayerPaintParams = extern struct {
+    src_x: u32,
+    src_y: u32,
+    w: u32,
+    h: u32,
+    dst_x: i32,
+    dst_y: i32,
+    kind: u32,
+    spread: u32,
+    x0: i32,
+    y0: i32,
+    x1: i32,
+    y1: i32,
+    n_stops: u32,
+    stops: [FR_GRADIENT_MAX_STOPS]GradientStop,
 };
 
 /// fr_font_line_metrics: hhea, post and OS/2 in font units, y up; present bit 0: post, bit 1: OS/2
@@ -235,6 +267,8 @@ pub extern "c" fn fr_layer_unpremultiply(ctx: *Ctx, rgba_dev: *anyopaque, stride
 pub extern "c" fn fr_layer_shadow(ctx: *Ctx, src_dev: *const anyopaque, src_stride_px: usize, src_rows: usize, dst_dev: *anyopaque, dst_stride_px: usize, dst_rows: usize, shadow: *const LayerShadowParams, flags: u32) c_int;
 /// anti-aliased rectangles, each in one straight colour, composited in order over a premultiplied image in device memory
 pub extern "c" fn fr_layer_rects(ctx: *Ctx, dst_dev: *anyopaque, dst_stride_px: usize, dst_rows: usize, rects: ?[*]const LayerRect, n_rects: u32, flags: u32) c_int;
+/// a linear or radial gradient composited over a premultiplied image through the alpha of a layer's window (src_dev null: full coverage)
+pub extern "c" fn fr_layer_paint(ctx: *Ctx, src_dev: ?*const anyopaque, src_stride_px: usize, src_rows: usize, dst_dev: *anyopaque, dst_stride_px: usize, dst_rows: usize, paint: *const LayerPaintParams, flags: u32) c_int;
 // ---- self-tests of the two arithmetic shortcuts (device-side, exhaustive)
 pub extern "c" fn fr_selftest_division(d_lo: u32, d_hi: u32, mismatches: *u64, bad_divisor: ?*u32, bad_x_bits: ?*u32) c_int;
 pub extern "c" fn fr_selftest_sqrt(mismatches: *u64, bad_x_bits: ?*u32) c_int;

@@ -13,7 +13,10 @@ FR_TEXT_SRGB, FR_TEXT_BGRA = 8, 4  # flags of fr_text_plan_create_rgba only: lin
 FR_TEXT_LOAD = 32                  # fr_text_plan_create_rgba only: draw over the pixels already in the output
 FR_TEXT_CACHE = 128                # the upright and _ex text plans: each distinct glyph image made once per render, same bytes
 FR_TEXT_OVER = 256                 # the RGBA text plans: source-over alpha (a premultiplied output) instead of alpha replaced
-FR_LAYER_SRGB = 1                  # the flag space of fr_layer_over, fr_layer_shadow and fr_layer_rects: work in linear light
+FR_LAYER_SRGB = 1                  # the flag space of the fr_layer_over / _shadow / _rects / _paint calls: work in linear light
+FR_GRADIENT_LINEAR, FR_GRADIENT_RADIAL = 0, 1                   # fr_layer_paint_params.kind
+FR_SPREAD_PAD, FR_SPREAD_REPEAT, FR_SPREAD_REFLECT = 0, 1, 2    # fr_layer_paint_params.spread
+FR_GRADIENT_MAX_STOPS = 8
 FR_DECOR_UNDERLINE, FR_DECOR_STRIKEOUT, FR_DECOR_LINE_BOX = 0, 1, 2    # the kinds of fr_text_decoration
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -73,6 +76,17 @@ class LayerShadowParams(C.Structure):    # == fr_layer_shadow_params
 
 class LayerRect(C.Structure):    # == fr_layer_rect
     _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32), ("rgba", C.c_uint8 * 4)]
+
+
+class GradientStop(C.Structure):  # == fr_gradient_stop
+    _fields_ = [("offset", C.c_uint32), ("rgba", C.c_uint8 * 4)]
+
+
+class LayerPaintParams(C.Structure):     # == fr_layer_paint_params
+    _fields_ = [("src_x", C.c_uint32), ("src_y", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32),
+                ("dst_x", C.c_int32), ("dst_y", C.c_int32), ("kind", C.c_uint32), ("spread", C.c_uint32),
+                ("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32),
+                ("n_stops", C.c_uint32), ("stops", GradientStop * FR_GRADIENT_MAX_STOPS)]
 
 
 class FontLine(C.Structure):     # == fr_font_line
@@ -156,6 +170,7 @@ SYMBOLS = [
     ("fr_layer_unpremultiply", C.c_int, [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.c_int]),
     ("fr_layer_shadow", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.POINTER(LayerShadowParams), C.c_uint32]),
     ("fr_layer_rects", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_uint32, C.c_uint32]),
+    ("fr_layer_paint", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.POINTER(LayerPaintParams), C.c_uint32]),
     ("fr_selftest_sqrt", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     ("fr_selftest_division", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("fr_selftest_row_cuts", C.c_int, [_P, _P, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),

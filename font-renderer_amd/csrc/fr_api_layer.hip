@@ -1,9 +1,11 @@
-// fr_api_layer.hip — C ABI (include/fr_raster.h): fr_layer_over, fr_layer_unpremultiply, fr_layer_shadow and fr_layer_rects.
-// The checks, the clipping and the tile table are fr_layer_plan.cpp's, the shadow's stages fr_layer_shadow_plan.cpp's, the
-// rectangles' tables fr_layer_rects_plan.cpp's; this unit stages the tables, keeps the shadow's planes and launches the
-// kernels of fr_layer.hip, fr_layer_shadow.hip and fr_layer_rects.hip.
+// fr_api_layer.hip — C ABI (include/fr_raster.h): fr_layer_over, fr_layer_unpremultiply, fr_layer_shadow, fr_layer_rects and
+// fr_layer_paint.  The checks, the clipping and the tile table are fr_layer_plan.cpp's, the shadow's stages
+// fr_layer_shadow_plan.cpp's, the rectangles' tables fr_layer_rects_plan.cpp's, the gradient's coefficients and colour table
+// fr_layer_paint_plan.cpp's; this unit stages the tables, keeps the shadow's planes and launches the kernels of fr_layer.hip,
+// fr_layer_shadow.hip, fr_layer_rects.hip and fr_layer_paint.hip.
 #include "fr_internal.hpp"
 #include "fr_layer.hpp"
+#include "fr_layer_paint.hpp"
 #include "fr_layer_rects.hpp"
 #include "fr_layer_shadow.hpp"
 
@@ -196,6 +198,26 @@ int fr_layer_rects(fr_ctx *ctx, void *dst_dev, size_t dst_stride_px, size_t dst_
     const fr::RectsArgs a{reinterpret_cast<const fr::RectTile *>(tab), reinterpret_cast<const uint32_t *>(tab + list_at),
                           reinterpret_cast<const fr::RectRec *>(tab + recs_at), static_cast<uint32_t *>(dst_dev), dst_stride_px, t.dst_vec ? 1u : 0u};
     HIP_TRY(fr::launch_layer_rects((flags & FR_LAYER_SRGB) != 0, (uint32_t)n, a, ctx->stream));
+    return FR_OK;
+}
+
+int fr_layer_paint(fr_ctx *ctx, const void *src_dev, size_t src_stride_px, size_t src_rows, void *dst_dev, size_t dst_stride_px,
+                   size_t dst_rows, const fr_layer_paint_params *paint, uint32_t flags)
+{
+    if (!ctx) return fail(FR_E_INVALID, "fr_layer_paint: ctx is NULL");
+    fr::PaintPlan p;
+    const fr::PaintIn in{(uintptr_t)src_dev, (uintptr_t)dst_dev, src_stride_px, src_rows, dst_stride_px, dst_rows, paint, flags};
+    if (const int rc = fr::layer_paint_plan(in, p)) return rc;
+    if (p.nothing) return FR_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    // the colour table goes through the staging; the clipped rectangle and the three coefficients are kernel arguments
+    static_assert(sizeof p.table == fr::PAINT_TABLE / 4 * sizeof(uint4), "the table in units of the staging");
+    const uint4 *tab = nullptr;
+    if (const int rc = layer_tables_to_device(ctx, fr::PAINT_TABLE / 4, &tab, [&](uint4 *to) { memcpy(to, p.table, sizeof p.table); })) return rc;
+    const fr::PaintArgs a{reinterpret_cast<const uint32_t *>(tab), static_cast<const uint32_t *>(src_dev), static_cast<uint32_t *>(dst_dev),
+                          src_stride_px, dst_stride_px, p.x0, p.x1, p.y0, p.y1, p.tx0, p.tiles_x, p.sx0, p.sy,
+                          (p.dst_vec ? fr::LAYER_DST_VEC : 0u) | (p.src_vec ? fr::LAYER_SRC_VEC : 0u), paint->spread, {p.c[0], p.c[1], p.c[2]}};
+    HIP_TRY(fr::launch_layer_paint((flags & FR_LAYER_SRGB) != 0, paint->kind == FR_GRADIENT_RADIAL, p.tiles_x * p.tiles_y, a, ctx->stream));
     return FR_OK;
 }
 

@@ -1,5 +1,5 @@
 // fr_layer_px.hpp — source-over of one premultiplied pixel, for the kernels that composite onto an image: layer_over_kernel
-// (fr_layer.hip) and layer_rects_kernel (fr_layer_rects.hip).  The arithmetic is that of the text plans' colour body
+// (fr_layer.hip), layer_rects_kernel (fr_layer_rects.hip) and layer_paint_kernel (fr_layer_paint.hip).  The arithmetic is that of the text plans' colour body
 // (fr_text_colour.hpp), per pixel instead of per sample.
 #pragma once
 #include "fr_text_colour.hpp"

@@ -222,6 +222,18 @@ inline void layer_rects(Context &ctx, const DeviceImage &image, const std::vecto
 {
     check(fr_layer_rects(ctx.get(), image.pixels, image.stride_px, image.rows, rects.data(), (uint32_t)rects.size(), srgb ? FR_LAYER_SRGB : 0u));
 }
+// fr_layer_paint: the gradient of `paint` composited over the premultiplied `image` through the alpha of the window of
+// `layer` that `paint` names: gradient text from a text layer, a gradient glow from a shadow.  Asynchronous on the
+// context's stream; `paint` may be reused at once.
+inline void layer_paint(Context &ctx, const DeviceImage &layer, const DeviceImage &image, const fr_layer_paint_params &paint, bool srgb = false)
+{
+    check(fr_layer_paint(ctx.get(), layer.pixels, layer.stride_px, layer.rows, image.pixels, image.stride_px, image.rows, &paint, srgb ? FR_LAYER_SRGB : 0u));
+}
+// the same through full coverage: a gradient panel of paint.w x paint.h (paint.src_x = paint.src_y = 0)
+inline void layer_paint(Context &ctx, const DeviceImage &image, const fr_layer_paint_params &paint, bool srgb = false)
+{
+    check(fr_layer_paint(ctx.get(), nullptr, 0, 0, image.pixels, image.stride_px, image.rows, &paint, srgb ? FR_LAYER_SRGB : 0u));
+}
 
 class PlacedText {
 public:

@@ -10,7 +10,7 @@ import numpy as np
 from . import _lib as L
 from .device import default_context, round_trip
 from .glyph import GlyphSet
-from .layer import layer_over, layer_rects, layer_shadow, layer_unpremultiply, make_blits, make_rects
+from .layer import layer_over, layer_paint, layer_rects, layer_shadow, layer_unpremultiply, make_blits, make_rects
 
 
 def q64(v) -> int:
@@ -171,6 +171,28 @@ class RGBA:                     # an RGBA text plan's image (fr_text_plan_create
         ctx = ctx or default_context()
         table = make_rects(rows)
         self.data[:] = round_trip(ctx, lambda d: layer_rects(ctx, d, self.width, self.height, table, srgb), dst)
+        return self
+
+    def paint(self, gradient, mask: "RGBA" = None, x: int = 0, y: int = 0, srgb: bool = False, ctx=None) -> "RGBA":
+        """fr_layer_paint, in place: `gradient` (make_gradient_linear / make_gradient_radial, its geometry in 1/64 pixel of
+        this image) composited over this premultiplied image through the alpha of the layer `mask` with its top-left pixel
+        at (x, y), whole pixels, clipped at the image's edges: gradient text when the mask is an over=True render, a gradient
+        glow when it is a shadow.  mask None: full coverage over the whole image, a gradient panel (x and y are not used).
+        srgb: the image is premultiplied in linear light.  The images are uploaded, painted on the device and this one
+        copied back.  Returns self."""
+        dst = rgba_pixels(self, "RGBA.paint: image")
+        if self.width == 0 or self.height == 0:
+            return self
+        ctx = ctx or default_context()
+        if mask is None:
+            self.data[:] = round_trip(ctx, lambda d: layer_paint(ctx, None, 0, 0, d, self.width, self.height, gradient,
+                                                                 (0, 0, self.width, self.height), (0, 0), srgb), dst)
+            return self
+        src = rgba_pixels(mask, "RGBA.paint: mask")
+        if mask.width == 0 or mask.height == 0:
+            return self
+        self.data[:] = round_trip(ctx, lambda d, s: layer_paint(ctx, s, mask.width, mask.height, d, self.width, self.height, gradient,
+                                                                (0, 0, mask.width, mask.height), (int(x), int(y)), srgb), dst, src)
         return self
 
     def shadow(self, offset=(0, 0), spread: int = 0, blur_radius: int = 0, blur_passes: int = 0, rgba=(0, 0, 0, 255),

@@ -1,6 +1,6 @@
 """The layer calls of the C ABI (fr_layer_*, include/fr_raster.h) on device addresses, and the builders of their tables.
-All of them are asynchronous on the context's stream; RGBA.over / fill_rects / shadow / unpremultiply (image.py) wrap them
-for host images."""
+All of them are asynchronous on the context's stream; RGBA.over / fill_rects / paint / shadow / unpremultiply (image.py) wrap
+them for host images."""
 from __future__ import annotations
 
 import ctypes as C
@@ -23,6 +23,34 @@ def make_blits(rows: Sequence) -> np.ndarray:
 def make_rects(rows: Sequence) -> np.ndarray:
     """rows of (x0, y0, x1, y1, (R, G, B, A)), the edges in 1/64 pixel -> fr_layer_rect array"""
     return np.array([(int(r[0]), int(r[1]), int(r[2]), int(r[3]), tuple(int(v) for v in r[4])) for r in rows], RECT_DTYPE)
+
+
+def _gradient(kind: int, geometry, stops, spread: int) -> L.LayerPaintParams:
+    stops = [(int(off), tuple(int(v) for v in rgba)) for off, rgba in stops]
+    if not 1 <= len(stops) <= L.FR_GRADIENT_MAX_STOPS:
+        raise ValueError(f"{len(stops)} gradient stops: expected 1 .. {L.FR_GRADIENT_MAX_STOPS}")
+    if not all(0 <= off < 2 ** 32 and len(rgba) == 4 and all(0 <= v <= 255 for v in rgba) for off, rgba in stops):
+        raise ValueError(f"gradient stops {stops!r}: expected (offset, (R, G, B, A)) with bytes in [0, 255]")
+    if not all(-2 ** 31 <= int(v) < 2 ** 31 for v in geometry):
+        raise ValueError(f"gradient geometry {tuple(geometry)!r}: a value beyond int32 in 1/64 pixel")
+    p = L.LayerPaintParams(kind=kind, spread=int(spread), n_stops=len(stops))
+    p.x0, p.y0, p.x1, p.y1 = (int(v) for v in geometry)
+    for i, (off, rgba) in enumerate(stops):
+        p.stops[i] = L.GradientStop(off, (C.c_uint8 * 4)(*rgba))
+    return p
+
+
+def make_gradient_linear(x0: int, y0: int, x1: int, y1: int, stops, spread: int = L.FR_SPREAD_PAD) -> L.LayerPaintParams:
+    """a linear gradient from (x0, y0) to (x1, y1), in 1/64 pixel of the destination image, y down -> the gradient part of
+    an fr_layer_paint_params (layer_paint fills in the window and the position).  stops: 1 .. 8 of (offset, (R, G, B, A)),
+    offset in 0 .. 65536 and not decreasing, the colour straight; spread: FR_SPREAD_PAD, _REPEAT or _REFLECT."""
+    return _gradient(L.FR_GRADIENT_LINEAR, (x0, y0, x1, y1), stops, spread)
+
+
+def make_gradient_radial(cx: int, cy: int, r: int, stops, spread: int = L.FR_SPREAD_PAD) -> L.LayerPaintParams:
+    """a radial gradient around (cx, cy) that reaches offset 65536 at radius r, in 1/64 pixel of the destination image
+    -> the gradient part of an fr_layer_paint_params; stops and spread as for make_gradient_linear"""
+    return _gradient(L.FR_GRADIENT_RADIAL, (cx, cy, r, 0), stops, spread)
 
 
 def _table(rows, dtype):
@@ -51,6 +79,22 @@ def layer_rects(ctx: Context, dst_ptr: int, dst_stride_px: int, dst_rows: int, r
     r, n = _table(rects, RECT_DTYPE)
     L.check(ctx._lib.fr_layer_rects(ctx._h, C.c_void_p(dst_ptr), dst_stride_px, dst_rows, None if r is None else L.ptr(r), n,
                                     _flags(flags, srgb)))
+
+
+def layer_paint(ctx: Context, src_ptr, src_stride_px: int, src_rows: int, dst_ptr: int, dst_stride_px: int, dst_rows: int,
+                gradient, window, dst=(0, 0), srgb: bool = False, flags: int = 0) -> None:
+    """fr_layer_paint: `gradient` (make_gradient_linear / make_gradient_radial) composited over the premultiplied image at
+    device address dst_ptr through the alpha of the window = (src_x, src_y, w, h) of the layer at src_ptr, with the window's
+    top-left pixel at dst = (dst_x, dst_y); src_ptr None or 0 (with src_stride_px = src_rows = 0 and a window at (0, 0)):
+    full coverage, a gradient panel of w x h.  Strides and rows in pixels; asynchronous on the context's stream.  srgb:
+    FR_LAYER_SRGB, composite in linear light.  gradient None passes a NULL parameter block (refused)."""
+    p = None
+    if gradient is not None:
+        p = L.LayerPaintParams.from_buffer_copy(gradient)           # the caller's gradient stays as it is
+        p.src_x, p.src_y, p.w, p.h = (int(v) for v in window)
+        p.dst_x, p.dst_y = int(dst[0]), int(dst[1])
+    L.check(ctx._lib.fr_layer_paint(ctx._h, C.c_void_p(src_ptr or None), src_stride_px, src_rows, C.c_void_p(dst_ptr), dst_stride_px, dst_rows,
+                                    None if p is None else C.byref(p), _flags(flags, srgb)))
 
 
 def layer_unpremultiply(ctx: Context, ptr: int, stride_px: int, w: int, h: int, srgb: bool = False) -> None:

@@ -697,8 +697,8 @@ int fr_rgba_unpremultiply(uint8_t *rgba, size_t n_pixels, int srgb);
  *     all blits of the call, behind a small kernel that brings the call's tile table into device memory; asynchronous on
  *     the context's stream, in stream order after earlier renders as fr_plan_render is; the caller may reuse `blits` as
  *     soon as the call returns.
- * FR_LAYER_SRGB is the flag space of fr_layer_over, fr_layer_shadow and fr_layer_rects: no other entry point knows it, and these know
- * none of the FR_TEXT_ / FR_FILL_ flags.                                                                                        */
+ * FR_LAYER_SRGB is the flag space of fr_layer_over, fr_layer_shadow, fr_layer_rects and fr_layer_paint: no other entry point knows
+ * it, and these know none of the FR_TEXT_ / FR_FILL_ flags.                                                                     */
 #define FR_LAYER_SRGB 1u
 
 typedef struct fr_layer_blit {
@@ -825,6 +825,92 @@ typedef struct fr_layer_rect {
 
 int fr_layer_rects(fr_ctx *ctx, void *dst_dev, size_t dst_stride_px, size_t dst_rows,
                    const fr_layer_rect *rects, uint32_t n_rects, uint32_t flags);   /* 0 or FR_LAYER_SRGB */
+
+/* ---- linear and radial gradients through a layer's alpha (BUILD-DEFINED; DESIGN.md sections 4.11 and 5) --------------------
+ * fr_layer_paint composites one gradient over a premultiplied image on the device, either through the alpha of a window
+ * of a layer (gradient text; a gradient glow when the layer is a shadow) or, with src_dev = NULL, through full coverage
+ * (a gradient panel).  Both images are what fr_layer_over's are; m, D and E as above.  All arithmetic is in integers.
+ *   rdiv(n, d) = floor((2 n + d) / (2 d)) for d > 0 and n of either sign, in exact integers (floor throughout: a half-way
+ *   case rounds up, also below zero).
+ *   Coverage: destination pixel (X, Y) = (dst_x + u, dst_y + v), 0 <= u < w, 0 <= v < h, is drawn with cov = the alpha byte
+ *     of layer pixel (src_x + u, src_y + v); with src_dev = NULL, cov = 255.  Only alpha is read from the layer, and
+ *     nothing outside the window.  The rectangle is clipped to [0, dst_stride_px) x [0, dst_rows) as a blit of
+ *     fr_layer_over is; a rectangle clipped away entirely is valid.
+ *   Gradient parameter t, a signed 64-bit integer, 65536 to one gradient length, taken at the pixel's centre.  The four
+ *     geometry values x0, y0, x1, y1 are in 1/64 pixel of the DESTINATION image, y down.
+ *     FR_GRADIENT_LINEAR, from (x0, y0) to (x1, y1): dx = x1 - x0, dy = y1 - y0, L2 = dx^2 + dy^2,
+ *         TX = rdiv(64 dx 2^32, L2),  TY = rdiv(64 dy 2^32, L2),  T0 = rdiv(((32 - x0) dx + (32 - y0) dy) 2^32, L2)
+ *         t  = (T0 + X TX + Y TY) >> 16                            (arithmetic shift; the sum stays below 2^60)
+ *       For X, Y < 32768, t differs from floor(65536 * the exact projection) by at most 1; it is exact where TX, TY and T0
+ *       are (dyadic gradients).
+ *     FR_GRADIENT_RADIAL, centre (x0, y0), radius r = x1 (y1 must be 0):
+ *         ddx = 64 X + 32 - x0,  ddy = 64 Y + 32 - y0,  s = isqrt((ddx^2 + ddy^2) 256)        (the floor square root)
+ *         R = rdiv(2^60, r),  t = floor(s R / 2^48)                                           (the full 128-bit product)
+ *       |t - floor(65536 dist / r)| <= 1 + 4096 / r.
+ *   Spread, t -> u in 0 .. 65535: FR_SPREAD_PAD: u = clamp(t, 0, 65535).  FR_SPREAD_REPEAT: u = t mod 65536 (floor mod).
+ *     FR_SPREAD_REFLECT: v = t mod 131072, u = v < 65536 ? v : 131071 - v.
+ *   Colour: a table G[0 .. 1023] of straight R G B A, built on the host.  Entry k is the gradient at q = 64 k + 32: stop 0
+ *     if q < off[0]; stop n - 1 if q >= off[n - 1]; else with i the largest index with off[i] <= q (equal offsets make a
+ *     hard edge, the later stop wins), wd = off[i + 1] - off[i], f = q - off[i], each of the four channels is
+ *         (c_i (wd - f) + c_{i+1} f + wd div 2) div wd
+ *     on the stored 8-bit straight values, in both colour spaces.  A pixel's colour is (R, G, B, A) = G[u >> 6].
+ *   Composite: fr_layer_rects' with a = m(cov, A) and C the table colour; a = 0 leaves the pixel byte-identical.
+ *   Consequences:
+ *     1. One stop (R, G, B, A), src_dev = NULL: the bytes of fr_layer_rects with the pixel-aligned rectangle
+ *        (64 dst_x, 64 dst_y, 64 (dst_x + w), 64 (dst_y + h)) of that colour, in both spaces.
+ *     2. One stop and a layer, flags = 0: the bytes of fr_layer_shadow (no stage, that colour) of the window into a cleared
+ *        layer, composited by fr_layer_over at o = 255.  Not promised with FR_LAYER_SRGB, for the reason given at
+ *        fr_layer_rects' consequence 3.
+ *     3. Over a (0, 0, 0, 0) destination the result is a valid premultiplied layer: the gradient-filled text, ready for
+ *        fr_layer_over.
+ *     4. Adding (64, 64) to the geometry's points (a radius stays) and (1, 1) to (dst_x, dst_y) moves the image by one
+ *        pixel: exactly for a radial gradient and for a linear one whose TX, TY and T0 are exact; else t may move within
+ *        its bound.
+ *     5. A horizontal linear gradient (dy = 0) gives identical rows.  A radial one is symmetric about its centre when the
+ *        centre is a pixel centre or a pixel corner.
+ *     6. No destination byte is read or written outside the clipped rectangle (inside it a pixel may be read and written
+ *        back unchanged); no layer byte is written; a pixel with cov = 0 or A = 0 is byte-identical.
+ *   Validation, in this order.  FR_E_INVALID: NULL ctx; an unknown flag bit; a NULL or not 4-byte aligned dst_dev, or
+ *     dst_stride_px beyond 2^26; with src_dev: not 4-byte aligned, or src_stride_px beyond 2^26; with src_dev = NULL: a
+ *     non-zero src_stride_px or src_rows.  FR_E_UNSUPPORTED: an image of 2^31 rows or more.  FR_E_INVALID: NULL `paint`;
+ *     with src_dev: a window of non-zero area that is not inside the layer; with src_dev = NULL: a non-zero src_x or
+ *     src_y; an unknown kind or spread; n_stops outside 1 .. 8; an offset above 65536, or one below the offset before it;
+ *     linear with L2 = 0; radial with r <= 0 or y1 != 0; overlapping byte ranges of the two images.  FR_E_UNSUPPORTED: a
+ *     geometry value with |v| > 2^26; L2 < 4096 or r < 64 (a gradient shorter than one pixel); radial with |ddx| or
+ *     |ddy| >= 2^27 at a corner pixel of the clipped rectangle; a clipped rectangle of more than 2^22 tiles of 256 x 16
+ *     pixels.  w = 0 or h = 0 is valid and launches nothing.
+ *   Execution: one launch of layer_paint_kernel<srgb, kind, layer or none>, one workgroup per 256 x 16 tile of the clipped
+ *     rectangle, behind the small kernel that brings the call's colour table into device memory.  The destination is
+ *     loaded only where some pixel of a lane's four has 0 < a < 255 and stored only where one has a != 0.  Asynchronous
+ *     on the context's stream, in stream order with renders and the other layer calls; the caller may reuse `paint` as
+ *     soon as the call returns.                                                                                            */
+#define FR_GRADIENT_LINEAR 0u
+#define FR_GRADIENT_RADIAL 1u
+#define FR_SPREAD_PAD      0u
+#define FR_SPREAD_REPEAT   1u
+#define FR_SPREAD_REFLECT  2u
+#define FR_GRADIENT_MAX_STOPS 8
+
+typedef struct fr_gradient_stop {
+    uint32_t offset;          /* 0 .. 65536, not below the stop before it */
+    uint8_t  rgba[4];         /* straight R G B A */
+} fr_gradient_stop;
+
+typedef struct fr_layer_paint_params {
+    uint32_t src_x, src_y;    /* top-left of the window in the layer, pixels (0 with src_dev = NULL)   */
+    uint32_t w, h;            /* the rectangle's size; 0 x anything is valid and does nothing           */
+    int32_t  dst_x, dst_y;    /* where that top-left lands in the destination; may be negative          */
+    uint32_t kind;            /* FR_GRADIENT_LINEAR or FR_GRADIENT_RADIAL                               */
+    uint32_t spread;          /* FR_SPREAD_PAD, _REPEAT or _REFLECT                                     */
+    int32_t  x0, y0, x1, y1;  /* linear: from (x0, y0) to (x1, y1); radial: centre (x0, y0), radius x1,
+                                 y1 = 0.  1/64 pixel of the destination, y down                         */
+    uint32_t n_stops;         /* 1 .. FR_GRADIENT_MAX_STOPS                                             */
+    fr_gradient_stop stops[FR_GRADIENT_MAX_STOPS];
+} fr_layer_paint_params;
+
+int fr_layer_paint(fr_ctx *ctx, const void *src_dev, size_t src_stride_px, size_t src_rows,
+                   void *dst_dev, size_t dst_stride_px, size_t dst_rows,
+                   const fr_layer_paint_params *paint, uint32_t flags);   /* 0 or FR_LAYER_SRGB */
 
 /* ---- self-test: exhaustive device-side check of an arithmetic shortcut ----------
  * The render kernel computes t = num / d (render_glyph.zig:51,60-61; d an integer, |d| <= 2^17)
