@@ -38,8 +38,12 @@ pub const FR_TEXT_LOAD: u32 = 32;
 pub const FR_TEXT_CACHE: u32 = 128;
 /// flag of the RGBA text plan entry points (fr_raster.h): source-over alpha, a premultiplied output
 pub const FR_TEXT_OVER: u32 = 256;
-/// the flag space of fr_layer_over, fr_layer_shadow, fr_layer_rects and fr_layer_paint (fr_raster.h): composite in linear light
+/// the flag space of fr_layer_over, fr_layer_shadow, fr_layer_rects, fr_layer_paint and fr_layer_lcd (fr_raster.h): composite in linear light
 pub const FR_LAYER_SRGB: u32 = 1;
+/// fr_layer_lcd alone, beside FR_LAYER_SRGB: memory byte b takes sub-pixel 2 - b (a B G R panel); the other layer calls refuse it
+pub const FR_LCD_BGR: u32 = 2;
+/// the length of fr_layer_lcd's filter
+pub const FR_LCD_TAPS = 5;
 /// LayerPaintParams.kind and .spread (fr_raster.h: fr_layer_paint)
 pub const FR_GRADIENT_LINEAR: u32 = 0;
 pub const FR_GRADIENT_RADIAL: u32 = 1;
@@ -157,6 +161,18 @@ pub const LayerPaintParams = extern struct {
     stops: [FR_GRADIENT_MAX_STOPS]GradientStop,
 };
 
+/// one window of fr_layer_lcd's coverage plane and where it lands: src_x in plane elements (three per pixel), w and h in
+/// destination pixels, the text colour straight
+pub const LcdBlit = extern struct {
+    src_x: u32,
+    src_y: u32,
+    w: u32,
+    h: u32,
+    dst_x: i32,
+    dst_y: i32,
+    rgba: [4]u8,
+};
+
 /// fr_font_line_metrics: hhea, post and OS/2 in font units, y up; present bit 0: post, bit 1: OS/2
 pub const FontLine = extern struct {
     ascender: i16,
@@ -269,6 +285,8 @@ pub extern "c" fn fr_layer_shadow(ctx: *Ctx, src_dev: *const anyopaque, src_stri
 pub extern "c" fn fr_layer_rects(ctx: *Ctx, dst_dev: *anyopaque, dst_stride_px: usize, dst_rows: usize, rects: ?[*]const LayerRect, n_rects: u32, flags: u32) c_int;
 /// a linear or radial gradient composited over a premultiplied image through the alpha of a layer's window (src_dev null: full coverage)
 pub extern "c" fn fr_layer_paint(ctx: *Ctx, src_dev: ?*const anyopaque, src_stride_px: usize, src_rows: usize, dst_dev: *anyopaque, dst_stride_px: usize, dst_rows: usize, paint: *const LayerPaintParams, flags: u32) c_int;
+/// sub-pixel (LCD) text: windows of a 3x-wide coverage plane filtered across sub-pixels (weights: FR_LCD_TAPS values adding up to 256, null: the default) and composited with an alpha per colour byte
+pub extern "c" fn fr_layer_lcd(ctx: *Ctx, cov_dev: *const anyopaque, cov_stride: usize, cov_rows: usize, dst_dev: *anyopaque, dst_stride_px: usize, dst_rows: usize, blits: ?[*]const LcdBlit, n_blits: u32, weights: ?*const [FR_LCD_TAPS]u16, flags: u32) c_int;
 // ---- self-tests of the two arithmetic shortcuts (device-side, exhaustive)
 pub extern "c" fn fr_selftest_division(d_lo: u32, d_hi: u32, mismatches: *u64, bad_divisor: ?*u32, bad_x_bits: ?*u32) c_int;
 pub extern "c" fn fr_selftest_sqrt(mismatches: *u64, bad_x_bits: ?*u32) c_int;

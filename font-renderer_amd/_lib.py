@@ -14,6 +14,8 @@ FR_TEXT_LOAD = 32                  # fr_text_plan_create_rgba only: draw over th
 FR_TEXT_CACHE = 128                # the upright and _ex text plans: each distinct glyph image made once per render, same bytes
 FR_TEXT_OVER = 256                 # the RGBA text plans: source-over alpha (a premultiplied output) instead of alpha replaced
 FR_LAYER_SRGB = 1                  # the flag space of the fr_layer_over / _shadow / _rects / _paint calls: work in linear light
+FR_LCD_BGR = 2                     # fr_layer_lcd alone, beside FR_LAYER_SRGB: memory byte b takes sub-pixel 2 - b
+FR_LCD_TAPS = 5                    # the length of fr_layer_lcd's filter
 FR_GRADIENT_LINEAR, FR_GRADIENT_RADIAL = 0, 1                   # fr_layer_paint_params.kind
 FR_SPREAD_PAD, FR_SPREAD_REPEAT, FR_SPREAD_REFLECT = 0, 1, 2    # fr_layer_paint_params.spread
 FR_GRADIENT_MAX_STOPS = 8
@@ -65,6 +67,11 @@ class TextRun(C.Structure):      # == fr_text_run
 class LayerBlit(C.Structure):    # == fr_layer_blit
     _fields_ = [("src_x", C.c_uint32), ("src_y", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32),
                 ("dst_x", C.c_int32), ("dst_y", C.c_int32), ("opacity", C.c_uint32)]
+
+
+class LcdBlit(C.Structure):      # == fr_lcd_blit
+    _fields_ = [("src_x", C.c_uint32), ("src_y", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32),
+                ("dst_x", C.c_int32), ("dst_y", C.c_int32), ("rgba", C.c_uint8 * 4)]
 
 
 class LayerShadowParams(C.Structure):    # == fr_layer_shadow_params
@@ -171,6 +178,7 @@ SYMBOLS = [
     ("fr_layer_shadow", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.POINTER(LayerShadowParams), C.c_uint32]),
     ("fr_layer_rects", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_uint32, C.c_uint32]),
     ("fr_layer_paint", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.POINTER(LayerPaintParams), C.c_uint32]),
+    ("fr_layer_lcd", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, _P, C.c_uint32, C.POINTER(C.c_uint16), C.c_uint32]),
     ("fr_selftest_sqrt", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     ("fr_selftest_division", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("fr_selftest_row_cuts", C.c_int, [_P, _P, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),

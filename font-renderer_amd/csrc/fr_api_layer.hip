@@ -1,10 +1,12 @@
-// fr_api_layer.hip — C ABI (include/fr_raster.h): fr_layer_over, fr_layer_unpremultiply, fr_layer_shadow, fr_layer_rects and
-// fr_layer_paint.  The checks, the clipping and the tile table are fr_layer_plan.cpp's, the shadow's stages
+// fr_api_layer.hip — C ABI (include/fr_raster.h): fr_layer_over, fr_layer_unpremultiply, fr_layer_shadow, fr_layer_rects,
+// fr_layer_paint and fr_layer_lcd.  The checks, the clipping and the tile table are fr_layer_plan.cpp's, the shadow's stages
 // fr_layer_shadow_plan.cpp's, the rectangles' tables fr_layer_rects_plan.cpp's, the gradient's coefficients and colour table
-// fr_layer_paint_plan.cpp's; this unit stages the tables, keeps the shadow's planes and launches the kernels of fr_layer.hip,
-// fr_layer_shadow.hip, fr_layer_rects.hip and fr_layer_paint.hip.
+// fr_layer_paint_plan.cpp's, the sub-pixel blits' tiles fr_layer_lcd_plan.cpp's; this unit stages the tables, keeps the
+// shadow's planes and launches the kernels of fr_layer.hip, fr_layer_shadow.hip, fr_layer_rects.hip, fr_layer_paint.hip and
+// fr_layer_lcd.hip.
 #include "fr_internal.hpp"
 #include "fr_layer.hpp"
+#include "fr_layer_lcd.hpp"
 #include "fr_layer_paint.hpp"
 #include "fr_layer_rects.hpp"
 #include "fr_layer_shadow.hpp"
@@ -218,6 +220,30 @@ int fr_layer_paint(fr_ctx *ctx, const void *src_dev, size_t src_stride_px, size_
                           src_stride_px, dst_stride_px, p.x0, p.x1, p.y0, p.y1, p.tx0, p.tiles_x, p.sx0, p.sy,
                           (p.dst_vec ? fr::LAYER_DST_VEC : 0u) | (p.src_vec ? fr::LAYER_SRC_VEC : 0u), paint->spread, {p.c[0], p.c[1], p.c[2]}};
     HIP_TRY(fr::launch_layer_paint((flags & FR_LAYER_SRGB) != 0, paint->kind == FR_GRADIENT_RADIAL, p.tiles_x * p.tiles_y, a, ctx->stream));
+    return FR_OK;
+}
+
+int fr_layer_lcd(fr_ctx *ctx, const void *cov_dev, size_t cov_stride, size_t cov_rows, void *dst_dev, size_t dst_stride_px, size_t dst_rows,
+                 const fr_lcd_blit *blits, uint32_t n_blits, const uint16_t *weights, uint32_t flags)
+{
+    if (!ctx) return fail(FR_E_INVALID, "fr_layer_lcd: ctx is NULL");
+    fr::LcdTables t;
+    try {
+        const fr::LcdIn in{(uintptr_t)cov_dev, (uintptr_t)dst_dev, cov_stride, cov_rows, dst_stride_px, dst_rows, blits, n_blits, weights, flags};
+        if (const int rc = fr::layer_lcd_tables(in, t)) return rc;
+    } catch (const std::bad_alloc &) {
+        return fail(FR_E_NOMEM, "fr_layer_lcd: host allocation");
+    }
+    const size_t n = t.tiles.size();
+    if (!n) return FR_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    // the tiles, each with its blit's colour and window, go through the staging; the filter is a kernel argument
+    static_assert(sizeof(fr::LcdTile) == 3 * sizeof(uint4), "a tile is three units of the staging");
+    const uint4 *tab = nullptr;
+    if (const int rc = layer_tables_to_device(ctx, 3 * n, &tab, [&](uint4 *to) { memcpy(to, t.tiles.data(), n * sizeof(fr::LcdTile)); })) return rc;
+    const fr::LcdArgs a{reinterpret_cast<const fr::LcdTile *>(tab), static_cast<const uint8_t *>(cov_dev), static_cast<uint32_t *>(dst_dev), cov_stride, dst_stride_px,
+                        {t.w[0], t.w[1], t.w[2], t.w[3], t.w[4]}, (flags & FR_LCD_BGR) ? 1u : 0u};
+    HIP_TRY(fr::launch_layer_lcd((flags & FR_LAYER_SRGB) != 0, (uint32_t)n, a, ctx->stream));
     return FR_OK;
 }
 

@@ -29,34 +29,16 @@ int layer_tables(const LayerIn &in, LayerTables &out)
         if ((uint64_t)bl.src_x + bl.w > in.src_stride || (uint64_t)bl.src_y + bl.h > in.src_rows)
             return set_error(FR_E_INVALID, "blit %u: %u x %u at (%u, %u) leaves the layer of %zu x %zu", b, bl.w, bl.h, bl.src_x, bl.src_y,
                              in.src_stride, in.src_rows);
-        // clip to [0, dst_stride) x [0, dst_rows)
-        const int64_t x0 = std::max<int64_t>(bl.dst_x, 0), y0 = std::max<int64_t>(bl.dst_y, 0);
-        const int64_t x1 = std::min<int64_t>((int64_t)bl.dst_x + bl.w, (int64_t)in.dst_stride);
-        const int64_t y1 = std::min<int64_t>((int64_t)bl.dst_y + bl.h, (int64_t)in.dst_rows);
-        if (x0 >= x1 || y0 >= y1) continue;                    // nothing of it is visible: valid
-        c = LayerClip{(uint32_t)x0, (uint32_t)y0, (uint32_t)x1, (uint32_t)y1, (uint32_t)(bl.src_x + (x0 - bl.dst_x)),
-                      (uint32_t)(bl.src_y + (y0 - bl.dst_y))};
-        out.pixels += (uint64_t)(x1 - x0) * (uint64_t)(y1 - y0);
+        c = layer_clip(bl.src_x, bl.src_y, bl.w, bl.h, bl.dst_x, bl.dst_y, in.dst_stride, in.dst_rows);
+        if (c.x0 >= c.x1) continue;                            // nothing of it is visible: valid
+        out.pixels += (uint64_t)(c.x1 - c.x0) * (uint64_t)(c.y1 - c.y0);
         if (bl.opacity == 0u) continue;                        // leaves every pixel as it is: no tile
         if (bl.opacity != 255u) out.opacity = true;
-        const uint32_t tx0 = c.x0 & ~(LAYER_LANE_PX - 1);
-        n_tiles += (uint64_t)((c.x1 - tx0 + LAYER_TILE_W - 1) / LAYER_TILE_W) * ((c.y1 - c.y0 + LAYER_TILE_H - 1) / LAYER_TILE_H);
+        n_tiles += layer_clip_tiles(c);
     }
     if (n_tiles > LAYER_MAX_TILES) return set_error(FR_E_UNSUPPORTED, "the blits need more than 2^22 tiles; split the call");
-    // the clipped rectangles own their pixels: no two may overlap (sweep down the rows, as for text runs)
-    {
-        std::vector<uint32_t> ord;
-        for (uint32_t b = 0; b < in.n_blits; ++b)
-            if (out.clips[b].x0 < out.clips[b].x1) ord.push_back(b);
-        std::sort(ord.begin(), ord.end(), [&](uint32_t p, uint32_t q) { return out.clips[p].y0 < out.clips[q].y0; });
-        for (size_t i = 0; i < ord.size(); ++i) {
-            const LayerClip &A = out.clips[ord[i]];
-            for (size_t j = i + 1; j < ord.size() && out.clips[ord[j]].y0 < A.y1; ++j) {
-                const LayerClip &B = out.clips[ord[j]];
-                if (B.x0 < A.x1 && A.x0 < B.x1) return set_error(FR_E_INVALID, "blits %u and %u overlap in the destination", ord[i], ord[j]);
-            }
-        }
-    }
+    // the clipped rectangles own their pixels: no two may overlap
+    if (uint32_t p, q; layer_clips_overlap(out.clips, p, q)) return set_error(FR_E_INVALID, "blits %u and %u overlap in the destination", p, q);
     out.tiles.reserve((size_t)n_tiles);
     for (uint32_t b = 0; b < in.n_blits; ++b) {
         const LayerClip &c = out.clips[b];
@@ -65,9 +47,7 @@ int layer_tables(const LayerIn &in, LayerTables &out)
         const uint32_t tx0 = c.x0 & ~(LAYER_LANE_PX - 1);
         const int32_t sx0 = (int32_t)c.sx - (int32_t)(c.x0 - tx0);             // the layer column of tx0
         const uint32_t ov = o | (dvec ? LAYER_DST_VEC : 0u) | (svec && !(sx0 & (int32_t)(LAYER_LANE_PX - 1)) ? LAYER_SRC_VEC : 0u);
-        for (uint32_t y = c.y0; y < c.y1; y += LAYER_TILE_H)
-            for (uint32_t x = tx0; x < c.x1; x += LAYER_TILE_W)
-                out.tiles.push_back(LayerTile{x, y, c.x0, c.x1, c.y1, sx0 + (int32_t)(x - tx0), c.sy + (y - c.y0), ov});
+        layer_each_tile(c, [&](uint32_t x, uint32_t y) { out.tiles.push_back(LayerTile{x, y, c.x0, c.x1, c.y1, sx0 + (int32_t)(x - tx0), c.sy + (y - c.y0), ov}); });
     }
     return FR_OK;
 }

@@ -4,6 +4,7 @@
 #pragma once
 #include "../../include/fr_raster.h"
 
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <vector>
@@ -47,6 +48,52 @@ struct LayerClip {
     uint32_t x0, y0, x1, y1;
     uint32_t sx, sy;
 };
+
+// The w x h rectangle at (dst_x, dst_y) clipped to [0, dst_stride) x [0, dst_rows), showing its source from (src_x, src_y);
+// empty when w or h is 0 or nothing of it is visible.  (fr_layer_lcd passes src_x = 0: sx is then the window's pixel column.)
+inline LayerClip layer_clip(uint32_t src_x, uint32_t src_y, uint32_t w, uint32_t h, int32_t dst_x, int32_t dst_y, size_t dst_stride, size_t dst_rows)
+{
+    if (!w || !h) return LayerClip{0, 0, 0, 0, 0, 0};
+    const int64_t x0 = std::max<int64_t>(dst_x, 0), y0 = std::max<int64_t>(dst_y, 0);
+    const int64_t x1 = std::min<int64_t>((int64_t)dst_x + w, (int64_t)dst_stride);
+    const int64_t y1 = std::min<int64_t>((int64_t)dst_y + h, (int64_t)dst_rows);
+    if (x0 >= x1 || y0 >= y1) return LayerClip{0, 0, 0, 0, 0, 0};
+    return LayerClip{(uint32_t)x0, (uint32_t)y0, (uint32_t)x1, (uint32_t)y1, (uint32_t)(src_x + (x0 - dst_x)), (uint32_t)(src_y + (y0 - dst_y))};
+}
+
+// the clipped rectangles own their pixels: whether two of them overlap, and which (a sweep down the rows, as for text runs)
+inline bool layer_clips_overlap(const std::vector<LayerClip> &clips, uint32_t &first, uint32_t &second)
+{
+    std::vector<uint32_t> ord;
+    for (uint32_t b = 0; b < clips.size(); ++b)
+        if (clips[b].x0 < clips[b].x1) ord.push_back(b);
+    std::sort(ord.begin(), ord.end(), [&](uint32_t p, uint32_t q) { return clips[p].y0 < clips[q].y0; });
+    for (size_t i = 0; i < ord.size(); ++i) {
+        const LayerClip &A = clips[ord[i]];
+        for (size_t j = i + 1; j < ord.size() && clips[ord[j]].y0 < A.y1; ++j) {
+            const LayerClip &B = clips[ord[j]];
+            if (B.x0 < A.x1 && A.x0 < B.x1) {
+                first = ord[i], second = ord[j];
+                return true;
+            }
+        }
+    }
+    return false;
+}
+
+// the tiles of a clipped rectangle that is not empty: their number, and f(x, y) for each, rows of tiles top to bottom, left
+// to right, the first at (x0 rounded down to LAYER_LANE_PX, y0)
+inline uint64_t layer_clip_tiles(const LayerClip &c)
+{
+    const uint32_t tx0 = c.x0 & ~(LAYER_LANE_PX - 1);
+    return (uint64_t)((c.x1 - tx0 + LAYER_TILE_W - 1) / LAYER_TILE_W) * ((c.y1 - c.y0 + LAYER_TILE_H - 1) / LAYER_TILE_H);
+}
+template <class F>
+inline void layer_each_tile(const LayerClip &c, F f)
+{
+    for (uint32_t y = c.y0; y < c.y1; y += LAYER_TILE_H)
+        for (uint32_t x = c.x0 & ~(LAYER_LANE_PX - 1); x < c.x1; x += LAYER_TILE_W) f(x, y);
+}
 
 struct LayerTables {
     std::vector<LayerClip> clips;      // one per blit, in the caller's order

@@ -1,5 +1,6 @@
 // fr_layer_px.hpp — source-over of one premultiplied pixel, for the kernels that composite onto an image: layer_over_kernel
-// (fr_layer.hip), layer_rects_kernel (fr_layer_rects.hip) and layer_paint_kernel (fr_layer_paint.hip).  The arithmetic is that of the text plans' colour body
+// (fr_layer.hip), layer_rects_kernel (fr_layer_rects.hip) and layer_paint_kernel (fr_layer_paint.hip), and its variant with
+// one alpha per colour byte for layer_lcd_kernel (fr_layer_lcd.hip).  The arithmetic is that of the text plans' colour body
 // (fr_text_colour.hpp), per pixel instead of per sample.
 #pragma once
 #include "fr_text_colour.hpp"
@@ -48,6 +49,27 @@ __device__ __forceinline__ uint32_t over_px(uint32_t s, uint32_t d, uint32_t o, 
         }
         return (out >> 8) | (r1a & 0x00ff0000u) << 8;          // alpha is stored linearly
     }
+}
+
+// The definition of fr_layer_lcd for one pixel, component alpha: colour byte b of the straight colour over d through an
+// alpha al[b] of its own; the pixel's alpha through the largest of the three.  cl[b]: the colour's byte b, or D of it in
+// linear light.  al = (0, 0, 0) gives d (E(D[v]) = v), and with al = (255, 255, 255) no bit of d reaches the result.
+template <int SRGB>
+__device__ __forceinline__ uint32_t over_px_ca(const uint32_t (&cl)[3], uint32_t d, const uint32_t (&al)[3], const uint16_t *D, const uint16_t *K)
+{
+    const uint32_t amax = max(al[0], max(al[1], al[2]));
+    uint32_t out = (amax + m2(d >> 24, 255u - amax)) << 24;    // a_max + m(d_a, 255 - a_max) <= 255
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const uint32_t dc = (d >> (8 * c)) & 0xffu, ia = 255u - al[c];
+        if constexpr (!SRGB) {
+            out |= min(255u, m2(cl[c], al[c]) + m2(dc, ia)) << (8 * c);
+        } else {
+            const uint32_t L = min(65535u, div255_24(cl[c] * al[c] + 127u) + div255_24((uint32_t)D[dc] * ia + 127u));
+            out |= srgb_encode(K, L) << (8 * c);
+        }
+    }
+    return out;
 }
 
 }  // namespace fr

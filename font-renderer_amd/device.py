@@ -65,10 +65,11 @@ def default_context() -> Context:
     return _default_ctx
 
 
-def round_trip(ctx: Context, call, *buffers, back: int = 0) -> np.ndarray:
+def round_trip(ctx: Context, call, *buffers, back=0):
     """The one way host data meets a call on the context's stream.  Each of `buffers` is a uint8 host array, which is
     uploaded, or a shape, for which uninitialised device bytes are allocated; call(*device addresses) then queues its
-    work, and buffers[back] comes back as a host array of the buffer's shape.  The library runs on its own stream, so
+    work, and buffers[back] comes back as a host array of the buffer's shape (back a tuple of indices: a tuple of
+    arrays).  The library runs on its own stream, so
     the order is fixed: torch's uploads are complete before the call is queued (a device-wide synchronise), and the
     context's stream is drained before the copy back (ctx.sync)."""
     import torch
@@ -79,4 +80,6 @@ def round_trip(ctx: Context, call, *buffers, back: int = 0) -> np.ndarray:
     torch.cuda.synchronize(ctx.device)
     call(*(d.data_ptr() for d in dev))
     ctx.sync()
+    if isinstance(back, tuple):
+        return tuple(dev[i].cpu().numpy() for i in back)
     return dev[back].cpu().numpy()

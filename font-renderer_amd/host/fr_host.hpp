@@ -234,6 +234,21 @@ inline void layer_paint(Context &ctx, const DeviceImage &image, const fr_layer_p
 {
     check(fr_layer_paint(ctx.get(), nullptr, 0, 0, image.pixels, image.stride_px, image.rows, &paint, srgb ? FR_LAYER_SRGB : 0u));
 }
+// fr_layer_lcd: sub-pixel (LCD) text.  `plane` is a FR_COVERAGE_U8 render three times as wide as the text (a PlacedText
+// of fr_glyph_place_affine rows with m = {3 s, 0, 0, s} and the pens' x tripled), one byte per element; each blit filters
+// its window across sub-pixels (weights: FR_LCD_TAPS values that add up to 256, or nullptr for the default filter) and
+// composites its colour over the premultiplied `image` with an alpha per colour byte.  bgr: the panel's stripes are B G R.
+// Asynchronous on the context's stream; `blits` and `weights` may be reused at once.
+struct DevicePlane {
+    const void *bytes;
+    size_t stride, rows;
+};
+inline void layer_lcd(Context &ctx, const DevicePlane &plane, const DeviceImage &image, const std::vector<fr_lcd_blit> &blits, const uint16_t *weights = nullptr,
+                      bool srgb = false, bool bgr = false)
+{
+    check(fr_layer_lcd(ctx.get(), plane.bytes, plane.stride, plane.rows, image.pixels, image.stride_px, image.rows, blits.data(), (uint32_t)blits.size(), weights,
+                       (srgb ? FR_LAYER_SRGB : 0u) | (bgr ? FR_LCD_BGR : 0u)));
+}
 
 class PlacedText {
 public:

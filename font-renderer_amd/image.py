@@ -10,7 +10,7 @@ import numpy as np
 from . import _lib as L
 from .device import default_context, round_trip
 from .glyph import GlyphSet
-from .layer import layer_over, layer_paint, layer_rects, layer_shadow, layer_unpremultiply, make_blits, make_rects
+from .layer import layer_lcd, layer_over, layer_paint, layer_rects, layer_shadow, layer_unpremultiply, make_blits, make_lcd_blits, make_rects
 
 
 def q64(v) -> int:
@@ -193,6 +193,28 @@ class RGBA:                     # an RGBA text plan's image (fr_text_plan_create
             return self
         self.data[:] = round_trip(ctx, lambda d, s: layer_paint(ctx, s, mask.width, mask.height, d, self.width, self.height, gradient,
                                                                 (0, 0, mask.width, mask.height), (int(x), int(y)), srgb), dst, src)
+        return self
+
+    def draw_lcd(self, plane: "Gray", x: int = 0, y: int = 0, rgba=(0, 0, 0, 255), weights=None, srgb: bool = False,
+                 bgr: bool = False, ctx=None) -> "RGBA":
+        """fr_layer_lcd, in place: sub-pixel (LCD) text.  `plane` is a coverage image three times as wide as the text it
+        holds (element 3 u + j: sub-pixel j of pixel u; text.lcd_line renders one); it is filtered across sub-pixels with
+        `weights` (FR_LCD_TAPS values that add up to 256; None: the default filter) and composited in the straight colour
+        `rgba` over this premultiplied image with its pixel (0, 0) at (x, y), whole pixels, clipped at the image's edges,
+        with an alpha of its own for each colour byte.  A plane width that is no multiple of 3 loses its last one or two
+        elements.  srgb: the image is premultiplied in linear light; bgr: the panel's stripes are B G R.  Both images are
+        uploaded and this one copied back.  Returns self."""
+        dst = rgba_pixels(self, "RGBA.draw_lcd: image")
+        cov = plane.data
+        if not isinstance(cov, np.ndarray) or cov.dtype != np.uint8 or cov.shape != (plane.width * plane.height,):
+            raise ValueError(f"RGBA.draw_lcd: plane.data must be a ({plane.width * plane.height},) uint8 array")
+        colour = colour_rgba(rgba, alpha_optional=False)
+        if self.width == 0 or self.height == 0 or plane.width < 3 or plane.height == 0:
+            return self
+        ctx = ctx or default_context()
+        blits = make_lcd_blits([(0, 0, plane.width // 3, plane.height, int(x), int(y), colour)])
+        self.data[:] = round_trip(ctx, lambda d, c: layer_lcd(ctx, c, plane.width, plane.height, d, self.width, self.height, blits,
+                                                              weights, srgb, bgr), dst, np.ascontiguousarray(cov))
         return self
 
     def shadow(self, offset=(0, 0), spread: int = 0, blur_radius: int = 0, blur_passes: int = 0, rgba=(0, 0, 0, 255),

@@ -1,6 +1,6 @@
 """The layer calls of the C ABI (fr_layer_*, include/fr_raster.h) on device addresses, and the builders of their tables.
-All of them are asynchronous on the context's stream; RGBA.over / fill_rects / paint / shadow / unpremultiply (image.py) wrap
-them for host images."""
+All of them are asynchronous on the context's stream; RGBA.over / fill_rects / paint / draw_lcd / shadow / unpremultiply
+(image.py) wrap them for host images."""
 from __future__ import annotations
 
 import ctypes as C
@@ -13,6 +13,7 @@ from .device import Context
 
 BLIT_DTYPE = np.dtype(L.LayerBlit)
 RECT_DTYPE = np.dtype(L.LayerRect)
+LCD_BLIT_DTYPE = np.dtype(L.LcdBlit)
 
 
 def make_blits(rows: Sequence) -> np.ndarray:
@@ -23,6 +24,12 @@ def make_blits(rows: Sequence) -> np.ndarray:
 def make_rects(rows: Sequence) -> np.ndarray:
     """rows of (x0, y0, x1, y1, (R, G, B, A)), the edges in 1/64 pixel -> fr_layer_rect array"""
     return np.array([(int(r[0]), int(r[1]), int(r[2]), int(r[3]), tuple(int(v) for v in r[4])) for r in rows], RECT_DTYPE)
+
+
+def make_lcd_blits(rows: Sequence) -> np.ndarray:
+    """rows of (src_x, src_y, w, h, dst_x, dst_y, (R, G, B, A)) -> fr_lcd_blit array: src_x in plane elements (three per
+    pixel), w and h in destination pixels, the colour straight"""
+    return np.array([tuple(int(v) for v in r[:6]) + (tuple(int(v) for v in r[6]),) for r in rows], LCD_BLIT_DTYPE)
 
 
 def _gradient(kind: int, geometry, stops, spread: int) -> L.LayerPaintParams:
@@ -95,6 +102,25 @@ def layer_paint(ctx: Context, src_ptr, src_stride_px: int, src_rows: int, dst_pt
         p.dst_x, p.dst_y = int(dst[0]), int(dst[1])
     L.check(ctx._lib.fr_layer_paint(ctx._h, C.c_void_p(src_ptr or None), src_stride_px, src_rows, C.c_void_p(dst_ptr), dst_stride_px, dst_rows,
                                     None if p is None else C.byref(p), _flags(flags, srgb)))
+
+
+def layer_lcd(ctx: Context, cov_ptr: int, cov_stride: int, cov_rows: int, dst_ptr: int, dst_stride_px: int, dst_rows: int, blits,
+              weights=None, srgb: bool = False, bgr: bool = False, flags: int = 0) -> None:
+    """fr_layer_lcd: sub-pixel (LCD) text.  Windows of the coverage plane at device address cov_ptr (one byte per element,
+    three elements per pixel, rows of cov_stride bytes) filtered across sub-pixels and composited over the premultiplied
+    image at dst_ptr (4 bytes per pixel, alpha last; stride and rows in pixels) with one alpha per colour byte;
+    asynchronous on the context's stream.  blits: an fr_lcd_blit array (make_lcd_blits) or None.  weights: FR_LCD_TAPS
+    values that add up to 256, or None for the default (8, 77, 86, 77, 8).  srgb: FR_LAYER_SRGB, composite in linear light;
+    bgr: FR_LCD_BGR, the panel's stripes are B G R (memory byte b takes sub-pixel 2 - b)."""
+    b, n = _table(blits, LCD_BLIT_DTYPE)
+    w = None
+    if weights is not None:
+        w = [int(v) for v in weights]
+        if len(w) != L.FR_LCD_TAPS or not all(0 <= v <= 65535 for v in w):
+            raise ValueError(f"weights {weights!r}: expected {L.FR_LCD_TAPS} values in [0, 65535]")
+        w = (C.c_uint16 * L.FR_LCD_TAPS)(*w)
+    L.check(ctx._lib.fr_layer_lcd(ctx._h, C.c_void_p(cov_ptr), cov_stride, cov_rows, C.c_void_p(dst_ptr), dst_stride_px, dst_rows,
+                                  None if b is None else L.ptr(b), n, w, _flags(flags, srgb) | (L.FR_LCD_BGR if bgr else 0)))
 
 
 def layer_unpremultiply(ctx: Context, ptr: int, stride_px: int, w: int, h: int, srgb: bool = False) -> None:

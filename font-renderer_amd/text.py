@@ -17,6 +17,7 @@ from . import _lib as L
 from .device import Context, default_context, round_trip
 from .font import Font
 from .image import RGBA, Gray, colour_rgba, q64, rgba_pixels
+from .layer import layer_lcd, make_lcd_blits
 from .render_glyph import DeviceGlyphSet, TextPlan, TextPlanRGBA, make_places, make_places_affine, make_places_ex, make_runs
 
 
@@ -450,3 +451,67 @@ def render_text_rgba_rotated(font: Font, text, font_size: int, angle_deg: float,
         return im
     return _render(ctx, line, int(width), int(height), samples_per_axis, phase, _flags(flags, srgb, bgra, over=over),
                    colours=per_char, clear=clear)
+
+
+# ---- sub-pixel (LCD) text
+
+def lcd_line(font: Font, text, font_size: int, x: float, y: float, width: int, height: int):
+    """The line draw_text_lcd draws, as a coverage plane three times as wide as the image: laid out at `font_size` with the
+    pen origin at image x and the baseline at image y, both kept to 1/64 pixel (floor(64 v + 1/2)), then stretched by 3
+    along x: every placement's matrix is {3 s, 0, 0, s} with s = font_size / units_per_em, and its pen's x is 3 times
+    the image's, in 1/64 plane element, so element 3 u + j of the plane is sub-pixel j of image pixel u.  -> (glyph set,
+    fr_glyph_place_affine places, runs): one run of 3 width x height elements that clips the line, or None for an empty
+    text or image."""
+    if not (math.isfinite(float(x)) and math.isfinite(float(y))):
+        raise ValueError("x / y: expected finite values")
+    _frame(width, height)
+    if 3 * int(width) > 65535:
+        raise ValueError(f"width {width!r}: the plane of 3 x width elements must not be wider than 65535")
+    laid = _layout(font, text, font_size, width == 0 or height == 0)
+    if laid is None:
+        return None
+    gs, local, pens, _ = laid
+    s = float(font_size) / float(font.information.units_per_em)
+    x64, y64 = q64(x), q64(y)
+    places = make_places_affine([(g, 3 * (x64 + p), y64, 3.0 * s, 0.0, 0.0, s) for g, p in zip(local, pens)])
+    return gs, places, make_runs([(0, len(places), 3 * int(width), int(height), 0, 0, 1.0)])
+
+
+def draw_text_lcd(image: RGBA, font: Font, text, font_size: int, x: float, y: float, color=(0, 0, 0, 255), *, weights=None,
+                  samples_per_axis: int = 4, phase: int = L.FR_SAMPLE_CENTER, flags: int = L.FR_FILL_CONSISTENT,
+                  srgb: bool = False, bgr: bool = False, return_plane: bool = False, ctx: Optional[Context] = None):
+    """One line of sub-pixel (LCD) text drawn in place over the premultiplied `image`: the line is rendered once as a
+    coverage plane of 3 width x height elements through the affine text plan (lcd_line; 3 x samples_per_axis sample
+    columns per pixel), and fr_layer_lcd filters it across sub-pixels with `weights` (None: the default filter) and
+    composites `color` with an alpha per colour byte, both on the context's stream with no sync between them.  x, y as
+    draw_text_rgba; the whole colour applies to the whole line.  srgb: the image is premultiplied in linear light; bgr:
+    the panel's stripes are B G R.  FR_FILL_CONSISTENT is the default, as for rotated text.  Returns `image`, or
+    (image, the plane as a Gray) with return_plane."""
+    w, h = image.width, image.height
+    dst = rgba_pixels(image, "draw_text_lcd: image")
+    colour = colour_rgba(color)
+    ctx = ctx or default_context()
+    line = None if len(text) == 0 else lcd_line(font, text, font_size, x, y, w, h)
+    if line is None:
+        return (image, Gray.init(3 * w, h)) if return_plane else image
+    gs, places, runs = line
+    blits = make_lcd_blits([(0, 0, w, h, 0, 0, colour)])
+    with closing(DeviceGlyphSet(ctx, gs)) as dgs, closing(TextPlan(dgs, places, runs, L.FR_COVERAGE_U8, samples_per_axis, phase, flags)) as plan:
+        def call(d, c):
+            plan.render(c, 3 * w, h)
+            layer_lcd(ctx, c, 3 * w, h, d, w, h, blits, weights, srgb, bgr)
+        out, cov = round_trip(ctx, call, dst, (h * 3 * w,), back=(0, 1))
+    image.data[:] = out
+    return (image, Gray(3 * w, h, cov)) if return_plane else image
+
+
+def render_text_lcd(font: Font, text, font_size: int, x: float, y: float, width: int, height: int, color=(0, 0, 0, 255),
+                    background=(255, 255, 255, 255), *, weights=None, samples_per_axis: int = 4, phase: int = L.FR_SAMPLE_CENTER,
+                    flags: int = L.FR_FILL_CONSISTENT, srgb: bool = False, bgr: bool = False, ctx: Optional[Context] = None) -> RGBA:
+    """draw_text_lcd over a new width x height image filled with the premultiplied colour `background`: black text on
+    white by default, what sub-pixel rendering is made for"""
+    _frame(width, height)
+    im = RGBA.init(int(width), int(height))
+    im.data[:] = colour_rgba(background)
+    return draw_text_lcd(im, font, text, font_size, x, y, color, weights=weights, samples_per_axis=samples_per_axis, phase=phase,
+                         flags=flags, srgb=srgb, bgr=bgr, ctx=ctx)

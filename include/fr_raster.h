@@ -697,8 +697,9 @@ int fr_rgba_unpremultiply(uint8_t *rgba, size_t n_pixels, int srgb);
  *     all blits of the call, behind a small kernel that brings the call's tile table into device memory; asynchronous on
  *     the context's stream, in stream order after earlier renders as fr_plan_render is; the caller may reuse `blits` as
  *     soon as the call returns.
- * FR_LAYER_SRGB is the flag space of fr_layer_over, fr_layer_shadow, fr_layer_rects and fr_layer_paint: no other entry point knows
- * it, and these know none of the FR_TEXT_ / FR_FILL_ flags.                                                                     */
+ * FR_LAYER_SRGB is the flag space of fr_layer_over, fr_layer_shadow, fr_layer_rects, fr_layer_paint and fr_layer_lcd: no other
+ * entry point knows it, and these know none of the FR_TEXT_ / FR_FILL_ flags.  (FR_LCD_BGR = 2 is fr_layer_lcd's alone: the
+ * other four refuse it as an unknown bit.)                                                                                      */
 #define FR_LAYER_SRGB 1u
 
 typedef struct fr_layer_blit {
@@ -911,6 +912,74 @@ typedef struct fr_layer_paint_params {
 int fr_layer_paint(fr_ctx *ctx, const void *src_dev, size_t src_stride_px, size_t src_rows,
                    void *dst_dev, size_t dst_stride_px, size_t dst_rows,
                    const fr_layer_paint_params *paint, uint32_t flags);   /* 0 or FR_LAYER_SRGB */
+
+/* ---- sub-pixel (LCD) text from a 3x-wide coverage plane (BUILD-DEFINED; DESIGN.md sections 4.12 and 5) ----------------------
+ * fr_layer_lcd turns a coverage plane sampled at three times the horizontal resolution into per-channel anti-aliased
+ * text over a premultiplied image on the device: a 5-tap FIR across sub-pixels, then a composite with an alpha of its own
+ * for each of the three colour bytes.  The plane comes from the text plans as they are: fr_text_plan_create_affine with
+ * m = {3 s, 0, 0, s}, the pens' x tripled and a run of 3 W x H gives a FR_COVERAGE_U8 plane whose element 3 u + j is
+ * sub-pixel j of pixel u (12 sample columns per pixel at n = 4).  m, D and E as above.  All arithmetic is in integers.
+ *   Plane: cov_rows rows of cov_stride bytes, one byte per element; any byte alignment of cov_dev and any cov_stride.  For
+ *     a blit, c(q, v) is the byte at element src_x + q of row src_y + v for 0 <= q < 3 w and 0 <= v < h, and 0 everywhere
+ *     else: bytes outside the window never influence the result.  Reads stay inside elements [0, cov_stride) of the rows
+ *     src_y .. src_y + h - 1; no plane byte is written.
+ *   Filter: W[0 .. 4] = weights, or (8, 77, 86, 77, 8) when weights is NULL; their sum must be exactly 256.  For window
+ *     pixel (u, v) and sub-pixel j in 0 .. 2, with q = 3 u + j:
+ *         f_j = (sum_i W[i] c(q + i - 2, v) + 128) div 256                                        (0 .. 255)
+ *   Channel map: memory byte b in 0 .. 2 of the destination pixel takes f_b; with FR_LCD_BGR it takes f_{2-b} (in what
+ *     follows f_b is the value byte b takes).  rgba[b] is always the colour of memory byte b: a caller with B G R A
+ *     images swaps rgba[0] and rgba[2], as for the other calls.
+ *   Composite: A = rgba[3], a_b = m(f_b, A); the destination pixel is (d_0, d_1, d_2, d_a).
+ *     flags without FR_LAYER_SRGB:  out_b = min(255, m(rgba[b], a_b) + m(d_b, 255 - a_b))
+ *     with FR_LAYER_SRGB:           out_b = E(min(65535, (D[rgba[b]] a_b + 127) div 255 + (D[d_b] (255 - a_b) + 127) div 255))
+ *     alpha:                        a_max = max(a_0, a_1, a_2),  out_a = a_max + m(d_a, 255 - a_max)
+ *   Geometry: window pixel (u, v) lands on destination pixel (dst_x + u, dst_y + v).  The window must lie inside the
+ *     plane: src_x + 3 w <= cov_stride and src_y + h <= cov_rows.  The destination rectangle is clipped to [0,
+ *     dst_stride_px) x [0, dst_rows) as a blit of fr_layer_over is; a blit clipped away entirely is valid.  Sub-pixels of
+ *     clipped-away pixels still serve as taps.  After clipping, the rectangles of one call must not overlap, nor may the
+ *     byte ranges of plane and image.  Outside the clipped rectangles no image byte is read or written; inside one, a
+ *     pixel may be read and written back unchanged.
+ *   Consequences:
+ *     1. A pixel with a_0 = a_1 = a_2 = 0 is byte-identical, in both spaces.
+ *     2. d_a = 255 stays 255.
+ *     3. With flags = 0, the colour (255, 255, 255, 255) and a destination pixel (0, 0, 0, 255), the result is
+ *        (f_0, f_1, f_2, 255).
+ *     4. A constant run of plane value v filters to v: (256 v + 128) div 256 = v.
+ *     5. With weights = (0, 0, 256, 0, 0) and a plane with c(3 u + j) = k(u) for all j, the bytes are those of
+ *        fr_layer_paint with one stop of that colour through a layer whose alpha is k, in both spaces, with or without
+ *        FR_LCD_BGR.
+ *     6. With flags = 0 a valid premultiplied destination (d_b <= d_a) stays valid: g(a) = a + m(d_a, 255 - a) does not
+ *        decrease with a, and m(C, a_b) <= a_b.
+ *     7. Adding 3 to src_x moves the image by one pixel, adding 1 by one sub-pixel.
+ *     8. FR_LCD_BGR equals swapping bytes 0 and 2 of the image and of the colour before and after the call without it.
+ *     9. One element of 255 alone in a row gives f = (255 W[i] + 128) div 256 on five consecutive sub-pixels (W[4] on the
+ *        first of them).
+ *   Validation, in this order.  FR_E_INVALID: NULL ctx; an unknown flag bit; NULL cov_dev; cov_stride beyond 2^26; a NULL
+ *     or not 4-byte aligned dst_dev; dst_stride_px beyond 2^26.  FR_E_UNSUPPORTED: 2^31 rows or more in either image.
+ *     FR_E_INVALID: NULL blits with n_blits > 0; weights whose sum is not 256; a window of non-zero area that is not
+ *     inside the plane; overlapping clipped rectangles; overlapping byte ranges of plane and image.  FR_E_UNSUPPORTED:
+ *     more than 2^22 tiles of 256 x 16 pixels.  w = 0 or h = 0 is valid; n_blits = 0 launches nothing.
+ *   Execution: one launch of layer_lcd_kernel<srgb> for all blits, one workgroup per 256 x 16 tile, behind the small kernel
+ *     that brings the call's tile table into device memory.  The destination is loaded only where some pixel of a lane's
+ *     four is touched (some a_b != 0) without all three a_b at 255, and stored only where one is touched.  Asynchronous on
+ *     the context's stream, in stream order with renders and the other layer calls; the caller may reuse blits and weights
+ *     as soon as the call returns.
+ * FR_LCD_BGR lives in the flag space of the layer calls, beside FR_LAYER_SRGB, and only fr_layer_lcd knows it: fr_layer_over,
+ * fr_layer_shadow, fr_layer_rects and fr_layer_paint refuse it as an unknown bit.                                             */
+#define FR_LCD_BGR  2u
+#define FR_LCD_TAPS 5
+
+typedef struct fr_lcd_blit {
+    uint32_t src_x, src_y;    /* plane element / row of sub-pixel 0 of window pixel (0, 0)              */
+    uint32_t w, h;            /* size in DESTINATION pixels; the window is 3 w x h plane elements       */
+    int32_t  dst_x, dst_y;    /* where window pixel (0, 0) lands; may be negative                       */
+    uint8_t  rgba[4];         /* the text colour, straight R G B A                                      */
+} fr_lcd_blit;
+
+int fr_layer_lcd(fr_ctx *ctx, const void *cov_dev, size_t cov_stride, size_t cov_rows,
+                 void *dst_dev, size_t dst_stride_px, size_t dst_rows,
+                 const fr_lcd_blit *blits, uint32_t n_blits,
+                 const uint16_t *weights /* FR_LCD_TAPS values, or NULL */, uint32_t flags);
 
 /* ---- self-test: exhaustive device-side check of an arithmetic shortcut ----------
  * The render kernel computes t = num / d (render_glyph.zig:51,60-61; d an integer, |d| <= 2^17)
