@@ -38,6 +38,8 @@ pub const FR_TEXT_LOAD: u32 = 32;
 pub const FR_TEXT_CACHE: u32 = 128;
 /// flag of the RGBA text plan entry points (fr_raster.h): source-over alpha, a premultiplied output
 pub const FR_TEXT_OVER: u32 = 256;
+/// flag of the two _affine text plan entry points (fr_raster.h): FR_TEXT_CACHE for the matrix form, keyed by the bits of m
+pub const FR_TEXT_CACHE_AFFINE: u32 = 512;
 /// the flag space of fr_layer_over, fr_layer_shadow, fr_layer_rects, fr_layer_paint and fr_layer_lcd (fr_raster.h): composite in linear light
 pub const FR_LAYER_SRGB: u32 = 1;
 /// fr_layer_lcd alone, beside FR_LAYER_SRGB: memory byte b takes sub-pixel 2 - b (a B G R panel); the other layer calls refuse it

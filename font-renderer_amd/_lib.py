@@ -13,7 +13,8 @@ FR_TEXT_SRGB, FR_TEXT_BGRA = 8, 4  # flags of fr_text_plan_create_rgba only: lin
 FR_TEXT_LOAD = 32                  # fr_text_plan_create_rgba only: draw over the pixels already in the output
 FR_TEXT_CACHE = 128                # the upright and _ex text plans: each distinct glyph image made once per render, same bytes
 FR_TEXT_OVER = 256                 # the RGBA text plans: source-over alpha (a premultiplied output) instead of alpha replaced
-FR_LAYER_SRGB = 1                  # the flag space of the fr_layer_over / _shadow / _rects / _paint calls: work in linear light
+FR_TEXT_CACHE_AFFINE = 512         # the matrix-form text plans: FR_TEXT_CACHE keyed by (glyph, pen fractions, bits of m), same bytes
+FR_LAYER_SRGB = 1              # the flag space of the fr_layer_over / _shadow / _rects / _paint calls: work in linear light
 FR_LCD_BGR = 2                     # fr_layer_lcd alone, beside FR_LAYER_SRGB: memory byte b takes sub-pixel 2 - b
 FR_LCD_TAPS = 5                    # the length of fr_layer_lcd's filter
 FR_GRADIENT_LINEAR, FR_GRADIENT_RADIAL = 0, 1                   # fr_layer_paint_params.kind

@@ -200,10 +200,9 @@ struct TextSide {
     fr::TextPlan tp;                   // what its launches depend on (fr_text_plan.hpp)
     DevBuf<fr::TextTile> tiles;
     DevBuf<fr::TextRun> runs;
-    DevBuf<unsigned char> insts;
+    DevBuf<unsigned char> insts, mcells;           // the records of tp.form (cached: TextCachedInst), and its mask cells
     DevBuf<uint32_t> list, glyphs, rec_count;
     DevBuf<fr::Rec> recs;
-    DevBuf<fr::TextMaskCell> mcells;
     DevBuf<fr::TextMaskTile> mtiles;
     DevBuf<uint16_t> masks;
 
@@ -218,7 +217,7 @@ struct TextSide {
     // every instance: a text kernel, a direct sum over the glyph's records (fr_text.hip)
     void stats(uint32_t &fast, uint32_t &general) const { fast = 0; general = tp.n_insts; }
     // One render: the records of its glyphs from their points (plan-owned, so a plain plan's records are never touched),
-    // then the text kernel over every tile of every run — two launches in stream order, nothing to fork.  An FR_TEXT_CACHE
+    // then the text kernel over every tile of every run — two launches in stream order, nothing to fork.  An FR_TEXT_CACHE or FR_TEXT_CACHE_AFFINE
     // plan fills its mask cells from the records in between: three launches in stream order.  A plan without tiles has
     // an empty list
     int launch(const fr_plan &p, void *out_dev, size_t out_stride) const
@@ -309,7 +308,8 @@ static int text_plan_upload(const char *fn, fr_plan *p, const fr::TextPlanTables
     s.runs.upload(e, t.runs, st);
     if (cache) {
         s.insts.upload(e, cache->insts, st);
-        s.mcells.upload(e, cache->cells, st);
+        if constexpr (std::is_same<PLACE, fr_glyph_place_affine>::value) s.mcells.upload(e, cache->acells, st);
+        else s.mcells.upload(e, cache->cells, st);
         s.mtiles.upload(e, cache->tiles, st);
         s.masks.alloc(e, (size_t)cache->elems * sizeof(uint16_t));
     } else {
@@ -342,8 +342,9 @@ static int text_plan_create(const char *fn, fr_ctx *ctx, const fr_glyphset *gs, 
 {
     if (!ctx || !gs || !out) return fail(FR_E_INVALID, "%s: NULL argument", fn);
     *out = nullptr;
-    constexpr bool can_cache = !std::is_same<PLACE, fr_glyph_place_affine>::value;
-    if (const int frc = fr::check_flags(flags, (rgba ? FR_TEXT_SRGB | FR_TEXT_BGRA | FR_TEXT_LOAD | FR_TEXT_OVER : 0u) | (can_cache ? FR_TEXT_CACHE : 0u))) return frc;
+    // (each form has its own cache flag, and answers FR_E_INVALID for the other's)
+    constexpr uint32_t cache_flag = std::is_same<PLACE, fr_glyph_place_affine>::value ? FR_TEXT_CACHE_AFFINE : FR_TEXT_CACHE;
+    if (const int frc = fr::check_flags(flags, (rgba ? FR_TEXT_SRGB | FR_TEXT_BGRA | FR_TEXT_LOAD | FR_TEXT_OVER : 0u) | cache_flag)) return frc;
     if (gs->ctx != ctx) return fail(FR_E_INVALID, "glyph set belongs to another context");
     if (!params) return fail(FR_E_INVALID, "params is NULL");
     if (params->mode < FR_WINDING_I16 || params->mode > FR_SDF_U8) return fail(FR_E_INVALID, "unknown mode %d", params->mode);
@@ -368,19 +369,18 @@ static int text_plan_create(const char *fn, fr_ctx *ctx, const fr_glyphset *gs, 
     in.glyph_seg_start = gs->h_glyph_seg_start.data(); in.n_glyphs = gs->n_glyphs;
     fr::TextPlanTables<PLACE> t;
     if (const int rc = fr::text_plan_tables(in, places, t)) return rc;
-    // FR_TEXT_CACHE: the mask cells and the composite records (a plan whose placements are all clipped away has no cell
-    // and stays the plan it is without the flag); the 2^31-element limit answers here, before anything is allocated
+    // FR_TEXT_CACHE, FR_TEXT_CACHE_AFFINE: the mask cells and the composite records (a plan whose placements are all clipped
+    // away has no cell and stays the plan it is without the flag); the 2^31-element limit answers here, before anything is
+    // allocated
     fr::TextCacheTables cache;
-    if constexpr (can_cache) {
-        if (flags & FR_TEXT_CACHE)
-            if (const int rc = fr::text_cache_tables(in, places, t, cache)) return rc;
-    }
+    if (flags & cache_flag)
+        if (const int rc = fr::text_cache_tables(in, places, t, cache)) return rc;
 
     // (behind the tables: whatever fails in the upload, ~fr_plan waits for the copies that read them)
     std::unique_ptr<fr_plan> p(new (std::nothrow) fr_plan);
     if (p) p->text.reset(new (std::nothrow) TextSide);
     if (!p || !p->text) return fail(FR_E_NOMEM, "%s: host allocation", fn);
-    const fr::TextCacheTables *const cached = cache.cells.empty() ? nullptr : &cache;
+    const fr::TextCacheTables *const cached = cache.n_cells() ? &cache : nullptr;
     p->ctx = ctx; p->gs = gs; p->params = *params; p->flags = flags;
     p->text->tp = fr::text_plan_of(in, *params, t, cached);
     if (const int rc = text_plan_upload(fn, p.get(), t, cached)) return rc;

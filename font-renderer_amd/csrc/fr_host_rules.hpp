@@ -12,7 +12,8 @@ namespace fr {
 
 int check_params(const fr_raster_params *p);
 // the bits an entry point takes besides FR_FILL_CONSISTENT (the RGBA text entry points: FR_TEXT_SRGB, FR_TEXT_BGRA,
-// FR_TEXT_LOAD, FR_TEXT_OVER; the four upright and _ex text entry points: FR_TEXT_CACHE)
+// FR_TEXT_LOAD, FR_TEXT_OVER; the four upright and _ex text entry points: FR_TEXT_CACHE; the two _affine ones:
+// FR_TEXT_CACHE_AFFINE)
 int check_flags(uint32_t flags, uint32_t also = 0u);
 // what job j must satisfy for the kernels' arithmetic to be the reference's (a plan's jobs, and the cells
 // fr_selftest_row_cuts walks), against a glyph set of n_glyphs

@@ -116,7 +116,7 @@ struct TextView {
     fr::Rec *recs;                     // into plan-owned memory before every render
     uint32_t *rec_count;
     // cached: a render fills the mask store from the cells' tiles between the prepare kernel and the composite
-    const fr::TextMaskCell *mcells;
+    const void *mcells;                // TextMaskCell; form TEXT_AFFINE: TextMaskCellAffine
     const fr::TextMaskTile *mtiles;
     uint16_t *masks;
 };

@@ -47,10 +47,10 @@ inline hipError_t launch_text_instance(const TextLaunch &e, const ARGS &a, hipSt
     }, Among<0, 1, 2, 3, 4>{}, Among<0, 1>{}, Among<0, 1, 2>{}, Among<1, 2, 4>{});
 }
 
-// ---- FR_TEXT_CACHE plans (fr_text_cached.hip) ---------------------------------------------------------------------------
-struct TextMaskArgs {      // what glyph_mask_kernel reads and writes
+// ---- FR_TEXT_CACHE and FR_TEXT_CACHE_AFFINE plans (fr_text_cached.hip) --------------------------------------------------
+struct TextMaskArgs {      // what glyph_mask_kernel and glyph_mask_affine_kernel read and write
     const TextMaskTile *tiles;
-    const TextMaskCell *cells;
+    const void *cells;     // TextMaskCell; glyph_mask_affine_kernel: TextMaskCellAffine (as TextView::insts, the form says which)
     const Rec *recs;
     const uint32_t *rec_count;
     uint16_t *masks;       // the mask store
@@ -60,7 +60,8 @@ struct TextCachedArgs : TextTables<TextCachedInst> {   // the text_cached_*_kern
     const uint16_t *masks;
 };
 
-// Fills every mask cell: glyph_mask_kernel<e.n, e.fill> over e.grid mask tiles.
+// Fills every mask cell: glyph_mask_kernel<e.n, e.fill>, or glyph_mask_affine_kernel<e.n, e.fill> when e.form is TEXT_AFFINE,
+// over e.grid mask tiles.  hipErrorInvalidValue for a form, n or fill the kernels have no instance of.
 hipError_t launch_glyph_mask(const TextLaunch &e, const TextMaskArgs &a, hipStream_t stream);
 // The composite of a cached plan over e.grid run tiles: the instance of (e.colour, e.n, e.blend); no fill rule (it acts
 // only where masks are made).

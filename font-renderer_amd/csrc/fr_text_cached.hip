@@ -9,6 +9,10 @@
 // slant 0 that arithmetic is the upright form's bit for bit (include/fr_raster.h), so the six instances N x FILL serve both
 // placement forms.  Every element of the cell is stored: 0 where the winding is zero.
 //
+// glyph_mask_affine_kernel: the same shape for FR_TEXT_CACHE_AFFINE plans (key: glyph, both pen fractions, the bits of the
+// matrix); the cell is an instance in the TextInstAffine layout and the mask is the text of fr_text_affine_mask_kernel.inc.
+// Six more instances N x FILL; the composites below serve these plans as they are.
+//
 // text_cached_*_kernel: the two row bodies of fr_text.hip — tile walk, row loop, instance loops, colour arithmetic, LOAD,
 // sRGB, stores — compiled here with FR_TEXT_MASK_CACHED, which replaces the evaluation of an instance's mask by one 2-byte
 // load from its key's cell, issued by the lanes inside the clipped cell only.  A preprocessor switch and a translation
@@ -30,7 +34,7 @@ FR_TEXT_GLOBAL glyph_mask_kernel(TextMaskArgs a)
 {
     constexpr bool PLACE = true;
     const TextMaskTile tl = a.tiles[blockIdx.x];
-    const TextMaskCell *cl = a.cells + tl.cell;
+    const TextMaskCell *cl = static_cast<const TextMaskCell *>(a.cells) + tl.cell;
     const dependent_t<N, TextInstEx> in = cl->in;
     [[maybe_unused]] const dependent_t<N, TextRun> rn{};                   // (named by the other form's branch of the mask text)
     uint16_t *cell = a.masks + cl->base;
@@ -46,6 +50,35 @@ FR_TEXT_GLOBAL glyph_mask_kernel(TextMaskArgs a)
         uint32_t m;
 #include "fr_text_mask_kernel.inc"
         if (X < in.x1) cell[(uint32_t)Y * (uint32_t)in.x1 + (uint32_t)X] = (uint16_t)m;
+    }
+}
+
+// The same for the cells of an FR_TEXT_CACHE_AFFINE plan (TextMaskCellAffine): the mask is the text of
+// fr_text_affine_mask_kernel.inc, exactly as the row bodies of fr_text_affine.hip include it, with `inside` the lanes left of
+// cw.  The map reads X and Y only through f32(X - ix) and f32(iy - Y), which in the cell are the small integers they are in
+// a run (ix = -min_x, iy = max_y), so the bits are those of every instance of the key.  Lanes right of cw stay out of the
+// cull range [cmin, cmax] and store nothing; a wave row is inside the cell in its first lane or not at all (Y < ch and
+// tl.x0 < cw), so no row runs the record loop for nobody.
+template <int N, int FILL>
+FR_TEXT_GLOBAL glyph_mask_affine_kernel(TextMaskArgs a)
+{
+    const TextMaskTile tl = a.tiles[blockIdx.x];
+    const TextMaskCellAffine *cl = static_cast<const TextMaskCellAffine *>(a.cells) + tl.cell;
+    const dependent_t<N, TextInstAffine> in = cl->in;
+    uint16_t *cell = a.masks + cl->base;
+    const int lane = (int)(threadIdx.x & 63u);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int X = (int)tl.x0 + lane;
+    float off[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) off[k] = sub_off(k, N, a.phase_center);
+    for (int yy = wave; yy < TEXT_TILE_H; yy += TEXT_WAVES) {
+        const int Y = (int)tl.y0 + yy;
+        if (Y >= in.y1) break;                                             // (x1 = cw, y1 = ch: the whole cell)
+        const bool inside = X < in.x1;
+        uint32_t m;
+#include "fr_text_affine_mask_kernel.inc"
+        if (inside) cell[(uint32_t)Y * (uint32_t)in.x1 + (uint32_t)X] = (uint16_t)m;
     }
 }
 
@@ -90,9 +123,11 @@ constexpr auto cached_kernel_of() -> void (*)(TextCachedArgs)
 
 hipError_t launch_glyph_mask(const TextLaunch &e, const TextMaskArgs &a, hipStream_t stream)
 {
-    const int key[] = {e.n, e.fill};
-    return pick(key, [&](auto N, auto FILL) { return launch_tiles<TextMaskArgs>(glyph_mask_kernel<N, FILL>, e.grid, stream, a); },
-                Among<1, 2, 4>{}, Among<0, 1>{});
+    const int key[] = {e.form, e.n, e.fill};
+    return pick(key, [&](auto FORM, auto N, auto FILL) {
+        if constexpr (decltype(FORM)::value == TEXT_AFFINE) return launch_tiles<TextMaskArgs>(glyph_mask_affine_kernel<N, FILL>, e.grid, stream, a);
+        else return launch_tiles<TextMaskArgs>(glyph_mask_kernel<N, FILL>, e.grid, stream, a);
+    }, Among<TEXT_PLAIN, TEXT_EX, TEXT_AFFINE>{}, Among<1, 2, 4>{}, Among<0, 1>{});
 }
 
 hipError_t launch_text_cached(const TextLaunch &e, const TextCachedArgs &a, hipStream_t stream)

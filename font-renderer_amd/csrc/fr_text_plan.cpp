@@ -5,7 +5,8 @@
 // resolve (the form's own checks, and what the build keeps of them: the affine inverse), cell_of (the cell in pixels about the pen) and
 // finish (the tail of the instance record).  The order of the checks fixes which error a caller sees: it is part of
 // the ABI's behaviour and host/text_plan_selftest.cpp pins it.  A second builder, text_cache_tables, adds the tables of an
-// FR_TEXT_CACHE plan from the same pieces (host/text_cache_selftest.cpp).  At the end: from a plan's flags and counts to the
+// FR_TEXT_CACHE or FR_TEXT_CACHE_AFFINE plan from the same pieces (host/text_cache_selftest.cpp,
+// host/text_cache_affine_selftest.cpp).  At the end: from a plan's flags and counts to the
 // launches of one render and their kernel names (text_plan_of, text_launches, text_launch_name).
 #include "fr_text_plan.hpp"
 #include "fr_srgb.hpp"
@@ -263,15 +264,35 @@ template int text_plan_tables(const TextPlanIn &, const fr_glyph_place *, TextPl
 template int text_plan_tables(const TextPlanIn &, const fr_glyph_place_ex *, TextPlanTables<fr_glyph_place_ex> &);
 template int text_plan_tables(const TextPlanIn &, const fr_glyph_place_affine *, TextPlanTables<fr_glyph_place_affine> &);
 
-// ---- FR_TEXT_CACHE (fr_text_plan.hpp) ---------------------------------------------------------------------------------
+// ---- FR_TEXT_CACHE, FR_TEXT_CACHE_AFFINE (fr_text_plan.hpp) -----------------------------------------------------------
 namespace {
 
 uint32_t bits_of(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
 
-// what the key holds besides the glyph and the pen fractions; the plain form is the _ex form at the run's scale, upright
-struct Shape { float scale, slant; };
-Shape shape_of(const fr_glyph_place &, float run_scale) { return Shape{run_scale, 0.0f}; }
-Shape shape_of(const fr_glyph_place_ex &p, float run_scale) { return Shape{scale_of(p, run_scale), p.slant}; }
+// what the key holds besides the glyph and the pen fractions, as bit patterns: the effective scale and the slant (the plain
+// form is the _ex form at the run's scale, upright), or the four entries of the caller's matrix (equal m gives equal q)
+using Shape = std::array<uint32_t, 4>;
+Shape shape_of(const fr_glyph_place &, float run_scale) { return Shape{bits_of(run_scale), bits_of(0.0f), 0u, 0u}; }
+Shape shape_of(const fr_glyph_place_ex &p, float run_scale) { return Shape{bits_of(scale_of(p, run_scale)), bits_of(p.slant), 0u, 0u}; }
+Shape shape_of(const fr_glyph_place_affine &p, float) { return Shape{bits_of(p.m[0]), bits_of(p.m[1]), bits_of(p.m[2]), bits_of(p.m[3])}; }
+
+// the cells of a form, and a key's cell record: the first instance `ti` of the key as an instance whose image is the whole
+// cell (fr_text_tables.hpp), so that the tail of the record (scale and slant, or the inverse matrix) is the one finish wrote
+std::vector<TextMaskCell> &cells_of(TextCacheTables &c, const TextInst *) { return c.cells; }
+std::vector<TextMaskCell> &cells_of(TextCacheTables &c, const TextInstEx *) { return c.cells; }
+std::vector<TextMaskCellAffine> &cells_of(TextCacheTables &c, const TextInstAffine *) { return c.acells; }
+template <class INST>
+TextInstEx whole_cell(const INST &ti, const Cell &c, int64_t cw, int64_t ch, uint32_t fy64, const Shape &sh)
+{
+    float scale, slant;
+    std::memcpy(&scale, &sh[0], 4); std::memcpy(&slant, &sh[1], 4);
+    return TextInstEx{(int32_t)-c.mnx, (int32_t)c.mxy, 0, (int32_t)cw, 0, (int32_t)ch, ti.glyph, ti.rec, ti.fx64, 0u, {0, 0}, fy64, scale, slant, 0u};
+}
+TextInstAffine whole_cell(const TextInstAffine &ti, const Cell &c, int64_t cw, int64_t ch, uint32_t fy64, const Shape &)
+{
+    return TextInstAffine{(int32_t)-c.mnx, (int32_t)c.mxy, 0, (int32_t)cw, 0, (int32_t)ch, ti.glyph, ti.rec, ti.fx64, 0u, {0, 0}, fy64,
+                          ti.q00, ti.q01, ti.q10, ti.q11, {0, 0, 0}};
+}
 
 }  // namespace
 
@@ -279,7 +300,10 @@ Shape shape_of(const fr_glyph_place_ex &p, float run_scale) { return Shape{scale
 template <class PLACE>
 int text_cache_tables(const TextPlanIn &in, const PLACE *places, const TextPlanTables<PLACE> &t, TextCacheTables &out)
 {
-    using Key = std::array<uint32_t, 5>;                   // glyph, fx64, fy64, bits of the scale, bits of the slant
+    using Key = std::array<uint32_t, 7>;                   // glyph, fx64, fy64, the form's Shape
+    using INST = typename TextInstOf<PLACE>::type;
+    auto &cells = cells_of(out, (const INST *)nullptr);
+    constexpr bool affine = std::is_same<PLACE, fr_glyph_place_affine>::value;
     std::map<Key, uint32_t> cell_of_key;
     out.insts.reserve(t.insts.size());
     uint64_t elems = 0;
@@ -301,38 +325,41 @@ int text_cache_tables(const TextPlanIn &in, const PLACE *places, const TextPlanT
             if (id >= t.insts.size()) return set_error(FR_E_INVALID, "text cache: the tables are not those of these placements");
             const auto &ti = t.insts[id];
             const Shape sh = shape_of(places[k], rn.scale);
-            const Key key{g, fx64, fy64, bits_of(sh.scale), bits_of(sh.slant)};
+            const Key key{g, fx64, fy64, sh[0], sh[1], sh[2], sh[3]};
             auto it = cell_of_key.find(key);
             if (it == cell_of_key.end()) {
                 if (elems + (uint64_t)(cw * ch) > TEXT_CACHE_MAX_ELEMS)
-                    return set_error(FR_E_UNSUPPORTED, "FR_TEXT_CACHE: the mask cells hold more than 2^31 elements; split the plan or drop the flag");
-                TextMaskCell mc{};
-                mc.in = TextInstEx{(int32_t)-c.mnx, (int32_t)c.mxy, 0, (int32_t)cw, 0, (int32_t)ch, g, ti.rec, fx64, 0u, {0, 0}, fy64, sh.scale, sh.slant, 0u};
+                    return set_error(FR_E_UNSUPPORTED, "%s: the mask cells hold more than 2^31 elements; split the plan or drop the flag",
+                                     affine ? "FR_TEXT_CACHE_AFFINE" : "FR_TEXT_CACHE");
+                typename std::remove_reference<decltype(cells)>::type::value_type mc{};
+                mc.in = whole_cell(ti, c, cw, ch, fy64, sh);
                 mc.base = (uint32_t)elems;
                 elems += (uint64_t)(cw * ch);
-                it = cell_of_key.emplace(key, (uint32_t)out.cells.size()).first;
-                out.cells.push_back(mc);
+                it = cell_of_key.emplace(key, (uint32_t)cells.size()).first;
+                cells.push_back(mc);
             }
-            const TextMaskCell &mc = out.cells[it->second];
+            const auto &mc = cells[it->second];
             out.insts.push_back(TextCachedInst{ti.x0, ti.x1, ti.y0, ti.y1, ti.rgba, {ti.pad[0], ti.pad[1]}, mc.base, (uint32_t)cw, (int32_t)c0, (int32_t)r0, 0u});
         }
     }
     if (out.insts.size() != t.insts.size()) return set_error(FR_E_INVALID, "text cache: the tables are not those of these placements");
     out.elems = elems;
     uint64_t n_tiles = 0;
-    for (const TextMaskCell &mc : out.cells)
+    for (const auto &mc : cells)
         n_tiles += (uint64_t)((mc.in.x1 + TEXT_TILE_W - 1) / TEXT_TILE_W) * (uint64_t)((mc.in.y1 + TEXT_TILE_H - 1) / TEXT_TILE_H);
-    if (n_tiles > 0x7fffffffull) return set_error(FR_E_UNSUPPORTED, "FR_TEXT_CACHE: the mask cells need more than 2^31 workgroups; split the plan");
+    if (n_tiles > 0x7fffffffull)
+        return set_error(FR_E_UNSUPPORTED, "%s: the mask cells need more than 2^31 workgroups; split the plan", affine ? "FR_TEXT_CACHE_AFFINE" : "FR_TEXT_CACHE");
     out.tiles.reserve((size_t)n_tiles);
-    for (uint32_t ci = 0; ci < out.cells.size(); ++ci)
-        for (int32_t y = 0; y < out.cells[ci].in.y1; y += TEXT_TILE_H)
-            for (int32_t x = 0; x < out.cells[ci].in.x1; x += TEXT_TILE_W)
+    for (uint32_t ci = 0; ci < cells.size(); ++ci)
+        for (int32_t y = 0; y < cells[ci].in.y1; y += TEXT_TILE_H)
+            for (int32_t x = 0; x < cells[ci].in.x1; x += TEXT_TILE_W)
                 out.tiles.push_back(TextMaskTile{ci, (uint32_t)x, (uint32_t)y, 0u});
     return FR_OK;
 }
 
 template int text_cache_tables(const TextPlanIn &, const fr_glyph_place *, const TextPlanTables<fr_glyph_place> &, TextCacheTables &);
 template int text_cache_tables(const TextPlanIn &, const fr_glyph_place_ex *, const TextPlanTables<fr_glyph_place_ex> &, TextCacheTables &);
+template int text_cache_tables(const TextPlanIn &, const fr_glyph_place_affine *, const TextPlanTables<fr_glyph_place_affine> &, TextCacheTables &);
 
 // ---- the launches of one render (fr_text_plan.hpp) --------------------------------------------------------------------
 template <class PLACE>
@@ -349,7 +376,7 @@ TextPlan text_plan_of(const TextPlanIn &in, const fr_raster_params &params, cons
     p.n_tiles = (uint32_t)t.tiles.size(); p.n_insts = (uint32_t)t.insts.size(); p.n_glyphs = (uint32_t)t.glyphs.size();
     if (cache) {
         p.cached = true;
-        p.n_mcells = (uint32_t)cache->cells.size(); p.n_mtiles = (uint32_t)cache->tiles.size();
+        p.n_mcells = (uint32_t)cache->n_cells(); p.n_mtiles = (uint32_t)cache->tiles.size();
     }
     return p;
 }
@@ -381,7 +408,10 @@ void text_launch_name(const TextLaunch &e, char *name, size_t cap)
     if (e.fill != 0 && e.fill != 1) return;
     if (e.family == TL_PREPARE) { snprintf(name, cap, e.fill ? "fr::prepare_fill_kernel" : "fr::prepare_kernel"); return; }
     if (e.n != 1 && e.n != 2 && e.n != 4) return;
-    if (e.family == TL_MASK) { snprintf(name, cap, "fr::glyph_mask_kernel<%d, %d>", e.n, e.fill); return; }
+    if (e.family == TL_MASK) {
+        snprintf(name, cap, e.form == TEXT_AFFINE ? "fr::glyph_mask_affine_kernel<%d, %d>" : "fr::glyph_mask_kernel<%d, %d>", e.n, e.fill);
+        return;
+    }
     if (e.colour < 0 || e.colour > 4 || e.blend < 0 || e.blend > 2 || (e.colour == 0 && e.blend != 0)) return;
     if (e.family == TL_CACHED) {
         if (e.colour == 0) snprintf(name, cap, "fr::text_cached_kernel<%d>", e.n);

@@ -49,15 +49,19 @@ int text_plan_tables(const TextPlanIn &in, const PLACE *places, TextPlanTables<P
 // ---- FR_TEXT_CACHE: one mask cell per key, filled once per render and read by every instance of the key ----------------
 struct TextCacheTables {
     std::vector<TextMaskCell> cells;   // one per distinct key among the surviving instances, in order of first use
+    std::vector<TextMaskCellAffine> acells;   // the same for fr_glyph_place_affine placements: a plan fills one of the two
     std::vector<TextMaskTile> tiles;   // every 64 x 16 tile of every cell, cell by cell
     std::vector<TextCachedInst> insts; // one per instance of TextPlanTables::insts, in its order (the tiles' lists name both alike)
     uint64_t elems = 0;                // the mask store: the sum of cw * ch over the cells, uint16_t each
+    size_t n_cells() const { return cells.size() + acells.size(); }
 };
 
 constexpr uint64_t TEXT_CACHE_MAX_ELEMS = (uint64_t)1 << 31;
 
-// PLACE: fr_glyph_place (key: glyph, pen_x64 mod 64, the bits of the run's scale) or fr_glyph_place_ex (key: glyph, pen_x64
-// mod 64, pen_y64 mod 64, the bits of the effective scale and of the slant).  `in`, `places` and `t` are what
+// PLACE: fr_glyph_place (key: glyph, pen_x64 mod 64, the bits of the run's scale), fr_glyph_place_ex (key: glyph, pen_x64
+// mod 64, pen_y64 mod 64, the bits of the effective scale and of the slant) or, for FR_TEXT_CACHE_AFFINE,
+// fr_glyph_place_affine (key: glyph, pen_x64 mod 64, pen_y64 mod 64, the bits of m[0..3]; its cells are `acells`).  `in`,
+// `places` and `t` are what
 // text_plan_tables took and returned.  FR_OK, or FR_E_UNSUPPORTED (message through fr::set_error) when the cells hold
 // more than TEXT_CACHE_MAX_ELEMS elements: decided before any tile is listed, so the caller has nothing to allocate.
 template <class PLACE>
@@ -76,7 +80,7 @@ struct TextPlan {                      // everything the launches of a text plan
     bool rgba = false;                 // RGBA pixels; else coverage / mask bytes
     bool srgb = false;                 // (rgba) FR_TEXT_SRGB: blending and resolve in linear light
     bool load = false;                 // (rgba) FR_TEXT_LOAD: the samples start at the output's pixels; occupied tiles only
-    bool cached = false;               // FR_TEXT_CACHE with at least one mask cell: the instance table holds TextCachedInst
+    bool cached = false;               // FR_TEXT_CACHE / FR_TEXT_CACHE_AFFINE with at least one mask cell: the instance table holds TextCachedInst
     int blend = 0;                     // (rgba) TextPlanTables::blend
     int fill = 0;                      // FR_FILL_CONSISTENT
     int samples = 1;                   // per axis
@@ -90,8 +94,8 @@ TextPlan text_plan_of(const TextPlanIn &in, const fr_raster_params &params, cons
 
 enum TextFamily : uint8_t { TL_PREPARE, TL_MASK, TL_TEXT, TL_CACHED };
 struct TextLaunch {
-    TextFamily family;                 // prepare_kernel, glyph_mask_kernel, a text kernel of `form`, a cached composite
-    TextForm form;                     // (text)
+    TextFamily family;                 // prepare_kernel, glyph_mask_kernel (glyph_mask_affine_kernel), a text kernel of `form`, a cached composite
+    TextForm form;                     // (text; mask: TEXT_AFFINE picks glyph_mask_affine_kernel and its cell record)
     int colour;                        // (text, cached) 0 coverage, 1 rgba, 2 srgb, 3 rgba load, 4 srgb load
     int n, fill, blend;                // the template arguments N, FILL, BLEND: the coverage kernels have no BLEND (0), the
                                        // composites no FILL (0: the fill rule acts only where masks are made)

@@ -63,6 +63,11 @@ struct TextMaskCell {  // one key's mask cell: cw x ch elements of uint16_t, row
     uint32_t base;     // first element in the store
     uint32_t pad[3];
 };
+struct TextMaskCellAffine {  // the same for a key of an FR_TEXT_CACHE_AFFINE plan: glyph_mask_affine_kernel reads these
+    TextInstAffine in; // as TextMaskCell::in, with the key's fx64, fy64 and the inverse q00 .. q11 of the key's matrix
+    uint32_t base;     // first element in the store
+    uint32_t pad[3];
+};
 struct TextMaskTile {  // one 64 x 16 tile of a mask cell
     uint32_t cell, x0, y0, pad;
 };
@@ -78,6 +83,7 @@ struct TextCachedInst {  // what a composite kernel reads of an instance: the cl
     uint32_t pad2;
 };
 static_assert(sizeof(TextMaskCell) == 80 && sizeof(TextMaskTile) == 16 && sizeof(TextCachedInst) == 48, "text tables");
+static_assert(sizeof(TextMaskCellAffine) == 96, "text tables");
 static_assert(sizeof(TextInstEx) == 64, "text tables");
 static_assert(sizeof(TextInstAffine) == 80, "text tables");
 static_assert(sizeof(TextInst) == 48 && sizeof(TextRun) == 32 && sizeof(TextTile) == 32, "text tables");

@@ -84,10 +84,11 @@ def _frame(width, height) -> None:
         raise ValueError(f"width {width!r} and height {height!r} must be integers in [0, 65535]")
 
 
-def _flags(flags: int, srgb: bool = False, bgra: bool = False, cache: bool = False, over: bool = False) -> int:
-    """the flag word of a text plan from the keyword arguments of the render functions"""
-    return (flags | (L.FR_TEXT_SRGB if srgb else 0) | (L.FR_TEXT_BGRA if bgra else 0) | (L.FR_TEXT_CACHE if cache else 0)
-            | (L.FR_TEXT_OVER if over else 0))
+def _flags(flags: int, srgb: bool = False, bgra: bool = False, cache: bool = False, over: bool = False, affine: bool = False) -> int:
+    """the flag word of a text plan from the keyword arguments of the render functions; affine: the plan is of the matrix
+    form, whose cache flag is FR_TEXT_CACHE_AFFINE"""
+    return (flags | (L.FR_TEXT_SRGB if srgb else 0) | (L.FR_TEXT_BGRA if bgra else 0)
+            | ((L.FR_TEXT_CACHE_AFFINE if affine else L.FR_TEXT_CACHE) if cache else 0) | (L.FR_TEXT_OVER if over else 0))
 
 
 def _per_char(text, color, colors) -> list:
@@ -426,30 +427,33 @@ def rotated_line(font: Font, text, font_size: int, angle_deg: float, x: float, y
 
 def render_text_rotated(font: Font, text, font_size: int, angle_deg: float, x: float, y: float, width: int, height: int, *,
                         zoom: float = 1.0, slant: float = 0.0, samples_per_axis: int = 4, mode: int = L.FR_COVERAGE_U8,
-                        phase: int = L.FR_SAMPLE_CENTER, flags: int = L.FR_FILL_CONSISTENT, ctx: Optional[Context] = None) -> Gray:
+                        phase: int = L.FR_SAMPLE_CENTER, flags: int = L.FR_FILL_CONSISTENT, cache: bool = False,
+                        ctx: Optional[Context] = None) -> Gray:
     """`text` along a direction (rotated_line), clipped to a width x height image: a vertical axis title is angle_deg = 90
     with (x, y) at its lower end.  FR_FILL_CONSISTENT is the default here: under a rotation the reference's false
-    windings on rows through vertices become slanted streaks (include/fr_raster.h)."""
+    windings on rows through vertices become slanted streaks (include/fr_raster.h).  cache: FR_TEXT_CACHE_AFFINE, the same
+    bytes with each distinct (glyph, pen fractions, matrix) rasterised once per render; it pays when characters repeat
+    at equal fractions and costs the mask store otherwise."""
     line = rotated_line(font, text, font_size, angle_deg, x, y, width, height, zoom, slant)
     if line is None:
         return Gray.init(int(width), int(height))
-    return _render(ctx, line, int(width), int(height), samples_per_axis, phase, flags, mode)
+    return _render(ctx, line, int(width), int(height), samples_per_axis, phase, _flags(flags, cache=cache, affine=True), mode)
 
 
 def render_text_rgba_rotated(font: Font, text, font_size: int, angle_deg: float, x: float, y: float, width: int, height: int,
                              color=(225, 105, 180, 255), background=(0, 0, 0, 0), colors=None, *, zoom: float = 1.0,
                              slant: float = 0.0, samples_per_axis: int = 4, phase: int = L.FR_SAMPLE_CENTER,
                              flags: int = L.FR_FILL_CONSISTENT, srgb: bool = False, bgra: bool = False, over: bool = False,
-                             ctx: Optional[Context] = None) -> RGBA:
+                             cache: bool = False, ctx: Optional[Context] = None) -> RGBA:
     """render_text_rotated as one RGBA image: colours, background, srgb, bgra and over as render_text_rgba (with over the
-    image is premultiplied)"""
+    image is premultiplied); cache as render_text_rotated"""
     per_char, clear = _per_char(text, color, colors), colour_rgba(background)
     line = rotated_line(font, text, font_size, angle_deg, x, y, width, height, zoom, slant)
     if line is None:
         im = RGBA.init(int(width), int(height))
         im.data[:] = clear
         return im
-    return _render(ctx, line, int(width), int(height), samples_per_axis, phase, _flags(flags, srgb, bgra, over=over),
+    return _render(ctx, line, int(width), int(height), samples_per_axis, phase, _flags(flags, srgb, bgra, cache, over, affine=True),
                    colours=per_char, clear=clear)
 
 
@@ -479,14 +483,16 @@ def lcd_line(font: Font, text, font_size: int, x: float, y: float, width: int, h
 
 def draw_text_lcd(image: RGBA, font: Font, text, font_size: int, x: float, y: float, color=(0, 0, 0, 255), *, weights=None,
                   samples_per_axis: int = 4, phase: int = L.FR_SAMPLE_CENTER, flags: int = L.FR_FILL_CONSISTENT,
-                  srgb: bool = False, bgr: bool = False, return_plane: bool = False, ctx: Optional[Context] = None):
+                  srgb: bool = False, bgr: bool = False, return_plane: bool = False, cache: bool = False,
+                  ctx: Optional[Context] = None):
     """One line of sub-pixel (LCD) text drawn in place over the premultiplied `image`: the line is rendered once as a
     coverage plane of 3 width x height elements through the affine text plan (lcd_line; 3 x samples_per_axis sample
     columns per pixel), and fr_layer_lcd filters it across sub-pixels with `weights` (None: the default filter) and
     composites `color` with an alpha per colour byte, both on the context's stream with no sync between them.  x, y as
     draw_text_rgba; the whole colour applies to the whole line.  srgb: the image is premultiplied in linear light; bgr:
-    the panel's stripes are B G R.  FR_FILL_CONSISTENT is the default, as for rotated text.  Returns `image`, or
-    (image, the plane as a Gray) with return_plane."""
+    the panel's stripes are B G R.  FR_FILL_CONSISTENT is the default, as for rotated text.  cache: FR_TEXT_CACHE_AFFINE
+    for the plane's plan: the same plane, each distinct (glyph, pen fraction) of the line rasterised once.  Returns
+    `image`, or (image, the plane as a Gray) with return_plane."""
     w, h = image.width, image.height
     dst = rgba_pixels(image, "draw_text_lcd: image")
     colour = colour_rgba(color)
@@ -496,7 +502,8 @@ def draw_text_lcd(image: RGBA, font: Font, text, font_size: int, x: float, y: fl
         return (image, Gray.init(3 * w, h)) if return_plane else image
     gs, places, runs = line
     blits = make_lcd_blits([(0, 0, w, h, 0, 0, colour)])
-    with closing(DeviceGlyphSet(ctx, gs)) as dgs, closing(TextPlan(dgs, places, runs, L.FR_COVERAGE_U8, samples_per_axis, phase, flags)) as plan:
+    with closing(DeviceGlyphSet(ctx, gs)) as dgs, closing(TextPlan(dgs, places, runs, L.FR_COVERAGE_U8, samples_per_axis, phase,
+                                                                 _flags(flags, cache=cache, affine=True))) as plan:
         def call(d, c):
             plan.render(c, 3 * w, h)
             layer_lcd(ctx, c, 3 * w, h, d, w, h, blits, weights, srgb, bgr)
@@ -507,11 +514,12 @@ def draw_text_lcd(image: RGBA, font: Font, text, font_size: int, x: float, y: fl
 
 def render_text_lcd(font: Font, text, font_size: int, x: float, y: float, width: int, height: int, color=(0, 0, 0, 255),
                     background=(255, 255, 255, 255), *, weights=None, samples_per_axis: int = 4, phase: int = L.FR_SAMPLE_CENTER,
-                    flags: int = L.FR_FILL_CONSISTENT, srgb: bool = False, bgr: bool = False, ctx: Optional[Context] = None) -> RGBA:
+                    flags: int = L.FR_FILL_CONSISTENT, srgb: bool = False, bgr: bool = False, cache: bool = False,
+                    ctx: Optional[Context] = None) -> RGBA:
     """draw_text_lcd over a new width x height image filled with the premultiplied colour `background`: black text on
-    white by default, what sub-pixel rendering is made for"""
+    white by default, what sub-pixel rendering is made for; cache as draw_text_lcd"""
     _frame(width, height)
     im = RGBA.init(int(width), int(height))
     im.data[:] = colour_rgba(background)
     return draw_text_lcd(im, font, text, font_size, x, y, color, weights=weights, samples_per_axis=samples_per_axis, phase=phase,
-                         flags=flags, srgb=srgb, bgr=bgr, ctx=ctx)
+                         flags=flags, srgb=srgb, bgr=bgr, cache=cache, ctx=ctx)

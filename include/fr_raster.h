@@ -477,6 +477,36 @@ int fr_text_plan_create_rgba_affine(fr_ctx *ctx, const fr_glyphset *gs, const fr
                                     const uint8_t *run_clear_rgba, uint32_t n_runs, const fr_raster_params *params,
                                     uint32_t flags, fr_plan **out);
 
+/* FR_TEXT_CACHE_AFFINE  (fr_text_plan_create_affine, fr_text_plan_create_rgba_affine) FR_TEXT_CACHE for the matrix form:
+ *       rasterise each distinct glyph image of the plan once per render and let every placement that shows it read it.
+ *       The plan renders, byte for byte, what the same plan without the flag renders: every mode, n in {1, 2, 4}, both
+ *       phases, FR_FILL_CONSISTENT, FR_TEXT_SRGB, FR_TEXT_BGRA, FR_TEXT_LOAD, FR_TEXT_OVER, every clipping case, the LOAD
+ *       tile rule and "every pixel of the run is written".  Only the work differs.
+ *   Key: the placements that survive clipping are grouped by (glyph, pen_x64 mod 64, pen_y64 mod 64, the bit patterns of
+ *       m[0], m[1], m[2], m[3]); floats compare as bit patterns (0.0 and -0.0 are two keys).  The key holds the caller's
+ *       matrix, not its inverse: the cell is defined from m, and equal m gives equal q.  By the sample definition above,
+ *       two placements of one key have identical n^2-bit sample masks at equal offsets from (ix, iy).
+ *   Mask cell: each key owns the placement's whole, unclipped cell (cw x ch as the matrix form defines it: the four mapped
+ *       corners, + 1, + (fx != 0), + (fy != 0)) as cw * ch elements of uint16_t, row-major with pitch cw: element (c, r)
+ *       is the non-zero mask (bit j*n + i: sample (i, j)) of the pixel at cell column c, row r.  The cells live in one
+ *       plan-owned store on the device.
+ *   Render: the prepare kernel as before, then one launch that fills every mask cell from the records, then the composite
+ *       launch of FR_TEXT_CACHE plans (it does not depend on the placement form), in stream order on the context's
+ *       stream.  The "graph" option captures the three launches.
+ *   Cost: as for FR_TEXT_CACHE.  A cell is the bounding box of the mapped glyph box, so at 45 degrees it holds about twice
+ *       the area the glyph does; the flag pays where many placements share few (glyph, pen fraction, matrix) keys:
+ *       running text under one matrix on a fixed set of sub-pixel pens, or the 3x-wide plane of sub-pixel (LCD) text.
+ *   Limits: those of FR_TEXT_CACHE: at most 2^31 elements over all cells of a plan (FR_E_UNSUPPORTED beyond, decided on the
+ *       host before anything is allocated); a device allocation failure is FR_E_NOMEM.  A plan whose placements are all
+ *       clipped away has no cell and is the plan without the flag.
+ *   Combines with FR_FILL_CONSISTENT and, on the RGBA entry point, with FR_TEXT_SRGB, FR_TEXT_BGRA, FR_TEXT_LOAD and
+ *   FR_TEXT_OVER.  The upright, _ex and raster entry points and every other entry point that takes flags return
+ *   FR_E_INVALID for it; FR_TEXT_CACHE stays FR_E_INVALID on the two _affine entry points, so the two bits together are
+ *   refused everywhere.  Bits 2, 16, 64 and 1 << 31 stay unassigned.
+ *   fr_plan_describe lists the prepare kernel with the glyph count, glyph_mask_affine_kernel<n, fill> with the cell count
+ *   and the composite of FR_TEXT_CACHE plans with the instance count.  fr_plan_pixels and fr_plan_stats are unchanged.   */
+#define FR_TEXT_CACHE_AFFINE 512u
+
 /* One-shot: plan + render + copy back.  out_host: HOST buffer (caller-allocated,
  * e.g. Image.Gray.data / Image.Winding.data from the Zig allocator).  Synchronous.  */
 int fr_render_batch(fr_ctx *ctx, const fr_glyphset *gs, const fr_job *jobs, uint32_t n_jobs,

@@ -13,8 +13,11 @@ of four pixels: 3 (the plane read alone) where the group's sixteen plane bytes a
 
 Case "lines": the 4 096 lines of tools/bench_text.py as the whole route per frame: the affine 3x coverage plan's render plus
 fr_layer_lcd, against the _ex RGBA plan's render (FR_TEXT_OVER over a clear layer) plus fr_layer_paint with one stop.
+--cache adds the same 3x plan with FR_TEXT_CACHE_AFFINE (one mask cell per (glyph, pen fraction) of the plane, filled once
+per render: csrc/fr_text_cached.hip) as routes of its own, alternated with the others; the two planes must be equal, and
+the summary line states the instances, the cells and the bytes of the mask store.
 
-    python tools/bench_lcd.py [--calls 50] [--repeats 5] [--lines 4096] [--cases frame,lines]"""
+    python tools/bench_lcd.py [--calls 50] [--repeats 5] [--lines 4096] [--cases frame,lines] [--cache]"""
 import argparse
 import json
 import os
@@ -81,6 +84,15 @@ def noise_frame(H, W):
     frame = torch.empty((H, W, 4), dtype=torch.uint8, device="cuda:0").random_(0, 256, generator=torch.Generator("cuda:0").manual_seed(W))
     frame[..., 3] = 255
     return frame
+
+
+def mask_store_bytes(gs, wide_places):
+    """-> (keys, bytes of the mask store) of the FR_TEXT_CACHE_AFFINE plan of these placements: one cell per (glyph, both pen
+    fractions) under the one matrix, 2 bytes per element (include/fr_raster.h)"""
+    seg = gs.segments_per_glyph()
+    keys = sorted({(int(p["glyph"]), int(p["pen_x64"]) & 63, int(p["pen_y64"]) & 63) for p in wide_places if seg[int(p["glyph"])]})
+    m = wide_places["m"][0]
+    return len(keys), sum(2 * int(cw) * int(ch) for _, _, cw, ch in (fr.instance_cell_affine(gs.boxes[g], m, fx, fy) for g, fx, fy in keys))
 
 
 def routes_of(ctx, gs, places, runs, shape, samples=4):
@@ -151,6 +163,19 @@ def lines_case(ctx, stream, args, font):
 
     routes = {"affine3x+lcd": lcd, "ex_rgba+paint": paint,
               "affine3x_render": lambda k: lcd_plan.render(plane.data_ptr(), 3 * W, H), "ex_rgba_render": lambda k: ex_plan.render(layer.data_ptr(), W, H)}
+    if args.cache:
+        import re
+        import torch
+        wide_places, wide_runs = as_lcd(places, runs)
+        cached_plan = fr.TextPlan(dgs, wide_places, wide_runs, fr.FR_COVERAGE_U8, 4, fr.FR_SAMPLE_CENTER, fr.FR_FILL_CONSISTENT | fr.FR_TEXT_CACHE_AFFINE)
+        cached_plane = torch.zeros_like(plane)
+        torch.cuda.synchronize()
+
+        def cached(k):
+            cached_plan.render(cached_plane.data_ptr(), 3 * W, H)
+            fr.layer_lcd(ctx, cached_plane.data_ptr(), 3 * W, H, frame.data_ptr(), W, H, blits)
+
+        routes.update({"affine3x_cached+lcd": cached, "affine3x_cached_render": lambda k: cached_plan.render(cached_plane.data_ptr(), 3 * W, H)})
     res = {r: [] for r in routes}
     for _ in range(args.repeats + 1):
         for r, fn in routes.items():
@@ -158,6 +183,21 @@ def lines_case(ctx, stream, args, font):
     ms = {r: report("lines", r, res[r], W * H, None, lines=args.lines, w=W, h=H) for r in routes}
     print(json.dumps({"case": "lines", "lcd_route_ms_by_paint_route_ms": round(ms["affine3x+lcd"] / ms["ex_rgba+paint"], 3),
                       "render_share_of_lcd_route": round(ms["affine3x_render"] / ms["affine3x+lcd"], 3)}), flush=True)
+    if args.cache:
+        ctx.sync()
+        if not torch.equal(plane, cached_plane):
+            raise SystemExit("--cache: the cached 3x plan's plane differs from the plain plan's")
+        desc = cached_plan.describe()
+        n_keys, store = mask_store_bytes(gs, wide_places)
+        n_cells = int(re.search(r"glyph_mask_affine_kernel<\d, \d> x(\d+)", desc).group(1))
+        if n_cells != n_keys:
+            raise SystemExit(f"--cache: {n_cells} cells for {n_keys} keys")
+        print(json.dumps({"case": "lines", "cache": True, "instances": int(re.search(r"text_cached_kernel<\d> x(\d+)", desc).group(1)), "cells": n_cells,
+                          "mask_store_bytes": store, "plain_render_by_cached_render": round(ms["affine3x_render"] / ms["affine3x_cached_render"], 2),
+                          "plain_route_by_cached_route": round(ms["affine3x+lcd"] / ms["affine3x_cached+lcd"], 2),
+                          "cached_route_ms_by_paint_route_ms": round(ms["affine3x_cached+lcd"] / ms["ex_rgba+paint"], 3),
+                          "render_share_of_cached_route": round(ms["affine3x_cached_render"] / ms["affine3x_cached+lcd"], 3), "cached_plan": desc}), flush=True)
+        cached_plan.close()
     lcd_plan.close(), ex_plan.close(), dgs.close()
 
 
@@ -167,6 +207,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5, help="repeats of each alternated timing")
     ap.add_argument("--lines", type=int, default=4096)
     ap.add_argument("--cases", default="frame,lines", help="which of frame and lines to run")
+    ap.add_argument("--cache", action="store_true", help="lines: also the 3x plan with FR_TEXT_CACHE_AFFINE, alternated with the plain one")
     args = ap.parse_args()
     import torch
     stream = torch.cuda.Stream(device="cuda:0")

@@ -47,6 +47,12 @@ placement exactly once, each in a run of its cell's size — the prepare kernel 
 glyph image once, which is the work of the cached plan's first two launches; the composite is what remains of (b).
 --cache-only leaves the other configurations out.
 
+--affine --cache together price the mask cache of the matrix form instead of those two: the five variants of --affine, each
+as its plain plan and as its cached plan (FR_TEXT_CACHE for the _ex plan (a), FR_TEXT_CACHE_AFFINE for (b)-(e)), the ten
+alternated in the same process, --repeats times; the two images of a variant must be equal.  One JSON line per font and
+size ("case": "affine_cache") with, per variant, the instances, the cells, the bytes of the mask store and both medians
+with their smallest and largest repeat.
+
 --over prices FR_TEXT_OVER (source-over alpha: the colour kernels' third blend value, csrc/fr_text_colour_kernel.inc),
 printed as its own JSON lines ("case": "over"), one per font and size: the --rgba translucent colouring as (a) the plan
 without the flag (blend = 1) and (b) the plan with it (blend = 2), UNORM and sRGB, timed alternately in the same process,
@@ -166,9 +172,11 @@ def main():
     ctx = fr.Context(0)
     if args.place:
         place(ctx, args)
-    if args.affine:
+    if args.affine and args.cache:
+        affine_cache(ctx, args)
+    elif args.affine:
         affine(ctx, args)
-    if args.cache:
+    elif args.cache:
         cache(ctx, args)
     if args.over:
         over(ctx, args)
@@ -455,6 +463,76 @@ def affine(ctx, args):
                 if k != "a":
                     out[f"{k}_over_a"] = round(med(ms[k]) / a, 2)
             out.update({"a_plan": plans["a"].describe(), "e_plan": plans["e"].describe()})
+            for plan in plans.values():
+                plan.close()
+            del bufs
+            dgs.close()
+            print(json.dumps(out), flush=True)
+
+
+def affine_store(gs, pl):
+    """-> (keys, bytes of the mask store) of the FR_TEXT_CACHE_AFFINE plan of rotated_runs' placements, all under one matrix
+    and none clipped: one cell per (glyph, both pen fractions), 2 bytes per element (include/fr_raster.h)"""
+    f = np.float32
+    m = pl["m"][0]
+    box = gs.boxes[pl["glyph"]].astype(f)
+    xs, ys = box[:, [0, 0, 2, 2]], box[:, [1, 3, 1, 3]]
+    u = (m[0] * xs).astype(f) + (m[1] * ys).astype(f)
+    v = (m[2] * xs).astype(f) + (m[3] * ys).astype(f)
+    fx, fy = pl["pen_x64"].astype(np.int64) & 63, pl["pen_y64"].astype(np.int64) & 63
+    cw = np.ceil(u.max(1)).astype(np.int64) - np.floor(u.min(1)).astype(np.int64) + 1 + (fx != 0)
+    ch = np.ceil(v.max(1)).astype(np.int64) - np.floor(v.min(1)).astype(np.int64) + 1 + (fy != 0)
+    drawn = gs.segments_per_glyph()[pl["glyph"]] > 0
+    keys = np.stack([pl["glyph"].astype(np.int64), fx, fy], 1)[drawn]
+    _, first = np.unique(keys, axis=0, return_index=True)
+    return len(first), int(2 * (cw[drawn][first] * ch[drawn][first]).sum())
+
+
+def affine_cache(ctx, args):
+    """--affine --cache: the five variants of --affine, each as the plain and as the cached plan; alternated, --repeats times"""
+    import re
+    import torch
+    ns, fill = args.samples, fr.FR_FILL_CONSISTENT if args.fill else 0
+    med = lambda v: sorted(v)[len(v) // 2]
+    for fi, name in enumerate(["DejaVuSans.ttf", "DejaVuSerif-Italic.ttf"]):
+        font = load_font(name, allow_hinted=True)
+        for size in (16, 32):
+            gs, places, runs, shape, _, _, _ = workload(font, args.lines, args.chars, size, seed=100 * fi + size)
+            ex = rg.make_places_ex([(int(p["glyph"]), int(p["pen_x64"]), 64 * int(p["pen_y"]), 0.0, 0.0) for p in places])
+            dgs = fr.DeviceGlyphSet(ctx, gs)
+            forms = {"a": (ex, runs, shape)}
+            for key, angle in (("b", 0), ("c", 5), ("d", 45), ("e", 90)):
+                forms[key] = rotated_runs(gs, places, runs, runs[0]["scale"], angle)
+            seg = gs.segments_per_glyph()
+            ekeys = sorted({(int(p["glyph"]), int(p["pen_x64"]) & 63) for p in places if seg[int(p["glyph"])]})
+            store = {"a": (len(ekeys), sum(2 * cw * ch for _, _, cw, ch in (fr.instance_cell(gs.boxes[g], runs[0]["scale"], fx, 0) for g, fx in ekeys)))}
+            store.update({k: affine_store(gs, forms[k][0]) for k in "bcde"})
+            plans, bufs = {}, {}
+            for k, (pl, rn, sh) in forms.items():
+                for c, flag in (("", 0), ("_cached", fr.FR_TEXT_CACHE if k == "a" else fr.FR_TEXT_CACHE_AFFINE)):
+                    plans[k + c] = fr.TextPlan(dgs, pl, rn, fr.FR_COVERAGE_U8, ns, fr.FR_SAMPLE_CENTER, fill | flag)
+                    bufs[k + c] = torch.zeros(sh, dtype=torch.uint8, device="cuda:0")
+            torch.cuda.synchronize()
+            ms = {k: [] for k in plans}
+            for _ in range(args.repeats):
+                for k, plan in plans.items():
+                    ms[k].append(timed(plan, bufs[k], forms[k[0]][2], args.steps, args.warmup))
+            out = {"case": "affine_cache", "font": name, "font_size": size, "lines": args.lines, "chars": args.chars, "samples": ns * ns,
+                   "steps": args.steps, "repeats": args.repeats}
+            for k in forms:
+                if not torch.equal(bufs[k], bufs[k + "_cached"]):
+                    raise SystemExit(f"--affine --cache: {name} {size} ({k}): the cached plan differs from the plain plan")
+                desc = plans[k + "_cached"].describe()
+                n_cells = int(re.search(r"glyph_mask(?:_affine)?_kernel<\d, \d> x(\d+)", desc).group(1))
+                if n_cells != store[k][0]:
+                    raise SystemExit(f"--affine --cache: {name} {size} ({k}): {n_cells} cells for {store[k][0]} keys")
+                out.update({f"{k}_instances": int(re.search(r"text_cached_kernel<\d> x(\d+)", desc).group(1)), f"{k}_cells": n_cells,
+                            f"{k}_mask_store_bytes": store[k][1], f"{k}_run_mpixel": round(plans[k].pixels / 1e6, 1)})
+                for c in ("", "_cached"):
+                    v = ms[k + c]
+                    out.update({f"{k}{c}_ms": round(med(v), 4), f"{k}{c}_min_ms": round(min(v), 4), f"{k}{c}_max_ms": round(max(v), 4)})
+                out[f"{k}_plain_over_cached"] = round(med(ms[k]) / med(ms[k + "_cached"]), 2)
+            out.update({"a_cached_plan": plans["a_cached"].describe(), "e_cached_plan": plans["e_cached"].describe()})
             for plan in plans.values():
                 plan.close()
             del bufs
