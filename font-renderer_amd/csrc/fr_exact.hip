@@ -4,6 +4,13 @@
 //
 // Bug-compatible by design (the reference marks it "still has some problem", :157-159):
 // the switch below follows the Zig arm by arm, including the -1 of .down_inv_u (:226).
+// A second deviation is kept the same way: a non-straight curve that is linear in y (ay == 0, so .up_normal /
+// .down_normal with |ax| >= 2).  With y(t) - p.y = ay t^2 + by t + cy and the same in x, the predicates compare
+// x(t) with p.x after multiplying through by ay: tmp = 2 ay (ax cy - ay cx) - by abxy.  At ay == 0 that leaves
+// abxy = ax by and tmp = -ax by^2, with no cx term, and dy = by^2, so dy abxy^2 == tmp^2 exactly: solve1 ends in
+// "l >= r" (ax < 0, tmp > 0) or "l <= r" (ax > 0, tmp < 0), both decided by that equality, and answers "crossing"
+// wherever p.x is.  Such a curve counts for every point of its rows, also those right of it (tests/test_exact_ref.py counts
+// both deviations against an independent crossing count).
 // Predicates are evaluated in 128-bit integers; the reference uses i64, which traps /
 // is undefined once dy*abxy*abxy leaves i64 — identical wherever the reference is defined.
 //
