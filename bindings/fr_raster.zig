@@ -40,7 +40,7 @@ pub const FR_TEXT_CACHE: u32 = 128;
 pub const FR_TEXT_OVER: u32 = 256;
 /// flag of the two _affine text plan entry points (fr_raster.h): FR_TEXT_CACHE for the matrix form, keyed by the bits of m
 pub const FR_TEXT_CACHE_AFFINE: u32 = 512;
-/// the flag space of fr_layer_over, fr_layer_shadow, fr_layer_rects, fr_layer_paint and fr_layer_lcd (fr_raster.h): composite in linear light
+/// the flag space of fr_layer_over, fr_layer_shadow, fr_layer_outline, fr_layer_rects, fr_layer_paint and fr_layer_lcd (fr_raster.h): composite in linear light
 pub const FR_LAYER_SRGB: u32 = 1;
 /// fr_layer_lcd alone, beside FR_LAYER_SRGB: memory byte b takes sub-pixel 2 - b (a B G R panel); the other layer calls refuse it
 pub const FR_LCD_BGR: u32 = 2;
@@ -126,6 +126,31 @@ pub const LayerShadowParams = extern struct {
     spread: u32,
     blur_radius: u32,
     blur_passes: u32,
+    rgba: [4]u8,
+};
+
+/// fr_layer_outline_params.kind: the grown shape, grown minus the layer, the layer minus its shrunk shape, the shrunk shape
+pub const FR_OUTLINE_GROW: u32 = 0;
+pub const FR_OUTLINE_RING: u32 = 1;
+pub const FR_OUTLINE_INNER: u32 = 2;
+pub const FR_OUTLINE_SHRINK: u32 = 3;
+/// the largest fr_layer_outline_params.radius, in 1/16 pixel
+pub const FR_OUTLINE_MAX_RADIUS: u32 = 256;
+
+/// the parameters of fr_layer_outline: the layer's window, the destination rectangle, the offset, the radius in 1/16 pixel, the kind and the colour
+pub const LayerOutlineParams = extern struct {
+    src_x: u32,
+    src_y: u32,
+    w: u32,
+    h: u32,
+    dst_x: u32,
+    dst_y: u32,
+    dst_w: u32,
+    dst_h: u32,
+    dx: i32,
+    dy: i32,
+    radius: u32,
+    kind: u32,
     rgba: [4]u8,
 };
 
@@ -283,6 +308,8 @@ pub extern "c" fn fr_layer_over(ctx: *Ctx, src_dev: *const anyopaque, src_stride
 pub extern "c" fn fr_layer_unpremultiply(ctx: *Ctx, rgba_dev: *anyopaque, stride_px: usize, w: u32, h: u32, srgb: c_int) c_int;
 /// the alpha of a layer's window, spread, box-blurred, moved and tinted: a premultiplied layer written over a rectangle of the destination
 pub extern "c" fn fr_layer_shadow(ctx: *Ctx, src_dev: *const anyopaque, src_stride_px: usize, src_rows: usize, dst_dev: *anyopaque, dst_stride_px: usize, dst_rows: usize, shadow: *const LayerShadowParams, flags: u32) c_int;
+/// the alpha of a layer's window grown or shrunk by a disc, combined with the layer by the kind, moved and tinted: a premultiplied layer written over a rectangle of the destination
+pub extern "c" fn fr_layer_outline(ctx: *Ctx, src_dev: *const anyopaque, src_stride_px: usize, src_rows: usize, dst_dev: *anyopaque, dst_stride_px: usize, dst_rows: usize, outline: *const LayerOutlineParams, flags: u32) c_int;
 /// anti-aliased rectangles, each in one straight colour, composited in order over a premultiplied image in device memory
 pub extern "c" fn fr_layer_rects(ctx: *Ctx, dst_dev: *anyopaque, dst_stride_px: usize, dst_rows: usize, rects: ?[*]const LayerRect, n_rects: u32, flags: u32) c_int;
 /// a linear or radial gradient composited over a premultiplied image through the alpha of a layer's window (src_dev null: full coverage)

@@ -17,6 +17,8 @@ FR_TEXT_CACHE_AFFINE = 512         # the matrix-form text plans: FR_TEXT_CACHE k
 FR_LAYER_SRGB = 1              # the flag space of the fr_layer_over / _shadow / _rects / _paint calls: work in linear light
 FR_LCD_BGR = 2                     # fr_layer_lcd alone, beside FR_LAYER_SRGB: memory byte b takes sub-pixel 2 - b
 FR_LCD_TAPS = 5                    # the length of fr_layer_lcd's filter
+FR_OUTLINE_GROW, FR_OUTLINE_RING, FR_OUTLINE_INNER, FR_OUTLINE_SHRINK = 0, 1, 2, 3      # fr_layer_outline_params.kind
+FR_OUTLINE_MAX_RADIUS = 256        # fr_layer_outline_params.radius, in 1/16 pixel
 FR_GRADIENT_LINEAR, FR_GRADIENT_RADIAL = 0, 1                   # fr_layer_paint_params.kind
 FR_SPREAD_PAD, FR_SPREAD_REPEAT, FR_SPREAD_REFLECT = 0, 1, 2    # fr_layer_paint_params.spread
 FR_GRADIENT_MAX_STOPS = 8
@@ -80,6 +82,12 @@ class LayerShadowParams(C.Structure):    # == fr_layer_shadow_params
                 ("dst_x", C.c_uint32), ("dst_y", C.c_uint32), ("dst_w", C.c_uint32), ("dst_h", C.c_uint32),
                 ("dx", C.c_int32), ("dy", C.c_int32), ("spread", C.c_uint32), ("blur_radius", C.c_uint32),
                 ("blur_passes", C.c_uint32), ("rgba", C.c_uint8 * 4)]
+
+
+class LayerOutlineParams(C.Structure):   # == fr_layer_outline_params
+    _fields_ = [("src_x", C.c_uint32), ("src_y", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32),
+                ("dst_x", C.c_uint32), ("dst_y", C.c_uint32), ("dst_w", C.c_uint32), ("dst_h", C.c_uint32),
+                ("dx", C.c_int32), ("dy", C.c_int32), ("radius", C.c_uint32), ("kind", C.c_uint32), ("rgba", C.c_uint8 * 4)]
 
 
 class LayerRect(C.Structure):    # == fr_layer_rect
@@ -177,6 +185,7 @@ SYMBOLS = [
     ("fr_layer_over", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, _P, C.c_uint32, C.c_uint32]),
     ("fr_layer_unpremultiply", C.c_int, [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.c_int]),
     ("fr_layer_shadow", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.POINTER(LayerShadowParams), C.c_uint32]),
+    ("fr_layer_outline", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.POINTER(LayerOutlineParams), C.c_uint32]),
     ("fr_layer_rects", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_uint32, C.c_uint32]),
     ("fr_layer_paint", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.POINTER(LayerPaintParams), C.c_uint32]),
     ("fr_layer_lcd", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, _P, C.c_uint32, C.POINTER(C.c_uint16), C.c_uint32]),

@@ -1,12 +1,14 @@
-// fr_api_layer.hip — C ABI (include/fr_raster.h): fr_layer_over, fr_layer_unpremultiply, fr_layer_shadow, fr_layer_rects,
-// fr_layer_paint and fr_layer_lcd.  The checks, the clipping and the tile table are fr_layer_plan.cpp's, the shadow's stages
-// fr_layer_shadow_plan.cpp's, the rectangles' tables fr_layer_rects_plan.cpp's, the gradient's coefficients and colour table
-// fr_layer_paint_plan.cpp's, the sub-pixel blits' tiles fr_layer_lcd_plan.cpp's; this unit stages the tables, keeps the
-// shadow's planes and launches the kernels of fr_layer.hip, fr_layer_shadow.hip, fr_layer_rects.hip, fr_layer_paint.hip and
+// fr_api_layer.hip — C ABI (include/fr_raster.h): fr_layer_over, fr_layer_unpremultiply, fr_layer_shadow, fr_layer_outline,
+// fr_layer_rects, fr_layer_paint and fr_layer_lcd.  The checks, the clipping and the tile table are fr_layer_plan.cpp's, the
+// shadow's stages fr_layer_shadow_plan.cpp's, the outline's rectangles and weights fr_layer_outline_plan.cpp's, the
+// rectangles' tables fr_layer_rects_plan.cpp's, the gradient's coefficients and colour table fr_layer_paint_plan.cpp's, the
+// sub-pixel blits' tiles fr_layer_lcd_plan.cpp's; this unit stages the tables, keeps the shadow's planes and launches the
+// kernels of fr_layer.hip, fr_layer_shadow.hip, fr_layer_outline.hip, fr_layer_rects.hip, fr_layer_paint.hip and
 // fr_layer_lcd.hip.
 #include "fr_internal.hpp"
 #include "fr_layer.hpp"
 #include "fr_layer_lcd.hpp"
+#include "fr_layer_outline.hpp"
 #include "fr_layer_paint.hpp"
 #include "fr_layer_rects.hpp"
 #include "fr_layer_shadow.hpp"
@@ -171,6 +173,68 @@ int fr_layer_shadow(fr_ctx *ctx, const void *src_dev, size_t src_stride_px, size
             in_rect = st.out;
         }
     }
+    return FR_OK;
+}
+
+int fr_layer_outline(fr_ctx *ctx, const void *src_dev, size_t src_stride_px, size_t src_rows, void *dst_dev, size_t dst_stride_px,
+                     size_t dst_rows, const fr_layer_outline_params *outline, uint32_t flags)
+{
+    if (!ctx) return fail(FR_E_INVALID, "fr_layer_outline: ctx is NULL");
+    fr::OutlinePlan p;
+    try {
+        const fr::OutlineIn in{(uintptr_t)src_dev, (uintptr_t)dst_dev, src_stride_px, src_rows, dst_stride_px, dst_rows, outline, flags};
+        if (const int rc = fr::outline_plan(in, p)) return rc;
+    } catch (const std::bad_alloc &) {
+        return fail(FR_E_NOMEM, "fr_layer_outline: host allocation");
+    }
+    if (p.nothing) return FR_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const fr_layer_outline_params &s = *outline;
+    uint32_t *const first = static_cast<uint32_t *>(dst_dev) + ((uint64_t)s.dst_y * dst_stride_px + s.dst_x);
+    const uint32_t rgba = (uint32_t)s.rgba[0] | (uint32_t)s.rgba[1] << 8 | (uint32_t)s.rgba[2] << 16 | (uint32_t)s.rgba[3] << 24;
+    if (p.zeros) {                                              // the shadow's extract-and-tint over an input without extent
+        fr::ShadowArgs z{};
+        z.in = src_dev;
+        z.in_pitch = src_stride_px;
+        z.out = first;
+        z.out_pitch = dst_stride_px;
+        z.out_w = s.dst_w;
+        z.out_h = s.dst_h;
+        z.vec = p.vec;
+        z.lead = p.lead;
+        z.rgba = rgba;
+        z.srgb = flags & FR_LAYER_SRGB;
+        HIP_TRY(fr::launch_layer_shadow(true, fr::SHADOW_OP_NONE, true, z, ctx->stream));
+        return FR_OK;
+    }
+    const uint4 *tab = nullptr;
+    if (const int rc = layer_tables_to_device(ctx, p.table.units(), &tab, [&](uint4 *to) { memcpy(to, p.table.packed.data(), p.table.packed.size() * sizeof(uint32_t)); }))
+        return rc;
+    fr::OutlineArgs a{};
+    a.in = static_cast<const uint32_t *>(src_dev) + ((uint64_t)s.src_y * src_stride_px + s.src_x);
+    a.out = first;
+    a.table = tab;
+    a.units = (uint32_t)p.table.units();
+    a.in_pitch = src_stride_px;
+    a.out_pitch = dst_stride_px;
+    a.off_x = p.want.x0;
+    a.off_y = p.want.y0;
+    a.in_w = s.w;
+    a.in_h = s.h;
+    a.out_w = s.dst_w;
+    a.out_h = s.dst_h;
+    a.live_x0 = (uint32_t)(p.live.x0 - p.want.x0);
+    a.live_y0 = (uint32_t)(p.live.y0 - p.want.y0);
+    a.live_x1 = (uint32_t)(p.live.x1 - p.want.x0);
+    a.live_y1 = (uint32_t)(p.live.y1 - p.want.y0);
+    a.reach = p.table.reach;
+    a.levels = p.table.levels;
+    a.lead = p.lead;
+    a.vec = p.vec;
+    a.rgba = rgba;
+    a.srgb = flags & FR_LAYER_SRGB;
+    a.tiles_x = (uint32_t)p.tiles_x;
+    HIP_TRY(fr::launch_layer_outline(s.kind, (uint32_t)(p.tiles_x * p.tiles_y), a, ctx->stream));
     return FR_OK;
 }
 

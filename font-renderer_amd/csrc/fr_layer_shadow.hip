@@ -3,26 +3,13 @@
 // destination.  One kernel, instantiated per input, operation and output; the host side (fr_layer_shadow_plan.cpp) lists
 // the stages and their rectangles.
 #include "fr_layer_shadow.hpp"
-#include "fr_srgb.hpp"
-#include "fr_text_colour.hpp"
+#include "fr_layer_tint.hpp"
 
 namespace fr {
 
 namespace {
 
-constexpr uint32_t M2 = 0x00ff00ffu, HALF2 = 0x00800080u;
 constexpr uint32_t T = SHADOW_TILE, THREADS = 256;
-
-// the stored element for one alpha: (m(R, a), m(G, a), m(B, a), a) or its sRGB form, a = m(alpha, A)
-__device__ __forceinline__ uint32_t tint_of(uint32_t alpha, uint32_t rgba, uint32_t srgb)
-{
-    const uint32_t a = blend2(alpha, HALF2, rgba >> 24) & 0xffu;
-    if (!srgb) return blend2(rgba & M2, HALF2, a) | blend2((rgba >> 8) & 0xffu, HALF2, a) << 8 | a << 24;
-    uint32_t out = a << 24;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) out |= srgb_encode(SRGB_K, div255_24((uint32_t)SRGB_D[(rgba >> (8 * c)) & 0xffu] * a + 127u)) << (8 * c);
-    return out;
-}
 
 __device__ __forceinline__ int32_t clamp_to(int64_t v, int32_t hi) { return (int32_t)(v < 0 ? 0 : v > hi ? hi : v); }
 
@@ -154,13 +141,7 @@ __global__ __launch_bounds__(THREADS) void layer_shadow_kernel(ShadowArgs a)
             if (y >= a.out_h) continue;
             const uint32_t al = *reinterpret_cast<const uint32_t *>(res + row * RP + 4u * g);
             uint32_t *p = static_cast<uint32_t *>(a.out) + ((int64_t)((uint64_t)y * a.out_pitch) + X0);
-            if (valid == 15u && a.vec) {
-                *reinterpret_cast<uint4 *>(p) = make_uint4(lut[al & 0xffu], lut[(al >> 8) & 0xffu], lut[(al >> 16) & 0xffu], lut[al >> 24]);
-            } else {
-#pragma unroll
-                for (uint32_t i = 0; i < 4u; ++i)
-                    if (valid >> i & 1u) p[i] = lut[(al >> (8u * i)) & 0xffu];
-            }
+            store_tinted4(p, al, valid, a.vec, lut);
         }
     }
 }

@@ -215,6 +215,16 @@ inline void layer_shadow(Context &ctx, const DeviceImage &layer, const DeviceIma
     check(fr_layer_shadow(ctx.get(), layer.pixels, layer.stride_px, layer.rows, image.pixels, image.stride_px, image.rows, &shadow,
                           srgb ? FR_LAYER_SRGB : 0u));
 }
+// fr_layer_outline: the alpha of a window of the layer grown or shrunk by a disc of outline.radius / 16 pixels, combined with
+// the layer as outline.kind says (FR_OUTLINE_GROW / _RING / _INNER / _SHRINK), moved by whole pixels and tinted, written as a
+// premultiplied R G B A layer over every pixel of the rectangle of `image` that `outline` names.  Composite a GROW outline
+// with layer_over, then the text over it; an INNER line goes over the text.  Asynchronous on the context's stream; `outline`
+// may be reused at once.
+inline void layer_outline(Context &ctx, const DeviceImage &layer, const DeviceImage &image, const fr_layer_outline_params &outline, bool srgb = false)
+{
+    check(fr_layer_outline(ctx.get(), layer.pixels, layer.stride_px, layer.rows, image.pixels, image.stride_px, image.rows, &outline,
+                           srgb ? FR_LAYER_SRGB : 0u));
+}
 // fr_layer_rects: anti-aliased rectangles (edges in 1/64 pixel, one straight colour each) composited in order over the
 // premultiplied `image`: underlines, strike-outs, highlights, carets, panels.  They may overlap.  Asynchronous on the
 // context's stream; `rects` may be reused at once.

@@ -10,7 +10,7 @@ import numpy as np
 from . import _lib as L
 from .device import default_context, round_trip
 from .glyph import GlyphSet
-from .layer import layer_lcd, layer_over, layer_paint, layer_rects, layer_shadow, layer_unpremultiply, make_blits, make_lcd_blits, make_rects
+from .layer import layer_lcd, layer_outline, layer_over, layer_paint, layer_rects, layer_shadow, layer_unpremultiply, make_blits, make_lcd_blits, make_rects
 
 
 def q64(v) -> int:
@@ -237,6 +237,28 @@ class RGBA:                     # an RGBA text plan's image (fr_text_plan_create
         out.data[:] = round_trip(ctx, lambda s, d: layer_shadow(
             ctx, s, self.width, self.height, d, out.width, out.height, (0, 0, self.width, self.height), (0, 0, out.width, out.height),
             (int(offset[0]) + pad, int(offset[1]) + pad), spread, blur_radius, blur_passes, rgba, srgb), src, out.data.shape, back=1)
+        return out
+
+    def outline(self, radius: int, kind: int = L.FR_OUTLINE_GROW, rgba=(0, 0, 0, 255), offset=(0, 0), pad: int = None,
+                srgb: bool = False, ctx=None) -> "RGBA":
+        """fr_layer_outline of this premultiplied layer as a new premultiplied layer, `pad` pixels larger on every side
+        (default: the reach ceil(radius / 16), which holds the whole outline at offset (0, 0)); radius is in sixteenths of a
+        pixel and kind one of FR_OUTLINE_GROW / _RING / _INNER / _SHRINK.  Pixel (pad, pad) of the result lies under pixel
+        (0, 0) of this layer moved by `offset`: composite a GROW outline with over(..., x - pad, y - pad), then this layer at
+        (x, y); an INNER line goes over the layer.  The layer is uploaded and the outline copied back."""
+        src = rgba_pixels(self, "RGBA.outline").reshape(-1)
+        pad = (int(radius) + 15) // 16 if pad is None else int(pad)
+        if pad < 0:
+            raise ValueError(f"pad {pad!r}: expected at least 0")
+        out = RGBA.init(self.width + 2 * pad, self.height + 2 * pad)
+        if out.width == 0 or out.height == 0:
+            return out
+        ctx = ctx or default_context()
+        if src.size == 0:
+            src = np.zeros(4, np.uint8)                     # an empty layer still needs an address
+        out.data[:] = round_trip(ctx, lambda s, d: layer_outline(
+            ctx, s, self.width, self.height, d, out.width, out.height, (0, 0, self.width, self.height), (0, 0, out.width, out.height),
+            (int(offset[0]) + pad, int(offset[1]) + pad), radius, kind, rgba, srgb), src, out.data.shape, back=1)
         return out
 
     def getWidth(self) -> int:

@@ -1,5 +1,5 @@
 """The layer calls of the C ABI (fr_layer_*, include/fr_raster.h) on device addresses, and the builders of their tables.
-All of them are asynchronous on the context's stream; RGBA.over / fill_rects / paint / draw_lcd / shadow / unpremultiply
+All of them are asynchronous on the context's stream; RGBA.over / fill_rects / paint / draw_lcd / shadow / outline / unpremultiply
 (image.py) wrap them for host images."""
 from __future__ import annotations
 
@@ -144,3 +144,21 @@ def layer_shadow(ctx: Context, src_ptr: int, src_stride_px: int, src_rows: int, 
                                 int(blur_radius), int(blur_passes), (C.c_uint8 * 4)(*[int(v) for v in rgba]))
     L.check(ctx._lib.fr_layer_shadow(ctx._h, C.c_void_p(src_ptr), src_stride_px, src_rows, C.c_void_p(dst_ptr), dst_stride_px, dst_rows,
                                      None if p is None else C.byref(p), _flags(flags, srgb)))
+
+
+def layer_outline(ctx: Context, src_ptr: int, src_stride_px: int, src_rows: int, dst_ptr: int, dst_stride_px: int, dst_rows: int,
+                  window, rect, offset=(0, 0), radius: int = 16, kind: int = L.FR_OUTLINE_GROW, rgba=(0, 0, 0, 255),
+                  srgb: bool = False, flags: int = 0) -> None:
+    """fr_layer_outline: the alpha of the window (src_x, src_y, w, h) of the premultiplied layer at device address src_ptr,
+    grown or shrunk by a disc of `radius` sixteenths of a pixel (0 .. FR_OUTLINE_MAX_RADIUS) as `kind` says (FR_OUTLINE_GROW:
+    the grown shape, _RING: grown minus the layer, _INNER: the layer minus its shrunk shape, _SHRINK: the shrunk shape), moved
+    by offset = (dx, dy) whole pixels and tinted with the straight colour rgba, written as a premultiplied R G B A layer over
+    every pixel of rect = (dst_x, dst_y, dst_w, dst_h) of the image at dst_ptr (strides and rows in pixels); asynchronous
+    on the context's stream.  srgb: FR_LAYER_SRGB, the colour bytes as an srgb=True render writes them.  window or rect
+    None passes a NULL parameter block (refused)."""
+    p = None
+    if window is not None and rect is not None:
+        p = L.LayerOutlineParams(*[int(v) for v in window], *[int(v) for v in rect], int(offset[0]), int(offset[1]), int(radius), int(kind),
+                                 (C.c_uint8 * 4)(*[int(v) for v in rgba]))
+    L.check(ctx._lib.fr_layer_outline(ctx._h, C.c_void_p(src_ptr), src_stride_px, src_rows, C.c_void_p(dst_ptr), dst_stride_px, dst_rows,
+                                      None if p is None else C.byref(p), _flags(flags, srgb)))

@@ -727,9 +727,9 @@ int fr_rgba_unpremultiply(uint8_t *rgba, size_t n_pixels, int srgb);
  *     all blits of the call, behind a small kernel that brings the call's tile table into device memory; asynchronous on
  *     the context's stream, in stream order after earlier renders as fr_plan_render is; the caller may reuse `blits` as
  *     soon as the call returns.
- * FR_LAYER_SRGB is the flag space of fr_layer_over, fr_layer_shadow, fr_layer_rects, fr_layer_paint and fr_layer_lcd: no other
- * entry point knows it, and these know none of the FR_TEXT_ / FR_FILL_ flags.  (FR_LCD_BGR = 2 is fr_layer_lcd's alone: the
- * other four refuse it as an unknown bit.)                                                                                      */
+ * FR_LAYER_SRGB is the flag space of fr_layer_over, fr_layer_shadow, fr_layer_outline, fr_layer_rects, fr_layer_paint and
+ * fr_layer_lcd: no other entry point knows it, and these know none of the FR_TEXT_ / FR_FILL_ flags.  (FR_LCD_BGR = 2 is
+ * fr_layer_lcd's alone: the others refuse it as an unknown bit.)                                                              */
 #define FR_LAYER_SRGB 1u
 
 typedef struct fr_layer_blit {
@@ -806,6 +806,80 @@ typedef struct fr_layer_shadow_params {
 int fr_layer_shadow(fr_ctx *ctx, const void *src_dev, size_t src_stride_px, size_t src_rows,
                     void *dst_dev, size_t dst_stride_px, size_t dst_rows,
                     const fr_layer_shadow_params *shadow, uint32_t flags);   /* 0 or FR_LAYER_SRGB */
+
+/* ---- round outlines of a finished layer (BUILD-DEFINED; DESIGN.md sections 4.13 and 5) -----------------------------------
+ * fr_layer_outline grows or shrinks the shape of a layer by a disc of radius rho / 16 pixels, anti-aliased, and tints the
+ * result: an outline to composite under the text (GROW), the outline alone for hollow or translucent text (RING), a line
+ * inside the edge to draw over the text (INNER), or the shrunk shape (SHRINK).  The result is itself a premultiplied layer
+ * (R G B A, alpha last), as fr_layer_shadow's is.  A spread of fr_layer_shadow is a maximum over a square, so its outlines
+ * have square corners and whole-pixel widths; this maximum is weighted by a disc.
+ *   All arithmetic is in integers; m, D and E are as defined above.
+ *   Source alpha: A0(u, v) is exactly fr_layer_shadow's: the alpha byte of layer pixel (src_x + u, src_y + v) for
+ *     0 <= u < w, 0 <= v < h, and 0 everywhere else on the integer plane.  No layer byte outside the window is read, and
+ *     only alpha is read.
+ *   Disc weight, for an integer offset (i, j), with rho = radius:
+ *       q = isqrt(65536 (i^2 + j^2))                      (the floor of 256 times the distance)
+ *       t = 16 rho + 256 - q
+ *       K(i, j) = 0 if t <= 0, else min(255, (255 t + 128) div 256)
+ *     a linear ramp one pixel wide that ends at distance rho / 16 + 1.  K(0, 0) = 255 for every rho, and K is 0 beyond
+ *     Chebyshev distance R = ceil(rho / 16).
+ *   Grow:   G[A](u, v) = max of m(A(u + i, v + j), K(i, j)) over |i| <= R, |j| <= R.
+ *   Shrink: S(u, v) = 255 - G[255 - A0](u, v); the complement 255 - A0 is 255 outside the window.
+ *   Alpha by kind:
+ *       FR_OUTLINE_GROW    G[A0]
+ *       FR_OUTLINE_RING    G[A0] - A0        (never negative: K(0, 0) = 255 and m(a, 255) = a)
+ *       FR_OUTLINE_INNER   A0 - S
+ *       FR_OUTLINE_SHRINK  S
+ *   Tint and writes: fr_layer_shadow's, word for word.  For pixel (X, Y) of the destination rectangle, 0 <= X < dst_w,
+ *     0 <= Y < dst_h: alpha is the kind's alpha at (X - dx, Y - dy), a = m(alpha, rgba[3]), and
+ *       stored = (m(R, a), m(G, a), m(B, a), a)                                              (flags = 0)
+ *       stored = (E((D[R] * a + 127) div 255), E((D[G] * a + 127) div 255), E((D[B] * a + 127) div 255), a)   (FR_LAYER_SRGB)
+ *     Every pixel of the destination rectangle is written and none of it is read.  No byte of the destination outside the
+ *     rectangle is read or written.  No layer byte is written.
+ *   Consequences:
+ *     1. rho = 0, GROW: the bytes of fr_layer_shadow with no stage and the same colour, in both colour spaces.  RING and
+ *        INNER give zeros, SHRINK equals GROW.
+ *     2. One pixel of alpha 255, GROW, colour (255, 255, 255, 255): the alpha plane is the table K around it.
+ *     3. rho = 16 k: a vertical or horizontal edge moves by exactly k pixels: columns 255 .. 255, 128, 0 .. become the same
+ *        row shifted by k.  rho = 8 puts K(1, 0) = 128 on the first pixel beyond a hard edge.
+ *     4. shadow(no stage) <= GROW <= shadow(spread = R, no blur) pointwise in alpha.  GROW is non-zero only within Chebyshev
+ *        distance R of a window pixel with non-zero alpha; INNER and SHRINK are zero outside the window.
+ *     5. Adding 1 to dx or dy moves the image by exactly one column or row.
+ *     6. The definition has the square's eight symmetries: a transposed or mirrored window gives the transposed or mirrored
+ *        image.
+ *     7. GROW does not decrease and SHRINK does not increase as rho grows.
+ *     The maximum of the raw products A * K followed by one (x + 127) div 255 equals the maximum of the m's (m is monotone),
+ *     which is how the kernel evaluates it.
+ *   Validation, in this order.  FR_E_INVALID: NULL ctx; an unknown flag bit; a NULL or not 4-byte aligned image pointer,
+ *     or a stride beyond 2^26 (the layer, then the destination).  FR_E_UNSUPPORTED: an image of 2^31 rows or more.
+ *     FR_E_INVALID: NULL `outline`; a window of non-zero area that is not inside the layer; a rectangle of non-zero area
+ *     that is not inside dst_stride_px x dst_rows; radius > FR_OUTLINE_MAX_RADIUS or kind > FR_OUTLINE_SHRINK; overlapping
+ *     byte ranges of the two images.  FR_E_UNSUPPORTED: a rectangle of more than 2^22 tiles of 64 x 64 pixels, counted as
+ *     ceil((dst_w + 3) / 64) * ceil(dst_h / 64).  w, h, dst_w or dst_h of 0 is valid: dst_w = 0 or dst_h = 0 writes nothing,
+ *     a window of zero area writes zeros over the rectangle for every kind.  Any int32 dx or dy is valid.
+ *   Execution: one launch of layer_outline_kernel behind the small kernel that brings the call's weight table into device
+ *     memory, with no intermediate plane; asynchronous on the context's stream, in stream order with renders, composites
+ *     and shadows.  A rectangle that the outline cannot reach takes fr_layer_shadow's zero-writing launch.  The caller may
+ *     reuse `outline` as soon as the call returns.                                                                          */
+#define FR_OUTLINE_GROW   0u   /* the layer's shape grown by the radius: composite it under the text      */
+#define FR_OUTLINE_RING   1u   /* grown minus the layer: the outline alone (hollow or translucent text)    */
+#define FR_OUTLINE_INNER  2u   /* the layer minus its shrunk shape: a line inside the edge, drawn over it   */
+#define FR_OUTLINE_SHRINK 3u   /* the layer's shape shrunk by the radius                                    */
+#define FR_OUTLINE_MAX_RADIUS 256u
+
+typedef struct fr_layer_outline_params {
+    uint32_t src_x, src_y, w, h;          /* the window of the layer, as fr_layer_shadow_params        */
+    uint32_t dst_x, dst_y, dst_w, dst_h;  /* the rectangle of the destination that receives it         */
+    int32_t  dx, dy;                      /* destination pixel (X, Y) of the rectangle shows window
+                                             coordinate (X - dx, Y - dy)                               */
+    uint32_t radius;                      /* rho, in 1/16 pixel, 0 .. 256 (16 pixels)                  */
+    uint32_t kind;                        /* FR_OUTLINE_*                                              */
+    uint8_t  rgba[4];                     /* the outline's colour, straight R G B A                    */
+} fr_layer_outline_params;
+
+int fr_layer_outline(fr_ctx *ctx, const void *src_dev, size_t src_stride_px, size_t src_rows,
+                     void *dst_dev, size_t dst_stride_px, size_t dst_rows,
+                     const fr_layer_outline_params *outline, uint32_t flags);   /* 0 or FR_LAYER_SRGB */
 
 /* ---- anti-aliased rectangles over an image (BUILD-DEFINED; DESIGN.md sections 4.10 and 5) ----------------------------------
  * fr_layer_rects fills axis-aligned rectangles with sub-pixel edges, each in one straight colour, over a premultiplied
