@@ -46,6 +46,10 @@ pub const FR_LAYER_SRGB: u32 = 1;
 pub const FR_LCD_BGR: u32 = 2;
 /// the length of fr_layer_lcd's filter
 pub const FR_LCD_TAPS = 5;
+/// fr_layer_mask alone, beside FR_LAYER_SRGB: the mask is a plane of 1-byte elements (a coverage plan's output), any alignment
+pub const FR_MASK_PLANE: u32 = 4;
+/// fr_layer_mask alone: no layer, the destination is multiplied by 255 - t (destination-out)
+pub const FR_MASK_ERASE: u32 = 8;
 /// LayerPaintParams.kind and .spread (fr_raster.h: fr_layer_paint)
 pub const FR_GRADIENT_LINEAR: u32 = 0;
 pub const FR_GRADIENT_RADIAL: u32 = 1;
@@ -200,6 +204,21 @@ pub const LcdBlit = extern struct {
     rgba: [4]u8,
 };
 
+/// one rectangle of fr_layer_mask: where it lies in the layer (not used when erasing), where it lands, the mask element over
+/// its top-left pixel, the opacity in 0 .. 255 and whether the mask is complemented (0 or 1)
+pub const LayerMaskBlit = extern struct {
+    src_x: u32,
+    src_y: u32,
+    w: u32,
+    h: u32,
+    dst_x: i32,
+    dst_y: i32,
+    mask_x: u32,
+    mask_y: u32,
+    opacity: u32,
+    invert: u32,
+};
+
 /// fr_font_line_metrics: hhea, post and OS/2 in font units, y up; present bit 0: post, bit 1: OS/2
 pub const FontLine = extern struct {
     ascender: i16,
@@ -316,6 +335,8 @@ pub extern "c" fn fr_layer_rects(ctx: *Ctx, dst_dev: *anyopaque, dst_stride_px: 
 pub extern "c" fn fr_layer_paint(ctx: *Ctx, src_dev: ?*const anyopaque, src_stride_px: usize, src_rows: usize, dst_dev: *anyopaque, dst_stride_px: usize, dst_rows: usize, paint: *const LayerPaintParams, flags: u32) c_int;
 /// sub-pixel (LCD) text: windows of a 3x-wide coverage plane filtered across sub-pixels (weights: FR_LCD_TAPS values adding up to 256, null: the default) and composited with an alpha per colour byte
 pub extern "c" fn fr_layer_lcd(ctx: *Ctx, cov_dev: *const anyopaque, cov_stride: usize, cov_rows: usize, dst_dev: *anyopaque, dst_stride_px: usize, dst_rows: usize, blits: ?[*]const LcdBlit, n_blits: u32, weights: ?*const [FR_LCD_TAPS]u16, flags: u32) c_int;
+/// rectangles of a premultiplied layer over a premultiplied image at an opacity per pixel taken from a mask (a layer's alpha, or with FR_MASK_PLANE a plane of bytes); with FR_MASK_ERASE (src_dev null) the mask lowers the image instead
+pub extern "c" fn fr_layer_mask(ctx: *Ctx, src_dev: ?*const anyopaque, src_stride_px: usize, src_rows: usize, mask_dev: *const anyopaque, mask_stride: usize, mask_rows: usize, dst_dev: *anyopaque, dst_stride_px: usize, dst_rows: usize, blits: ?[*]const LayerMaskBlit, n_blits: u32, flags: u32) c_int;
 // ---- self-tests of the two arithmetic shortcuts (device-side, exhaustive)
 pub extern "c" fn fr_selftest_division(d_lo: u32, d_hi: u32, mismatches: *u64, bad_divisor: ?*u32, bad_x_bits: ?*u32) c_int;
 pub extern "c" fn fr_selftest_sqrt(mismatches: *u64, bad_x_bits: ?*u32) c_int;

@@ -17,6 +17,7 @@ FR_TEXT_CACHE_AFFINE = 512         # the matrix-form text plans: FR_TEXT_CACHE k
 FR_LAYER_SRGB = 1              # the flag space of the fr_layer_over / _shadow / _rects / _paint calls: work in linear light
 FR_LCD_BGR = 2                     # fr_layer_lcd alone, beside FR_LAYER_SRGB: memory byte b takes sub-pixel 2 - b
 FR_LCD_TAPS = 5                    # the length of fr_layer_lcd's filter
+FR_MASK_PLANE, FR_MASK_ERASE = 4, 8    # fr_layer_mask alone: the mask is a plane of bytes; no layer, the destination is erased
 FR_OUTLINE_GROW, FR_OUTLINE_RING, FR_OUTLINE_INNER, FR_OUTLINE_SHRINK = 0, 1, 2, 3      # fr_layer_outline_params.kind
 FR_OUTLINE_MAX_RADIUS = 256        # fr_layer_outline_params.radius, in 1/16 pixel
 FR_GRADIENT_LINEAR, FR_GRADIENT_RADIAL = 0, 1                   # fr_layer_paint_params.kind
@@ -70,6 +71,12 @@ class TextRun(C.Structure):      # == fr_text_run
 class LayerBlit(C.Structure):    # == fr_layer_blit
     _fields_ = [("src_x", C.c_uint32), ("src_y", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32),
                 ("dst_x", C.c_int32), ("dst_y", C.c_int32), ("opacity", C.c_uint32)]
+
+
+class LayerMaskBlit(C.Structure):    # == fr_layer_mask_blit
+    _fields_ = [("src_x", C.c_uint32), ("src_y", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32),
+                ("dst_x", C.c_int32), ("dst_y", C.c_int32), ("mask_x", C.c_uint32), ("mask_y", C.c_uint32),
+                ("opacity", C.c_uint32), ("invert", C.c_uint32)]
 
 
 class LcdBlit(C.Structure):      # == fr_lcd_blit
@@ -189,6 +196,7 @@ SYMBOLS = [
     ("fr_layer_rects", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_uint32, C.c_uint32]),
     ("fr_layer_paint", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.POINTER(LayerPaintParams), C.c_uint32]),
     ("fr_layer_lcd", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, _P, C.c_uint32, C.POINTER(C.c_uint16), C.c_uint32]),
+    ("fr_layer_mask", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, _P, C.c_uint32, C.c_uint32]),
     ("fr_selftest_sqrt", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     ("fr_selftest_division", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("fr_selftest_row_cuts", C.c_int, [_P, _P, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),

@@ -1,7 +1,8 @@
 // fr_layer_px.hpp — source-over of one premultiplied pixel, for the kernels that composite onto an image: layer_over_kernel
-// (fr_layer.hip), layer_rects_kernel (fr_layer_rects.hip) and layer_paint_kernel (fr_layer_paint.hip), and its variant with
-// one alpha per colour byte for layer_lcd_kernel (fr_layer_lcd.hip).  The arithmetic is that of the text plans' colour body
-// (fr_text_colour.hpp), per pixel instead of per sample.
+// (fr_layer.hip), layer_rects_kernel (fr_layer_rects.hip), layer_paint_kernel (fr_layer_paint.hip) and layer_mask_kernel
+// (fr_layer_mask.hip) with its erase, and its variant with one alpha per colour byte for layer_lcd_kernel
+// (fr_layer_lcd.hip).  The arithmetic is that of the text plans' colour body (fr_text_colour.hpp), per pixel instead of per
+// sample.
 #pragma once
 #include "fr_text_colour.hpp"
 
@@ -45,6 +46,26 @@ __device__ __forceinline__ uint32_t over_px(uint32_t s, uint32_t d, uint32_t o, 
             uint32_t S = D[(s >> (8 * c)) & 0xffu];
             if (OPACITY) S = div255_24(S * o + 127u);
             const uint32_t L = min(65535u, S + div255_24((uint32_t)D[(d >> (8 * c)) & 0xffu] * ia + 127u));
+            out = (out >> 8) | (srgb_encode(K, L) << 24);
+        }
+        return (out >> 8) | (r1a & 0x00ff0000u) << 8;          // alpha is stored linearly
+    }
+}
+
+// The erase of fr_layer_mask for one pixel: d times 255 - t (destination-out).  t == 0 gives d (m(x, 255) = x, E(D[v]) = v)
+// and t == 255 gives 0 whatever d is, so the caller may pass anything for a destination it did not load.
+template <int SRGB>
+__device__ __forceinline__ uint32_t erase_px(uint32_t d, uint32_t t, const uint16_t *D, const uint16_t *K)
+{
+    const uint32_t ia = 255u - t;
+    const uint32_t r1a = m2((d >> 8) & M2, ia);                // channel 1 and alpha
+    if constexpr (!SRGB) {
+        return m2(d & M2, ia) | r1a << 8;
+    } else {
+        uint32_t out = 0u;                                     // a shift register: a channel enters at the top byte
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const uint32_t L = div255_24((uint32_t)D[(d >> (8 * c)) & 0xffu] * ia + 127u);
             out = (out >> 8) | (srgb_encode(K, L) << 24);
         }
         return (out >> 8) | (r1a & 0x00ff0000u) << 8;          // alpha is stored linearly

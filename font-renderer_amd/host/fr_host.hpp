@@ -259,6 +259,34 @@ inline void layer_lcd(Context &ctx, const DevicePlane &plane, const DeviceImage 
     check(fr_layer_lcd(ctx.get(), plane.bytes, plane.stride, plane.rows, image.pixels, image.stride_px, image.rows, blits.data(), (uint32_t)blits.size(), weights,
                        (srgb ? FR_LAYER_SRGB : 0u) | (bgr ? FR_LCD_BGR : 0u)));
 }
+// fr_layer_mask: layer_over with an opacity per pixel, t = m(k', o), where k is the alpha of the pixel of `mask` (a layer:
+// a panel, a shadow, an outline) that a blit lays over the pixel and k' = 255 - k where the blit inverts: text clipped to a
+// shape, pixels showing through text, a soft wipe.  Asynchronous on the context's stream; `blits` may be reused at once.
+inline void layer_mask(Context &ctx, const DeviceImage &layer, const DeviceImage &mask, const DeviceImage &image, const std::vector<fr_layer_mask_blit> &blits,
+                       bool srgb = false)
+{
+    check(fr_layer_mask(ctx.get(), layer.pixels, layer.stride_px, layer.rows, mask.pixels, mask.stride_px, mask.rows, image.pixels, image.stride_px, image.rows,
+                        blits.data(), (uint32_t)blits.size(), srgb ? FR_LAYER_SRGB : 0u));
+}
+// the same through a plane of bytes (a FR_COVERAGE_U8 render; any alignment)
+inline void layer_mask(Context &ctx, const DeviceImage &layer, const DevicePlane &mask, const DeviceImage &image, const std::vector<fr_layer_mask_blit> &blits,
+                       bool srgb = false)
+{
+    check(fr_layer_mask(ctx.get(), layer.pixels, layer.stride_px, layer.rows, mask.bytes, mask.stride, mask.rows, image.pixels, image.stride_px, image.rows,
+                        blits.data(), (uint32_t)blits.size(), (srgb ? FR_LAYER_SRGB : 0u) | FR_MASK_PLANE));
+}
+// FR_MASK_ERASE: no layer; the image is multiplied by 255 - t (destination-out): a knock-out, or underlines that skip the ink
+// of a grown text layer.  A blit's src_x and src_y are not used.
+inline void layer_erase(Context &ctx, const DeviceImage &mask, const DeviceImage &image, const std::vector<fr_layer_mask_blit> &blits, bool srgb = false)
+{
+    check(fr_layer_mask(ctx.get(), nullptr, 0, 0, mask.pixels, mask.stride_px, mask.rows, image.pixels, image.stride_px, image.rows, blits.data(),
+                        (uint32_t)blits.size(), (srgb ? FR_LAYER_SRGB : 0u) | FR_MASK_ERASE));
+}
+inline void layer_erase(Context &ctx, const DevicePlane &mask, const DeviceImage &image, const std::vector<fr_layer_mask_blit> &blits, bool srgb = false)
+{
+    check(fr_layer_mask(ctx.get(), nullptr, 0, 0, mask.bytes, mask.stride, mask.rows, image.pixels, image.stride_px, image.rows, blits.data(),
+                        (uint32_t)blits.size(), (srgb ? FR_LAYER_SRGB : 0u) | FR_MASK_PLANE | FR_MASK_ERASE));
+}
 
 class PlacedText {
 public:

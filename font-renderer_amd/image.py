@@ -10,7 +10,8 @@ import numpy as np
 from . import _lib as L
 from .device import default_context, round_trip
 from .glyph import GlyphSet
-from .layer import layer_lcd, layer_outline, layer_over, layer_paint, layer_rects, layer_shadow, layer_unpremultiply, make_blits, make_lcd_blits, make_rects
+from .layer import (layer_lcd, layer_mask, layer_outline, layer_over, layer_paint, layer_rects, layer_shadow, layer_unpremultiply, make_blits, make_lcd_blits,
+                    make_mask_blits, make_rects)
 
 
 def q64(v) -> int:
@@ -153,6 +154,57 @@ class RGBA:                     # an RGBA text plan's image (fr_text_plan_create
         self.data[:] = round_trip(ctx, lambda d, s: layer_over(ctx, s, layer.width, layer.height, d, self.width, self.height,
                                                                blits, srgb), dst, src)
         return self
+
+    def _masked(self, what: str, layer, mask, x, y, mask_xy, opacity, invert, srgb, ctx) -> "RGBA":
+        """over_masked (layer an RGBA) and erase (layer None): one blit of fr_layer_mask over the part of the rectangle that
+        the mask covers"""
+        dst = rgba_pixels(self, f"{what}: image")
+        src = None if layer is None else rgba_pixels(layer, f"{what}: layer")
+        plane = isinstance(mask, Gray)
+        if plane:
+            m = mask.data
+            if not isinstance(m, np.ndarray) or m.dtype != np.uint8 or m.shape != (mask.width * mask.height,):
+                raise ValueError(f"{what}: mask.data must be a ({mask.width * mask.height},) uint8 array")
+            m = np.ascontiguousarray(m)
+        else:
+            m = rgba_pixels(mask, f"{what}: mask")
+        mx, my = int(mask_xy[0]), int(mask_xy[1])
+        if not 0 <= int(opacity) <= 255:
+            raise ValueError(f"opacity {opacity!r}: expected 0 .. 255")
+        if mx < 0 or my < 0:
+            raise ValueError(f"mask_xy {mask_xy!r}: expected an element of the mask")
+        w, h = mask.width - mx, mask.height - my
+        if layer is not None:
+            w, h = min(w, layer.width), min(h, layer.height)
+        if self.width == 0 or self.height == 0 or w <= 0 or h <= 0:
+            return self
+        ctx = ctx or default_context()
+        blits = make_mask_blits([(0, 0, w, h, int(x), int(y), mx, my, int(opacity), 1 if invert else 0)])
+        if layer is None:
+            self.data[:] = round_trip(ctx, lambda d, k: layer_mask(ctx, None, 0, 0, k, mask.width, mask.height, d, self.width, self.height, blits,
+                                                                   srgb, plane, True), dst, m)
+        else:
+            self.data[:] = round_trip(ctx, lambda d, s, k: layer_mask(ctx, s, layer.width, layer.height, k, mask.width, mask.height, d, self.width,
+                                                                      self.height, blits, srgb, plane), dst, src, m)
+        return self
+
+    def over_masked(self, layer: "RGBA", mask, x: int = 0, y: int = 0, mask_xy=(0, 0), opacity: int = 255, invert: bool = False,
+                    srgb: bool = False, ctx=None) -> "RGBA":
+        """fr_layer_mask, in place: over() with an opacity per pixel.  The premultiplied `layer` lands with its top-left pixel
+        at (x, y) and element mask_xy of `mask` lies over that pixel; each pixel is composited at m(k, opacity), where k is
+        the mask's value there: the alpha of an RGBA mask (a layer: a panel, a shadow, an outline), or the byte of a Gray
+        one (a coverage render).  invert: through 255 - k instead.  Only the part of the layer that the mask covers is
+        drawn.  srgb: the images are premultiplied in linear light.  The three images are uploaded and this one copied back.
+        Returns self."""
+        return self._masked("RGBA.over_masked", layer, mask, x, y, mask_xy, opacity, invert, srgb, ctx)
+
+    def erase(self, mask, x: int = 0, y: int = 0, mask_xy=(0, 0), opacity: int = 255, invert: bool = False, srgb: bool = False,
+              ctx=None) -> "RGBA":
+        """fr_layer_mask with FR_MASK_ERASE, in place: this premultiplied image is multiplied by 255 - m(k, opacity) where
+        `mask` (an RGBA: its alpha; a Gray: its bytes) lies over it, element mask_xy on pixel (x, y) and the rest of the
+        mask to its right and below: a knock-out, or underlines that skip the ink of a grown text layer.  invert: erase
+        through 255 - k.  srgb: the image is premultiplied in linear light.  Returns self."""
+        return self._masked("RGBA.erase", None, mask, x, y, mask_xy, opacity, invert, srgb, ctx)
 
     def fill_rects(self, rects, srgb: bool = False, ctx=None) -> "RGBA":
         """fr_layer_rects, in place: rects of (x0, y0, x1, y1, (R, G, B, A)) in float pixels, y down, each edge kept to 1/64

@@ -1,5 +1,5 @@
 """The layer calls of the C ABI (fr_layer_*, include/fr_raster.h) on device addresses, and the builders of their tables.
-All of them are asynchronous on the context's stream; RGBA.over / fill_rects / paint / draw_lcd / shadow / outline / unpremultiply
+All of them are asynchronous on the context's stream; RGBA.over / over_masked / erase / fill_rects / paint / draw_lcd / shadow / outline / unpremultiply
 (image.py) wrap them for host images."""
 from __future__ import annotations
 
@@ -14,11 +14,17 @@ from .device import Context
 BLIT_DTYPE = np.dtype(L.LayerBlit)
 RECT_DTYPE = np.dtype(L.LayerRect)
 LCD_BLIT_DTYPE = np.dtype(L.LcdBlit)
+MASK_BLIT_DTYPE = np.dtype(L.LayerMaskBlit)
 
 
 def make_blits(rows: Sequence) -> np.ndarray:
     """rows of (src_x, src_y, w, h, dst_x, dst_y, opacity) -> fr_layer_blit array"""
     return np.array([tuple(r) for r in rows], BLIT_DTYPE)
+
+
+def make_mask_blits(rows: Sequence) -> np.ndarray:
+    """rows of (src_x, src_y, w, h, dst_x, dst_y, mask_x, mask_y, opacity, invert) -> fr_layer_mask_blit array"""
+    return np.array([tuple(r) for r in rows], MASK_BLIT_DTYPE)
 
 
 def make_rects(rows: Sequence) -> np.ndarray:
@@ -121,6 +127,21 @@ def layer_lcd(ctx: Context, cov_ptr: int, cov_stride: int, cov_rows: int, dst_pt
         w = (C.c_uint16 * L.FR_LCD_TAPS)(*w)
     L.check(ctx._lib.fr_layer_lcd(ctx._h, C.c_void_p(cov_ptr), cov_stride, cov_rows, C.c_void_p(dst_ptr), dst_stride_px, dst_rows,
                                   None if b is None else L.ptr(b), n, w, _flags(flags, srgb) | (L.FR_LCD_BGR if bgr else 0)))
+
+
+def layer_mask(ctx: Context, src_ptr, src_stride_px: int, src_rows: int, mask_ptr: int, mask_stride: int, mask_rows: int, dst_ptr: int,
+               dst_stride_px: int, dst_rows: int, blits, srgb: bool = False, plane: bool = False, erase: bool = False, flags: int = 0) -> None:
+    """fr_layer_mask: fr_layer_over with an opacity per pixel.  Rectangles of the premultiplied layer at device address src_ptr
+    composited over the premultiplied image at dst_ptr at t = m(k', opacity), where k is the alpha byte of the pixel of the
+    layer at mask_ptr that lies over the pixel (4 bytes per pixel, mask_stride in pixels) and k' = 255 - k where the blit
+    inverts; asynchronous on the context's stream.  blits: an fr_layer_mask_blit array (make_mask_blits) or None.  srgb:
+    FR_LAYER_SRGB, composite in linear light.  plane: FR_MASK_PLANE, the mask is a plane of bytes (a coverage render;
+    mask_stride in bytes, any alignment).  erase: FR_MASK_ERASE, no layer (src_ptr None or 0; src_stride_px and src_rows are
+    ignored): the image is multiplied by 255 - t."""
+    b, n = _table(blits, MASK_BLIT_DTYPE)
+    L.check(ctx._lib.fr_layer_mask(ctx._h, C.c_void_p(src_ptr or None), src_stride_px, src_rows, C.c_void_p(mask_ptr), mask_stride, mask_rows,
+                                   C.c_void_p(dst_ptr), dst_stride_px, dst_rows, None if b is None else L.ptr(b), n,
+                                   _flags(flags, srgb) | (L.FR_MASK_PLANE if plane else 0) | (L.FR_MASK_ERASE if erase else 0)))
 
 
 def layer_unpremultiply(ctx: Context, ptr: int, stride_px: int, w: int, h: int, srgb: bool = False) -> None:

@@ -1085,6 +1085,75 @@ int fr_layer_lcd(fr_ctx *ctx, const void *cov_dev, size_t cov_stride, size_t cov
                  const fr_lcd_blit *blits, uint32_t n_blits,
                  const uint16_t *weights /* FR_LCD_TAPS values, or NULL */, uint32_t flags);
 
+/* ---- a layer through a mask, or an erase through one (BUILD-DEFINED; DESIGN.md sections 4.14 and 5) ------------------------
+ * fr_layer_mask is fr_layer_over with an opacity per pixel: a second image, the mask, decides where the layer's pixels
+ * land (text clipped to a rounded panel, a photo showing inside the glyphs, a soft wipe).  With FR_MASK_ERASE there is no
+ * layer and the mask lowers the destination instead (destination-out: a knock-out, or underlines that skip the glyphs'
+ * ink).  The layer and the destination are what fr_layer_over's are; m, D and E as defined there.  All integers.
+ *   Mask value: for a pixel of the rectangle, k is the alpha byte of the mask pixel over it when the mask is a 4-byte
+ *     layer (mask_stride in pixels, mask_dev 4-byte aligned); with FR_MASK_PLANE k is the byte of a plane of 1-byte
+ *     elements, such as a coverage plan's output (mask_stride in bytes; any pointer and any pitch).  Then
+ *         k' = invert ? 255 - k : k,      t = m(k', o)          (o: the blit's opacity)
+ *   Composite (no FR_MASK_ERASE): fr_layer_over's definition with t in the place of o:
+ *       a'    = m(s_a, t)
+ *       out_a = a' + m(d_a, 255 - a')
+ *       out_c = min(255, m(s_c, t) + m(d_c, 255 - a'))                                             (UNORM)
+ *       out_c = E(min(65535, (D[s_c] * t + 127) div 255 + (D[d_c] * (255 - a') + 127) div 255))    (FR_LAYER_SRGB)
+ *   Erase (FR_MASK_ERASE; src_dev must be NULL, src_stride_px and src_rows are ignored, and so are src_x and src_y):
+ *       out_a = m(d_a, 255 - t)
+ *       out_c = m(d_c, 255 - t)                                  (UNORM)
+ *       out_c = E((D[d_c] * (255 - t) + 127) div 255)            (FR_LAYER_SRGB)
+ *   Consequences:
+ *     1. A mask that is 255 everywhere with invert = 0, or 0 everywhere with invert = 1, gives the bytes of fr_layer_over
+ *        with the same rectangles and opacities, in both spaces (m(255, o) = o).
+ *     2. Where t = 0 the destination pixel is byte-identical, in both spaces and both modes.
+ *     3. A valid premultiplied layer pixel never reaches the clamp: m(s_c, t) <= m(s_a, t).
+ *     4. A layer of one opaque colour (C0, C1, C2, 255) through a layer mask at opacity o gives the bytes of fr_layer_paint
+ *        with the single stop (C0, C1, C2, A = o) through that mask layer's window, in both spaces: both reduce to
+ *        a = m(k, o).
+ *     5. FR_MASK_PLANE gives the bytes of the same call with a layer mask whose alpha bytes are the plane's.
+ *     6. Erase: t = 255 stores (0, 0, 0, 0); a destination alpha never grows; the three colour bytes of an erase through an
+ *        all-255 plane at opacity o equal those of fr_layer_rects with the pixel-aligned black rectangle of alpha o, in
+ *        both spaces (the alpha differs: the rectangle's is o + m(d_a, 255 - o)).
+ *     7. invert = 1 equals invert = 0 on the byte-complemented mask.
+ *   Geometry: fr_layer_over's, with the mask added.  The rectangle must lie inside the layer (unless erasing) and inside
+ *     the mask (mask_x + w <= mask_stride, mask_y + h <= mask_rows); its destination is clipped to the image; the clipped
+ *     rectangles of one call must not overlap each other.  The destination's bytes must not overlap the layer's or the
+ *     mask's; layer and mask may overlap each other or be the same memory (both are only read).  No byte of the layer or
+ *     the mask is written, no byte outside the mask's mask_stride x mask_rows elements is read, and outside every
+ *     clipped rectangle no byte of the image is read or written.
+ *   Validation, in this order.  FR_E_INVALID: NULL ctx; an unknown flag bit (FR_LCD_BGR is one); a bad dst (NULL, not
+ *     4-byte aligned, a pitch above 2^26); a bad mask (NULL, a pitch above 2^26 elements, a layer mask that is not 4-byte
+ *     aligned); FR_MASK_ERASE with a non-NULL src_dev, or no FR_MASK_ERASE with a NULL one; a bad src.  FR_E_UNSUPPORTED:
+ *     2^31 rows or more in any image.  FR_E_INVALID: NULL blits with n_blits > 0; the destination overlapping the layer or
+ *     the mask in memory; per blit, in order, opacity > 255, invert > 1, then for w, h != 0 a rectangle that leaves the
+ *     layer, one that leaves the mask.  FR_E_UNSUPPORTED: more than 2^22 tiles of 256 x 16 pixels.  FR_E_INVALID:
+ *     overlapping clipped rectangles (the message names the first pair).  After any refusal the image is untouched.
+ *     n_blits = 0 is valid and launches nothing, and so does a call whose blits all have o = 0.
+ *   Execution: one launch of layer_mask_kernel<srgb, plane, erase> for all blits of the call, behind the small kernel that
+ *     brings the call's tile table into device memory; invert and opacity are per-tile values.  A group of four pixels
+ *     whose t are all 0, or whose layer pixels are all 0, is neither loaded from the destination nor stored; the
+ *     destination is not loaded where every a' (erase: every t) is 255.  Asynchronous on the context's stream, in stream
+ *     order with renders and the other layer calls; the caller may reuse `blits` as soon as the call returns.
+ * FR_MASK_PLANE and FR_MASK_ERASE live in the flag space of the layer calls beside FR_LAYER_SRGB and FR_LCD_BGR, and only
+ * fr_layer_mask knows them: the other layer calls refuse them as unknown bits.                                             */
+#define FR_MASK_PLANE 4u   /* the mask is a plane of 1-byte elements (a coverage plan's output), any alignment */
+#define FR_MASK_ERASE 8u   /* no source: the destination is multiplied by 255 - t (destination-out)           */
+
+typedef struct fr_layer_mask_blit {
+    uint32_t src_x, src_y;     /* top-left of the rectangle in the layer (ignored with FR_MASK_ERASE)  */
+    uint32_t w, h;             /* 0 x anything: valid, does nothing                                    */
+    int32_t  dst_x, dst_y;     /* where that top-left lands in the destination; may be negative        */
+    uint32_t mask_x, mask_y;   /* the mask element that lies over the rectangle's top-left             */
+    uint32_t opacity;          /* o in 0 .. 255                                                        */
+    uint32_t invert;           /* 0: through the mask; 1: through its complement; else FR_E_INVALID    */
+} fr_layer_mask_blit;
+
+int fr_layer_mask(fr_ctx *ctx, const void *src_dev, size_t src_stride_px, size_t src_rows,
+                  const void *mask_dev, size_t mask_stride, size_t mask_rows,
+                  void *dst_dev, size_t dst_stride_px, size_t dst_rows,
+                  const fr_layer_mask_blit *blits, uint32_t n_blits, uint32_t flags);
+
 /* ---- self-test: exhaustive device-side check of an arithmetic shortcut ----------
  * The render kernel computes t = num / d (render_glyph.zig:51,60-61; d an integer, |d| <= 2^17)
  * as a reciprocal multiply + FMA correction.  This compares that sequence with IEEE division
