@@ -204,6 +204,28 @@ pub const LcdBlit = extern struct {
     rgba: [4]u8,
 };
 
+/// one blit of fr_layer_warp: the window of the layer that is sampled, the rectangle of the image it owns, and the inverse
+/// map (rectangle pixel to window position, 1/65536 pixel): u0, v0 at the centre of rectangle pixel (0, 0), (ux, vx) per
+/// column and (uy, vy) per row; the opacity in 0 .. 255; reserved must be 0
+pub const LayerWarpBlit = extern struct {
+    src_x: u32,
+    src_y: u32,
+    w: u32,
+    h: u32,
+    dst_x: i32,
+    dst_y: i32,
+    dst_w: u32,
+    dst_h: u32,
+    u0: i64,
+    v0: i64,
+    ux: i32,
+    uy: i32,
+    vx: i32,
+    vy: i32,
+    opacity: u32,
+    reserved: u32,
+};
+
 /// one rectangle of fr_layer_mask: where it lies in the layer (not used when erasing), where it lands, the mask element over
 /// its top-left pixel, the opacity in 0 .. 255 and whether the mask is complemented (0 or 1)
 pub const LayerMaskBlit = extern struct {
@@ -337,6 +359,8 @@ pub extern "c" fn fr_layer_paint(ctx: *Ctx, src_dev: ?*const anyopaque, src_stri
 pub extern "c" fn fr_layer_lcd(ctx: *Ctx, cov_dev: *const anyopaque, cov_stride: usize, cov_rows: usize, dst_dev: *anyopaque, dst_stride_px: usize, dst_rows: usize, blits: ?[*]const LcdBlit, n_blits: u32, weights: ?*const [FR_LCD_TAPS]u16, flags: u32) c_int;
 /// rectangles of a premultiplied layer over a premultiplied image at an opacity per pixel taken from a mask (a layer's alpha, or with FR_MASK_PLANE a plane of bytes); with FR_MASK_ERASE (src_dev null) the mask lowers the image instead
 pub extern "c" fn fr_layer_mask(ctx: *Ctx, src_dev: ?*const anyopaque, src_stride_px: usize, src_rows: usize, mask_dev: *const anyopaque, mask_stride: usize, mask_rows: usize, dst_dev: *anyopaque, dst_stride_px: usize, dst_rows: usize, blits: ?[*]const LayerMaskBlit, n_blits: u32, flags: u32) c_int;
+/// windows of a premultiplied layer over a premultiplied image through an affine map each (scaled, turned, moved by a fraction of a pixel), sampled bilinearly in exact integers
+pub extern "c" fn fr_layer_warp(ctx: *Ctx, src_dev: *const anyopaque, src_stride_px: usize, src_rows: usize, dst_dev: *anyopaque, dst_stride_px: usize, dst_rows: usize, blits: ?[*]const LayerWarpBlit, n_blits: u32, flags: u32) c_int;
 // ---- self-tests of the two arithmetic shortcuts (device-side, exhaustive)
 pub extern "c" fn fr_selftest_division(d_lo: u32, d_hi: u32, mismatches: *u64, bad_divisor: ?*u32, bad_x_bits: ?*u32) c_int;
 pub extern "c" fn fr_selftest_sqrt(mismatches: *u64, bad_x_bits: ?*u32) c_int;

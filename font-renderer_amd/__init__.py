@@ -13,12 +13,12 @@ from ._lib import (  # noqa: F401
     FR_GRADIENT_LINEAR, FR_GRADIENT_MAX_STOPS, FR_GRADIENT_RADIAL, FR_SPREAD_PAD, FR_SPREAD_REFLECT, FR_SPREAD_REPEAT,
     FR_OUTLINE_GROW, FR_OUTLINE_INNER, FR_OUTLINE_MAX_RADIUS, FR_OUTLINE_RING, FR_OUTLINE_SHRINK,
     FR_LAYER_SRGB, FR_LCD_BGR, FR_LCD_TAPS, FR_MASK_ERASE, FR_MASK_PLANE, FR_TEXT_BGRA, FR_TEXT_CACHE, FR_TEXT_CACHE_AFFINE, FR_TEXT_LOAD, FR_TEXT_OVER, FR_TEXT_SRGB, FR_WINDING_I16, FrError, GlyphPlace, GlyphPlaceAffine, GlyphPlaceEx,
-    FontLine, GradientStop, Job, LayerBlit, LayerMaskBlit, LayerOutlineParams, LayerPaintParams, LayerRect, LayerShadowParams, LcdBlit, TextRun, lib_path, load_library,
+    FontLine, GradientStop, Job, LayerBlit, LayerMaskBlit, LayerOutlineParams, LayerPaintParams, LayerRect, LayerShadowParams, LayerWarpBlit, LcdBlit, TextRun, lib_path, load_library,
 )
 from .device import Context  # noqa: F401
 from .layer import (  # noqa: F401
-    layer_lcd, layer_mask, layer_outline, layer_over, layer_paint, layer_rects, layer_shadow, layer_unpremultiply, make_blits, make_gradient_linear, make_gradient_radial,
-    make_lcd_blits, make_mask_blits, make_rects,
+    layer_lcd, layer_mask, layer_outline, layer_over, layer_paint, layer_rects, layer_shadow, layer_unpremultiply, layer_warp, make_blits, make_gradient_linear, make_gradient_radial,
+    make_lcd_blits, make_mask_blits, make_rects, make_warp_blits, warp_from_matrix,
 )
 from .render_glyph import (  # noqa: F401
     GlyphInfo, Plan, TextPlan, TextPlanRGBA, DeviceGlyphSet, make_places, make_places_affine, make_places_ex, make_runs, renderGlyph,

@@ -97,6 +97,13 @@ class LayerOutlineParams(C.Structure):   # == fr_layer_outline_params
                 ("dx", C.c_int32), ("dy", C.c_int32), ("radius", C.c_uint32), ("kind", C.c_uint32), ("rgba", C.c_uint8 * 4)]
 
 
+class LayerWarpBlit(C.Structure):    # == fr_layer_warp_blit (72 bytes)
+    _fields_ = [("src_x", C.c_uint32), ("src_y", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32),
+                ("dst_x", C.c_int32), ("dst_y", C.c_int32), ("dst_w", C.c_uint32), ("dst_h", C.c_uint32),
+                ("u0", C.c_int64), ("v0", C.c_int64), ("ux", C.c_int32), ("uy", C.c_int32), ("vx", C.c_int32), ("vy", C.c_int32),
+                ("opacity", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class LayerRect(C.Structure):    # == fr_layer_rect
     _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32), ("rgba", C.c_uint8 * 4)]
 
@@ -197,6 +204,7 @@ SYMBOLS = [
     ("fr_layer_paint", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.POINTER(LayerPaintParams), C.c_uint32]),
     ("fr_layer_lcd", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, _P, C.c_uint32, C.POINTER(C.c_uint16), C.c_uint32]),
     ("fr_layer_mask", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, _P, C.c_uint32, C.c_uint32]),
+    ("fr_layer_warp", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, _P, C.c_uint32, C.c_uint32]),
     ("fr_selftest_sqrt", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     ("fr_selftest_division", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("fr_selftest_row_cuts", C.c_int, [_P, _P, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),

@@ -1,11 +1,11 @@
 // fr_api_layer.hip — C ABI (include/fr_raster.h): fr_layer_over, fr_layer_unpremultiply, fr_layer_shadow, fr_layer_outline,
-// fr_layer_rects, fr_layer_paint, fr_layer_lcd and fr_layer_mask.  The checks, the clipping and the tile table are
+// fr_layer_rects, fr_layer_paint, fr_layer_lcd, fr_layer_mask and fr_layer_warp.  The checks, the clipping and the tile table are
 // fr_layer_plan.cpp's, the shadow's stages fr_layer_shadow_plan.cpp's, the outline's rectangles and weights
 // fr_layer_outline_plan.cpp's, the rectangles' tables fr_layer_rects_plan.cpp's, the gradient's coefficients and colour
 // table fr_layer_paint_plan.cpp's, the sub-pixel blits' tiles fr_layer_lcd_plan.cpp's, the masked blits' tiles
-// fr_layer_mask_plan.cpp's; this unit stages the tables, keeps the shadow's planes and launches the kernels of
-// fr_layer.hip, fr_layer_shadow.hip, fr_layer_outline.hip, fr_layer_rects.hip, fr_layer_paint.hip, fr_layer_lcd.hip and
-// fr_layer_mask.hip.
+// fr_layer_mask_plan.cpp's, the warped blits' culled tiles fr_layer_warp_plan.cpp's; this unit stages the tables, keeps the shadow's planes and launches the kernels of
+// fr_layer.hip, fr_layer_shadow.hip, fr_layer_outline.hip, fr_layer_rects.hip, fr_layer_paint.hip, fr_layer_lcd.hip,
+// fr_layer_mask.hip and fr_layer_warp.hip.
 #include "fr_internal.hpp"
 #include "fr_layer.hpp"
 #include "fr_layer_lcd.hpp"
@@ -14,6 +14,7 @@
 #include "fr_layer_paint.hpp"
 #include "fr_layer_rects.hpp"
 #include "fr_layer_shadow.hpp"
+#include "fr_layer_warp.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -333,6 +334,28 @@ int fr_layer_mask(fr_ctx *ctx, const void *src_dev, size_t src_stride_px, size_t
     const fr::MaskArgs a{reinterpret_cast<const fr::MaskTile *>(tab), static_cast<const uint32_t *>(src_dev), mask_dev, static_cast<uint32_t *>(dst_dev),
                          src_stride_px, mask_stride, dst_stride_px};
     HIP_TRY(fr::launch_layer_mask((flags & FR_LAYER_SRGB) != 0, (flags & FR_MASK_PLANE) != 0, (flags & FR_MASK_ERASE) != 0, (uint32_t)n, a, ctx->stream));
+    return FR_OK;
+}
+
+int fr_layer_warp(fr_ctx *ctx, const void *src_dev, size_t src_stride_px, size_t src_rows, void *dst_dev, size_t dst_stride_px,
+                  size_t dst_rows, const fr_layer_warp_blit *blits, uint32_t n_blits, uint32_t flags)
+{
+    if (!ctx) return fail(FR_E_INVALID, "fr_layer_warp: ctx is NULL");
+    fr::WarpTables t;
+    try {
+        const fr::WarpIn in{(uintptr_t)src_dev, (uintptr_t)dst_dev, src_stride_px, src_rows, dst_stride_px, dst_rows, blits, n_blits, flags};
+        if (const int rc = fr::layer_warp_tables(in, t)) return rc;
+    } catch (const std::bad_alloc &) {
+        return fail(FR_E_NOMEM, "fr_layer_warp: host allocation");
+    }
+    const size_t n = t.tiles.size();
+    if (!n) return FR_OK;                                       // no tap of any tile reaches a window
+    HIP_TRY(hipSetDevice(ctx->device));
+    static_assert(sizeof(fr::WarpTile) == 6 * sizeof(uint4), "a tile is six units of the staging");
+    const uint4 *tab = nullptr;
+    if (const int rc = layer_tables_to_device(ctx, 6 * n, &tab, [&](uint4 *to) { memcpy(to, t.tiles.data(), n * sizeof(fr::WarpTile)); })) return rc;
+    const fr::WarpArgs a{reinterpret_cast<const fr::WarpTile *>(tab), static_cast<const uint32_t *>(src_dev), static_cast<uint32_t *>(dst_dev), src_stride_px, dst_stride_px};
+    HIP_TRY(fr::launch_layer_warp((flags & FR_LAYER_SRGB) != 0, t.opacity, (uint32_t)n, a, ctx->stream));
     return FR_OK;
 }
 

@@ -1,6 +1,6 @@
 // fr_layer_px.hpp — source-over of one premultiplied pixel, for the kernels that composite onto an image: layer_over_kernel
 // (fr_layer.hip), layer_rects_kernel (fr_layer_rects.hip), layer_paint_kernel (fr_layer_paint.hip) and layer_mask_kernel
-// (fr_layer_mask.hip) with its erase, and its variant with one alpha per colour byte for layer_lcd_kernel
+// (fr_layer_mask.hip) with its erase, layer_warp_kernel (fr_layer_warp.hip) with its linear-light sibling, and its variant with one alpha per colour byte for layer_lcd_kernel
 // (fr_layer_lcd.hip).  The arithmetic is that of the text plans' colour body (fr_text_colour.hpp), per pixel instead of per
 // sample.
 #pragma once
@@ -50,6 +50,25 @@ __device__ __forceinline__ uint32_t over_px(uint32_t s, uint32_t d, uint32_t o, 
         }
         return (out >> 8) | (r1a & 0x00ff0000u) << 8;          // alpha is stored linearly
     }
+}
+
+// over_px in linear light for a layer pixel that comes as linear values: the definition of fr_layer_warp with FR_LAYER_SRGB,
+// where the sampler hands over S[c], 16 bits each, in the place of D[s_c], and the sampled alpha sa.  sa == 0 with S == 0
+// gives d, and with a' == 255 no bit of d reaches the result, as for over_px.
+template <int OPACITY>
+__device__ __forceinline__ uint32_t over_px_lin(uint32_t sa, const uint32_t (&S)[3], uint32_t d, uint32_t o, const uint16_t *D, const uint16_t *K)
+{
+    const uint32_t a1 = OPACITY ? m2(sa, o) : sa;
+    const uint32_t ia = 255u - a1;
+    uint32_t out = 0u;                                         // a shift register: a channel enters at the top byte
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        uint32_t Sc = S[c];
+        if (OPACITY) Sc = div255_24(Sc * o + 127u);
+        const uint32_t L = min(65535u, Sc + div255_24((uint32_t)D[(d >> (8 * c)) & 0xffu] * ia + 127u));
+        out = (out >> 8) | (srgb_encode(K, L) << 24);
+    }
+    return (out >> 8) | (a1 + m2(d >> 24, ia)) << 24;          // alpha is stored linearly; a' + m(d_a, 255 - a') <= 255
 }
 
 // The erase of fr_layer_mask for one pixel: d times 255 - t (destination-out).  t == 0 gives d (m(x, 255) = x, E(D[v]) = v)

@@ -287,6 +287,15 @@ inline void layer_erase(Context &ctx, const DevicePlane &mask, const DeviceImage
     check(fr_layer_mask(ctx.get(), nullptr, 0, 0, mask.bytes, mask.stride, mask.rows, image.pixels, image.stride_px, image.rows, blits.data(),
                         (uint32_t)blits.size(), (srgb ? FR_LAYER_SRGB : 0u) | FR_MASK_PLANE | FR_MASK_ERASE));
 }
+// fr_layer_warp: windows of `layer` composited over `image` through an affine map each: a blit names the window, the
+// rectangle of the image it owns and the inverse map in 1/65536 window pixel (u0, v0 at the centre of rectangle pixel
+// (0, 0); ux, vx per column; uy, vy per row), sampled bilinearly in exact integers.  A viewer that zooms, spins or
+// smooth-scrolls finished text calls this per frame.  Asynchronous on the context's stream; `blits` may be reused at once.
+inline void layer_warp(Context &ctx, const DeviceImage &layer, const DeviceImage &image, const std::vector<fr_layer_warp_blit> &blits, bool srgb = false)
+{
+    check(fr_layer_warp(ctx.get(), layer.pixels, layer.stride_px, layer.rows, image.pixels, image.stride_px, image.rows, blits.data(), (uint32_t)blits.size(),
+                        srgb ? FR_LAYER_SRGB : 0u));
+}
 
 class PlacedText {
 public:

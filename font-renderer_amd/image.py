@@ -10,8 +10,8 @@ import numpy as np
 from . import _lib as L
 from .device import default_context, round_trip
 from .glyph import GlyphSet
-from .layer import (layer_lcd, layer_mask, layer_outline, layer_over, layer_paint, layer_rects, layer_shadow, layer_unpremultiply, make_blits, make_lcd_blits,
-                    make_mask_blits, make_rects)
+from .layer import (layer_lcd, layer_mask, layer_outline, layer_over, layer_paint, layer_rects, layer_shadow, layer_unpremultiply, layer_warp, make_blits, make_lcd_blits,
+                    make_mask_blits, make_rects, make_warp_blits, warp_from_matrix)
 
 
 def q64(v) -> int:
@@ -152,6 +152,23 @@ class RGBA:                     # an RGBA text plan's image (fr_text_plan_create
         ctx = ctx or default_context()
         blits = make_blits([(0, 0, layer.width, layer.height, int(x), int(y), int(opacity))])
         self.data[:] = round_trip(ctx, lambda d, s: layer_over(ctx, s, layer.width, layer.height, d, self.width, self.height,
+                                                               blits, srgb), dst, src)
+        return self
+
+    def over_warped(self, layer: "RGBA", matrix, opacity: int = 255, srgb: bool = False, ctx=None) -> "RGBA":
+        """fr_layer_warp, in place: the premultiplied `layer` composited over this premultiplied image through the forward
+        map `matrix` = ((a, b, tx), (c, d, ty)), layer pixels to image pixels with pixel centres at + 1/2: scaled, turned or
+        moved by a fraction of a pixel, sampled bilinearly (warp_from_matrix makes the blit), clipped at the image's edges,
+        at `opacity` in 0 .. 255.  Outside the layer the sample blends with transparent.  srgb: both images are premultiplied
+        in linear light.  Both images are uploaded and this one copied back.  Returns self."""
+        dst, src = rgba_pixels(self, "RGBA.over_warped: image"), rgba_pixels(layer, "RGBA.over_warped: layer")
+        if not 0 <= int(opacity) <= 255:
+            raise ValueError(f"opacity {opacity!r}: expected 0 .. 255")
+        if self.width == 0 or self.height == 0 or layer.width == 0 or layer.height == 0:
+            return self
+        ctx = ctx or default_context()
+        blits = make_warp_blits([warp_from_matrix(matrix, (0, 0, layer.width, layer.height), opacity)])
+        self.data[:] = round_trip(ctx, lambda d, s: layer_warp(ctx, s, layer.width, layer.height, d, self.width, self.height,
                                                                blits, srgb), dst, src)
         return self
 

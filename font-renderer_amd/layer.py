@@ -1,9 +1,11 @@
 """The layer calls of the C ABI (fr_layer_*, include/fr_raster.h) on device addresses, and the builders of their tables.
-All of them are asynchronous on the context's stream; RGBA.over / over_masked / erase / fill_rects / paint / draw_lcd / shadow / outline / unpremultiply
+All of them are asynchronous on the context's stream; RGBA.over / over_warped / over_masked / erase / fill_rects / paint / draw_lcd / shadow / outline / unpremultiply
 (image.py) wrap them for host images."""
 from __future__ import annotations
 
 import ctypes as C
+import math
+from fractions import Fraction
 from typing import Sequence
 
 import numpy as np
@@ -15,6 +17,7 @@ BLIT_DTYPE = np.dtype(L.LayerBlit)
 RECT_DTYPE = np.dtype(L.LayerRect)
 LCD_BLIT_DTYPE = np.dtype(L.LcdBlit)
 MASK_BLIT_DTYPE = np.dtype(L.LayerMaskBlit)
+WARP_BLIT_DTYPE = np.dtype(L.LayerWarpBlit)
 
 
 def make_blits(rows: Sequence) -> np.ndarray:
@@ -25,6 +28,37 @@ def make_blits(rows: Sequence) -> np.ndarray:
 def make_mask_blits(rows: Sequence) -> np.ndarray:
     """rows of (src_x, src_y, w, h, dst_x, dst_y, mask_x, mask_y, opacity, invert) -> fr_layer_mask_blit array"""
     return np.array([tuple(r) for r in rows], MASK_BLIT_DTYPE)
+
+
+def make_warp_blits(rows: Sequence) -> np.ndarray:
+    """rows of (src_x, src_y, w, h, dst_x, dst_y, dst_w, dst_h, u0, v0, ux, uy, vx, vy, opacity[, reserved]) -> fr_layer_warp_blit
+    array: the window of the layer, the rectangle of the image, and the inverse map in 1/65536 window pixel"""
+    return np.array([tuple(int(v) for v in r) + (0,) * (16 - len(r)) for r in rows], WARP_BLIT_DTYPE)
+
+
+def warp_from_matrix(matrix, window, opacity: int = 255) -> tuple:
+    """The fr_layer_warp_blit row (for make_warp_blits) that places the window = (src_x, src_y, w, h) of a layer through the
+    forward map `matrix` = ((a, b, tx), (c, d, ty)): the point (u, v) of the window, in pixels with pixel centres at + 1/2,
+    lands on (a u + b v + tx, c u + d v + ty) of the image, pixel centres at + 1/2 there too.  The matrix is inverted in
+    exact rationals (floats are taken at their exact value) and each coefficient of the inverse map rounded as
+    floor(65536 x + 1/2).  The blit's rectangle is the bounding box of the image of [-1/2, w + 1/2] x [-1/2, h + 1/2], every
+    point a tap can reach, grown by one pixel all round.  ValueError: a singular matrix, or a map beyond the call's ranges."""
+    (a, b, tx), (c, d, ty) = [[Fraction(v) for v in row] for row in matrix]
+    sx, sy, w, h = (int(v) for v in window)
+    det = a * d - b * c
+    if det == 0:
+        raise ValueError(f"matrix {matrix!r} is singular")
+    half = Fraction(1, 2)
+    corners = [(a * u + b * v + tx, c * u + d * v + ty) for u in (-half, w + half) for v in (-half, h + half)]
+    x0, y0 = math.floor(min(p[0] for p in corners)) - 1, math.floor(min(p[1] for p in corners)) - 1
+    x1, y1 = math.ceil(max(p[0] for p in corners)) + 1, math.ceil(max(p[1] for p in corners)) + 1
+    ia, ib, ic, id_ = d / det, -b / det, -c / det, a / det
+    q = lambda v: math.floor(65536 * v + half)
+    cx, cy = x0 + half - tx, y0 + half - ty                  # the centre of rectangle pixel (0, 0), from the map's origin
+    row = (sx, sy, w, h, x0, y0, x1 - x0, y1 - y0, q(ia * cx + ib * cy), q(ic * cx + id_ * cy), q(ia), q(ib), q(ic), q(id_), int(opacity))
+    if not (all(-2 ** 31 <= v < 2 ** 31 for v in row[4:6] + row[10:14]) and all(abs(v) <= 2 ** 47 for v in row[8:10]) and all(v <= 2 ** 26 for v in row[6:8])):
+        raise ValueError(f"matrix {matrix!r} over a window of {w} x {h}: beyond the ranges of fr_layer_warp")
+    return row
 
 
 def make_rects(rows: Sequence) -> np.ndarray:
@@ -142,6 +176,18 @@ def layer_mask(ctx: Context, src_ptr, src_stride_px: int, src_rows: int, mask_pt
     L.check(ctx._lib.fr_layer_mask(ctx._h, C.c_void_p(src_ptr or None), src_stride_px, src_rows, C.c_void_p(mask_ptr), mask_stride, mask_rows,
                                    C.c_void_p(dst_ptr), dst_stride_px, dst_rows, None if b is None else L.ptr(b), n,
                                    _flags(flags, srgb) | (L.FR_MASK_PLANE if plane else 0) | (L.FR_MASK_ERASE if erase else 0)))
+
+
+def layer_warp(ctx: Context, src_ptr: int, src_stride_px: int, src_rows: int, dst_ptr: int, dst_stride_px: int, dst_rows: int,
+               blits, srgb: bool = False, flags: int = 0) -> None:
+    """fr_layer_warp: windows of the premultiplied layer at device address src_ptr composited over the premultiplied image at
+    dst_ptr through an affine map each, scaled, turned or moved by a fraction of a pixel, sampled bilinearly in exact
+    integers (both 4 bytes per pixel, alpha last; strides and rows in pixels); asynchronous on the context's stream.
+    blits: an fr_layer_warp_blit array (make_warp_blits; warp_from_matrix makes a row from a forward matrix) or None.
+    srgb: FR_LAYER_SRGB, sample and composite in linear light."""
+    b, n = _table(blits, WARP_BLIT_DTYPE)
+    L.check(ctx._lib.fr_layer_warp(ctx._h, C.c_void_p(src_ptr), src_stride_px, src_rows, C.c_void_p(dst_ptr), dst_stride_px,
+                                   dst_rows, None if b is None else L.ptr(b), n, _flags(flags, srgb)))
 
 
 def layer_unpremultiply(ctx: Context, ptr: int, stride_px: int, w: int, h: int, srgb: bool = False) -> None:

@@ -727,8 +727,8 @@ int fr_rgba_unpremultiply(uint8_t *rgba, size_t n_pixels, int srgb);
  *     all blits of the call, behind a small kernel that brings the call's tile table into device memory; asynchronous on
  *     the context's stream, in stream order after earlier renders as fr_plan_render is; the caller may reuse `blits` as
  *     soon as the call returns.
- * FR_LAYER_SRGB is the flag space of fr_layer_over, fr_layer_shadow, fr_layer_outline, fr_layer_rects, fr_layer_paint and
- * fr_layer_lcd: no other entry point knows it, and these know none of the FR_TEXT_ / FR_FILL_ flags.  (FR_LCD_BGR = 2 is
+ * FR_LAYER_SRGB is the flag space of fr_layer_over, fr_layer_shadow, fr_layer_outline, fr_layer_rects, fr_layer_paint,
+ * fr_layer_lcd, fr_layer_mask and fr_layer_warp: no other entry point knows it, and these know none of the FR_TEXT_ / FR_FILL_ flags.  (FR_LCD_BGR = 2 is
  * fr_layer_lcd's alone: the others refuse it as an unknown bit.)                                                              */
 #define FR_LAYER_SRGB 1u
 
@@ -1153,6 +1153,73 @@ int fr_layer_mask(fr_ctx *ctx, const void *src_dev, size_t src_stride_px, size_t
                   const void *mask_dev, size_t mask_stride, size_t mask_rows,
                   void *dst_dev, size_t dst_stride_px, size_t dst_rows,
                   const fr_layer_mask_blit *blits, uint32_t n_blits, uint32_t flags);
+
+/* ---- a layer through an affine map: scaled, rotated and sub-pixel placement (BUILD-DEFINED; DESIGN.md sections 4.15 and 5) --
+ * fr_layer_warp composites a premultiplied layer over a premultiplied image through an affine map, sampled bilinearly in
+ * exact integers: a viewer that zooms, spins or smooth-scrolls finished text composites the layer per frame and does not
+ * render the plan again.  Images, m, D, E, opacity, clipping, the non-overlap rule and the aliasing rule are
+ * fr_layer_over's.  FR_LAYER_SRGB is the only known flag.
+ *   Map: the caller gives the INVERSE map, destination to window.  A blit owns the dst_w x dst_h rectangle at (dst_x, dst_y)
+ *     of the image and samples the w x h window at (src_x, src_y) of the layer.  For rectangle pixel (X, Y), 0 <= X < dst_w,
+ *     0 <= Y < dst_h, in 1/65536 window pixel:
+ *         U = u0 + X * ux + Y * uy,      V = v0 + X * vx + Y * vy
+ *     exact integers that never wrap: |u0|, |v0| <= 2^47, dst_w, dst_h <= 2^26, the four coefficients any int32.  The centre
+ *     of window pixel (i, j) is at ((i + 1/2) * 65536, (j + 1/2) * 65536).
+ *   Taps: P = U - 32768, Q = V - 32768;  i = P >> 16, j = Q >> 16 (arithmetic shifts: floors);  fx = (P & 0xffff) >> 8,
+ *     fy = (Q & 0xffff) >> 8 (0 .. 255: the fractions are truncated to 8 bits).  p(i, j) is window pixel (i, j) for
+ *     0 <= i < w and 0 <= j < h and (0, 0, 0, 0) everywhere else.  No byte of the layer outside the window is ever read,
+ *     whatever the map.
+ *   Sample (UNORM), each of the four bytes c on its own:
+ *         top = p(i, j)_c * (256 - fx) + p(i+1, j)_c * fx
+ *         bot = p(i, j+1)_c * (256 - fx) + p(i+1, j+1)_c * fx
+ *         s_c = (top * (256 - fy) + bot * fy + 32768) >> 16          (at most 255; the numerator fits 32 bits)
+ *     and the pixel s is composited exactly as fr_layer_over composites a layer pixel at opacity o.
+ *   Sample (FR_LAYER_SRGB): the alpha as above; the three colour bytes by the same formula on D[p_c], the 16-bit linear
+ *     values (65535 * 65536 + 32768 < 2^32), giving S_c; the composite is fr_layer_over's sRGB line with S_c in the place
+ *     of D[s_c]:
+ *         out_c = E(min(65535, (S_c * o + 127) div 255 + (D[d_c] * (255 - a') + 127) div 255))
+ *   Consequences:
+ *     1. ux = vy = 65536, uy = vx = 0, u0 = 32768 + 65536 a, v0 = 32768 + 65536 b and a rectangle whose pixels stay inside
+ *        the window: the bytes of fr_layer_over of that rectangle, at any o, in both spaces (fx = fy = 0, s = p).
+ *     2. The eight quarter turns and mirrors in exact coefficients (+-65536 and 0) sample fx = fy = 0 everywhere: the bytes
+ *        of fr_layer_over of the turned or mirrored layer.
+ *     3. Where the four taps are equal the sample is that pixel; s lies between the smallest and the largest tap, per byte.
+ *        A UNORM layer with s_c <= s_a everywhere gives samples with s_c <= s_a, so fr_layer_over's consequence 4 (no
+ *        clamp) carries over.
+ *     4. A shift of exactly half a pixel along one axis gives (p0 + p1 + 1) >> 1.
+ *     5. A rectangle pixel whose four taps all lie outside the window is left byte-identical; so is any pixel under o = 0.
+ *   Geometry: the rectangle is clipped to [0, dst_stride_px) x [0, dst_rows) as a blit of fr_layer_over is (X and Y keep
+ *     counting from the unclipped corner); after clipping, the rectangles of one call must not overlap.  Inside a clipped
+ *     rectangle any pixel may be read and written back unchanged; outside every clipped rectangle no byte of the image is
+ *     touched.  A zero matrix is valid: every pixel samples one point.  w = 0 or h = 0 is valid and draws nothing.
+ *   Validation, in this order.  FR_E_INVALID: NULL ctx; an unknown flag bit (FR_LCD_BGR, FR_MASK_PLANE and FR_MASK_ERASE
+ *     are unknown here); a bad src, then a bad dst (NULL, not 4-byte aligned, a pitch above 2^26).  FR_E_UNSUPPORTED: 2^31
+ *     rows or more in either image.  FR_E_INVALID: NULL blits with n_blits > 0; the two images overlapping in memory; per
+ *     blit, in order, opacity > 255, reserved != 0, |u0| or |v0| above 2^47, dst_w or dst_h above 2^26, a window that
+ *     leaves the layer (src_x + w > src_stride_px or src_y + h > src_rows).  FR_E_UNSUPPORTED: clipped rectangles that need
+ *     more than 2^22 tiles of 32 x 32 pixels (counted before the culling below, blits with o = 0 or an empty window left
+ *     out).  FR_E_INVALID: overlapping clipped rectangles.  After any refusal the image is untouched.  A call stages 96 bytes
+ *     per listed tile in pinned host memory and in device memory, both kept by the context and grown by half as much again:
+ *     0.8 MB for a 3840 x 2160 rectangle, and about 600 MB of each at the limit of 2^22 listed tiles (fr_layer_over: 200 MB);
+ *     a call that cannot have them returns FR_E_HIP or FR_E_NOMEM with the image untouched.
+ *   Execution: the host lists a 32 x 32 tile of a clipped rectangle only if the taps of some pixel of it can hit the window
+ *     (U and V are affine, so their extremes sit at the tile's corners); a call that lists none launches nothing.  One
+ *     launch of layer_warp_kernel<srgb, opacity> for all blits, behind the small kernel that brings the tile table into
+ *     device memory; every lane gathers its taps from global memory.  Asynchronous on the context's stream, in stream
+ *     order with renders and the other layer calls; the caller may reuse `blits` as soon as the call returns.            */
+typedef struct fr_layer_warp_blit {
+    uint32_t src_x, src_y, w, h;   /* the window of the layer that is sampled; must lie inside the layer        */
+    int32_t  dst_x, dst_y;         /* top-left of the destination rectangle this blit owns; may be negative     */
+    uint32_t dst_w, dst_h;         /* its size; 0 x anything is valid and does nothing                          */
+    int64_t  u0, v0;               /* window position, 1/65536 pixel, sampled by the centre of rectangle pixel (0, 0) */
+    int32_t  ux, uy, vx, vy;       /* its change per destination column (ux, vx) and row (uy, vy), 1/65536 pixel */
+    uint32_t opacity;              /* o in 0 .. 255                                                             */
+    uint32_t reserved;             /* must be 0                                                                 */
+} fr_layer_warp_blit;              /* 72 bytes */
+
+int fr_layer_warp(fr_ctx *ctx, const void *src_dev, size_t src_stride_px, size_t src_rows,
+                  void *dst_dev, size_t dst_stride_px, size_t dst_rows,
+                  const fr_layer_warp_blit *blits, uint32_t n_blits, uint32_t flags);
 
 /* ---- self-test: exhaustive device-side check of an arithmetic shortcut ----------
  * The render kernel computes t = num / d (render_glyph.zig:51,60-61; d an integer, |d| <= 2^17)
