@@ -50,6 +50,17 @@ pub const FR_LCD_TAPS = 5;
 pub const FR_MASK_PLANE: u32 = 4;
 /// fr_layer_mask alone: no layer, the destination is multiplied by 255 - t (destination-out)
 pub const FR_MASK_ERASE: u32 = 8;
+/// the modes of fr_layer_blend (fr_raster.h); FR_BLEND_MODES is their number
+pub const FR_BLEND_MULTIPLY: u32 = 0;
+pub const FR_BLEND_SCREEN: u32 = 1;
+pub const FR_BLEND_OVERLAY: u32 = 2;
+pub const FR_BLEND_DARKEN: u32 = 3;
+pub const FR_BLEND_LIGHTEN: u32 = 4;
+pub const FR_BLEND_HARD_LIGHT: u32 = 5;
+pub const FR_BLEND_DIFFERENCE: u32 = 6;
+pub const FR_BLEND_EXCLUSION: u32 = 7;
+pub const FR_BLEND_PLUS: u32 = 8;
+pub const FR_BLEND_MODES: u32 = 9;
 /// LayerPaintParams.kind and .spread (fr_raster.h: fr_layer_paint)
 pub const FR_GRADIENT_LINEAR: u32 = 0;
 pub const FR_GRADIENT_RADIAL: u32 = 1;
@@ -361,6 +372,8 @@ pub extern "c" fn fr_layer_lcd(ctx: *Ctx, cov_dev: *const anyopaque, cov_stride:
 pub extern "c" fn fr_layer_mask(ctx: *Ctx, src_dev: ?*const anyopaque, src_stride_px: usize, src_rows: usize, mask_dev: *const anyopaque, mask_stride: usize, mask_rows: usize, dst_dev: *anyopaque, dst_stride_px: usize, dst_rows: usize, blits: ?[*]const LayerMaskBlit, n_blits: u32, flags: u32) c_int;
 /// windows of a premultiplied layer over a premultiplied image through an affine map each (scaled, turned, moved by a fraction of a pixel), sampled bilinearly in exact integers
 pub extern "c" fn fr_layer_warp(ctx: *Ctx, src_dev: *const anyopaque, src_stride_px: usize, src_rows: usize, dst_dev: *anyopaque, dst_stride_px: usize, dst_rows: usize, blits: ?[*]const LayerWarpBlit, n_blits: u32, flags: u32) c_int;
+/// fr_layer_over with a separable blend mode (FR_BLEND_*) in the place of source-over, one mode per call, in exact integers with one rounding
+pub extern "c" fn fr_layer_blend(ctx: *Ctx, src_dev: *const anyopaque, src_stride_px: usize, src_rows: usize, dst_dev: *anyopaque, dst_stride_px: usize, dst_rows: usize, blits: ?[*]const LayerBlit, n_blits: u32, mode: u32, flags: u32) c_int;
 // ---- self-tests of the two arithmetic shortcuts (device-side, exhaustive)
 pub extern "c" fn fr_selftest_division(d_lo: u32, d_hi: u32, mismatches: *u64, bad_divisor: ?*u32, bad_x_bits: ?*u32) c_int;
 pub extern "c" fn fr_selftest_sqrt(mismatches: *u64, bad_x_bits: ?*u32) c_int;

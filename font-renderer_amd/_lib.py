@@ -18,6 +18,9 @@ FR_LAYER_SRGB = 1              # the flag space of the fr_layer_over / _shadow /
 FR_LCD_BGR = 2                     # fr_layer_lcd alone, beside FR_LAYER_SRGB: memory byte b takes sub-pixel 2 - b
 FR_LCD_TAPS = 5                    # the length of fr_layer_lcd's filter
 FR_MASK_PLANE, FR_MASK_ERASE = 4, 8    # fr_layer_mask alone: the mask is a plane of bytes; no layer, the destination is erased
+# fr_layer_blend's modes; FR_BLEND_MODES is their number
+(FR_BLEND_MULTIPLY, FR_BLEND_SCREEN, FR_BLEND_OVERLAY, FR_BLEND_DARKEN, FR_BLEND_LIGHTEN, FR_BLEND_HARD_LIGHT, FR_BLEND_DIFFERENCE, FR_BLEND_EXCLUSION,
+ FR_BLEND_PLUS, FR_BLEND_MODES) = range(10)
 FR_OUTLINE_GROW, FR_OUTLINE_RING, FR_OUTLINE_INNER, FR_OUTLINE_SHRINK = 0, 1, 2, 3      # fr_layer_outline_params.kind
 FR_OUTLINE_MAX_RADIUS = 256        # fr_layer_outline_params.radius, in 1/16 pixel
 FR_GRADIENT_LINEAR, FR_GRADIENT_RADIAL = 0, 1                   # fr_layer_paint_params.kind
@@ -205,6 +208,7 @@ SYMBOLS = [
     ("fr_layer_lcd", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, _P, C.c_uint32, C.POINTER(C.c_uint16), C.c_uint32]),
     ("fr_layer_mask", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, _P, C.c_uint32, C.c_uint32]),
     ("fr_layer_warp", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, _P, C.c_uint32, C.c_uint32]),
+    ("fr_layer_blend", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, _P, C.c_uint32, C.c_uint32, C.c_uint32]),
     ("fr_selftest_sqrt", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     ("fr_selftest_division", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("fr_selftest_row_cuts", C.c_int, [_P, _P, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),

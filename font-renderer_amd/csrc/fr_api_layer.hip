@@ -1,13 +1,14 @@
 // fr_api_layer.hip — C ABI (include/fr_raster.h): fr_layer_over, fr_layer_unpremultiply, fr_layer_shadow, fr_layer_outline,
-// fr_layer_rects, fr_layer_paint, fr_layer_lcd, fr_layer_mask and fr_layer_warp.  The checks, the clipping and the tile table are
-// fr_layer_plan.cpp's, the shadow's stages fr_layer_shadow_plan.cpp's, the outline's rectangles and weights
+// fr_layer_rects, fr_layer_paint, fr_layer_lcd, fr_layer_mask, fr_layer_warp and fr_layer_blend.  The checks, the clipping and the tile table are
+// fr_layer_plan.cpp's (fr_layer_blend's too, behind its mode check: fr_layer_blend_math.hpp), the shadow's stages fr_layer_shadow_plan.cpp's, the outline's rectangles and weights
 // fr_layer_outline_plan.cpp's, the rectangles' tables fr_layer_rects_plan.cpp's, the gradient's coefficients and colour
 // table fr_layer_paint_plan.cpp's, the sub-pixel blits' tiles fr_layer_lcd_plan.cpp's, the masked blits' tiles
 // fr_layer_mask_plan.cpp's, the warped blits' culled tiles fr_layer_warp_plan.cpp's; this unit stages the tables, keeps the shadow's planes and launches the kernels of
 // fr_layer.hip, fr_layer_shadow.hip, fr_layer_outline.hip, fr_layer_rects.hip, fr_layer_paint.hip, fr_layer_lcd.hip,
-// fr_layer_mask.hip and fr_layer_warp.hip.
+// fr_layer_mask.hip, fr_layer_warp.hip and fr_layer_blend.hip.
 #include "fr_internal.hpp"
 #include "fr_layer.hpp"
+#include "fr_layer_blend.hpp"
 #include "fr_layer_lcd.hpp"
 #include "fr_layer_mask.hpp"
 #include "fr_layer_outline.hpp"
@@ -356,6 +357,27 @@ int fr_layer_warp(fr_ctx *ctx, const void *src_dev, size_t src_stride_px, size_t
     if (const int rc = layer_tables_to_device(ctx, 6 * n, &tab, [&](uint4 *to) { memcpy(to, t.tiles.data(), n * sizeof(fr::WarpTile)); })) return rc;
     const fr::WarpArgs a{reinterpret_cast<const fr::WarpTile *>(tab), static_cast<const uint32_t *>(src_dev), static_cast<uint32_t *>(dst_dev), src_stride_px, dst_stride_px};
     HIP_TRY(fr::launch_layer_warp((flags & FR_LAYER_SRGB) != 0, t.opacity, (uint32_t)n, a, ctx->stream));
+    return FR_OK;
+}
+
+int fr_layer_blend(fr_ctx *ctx, const void *src_dev, size_t src_stride_px, size_t src_rows, void *dst_dev, size_t dst_stride_px,
+                   size_t dst_rows, const fr_layer_blit *blits, uint32_t n_blits, uint32_t mode, uint32_t flags)
+{
+    if (!ctx) return fail(FR_E_INVALID, "fr_layer_blend: ctx is NULL");
+    fr::LayerTables t;
+    try {
+        const fr::LayerIn in{(uintptr_t)src_dev, (uintptr_t)dst_dev, src_stride_px, src_rows, dst_stride_px, dst_rows, blits, n_blits, flags};
+        if (const int rc = fr::layer_blend_tables(in, mode, t)) return rc;
+    } catch (const std::bad_alloc &) {
+        return fail(FR_E_NOMEM, "fr_layer_blend: host allocation");
+    }
+    const size_t n = t.tiles.size();
+    if (!n) return FR_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const uint4 *tab = nullptr;
+    if (const int rc = layer_tables_to_device(ctx, 2 * n, &tab, [&](uint4 *to) { memcpy(to, t.tiles.data(), n * sizeof(fr::LayerTile)); })) return rc;
+    const fr::LayerArgs a{reinterpret_cast<const fr::LayerTile *>(tab), static_cast<const uint32_t *>(src_dev), static_cast<uint32_t *>(dst_dev), src_stride_px, dst_stride_px};
+    HIP_TRY(fr::launch_layer_blend((flags & FR_LAYER_SRGB) != 0, mode, t.opacity, (uint32_t)n, a, ctx->stream));
     return FR_OK;
 }
 

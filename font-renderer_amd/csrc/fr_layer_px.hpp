@@ -2,8 +2,10 @@
 // (fr_layer.hip), layer_rects_kernel (fr_layer_rects.hip), layer_paint_kernel (fr_layer_paint.hip) and layer_mask_kernel
 // (fr_layer_mask.hip) with its erase, layer_warp_kernel (fr_layer_warp.hip) with its linear-light sibling, and its variant with one alpha per colour byte for layer_lcd_kernel
 // (fr_layer_lcd.hip).  The arithmetic is that of the text plans' colour body (fr_text_colour.hpp), per pixel instead of per
-// sample.
+// sample.  blend_px, the pixel of layer_blend_kernel (fr_layer_blend.hip), takes its colour bytes through blend_channel
+// (fr_layer_blend_math.hpp), which the host compiles too.
 #pragma once
+#include "fr_layer_blend_math.hpp"
 #include "fr_text_colour.hpp"
 
 namespace fr {
@@ -49,6 +51,47 @@ __device__ __forceinline__ uint32_t over_px(uint32_t s, uint32_t d, uint32_t o, 
             out = (out >> 8) | (srgb_encode(K, L) << 24);
         }
         return (out >> 8) | (r1a & 0x00ff0000u) << 8;          // alpha is stored linearly
+    }
+}
+
+// The definition of fr_layer_blend for one pixel: s blended into d in mode MODE at opacity o.  s == 0 gives d in every mode
+// (consequence 2: x = p = 0 leaves N = y Q, and E(D[v]) = v); unlike over_px it needs d whatever the layer's alpha is.
+template <int SRGB, uint32_t MODE, int OPACITY>
+__device__ __forceinline__ uint32_t blend_px(uint32_t s, uint32_t d, uint32_t o, const uint16_t *D, const uint16_t *K)
+{
+    constexpr bool PLUS = MODE == FR_BLEND_PLUS;
+    uint32_t s1a = (s >> 8) & M2;                              // channel 1 and alpha
+    if (OPACITY) s1a = m2(s1a, o);
+    const uint32_t a1 = s1a >> 16, da = d >> 24;
+    const uint32_t out_a = PLUS ? min(255u, a1 + da) : a1 + m2(da, 255u - a1);     // a' + m(d_a, 255 - a') <= 255
+    if constexpr (!SRGB) {
+        uint32_t s02 = s & M2;
+        if (OPACITY) s02 = m2(s02, o);
+        const uint32_t x[3] = {s02 & 0xffu, s1a & 0xffu, s02 >> 16};
+        uint32_t out = out_a << 24;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const uint32_t y = (d >> (8 * c)) & 0xffu;
+            uint32_t v;
+            if constexpr (PLUS) v = min(255u, x[c] + y);
+            else v = blend_channel<MODE, 255u>(x[c], y, a1, da);
+            out |= v << (8 * c);
+        }
+        return out;
+    } else {
+        [[maybe_unused]] const uint32_t p = 257u * a1, q = 257u * da;
+        uint32_t out = 0u;                                     // a shift register: a channel enters at the top byte
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            uint32_t X = D[(s >> (8 * c)) & 0xffu];
+            if (OPACITY) X = div255_24(X * o + 127u);
+            const uint32_t Y = D[(d >> (8 * c)) & 0xffu];
+            uint32_t L;
+            if constexpr (PLUS) L = min(65535u, X + Y);
+            else L = blend_channel<MODE, 65535u>(X, Y, p, q);
+            out = (out >> 8) | (srgb_encode(K, L) << 24);
+        }
+        return (out >> 8) | out_a << 24;                       // alpha is stored linearly
     }
 }
 

@@ -296,6 +296,15 @@ inline void layer_warp(Context &ctx, const DeviceImage &layer, const DeviceImage
     check(fr_layer_warp(ctx.get(), layer.pixels, layer.stride_px, layer.rows, image.pixels, image.stride_px, image.rows, blits.data(), (uint32_t)blits.size(),
                         srgb ? FR_LAYER_SRGB : 0u));
 }
+// fr_layer_blend: layer_over with a blend mode in the place of source-over (mode: FR_BLEND_MULTIPLY, _SCREEN, _OVERLAY,
+// _DARKEN, _LIGHTEN, _HARD_LIGHT, _DIFFERENCE, _EXCLUSION or _PLUS): a highlighter stroke multiplied over text, a glow
+// screened or added, text differenced into a photo.  One mode per call.  Asynchronous on the context's stream; `blits`
+// may be reused at once.
+inline void layer_blend(Context &ctx, const DeviceImage &layer, const DeviceImage &image, const std::vector<fr_layer_blit> &blits, uint32_t mode, bool srgb = false)
+{
+    check(fr_layer_blend(ctx.get(), layer.pixels, layer.stride_px, layer.rows, image.pixels, image.stride_px, image.rows, blits.data(), (uint32_t)blits.size(),
+                         mode, srgb ? FR_LAYER_SRGB : 0u));
+}
 
 class PlacedText {
 public:

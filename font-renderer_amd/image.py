@@ -10,7 +10,7 @@ import numpy as np
 from . import _lib as L
 from .device import default_context, round_trip
 from .glyph import GlyphSet
-from .layer import (layer_lcd, layer_mask, layer_outline, layer_over, layer_paint, layer_rects, layer_shadow, layer_unpremultiply, layer_warp, make_blits, make_lcd_blits,
+from .layer import (layer_blend, layer_lcd, layer_mask, layer_outline, layer_over, layer_paint, layer_rects, layer_shadow, layer_unpremultiply, layer_warp, make_blits, make_lcd_blits,
                     make_mask_blits, make_rects, make_warp_blits, warp_from_matrix)
 
 
@@ -153,6 +153,24 @@ class RGBA:                     # an RGBA text plan's image (fr_text_plan_create
         blits = make_blits([(0, 0, layer.width, layer.height, int(x), int(y), int(opacity))])
         self.data[:] = round_trip(ctx, lambda d, s: layer_over(ctx, s, layer.width, layer.height, d, self.width, self.height,
                                                                blits, srgb), dst, src)
+        return self
+
+    def blend(self, layer: "RGBA", mode: int, x: int = 0, y: int = 0, opacity: int = 255, srgb: bool = False, ctx=None) -> "RGBA":
+        """fr_layer_blend, in place: the premultiplied `layer` blended into this premultiplied image in `mode` (FR_BLEND_MULTIPLY,
+        _SCREEN, _OVERLAY, _DARKEN, _LIGHTEN, _HARD_LIGHT, _DIFFERENCE, _EXCLUSION or _PLUS) with its top-left pixel at
+        (x, y), whole pixels, clipped at the image's edges, at `opacity` in 0 .. 255.  srgb: both images are premultiplied in
+        linear light.  Both images are uploaded, blended on the device and this one copied back, as over does.  Returns self."""
+        dst, src = rgba_pixels(self, "RGBA.blend: image"), rgba_pixels(layer, "RGBA.blend: layer")
+        if not 0 <= int(opacity) <= 255:
+            raise ValueError(f"opacity {opacity!r}: expected 0 .. 255")
+        if not 0 <= int(mode) < L.FR_BLEND_MODES:
+            raise ValueError(f"mode {mode!r}: expected 0 .. {L.FR_BLEND_MODES - 1}")
+        if self.width == 0 or self.height == 0 or layer.width == 0 or layer.height == 0:
+            return self
+        ctx = ctx or default_context()
+        blits = make_blits([(0, 0, layer.width, layer.height, int(x), int(y), int(opacity))])
+        self.data[:] = round_trip(ctx, lambda d, s: layer_blend(ctx, s, layer.width, layer.height, d, self.width, self.height,
+                                                                blits, int(mode), srgb), dst, src)
         return self
 
     def over_warped(self, layer: "RGBA", matrix, opacity: int = 255, srgb: bool = False, ctx=None) -> "RGBA":

@@ -1,5 +1,5 @@
 """The layer calls of the C ABI (fr_layer_*, include/fr_raster.h) on device addresses, and the builders of their tables.
-All of them are asynchronous on the context's stream; RGBA.over / over_warped / over_masked / erase / fill_rects / paint / draw_lcd / shadow / outline / unpremultiply
+All of them are asynchronous on the context's stream; RGBA.over / blend / over_warped / over_masked / erase / fill_rects / paint / draw_lcd / shadow / outline / unpremultiply
 (image.py) wrap them for host images."""
 from __future__ import annotations
 
@@ -188,6 +188,18 @@ def layer_warp(ctx: Context, src_ptr: int, src_stride_px: int, src_rows: int, ds
     b, n = _table(blits, WARP_BLIT_DTYPE)
     L.check(ctx._lib.fr_layer_warp(ctx._h, C.c_void_p(src_ptr), src_stride_px, src_rows, C.c_void_p(dst_ptr), dst_stride_px,
                                    dst_rows, None if b is None else L.ptr(b), n, _flags(flags, srgb)))
+
+
+def layer_blend(ctx: Context, src_ptr: int, src_stride_px: int, src_rows: int, dst_ptr: int, dst_stride_px: int, dst_rows: int,
+                blits, mode: int, srgb: bool = False, flags: int = 0) -> None:
+    """fr_layer_blend: fr_layer_over with a blend mode in the place of source-over.  Rectangles of the premultiplied layer at
+    device address src_ptr blended into the premultiplied image at dst_ptr (both 4 bytes per pixel, alpha last; strides and
+    rows in pixels) in `mode`, one of FR_BLEND_MULTIPLY, _SCREEN, _OVERLAY, _DARKEN, _LIGHTEN, _HARD_LIGHT, _DIFFERENCE,
+    _EXCLUSION and _PLUS; asynchronous on the context's stream.  blits: an fr_layer_blit array (make_blits) or None.  srgb:
+    FR_LAYER_SRGB, blend in linear light."""
+    b, n = _table(blits, BLIT_DTYPE)
+    L.check(ctx._lib.fr_layer_blend(ctx._h, C.c_void_p(src_ptr), src_stride_px, src_rows, C.c_void_p(dst_ptr), dst_stride_px,
+                                    dst_rows, None if b is None else L.ptr(b), n, mode, _flags(flags, srgb)))
 
 
 def layer_unpremultiply(ctx: Context, ptr: int, stride_px: int, w: int, h: int, srgb: bool = False) -> None:

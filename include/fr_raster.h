@@ -728,7 +728,7 @@ int fr_rgba_unpremultiply(uint8_t *rgba, size_t n_pixels, int srgb);
  *     the context's stream, in stream order after earlier renders as fr_plan_render is; the caller may reuse `blits` as
  *     soon as the call returns.
  * FR_LAYER_SRGB is the flag space of fr_layer_over, fr_layer_shadow, fr_layer_outline, fr_layer_rects, fr_layer_paint,
- * fr_layer_lcd, fr_layer_mask and fr_layer_warp: no other entry point knows it, and these know none of the FR_TEXT_ / FR_FILL_ flags.  (FR_LCD_BGR = 2 is
+ * fr_layer_lcd, fr_layer_mask, fr_layer_warp and fr_layer_blend: no other entry point knows it, and these know none of the FR_TEXT_ / FR_FILL_ flags.  (FR_LCD_BGR = 2 is
  * fr_layer_lcd's alone: the others refuse it as an unknown bit.)                                                              */
 #define FR_LAYER_SRGB 1u
 
@@ -1220,6 +1220,65 @@ typedef struct fr_layer_warp_blit {
 int fr_layer_warp(fr_ctx *ctx, const void *src_dev, size_t src_stride_px, size_t src_rows,
                   void *dst_dev, size_t dst_stride_px, size_t dst_rows,
                   const fr_layer_warp_blit *blits, uint32_t n_blits, uint32_t flags);
+
+/* ---- blend modes: multiply, screen, overlay and the like (BUILD-DEFINED; DESIGN.md sections 4.16 and 5) --------------------
+ * fr_layer_blend is fr_layer_over with a separable blend mode in the place of source-over: a highlighter stroke over text
+ * (multiply), a glow (screen, plus), text that stays legible over light and dark (difference), a texture through a caption
+ * (overlay).  The images (both premultiplied, alpha last), the blits with their geometry and clipping, the no-overlap
+ * rules, the limits, the stream order and the promise that no byte outside a clipped rectangle is read or written are
+ * fr_layer_over's, word for word; m, D and E as defined there.  One mode per call.  All integers.
+ *   Definition: the W3C compositing formula co = cs (1 - ab) + cb (1 - as) + as ab B(Cb, Cs) on premultiplied values, with
+ *   one rounding.  For a layer pixel (s_c, s_a), the destination pixel (d_c, d_a) under it, the blit's opacity o and
+ *   a' = m(s_a, o), per colour byte c:
+ *       flags = 0:      Q = 255,    x = m(s_c, o),                   p = a',      y = d_c,     q = d_a
+ *       FR_LAYER_SRGB:  Q = 65535,  x = (D[s_c] * o + 127) div 255,  p = 257 a',  y = D[d_c],  q = 257 d_a
+ *   and with (v)+ = max(0, v):
+ *       N     = x (Q - q) + y (Q - p) + B2
+ *       out   = min(Q, (N + (Q - 1) / 2) div Q)        stored as out_c = out (flags = 0) or E(out) (FR_LAYER_SRGB)
+ *       out_a = a' + m(d_a, 255 - a')                  (fr_layer_over's alpha, in both spaces)
+ *       B2:  FR_BLEND_MULTIPLY    x y
+ *            FR_BLEND_SCREEN      (x q + y p - x y)+
+ *            FR_BLEND_DARKEN      min(x q, y p)                 FR_BLEND_LIGHTEN    max(x q, y p)
+ *            FR_BLEND_DIFFERENCE  |x q - y p|                   FR_BLEND_EXCLUSION  (x q + y p - 2 x y)+
+ *            FR_BLEND_HARD_LIGHT  2 x <= p ?  2 x y  :  (p q - 2 (q - y)+ (p - x)+)+
+ *            FR_BLEND_OVERLAY     2 y <= q ?  2 x y  :  (p q - 2 (q - y)+ (p - x)+)+
+ *       FR_BLEND_PLUS (no N):  out = min(Q, x + y), stored likewise;  out_a = min(255, a' + d_a)
+ *   Q is odd, so no ties occur.  The (.)+ and the final min make every byte combination defined, valid premultiplied or not.
+ *   Consequences:
+ *     1. For valid premultiplied inputs (x <= p, y <= q), N <= Q^2 and out is the integer nearest to the exact rational
+ *        value of the W3C formula: the error is below 1/2 and never a tie.
+ *     2. A layer pixel (0, 0, 0, 0), or o = 0, leaves the destination pixel byte-identical in every mode and both spaces.
+ *     3. Over a destination pixel (0, 0, 0, 0) every mode gives fr_layer_over's bytes, for any layer bytes.
+ *     4. MULTIPLY, SCREEN, DARKEN, LIGHTEN, DIFFERENCE, EXCLUSION and PLUS are symmetric in (layer, destination) at
+ *        o = 255, for any bytes.
+ *     5. HARD_LIGHT is OVERLAY with layer and destination swapped (at o = 255), for any bytes.
+ *     6. For any bytes N never exceeds 3 Q^2 (MULTIPLY reaches it at x = y = Q, p = q = 0), which is above 2^32 in linear
+ *        light: the kernel sums its 32-bit products in 64 bits.
+ *   Not offered: colour-dodge, colour-burn and soft-light (a division or a square root per colour byte), the four
+ *     non-separable modes (hue, saturation, colour, luminosity), a mode per blit, and blending through a mask or a warp:
+ *     composite those into a cleared layer first (fr_layer_mask, fr_layer_warp) and blend that layer.
+ *   Validation, in this order.  FR_E_INVALID: NULL ctx; an unknown flag bit (FR_LCD_BGR, FR_MASK_PLANE and FR_MASK_ERASE
+ *     are unknown here); mode >= FR_BLEND_MODES; then everything fr_layer_over checks, in its order and with its codes.
+ *     n_blits = 0 is valid and launches nothing.  After any refusal the image is untouched.
+ *   Execution: one launch of layer_blend_kernel<srgb, mode, opacity> (opacity = 0 when every blit that draws has o = 255)
+ *     over fr_layer_over's tiles of 256 x 16 pixels, behind the small kernel that brings the tile table into device memory.  A
+ *     group of four layer pixels that are all zero is neither loaded from the image nor stored; every other pixel of a
+ *     clipped rectangle needs its destination, opaque or not.  Asynchronous on the context's stream, in stream order with
+ *     renders and the other layer calls; the caller may reuse `blits` as soon as the call returns.                        */
+#define FR_BLEND_MULTIPLY   0u
+#define FR_BLEND_SCREEN     1u
+#define FR_BLEND_OVERLAY    2u
+#define FR_BLEND_DARKEN     3u
+#define FR_BLEND_LIGHTEN    4u
+#define FR_BLEND_HARD_LIGHT 5u
+#define FR_BLEND_DIFFERENCE 6u
+#define FR_BLEND_EXCLUSION  7u
+#define FR_BLEND_PLUS       8u
+#define FR_BLEND_MODES      9u   /* the number of modes: mode >= FR_BLEND_MODES is FR_E_INVALID */
+
+int fr_layer_blend(fr_ctx *ctx, const void *src_dev, size_t src_stride_px, size_t src_rows,
+                   void *dst_dev, size_t dst_stride_px, size_t dst_rows,
+                   const fr_layer_blit *blits, uint32_t n_blits, uint32_t mode, uint32_t flags);   /* 0 or FR_LAYER_SRGB */
 
 /* ---- self-test: exhaustive device-side check of an arithmetic shortcut ----------
  * The render kernel computes t = num / d (render_glyph.zig:51,60-61; d an integer, |d| <= 2^17)
